@@ -18,7 +18,9 @@ observations) are sharded by landmark block, cameras are replicated and the redu
 camera system is all-reduced with RCCL inside the library (torch.distributed is used
 only to ship the 128-byte RCCL id, for the barriers and for the max over ranks).
 
-One JSON line is printed by rank 0 (fields: see DESIGN.md "Measurement").
+One JSON line is printed by rank 0 (fields: see DESIGN.md "Measurement"); ``ms_per_step`` is the median repeat over K.
+``--dump-outputs DIR`` also writes what the last timed solve returned (cameras, points, summary scalars) as float64
+``DIR/<name>.npy``, so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -156,6 +158,35 @@ def cpu_baseline_bal(bal, budget_s=15.0):
                        f"{tg:.1f} s); LSMR not timed; host has {os.cpu_count()} cores")
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SUMMARY_FIELDS = ("iterations", "accepted", "pcg_iterations", "status", "initial_sse", "final_sse", "initial_cost",
+                       "final_cost", "final_lambda")
+
+
+def dump_outputs(out_dir, solver, summary, intr, p_begin, n_pts_total, rank, world):
+    """--dump-outputs DIR: what the last timed solve handed its caller, as float64 .npy files -- cams (Nc, 6), or (Nc, 9)
+    with the adjusted (f, k1, k2) of the BAL camera; pts (Np, 3) of the whole problem (gathered from every rank); and the
+    summary's scalars except its timings.  Above 64 MB in all, pts is a fixed seeded sample of rows, whose indices go to
+    pts_rows.npy.  Called on every rank (the point gather is collective); rank 0 writes."""
+    cams, pts = solver.get_params()
+    if world > 1:
+        pts = solver.allgather_points(p_begin, n_pts_total)
+    if rank != 0:
+        return
+    if intr is not None:
+        cams = np.concatenate([cams, intr], axis=1)
+    arrays = {"cams": cams, "pts": pts}
+    arrays.update({k: np.float64(summary[k]) for k in DUMP_SUMMARY_FIELDS})
+    room = DUMP_LIMIT_BYTES - sum(a.nbytes for k, a in arrays.items() if k != "pts") - 4096
+    if pts.nbytes > room:
+        n_rows = room // (pts.itemsize * 4)                       # 3 coordinates + the row index per sampled point
+        rows = np.sort(np.random.default_rng(0).choice(pts.shape[0], n_rows, replace=False))
+        arrays["pts"], arrays["pts_rows"] = pts[rows], rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 class _stdout_to_stderr:
     """RCCL prints a version banner on file descriptor 1 when a communicator comes up; stdout must carry exactly one JSON
     line, so the descriptor points at stderr while the transport is being set up."""
@@ -232,6 +263,8 @@ def main():
     ap.add_argument("--jacobian", default="f64", choices=["f64", "f32"], help="f32: config 5's fp32 Jacobian blocks in the PCG passes")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--repeats", type=int, default=11, help="timed repeats of the K-step solve; value = the median repeat")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed repeats, write what the last one returned (cams, pts, summary scalars) as DIR/<name>.npy")
     ap.add_argument("--weak", action="store_true",
                     help="also time the problem that GROWS with the ranks (every rank a C3-sized landmark shard) and report it "
                          "under 'weak_scaling'; on by default for --gpus > 1 with the headline config")
@@ -242,6 +275,8 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started without a launcher: this process starts the N ranks itself (before it has touched the GPU in any way),
         # relays rank 0's JSON line and exits with the launcher's code -- it never times ONE GPU under the name of N
@@ -272,8 +307,10 @@ def main():
         prob = make_bal_like(seed=args.seed) if args.config == "C5" else make_config(args.config, seed=args.seed)
     n_obs_total = prob.n_obs
     shard = prob
+    p_begin = 0
     if world > 1:
         b, e = shard_by_landmark(prob, world)[rank]
+        p_begin = b
         shard, _ = extract_shard(prob, b, e)
 
     ndev = hip_backend.device_count()
@@ -350,9 +387,12 @@ def main():
     # (the automatic default needs a loose outer tolerance, ftol >= 1e-6; the bench runs with ftol = 0: off)
     model_tol_eff = args.pcg_model_tol if args.pcg_model_tol >= 0 else 0.0
 
+    intr_last = [None]
+
     def run_solve(**k):
         if intr0 is not None:
-            return solver.solve_bal_resident(intr0.copy(), **k)      # (the copy: ba_solve_bal adjusts the intrinsics in place)
+            intr_last[0] = intr0.copy()                # (the copy: ba_solve_bal adjusts the intrinsics in place)
+            return solver.solve_bal_resident(intr_last[0], **k)
         return solver.solve(**k)
 
     def barrier():
@@ -383,6 +423,10 @@ def main():
         dts.append(dt_rep)
     dt = float(np.median(dts))
     steps_done = out["iterations"]
+    if steps_done != args.steps:
+        raise SystemExit(f"the timed solve stopped after {steps_done} of {args.steps} LM iterations (status {out['status_name']})")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solver, out, intr_last[0], p_begin, prob.n_pts, rank, world)
     rmse = float(np.sqrt(out["final_sse"] / n_obs_total))
 
     # per-kernel durations with HIP events on the solver's stream: same workload again

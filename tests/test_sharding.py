@@ -116,7 +116,10 @@ def _rank_main(rank, world, port, q):
 
 
 def test_two_rank_gloo_allreduce_of_reduced_camera_system():
-    import torch.multiprocessing as mp
+    # stdlib, not torch.multiprocessing: torch is imported in the spawned ranks only.  In this process libba_hip.so may already
+    # have loaded the ROCm HIP runtime, and importing torch next to it maps torch's own copy as well (two runtimes, which abort
+    # at interpreter exit).
+    import multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
@@ -188,7 +191,7 @@ def test_two_rank_spmd_run_matches_single_rank_host_logic():
     the oracle-backed doubles of tests/fake_solver.py)."""
     import io
     from contextlib import redirect_stdout
-    import torch.multiprocessing as mp
+    import multiprocessing as mp          # (stdlib: torch stays out of this process, see above)
     from bundle_adjustment_amd import bundle_adjuster as ba_mod
     from bundle_adjustment_amd.synthetic import problem_to_map
     from tests.fake_solver import OracleSolver
