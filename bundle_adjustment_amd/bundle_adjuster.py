@@ -46,6 +46,7 @@ class BundleAdjuster:
         self.camera_matrix = camera_matrix
         self.window_size = window_size
         self.device_id = device_id
+        hip_backend.loss_code(loss)            # an unknown loss name fails here, not at the first run()
         self.solver_options = dict(loss=loss, f_scale=f_scale, ftol=ftol, xtol=xtol, gtol=gtol, max_iters=max_iters,
                                    pcg_tol=pcg_tol, pcg_max_iters=pcg_max_iters, pcg_model_tol=pcg_model_tol, preconditioner=preconditioner,
                                    jacobian_precision={'f64': 0, 'f32': 1}[jacobian], verbose=verbose)

@@ -145,6 +145,35 @@ __device__ inline void huber(const double f, const double C, double& term, doubl
   else        { term = 2.0 * C * a - C * C; w = C / a; }
 }
 
+// loss codes: enum ba_loss of ba_hip.h (checked there)
+enum : int { LOSS_LINEAR = 0, LOSS_HUBER = 1, LOSS_SOFT_L1 = 2, LOSS_CAUCHY = 3, LOSS_ARCTAN = 4 };
+
+// rho(z) of the smooth losses, out of line: inlined, log1p / atan raise the register allocation of every kernel that
+// accumulates a cost -- Huber's instantiations included, since the loss is a run-time value
+__device__ __noinline__ double smooth_rho(const int loss, const double z) {
+  if (loss == LOSS_SOFT_L1) return 2.0 * z / (sqrt(1.0 + z) + 1.0);
+  if (loss == LOSS_CAUCHY) return log1p(z);
+  return atan(z);
+}
+
+// Any non-linear loss (scipy least_squares.py IMPLEMENTED_LOSSES), z = (f/C)^2: rho-term C^2 rho(z) and IRLS weight
+// rho'(z).  Huber is huber() above, bit for bit.  The loss is a launch-uniform value: the branch is scalar.
+//   soft_l1  rho = 2 (sqrt(1+z) - 1)  rho' = 1 / sqrt(1+z)
+//   cauchy   rho = log(1+z)           rho' = 1 / (1+z)
+//   arctan   rho = atan(z)            rho' = 1 / (1+z^2)
+// COST = false: the weight alone (no log / atan; soft_l1's weight is its one sqrt), term is not formed.
+// The terms are written without cancellation -- 2 z / (sqrt(1+z) + 1) and log1p(z) -- because ftol compares small
+// differences of the cost near the solution.
+template <bool COST>
+__device__ inline void robust_loss(const int loss, const double f, const double C, double& term, double& w) {
+  if (loss == LOSS_HUBER) { huber(f, C, term, w); return; }
+  const double u = f / C, z = u * u;
+  if (loss == LOSS_SOFT_L1) w = 1.0 / sqrt(1.0 + z);
+  else if (loss == LOSS_CAUCHY) w = 1.0 / (1.0 + z);
+  else w = 1.0 / (1.0 + z * z);
+  term = COST ? C * C * smooth_rho(loss, z) : 0.0;
+}
+
 // ---- small dense algebra -----------------------------------------------------------
 __device__ inline void sym3_inverse(const double* __restrict__ h, double* __restrict__ inv) {
   // h, inv packed upper: 00 01 02 11 12 22

@@ -50,6 +50,9 @@ static int fail(int code, const char* fmt, ...) {
   g_err = buf;
   return code;
 }
+static bool loss_valid(int32_t loss) { return loss >= BA_LOSS_LINEAR && loss <= BA_LOSS_ARCTAN; }
+static_assert(LOSS_LINEAR == BA_LOSS_LINEAR && LOSS_HUBER == BA_LOSS_HUBER && LOSS_SOFT_L1 == BA_LOSS_SOFT_L1 &&
+              LOSS_CAUCHY == BA_LOSS_CAUCHY && LOSS_ARCTAN == BA_LOSS_ARCTAN, "device loss codes (ba_device.hpp)");
 #define HIPCHECK(expr)                                                                      \
   do {                                                                                      \
     hipError_t e_ = (expr);                                                                 \
@@ -158,7 +161,7 @@ struct ba_handle {
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;   // second stream: test hook ba_debug_occupy only
   bool have_problem = false, have_params = false, linearized = false;
-  int lin_robust = 0;
+  ba_loss lin_loss = BA_LOSS_LINEAR;   // loss and f_scale of the last linearisation (ba_schur_apply, ba_time_kernel)
   double lin_fscale = 1.0;
   int Nc = 0, Np = 0, Nobs = 0, fixed = -1;
   double K4[4] = {1, 1, 0, 0};
@@ -1652,17 +1655,18 @@ extern "C" int ba_get_rotations(ba_handle* h, double* R) {
     else CALL_T(Pinhole);                        \
   } while (0)
 
-static void launch_residual(ba_handle* h, int which, bool robust, double fscale, double* r_out) {
+static void launch_residual(ba_handle* h, int which, ba_loss loss, double fscale, double* r_out) {
   Scope sc(h, BA_K_RESIDUAL);
+  const bool robust = loss != BA_LOSS_LINEAR;
   if (h->model) {
     auto kern = robust ? k_cam_residual_bal<true> : k_cam_residual_bal<false>;
     BA_LAUNCH(kern, dim3(cam_grid(h)), dim3(64 * WPB), 0, h->stream, h->cs[which].p, (const double*)h->intr[which].p, h->ptab[which].p,
-              h->offk.p, h->c_pt.p, uv_arr(h, h->c_uv), h->c_orig.p, fscale, h->Nc, h->cam_band, r_out, h->partR.p);
+              h->offk.p, h->c_pt.p, uv_arr(h, h->c_uv), h->c_orig.p, fscale, (int)loss, h->Nc, h->cam_band, r_out, h->partR.p);
     return;
   }
   auto kern = robust ? k_cam_residual<true> : k_cam_residual<false>;
   BA_LAUNCH(kern, dim3(cam_grid(h)), dim3(64 * WPB), 0, h->stream, h->cs[which].p, h->ptab[which].p, h->offk.p,
-                     h->c_pt.p, uv_arr(h, h->c_uv), h->c_orig.p, h->K4[0], h->K4[1], h->K4[2], h->K4[3], fscale, h->Nc, h->cam_band, r_out,
+                     h->c_pt.p, uv_arr(h, h->c_uv), h->c_orig.p, h->K4[0], h->K4[1], h->K4[2], h->K4[3], fscale, (int)loss, h->Nc, h->cam_band, r_out,
                      h->partR.p);
 }
 // fold the partial arrays of a step into `scal` (residual always; point / camera parts optional)
@@ -1720,16 +1724,17 @@ static int wait_flag(ba_handle* h, int idx, long long target) {
 // camera half of the linearisation at parameter set `which`, into buffer set `buf`
 // cost: also the cost partials at that parameter set (partR) -- the pass then doubles as the trial-cost evaluation
 template <class CM>
-static void launch_lin_cam_t(ba_handle* h, int which, int buf, bool robust, double fscale, bool cost) {
+static void launch_lin_cam_t(ba_handle* h, int which, int buf, ba_loss loss, double fscale, bool cost) {
+  const bool robust = loss != BA_LOSS_LINEAR;
   auto kern = robust ? (cost ? k_camrow_linearize<CM, true, true> : k_camrow_linearize<CM, true, false>)
                      : (cost ? k_camrow_linearize<CM, false, true> : k_camrow_linearize<CM, false, false>);
   BA_LAUNCH(kern, dim3(row_grid(h)), dim3(ROW_LANES * ROWS), 0, h->stream, h->cs[which].p, (const double*)h->intr[which].p,
-                     h->ptab[which].p, h->offk.p, h->c_pt.p, uv_arr(h, h->c_uv), h->K4[0], h->K4[1], h->K4[2], h->K4[3], fscale, h->Nc,
-                     h->cam_band, h->c_w[buf].p, h->c_ptf[buf].p, h->partL[buf].p, h->partR.p);
+                     h->ptab[which].p, h->offk.p, h->c_pt.p, uv_arr(h, h->c_uv), h->K4[0], h->K4[1], h->K4[2], h->K4[3], fscale, (int)loss,
+                     h->Nc, h->cam_band, h->c_w[buf].p, h->c_ptf[buf].p, h->partL[buf].p, h->partR.p);
 }
-static void launch_lin_cam(ba_handle* h, int which, int buf, bool robust, double fscale, bool cost = false) {
+static void launch_lin_cam(ba_handle* h, int which, int buf, ba_loss loss, double fscale, bool cost = false) {
   Scope sc(h, BA_K_LINEARIZE_CAM);
-#define CALL_T(CM) launch_lin_cam_t<CM>(h, which, buf, robust, fscale, cost)
+#define CALL_T(CM) launch_lin_cam_t<CM>(h, which, buf, loss, fscale, cost)
   BA_BY_MODEL(CALL_T);
 #undef CALL_T
 }
@@ -1747,11 +1752,12 @@ static PtWork pt_work_long(ba_handle* h) { return PtWork{h->long_pts.p, h->n_lon
 // point half at parameter set `w` into point-buffer set `pbuf`, with the damped inverse / y0 at `lambda` fused in
 // (lam_dev != null: the damping is read from that device word instead -- a speculated pass, see ba_solve)
 template <class CM>
-static void launch_lin_pt_t(ba_handle* h, int w, int pbuf, bool robust, double fscale, double lambda, const double* lam_dev,
+static void launch_lin_pt_t(ba_handle* h, int w, int pbuf, ba_loss loss, double fscale, double lambda, const double* lam_dev,
                             const ScalarsArgs& sa) {
+  const bool robust = loss != BA_LOSS_LINEAR;
   const int ride = sa.on * NPART;                      // the step's scalar fold + verdict as workgroup 0 of this launch (+ NPART - 1 idle ones)
 #define LP_HEAD h->camA[w].p, h->ptab[w].p, h->pt_off.p, h->p_cam.p, uv_arr(h, h->p_uv), h->blk_win.p
-#define LP_TAIL h->K4[0], h->K4[1], h->K4[2], h->K4[3], fscale, lambda, lam_dev, h->Hpp[pbuf].p, h->bp[pbuf].p, h->p_w[pbuf].p,      \
+#define LP_TAIL h->K4[0], h->K4[1], h->K4[2], h->K4[3], fscale, (int)loss, lambda, lam_dev, h->Hpp[pbuf].p, h->bp[pbuf].p, h->p_w[pbuf].p,      \
                 h->p_camf[pbuf].p, h->Hppinv[pbuf].p, h->y0[pbuf].p, h->partG[pbuf].p, sa
 #define LP_LAUNCH(R, L, LN, G, WK) BA_LAUNCH((k_pt_linearize<CM, R, L, LN>), dim3((G) + ride), dim3(PT_THREADS), lds_of(h), h->stream, LP_HEAD, WK, LP_TAIL)
 #define LP_BOTH(R, L) BA_LAUNCH((k_pt_linearize_both<CM, R, L>), dim3(h->nblkP + h->nblkL + ride), dim3(PT_THREADS), lds_of(h), h->stream, \
@@ -1779,14 +1785,14 @@ static void launch_lin_pt_t(ba_handle* h, int w, int pbuf, bool robust, double f
 #undef LP_HEAD
 #undef LP_TAIL
 }
-static void launch_lin_pt(ba_handle* h, int w, int pbuf, bool robust, double fscale, double lambda, const double* lam_dev = nullptr,
+static void launch_lin_pt(ba_handle* h, int w, int pbuf, ba_loss loss, double fscale, double lambda, const double* lam_dev = nullptr,
                           const ScalarsArgs* rider = nullptr) {
   if (h->Np == 0) return;
   Scope sc(h, BA_K_LINEARIZE_PT);
   ScalarsArgs sa;
   if (rider) sa = *rider;
   else { memset(&sa, 0, sizeof sa); }
-#define CALL_T(CM) launch_lin_pt_t<CM>(h, w, pbuf, robust, fscale, lambda, lam_dev, sa)
+#define CALL_T(CM) launch_lin_pt_t<CM>(h, w, pbuf, loss, fscale, lambda, lam_dev, sa)
   BA_BY_MODEL(CALL_T);
 #undef CALL_T
 }
@@ -1980,7 +1986,7 @@ static void launch_pcg_setup(ba_handle* h, double lambda, int precond, bool fina
 extern "C" int ba_residuals(ba_handle* h, int32_t loss, double f_scale, double* r, double* sse, double* cost) {
   if (!h) return fail(BA_ERR_INVALID, "null handle");
   if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
-  if (loss != BA_LOSS_LINEAR && loss != BA_LOSS_HUBER) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
+  if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
   if (!(f_scale > 0)) return fail(BA_ERR_INVALID, "f_scale must be positive");
   if (set_device(h)) return BA_ERR_HIP;
   double* rdev = nullptr;
@@ -1988,7 +1994,7 @@ extern "C" int ba_residuals(ba_handle* h, int32_t loss, double f_scale, double* 
     HIPCHECK(h->rbuf.alloc(2 * (size_t)h->Nobs));
     rdev = h->rbuf.p;
   }
-  launch_residual(h, h->cur, loss == BA_LOSS_HUBER, f_scale, rdev);
+  launch_residual(h, h->cur, (ba_loss)loss, f_scale, rdev);
   launch_scalars(h, false);
   if (int rc = allreduce(h, h->scal.p, 2)) return rc;
   HIPCHECK(hipMemcpyAsync(h->h_scal, h->scal.p, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2005,7 +2011,7 @@ extern "C" int ba_residuals_bal(ba_handle* h, const double* intr, int32_t loss, 
                                 double* cost) {
   if (!h || !intr) return fail(BA_ERR_INVALID, "null argument");
   if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
-  if (loss != BA_LOSS_LINEAR && loss != BA_LOSS_HUBER) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
+  if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
   if (!(f_scale > 0)) return fail(BA_ERR_INVALID, "f_scale must be positive");
   if (set_device(h)) return BA_ERR_HIP;
   HIPCHECK(h->tri.alloc(3 * (size_t)h->Nc + 8));
@@ -2017,9 +2023,9 @@ extern "C" int ba_residuals_bal(ba_handle* h, const double* intr, int32_t loss, 
   }
   {
     Scope sc(h, BA_K_RESIDUAL);
-    auto kern = loss == BA_LOSS_HUBER ? k_cam_residual_bal<true> : k_cam_residual_bal<false>;
+    auto kern = loss != BA_LOSS_LINEAR ? k_cam_residual_bal<true> : k_cam_residual_bal<false>;
     BA_LAUNCH(kern, dim3(cam_grid(h)), dim3(64 * WPB), 0, h->stream, h->cs[h->cur].p, (const double*)h->tri.p, h->ptab[h->cur].p,
-              h->offk.p, h->c_pt.p, uv_arr(h, h->c_uv), h->c_orig.p, f_scale, h->Nc, h->cam_band, rdev, h->partR.p);
+              h->offk.p, h->c_pt.p, uv_arr(h, h->c_uv), h->c_orig.p, f_scale, (int)loss, h->Nc, h->cam_band, rdev, h->partR.p);
   }
   launch_scalars(h, false);
   if (int rc = allreduce(h, h->scal.p, 2)) return rc;
@@ -2035,15 +2041,15 @@ extern "C" int ba_residuals_bal(ba_handle* h, const double* intr, int32_t loss, 
 extern "C" int ba_linearize(ba_handle* h, int32_t loss, double f_scale, double* Hcc, double* bc, double* Hpp, double* bp) {
   if (!h) return fail(BA_ERR_INVALID, "null handle");
   if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
-  if (loss != BA_LOSS_LINEAR && loss != BA_LOSS_HUBER) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
+  if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
   if (!(f_scale > 0)) return fail(BA_ERR_INVALID, "f_scale must be positive");
   if (set_device(h)) return BA_ERR_HIP;
-  launch_lin_cam(h, h->cur, h->lb, loss == BA_LOSS_HUBER, f_scale);
+  launch_lin_cam(h, h->cur, h->lb, (ba_loss)loss, f_scale);
   if (int rc = exchange_partL(h, h->lb)) return rc;
   launch_lin_finalize(h);
-  launch_lin_pt(h, h->cur, h->pb, loss == BA_LOSS_HUBER, f_scale, 1.0);
+  launch_lin_pt(h, h->cur, h->pb, (ba_loss)loss, f_scale, 1.0);
   h->linearized = true;
-  h->lin_robust = (loss == BA_LOSS_HUBER);
+  h->lin_loss = (ba_loss)loss;
   h->lin_fscale = f_scale;
   if (Hcc) HIPCHECK(hipMemcpyAsync(Hcc, h->HccBc.p, 21 * (size_t)h->Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (bc) HIPCHECK(hipMemcpyAsync(bc, bc_ptr(h), 6 * (size_t)h->Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2066,7 +2072,7 @@ extern "C" int ba_linearize(ba_handle* h, int32_t loss, double f_scale, double* 
 // PCG vectors redone with the coarse term (k_pcg_coarse with k = -1 writes the partials iteration 0's probe sums).
 static void coarse_build(ba_handle* h) {
   const int n = 6 * h->n_agg;
-  const bool robust = h->lin_robust;
+  const bool robust = h->lin_loss != BA_LOSS_LINEAR;
   Scope sc(h, BA_K_PRECOND);
   (void)hipMemsetAsync(h->coarseEint.p, 0, (size_t)n * n * sizeof(long long), h->stream);
   BA_LAUNCH(k_coarse_diag, dim3(1), dim3(1024), 0, h->stream, (const double*)h->Hccd.p, h->Nc, h->fixed, h->n_agg, h->coarseEint.p,
@@ -2102,7 +2108,7 @@ static void coarse_build(ba_handle* h);
 static int damped_system(ba_handle* h, double lambda, bool schur_diag, bool invert = true, bool finalize = false, bool keep = false) {
   if (invert) launch_point_invert(h, lambda);
   const bool diag_pass = schur_diag && !keep;
-  launch_cam_schur(h, h->lin_robust, diag_pass, false, 0, 0.0, 0);
+  launch_cam_schur(h, h->lin_loss != BA_LOSS_LINEAR, diag_pass, false, 0, 0.0, 0);
   if (int rc = exchange_system(h, diag_pass)) return rc;
   launch_pcg_setup(h, lambda, schur_diag ? (keep ? 2 : 1) : 0, finalize);
   if (h->two_level) coarse_build(h);
@@ -2132,8 +2138,8 @@ extern "C" int ba_schur_apply(ba_handle* h, double lambda, const double* v, doub
                        h->fixed, h->camA[h->cur].p);
     BA_LAUNCH(k_pcg_reset, dim3(1), dim3(64), 0, h->stream, h->st.p, h->partV.p, nbv(h));
   }
-  launch_pt_schur(h, h->lin_robust, 0, 0, -1.0, 1 << 30);        // y = Hppinv W^T v into the point table
-  launch_cam_schur(h, h->lin_robust, false, false, 0, 0.0, 0);
+  launch_pt_schur(h, h->lin_loss != BA_LOSS_LINEAR, 0, 0, -1.0, 1 << 30);        // y = Hppinv W^T v into the point table
+  launch_cam_schur(h, h->lin_loss != BA_LOSS_LINEAR, false, false, 0, 0.0, 0);
   if (int rc = exchange_schur(h)) return rc;
   {
     Scope sc(h, BA_K_MISC);
@@ -2175,8 +2181,8 @@ static double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-static int eval_cost(ba_handle* h, int which, bool robust, double fscale, double* sse, double* cost) {
-  launch_residual(h, which, robust, fscale, nullptr);
+static int eval_cost(ba_handle* h, int which, ba_loss loss, double fscale, double* sse, double* cost) {
+  launch_residual(h, which, loss, fscale, nullptr);
   launch_scalars(h, false);
   if (int rc = allreduce(h, h->scal.p, 2)) return rc;
   HIPCHECK(hipMemcpyAsync(h->h_scal, h->scal.p, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2235,7 +2241,7 @@ static int small_solve(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   bool used_mw = h->mw_ok && (!mw_env || atoi(mw_env) != 0);
   HIPCHECK(h->small_gS.alloc((size_t)SMALL_WAVES * SMALL_TILES * 256 + 16));        // + 16 words of diagnostic stamps
   A.gS = h->small_gS.p;
-  A.n_cams = h->Nc; A.n_pts = h->Np; A.fixed_cam = h->fixed; A.robust = opts->loss == BA_LOSS_HUBER;
+  A.n_cams = h->Nc; A.n_pts = h->Np; A.fixed_cam = h->fixed; A.loss = opts->loss;
   A.fx = h->K4[0]; A.fy = h->K4[1]; A.cx = h->K4[2]; A.cy = h->K4[3]; A.hub_c = opts->f_scale;
   A.max_iters = opts->max_iters; A.ftol = opts->ftol; A.xtol = opts->xtol; A.gtol = opts->gtol; A.lambda0 = opts->initial_lambda;
   A.cur = h->cur;
@@ -2354,15 +2360,15 @@ extern "C" int ba_linearize_bal(ba_handle* h, const double* intr, int32_t loss, 
                                 double* Hpp, double* bp) {
   if (!h || !intr) return fail(BA_ERR_INVALID, "null argument");
   if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
-  if (loss != BA_LOSS_LINEAR && loss != BA_LOSS_HUBER) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
+  if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
   if (!(f_scale > 0)) return fail(BA_ERR_INVALID, "f_scale must be positive");
   if (set_device(h)) return BA_ERR_HIP;
   if (int rc = bal_enter(h, intr)) return rc;
   auto body = [&]() -> int {
-    launch_lin_cam(h, h->cur, h->lb, loss == BA_LOSS_HUBER, f_scale);
+    launch_lin_cam(h, h->cur, h->lb, (ba_loss)loss, f_scale);
     if (int rc = exchange_partL(h, h->lb)) return rc;
     launch_lin_finalize(h);
-    launch_lin_pt(h, h->cur, h->pb, loss == BA_LOSS_HUBER, f_scale, 1.0);
+    launch_lin_pt(h, h->cur, h->pb, (ba_loss)loss, f_scale, 1.0);
     if (Hcc) HIPCHECK(hipMemcpyAsync(Hcc, h->HccBc.p, BalCam::NH * (size_t)h->Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (bc) HIPCHECK(hipMemcpyAsync(bc, bc_ptr(h), BalCam::NB * (size_t)h->Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if ((Hpp || bp) && h->Np) {
@@ -2409,7 +2415,7 @@ extern "C" int ba_solve_bal(ba_handle* h, double* intr, const ba_options* opts, 
 
 static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
-  if (opts->loss != BA_LOSS_LINEAR && opts->loss != BA_LOSS_HUBER) return fail(BA_ERR_INVALID, "unknown loss");
+  if (!loss_valid(opts->loss)) return fail(BA_ERR_INVALID, "unknown loss %d", opts->loss);
   if (!(opts->f_scale > 0) || opts->max_iters < 0 || opts->pcg_max_iters < 1 || !(opts->initial_lambda > 0))
     return fail(BA_ERR_INVALID, "bad options");
   if (opts->jacobian_precision != 0 && opts->jacobian_precision != 1)
@@ -2433,7 +2439,8 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   h->jac_f32 = opts->jacobian_precision == 1;
   roctx_load();
   Range r_solve("ba_solve");
-  const bool robust = opts->loss == BA_LOSS_HUBER;
+  const ba_loss loss = (ba_loss)opts->loss;
+  const bool robust = loss != BA_LOSS_LINEAR;        // (the Schur passes only read the weights: the same for every non-linear loss)
   const bool schur_diag = opts->preconditioner != BA_PRECOND_JACOBI;
   h->two_level = opts->preconditioner == BA_PRECOND_TWO_LEVEL && h->model == 0;
   const double fs = opts->f_scale;
@@ -2447,7 +2454,7 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   BA_SYNC(h);
   const double t_begin = now_s();
   double sse = 0, cost = 0;
-  if (int rc = eval_cost(h, h->cur, robust, fs, &sse, &cost)) return rc;
+  if (int rc = eval_cost(h, h->cur, loss, fs, &sse, &cost)) return rc;
   if (!std::isfinite(cost)) return fail(BA_ERR_NUMERIC, "non-finite cost at the initial parameters");
   sum->initial_sse = sse;
   sum->initial_cost = cost;
@@ -2488,13 +2495,13 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     if (need_linearize) {
       Range r_lin("linearize");
       if (!have_lin) {
-        launch_lin_cam(h, h->cur, h->lb, robust, fs);
-        launch_lin_pt(h, h->cur, h->pb, robust, fs, lambda);          // also Hpp^-1, y0 at this lambda
+        launch_lin_cam(h, h->cur, h->lb, loss, fs);
+        launch_lin_pt(h, h->cur, h->pb, loss, fs, lambda);          // also Hpp^-1, y0 at this lambda
         // multi-rank: the camera-half partials of a pass launched here still have to be all-reduced
         // (a speculated pass was reduced right behind its launch)
         if (int rc = exchange_partL(h, h->lb)) return rc;
       }
-      h->lin_robust = robust; h->lin_fscale = fs;
+      h->lin_loss = loss; h->lin_fscale = fs;
       need_linearize = false;
       have_lin = false;
       fresh = true;
@@ -2654,8 +2661,8 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     // GPU already runs the point half at the trial point with that damping, into the other point buffers.  An accepted
     // step finds its linearisation done; a rejected one ignores both.
     const bool speculated = (it + 1 < opts->max_iters);
-    if (speculated) launch_lin_cam(h, 1 - h->cur, 1 - h->lb, robust, fs, true);
-    else            launch_residual(h, 1 - h->cur, robust, fs, nullptr);
+    if (speculated) launch_lin_cam(h, 1 - h->cur, 1 - h->lb, loss, fs, true);
+    else            launch_residual(h, 1 - h->cur, loss, fs, nullptr);
     if (debug_poison) BA_LAUNCH(k_poison, dim3(1), dim3(64), 0, h->stream, h->partR.p);
     const long long seq = ++h->step_seq;
     // the step's scalar fold + verdict: single rank with a speculated point half behind it -> workgroup 0 of that launch
@@ -2676,7 +2683,7 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     if (speculated) {
       ScalarsArgs sa = scalars_args(h, true, k, tol2, opts->pcg_min_iters, seq, cost, lambda, lam_floor);
       sa.on = 1; sa.lam_slot = h->dev_lam.p; sa.err_flag = h->d_flags + 6;
-      launch_lin_pt(h, 1 - h->cur, 1 - h->pb, robust, fs, 0.0, h->scal.p + S_LAM_NEXT, ride_scalars ? &sa : nullptr);
+      launch_lin_pt(h, 1 - h->cur, 1 - h->pb, loss, fs, 0.0, h->scal.p + S_LAM_NEXT, ride_scalars ? &sa : nullptr);
     }
     if (int rc = wait_flag(h, 2, seq)) return rc;
     if (h->h_flags[6] != 0) {          // a point workgroup of the speculated pass waited RIDER_WAIT_TICKS for the riding verdict
@@ -2861,10 +2868,11 @@ extern "C" int ba_time_kernel(ba_handle* h, int slot, int reps, double* mean_us)
   if (set_device(h)) return BA_ERR_HIP;
   const bool saved = h->profile;
   h->profile = false;
-  const bool robust = h->lin_robust;
-  launch_lin_cam(h, h->cur, h->lb, robust, h->lin_fscale);
+  const ba_loss loss = h->lin_loss;
+  const bool robust = loss != BA_LOSS_LINEAR;
+  launch_lin_cam(h, h->cur, h->lb, loss, h->lin_fscale);
   launch_lin_finalize(h);
-  launch_lin_pt(h, h->cur, h->pb, robust, h->lin_fscale, 1e-4);
+  launch_lin_pt(h, h->cur, h->pb, loss, h->lin_fscale, 1e-4);
   h->linearized = true;
   if (int rc = damped_system(h, 1e-4, true)) return rc;
   BA_LAUNCH(k_pcg_reset, dim3(1), dim3(64), 0, h->stream, h->st.p, h->partV.p, nbv(h));
@@ -2873,9 +2881,9 @@ extern "C" int ba_time_kernel(ba_handle* h, int slot, int reps, double* mean_us)
   HIPCHECK(hipEventCreate(&e1));
   auto once = [&]() {
     switch (slot) {
-      case BA_K_RESIDUAL: launch_residual(h, h->cur, robust, h->lin_fscale, nullptr); break;
-      case BA_K_LINEARIZE_CAM: launch_lin_cam(h, h->cur, h->lb, robust, h->lin_fscale); break;
-      case BA_K_LINEARIZE_PT: launch_lin_pt(h, h->cur, h->pb, robust, h->lin_fscale, 1e-4); break;
+      case BA_K_RESIDUAL: launch_residual(h, h->cur, loss, h->lin_fscale, nullptr); break;
+      case BA_K_LINEARIZE_CAM: launch_lin_cam(h, h->cur, h->lb, loss, h->lin_fscale); break;
+      case BA_K_LINEARIZE_PT: launch_lin_pt(h, h->cur, h->pb, loss, h->lin_fscale, 1e-4); break;
       case BA_K_SCHUR_PT: launch_pt_schur(h, robust, 0, 0, -1.0, 1 << 30); break;
       case BA_K_SCHUR_CAM: launch_cam_schur(h, robust, false, false, 0, 0.0, 0); break;
       case BA_K_PRECOND: launch_cam_schur(h, robust, true, false, 0, 0.0, 0); break;

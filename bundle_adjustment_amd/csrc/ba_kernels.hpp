@@ -68,7 +68,8 @@ constexpr int VEC_CAMS = Pinhole::VC;   // cameras per workgroup (CM::VC per cam
 // a copy of each index stream whose top bit says "this observation's weights are not (1, 1)".
 // The Schur passes read that copy and fetch the 16-byte weight only for flagged observations:
 // near the solution most observations are Huber inliers, and the weight streams are otherwise
-// the largest share of a pass's traffic.  Bit-identical results: an unflagged weight IS (1, 1).
+// the largest share of a pass's traffic.  Bit-identical results: an unflagged weight IS (1, 1).  (Under the smooth losses
+// -- soft_l1, cauchy, arctan -- almost no weight is exactly 1: every index is flagged and every weight fetched.)
 constexpr int IDX_FLAG = (int)0x80000000;
 constexpr int IDX_MASK = 0x7fffffff;
 __device__ inline int flagged_index(int idx, double w0, double w1) { return (w0 != 1.0 || w1 != 1.0) ? (idx | IDX_FLAG) : idx; }
@@ -298,7 +299,7 @@ template <bool ROBUST>
 __global__ void __launch_bounds__(64 * WPB)
 k_cam_residual(const double* __restrict__ cs, const double* __restrict__ ptab, const int* __restrict__ offk,
                const int* __restrict__ c_pt, const UvArr c_uv, const int* __restrict__ c_orig,
-               double fx, double fy, double cx, double cy, double hub_c, int n_cams, int band,
+               double fx, double fy, double cx, double cy, double hub_c, int loss, int n_cams, int band,
                double* __restrict__ r_out, double* __restrict__ partR) {
   Seg s;
   if (!cam_segment(offk, n_cams, band, s)) return;
@@ -315,8 +316,8 @@ k_cam_residual(const double* __restrict__ cs, const double* __restrict__ ptab, c
     acc[0] += ru * ru + rv * rv;
     if (ROBUST) {
       double t0, t1, w;
-      huber(ru, hub_c, t0, w);
-      huber(rv, hub_c, t1, w);
+      robust_loss<true>(loss, ru, hub_c, t0, w);
+      robust_loss<true>(loss, rv, hub_c, t1, w);
       acc[1] += t0 + t1;
     }
     if (r_out) {
@@ -336,7 +337,7 @@ template <bool ROBUST>
 __global__ void __launch_bounds__(64 * WPB)
 k_cam_residual_bal(const double* __restrict__ cs, const double* __restrict__ intr, const double* __restrict__ ptab,
                    const int* __restrict__ offk, const int* __restrict__ c_pt, const UvArr c_uv,
-                   const int* __restrict__ c_orig, double hub_c, int n_cams, int band,
+                   const int* __restrict__ c_orig, double hub_c, int loss, int n_cams, int band,
                    double* __restrict__ r_out, double* __restrict__ partR) {
   Seg s;
   if (!cam_segment(offk, n_cams, band, s)) return;
@@ -357,8 +358,8 @@ k_cam_residual_bal(const double* __restrict__ cs, const double* __restrict__ int
     acc[0] += ru * ru + rv * rv;
     if (ROBUST) {
       double t0, t1, w;
-      huber(ru, hub_c, t0, w);
-      huber(rv, hub_c, t1, w);
+      robust_loss<true>(loss, ru, hub_c, t0, w);
+      robust_loss<true>(loss, rv, hub_c, t1, w);
       acc[1] += t0 + t1;
     }
     if (r_out) {
@@ -622,7 +623,7 @@ template <class CM, bool ROBUST, bool COST>
 __global__ void __launch_bounds__(ROW_LANES * ROWS)
 k_camrow_linearize(const double* __restrict__ cs, const double* __restrict__ intr, const double* __restrict__ ptab,
                    const int* __restrict__ offk, const int* __restrict__ c_pt, const UvArr c_uv,
-                   double fx, double fy, double cx, double cy, double hub_c, int n_cams, int band,
+                   double fx, double fy, double cx, double cy, double hub_c, int loss, int n_cams, int band,
                    double2* __restrict__ c_w, int* __restrict__ c_ptf, double* __restrict__ partL,
                    double* __restrict__ partR) {
   constexpr int NB = CM::NB, NH = CM::NH, NL = CM::NL;
@@ -656,8 +657,8 @@ k_camrow_linearize(const double* __restrict__ cs, const double* __restrict__ int
       if (COST) acc[NL] += ru * ru + rv * rv;
       if (ROBUST) {
         double t0, t1;
-        huber(ru, hub_c, t0, w0);
-        huber(rv, hub_c, t1, w1);
+        robust_loss<COST>(loss, ru, hub_c, t0, w0);
+        robust_loss<COST>(loss, rv, hub_c, t1, w1);
         if (COST) acc[NL + 1] += t0 + t1;
         const int pfl = flagged_index(p, w0, w1);
         if (pfl != pr) c_ptf[i] = pfl;
@@ -967,7 +968,7 @@ template <class CM, bool ROBUST, bool ALL_LDS, int LANES>
 __device__ __forceinline__ void
 pt_linearize_body(const double* __restrict__ camA, double* __restrict__ ptab, const int* __restrict__ pt_off,
                   const int* __restrict__ p_cam, const UvArr p_uv, const int2* __restrict__ blk_win,
-                  const PtWork& wk, int bid, int nblk, double fx, double fy, double cx, double cy, double hub_c,
+                  const PtWork& wk, int bid, int nblk, double fx, double fy, double cx, double cy, double hub_c, int loss,
                   double lambda_arg, const double* __restrict__ lam_dev, double* __restrict__ Hpp, double* __restrict__ bp,
                   double2* __restrict__ p_w, int* __restrict__ p_camf, double* __restrict__ Hppinv, double* __restrict__ y0,
                   double* __restrict__ partG, const double* __restrict__ lam_slot = nullptr, long long* __restrict__ err_flag = nullptr) {
@@ -1016,8 +1017,8 @@ pt_linearize_body(const double* __restrict__ camA, double* __restrict__ ptab, co
         double w0 = 1.0, w1 = 1.0;
         if (ROBUST) {
           double t;
-          huber(ru, hub_c, t, w0);
-          huber(rv, hub_c, t, w1);
+          robust_loss<false>(loss, ru, hub_c, t, w0);
+          robust_loss<false>(loss, rv, hub_c, t, w1);
           const int cfl = flagged_index(c, w0, w1);
           if (cfl != cr) p_camf[j] = cfl;
           if (cfl < 0) p_w[j] = make_double2(w0, w1);      // unflagged weights are never read
@@ -1086,7 +1087,7 @@ pt_linearize_body(const double* __restrict__ camA, double* __restrict__ ptab, co
 
 #define BA_LIN_PARAMS const double* __restrict__ camA, double* __restrict__ ptab, const int* __restrict__ pt_off,               \
                       const int* __restrict__ p_cam, const UvArr p_uv, const int2* __restrict__ blk_win
-#define BA_LIN_TAIL double fx, double fy, double cx, double cy, double hub_c, double lambda, const double* __restrict__ lam_dev, \
+#define BA_LIN_TAIL double fx, double fy, double cx, double cy, double hub_c, int loss, double lambda, const double* __restrict__ lam_dev, \
                     double* __restrict__ Hpp, double* __restrict__ bp, double2* __restrict__ p_w, int* __restrict__ p_camf,      \
                     double* __restrict__ Hppinv, double* __restrict__ y0, double* __restrict__ partG, ScalarsArgs sa
 // one kind of track per launch
@@ -1096,7 +1097,7 @@ k_pt_linearize(BA_LIN_PARAMS, PtWork wk, BA_LIN_TAIL) {
   // the rider: workgroup 0; workgroups 1 .. NPART-1 leave at once, so that the point workgroups keep their XCD (= index mod NPART)
   if (sa.on && blockIdx.x < NPART) { if (blockIdx.x == 0) scalars_body(sa); return; }
   pt_linearize_body<CM, ROBUST, ALL_LDS, LANES>(camA, ptab, pt_off, p_cam, p_uv, blk_win, wk, (int)blockIdx.x - sa.on * NPART, (int)gridDim.x - sa.on * NPART,
-                                            fx, fy, cx, cy, hub_c, lambda, lam_dev, Hpp, bp, p_w, p_camf, Hppinv, y0, partG,
+                                            fx, fy, cx, cy, hub_c, loss, lambda, lam_dev, Hpp, bp, p_w, p_camf, Hppinv, y0, partG,
                                             sa.on ? sa.lam_slot : (const double*)nullptr, sa.err_flag);
 }
 // short and long tracks in one launch: workgroups [0, nblk_short) take the range list with LPP lanes
@@ -1110,10 +1111,10 @@ k_pt_linearize_both(BA_LIN_PARAMS, PtWork wk, int nblk_short, PtWork wl, BA_LIN_
   const double* lf = sa.on ? sa.lam_slot : (const double*)nullptr;
   if (bid < nblk_short)
     pt_linearize_body<CM, ROBUST, ALL_LDS, LPP>(camA, ptab, pt_off, p_cam, p_uv, blk_win, wk, bid, nblk_short, fx, fy, cx, cy,
-                                            hub_c, lambda, lam_dev, Hpp, bp, p_w, p_camf, Hppinv, y0, partG, lf, sa.err_flag);
+                                            hub_c, loss, lambda, lam_dev, Hpp, bp, p_w, p_camf, Hppinv, y0, partG, lf, sa.err_flag);
   else
     pt_linearize_body<CM, ROBUST, ALL_LDS, LPP_LONG>(camA, ptab, pt_off, p_cam, p_uv, blk_win, wl, bid - nblk_short,
-                                                 nblk - nblk_short, fx, fy, cx, cy, hub_c, lambda, lam_dev, Hpp, bp, p_w,
+                                                 nblk - nblk_short, fx, fy, cx, cy, hub_c, loss, lambda, lam_dev, Hpp, bp, p_w,
                                                  p_camf, Hppinv, y0, partG, lf, sa.err_flag);
 }
 #undef BA_LIN_PARAMS

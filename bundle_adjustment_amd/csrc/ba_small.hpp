@@ -62,7 +62,7 @@ struct SmallArgs {
   double* V;                                                 // Kp / 16 slabs of [SMALL_VROWS][16], zero outside what P1 writes
   double* gS;                                                // [waves][SMALL_TILES][64 lanes x 4]: partial V V^T
   int Kp, Np_pad;                                            // Kp = 3 Np_pad, Np_pad a multiple of 16
-  int n_cams, n_pts, fixed_cam, robust;
+  int n_cams, n_pts, fixed_cam, loss;                       // loss: ba_loss code
   double fx, fy, cx, cy, hub_c;
   int max_iters; double ftol, xtol, gtol, lambda0;
   int cur;                                                   // which parameter set holds the start point
@@ -174,7 +174,7 @@ k_small_lm(SmallArgs A) {
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave id in a scalar register
   const int Nc = A.n_cams, Np = A.n_pts, n = 6 * Nc;
   const int Kp = A.Kp, Npp = A.Np_pad;
-  const bool robust = A.robust != 0;
+  const bool robust = A.loss != LOSS_LINEAR;
   // camera-major passes: wpc waves share one camera (lanes stride 64 wpc), partial sums combined in wave order
   const int wpc = Nc <= 1 ? SMALL_WAVES : Nc <= 2 ? SMALL_WAVES / 2 : Nc <= 4 ? SMALL_WAVES / 4 : SMALL_WAVES / 8;
   const int my_cam = wv / wpc, my_sub = wv % wpc;
@@ -200,7 +200,7 @@ k_small_lm(SmallArgs A) {
         obs_project(cs, X.x, X.y, X.z, xh, yh);
         const double ru = uv.x - (xh * A.fx + A.cx), rv = uv.y - (yh * A.fy + A.cy);
         acc[0] += ru * ru + rv * rv;
-        if (robust) { double t0, t1, ww; huber(ru, A.hub_c, t0, ww); huber(rv, A.hub_c, t1, ww); acc[1] += t0 + t1; }
+        if (robust) { double t0, t1, ww; robust_loss<true>(A.loss, ru, A.hub_c, t0, ww); robust_loss<true>(A.loss, rv, A.hub_c, t1, ww); acc[1] += t0 + t1; }
       }
       if (!robust) acc[1] = acc[0];
       acc[0] = wave_total_dpp(acc[0]); acc[1] = wave_total_dpp(acc[1]);
@@ -245,7 +245,7 @@ k_small_lm(SmallArgs A) {
             obs_geom(cs, X.x, X.y, X.z, A.fx, A.fy, g);
             const double ru = uv.x - (g.xh * A.fx + A.cx), rv = uv.y - (g.yh * A.fy + A.cy);
             double w0 = 1.0, w1 = 1.0;
-            if (robust) { double t; huber(ru, A.hub_c, t, w0); huber(rv, A.hub_c, t, w1); }
+            if (robust) { double t; robust_loss<false>(A.loss, ru, A.hub_c, t, w0); robust_loss<false>(A.loss, rv, A.hub_c, t, w1); }
             double c0[6], c1[6];
             small_cam_rows(cs, g, X.x, X.y, X.z, c0, c1);
 #pragma unroll
@@ -294,7 +294,7 @@ k_small_lm(SmallArgs A) {
           obs_geom(&l_cs[cur][c][0], X.x, X.y, X.z, A.fx, A.fy, g);
           const double ru = uv.x - (g.xh * A.fx + A.cx), rv = uv.y - (g.yh * A.fy + A.cy);
           double w0 = 1.0, w1 = 1.0;
-          if (robust) { double t; huber(ru, A.hub_c, t, w0); huber(rv, A.hub_c, t, w1); }
+          if (robust) { double t; robust_loss<false>(A.loss, ru, A.hub_c, t, w0); robust_loss<false>(A.loss, rv, A.hub_c, t, w1); }
 #pragma unroll
           for (int q = 0; q < 3; ++q) {
             const double wa0 = w0 * g.P[q], wa1 = w1 * g.P[3 + q];
@@ -342,7 +342,7 @@ k_small_lm(SmallArgs A) {
         double w0 = 1.0, w1 = 1.0;
         if (robust) {
           const double ru = uv.x - (g.xh * A.fx + A.cx), rv = uv.y - (g.yh * A.fy + A.cy);
-          double t; huber(ru, A.hub_c, t, w0); huber(rv, A.hub_c, t, w1);
+          double t; robust_loss<false>(A.loss, ru, A.hub_c, t, w0); robust_loss<false>(A.loss, rv, A.hub_c, t, w1);
         }
         double c0[6], c1[6];
         small_cam_rows(&l_cs[cur][c][0], g, X.x, X.y, X.z, c0, c1);

@@ -110,7 +110,7 @@ k_small_mw(MwArgs M) {
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = blockIdx.x, G = M.G;
   const int Nc = A.n_cams, Np = A.n_pts, n = 6 * Nc;
-  const bool robust = A.robust != 0;
+  const bool robust = A.loss != LOSS_LINEAR;
   const int nS = n * (n + 1) / 2;                    // message: [0, nS) upper triangle | V z (n) | bc (n) | diag Hcc (n) | max |bp|
   const int msg_len = nS + 3 * n + 1;
   const int pl = tid / MW_LPP, sub = tid % MW_LPP;   // landmark of this thread inside the workgroup, lane inside the landmark
@@ -226,7 +226,7 @@ k_small_mw(MwArgs M) {
         obs_project(cs, X.x, X.y, X.z, xh, yh);
         const double ru = uv.x - (xh * A.fx + A.cx), rv = uv.y - (yh * A.fy + A.cy);
         acc[0] += ru * ru + rv * rv;
-        if (robust) { double t0, t1, ww; huber(ru, A.hub_c, t0, ww); huber(rv, A.hub_c, t1, ww); acc[1] += t0 + t1; }
+        if (robust) { double t0, t1, ww; robust_loss<true>(A.loss, ru, A.hub_c, t0, ww); robust_loss<true>(A.loss, rv, A.hub_c, t1, ww); acc[1] += t0 + t1; }
       }
       if (!robust) acc[1] = acc[0];
       acc[0] = wave_total_dpp(acc[0]); acc[1] = wave_total_dpp(acc[1]);
@@ -288,7 +288,7 @@ k_small_mw(MwArgs M) {
             obs_geom(cs, X.x, X.y, X.z, A.fx, A.fy, gm);
             const double ru = uv.x - (gm.xh * A.fx + A.cx), rv = uv.y - (gm.yh * A.fy + A.cy);
             double w0 = 1.0, w1 = 1.0;
-            if (robust) { double t; huber(ru, A.hub_c, t, w0); huber(rv, A.hub_c, t, w1); }
+            if (robust) { double t; robust_loss<false>(A.loss, ru, A.hub_c, t, w0); robust_loss<false>(A.loss, rv, A.hub_c, t, w1); }
             double c0[6], c1[6];
             small_cam_rows(cs, gm, X.x, X.y, X.z, c0, c1);
 #pragma unroll
@@ -320,7 +320,7 @@ k_small_mw(MwArgs M) {
       if (my_c >= 0) {
         obs_geom(&l_cs[cur][my_c][0], X.x, X.y, X.z, A.fx, A.fy, gm);
         ru = my_uv.x - (gm.xh * A.fx + A.cx); rv = my_uv.y - (gm.yh * A.fy + A.cy);
-        if (robust) { double t; huber(ru, A.hub_c, t, w0); huber(rv, A.hub_c, t, w1); }
+        if (robust) { double t; robust_loss<false>(A.loss, ru, A.hub_c, t, w0); robust_loss<false>(A.loss, rv, A.hub_c, t, w1); }
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
           const double wa0 = w0 * gm.P[q], wa1 = w1 * gm.P[3 + q];

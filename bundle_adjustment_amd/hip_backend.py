@@ -16,7 +16,7 @@ from .problem import BAProblem
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BA_HIP_LIB") or os.path.join(_HERE, "libba_hip.so")   # BA_HIP_LIB: another build of the same ABI
 
-LOSS = {"linear": 0, "huber": 1}
+LOSS = {"linear": 0, "huber": 1, "soft_l1": 2, "cauchy": 3, "arctan": 4}    # scipy least_squares' losses (enum ba_loss)
 PRECOND = {"jacobi": 0, "schur_jacobi": 1, "two_level": 2}
 STATUS_NAMES = {0: "max_iters", 1: "ftol", 2: "xtol", 3: "gtol"}
 PROFILE_SLOTS = 16
@@ -25,6 +25,15 @@ K_RESIDUAL, K_LINEARIZE_CAM, K_LINEARIZE_PT, K_POINT_INVERT, K_SCHUR_PT, K_SCHUR
 
 class BAHipError(RuntimeError):
     pass
+
+
+def loss_code(loss):
+    """enum ba_loss value of a loss given by scipy name (or already by value); an unknown name raises ValueError."""
+    if isinstance(loss, str):
+        if loss not in LOSS:
+            raise ValueError(f"unknown loss {loss!r}: expected one of {', '.join(map(repr, LOSS))}")
+        return LOSS[loss]
+    return loss
 
 
 class BAOptions(C.Structure):
@@ -211,13 +220,13 @@ class Solver:
     def residuals(self, loss="linear", f_scale=1.0, want_vector=True):
         r = np.empty((self.n_obs, 2)) if want_vector else None
         sse, cost = C.c_double(), C.c_double()
-        _check(self._lib.ba_residuals(self._h, LOSS[loss], float(f_scale), _dp(r), C.byref(sse), C.byref(cost)))
+        _check(self._lib.ba_residuals(self._h, loss_code(loss), float(f_scale), _dp(r), C.byref(sse), C.byref(cost)))
         return r, sse.value, cost.value
 
     def linearize(self, loss="linear", f_scale=1.0):
         Hcc = np.empty((self.n_cams, 21)); bc = np.empty((self.n_cams, 6))
         Hpp = np.empty((self.n_pts, 6)); bp = np.empty((self.n_pts, 3))
-        _check(self._lib.ba_linearize(self._h, LOSS[loss], float(f_scale), _dp(Hcc), _dp(bc), _dp(Hpp), _dp(bp)))
+        _check(self._lib.ba_linearize(self._h, loss_code(loss), float(f_scale), _dp(Hcc), _dp(bc), _dp(Hpp), _dp(bp)))
         return Hcc, bc, Hpp, bp
 
     def schur_rhs(self, lam):
@@ -238,7 +247,7 @@ class Solver:
         return o
 
     def solve(self, **kw):
-        """kw: loss ('linear'|'huber'), preconditioner ('jacobi'|'schur_jacobi') or any
+        """kw: loss ('linear'|'huber'|'soft_l1'|'cauchy'|'arctan'), preconditioner ('jacobi'|'schur_jacobi') or any
         ba_options field.  Returns the summary as a dict."""
         o = self._options(kw)
         s = BASummary()
@@ -253,7 +262,7 @@ class Solver:
         intr = np.ascontiguousarray(bal.cams[:, 6:9], dtype=np.float64)
         r = np.empty((self.n_obs, 2)) if want_vector else None
         sse, cost = C.c_double(0), C.c_double(0)
-        _check(self._lib.ba_residuals_bal(self._h, _dp(intr), LOSS[loss] if isinstance(loss, str) else loss, float(f_scale),
+        _check(self._lib.ba_residuals_bal(self._h, _dp(intr), loss_code(loss), float(f_scale),
                                           _dp(r), C.byref(sse), C.byref(cost)))
         return r, sse.value, cost.value
 
@@ -268,7 +277,7 @@ class Solver:
         intr = self._set_bal(bal, fixed_cam)
         out = dict(Hcc=np.empty((self.n_cams, 45)), bc=np.empty((self.n_cams, 9)), Hpp=np.empty((self.n_pts, 6)),
                    bp=np.empty((self.n_pts, 3)))
-        _check(self._lib.ba_linearize_bal(self._h, _dp(intr), LOSS[loss] if isinstance(loss, str) else loss, float(f_scale),
+        _check(self._lib.ba_linearize_bal(self._h, _dp(intr), loss_code(loss), float(f_scale),
                                           _dp(out["Hcc"]), _dp(out["bc"]), _dp(out["Hpp"]), _dp(out["bp"])))
         return out
 
@@ -291,7 +300,7 @@ class Solver:
         o = self.default_options()
         for k, v in kw.items():
             if k == "loss":
-                v = LOSS[v] if isinstance(v, str) else v
+                v = loss_code(v)
             if k == "preconditioner":
                 v = PRECOND[v] if isinstance(v, str) else v
             if not hasattr(o, k):

@@ -40,7 +40,9 @@ enum ba_status {
   BA_ERR_COMM = -5       /* RCCL load / init / collective failure */
 };
 
-enum ba_loss { BA_LOSS_LINEAR = 0, BA_LOSS_HUBER = 1 };
+/* scipy least_squares' losses, rho(z) of z = (f / f_scale)^2 per scalar residual f; cost = 0.5 sum f_scale^2 rho(z):
+ * linear z, huber z <= 1 ? z : 2 sqrt(z) - 1, soft_l1 2 (sqrt(1 + z) - 1), cauchy log(1 + z), arctan atan(z). */
+enum ba_loss { BA_LOSS_LINEAR = 0, BA_LOSS_HUBER = 1, BA_LOSS_SOFT_L1 = 2, BA_LOSS_CAUCHY = 3, BA_LOSS_ARCTAN = 4 };
 /* JACOBI: blocks of Hcc + lambda D.  SCHUR_JACOBI (default): the diagonal blocks of the reduced camera matrix S.
  * TWO_LEVEL: Schur-Jacobi plus an additive coarse correction P E^-1 P^T over aggregates of 16 consecutive cameras,
  * E = P^T S P, for band-structured problems (sequential captures such as BASELINE config 5, where block
@@ -55,7 +57,7 @@ enum ba_precond { BA_PRECOND_JACOBI = 0, BA_PRECOND_SCHUR_JACOBI = 1, BA_PRECOND
 typedef struct ba_options {
   int32_t loss;            /* ba_loss */
   int32_t max_iters;       /* LM iterations (accepted + rejected) */
-  double f_scale;          /* Huber threshold in pixels */
+  double f_scale;          /* the loss's soft threshold in pixels (scipy f_scale) */
   double ftol;             /* stop when cost decrease <= ftol * cost (on an accepted step) */
   double xtol;             /* stop when |step| <= xtol * (xtol + |x|) */
   double gtol;             /* stop when max |gradient| <= gtol */
