@@ -138,10 +138,13 @@ def from_pinhole(prob: BAProblem) -> BALProblem:
     return BALProblem(cams, prob.pts.copy(), prob.cam_idx.copy(), prob.pt_idx.copy(), uv).validate()
 
 
-def solve(prob: BALProblem, device=0, fixed_cam=-1, **options):
+def solve(prob: BALProblem, device=0, fixed_cam=-1, hold_intrinsics=False, held_cameras=None, held_points=None, **options):
     """Adjust a BAL problem on the GPU (``ba_solve_bal``: poses, points AND f / k1 / k2 per camera).  Returns
-    ``(BALProblem with the adjusted parameters, summary dict)``; options as ``hip_backend.Solver.solve``."""
+    ``(BALProblem with the adjusted parameters, summary dict)``; options as ``hip_backend.Solver.solve``.
+    hold_intrinsics: keep every camera's f, k1, k2 (calibrated cameras); held_cameras / held_points: parameters kept
+    constant, in the forms of ``hip_backend.Solver.set_held`` (a (Nc, 9) bool array names single BAL parameters)."""
     from . import hip_backend
     with hip_backend.Solver(device) as s:
-        summary, cams, pts = s.solve_bal(prob, fixed_cam=fixed_cam, **options)
+        summary, cams, pts = s.solve_bal(prob, fixed_cam=fixed_cam, hold_intrinsics=hold_intrinsics,
+                                         held_cameras=held_cameras, held_points=held_points, **options)
     return BALProblem(cams, pts, prob.cam_idx.copy(), prob.pt_idx.copy(), prob.uv.copy()), summary

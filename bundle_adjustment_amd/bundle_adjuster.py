@@ -39,12 +39,17 @@ from .rotations import matrices_to_rvecs
 
 
 class BundleAdjuster:
-    def __init__(self, camera_matrix, window_size=5, *, device_id=0, loss='huber', f_scale=1.0, ftol=1e-5,
+    def __init__(self, camera_matrix, window_size=5, *, fixed_keyframes=1, device_id=0, loss='huber', f_scale=1.0, ftol=1e-5,
                  xtol=1e-5, gtol=1e-8, max_iters=50, pcg_tol=0.1, pcg_max_iters=200, pcg_model_tol=0.0, preconditioner='schur_jacobi',
                  jacobian='f64', comm=None, sparsity_plot_hook=None, verbose=0, reuse_window=True, metrics_path=None,
                  inplace_writeback=False, reuse_min_obs=20000):
         self.camera_matrix = camera_matrix
         self.window_size = window_size
+        # the first fixed_keyframes keyframes of the window are held (1: the reference's rule, src/bundle_adjuster.py:141-143:
+        # the first one is the problem's fixed camera; the others are held through ba_set_held and never written back)
+        if int(fixed_keyframes) != fixed_keyframes or fixed_keyframes < 1:
+            raise ValueError("fixed_keyframes must be an integer >= 1")
+        self.fixed_keyframes = int(fixed_keyframes)
         self.device_id = device_id
         hip_backend.loss_code(loss)            # an unknown loss name fails here, not at the first run()
         self.solver_options = dict(loss=loss, f_scale=f_scale, ftol=ftol, xtol=xtol, gtol=gtol, max_iters=max_iters,
@@ -174,6 +179,12 @@ class BundleAdjuster:
         for i in todo:
             map_points[int(ids[i])].position = views[i]
 
+    def _hold_keyframes(self, solver, n_cams):
+        """Cameras 1 .. fixed_keyframes-1 of a freshly uploaded window are held (camera 0 is the problem's fixed camera).
+        The mask stays with the solver while the window's structure is reused (set_params keeps it)."""
+        if self.fixed_keyframes > 1:
+            solver.set_held(cams=np.arange(n_cams) < self.fixed_keyframes)
+
     # -- the solve step -------------------------------------------------------------------
     def run(self, gmap: Map):
         """Sliding-window / global bundle adjustment, ``src/bundle_adjuster.py:122-193``."""
@@ -184,7 +195,8 @@ class BundleAdjuster:
             return
         local_kf_ids = all_kf_ids[-(self.window_size + 1):-1]      # newest keyframe excluded (:139)
         fixed_kf_id = local_kf_ids[0]
-        adjustable_kf_ids = local_kf_ids[1:]
+        k_held = self.fixed_keyframes
+        adjustable_kf_ids = local_kf_ids[k_held:]
         if not adjustable_kf_ids:
             print("    -> LBA Skipped: No adjustable keyframes.")
             return
@@ -218,10 +230,12 @@ class BundleAdjuster:
             else:
                 shard, _ = extract_shard(prob, p_begin, p_end)
                 solver.set_problem(shard)
+                self._hold_keyframes(solver, prob.n_cams)
         elif same_structure:
             solver.set_params(prob.cams, prob.pts)
         else:
             solver.set_problem(prob)
+            self._hold_keyframes(solver, prob.n_cams)
         self._uploaded_token = token
         summary = solver.solve(**self.solver_options)          # costs / verdicts are global on every rank
         self.last_summary = summary
@@ -236,8 +250,8 @@ class BundleAdjuster:
         if world > 1:
             pts = solver.allgather_points(p_begin, prob.n_pts)
         R = solver.get_rotations()
-        x = np.concatenate([cams[1:, :3].ravel(), cams[1:, 3:].ravel(), pts.ravel()])
-        self._update_map(gmap, x, adjustable_kf_ids, local_map_point_ids, rotations=R[1:])
+        x = np.concatenate([cams[k_held:, :3].ravel(), cams[k_held:, 3:].ravel(), pts.ravel()])
+        self._update_map(gmap, x, adjustable_kf_ids, local_map_point_ids, rotations=R[k_held:])
 
         improvement = 100.0 * (initial_cost - final_cost) / (initial_cost + 1e-8)
         print(f"    -> LBA Complete. Initial Cost: {initial_cost:.2f}, Final Cost: {final_cost:.2f}, "

@@ -165,6 +165,17 @@ struct ba_handle {
   double lin_fscale = 1.0;
   int Nc = 0, Np = 0, Nobs = 0, fixed = -1;
   double K4[4] = {1, 1, 0, 0};
+  // held parameters (ba_set_held): camera bit sets in camera order, point flags in point-slot order; the kernels get null
+  // pointers while nothing is held.  held_x2: sum of the held points' |X|^2 at the current parameters -- constant, since a
+  // held point never moves, and taken off the point share of |x| in the xtol test.  Host copies in the caller's orders.
+  DBuf<unsigned short> cam_held;
+  DBuf<unsigned char> pt_held, pt_held_in;
+  bool any_cam_held = false, any_pt_held = false;
+  unsigned cam_held_or = 0;        // OR of every camera's bits (pinhole solves refuse bits 6-8)
+  std::vector<unsigned short> h_cam_held;
+  std::vector<unsigned char> h_pt_held;
+  double held_x2 = 0.0;
+  DBuf<double> held_red;           // multi-rank: held_x2 summed over the shards (one all-reduce per solve)
   // observation lists (camera order, point order)
   DBuf<int> offk, c_pt, c_orig, pt_off, p_cam, slot, long_pts;
   DBuf<int> c_ptf[2], p_camf[2];  // index streams with the "weights are not (1, 1)" flag (robust loss; c_ptf pairs with c_w, p_camf with p_w)
@@ -1009,6 +1020,22 @@ static int set_problem_device(ba_handle* h, int Nc, int Np, int No, const int32_
   return BA_OK;
 }
 
+static void clear_held(ba_handle* h) {
+  h->any_cam_held = h->any_pt_held = false;
+  h->cam_held_or = 0;
+  h->h_cam_held.clear();
+  h->h_pt_held.clear();
+  h->held_x2 = 0.0;
+}
+// sum of the held points' |X|^2 (caller's point order), summed in point order
+static double held_points_x2(const ba_handle* h, const double* pts) {
+  double s = 0.0;
+  if (!h->any_pt_held) return s;
+  for (int p = 0; p < h->Np; ++p)
+    if (h->h_pt_held[p]) s += pts[3 * (size_t)p] * pts[3 * (size_t)p] + pts[3 * (size_t)p + 1] * pts[3 * (size_t)p + 1] +
+                              pts[3 * (size_t)p + 2] * pts[3 * (size_t)p + 2];
+  return s;
+}
 extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64_t n_obs, const int32_t* cam_idx,
                               const int32_t* pt_idx_in, const double* uv, const double K4[4], int32_t fixed_cam) {
   const int32_t* pt_idx = pt_idx_in;
@@ -1026,6 +1053,7 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
   if (n_obs > 0 && (!cam_idx || !pt_idx || !uv)) return fail(BA_ERR_INVALID, "null observation arrays");
   if (!K4) return fail(BA_ERR_INVALID, "null intrinsics");
   if (fixed_cam < -1 || fixed_cam >= n_cams) return fail(BA_ERR_INVALID, "fixed_cam %d out of range", fixed_cam);
+  clear_held(h);                     // a new problem starts with nothing held beyond its fixed camera
   {   // index ranges, before anything is touched (a rejected call keeps the previous problem): branch-free sweep first
     int ok = 1;
     for (int64_t i = 0; i < n_obs; ++i)
@@ -1574,6 +1602,7 @@ extern "C" int ba_set_params(ba_handle* h, const double* cams, const double* pts
     if (pb) memcpy(h->h_par + cb, pts, pb);
     cams_src = (const double*)h->h_par; pts_src = (const double*)(h->h_par + cb);
   }
+  h->held_x2 = held_points_x2(h, pts);
   HIPCHECK(hipMemcpyAsync(h->cams[0].p, cams_src, cb, hipMemcpyHostToDevice, h->stream));
   if (h->Np > 0) {
     HIPCHECK(hipMemcpyAsync(h->stage.p, pts_src, pb, hipMemcpyHostToDevice, h->stream));
@@ -1612,6 +1641,47 @@ extern "C" int ba_get_params(ba_handle* h, double* cams, double* pts) {
     if (cb) memcpy(cams, h->h_par, cb);
     if (pb) memcpy(pts, h->h_par + cb, pb);
   }
+  return BA_OK;
+}
+
+// Held parameters: validated, kept on the host (caller's orders) and uploaded in the problem's orders (point flags through
+// the point -> slot permutation of ba_set_problem).  NULL / all-zero arrays hold nothing.
+extern "C" int ba_set_held(ba_handle* h, const uint16_t* cam_held, const uint8_t* pt_held) {
+  if (!h) return fail(BA_ERR_INVALID, "null handle");
+  if (!h->have_problem) return fail(BA_ERR_STATE, "ba_set_problem has not been called");
+  unsigned bits = 0;
+  bool any_c = false, any_p = false;
+  if (cam_held)
+    for (int c = 0; c < h->Nc; ++c) { bits |= cam_held[c]; any_c |= cam_held[c] != 0; }
+  if (bits & ~0x1ffu) return fail(BA_ERR_INVALID, "camera mask bits beyond bit 8 (the 9-parameter BAL block)");
+  if (pt_held)
+    for (int p = 0; p < h->Np; ++p) any_p |= pt_held[p] != 0;
+  if (set_device(h)) return BA_ERR_HIP;
+  clear_held(h);
+  if (any_c) {
+    h->h_cam_held.assign(cam_held, cam_held + h->Nc);
+    HIPCHECK(h->cam_held.alloc((size_t)h->Nc));
+    HIPCHECK(hipMemcpyAsync(h->cam_held.p, h->h_cam_held.data(), (size_t)h->Nc * sizeof(unsigned short), hipMemcpyHostToDevice, h->stream));
+    h->cam_held_or = bits;
+    h->any_cam_held = true;
+  }
+  if (any_p) {
+    h->h_pt_held.resize((size_t)h->Np);
+    for (int p = 0; p < h->Np; ++p) h->h_pt_held[p] = pt_held[p] ? 1 : 0;
+    HIPCHECK(h->pt_held.alloc((size_t)h->Np));
+    HIPCHECK(h->pt_held_in.alloc((size_t)h->Np));
+    HIPCHECK(hipMemcpyAsync(h->pt_held_in.p, h->h_pt_held.data(), (size_t)h->Np, hipMemcpyHostToDevice, h->stream));
+    BA_LAUNCH(k_scatter_flags, dim3((h->Np + 255) / 256), dim3(256), 0, h->stream, (const unsigned char*)h->pt_held_in.p, h->slot.p,
+              h->Np, h->pt_held.p);
+    h->any_pt_held = true;
+  }
+  BA_SYNC(h);
+  if (any_p && h->have_params) {                 // the held share of |x| at the current points
+    std::vector<double> pts(3 * (size_t)h->Np);
+    if (int rc = ba_get_params(h, nullptr, pts.data())) { clear_held(h); return rc; }
+    h->held_x2 = held_points_x2(h, pts.data());
+  }
+  h->linearized = false;
   return BA_OK;
 }
 
@@ -1721,6 +1791,8 @@ static int wait_flag(ba_handle* h, int idx, long long target) {
   std::atomic_thread_fence(std::memory_order_acquire);
   return BA_OK;
 }
+static const unsigned short* cam_held_ptr(const ba_handle* h) { return h->any_cam_held ? h->cam_held.p : nullptr; }
+static const unsigned char* pt_held_ptr(const ba_handle* h) { return h->any_pt_held ? h->pt_held.p : nullptr; }
 // camera half of the linearisation at parameter set `which`, into buffer set `buf`
 // cost: also the cost partials at that parameter set (partR) -- the pass then doubles as the trial-cost evaluation
 template <class CM>
@@ -1741,7 +1813,7 @@ static void launch_lin_cam(ba_handle* h, int which, int buf, ba_loss loss, doubl
 static void launch_lin_finalize(ba_handle* h) {
   Scope sc(h, BA_K_MISC);
 #define CALL_T(CM) BA_LAUNCH(k_lin_finalize<CM::NB>, dim3(h->nblkV), dim3(VEC_BLOCK), 0, h->stream, partL_of(h, h->lb), \
-                             nparts_of(h), h->cs[h->cur].p, h->Nc, h->fixed, h->HccBc.p, bc_ptr(h))
+                             nparts_of(h), h->cs[h->cur].p, h->Nc, h->fixed, h->HccBc.p, bc_ptr(h), cam_held_ptr(h))
   BA_BY_MODEL(CALL_T);
 #undef CALL_T
 }
@@ -1795,12 +1867,17 @@ static void launch_lin_pt(ba_handle* h, int w, int pbuf, ba_loss loss, double fs
 #define CALL_T(CM) launch_lin_pt_t<CM>(h, w, pbuf, loss, fscale, lambda, lam_dev, sa)
   BA_BY_MODEL(CALL_T);
 #undef CALL_T
+  // held points: their blocks and inverses zeroed, the gtol maxima redone without them (the point pass itself is not
+  // told about held points: its observation loop and registers stay those of an unmasked solve)
+  if (h->any_pt_held)
+    BA_LAUNCH(k_held_points, dim3(h->nblkP + h->nblkL), dim3(256), 0, h->stream, (const unsigned char*)h->pt_held.p, h->Np,
+              h->Hpp[pbuf].p, h->bp[pbuf].p, h->Hppinv[pbuf].p, h->y0[pbuf].p, h->ptab[w].p, h->partG[pbuf].p);
 }
 static void launch_point_invert(ba_handle* h, double lambda) {
   if (h->Np == 0) return;
   Scope sc(h, BA_K_POINT_INVERT);
   BA_LAUNCH(k_point_invert, dim3((h->Np + 255) / 256), dim3(256), 0, h->stream, h->Hpp[h->pb].p, h->bp[h->pb].p, lambda,
-                     h->Np, h->Hppinv[h->pb].p, h->y0[h->pb].p, h->ptab[h->cur].p);
+                     h->Np, h->Hppinv[h->pb].p, h->y0[h->pb].p, h->ptab[h->cur].p, pt_held_ptr(h));
 }
 // part6 buffer: [u.y word, pad | NPART x Nc x NB partial sums]; the u.y word sits in FRONT of partition 0 so that a
 // multi-rank job all-reduces it together with the folded partition (one contiguous message)
@@ -1971,7 +2048,8 @@ static void launch_pcg_setup(ba_handle* h, double lambda, int precond, bool fina
   Scope sc(h, BA_K_PCG_UPDATE);
 #define SU_ARGS partL_of(h, h->lb), h->HccBc.p, bc_ptr(h), sys_p6(h), sys_E(h), nparts_of(h), h->cs[h->cur].p, lambda,           \
                 precond, h->Nc, h->fixed, h->Hccd.p, h->Minv.p, h->gvec.p, h->x.p, h->r.p, h->p.p, h->s.p,     \
-                h->z.p, h->camA[h->cur].p, h->partV.p, h->st.p, h->partGc.p, (h->two_level ? h->coarse_rc.p : (double*)nullptr), h->vx.p
+                h->z.p, h->camA[h->cur].p, h->partV.p, h->st.p, h->partGc.p, (h->two_level ? h->coarse_rc.p : (double*)nullptr), h->vx.p, \
+                cam_held_ptr(h)
 #define CALL_T(CM)                                                                                               \
   do {                                                                                                           \
     if (finalize) BA_LAUNCH((k_pcg_setup<CM, true>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, SU_ARGS);    \
@@ -2041,6 +2119,7 @@ extern "C" int ba_residuals_bal(ba_handle* h, const double* intr, int32_t loss, 
 extern "C" int ba_linearize(ba_handle* h, int32_t loss, double f_scale, double* Hcc, double* bc, double* Hpp, double* bp) {
   if (!h) return fail(BA_ERR_INVALID, "null handle");
   if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
+  if (h->cam_held_or & ~0x3fu) return fail(BA_ERR_INVALID, "camera mask bits 6-8 (f, k1, k2) need the BAL camera model");
   if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
   if (!(f_scale > 0)) return fail(BA_ERR_INVALID, "f_scale must be positive");
   if (set_device(h)) return BA_ERR_HIP;
@@ -2135,7 +2214,7 @@ extern "C" int ba_schur_apply(ba_handle* h, double lambda, const double* v, doub
   {
     Scope sc(h, BA_K_MISC);
     BA_LAUNCH(k_vtil, dim3((h->Nc + 63) / 64), dim3(64), 0, h->stream, h->vin.p, h->cs[h->cur].p, h->Nc,
-                       h->fixed, h->camA[h->cur].p);
+                       h->fixed, h->camA[h->cur].p, cam_held_ptr(h));
     BA_LAUNCH(k_pcg_reset, dim3(1), dim3(64), 0, h->stream, h->st.p, h->partV.p, nbv(h));
   }
   launch_pt_schur(h, h->lin_loss != BA_LOSS_LINEAR, 0, 0, -1.0, 1 << 30);        // y = Hppinv W^T v into the point table
@@ -2144,7 +2223,7 @@ extern "C" int ba_schur_apply(ba_handle* h, double lambda, const double* v, doub
   {
     Scope sc(h, BA_K_MISC);
     BA_LAUNCH(k_schur_combine, dim3((h->Nc + 63) / 64), dim3(64), 0, h->stream, h->Hccd.p, h->vin.p, p6_ptr(h),
-                       nparts_of(h), h->cs[h->cur].p, h->Nc, h->fixed, h->z.p);
+                       nparts_of(h), h->cs[h->cur].p, h->Nc, h->fixed, h->z.p, cam_held_ptr(h));
   }
   HIPCHECK(hipMemcpyAsync(out, h->z.p, 6 * (size_t)h->Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   BA_SYNC(h);
@@ -2242,6 +2321,8 @@ static int small_solve(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   HIPCHECK(h->small_gS.alloc((size_t)SMALL_WAVES * SMALL_TILES * 256 + 16));        // + 16 words of diagnostic stamps
   A.gS = h->small_gS.p;
   A.n_cams = h->Nc; A.n_pts = h->Np; A.fixed_cam = h->fixed; A.loss = opts->loss;
+  for (int c = 0; c < 8; ++c) A.cam_held[c] = (h->any_cam_held && c < h->Nc) ? h->h_cam_held[c] : 0;
+  A.pt_held = pt_held_ptr(h);
   A.fx = h->K4[0]; A.fy = h->K4[1]; A.cx = h->K4[2]; A.cy = h->K4[3]; A.hub_c = opts->f_scale;
   A.max_iters = opts->max_iters; A.ftol = opts->ftol; A.xtol = opts->xtol; A.gtol = opts->gtol; A.lambda0 = opts->initial_lambda;
   A.cur = h->cur;
@@ -2413,6 +2494,21 @@ extern "C" int ba_solve_bal(ba_handle* h, double* intr, const ba_options* opts, 
   return rc;
 }
 
+static int64_t held_params(const ba_handle* h, int nb) {       // held scalar parameters, the fixed camera's whole block included
+  const unsigned full = (1u << nb) - 1;
+  int64_t n = 0;
+  for (int c = 0; c < h->Nc; ++c) {
+    const unsigned m = ((h->any_cam_held ? h->h_cam_held[c] : 0u) | (c == h->fixed ? full : 0u)) & full;
+    n += __builtin_popcount(m);
+  }
+  if (h->any_pt_held)
+    for (int p = 0; p < h->Np; ++p) n += 3 * h->h_pt_held[p];
+  return n;
+}
+static bool all_held(const ba_handle* h) {
+  const int nb = h->model ? BalCam::NB : Pinhole::NB;
+  return held_params(h, nb) == (int64_t)nb * h->Nc + 3 * (int64_t)h->Np;
+}
 static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
   if (!loss_valid(opts->loss)) return fail(BA_ERR_INVALID, "unknown loss %d", opts->loss);
@@ -2424,9 +2520,20 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   if (!(opts->pcg_model_tol >= 0.0 || opts->pcg_model_tol == -1.0) || opts->pcg_model_min_iters < 0)
     return fail(BA_ERR_INVALID, "bad pcg_model_tol (>= 0, or -1 = automatic) / pcg_model_min_iters");
   if (opts->precond_lag < 0) return fail(BA_ERR_INVALID, "precond_lag must not be negative");
+  if (h->model == 0 && (h->cam_held_or & ~0x3fu))
+    return fail(BA_ERR_INVALID, "camera mask bits 6-8 (f, k1, k2) need the BAL camera model");
+  if (h->model == 0 && opts->preconditioner == BA_PRECOND_TWO_LEVEL && (h->any_cam_held || h->any_pt_held))
+    return fail(BA_ERR_STATE, "the two-level preconditioner does not support held parameters (ba_set_held)");
   if (set_device(h)) return BA_ERR_HIP;
   memset(sum, 0, sizeof *sum);
   h->trace.clear();
+  // single rank, every parameter held: nothing to adjust
+  if (!h->multi && all_held(h)) {
+    double sse = 0, cost = 0;
+    if (int rc = eval_cost(h, h->cur, (ba_loss)opts->loss, opts->f_scale, &sse, &cost)) return rc;
+    sum->initial_sse = sum->final_sse = sse; sum->initial_cost = sum->final_cost = cost; sum->final_lambda = opts->initial_lambda;
+    return BA_OK;
+  }
   // window-sized problems: one launch, exact reduced solve -- no PCG, so preconditioner / jacobian_precision (validated
   // above) have nothing to act on, and no per-solve mode of the multi-kernel path is left switched on behind it
   h->jac_f32 = false;
@@ -2467,6 +2574,29 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     return BA_OK;
   }
   const bool debug_poison = getenv("BA_DEBUG_POISON_TRIAL") != nullptr;     // tests: every trial cost comes out NaN
+  // the held parameters' share of |x|^2 (xtol test): the held points' over every shard of a multi-rank job, the held camera
+  // parameters' read from the current cameras (the camera update adds their zero step and keeps their share in its sum)
+  double held_x2 = h->held_x2, held_cam_x2 = 0.0;
+  if (h->any_cam_held) {
+    const int nb = nb_of(h);
+    std::vector<double> cams(6 * (size_t)Nc), intr(nb > 6 ? 3 * (size_t)Nc : 0);
+    HIPCHECK(hipMemcpyAsync(cams.data(), h->cams[h->cur].p, cams.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (nb > 6) HIPCHECK(hipMemcpyAsync(intr.data(), h->intr[h->cur].p, intr.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    BA_SYNC(h);
+    for (int c = 0; c < Nc; ++c)
+      for (int q = 0; q < nb; ++q)
+        if ((h->h_cam_held[c] >> q) & 1u) {
+          const double v = q < 6 ? cams[6 * (size_t)c + q] : intr[3 * (size_t)c + q - 6];
+          held_cam_x2 += v * v;
+        }
+  }
+  if (h->multi) {
+    HIPCHECK(h->held_red.alloc(1));
+    HIPCHECK(hipMemcpyAsync(h->held_red.p, &held_x2, sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (int rc = allreduce(h, h->held_red.p, 1)) return rc;
+    HIPCHECK(hipMemcpyAsync(&held_x2, h->held_red.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    BA_SYNC(h);
+  }
   // BA_RIDERS: bit 0 = the camera update rides along the back substitution, bit 1 = the scalar fold + verdict rides along
   // the speculated point half (ba_kernels.hpp, "riders"), bit 2 = the PCG probe that finds PCG finished goes on as the back
   // substitution in the same launch (needs bit 0); BA_NO_RIDERS / BA_RIDERS=0: launches of their own (tuning, tests)
@@ -2592,7 +2722,7 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
 #define STEP_ARGS kk, (const double*)p6_ptr(h), step_parts, (const double*)uy_ptr(h), h->Hccd.p, h->Minv.p, h->cs[h->cur].p, Nc, h->fixed, tol2,       \
                   opts->pcg_min_iters, h->x.p, h->r.p, h->p.p, h->s.p, h->z.p, h->camA[h->cur].p, h->partV.p, nbv(h), h->st.p, \
                   h->d_flags, base, (const double*)h->verdict.p
-#define STEP_TAIL h->vx.p, model_tol, opts->pcg_model_min_iters, ipc, h->d_flags + 6
+#define STEP_TAIL h->vx.p, model_tol, opts->pcg_model_min_iters, ipc, h->d_flags + 6, cam_held_ptr(h)
       if (h->two_level) {
         BA_LAUNCH((k_pcg_step<Pinhole, true>), dim3(h->nblkV), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS, h->coarse_rc.p, STEP_TAIL);
         BA_LAUNCH(k_pcg_coarse, dim3(h->n_agg), dim3(VEC_BLOCK), 0, h->stream, kk, (const double*)h->coarseEinv.p,
@@ -2698,7 +2828,10 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     sum->seconds_pcg += t2 - t1;
     const double* S = h->h_scal;
     const double sse_new = S[S_SSE], cost_new = 0.5 * S[S_RHO];
-    const double step2 = S[S_PT_DD] + S[S_CAM_DD], x2 = S[S_PT_XX] + S[S_CAM_XX];
+    const double step2 = S[S_PT_DD] + S[S_CAM_DD];
+    const double x2 = (held_x2 != 0.0 || held_cam_x2 != 0.0)
+                          ? std::max(0.0, S[S_PT_XX] - held_x2) + std::max(0.0, S[S_CAM_XX] - held_cam_x2)
+                          : S[S_PT_XX] + S[S_CAM_XX];
     const double rho = S[S_GAIN];               // gain ratio and next damping: decided on the device (lm_decide)
     ++it;
     if (opts->verbose)
@@ -2752,6 +2885,10 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
 // ------------------------------------------------------------------ counters, test hooks
 extern "C" int ba_get_stat(ba_handle* h, int32_t which, int64_t* value) {
   if (!h || !value || which < 0 || which >= BA_STAT_COUNT) return fail(BA_ERR_INVALID, "bad argument");
+  if (which == BA_STAT_HELD_PARAMS) {
+    *value = h->have_problem ? held_params(h, (h->cam_held_or & ~0x3fu) ? BalCam::NB : Pinhole::NB) : 0;
+    return BA_OK;
+  }
   *value = which == BA_STAT_PIXELS_F32 ? (int64_t)(h->have_problem && h->uv_f32) : (int64_t)h->stats[which];
   return BA_OK;
 }

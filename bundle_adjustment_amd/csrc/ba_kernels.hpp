@@ -240,6 +240,11 @@ __global__ void k_pack_points(const double* __restrict__ pts, const int* __restr
   o[0] = pts[3 * (size_t)p]; o[1] = pts[3 * (size_t)p + 1]; o[2] = pts[3 * (size_t)p + 2];
   o[3] = 0; o[4] = 0; o[5] = 0; o[6] = 0; o[7] = 0;
 }
+// flags in the caller's point order -> point slots (ba_set_held)
+__global__ void k_scatter_flags(const unsigned char* __restrict__ in, const int* __restrict__ slot, int n, unsigned char* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[slot[i]] = in[i];
+}
 __global__ void k_unpack_points(const double* __restrict__ ptab, const int* __restrict__ slot, int n_pts,
                                 double* __restrict__ pts) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -397,12 +402,25 @@ __device__ inline void m_congruence(const double* __restrict__ M, double (&A)[NB
   }
 }
 
+// Held parameters (ba_set_held): per camera a bit set over its NB block columns (the caller's coordinates, after M), per
+// point one flag.  A held camera parameter has zero rows and columns in Hcc | bc, identity ones in every damped block, and
+// zero entries in every PCG vector and step; a held point has Hpp = bp = 0 and Hpp^-1 := 0, so that it neither moves nor
+// couples into S.  The observation loops are untouched: they only ever see camera vectors whose held entries are 0.
+// cam_held == null: nothing held beyond fixed_cam.
+__device__ inline unsigned cam_held_bits(const unsigned short* __restrict__ cam_held, int c) { return cam_held ? cam_held[c] : 0u; }
+template <int NB>
+__device__ inline void held_identity(unsigned held, double* __restrict__ H) {   // held rows / columns of an NB block -> identity
+  for (int i = 0; i < NB; ++i)
+    for (int j = i; j < NB; ++j)
+      if (((held >> i) | (held >> j)) & 1u) H[UT(NB, i, j)] = (i == j) ? 1.0 : 0.0;
+}
+
 // Combine the NPART partial sums of k_camrow_linearize (fixed order), apply M:
-//   Hcc[c] (NH) = Jc^T w Jc,  bc[c] (NB) = Jc^T w r  (zero for the fixed camera).
+//   Hcc[c] (NH) = Jc^T w Jc,  bc[c] (NB) = Jc^T w r  (zero for the fixed camera; zero rows / columns for held parameters).
 // a[NH + NB] = the camera's pre-M sums (NH of Jc^T w Jc, upper triangle; NB of Jc^T w r), M from its state
 template <int NB>
 __device__ inline void lin_finalize_sums(const double* __restrict__ a, const double* __restrict__ M, bool fixed,
-                                         double* __restrict__ H, double* __restrict__ b) {
+                                         double* __restrict__ H, double* __restrict__ b, unsigned held = 0u) {
   constexpr int NH = NB * (NB + 1) / 2;
   if (fixed) {
     for (int q = 0; q < NH; ++q) H[q] = 0.0;
@@ -417,10 +435,17 @@ __device__ inline void lin_finalize_sums(const double* __restrict__ a, const dou
   b[1] = M[1] * a[NH] + M[4] * a[NH + 1] + M[7] * a[NH + 2];
   b[2] = M[2] * a[NH] + M[5] * a[NH + 1] + M[8] * a[NH + 2];
   for (int q = 3; q < NB; ++q) b[q] = a[NH + q];
+  if (held) {
+    for (int i = 0; i < NB; ++i) {
+      if ((held >> i) & 1u) b[i] = 0.0;
+      for (int j = i; j < NB; ++j)
+        if (((held >> i) | (held >> j)) & 1u) H[UT(NB, i, j)] = 0.0;
+    }
+  }
 }
 template <int NB>
 __device__ inline void lin_finalize_camera(const double* __restrict__ partL, int nparts, const double* __restrict__ cam, int n_cams,
-                                           int c, int fixed_cam, double* __restrict__ H, double* __restrict__ b) {
+                                           int c, int fixed_cam, double* __restrict__ H, double* __restrict__ b, unsigned held) {
   constexpr int NL = NB * (NB + 1) / 2 + NB;
   double a[NL];
   for (int q = 0; q < NL; ++q) a[q] = 0.0;
@@ -430,16 +455,17 @@ __device__ inline void lin_finalize_camera(const double* __restrict__ partL, int
       for (int q = 0; q < NL; ++q) a[q] += src[q];
     }
   }
-  lin_finalize_sums<NB>(a, cam + 12, c == fixed_cam, H, b);
+  lin_finalize_sums<NB>(a, cam + 12, c == fixed_cam, H, b, held);
 }
 // stand-alone form (multi-rank jobs all-reduce Hcc|bc between this and k_pcg_setup; test hook)
 template <int NB>
 __global__ void __launch_bounds__(VEC_BLOCK)
 k_lin_finalize(const double* __restrict__ partL, int nparts, const double* __restrict__ cs, int n_cams, int fixed_cam,
-               double* __restrict__ Hcc, double* __restrict__ bc) {
+               double* __restrict__ Hcc, double* __restrict__ bc, const unsigned short* __restrict__ cam_held) {
   const int c = vec_camera(n_cams);
   if (c >= n_cams) return;
-  lin_finalize_camera<NB>(partL, nparts, cs + CS * c, n_cams, c, fixed_cam, Hcc + (NB * (NB + 1) / 2) * (size_t)c, bc + NB * (size_t)c);
+  lin_finalize_camera<NB>(partL, nparts, cs + CS * c, n_cams, c, fixed_cam, Hcc + (NB * (NB + 1) / 2) * (size_t)c, bc + NB * (size_t)c,
+                          cam_held_bits(cam_held, c));
 }
 
 // K4b: camera pass of the Schur product, pre-M:  part6[(k*Nc + c)*6 + ..] = sum Jc^T w (Jp y_p)
@@ -1124,7 +1150,8 @@ k_pt_linearize_both(BA_LIN_PARAMS, PtWork wk, int nblk_short, PtWork wl, BA_LIN_
 // slot of the point table, where the right-hand-side camera pass reads it).
 __global__ void __launch_bounds__(256)
 k_point_invert(const double* __restrict__ Hpp, const double* __restrict__ bp, double lambda, int n_pts,
-               double* __restrict__ Hppinv, double* __restrict__ y0, double* __restrict__ ptab) {
+               double* __restrict__ Hppinv, double* __restrict__ y0, double* __restrict__ ptab,
+               const unsigned char* __restrict__ pt_held) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= n_pts) return;
   double h[6], inv[6];
@@ -1134,6 +1161,10 @@ k_point_invert(const double* __restrict__ Hpp, const double* __restrict__ bp, do
   h[3] += lambda * fmax(h[3], DIAG_FLOOR);
   h[5] += lambda * fmax(h[5], DIAG_FLOOR);
   sym3_inverse(h, inv);
+  if (pt_held && pt_held[p]) {                     // held point: Hpp^-1 := 0 (its Hpp and bp are 0 already)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) inv[k] = 0.0;
+  }
 #pragma unroll
   for (int k = 0; k < 6; ++k) Hppinv[6 * (size_t)p + k] = inv[k];
   const double b[3] = {bp[3 * (size_t)p], bp[3 * (size_t)p + 1], bp[3 * (size_t)p + 2]};
@@ -1142,6 +1173,28 @@ k_point_invert(const double* __restrict__ Hpp, const double* __restrict__ bp, do
   y0[3 * (size_t)p] = y[0]; y0[3 * (size_t)p + 1] = y[1]; y0[3 * (size_t)p + 2] = y[2];
   double* o = ptab + PT * (size_t)p + 4;
   o[0] = y[0]; o[1] = y[1]; o[2] = y[2];
+}
+
+// Held points (ba_set_held) after a point half of the linearisation, which knows nothing of them: Hpp = bp = 0,
+// Hpp^-1 := 0, y0 = 0 (also in the point table's y slot), and the gtol maxima redone without them -- one workgroup per
+// partG word (the linearisation's count of them), grid-stride over every point slot.  Launched only while points are held.
+__global__ void __launch_bounds__(256)
+k_held_points(const unsigned char* __restrict__ pt_held, int n_pts, double* __restrict__ Hpp, double* __restrict__ bp,
+              double* __restrict__ Hppinv, double* __restrict__ y0, double* __restrict__ ptab, double* __restrict__ partG) {
+  __shared__ double smg[4];
+  double gm = 0.0;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < n_pts; p += gridDim.x * 256) {
+    if (pt_held[p]) {
+      for (int q = 0; q < 6; ++q) { Hpp[6 * (size_t)p + q] = 0.0; Hppinv[6 * (size_t)p + q] = 0.0; }
+      for (int q = 0; q < 3; ++q) { bp[3 * (size_t)p + q] = 0.0; y0[3 * (size_t)p + q] = 0.0; ptab[PT * (size_t)p + 4 + q] = 0.0; }
+    } else {
+      for (int q = 0; q < 3; ++q) gm = nanmax(gm, fabs(bp[3 * (size_t)p + q]));
+    }
+  }
+  gm = wave_nanmax(gm);
+  if ((threadIdx.x & 63) == 0) smg[threadIdx.x >> 6] = gm;
+  __syncthreads();
+  if (threadIdx.x == 0) partG[blockIdx.x] = nanmax(nanmax(smg[0], smg[1]), nanmax(smg[2], smg[3]));
 }
 
 // K4a / K6: point pass of the Schur product.  u = sum_o Jp^T w (Jc v_c) with
@@ -1558,7 +1611,7 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
             double* __restrict__ gvec, double* __restrict__ x, double* __restrict__ r, double* __restrict__ p,
             double* __restrict__ s, double* __restrict__ z, double* __restrict__ vtil,
             double* __restrict__ partV, PcgState* __restrict__ st, double* __restrict__ partGc, double* __restrict__ rc,
-            double* __restrict__ vx) {
+            double* __restrict__ vx, const unsigned short* __restrict__ cam_held) {
   constexpr int NB = CM::NB, NH = CM::NH, NL = CM::NL, VC = CM::VC;
   // (rc != null: two-level preconditioner -- also the aggregate's restricted right-hand side; z, partV and vtil written
   // here are then the single-level ones and are redone by k_pcg_coarse once E^-1 exists)
@@ -1635,7 +1688,8 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
   if (c < n_cams) {
     const double* M = l_cs + CS * t + 12;
     const bool fixed = c == fixed_cam;
-    if (FINALIZE) lin_finalize_sums<NB>(l_a + NL * t, M, fixed, l_hcc + NH * t, l_bc + NB * t);
+    const unsigned held = cam_held_bits(cam_held, c);
+    if (FINALIZE) lin_finalize_sums<NB>(l_a + NL * t, M, fixed, l_hcc + NH * t, l_bc + NB * t, held);
     double h[NH], m[NH], inv[NH];
     for (int q = 0; q < NH; ++q) h[q] = l_hcc[NH * t + q];
     if (fixed) {
@@ -1643,6 +1697,7 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
       for (int i = 0; i < NB; ++i) h[UT(NB, i, i)] = 1.0;
     } else {
       for (int i = 0; i < NB; ++i) h[UT(NB, i, i)] += lambda * fmax(h[UT(NB, i, i)], DIAG_FLOOR);
+      if (held) held_identity<NB>(held, h);
     }
     for (int q = 0; q < NH; ++q) { l_hd[NH * t + q] = h[q]; m[q] = h[q]; }
     if (use_schur_diag == 2) {
@@ -1653,6 +1708,7 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
         for (int i = 0; i < NB; ++i) for (int j = 0; j < NB; ++j) A[i][j] = l_e[NH * t + ST(NB, i, j)];
         m_congruence<NB>(M, A);
         for (int i = 0; i < NB; ++i) for (int j = i; j < NB; ++j) m[UT(NB, i, j)] -= A[i][j];
+        if (held) held_identity<NB>(held, m);
       }
       spdN_inverse<NB>(m, inv);
       for (int q = 0; q < NH; ++q) l_mi[NH * t + q] = inv[q];
@@ -1665,7 +1721,7 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
       wy[2] = M[2] * a[0] + M[5] * a[1] + M[8] * a[2];
       for (int q = 3; q < NB; ++q) wy[q] = a[q];
     }
-    for (int q = 0; q < NB; ++q) g[q] = fixed ? 0.0 : -(l_bc[NB * t + q] - wy[q]);
+    for (int q = 0; q < NB; ++q) g[q] = (fixed || ((held >> q) & 1u)) ? 0.0 : -(l_bc[NB * t + q] - wy[q]);
     for (int q = 0; q < NB; ++q) gmc = nanmax(gmc, fabs(l_bc[NB * t + q]));     // max |bc| (gtol test)
     symN_mul<NB>(inv, g, zz);
     symN_mul<NB>(h, zz, hz);
@@ -1735,7 +1791,8 @@ k_pcg_step(int k, const double* __restrict__ part6, int nparts, const double* __
            double* __restrict__ z, double* __restrict__ vtil, double* __restrict__ partV, int nblkV,
            PcgState* __restrict__ st, long long* __restrict__ host_flag, long long flag_base,
            const double* __restrict__ verdict, double* __restrict__ rc, double* __restrict__ vx,
-           double model_tol, int model_min_iters, IpcStep ipc, long long* __restrict__ err_flag) {
+           double model_tol, int model_min_iters, IpcStep ipc, long long* __restrict__ err_flag,
+           const unsigned short* __restrict__ cam_held) {
   // ipc.on (multi-rank, device-side exchange): part6 / uy_src are this rank's own sums; the other ranks' arrive in the
   // receive buffer while the kernel runs (see "device-side all-reduce" above)
   constexpr int NB = CM::NB, NH = CM::NH, VC = CM::VC;
@@ -1870,9 +1927,10 @@ k_pcg_step(int k, const double* __restrict__ part6, int nparts, const double* __
       rr[q] = l_v[3][NB * t + q]; xx[q] = l_v[4][NB * t + q];
     }
     symN_mul<NB>(h, zz, w);
+    const unsigned held = cam_held_bits(cam_held, c);      // held rows of S: identity, so that r, z, p, s, x stay 0 there
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
-      w[q] -= wy[q];
+      w[q] = ((held >> q) & 1u) ? 0.0 : w[q] - wy[q];
       pp[q] = zz[q] + beta * pp[q];
       ss[q] = w[q] + beta * ss[q];
       xx[q] = xx[q] + alpha * pp[q];
@@ -2152,23 +2210,25 @@ __global__ void k_pcg_reset(PcgState* __restrict__ st, double* __restrict__ part
 // out = Hccd v - Wy   (test hook behind ba_schur_apply; fixed row = identity)
 __global__ void k_schur_combine(const double* __restrict__ Hccd, const double* __restrict__ v,
                                 const double* __restrict__ part6, int nparts, const double* __restrict__ cs,
-                                int n_cams, int fixed_cam, double* __restrict__ out) {
+                                int n_cams, int fixed_cam, double* __restrict__ out, const unsigned short* __restrict__ cam_held) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n_cams) return;
   double vv[6], w[6], wy[6];
   for (int q = 0; q < 6; ++q) vv[q] = v[6 * c + q];
   sym6_mul(Hccd + 21 * c, vv, w);
   combine_wy(part6, nparts, n_cams, c, cs + CS * c + 12, wy);
-  for (int q = 0; q < 6; ++q) out[6 * c + q] = (c == fixed_cam) ? vv[q] : w[q] - wy[q];
+  const unsigned held = cam_held_bits(cam_held, c);
+  for (int q = 0; q < 6; ++q) out[6 * c + q] = (c == fixed_cam || ((held >> q) & 1u)) ? vv[q] : w[q] - wy[q];
 }
 
 // vtil half of camA for an arbitrary camera vector (test hook)
 __global__ void k_vtil(const double* __restrict__ v, const double* __restrict__ cs, int n_cams, int fixed_cam,
-                       double* __restrict__ vtil) {
+                       double* __restrict__ vtil, const unsigned short* __restrict__ cam_held) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n_cams) return;
+  const unsigned held = cam_held_bits(cam_held, c);
   double d[6];
-  for (int q = 0; q < 6; ++q) d[q] = (c == fixed_cam) ? 0.0 : v[6 * c + q];
+  for (int q = 0; q < 6; ++q) d[q] = (c == fixed_cam || ((held >> q) & 1u)) ? 0.0 : v[6 * c + q];
   write_vtil(cs + CS * c + 12, d, vtil + TA * c + 12);
 }
 

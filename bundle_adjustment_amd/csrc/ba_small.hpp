@@ -63,6 +63,8 @@ struct SmallArgs {
   double* gS;                                                // [waves][SMALL_TILES][64 lanes x 4]: partial V V^T
   int Kp, Np_pad;                                            // Kp = 3 Np_pad, Np_pad a multiple of 16
   int n_cams, n_pts, fixed_cam, loss;                       // loss: ba_loss code
+  unsigned short cam_held[8];                                // held parameters per camera (ba_set_held; 0: none beyond fixed_cam)
+  const unsigned char* pt_held;                              // held points, per point slot (null: none)
   double fx, fy, cx, cy, hub_c;
   int max_iters; double ftol, xtol, gtol, lambda0;
   int cur;                                                   // which parameter set holds the start point
@@ -270,6 +272,15 @@ k_small_lm(SmallArgs A) {
         double a = 0.0;
         for (int sb = 0; sb < wpc; ++sb) a += l_wpart[c * wpc + sb][q];
         if (q < 21) l_Hcc[c][q] = a; else l_bc[c][q - 21] = a;
+        const unsigned held = A.cam_held[c];               // held parameters: zero rows / columns, zero gradient
+        if (held) {
+          if (q >= 21) { if ((held >> (q - 21)) & 1u) l_bc[c][q - 21] = 0.0; }
+          else {
+            int i = 0, r = q;                              // (i, j) of upper-triangle entry q
+            while (r >= 6 - i) { r -= 6 - i; ++i; }
+            if (((held >> i) | (held >> (i + r))) & 1u) l_Hcc[c][q] = 0.0;
+          }
+        }
       }
       __syncthreads();
       if (tid == 0) {
@@ -285,9 +296,10 @@ k_small_lm(SmallArgs A) {
     for (int p = tid; p < Np; p += SMALL_THREADS) {
       const double4 X = *(const double4*)(A.ptab[cur] + PT * (size_t)p);
       const int beg = A.pt_off[p], end = A.pt_off[p + 1];
+      const bool held = A.pt_held && A.pt_held[p];      // held point: Hpp = bp = 0, inverse (L) := 0, y0 = 0
       if (need_lin) {
         double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int j = beg; j < end; ++j) {
+        for (int j = held ? end : beg; j < end; ++j) {
           const int c = A.p_cam[j];
           const double2 uv = A.p_uv[j];
           Geom g;
@@ -319,11 +331,12 @@ k_small_lm(SmallArgs A) {
       sym3_inverse(h, hinv);
       sym3_mul(hinv, b3, y);
       // hinv = L L^T, L lower triangular: l00 | l10 l11 | l20 l21 l22
-      const double l00 = sqrt(fmax(hinv[0], 1e-300));
-      const double l10 = hinv[1] / l00, l20 = hinv[2] / l00;
-      const double l11 = sqrt(fmax(hinv[3] - l10 * l10, 1e-300));
-      const double l21 = (hinv[4] - l20 * l10) / l11;
-      const double l22 = sqrt(fmax(hinv[5] - l20 * l20 - l21 * l21, 1e-300));
+      double l00 = sqrt(fmax(hinv[0], 1e-300));
+      double l10 = hinv[1] / l00, l20 = hinv[2] / l00;
+      double l11 = sqrt(fmax(hinv[3] - l10 * l10, 1e-300));
+      double l21 = (hinv[4] - l20 * l10) / l11;
+      double l22 = sqrt(fmax(hinv[5] - l20 * l20 - l21 * l21, 1e-300));
+      if (held) { l00 = l10 = l11 = l20 = l21 = l22 = 0.0; y[0] = y[1] = y[2] = 0.0; }
       double* Lf = A.Lf + 6 * (size_t)p;
       Lf[0] = l00; Lf[1] = l10; Lf[2] = l11; Lf[3] = l20; Lf[4] = l21; Lf[5] = l22;
 #pragma unroll
@@ -399,8 +412,9 @@ k_small_lm(SmallArgs A) {
       double vv = 0.0;
 #pragma unroll
       for (int w = 0; w < SMALL_WAVES; ++w) vv += ps[(size_t)w * SMALL_TILES * 256];
+      const bool hi = (A.cam_held[ci] >> (i % 6)) & 1u, hj = j < n && ((A.cam_held[cj] >> (j % 6)) & 1u);
       if (j == n) {
-        l_g[i] = (ci == A.fixed_cam) ? 0.0 : -(l_bc[ci][i % 6] - vv);
+        l_g[i] = (ci == A.fixed_cam || hi) ? 0.0 : -(l_bc[ci][i % 6] - vv);
         continue;
       }
       double v = -vv;
@@ -410,7 +424,7 @@ k_small_lm(SmallArgs A) {
         if (a == b) d += lambda * fmax(d, DIAG_FLOOR);
         v += d;
       }
-      if (ci == A.fixed_cam || cj == A.fixed_cam) v = (i == j) ? 1.0 : 0.0;
+      if (ci == A.fixed_cam || cj == A.fixed_cam || hi || hj) v = (i == j) ? 1.0 : 0.0;
       l_S[i][j] = v;
     }
     __syncthreads();
@@ -469,13 +483,14 @@ k_small_lm(SmallArgs A) {
       const int c = tid;
       double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
       for (int q = 0; q < 6; ++q) {
-        const double d = (c == A.fixed_cam) ? 0.0 : l_dc[6 * c + q];
+        const bool hq = (A.cam_held[c] >> q) & 1u;      // held: no step, no share of |x| (the fixed camera keeps its share)
+        const double d = (c == A.fixed_cam || hq) ? 0.0 : l_dc[6 * c + q];
         const double xq = l_cam[cur][c][q];
         l_cam[tr][c][q] = xq + d;
         a0 += l_bc[c][q] * d;
         a1 += fmax(l_Hcc[c][U6(q, q)], DIAG_FLOOR) * d * d;
         a2 += d * d;
-        a3 += xq * xq;
+        if (!hq) a3 += xq * xq;
       }
       l_camred[c][0] = a0; l_camred[c][1] = a1; l_camred[c][2] = a2; l_camred[c][3] = a3;
       camera_state(&l_cam[tr][c][0], &l_cs[tr][c][0]);
@@ -510,7 +525,7 @@ k_small_lm(SmallArgs A) {
       ps[0] += A.bp[3 * (size_t)p] * d0 + A.bp[3 * (size_t)p + 1] * d1 + A.bp[3 * (size_t)p + 2] * d2;
       ps[1] += D0 * d0 * d0 + D1 * d1 * d1 + D2 * d2 * d2;
       ps[2] += d0 * d0 + d1 * d1 + d2 * d2;
-      ps[3] += X.x * X.x + X.y * X.y + X.z * X.z;
+      if (!(A.pt_held && A.pt_held[p])) ps[3] += X.x * X.x + X.y * X.y + X.z * X.z;
     }
     small_block_sum<4>(ps, l_red, l_tot);
     __threadfence_block();

@@ -116,6 +116,7 @@ k_small_mw(MwArgs M) {
   const int pl = tid / MW_LPP, sub = tid % MW_LPP;   // landmark of this thread inside the workgroup, lane inside the landmark
   const int p = g * MW_PTS + pl;
   const bool have_p = p < Np;
+  const bool held_p = have_p && A.pt_held && A.pt_held[p];
   // Each exchange buffer has a parity of its own: a workgroup that has passed the barrier of use u of a buffer may write
   // its slot for use u + 1 (the other half) while a slower one still reads use u; it cannot reach use u + 2 (the same
   // half again) before everybody has arrived at use u + 1, i.e. has finished reading use u.  No assumption about how the
@@ -331,6 +332,10 @@ k_small_mw(MwArgs M) {
       }
 #pragma unroll
       for (int q = 0; q < 9; ++q) a[q] = mw_allreduce8(a[q]);
+      if (held_p) {                                      // held point: Hpp = bp = 0, L := 0, y0 = 0 (no step, no coupling)
+#pragma unroll
+        for (int q = 0; q < 9; ++q) a[q] = 0.0;
+      }
 #pragma unroll
       for (int q = 0; q < 6; ++q) hp[q] = a[q];
 #pragma unroll
@@ -343,11 +348,12 @@ k_small_mw(MwArgs M) {
       h[5] += lambda * fmax(h[5], DIAG_FLOOR);
       sym3_inverse(h, hinv);
       sym3_mul(hinv, bp3, y0);
-      const double l00 = sqrt(fmax(hinv[0], 1e-300));
-      const double l10 = hinv[1] / l00, l20 = hinv[2] / l00;
-      const double l11 = sqrt(fmax(hinv[3] - l10 * l10, 1e-300));
-      const double l21 = (hinv[4] - l20 * l10) / l11;
-      const double l22 = sqrt(fmax(hinv[5] - l20 * l20 - l21 * l21, 1e-300));
+      double l00 = sqrt(fmax(hinv[0], 1e-300));
+      double l10 = hinv[1] / l00, l20 = hinv[2] / l00;
+      double l11 = sqrt(fmax(hinv[3] - l10 * l10, 1e-300));
+      double l21 = (hinv[4] - l20 * l10) / l11;
+      double l22 = sqrt(fmax(hinv[5] - l20 * l20 - l21 * l21, 1e-300));
+      if (held_p) { l00 = l10 = l11 = l20 = l21 = l22 = 0.0; y0[0] = y0[1] = y0[2] = 0.0; }
       Lf[0] = l00; Lf[1] = l10; Lf[2] = l11; Lf[3] = l20; Lf[4] = l21; Lf[5] = l22;
       if (have_p && sub == 0) {                          // z = L^T bp: row n of the image
         l_V[o0 + 16 * n] = l00 * bp3[0] + l10 * bp3[1] + l20 * bp3[2];
@@ -437,15 +443,18 @@ k_small_mw(MwArgs M) {
       const int i = l_ij[t] & 0xff, j = l_ij[t] >> 8, ci = i / 6, cj = j / 6;
       double v = l_msg[t];
       if (i == j) v += lambda * fmax(l_msg[nS + 2 * n + i], DIAG_FLOOR);
-      if (ci == A.fixed_cam || cj == A.fixed_cam) v = (i == j) ? 1.0 : 0.0;
+      // held parameters (ba_set_held): identity rows / columns as the fixed camera's
+      if (ci == A.fixed_cam || cj == A.fixed_cam || ((A.cam_held[ci] >> (i % 6)) & 1u) || ((A.cam_held[cj] >> (j % 6)) & 1u))
+        v = (i == j) ? 1.0 : 0.0;
       l_S[i][j] = v;
       l_S[j][i] = v;
     }
     if (tid < n) {
       const int i = tid, ci = i / 6;
-      l_bc[i] = l_msg[nS + n + i];
+      const bool hi = (A.cam_held[ci] >> (i % 6)) & 1u;   // held: zero gradient entry
+      l_bc[i] = hi ? 0.0 : l_msg[nS + n + i];
       l_dH[i] = l_msg[nS + 2 * n + i];
-      l_S[i][n] = (ci == A.fixed_cam) ? 0.0 : -(l_msg[nS + n + i] - l_msg[nS + i]);     // right-hand side g: the augmented column
+      l_S[i][n] = (ci == A.fixed_cam || hi) ? 0.0 : -(l_msg[nS + n + i] - l_msg[nS + i]);     // right-hand side g: the augmented column
     }
     __syncthreads();
     if (need_lin && wv == 0) {                           // max |gradient| = max(max |bp| over the workgroups, max |bc|)
@@ -513,13 +522,14 @@ k_small_mw(MwArgs M) {
       const int c = tid;
       double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
       for (int q = 0; q < 6; ++q) {
-        const double d = (c == A.fixed_cam) ? 0.0 : l_dc[6 * c + q];
+        const bool hq = (A.cam_held[c] >> q) & 1u;      // held: no step, no share of |x| (the fixed camera keeps its share)
+        const double d = (c == A.fixed_cam || hq) ? 0.0 : l_dc[6 * c + q];
         const double xq = l_cam[cur][c][q];
         l_cam[tr][c][q] = xq + d;
         a0 += l_bc[6 * c + q] * d;
         a1 += fmax(l_dH[6 * c + q], DIAG_FLOOR) * d * d;
         a2 += d * d;
-        a3 += xq * xq;
+        if (!hq) a3 += xq * xq;
       }
       l_camred[c][0] = a0; l_camred[c][1] = a1; l_camred[c][2] = a2; l_camred[c][3] = a3;
       camera_state(&l_cam[tr][c][0], &l_cs[tr][c][0]);
@@ -549,7 +559,7 @@ k_small_mw(MwArgs M) {
         ps[0] = bp3[0] * d0 + bp3[1] * d1 + bp3[2] * d2;
         ps[1] = D0 * d0 * d0 + D1 * d1 * d1 + D2 * d2 * d2;
         ps[2] = d0 * d0 + d1 * d1 + d2 * d2;
-        ps[3] = X.x * X.x + X.y * X.y + X.z * X.z;
+        ps[3] = held_p ? 0.0 : X.x * X.x + X.y * X.y + X.z * X.z;
       }
     }
     small_block_sum<4>(ps, l_red, l_sc);                 // l_sc[0 .. 3]

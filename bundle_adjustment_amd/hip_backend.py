@@ -84,6 +84,7 @@ SYMBOLS = {
     "ba_comm_unique_id": (C.c_int, [C.c_void_p]),
     "ba_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ba_set_problem": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, _IP, _IP, _DP, _DP, C.c_int32]),
+    "ba_set_held": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)]),
     "ba_set_params": (C.c_int, [C.c_void_p, _DP, _DP]),
     "ba_get_params": (C.c_int, [C.c_void_p, _DP, _DP]),
     "ba_get_rotations": (C.c_int, [C.c_void_p, _DP]),
@@ -108,7 +109,41 @@ SYMBOLS = {
 }
 # enum ba_stat (include/ba_hip.h)
 STATS = {"window_mw_launches": 0, "window_lm_launches": 1, "window_fallbacks": 2, "precond_builds": 3, "precond_reuses": 4, "banded": 5,
-         "cap_floor_raises": 6, "ipc_exchanges": 7, "pixels_f32": 8}
+         "cap_floor_raises": 6, "ipc_exchanges": 7, "pixels_f32": 8, "held_params": 9}
+
+
+def held_camera_mask(cams, n_cams, nb=6):
+    """Normalise a camera hold spec to ba_set_held's uint16 (Nc,) bit masks: a bool (Nc,) array (whole cameras: all nb
+    block parameters -- 6 for the pinhole, 9 for the BAL camera), a bool (Nc, 6) or (Nc, 9) array (one column per block parameter: rvec, t, then f, k1, k2), or an integer
+    (Nc,) array of bit masks (bits 0-8).  None -> None.  Raises ValueError on a bad shape, dtype or bit."""
+    if cams is None:
+        return None
+    a = np.asarray(cams)
+    if a.dtype == np.bool_:
+        if a.shape == (n_cams,):
+            return np.where(a, (1 << nb) - 1, 0).astype(np.uint16)
+        if a.ndim == 2 and a.shape[0] == n_cams and a.shape[1] in (6, 9):
+            return (a.astype(np.uint16) << np.arange(a.shape[1], dtype=np.uint16)).sum(axis=1).astype(np.uint16)
+        raise ValueError(f"a bool camera mask must be ({n_cams},), ({n_cams}, 6) or ({n_cams}, 9), not {a.shape}")
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"camera mask must be bool or integer bit masks, not {a.dtype}")
+    if a.shape != (n_cams,):
+        raise ValueError(f"an integer camera mask must be ({n_cams},), not {a.shape}")
+    if a.size and (a.min() < 0 or a.max() > 0x1FF):
+        raise ValueError("camera mask bits must lie in 0-8 (rvec 0-2, t 3-5, f 6, k1 7, k2 8)")
+    return a.astype(np.uint16)
+
+
+def held_point_mask(points, n_pts):
+    """Normalise a point hold spec (bool (Np,) array) to ba_set_held's uint8 flags.  None -> None."""
+    if points is None:
+        return None
+    a = np.asarray(points)
+    if a.dtype != np.bool_:
+        raise ValueError(f"point mask must be a bool array, not {a.dtype}")
+    if a.shape != (n_pts,):
+        raise ValueError(f"point mask must be ({n_pts},), not {a.shape}")
+    return a.astype(np.uint8)
 
 
 def load_library():
@@ -191,8 +226,23 @@ class Solver:
                                         cam_idx.ctypes.data_as(_IP), pt_idx.ctypes.data_as(_IP), _dp(uv), _dp(K4),
                                         int(prob.fixed_cam)))
         self.n_cams, self.n_pts, self.n_obs = prob.n_cams, prob.n_pts, prob.n_obs
+        self._nb = 6                           # block size a whole-camera mask covers (the BAL uploads set 9)
+        if prob.cam_held is not None or prob.pt_held is not None:
+            self.set_held(prob.cam_held, prob.pt_held)
         if with_params:
             self.set_params(prob.cams, prob.pts)
+
+    def set_held(self, cams=None, points=None):
+        """ba_set_held: parameters the solves keep constant.  cams: bool (Nc,) (whole cameras), bool (Nc, 6 | 9) (per block
+        parameter) or integer bit masks (Nc,); points: bool (Np,).  A whole camera of a BAL upload (set_problem_bal,
+        solve_bal) includes its f, k1, k2.  set_held() clears both.  The masks stay with the
+        handle across set_params and solves; set_problem clears them."""
+        cm = held_camera_mask(cams, self.n_cams, getattr(self, "_nb", 6))
+        pm = held_point_mask(points, self.n_pts)
+        cm = None if cm is None else np.ascontiguousarray(cm)
+        pm = None if pm is None else np.ascontiguousarray(pm)
+        _check(self._lib.ba_set_held(self._h, None if cm is None else cm.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                     None if pm is None else pm.ctypes.data_as(C.POINTER(C.c_uint8))))
 
     def set_params(self, cams, pts):
         cams = np.ascontiguousarray(cams, dtype=np.float64).reshape(self.n_cams, 6)
@@ -270,6 +320,7 @@ class Solver:
         from .problem import BAProblem
         self.set_problem(BAProblem(np.ascontiguousarray(bal.cams[:, :6]), bal.pts, bal.cam_idx, bal.pt_idx, bal.uv,
                                    np.array([1.0, 1.0, 0.0, 0.0]), fixed_cam))
+        self._nb = 9
         return np.ascontiguousarray(bal.cams[:, 6:9], dtype=np.float64).copy()
 
     def linearize_bal(self, bal, loss="linear", f_scale=1.0, fixed_cam=-1):
@@ -308,10 +359,16 @@ class Solver:
             setattr(o, k, v)
         return o
 
-    def solve_bal(self, bal, fixed_cam=-1, **kw):
+    def solve_bal(self, bal, fixed_cam=-1, hold_intrinsics=False, held_cameras=None, held_points=None, **kw):
         """ba_solve_bal on a bal.BALProblem (9-parameter cameras, f / k1 / k2 adjusted with the pose): returns
-        (summary dict, cams (Nc,9), pts (Np,3)).  kw as for solve()."""
+        (summary dict, cams (Nc,9), pts (Np,3)).  hold_intrinsics: keep every camera's f, k1, k2; held_cameras /
+        held_points: as set_held (added to hold_intrinsics).  kw as for solve()."""
         intr = self._set_bal(bal, fixed_cam)
+        cm = held_camera_mask(held_cameras, self.n_cams, 9)
+        if hold_intrinsics:
+            cm = (np.zeros(self.n_cams, np.uint16) if cm is None else cm) | np.uint16(0x1C0)
+        if cm is not None or held_points is not None:
+            self.set_held(cm, held_points)
         o = self._options(kw)
         s = BASummary()
         _check(self._lib.ba_solve_bal(self._h, _dp(intr), C.byref(o), C.byref(s)))

@@ -31,6 +31,8 @@ class BAProblem:
     uv: np.ndarray          # (Nobs,2) float64
     K4: np.ndarray          # (4,) fx, fy, cx, cy
     fixed_cam: int = 0      # index into cams, -1 = none fixed
+    cam_held: np.ndarray | None = None   # optional held camera parameters (hip_backend.held_camera_mask forms; ba_set_held)
+    pt_held: np.ndarray | None = None    # optional (Np,) bool: held points
 
     @property
     def n_cams(self):
@@ -58,6 +60,10 @@ class BAProblem:
                 raise ValueError("pt_idx out of range")
         if not (-1 <= self.fixed_cam < nc):
             raise ValueError("fixed_cam out of range")
+        if self.cam_held is not None or self.pt_held is not None:
+            from .hip_backend import held_camera_mask, held_point_mask
+            held_camera_mask(self.cam_held, nc)
+            held_point_mask(self.pt_held, npt)
         return self
 
 
@@ -214,7 +220,9 @@ def extract_shard(problem: BAProblem, p_begin: int, p_end: int):
     sel = np.nonzero((problem.pt_idx >= p_begin) & (problem.pt_idx < p_end))[0]
     sub = BAProblem(problem.cams.copy(), problem.pts[p_begin:p_end].copy(),
                     problem.cam_idx[sel].copy(), (problem.pt_idx[sel] - p_begin).astype(np.int32),
-                    problem.uv[sel].copy(), problem.K4.copy(), problem.fixed_cam)
+                    problem.uv[sel].copy(), problem.K4.copy(), problem.fixed_cam,
+                    None if problem.cam_held is None else np.array(problem.cam_held, copy=True),
+                    None if problem.pt_held is None else np.array(problem.pt_held[p_begin:p_end], copy=True))
     return sub, sel
 
 

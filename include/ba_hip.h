@@ -164,7 +164,9 @@ enum ba_stat {
   BA_STAT_PIXELS_F32 = 8,           /* 1: every pixel of the current problem is a float32 value (as cv2 keypoints are) and the
                                        multi-kernel path keeps its two pixel streams as float2, widened on load: same results,
                                        8 bytes per observation and pass less (BA_PIXELS=f64 switches it off) */
-  BA_STAT_COUNT = 9
+  BA_STAT_HELD_PARAMS = 9,          /* held scalar parameters of the current problem (ba_set_held), fixed_cam's whole block included
+                                       (6 parameters, or 9 once a camera mask sets a BAL bit); 3 per held point */
+  BA_STAT_COUNT = 10
 };
 
 const char* ba_last_error(void);
@@ -209,6 +211,21 @@ int ba_comm_init(ba_handle* h, int rank, int world, const void* id128);
 int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64_t n_obs,
                    const int32_t* cam_idx, const int32_t* pt_idx, const double* uv,
                    const double K4[4], int32_t fixed_cam);
+/* Held parameters: unknowns that keep their values through ba_solve / ba_solve_bal (Ceres' constant parameter blocks and
+ * subset parameterisations, g2o's setFixed; no reference counterpart beyond fixed_cam, src/bundle_adjuster.py:141-143).
+ *   cam_held uint16[Nc] or NULL: a bit set over the camera's block columns -- bits 0-2 rvec, 3-5 t (the caller's additive
+ *            coordinates, as the columns of ba_linearize's blocks), and under the BAL model bit 6 f, 7 k1, 8 k2
+ *   pt_held  uint8[Np]  or NULL: nonzero = all three coordinates of the point are held
+ * A held parameter ends bit-equal to its input; it has zero rows and columns in Hcc | bc (and Hpp = bp = 0 for a held point)
+ * as reported by ba_linearize*, identity ones in the damped system, ba_schur_apply and the preconditioner, and a zero
+ * right-hand side (ba_schur_rhs) and step.  A held point keeps its observations: they enter the cost and the cameras'
+ * blocks.  The stopping tests see the free parameters only (gtol: max |g| over free entries; xtol: |x| and |dx| over free
+ * entries).  fixed_cam holds its camera in addition to the masks.  The masks belong to the handle: they survive
+ * ba_set_params and repeated solves; ba_set_problem clears them, and so does ba_set_held(h, NULL, NULL).
+ * Bits 9-15 are refused here; bits 6-8 by the pinhole solve / linearisation that meets them (BA_ERR_INVALID).
+ * BA_PRECOND_TWO_LEVEL with any mask is refused by ba_solve (BA_ERR_STATE).  Multi-rank jobs: cam_held covers ALL cameras
+ * and must be the same on every rank (the caller's obligation); pt_held is per shard, in the shard's local point order. */
+int ba_set_held(ba_handle* h, const uint16_t* cam_held, const uint8_t* pt_held);
 int ba_set_params(ba_handle* h, const double* cams, const double* pts);
 int ba_get_params(ba_handle* h, double* cams, double* pts);
 /* 3x3 rotation matrices of the current cameras, double[Nc][9] row-major: the
@@ -249,7 +266,8 @@ int ba_linearize_bal(ba_handle* h, const double* intr, int32_t loss, double f_sc
  * (the window solver is built for the reference's pinhole only).  Multi-rank jobs are supported exactly as in ba_solve
  * (landmark shards, the same all-reduces; fold sizes follow the 9-parameter blocks).  Cameras (rvec, t) and points are the
  * handle's (ba_set_params before, ba_get_params after); intr double[Nc][3] = (f, k1, k2) per camera is read AND updated.
- * fixed_cam of ba_set_problem is honoured (-1: no camera held; the damping carries the gauge). */
+ * fixed_cam of ba_set_problem is honoured (-1: no camera held; the damping carries the gauge), and so are the masks of
+ * ba_set_held, bits 6-8 included: a held intrinsic comes back in intr unchanged, bit for bit. */
 int ba_solve_bal(ba_handle* h, double* intr, const ba_options* opts, ba_summary* sum);
 
 /* K2/K3: linearise at the current parameters.  Outputs (any may be NULL):

@@ -1,0 +1,344 @@
+"""GPU: held parameters (ba_set_held) through every layer -- linearisation and reduced-system hooks against the reduced
+problem (tests/held_reference.py), solves that leave held values bit-equal and are certified on the reduced problem, the
+extremes, BAL intrinsics, both window-solver forms, the drop-in's fixed_keyframes, two ranks, and the error rules."""
+import io
+import json
+import os
+import subprocess
+import sys
+from contextlib import redirect_stdout
+
+import numpy as np
+import pytest
+
+from bundle_adjustment_amd import BundleAdjuster, bal, hip_backend
+from bundle_adjustment_amd.bal import BALProblem
+from bundle_adjustment_amd.problem import BAProblem
+from bundle_adjustment_amd.synthetic import make_bal_problem, make_config, make_problem, problem_to_map
+from oracle import ba_oracle as o
+from tests import robust_losses as rl
+from tests.held_reference import Reduced
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TIGHT = dict(ftol=0.0, xtol=0.0, gtol=0.0)
+
+
+def _rel(a, b):
+    return float(np.abs(a - b).max() / max(1e-300, np.abs(b).max()))
+
+
+def _masks(nc, npt, nb, seed, frac_pts=0.1):
+    rng = np.random.default_rng(seed)
+    cm = rng.integers(0, 1 << nb, size=nc) * (rng.random(nc) < 0.3)
+    pm = rng.random(npt) < frac_pts
+    return cm.astype(np.uint16), pm
+
+
+@pytest.fixture(scope="module")
+def solver():
+    s = hip_backend.Solver(0)
+    yield s
+    s.close()
+
+
+# ---------------------------------------------------------------- linearisation and the reduced system
+@pytest.mark.parametrize("loss", ["linear", "huber"])
+def test_linearize_zeroes_held_rows_and_columns(solver, loss):
+    p = make_problem(12, 800, 5, seed=4, outlier_frac=0.02)
+    cm, pm = _masks(p.n_cams, p.n_pts, 6, seed=1)
+    solver.set_problem(p)
+    solver.set_held(cm, pm)
+    Hcc, bc, Hpp, bp = solver.linearize(loss, f_scale=2.0)
+    red = Reduced(p.cams, p.pts, p.cam_idx, p.pt_idx, p.uv, p.K4, p.fixed_cam, cm, pm)
+    ne = red.normal_equations(p.cams, p.pts, loss, 2.0)
+    assert _rel(Hcc, rl.pack_upper(ne["Hcc"])) <= 1e-12 and _rel(bc, ne["bc"]) <= 1e-12
+    assert _rel(Hpp, rl.pack_upper(ne["Hpp"])) <= 1e-12 and _rel(bp, ne["bp"]) <= 1e-12
+    assert np.all(Hpp[pm] == 0) and np.all(bp[pm] == 0)
+    lam = 1e-3
+    S, rhs = red.schur(ne, lam)
+    g = solver.schur_rhs(lam).ravel()
+    assert _rel(g, rhs) <= 1e-9 and np.all(g[red.held_cam.ravel()] == 0)
+    v = np.random.default_rng(0).normal(size=(p.n_cams, 6))
+    assert _rel(solver.schur_apply(lam, v).ravel(), S @ v.ravel()) <= 1e-9
+
+
+def test_bal_linearize_honours_intrinsic_bits(solver):
+    p = make_bal_problem(n_cams=16, n_pts=800, n_obs_target=3500, seed=2)
+    cm, pm = _masks(p.n_cams, p.n_pts, 9, seed=3)
+    cm[:4] |= 0x1C0
+    intr = solver.set_problem_bal(p, fixed_cam=0)
+    solver.set_held(cm, pm)
+    out = dict(Hcc=np.empty((p.n_cams, 45)), bc=np.empty((p.n_cams, 9)), Hpp=np.empty((p.n_pts, 6)), bp=np.empty((p.n_pts, 3)))
+    dp = hip_backend._dp
+    hip_backend._check(solver._lib.ba_linearize_bal(solver._h, dp(intr), hip_backend.loss_code("huber"), 2.0, dp(out["Hcc"]),
+                                                    dp(out["bc"]), dp(out["Hpp"]), dp(out["bp"])))
+    red = Reduced(p.cams, p.pts, p.cam_idx, p.pt_idx, p.uv, None, 0, cm, pm)
+    ne = red.normal_equations(p.cams, p.pts, "huber", 2.0)
+    assert _rel(out["Hcc"], rl.pack_upper(ne["Hcc"])) <= 1e-12 and _rel(out["bc"], ne["bc"]) <= 1e-12
+    assert _rel(out["Hpp"], rl.pack_upper(ne["Hpp"])) <= 1e-12 and _rel(out["bp"], ne["bp"]) <= 1e-12
+
+
+# ---------------------------------------------------------------- solves
+@pytest.mark.parametrize("loss", ["linear", "huber"])
+def test_solve_keeps_held_values_and_is_a_reduced_minimiser(solver, loss):
+    p = make_config("C2", seed=3)
+    cm, pm = _masks(p.n_cams, p.n_pts, 6, seed=5)
+    solver.set_problem(p)
+    solver.set_held(cm, pm)
+    # (Huber: IRLS converges linearly, the certificate needs the longer budget)
+    out = solver.solve(loss=loss, max_iters=100 if loss == "linear" else 400, pcg_tol=1e-6, small_solver=1, **TIGHT)
+    assert out["status"] >= 0 and out["final_cost"] < out["initial_cost"]
+    cams, pts = solver.get_params()
+    red = Reduced(p.cams, p.pts, p.cam_idx, p.pt_idx, p.uv, p.K4, p.fixed_cam, cm, pm)
+    held = ~red.free
+    assert np.array_equal(red.x_full(cams, pts)[held], red.x_full(p.cams, p.pts)[held])      # bit-equal
+    assert not np.array_equal(red.x_full(cams, pts)[red.free], red.x_full(p.cams, p.pts)[red.free])
+    red.certify(p.cams, p.pts, cams, pts, loss)
+    assert solver.stats()["held_params"] == int(held.sum())
+
+
+def test_mask_of_one_whole_camera_equals_fixed_cam(solver):
+    p = make_problem(20, 2000, 5, seed=6)
+    kw = dict(loss="huber", max_iters=20, small_solver=1, ftol=1e-14, xtol=0.0, gtol=0.0, pcg_tol=1e-3)
+    c = 7
+    solver.set_problem(BAProblem(p.cams, p.pts, p.cam_idx, p.pt_idx, p.uv, p.K4, c))
+    a = solver.solve(**kw)
+    ta, (ca, pa) = solver.trace(), solver.get_params()
+    solver.set_problem(BAProblem(p.cams, p.pts, p.cam_idx, p.pt_idx, p.uv, p.K4, -1))
+    m = np.zeros(p.n_cams, bool)
+    m[c] = True
+    solver.set_held(cams=m)
+    b = solver.solve(**kw)
+    tb, (cb, pb) = solver.trace(), solver.get_params()
+    assert [r["accepted"] for r in ta] == [r["accepted"] for r in tb] and a["iterations"] == b["iterations"]
+    assert np.array_equal(cb[c], p.cams[c])
+    assert _rel(cb, ca) <= 1e-12 and _rel(pb, pa) <= 1e-12
+
+
+def _gn_point(R, t, K4, uv, X):
+    """Per-point Gauss-Newton under known cameras (numpy, 3x3)."""
+    for _ in range(50):
+        Xc = np.einsum('nij,j->ni', R, X) + t
+        iz = 1.0 / Xc[:, 2]
+        r = uv - np.stack([Xc[:, 0] * iz * K4[0] + K4[2], Xc[:, 1] * iz * K4[1] + K4[3]], axis=1)
+        dpi = np.zeros((len(uv), 2, 3))
+        dpi[:, 0, 0] = K4[0] * iz; dpi[:, 0, 2] = -K4[0] * Xc[:, 0] * iz * iz
+        dpi[:, 1, 1] = K4[1] * iz; dpi[:, 1, 2] = -K4[1] * Xc[:, 1] * iz * iz
+        J = -(dpi @ R).reshape(-1, 3)
+        X = X - np.linalg.solve(J.T @ J, J.T @ r.ravel())
+    return X
+
+
+def test_all_cameras_held_gives_per_point_minimisers(solver):
+    p = make_problem(10, 400, 5, seed=8)
+    solver.set_problem(p)
+    solver.set_held(cams=np.ones(p.n_cams, bool))
+    solver.solve(loss="linear", max_iters=60, small_solver=1, pcg_tol=1e-8, **TIGHT)
+    cams, pts = solver.get_params()
+    assert np.array_equal(cams, p.cams)
+    R = o.rodrigues_batch(p.cams[:, :3])
+    for j in range(0, p.n_pts, 37):
+        sel = p.pt_idx == j
+        ref = _gn_point(R[p.cam_idx[sel]], p.cams[p.cam_idx[sel], 3:], p.K4, p.uv[sel], p.pts[j].copy())
+        assert np.abs(pts[j] - ref).max() <= 1e-8 * max(1.0, np.abs(ref).max())
+
+
+def test_all_points_held_gives_per_camera_minimisers(solver):
+    p = make_problem(10, 400, 5, seed=9)
+    solver.set_problem(p)
+    solver.set_held(points=np.ones(p.n_pts, bool))
+    solver.solve(loss="linear", max_iters=60, small_solver=1, pcg_tol=1e-8, **TIGHT)
+    cams, pts = solver.get_params()
+    assert np.array_equal(pts, p.pts)
+    red = Reduced(p.cams, p.pts, p.cam_idx, p.pt_idx, p.uv, p.K4, p.fixed_cam, None, np.ones(p.n_pts, bool))
+    g0 = red.grad_inf(p.cams, p.pts, "linear")
+    for c in range(1, p.n_cams):      # each camera alone against fixed points: its own 6-parameter gradient vanishes
+        sel = p.cam_idx == c
+        r = o.residuals(cams, pts, p.cam_idx[sel], p.pt_idx[sel], p.uv[sel], p.K4)
+        Jc, _ = o.jacobian_blocks(cams, pts, p.cam_idx[sel], p.pt_idx[sel], p.K4)
+        assert np.abs(np.einsum('nki,nk->i', Jc, r)).max() <= 1e-7 * g0
+
+
+@pytest.mark.parametrize("small", [0, 1])
+def test_everything_held_returns_at_once(solver, small):
+    p = make_problem(6, 300, 4, seed=10)
+    solver.set_problem(p)
+    solver.set_held(np.ones(p.n_cams, bool), np.ones(p.n_pts, bool))
+    out = solver.solve(loss="huber", max_iters=20, small_solver=small)
+    cams, pts = solver.get_params()
+    assert out["iterations"] == 0 and out["final_cost"] == out["initial_cost"]
+    assert np.array_equal(cams, p.cams) and np.array_equal(pts, p.pts)
+
+
+@pytest.mark.parametrize("precision", [0, 1])
+def test_bal_hold_intrinsics(solver, precision):
+    p = make_bal_problem(n_cams=16, n_pts=800, n_obs_target=3500, seed=12)
+    out, cams, pts = solver.solve_bal(p, fixed_cam=0, hold_intrinsics=True, loss="linear", max_iters=200, pcg_tol=1e-6,
+                                      jacobian_precision=precision, **TIGHT)
+    assert np.array_equal(cams[:, 6:], p.cams[:, 6:])
+    assert out["final_cost"] < out["initial_cost"]
+    cm = np.full(p.n_cams, 0x1C0, np.uint16)
+    Reduced(p.cams, p.pts, p.cam_idx, p.pt_idx, p.uv, None, 0, cm, None).certify(p.cams, p.pts, cams, pts, "linear")
+    bp_, summary = bal.solve(p, fixed_cam=0, hold_intrinsics=True, loss="linear", max_iters=5)
+    assert np.array_equal(bp_.cams[:, 6:], p.cams[:, 6:])
+
+
+# ---------------------------------------------------------------- window solvers and the drop-in
+def _window(seed=13):
+    return make_problem(5, 600, 4, seed=seed)
+
+
+@pytest.mark.parametrize("mw,stat", [(None, "window_mw_launches"), ("0", "window_lm_launches")])
+def test_window_solvers_serve_held_windows(monkeypatch, mw, stat):
+    if mw is not None:
+        monkeypatch.setenv("BA_SMALL_MW", mw)
+    else:
+        monkeypatch.delenv("BA_SMALL_MW", raising=False)
+    p = _window()
+    cm = np.zeros(p.n_cams, np.uint16)
+    cm[1] = 0x3F
+    cm[2] = 0b001100
+    pm = np.zeros(p.n_pts, bool)
+    pm[::13] = True
+    kw = dict(loss="huber", max_iters=30, ftol=1e-12, xtol=1e-12, gtol=0.0, pcg_tol=1e-10)
+    with hip_backend.Solver(0) as s:
+        s.set_problem(p)
+        s.set_held(cm, pm)
+        before = s.stats()[stat]
+        win = s.solve(small_solver=0, **kw)
+        assert s.stats()[stat] == before + 1
+        cw, pw = s.get_params()
+        s.set_params(p.cams, p.pts)
+        ref = s.solve(small_solver=1, **kw)
+        cr, pr = s.get_params()
+    red = Reduced(p.cams, p.pts, p.cam_idx, p.pt_idx, p.uv, p.K4, p.fixed_cam, cm, pm)
+    held = ~red.free
+    assert np.array_equal(red.x_full(cw, pw)[held], red.x_full(p.cams, p.pts)[held])
+    assert abs(win["final_cost"] - ref["final_cost"]) <= 1e-9 * ref["final_cost"]
+    assert np.abs(cw - cr).max() <= 1e-6 and np.abs(pw - pr).max() <= 1e-5
+
+
+def test_bundle_adjuster_holds_two_keyframes():
+    p = make_problem(6, 600, 4, seed=14)
+    gmap = problem_to_map(p)
+    K = np.array([[p.K4[0], 0, p.K4[2]], [0, p.K4[1], p.K4[3]], [0, 0, 1.0]])
+    ids = sorted(gmap.keyframes)
+    before = {k: (gmap.keyframes[k].R.copy(), gmap.keyframes[k].t.copy()) for k in ids}
+    ba = BundleAdjuster(K, window_size=5, fixed_keyframes=2)
+    buf = io.StringIO()
+    with redirect_stdout(buf):
+        ba.run(gmap)
+    ba.close()
+    assert "LBA Complete" in buf.getvalue()
+    s = ba.last_summary
+    assert s["final_sse"] <= s["initial_sse"]
+    window = ids[-6:-1]
+    for k in window[:2]:
+        assert np.array_equal(gmap.keyframes[k].R, before[k][0]) and np.array_equal(gmap.keyframes[k].t, before[k][1])
+    assert not np.array_equal(gmap.keyframes[window[2]].t, before[window[2]][1])
+
+
+# ---------------------------------------------------------------- two ranks
+WORKER = r"""
+import json, os, sys
+import numpy as np
+sys.path.insert(0, %(root)r)
+import torch.distributed as dist
+from bundle_adjustment_amd import hip_backend
+from bundle_adjustment_amd.problem import BAProblem, extract_shard, shard_by_landmark
+from bundle_adjustment_amd.synthetic import make_problem
+rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+dist.init_process_group(backend="gloo")
+p = make_problem(14, 1500, 5, seed=11)
+rng = np.random.default_rng(3)
+cm = (rng.integers(0, 64, size=p.n_cams) * (rng.random(p.n_cams) < 0.3)).astype(np.uint16)
+pm = rng.random(p.n_pts) < 0.1
+p = BAProblem(p.cams, p.pts, p.cam_idx, p.pt_idx, p.uv, p.K4, p.fixed_cam, cm, pm)
+b, e = shard_by_landmark(p, world)[rank]
+sub, _ = extract_shard(p, b, e)
+s = hip_backend.Solver(0)
+uid = [hip_backend.comm_unique_id() if rank == 0 else None]
+dist.broadcast_object_list(uid, src=0)
+s.comm_init(rank, world, uid[0])
+s.set_problem(sub)
+out = s.solve(loss="huber", max_iters=25, ftol=1e-13, xtol=1e-13, gtol=1e-12, pcg_tol=1e-3)
+cams, pts = s.get_params()
+np.save(os.path.join(%(out)r, f"cams_{rank}.npy"), cams)
+np.save(os.path.join(%(out)r, f"pts_{rank}.npy"), pts)
+json.dump(out, open(os.path.join(%(out)r, f"out_{rank}.json"), "w"))
+s.close()
+dist.barrier()
+dist.destroy_process_group()
+"""
+
+
+def _free_port():
+    import socket
+    sk = socket.socket()
+    sk.bind(("127.0.0.1", 0))
+    port = sk.getsockname()[1]
+    sk.close()
+    return str(port)
+
+
+def test_two_ranks_with_held_points_in_both_shards_match_one_rank(tmp_path):
+    from bundle_adjustment_amd.problem import shard_by_landmark
+    script = tmp_path / "worker.py"
+    script.write_text(WORKER % dict(root=ROOT, out=str(tmp_path)))
+    env = dict(os.environ, BA_COMM="shm")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
+           "--master-port", _free_port(), str(script)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    p = make_problem(14, 1500, 5, seed=11)
+    rng = np.random.default_rng(3)
+    cm = (rng.integers(0, 64, size=p.n_cams) * (rng.random(p.n_cams) < 0.3)).astype(np.uint16)
+    pm = rng.random(p.n_pts) < 0.1
+    ranges = shard_by_landmark(p, 2)
+    assert all(pm[b:e].any() for b, e in ranges)
+    with hip_backend.Solver(0) as s:
+        s.set_problem(BAProblem(p.cams, p.pts, p.cam_idx, p.pt_idx, p.uv, p.K4, p.fixed_cam, cm, pm))
+        ref = s.solve(loss="huber", max_iters=25, ftol=1e-13, xtol=1e-13, gtol=1e-12, pcg_tol=1e-3)
+        cams_ref, pts_ref = s.get_params()
+    outs = [json.load(open(tmp_path / f"out_{k}.json")) for k in range(2)]
+    for key in ("iterations", "accepted", "final_sse", "final_cost"):
+        assert outs[0][key] == outs[1][key], key
+    assert abs(outs[0]["final_cost"] - ref["final_cost"]) <= 1e-9 * ref["final_cost"]
+    cams0 = np.load(tmp_path / "cams_0.npy")
+    assert np.array_equal(cams0, np.load(tmp_path / "cams_1.npy"))
+    assert np.abs(cams0 - cams_ref).max() <= 1e-6
+    pts = np.concatenate([np.load(tmp_path / f"pts_{k}.npy") for k in range(2)])
+    assert np.abs(pts - pts_ref).max() <= 1e-5
+    assert np.array_equal(pts[pm], p.pts[pm])
+
+
+# ---------------------------------------------------------------- errors and clearing
+def test_errors_and_clearing(solver):
+    p = make_problem(12, 800, 5, seed=15)
+    solver.set_problem(p)
+    solver.set_held(cams=np.full(p.n_cams, 1 << 6, np.uint16))
+    with pytest.raises(hip_backend.BAHipError, match="error -1: .*f, k1, k2"):          # BA_ERR_INVALID
+        solver.solve(loss="huber", max_iters=3, small_solver=1)
+    with pytest.raises(hip_backend.BAHipError, match="error -1: .*f, k1, k2"):
+        solver.linearize("huber")
+    solver.set_held(points=np.arange(p.n_pts) % 5 == 0)
+    with pytest.raises(hip_backend.BAHipError, match="error -3: .*two-level"):          # BA_ERR_STATE
+        solver.solve(loss="huber", max_iters=3, preconditioner="two_level", small_solver=1)
+    kw = dict(loss="huber", max_iters=8, small_solver=1)
+    with hip_backend.Solver(0) as plain:
+        plain.set_problem(p)
+        ref = plain.solve(**kw)
+        cref, pref = plain.get_params()
+    solver.set_held()                                   # cleared by set_held(None, None)
+    solver.set_params(p.cams, p.pts)
+    a = solver.solve(**kw)
+    ca, pa = solver.get_params()
+    assert a == ref or (a["final_cost"] == ref["final_cost"] and a["iterations"] == ref["iterations"])
+    assert np.array_equal(ca, cref) and np.array_equal(pa, pref)
+    solver.set_held(cams=np.ones(p.n_cams, bool))
+    solver.set_problem(p)                               # cleared by set_problem
+    assert solver.stats()["held_params"] == 6
+    solver.solve(**kw)
+    cb, pb = solver.get_params()
+    assert np.array_equal(cb, cref) and np.array_equal(pb, pref)
