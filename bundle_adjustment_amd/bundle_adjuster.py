@@ -51,7 +51,8 @@ class BundleAdjuster:
             raise ValueError("fixed_keyframes must be an integer >= 1")
         self.fixed_keyframes = int(fixed_keyframes)
         self.device_id = device_id
-        hip_backend.loss_code(loss)            # an unknown loss name fails here, not at the first run()
+        hip_backend.loss_code(loss)            # an unknown loss or preconditioner name fails here, not at the first run()
+        hip_backend.precond_code(preconditioner)
         self.solver_options = dict(loss=loss, f_scale=f_scale, ftol=ftol, xtol=xtol, gtol=gtol, max_iters=max_iters,
                                    pcg_tol=pcg_tol, pcg_max_iters=pcg_max_iters, pcg_model_tol=pcg_model_tol, preconditioner=preconditioner,
                                    jacobian_precision={'f64': 0, 'f32': 1}[jacobian], verbose=verbose)

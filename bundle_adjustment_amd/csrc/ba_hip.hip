@@ -32,7 +32,6 @@
 #include "../../include/ba_hip.h"
 #include "ba_kernels.hpp"
 #include "ba_triangulate.hpp"
-#include "ba_coarse.hpp"
 #include "ba_small.hpp"
 #include "ba_small_mw.hpp"
 #include "ba_setup.hpp"
@@ -225,15 +224,7 @@ struct ba_handle {
   int setup_path = 0;                     // how the current problem's layout was built: 0 host, 1 device
   DBuf<double> stat2;                     // multi-rank: the band statistic (span sum, tracks) summed over the shards
   bool banded_known = false;              // ... already decided for the problem being set (device build that fell back to the host build)
-  // two-level preconditioner for band-structured problems (ba_coarse.hpp): structures built by ba_set_problem
   bool banded = false;         // mean camera span of a track <= Nc / 8 (sequential captures): pcg_model_tol's automatic default
-  bool two_level_ok = false;   // this problem has them
-  bool two_level = false;      // the current solve uses them
-  int n_agg = 0, n_runs = 0, n_pairs = 0, coarse_bw = 0;
-  DBuf<int> run_beg, run_pt, run_agg;
-  DBuf<int2> run_pairs;
-  DBuf<double> coarseU, coarseE, coarseEinv, coarse_rc, coarse_info;
-  DBuf<long long> coarseEint;
   DBuf<double> dev_lam;        // device word a riding k_scalars stores the next damping in; 0 = not yet (ba_kernels.hpp, ScalarsArgs::lam_slot)
   DBuf<double> verdict;        // PCG verdict words {gamma, zeta, finished, -} x 2 iteration parities (point pass -> camera pass, vector kernel)
   int cam_segl = 64;           // lanes per (camera, partition) segment in the PCG camera pass (BA_CAM_SEGL, tuning)
@@ -251,7 +242,6 @@ struct ba_handle {
   // comm
   int rank = 0, world = 1;
   bool sys_diag = false;   // the last exchange_system carried Schur-Jacobi blocks (layout of sysmsg)
-  bool one_part = false;       // multi-rank, thin shards: every camera's local observations in partition 0 (no fold kernels; ba_set_problem)
   bool multi = false;          // the multi-rank control flow is on: world > 1, or a communicator of ONE rank was forced
                                // (BA_COMM_FORCE=1: lets a single GPU execute every fold / all-reduce / decide step of the
                                // multi-rank loop through the real RCCL library)
@@ -410,9 +400,6 @@ extern "C" int ba_destroy(ba_handle* h) {
   h->intr[0].release(); h->intr[1].release();
   h->small_gS.release();
   h->small_np_pad = -1;
-  h->run_beg.release(); h->run_pt.release(); h->run_agg.release(); h->run_pairs.release();
-  h->coarseU.release(); h->coarseE.release(); h->coarseEinv.release(); h->coarse_rc.release(); h->coarse_info.release();
-  h->coarseEint.release();
   h->verdict.release();
   h->dev_lam.release();
   if (h->h_scal) (void)hipHostFree(h->h_scal);
@@ -952,14 +939,7 @@ static int set_problem_device(ba_handle* h, int Nc, int Np, int No, const int32_
   if (h->long_thr != 0x7fffffff) for (int L = h->long_thr + 1; L < SETUP_HIST_BINS; ++L) n_long += hh[L];
   config_long_grid(h, grid, Np, n_long);
   if (int rc = decide_banded(h, (double)span_sum, (double)n_tracks, Nc)) return rc;
-  {   // problems the two-level preconditioner's structures would be built for: the host build (it also re-sorts every track by camera)
-    bool want = h->banded && !h->multi;
-    if (const char* e = getenv("BA_TWO_LEVEL")) want = atoi(e) != 0 && !h->multi;
-    if (want && Nc >= 2 * VEC_CAMS) return 1;
-  }
-  h->two_level_ok = false;
   h->mw_ok = false;
-  h->one_part = false;
   HIPCHECK(h->long_pts.alloc(std::max(h->n_long, 1)));
   if (h->n_long > 0) {
     BA_LAUNCH(k_setup_long_flags, gp, b256, 0, h->stream, (const int*)h->pt_off.p, Np, h->long_thr, S + o_flag);
@@ -1085,8 +1065,7 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
   {
     static const long dev_min = [] { const char* e = getenv("BA_SETUP_DEVICE_MIN"); return e ? atol(e) : 50000L; }();
     const char* mode = getenv("BA_SETUP");
-    bool try_dev = n_obs > 0 && n_pts > 0 && n_cams > MW_MAX_CAMS && (size_t)n_cams * TA * sizeof(double) <= (size_t)LDS_TAB_BYTES &&
-                   !(getenv("BA_ONE_PART") && atoi(getenv("BA_ONE_PART")) != 0 && h->multi);
+    bool try_dev = n_obs > 0 && n_pts > 0 && n_cams > MW_MAX_CAMS && (size_t)n_cams * TA * sizeof(double) <= (size_t)LDS_TAB_BYTES;
     if (mode && strcmp(mode, "host") == 0) try_dev = false;
     else if (!(mode && strcmp(mode, "device") == 0) && n_obs < dev_min) try_dev = false;
     if (try_dev) {
@@ -1264,18 +1243,10 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
   // uniformly spread observations chunk k covers about the k-th eighth of the point table (what
   // keeps it resident in XCD k's L2); for band-structured data the chunks stay balanced and are
   // narrow in point index anyway.
-  // BA_ONE_PART=1 (experiment, multi-rank only): the whole local list of a camera goes into partition 0, the others stay
-  // empty -- the partial sums then come out already "folded" and the fold kernels in front of the all-reduces
-  // (fold_and_reduce) disappear.  Measured on a rank's share of C3 with every collective issued (tools/shard_times.py):
-  // slower at every shard size (1/8 of the points: 240 against 182 us per LM iteration, 1/4: 279 against 184) -- a
-  // camera's list handled by ONE 16-lane row in the camera passes costs more than the 3 us fold it saves.  Off by default.
-  h->one_part = false;
-  if (const char* e = getenv("BA_ONE_PART")) h->one_part = atoi(e) != 0 && h->multi;
   std::vector<int> offk((size_t)Nc * (NPART + 1));
   for (int c = 0; c < Nc; ++c) {
     const long long n = cam_off[c + 1] - cam_off[c];
-    for (int k = 0; k <= NPART; ++k)
-      offk[(size_t)c * (NPART + 1) + k] = h->one_part ? (k == 0 ? cam_off[c] : cam_off[c + 1]) : cam_off[c] + (int)((n * k) / NPART);
+    for (int k = 0; k <= NPART; ++k) offk[(size_t)c * (NPART + 1) + k] = cam_off[c] + (int)((n * k) / NPART);
   }
   // which workgroup -> XCD assignment of the camera passes keeps an XCD on one slice of the point table
   // (group_of_block): count the observations whose point lies in the slice of their partition, and in
@@ -1301,14 +1272,8 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
     if (const char* e = getenv("BA_CAM_BAND")) h->cam_band = atoi(e) != 0;
   }
   stage("partitions + XCD statistic");
-  // ---- two-level preconditioner structures (ba_coarse.hpp), for band-structured problems on one rank: observations
-  // inside a point sorted by camera, so that a point's observations of one 16-camera aggregate are one RUN
-  std::vector<int> run_beg, run_pt, run_agg;
-  std::vector<int2> run_pairs;
-  h->two_level_ok = false;
-  {
-    // band statistic: mean camera span of a track against the number of cameras (sequential captures: a few
-    // cameras; random visibility: most of the range)
+  {   // band statistic: mean camera span of a track against the number of cameras (sequential captures: a few
+      // cameras; random visibility: most of the range)
     double span_sum = 0.0;
     long long tracks = 0;
     for (int p = 0; p < Np; ++p) {
@@ -1319,51 +1284,8 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
       ++tracks;
     }
     if (!h->banded_known) { if (int rc = decide_banded(h, span_sum, (double)tracks, Nc)) return rc; }
-    bool want = h->banded && !h->multi;
-    if (const char* e = getenv("BA_TWO_LEVEL")) want = atoi(e) != 0 && !h->multi;
-    if (want && Nc >= 2 * VEC_CAMS && Np > 0 && No > 0) {
-      std::vector<std::pair<int, int>> tmp;
-      int bwa = 0;
-      run_beg.reserve(No / 2 + 16); run_pt.reserve(No / 2 + 16); run_agg.reserve(No / 2 + 16); run_pairs.reserve(No);
-      for (int p = 0; p < Np; ++p) {
-        const int b = pt_off[p], e = pt_off[p + 1];
-        if (e - b <= 32) {             // the usual track: stable insertion sort by camera, in place
-          for (int j = b + 1; j < e; ++j) {
-            const int c = p_cam[j], sidx = p_src[j];
-            int q = j;
-            while (q > b && p_cam[q - 1] > c) { p_cam[q] = p_cam[q - 1]; p_src[q] = p_src[q - 1]; --q; }
-            p_cam[q] = c; p_src[q] = sidx;
-          }
-        } else {
-          tmp.resize(e - b);
-          for (int j = b; j < e; ++j) tmp[j - b] = std::make_pair(p_cam[j], p_src[j]);
-          std::stable_sort(tmp.begin(), tmp.end(), [](const std::pair<int, int>& x, const std::pair<int, int>& y) { return x.first < y.first; });
-          for (int j = b; j < e; ++j) { p_cam[j] = tmp[j - b].first; p_src[j] = tmp[j - b].second; }
-        }
-        const int first_run = (int)run_pt.size();
-        for (int j = b; j < e;) {
-          const int a = p_cam[j] / VEC_CAMS;
-          run_beg.push_back(j); run_pt.push_back(p); run_agg.push_back(a);
-          while (j < e && p_cam[j] / VEC_CAMS == a) ++j;
-        }
-        const int last_run = (int)run_pt.size();
-        for (int r1 = first_run; r1 < last_run; ++r1)
-          for (int r2 = r1; r2 < last_run; ++r2) {
-            run_pairs.push_back(make_int2(r1, r2));
-            bwa = std::max(bwa, run_agg[r2] - run_agg[r1]);
-          }
-      }
-      run_beg.push_back(No);
-      h->n_agg = (Nc + VEC_CAMS - 1) / VEC_CAMS;
-      h->n_runs = (int)run_pt.size();
-      h->n_pairs = (int)run_pairs.size();
-      h->coarse_bw = std::min(6 * h->n_agg - 1, 6 * bwa + 5);
-      // the banded factorisation keeps one column of the band in LDS (512 words) and E^-1 is dense: give up the
-      // coarse level when the problem is not band-structured enough for either
-      h->two_level_ok = h->coarse_bw <= 500 && 6 * h->n_agg <= 4096;
-    }
   }
-  stage("coarse-level structures");
+  stage("band statistic");
   h->Nc = Nc; h->Np = Np; h->Nobs = No; h->fixed = fixed_cam;
   memcpy(h->K4, K4, sizeof h->K4);
   h->nblkV = (Nc + VEC_CAMS - 1) / VEC_CAMS;
@@ -1419,6 +1341,7 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
   // (staged: the sections are only collected here; ONE copy of the arena and ONE kernel deal them out at the end)
   UnpackArgs ua;
   memset(&ua, 0, sizeof ua);
+  bool unstaged = false;       // some array was copied straight from its host vector (not through the arena)
   auto upload = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
     if (bytes == 0) return hipSuccess;
     if (staged && up_used + bytes <= h->h_up_cap && ua.n_sections < UNPACK_MAX_SECTIONS && bytes % 4 == 0) {
@@ -1428,6 +1351,7 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
       up_used += (bytes + 63) & ~(size_t)63;
       return hipSuccess;
     }
+    unstaged = true;
     return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
   };
   // a section that only the unpack kernel reads (no array of its own): returns its arena offset, or (size_t)-1
@@ -1484,17 +1408,6 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
     }
   }
   if (int rc = alloc_solver_buffers(h)) return rc;
-  if (h->two_level_ok) {
-    const size_t nc6 = 6 * (size_t)h->n_agg;
-    HIPCHECK(h->run_beg.alloc(run_beg.size())); HIPCHECK(h->run_pt.alloc(run_pt.size())); HIPCHECK(h->run_agg.alloc(run_agg.size()));
-    HIPCHECK(h->run_pairs.alloc(run_pairs.size()));
-    HIPCHECK(hipMemcpyAsync(h->run_beg.p, run_beg.data(), run_beg.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemcpyAsync(h->run_pt.p, run_pt.data(), run_pt.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemcpyAsync(h->run_agg.p, run_agg.data(), run_agg.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemcpyAsync(h->run_pairs.p, run_pairs.data(), run_pairs.size() * sizeof(int2), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(h->coarseU.alloc(18 * (size_t)h->n_runs)); HIPCHECK(h->coarseE.alloc(nc6 * nc6)); HIPCHECK(h->coarseEinv.alloc(nc6 * nc6));
-    HIPCHECK(h->coarseEint.alloc(nc6 * nc6)); HIPCHECK(h->coarse_rc.alloc(nc6)); HIPCHECK(h->coarse_info.alloc(8));
-  }
   h->lb = 0;
   stage("allocations");
   HIPCHECK(upload(h->offk.p, offk.data(), offk.size() * sizeof(int)));
@@ -1542,8 +1455,9 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
     BA_LAUNCH(k_init_flagged, gg, gb, 0, h->stream, (const int*)h->c_pt.p, (const int*)h->p_cam.p, No, h->c_ptf[0].p, h->c_ptf[1].p,
               h->p_camf[0].p, h->p_camf[1].p);
   }
-  if (packed || (staged && No == 0 && ua.n_sections > 0)) {
-    // everything the device still reads sits in the pinned arena (the host vectors were copied into it): no need to wait
+  if (!unstaged && (packed || (staged && No == 0 && ua.n_sections > 0))) {
+    // everything the device still reads sits in the pinned arena (the host vectors were copied into it, none went to the
+    // device straight from its own memory): no need to wait
     // for the copy and the kernel -- whatever comes next is ordered behind them on the stream; the arena's next use
     // (the next ba_set_problem) waits for this event first
     if (!h->up_event) HIPCHECK(hipEventCreateWithFlags(&h->up_event, hipEventDisableTiming));
@@ -2003,7 +1917,7 @@ static void launch_pt_schur(ba_handle* h, bool robust, int mode, int k, double t
 // An eighth of the bytes on the wire for two launch-floor kernels.  Single rank: nothing.
 static int fold_and_reduce(ba_handle* h, double* parts, size_t n_per_part, double* msg, size_t msg_count) {
   if (!h->multi) return BA_OK;
-  if (!h->one_part) {        // (one_part: partitions 1 .. NPART-1 are empty, partition 0 already is the sum)
+  {
     Scope sc(h, BA_K_MISC);
     BA_LAUNCH(k_fold_parts, dim3((unsigned)((n_per_part + 255) / 256)), dim3(256), 0, h->stream, parts, n_per_part, NPART);
   }
@@ -2017,7 +1931,7 @@ static int exchange_partL(ba_handle* h, int buf, bool with_scalars = false) {
   {
     Scope sc(h, BA_K_MISC);
     BA_LAUNCH(k_fold_lin, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, with_scalars ? (const double*)h->scal.p : (const double*)nullptr,
-              (const double*)h->partL[buf].p, n, h->one_part ? 1 : NPART, h->linmsg[buf].p);
+              (const double*)h->partL[buf].p, n, NPART, h->linmsg[buf].p);
   }
   return allreduce(h, h->linmsg[buf].p, 8 + n);
 }
@@ -2037,7 +1951,7 @@ static int exchange_system(ba_handle* h, bool with_diag) {
   {
     Scope sc(h, BA_K_MISC);
     BA_LAUNCH(k_fold_msg, dim3((unsigned)((n6 + nE + 255) / 256)), dim3(256), 0, h->stream, (const double*)uy_ptr(h),
-              (const double*)p6_ptr(h), n6, (const double*)h->partE.p, nE, h->one_part ? 1 : NPART,
+              (const double*)p6_ptr(h), n6, (const double*)h->partE.p, nE, NPART,
               (const double*)h->partG[h->pb].p, h->Np > 0 ? h->nblkP + h->nblkL : 0, h->rank, h->world, h->sysmsg.p);
   }
   return allreduce(h, h->sysmsg.p, 2 + n6 + nE + (size_t)h->world);
@@ -2048,7 +1962,7 @@ static void launch_pcg_setup(ba_handle* h, double lambda, int precond, bool fina
   Scope sc(h, BA_K_PCG_UPDATE);
 #define SU_ARGS partL_of(h, h->lb), h->HccBc.p, bc_ptr(h), sys_p6(h), sys_E(h), nparts_of(h), h->cs[h->cur].p, lambda,           \
                 precond, h->Nc, h->fixed, h->Hccd.p, h->Minv.p, h->gvec.p, h->x.p, h->r.p, h->p.p, h->s.p,     \
-                h->z.p, h->camA[h->cur].p, h->partV.p, h->st.p, h->partGc.p, (h->two_level ? h->coarse_rc.p : (double*)nullptr), h->vx.p, \
+                h->z.p, h->camA[h->cur].p, h->partV.p, h->st.p, h->partGc.p, h->vx.p, \
                 cam_held_ptr(h)
 #define CALL_T(CM)                                                                                               \
   do {                                                                                                           \
@@ -2147,40 +2061,9 @@ extern "C" int ba_linearize(ba_handle* h, int32_t loss, double f_scale, double* 
   return BA_OK;
 }
 
-// Two-level preconditioner: E = P^T S P at the current damping, its banded factor and explicit inverse, then the first
-// PCG vectors redone with the coarse term (k_pcg_coarse with k = -1 writes the partials iteration 0's probe sums).
-static void coarse_build(ba_handle* h) {
-  const int n = 6 * h->n_agg;
-  const bool robust = h->lin_loss != BA_LOSS_LINEAR;
-  Scope sc(h, BA_K_PRECOND);
-  (void)hipMemsetAsync(h->coarseEint.p, 0, (size_t)n * n * sizeof(long long), h->stream);
-  BA_LAUNCH(k_coarse_diag, dim3(1), dim3(1024), 0, h->stream, (const double*)h->Hccd.p, h->Nc, h->fixed, h->n_agg, h->coarseEint.p,
-            h->coarse_info.p);
-  if (robust)
-    BA_LAUNCH(k_coarse_runs<true>, dim3((h->n_runs + 255) / 256), dim3(256), 0, h->stream, (const double*)h->cs[h->cur].p,
-              (const double*)h->ptab[h->cur].p, (const int*)h->run_beg.p, (const int*)h->run_pt.p, (const int*)h->p_camf[h->pb].p,
-              (const double2*)h->p_w[h->pb].p, h->K4[0], h->K4[1], h->fixed, h->n_runs, h->coarseU.p);
-  else
-    BA_LAUNCH(k_coarse_runs<false>, dim3((h->n_runs + 255) / 256), dim3(256), 0, h->stream, (const double*)h->cs[h->cur].p,
-              (const double*)h->ptab[h->cur].p, (const int*)h->run_beg.p, (const int*)h->run_pt.p, (const int*)h->p_cam.p,
-              (const double2*)h->p_w[h->pb].p, h->K4[0], h->K4[1], h->fixed, h->n_runs, h->coarseU.p);
-  BA_LAUNCH(k_coarse_pairs, dim3((h->n_pairs + 255) / 256), dim3(256), 0, h->stream, (const int2*)h->run_pairs.p, h->n_pairs,
-            (const int*)h->run_pt.p, (const int*)h->run_agg.p, (const double*)h->coarseU.p, (const double*)h->Hppinv[h->pb].p,
-            h->n_agg, (const double*)h->coarse_info.p, (unsigned long long*)h->coarseEint.p);
-  BA_LAUNCH(k_coarse_to_double, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, h->stream,
-            (const long long*)h->coarseEint.p, n, (const double*)h->coarse_info.p, h->coarseE.p);
-  BA_LAUNCH(k_coarse_cholesky, dim3(1), dim3(1024), 0, h->stream, h->coarseE.p, n, h->coarse_bw);
-  BA_LAUNCH(k_coarse_inverse, dim3((n + 63) / 64), dim3(64), 0, h->stream, (const double*)h->coarseE.p, n, h->coarse_bw,
-            h->coarseEinv.p);
-  BA_LAUNCH(k_pcg_coarse, dim3(h->n_agg), dim3(VEC_BLOCK), 0, h->stream, -1, (const double*)h->coarseEinv.p,
-            (const double*)h->coarse_rc.p, h->n_agg, (const double*)h->Hccd.p, (const double*)h->cs[h->cur].p, h->Nc, h->fixed,
-            (const double*)h->r.p, h->z.p, h->camA[h->cur].p, h->partV.p, nbv(h), (const double*)h->verdict.p, 0);
-}
-
 // --------------------------------------------------------------------- K4 test hooks
 // invert: (re)compute the damped point inverses (not needed right after launch_lin_pt at the
 // same lambda); finalize: Hcc | bc still have to be folded from the camera-half partials
-static void coarse_build(ba_handle* h);
 // keep = true (Schur-Jacobi only, ba_options.precond_lag): the preconditioner blocks in Minv stay as they are -- the
 // right-hand side W y0 then comes from the 6-sum camera pass (k_cam_schur) instead of the 27-sum one that also builds
 // the blocks' Schur terms, and k_pcg_setup neither folds them nor inverts anything
@@ -2190,7 +2073,6 @@ static int damped_system(ba_handle* h, double lambda, bool schur_diag, bool inve
   launch_cam_schur(h, h->lin_loss != BA_LOSS_LINEAR, diag_pass, false, 0, 0.0, 0);
   if (int rc = exchange_system(h, diag_pass)) return rc;
   launch_pcg_setup(h, lambda, schur_diag ? (keep ? 2 : 1) : 0, finalize);
-  if (h->two_level) coarse_build(h);
   if (schur_diag) h->stats[keep ? BA_STAT_PRECOND_REUSES : BA_STAT_PRECOND_BUILDS]++;
   return BA_OK;
 }
@@ -2282,7 +2164,6 @@ extern "C" int ba_solve(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     if (h->profile) flush_profile(h);
     h->profile = false;
     h->jac_f32 = false;
-    h->two_level = false;
     h->linearized = false;
     g_err = msg;
   }
@@ -2516,14 +2397,12 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     return fail(BA_ERR_INVALID, "bad options");
   if (opts->jacobian_precision != 0 && opts->jacobian_precision != 1)
     return fail(BA_ERR_INVALID, "jacobian_precision must be 0 (f64) or 1 (f32 blocks, f64 accumulation)");
-  if (opts->preconditioner < BA_PRECOND_JACOBI || opts->preconditioner > BA_PRECOND_TWO_LEVEL) return fail(BA_ERR_INVALID, "unknown preconditioner");
+  if (opts->preconditioner < BA_PRECOND_JACOBI || opts->preconditioner > BA_PRECOND_SCHUR_JACOBI) return fail(BA_ERR_INVALID, "unknown preconditioner");
   if (!(opts->pcg_model_tol >= 0.0 || opts->pcg_model_tol == -1.0) || opts->pcg_model_min_iters < 0)
     return fail(BA_ERR_INVALID, "bad pcg_model_tol (>= 0, or -1 = automatic) / pcg_model_min_iters");
   if (opts->precond_lag < 0) return fail(BA_ERR_INVALID, "precond_lag must not be negative");
   if (h->model == 0 && (h->cam_held_or & ~0x3fu))
     return fail(BA_ERR_INVALID, "camera mask bits 6-8 (f, k1, k2) need the BAL camera model");
-  if (h->model == 0 && opts->preconditioner == BA_PRECOND_TWO_LEVEL && (h->any_cam_held || h->any_pt_held))
-    return fail(BA_ERR_STATE, "the two-level preconditioner does not support held parameters (ba_set_held)");
   if (set_device(h)) return BA_ERR_HIP;
   memset(sum, 0, sizeof *sum);
   h->trace.clear();
@@ -2537,19 +2416,13 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   // window-sized problems: one launch, exact reduced solve -- no PCG, so preconditioner / jacobian_precision (validated
   // above) have nothing to act on, and no per-solve mode of the multi-kernel path is left switched on behind it
   h->jac_f32 = false;
-  h->two_level = false;
   if (h->model == 0 && small_applies(h, opts)) return small_solve(h, opts, sum);
-  // (the coarse level is built for the pinhole's 6x6 blocks; the BAL camera runs Schur-Jacobi under that option)
-  if (h->model == 0 && opts->preconditioner == BA_PRECOND_TWO_LEVEL && !h->two_level_ok)
-    return fail(BA_ERR_STATE, "the two-level preconditioner needs a band-structured problem on a single rank "
-                              "(ba_set_problem found none for this one)");
   h->jac_f32 = opts->jacobian_precision == 1;
   roctx_load();
   Range r_solve("ba_solve");
   const ba_loss loss = (ba_loss)opts->loss;
   const bool robust = loss != BA_LOSS_LINEAR;        // (the Schur passes only read the weights: the same for every non-linear loss)
   const bool schur_diag = opts->preconditioner != BA_PRECOND_JACOBI;
-  h->two_level = opts->preconditioner == BA_PRECOND_TWO_LEVEL && h->model == 0;
   const double fs = opts->f_scale;
   const int Nc = h->Nc;
   h->profile = opts->profile != 0;
@@ -2613,7 +2486,7 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   double lam_built = 0.0;
   double last_decrease = 1.0;      // relative cost decrease of the last accepted step
   int kept = 0, pcg_at_build = -1, pcg_last = -1;
-  const int lag = (schur_diag && !h->two_level) ? opts->precond_lag : 0;
+  const int lag = schur_diag ? opts->precond_lag : 0;
   bool need_linearize = true;      // a linearisation at the current parameters is needed before the next damped system
   bool have_lin = false;           // ... and buffer sets [lb] / [pb] already hold it (speculated at the trial point that was accepted)
   h->linearized = false;
@@ -2700,7 +2573,7 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     };
     // BA_IPC: the exchange of the Schur product happens inside k_pcg_step, workgroup by workgroup (ba_kernels.hpp,
     // "device-side all-reduce"); every workgroup's record has to fit its slot of the receive buffers
-    const bool use_ipc = h->ipc && h->multi && !h->two_level && nbv(h) <= IPC_MAX_BLOCKS &&
+    const bool use_ipc = h->ipc && h->multi && nbv(h) <= IPC_MAX_BLOCKS &&
                          (size_t)nbv(h) * (2 + (size_t)nb_of(h) * (h->model ? BalCam::VC : Pinhole::VC)) <= IpcComm::STRIDE;
     auto launch_rest = [&](int kk) -> int {
       launch_cam_schur(h, robust, false, true, kk, tol2, opts->pcg_min_iters);
@@ -2718,23 +2591,14 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
       } else if (int rc = exchange_schur(h)) return rc;
       Scope sc(h, BA_K_PCG_UPDATE);
       // (device-side exchange: k_cam_schur's raw partitions, folded inside the kernel; else partition 0 holds the all-reduced sums)
-      const int step_parts = use_ipc ? (h->one_part ? 1 : NPART) : nparts_of(h);
+      const int step_parts = use_ipc ? NPART : nparts_of(h);
 #define STEP_ARGS kk, (const double*)p6_ptr(h), step_parts, (const double*)uy_ptr(h), h->Hccd.p, h->Minv.p, h->cs[h->cur].p, Nc, h->fixed, tol2,       \
                   opts->pcg_min_iters, h->x.p, h->r.p, h->p.p, h->s.p, h->z.p, h->camA[h->cur].p, h->partV.p, nbv(h), h->st.p, \
-                  h->d_flags, base, (const double*)h->verdict.p
-#define STEP_TAIL h->vx.p, model_tol, opts->pcg_model_min_iters, ipc, h->d_flags + 6, cam_held_ptr(h)
-      if (h->two_level) {
-        BA_LAUNCH((k_pcg_step<Pinhole, true>), dim3(h->nblkV), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS, h->coarse_rc.p, STEP_TAIL);
-        BA_LAUNCH(k_pcg_coarse, dim3(h->n_agg), dim3(VEC_BLOCK), 0, h->stream, kk, (const double*)h->coarseEinv.p,
-                  (const double*)h->coarse_rc.p, h->n_agg, (const double*)h->Hccd.p, (const double*)h->cs[h->cur].p, Nc, h->fixed,
-                  (const double*)h->r.p, h->z.p, h->camA[h->cur].p, h->partV.p, nbv(h), (const double*)h->verdict.p, 1);
-      } else if (h->model) {
-        BA_LAUNCH((k_pcg_step<BalCam, false>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS, (double*)nullptr, STEP_TAIL);
-      } else {
-        BA_LAUNCH((k_pcg_step<Pinhole, false>), dim3(h->nblkV), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS, (double*)nullptr, STEP_TAIL);
-      }
+                  h->d_flags, base, (const double*)h->verdict.p, h->vx.p, model_tol, opts->pcg_model_min_iters, ipc, h->d_flags + 6,        \
+                  cam_held_ptr(h)
+      if (h->model) BA_LAUNCH((k_pcg_step<BalCam>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS);
+      else          BA_LAUNCH((k_pcg_step<Pinhole>), dim3(h->nblkV), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS);
 #undef STEP_ARGS
-#undef STEP_TAIL
       return BA_OK;
     };
     Range* r_pcg = new Range("pcg");
@@ -2878,7 +2742,6 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   if (h->profile) flush_profile(h);
   h->profile = false;
   h->jac_f32 = false;
-  h->two_level = false;
   return BA_OK;
 }
 

@@ -180,23 +180,7 @@ k_fold_lin(const double* __restrict__ scal6, const double* __restrict__ partL, s
 // a value (ba_set_problem checks all of them) the two streams are stored as float2 -- half the bytes of the linearisation
 // passes' largest input -- and widened on load: exactly the doubles the caller gave, so every result stays bit-identical.
 // Loads of the observation streams (index, pixel and weight arrays: every element is read once per pass, in order).
-// BA_STREAM_NT=1 marks them non-temporal, so that they do not push the gathered point records out of the XCD's L2.
-#ifndef BA_STREAM_NT
-#define BA_STREAM_NT 0
-#endif
-typedef double ba_d2v __attribute__((ext_vector_type(2)));
-typedef float ba_f2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ int ld_stream(const int* p) { return BA_STREAM_NT ? __builtin_nontemporal_load(p) : *p; }
-__device__ __forceinline__ double2 ld_stream(const double2* p) {
-  if (!BA_STREAM_NT) return *p;
-  const ba_d2v v = __builtin_nontemporal_load((const ba_d2v*)p);
-  return make_double2(v.x, v.y);
-}
-__device__ __forceinline__ float2 ld_stream(const float2* p) {
-  if (!BA_STREAM_NT) return *p;
-  const ba_f2v v = __builtin_nontemporal_load((const ba_f2v*)p);
-  return make_float2(v.x, v.y);
-}
+template <class T> __device__ __forceinline__ T ld_stream(const T* p) { return *p; }
 // "this double is a float32 value" (finite; out-of-range values are clamped first: a double -> float conversion outside
 // float's range is undefined in C++; NaN, infinities and anything beyond FLT_MAX keep the problem on double2)
 __host__ __device__ inline bool pixel_is_f32(double u) {
@@ -1372,12 +1356,7 @@ pt_schur_body(const double* __restrict__ camA, double* __restrict__ ptab, const 
         const int cc = ROBUST ? (c & IDX_MASK) : c;
         if (cc != fixed_cam) {
           double rowd[CM::SCH_ROW];
-#ifdef BA_EXP_NOCONFLICT
-          // diagnostic build only (wrong results): every 16 consecutive lanes read rows of 16 distinct bank classes
-          load_cam_row<CM::SCH_ROW, CM::TA>(use_lds, tab, camA, win.x, win.x + (int)(threadIdx.x & 15) + 16 * (cc & 31), rowd);
-#else
           load_cam_row<CM::SCH_ROW, CM::TA>(use_lds, tab, camA, win.x, cc, rowd);
-#endif
           JT row[CM::SCH_ROW];                   // Jacobian blocks in JT (double, or float for config 5)
 #pragma unroll
           for (int q = 0; q < CM::SCH_ROW; ++q) row[q] = (JT)rowd[q];
@@ -1591,7 +1570,6 @@ __device__ inline void slice_write_back(double* __restrict__ dst, const double* 
     else dst[2 * i] = lds[2 * i];
   }
 }
-static_assert(Pinhole::VC == 16, "the coarse level of ba_coarse.hpp and its oracle mirror assume aggregates of 16 cameras");
 static_assert(BalCam::VC == 16 || BalCam::VC == 8 || BalCam::VC == 4, "camera-vector workgroups: 4, 8 or 16 cameras per wave");
 constexpr int slice_chunks(int doubles) { return (doubles + 127) / 128; }      // double2 per lane that cover a slice
 
@@ -1610,11 +1588,9 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
             int use_schur_diag, int n_cams, int fixed_cam, double* __restrict__ Hccd, double* __restrict__ Minv,
             double* __restrict__ gvec, double* __restrict__ x, double* __restrict__ r, double* __restrict__ p,
             double* __restrict__ s, double* __restrict__ z, double* __restrict__ vtil,
-            double* __restrict__ partV, PcgState* __restrict__ st, double* __restrict__ partGc, double* __restrict__ rc,
+            double* __restrict__ partV, PcgState* __restrict__ st, double* __restrict__ partGc,
             double* __restrict__ vx, const unsigned short* __restrict__ cam_held) {
   constexpr int NB = CM::NB, NH = CM::NH, NL = CM::NL, VC = CM::VC;
-  // (rc != null: two-level preconditioner -- also the aggregate's restricted right-hand side; z, partV and vtil written
-  // here are then the single-level ones and are redone by k_pcg_coarse once E^-1 exists)
   // LDS image of the workgroup's VC cameras.  Inputs: partition-folded sums (a: NL of the linearisation when
   // FINALIZE, e: NH Schur-Jacobi, w6: NB of W y0), Hcc | bc (when not FINALIZE), cs.  Outputs staged for a
   // coalesced write-back: Hcc | bc (FINALIZE), Hccd, Minv, g = r, z (x = p = s = 0 written directly).
@@ -1680,9 +1656,6 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
   }
   __syncthreads();
   double acc[2] = {0, 0};
-  double gsum[NB];
-#pragma unroll
-  for (int q = 0; q < NB; ++q) gsum[q] = 0.0;
   double gmc = 0.0;
   const int t = threadIdx.x;
   if (c < n_cams) {
@@ -1730,17 +1703,8 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
       l_z[NB * t + q] = zz[q];
       acc[0] += g[q] * zz[q];
       acc[1] += zz[q] * hz[q];
-      gsum[q] = g[q];
     }
     write_vtil<NB>(M, zz, vtil + CM::TA * (size_t)c + CM::VOFF);
-  }
-  if (rc) {
-#pragma unroll
-    for (int q = 0; q < NB; ++q) gsum[q] = wave_total_dpp(gsum[q]);
-    if (threadIdx.x == 0) {
-#pragma unroll
-      for (int q = 0; q < NB; ++q) rc[NB * blockIdx.x + q] = gsum[q];
-    }
   }
   __syncthreads();
   // ---- coalesced write-back
@@ -1780,9 +1744,7 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
 // Every workgroup recomputes the scalars from the same words; workgroup 0 publishes the
 // next state into the other parity slot.  uy_src: the u.y word (folded by k_cam_schur's
 // extra workgroup, or all-reduced in a multi-rank job).
-// COARSE (two-level preconditioner, ba_coarse.hpp): the kernel stops after r and zJ = M_J^-1 r and leaves the
-// aggregate's restricted residual in rc; z, the dot products and vtil are finished by k_pcg_coarse.
-template <class CM, bool COARSE>
+template <class CM>
 __global__ void __launch_bounds__(VEC_BLOCK)
 k_pcg_step(int k, const double* __restrict__ part6, int nparts, const double* __restrict__ uy_src,
            const double* __restrict__ Hccd, const double* __restrict__ Minv, const double* __restrict__ cs,
@@ -1790,7 +1752,7 @@ k_pcg_step(int k, const double* __restrict__ part6, int nparts, const double* __
            double* __restrict__ x, double* __restrict__ r, double* __restrict__ p, double* __restrict__ s,
            double* __restrict__ z, double* __restrict__ vtil, double* __restrict__ partV, int nblkV,
            PcgState* __restrict__ st, long long* __restrict__ host_flag, long long flag_base,
-           const double* __restrict__ verdict, double* __restrict__ rc, double* __restrict__ vx,
+           const double* __restrict__ verdict, double* __restrict__ vx,
            double model_tol, int model_min_iters, IpcStep ipc, long long* __restrict__ err_flag,
            const unsigned short* __restrict__ cam_held) {
   // ipc.on (multi-rank, device-side exchange): part6 / uy_src are this rank's own sums; the other ranks' arrive in the
@@ -1891,9 +1853,6 @@ k_pcg_step(int k, const double* __restrict__ part6, int nparts, const double* __
   const double alpha = gamma / denom;
   __syncthreads();                                      // the LDS image is complete
   double acc[2] = {0, 0};
-  double rsum[NB];
-#pragma unroll
-  for (int q = 0; q < NB; ++q) rsum[q] = 0.0;
   const int t = threadIdx.x;
   if (live) {
     const double* M = l_cs + CS * t + 12;
@@ -1937,30 +1896,18 @@ k_pcg_step(int k, const double* __restrict__ part6, int nparts, const double* __
       rr[q] -= alpha * ss[q];
     }
     symN_mul<NB>(mi, rr, zz);
-    if (!COARSE) symN_mul<NB>(h, zz, hz);
+    symN_mul<NB>(h, zz, hz);
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
       l_v[0][NB * t + q] = zz[q]; l_v[1][NB * t + q] = pp[q]; l_v[2][NB * t + q] = ss[q];
       l_v[3][NB * t + q] = rr[q]; l_v[4][NB * t + q] = xx[q];
-      if (!COARSE) {
-        acc[0] += rr[q] * zz[q];
-        acc[1] += zz[q] * hz[q];
-      } else {
-        rsum[q] = rr[q];
-      }
+      acc[0] += rr[q] * zz[q];
+      acc[1] += zz[q] * hz[q];
     }
-    if (!COARSE) write_vtil<NB>(M, zz, vtil + CM::TA * (size_t)c + CM::VOFF);
+    write_vtil<NB>(M, zz, vtil + CM::TA * (size_t)c + CM::VOFF);
     // the iterate itself in the point passes' form, (M x_r, x_t, ..): what the back substitution multiplies with once PCG
     // has stopped -- kept current here so that no kernel has to run between the last PCG iteration and the step
     write_vtil<NB>(M, xx, vx + NB * (size_t)c);
-  }
-  if (COARSE) {                                         // restricted residual of this aggregate (= this workgroup)
-#pragma unroll
-    for (int q = 0; q < NB; ++q) rsum[q] = wave_total_dpp(rsum[q]);
-    if (threadIdx.x == 0) {
-#pragma unroll
-      for (int q = 0; q < NB; ++q) rc[NB * blockIdx.x + q] = rsum[q];
-    }
   }
   __syncthreads();
   {                                                     // the five vectors back, coalesced (fixed camera: unchanged image)
@@ -1972,11 +1919,9 @@ k_pcg_step(int k, const double* __restrict__ part6, int nparts, const double* __
 #pragma unroll
   for (int q = 0; q < 2; ++q) acc[q] = wave_total_dpp(acc[q]);
   if (threadIdx.x == 0) {
-    if (!COARSE) {
-      double* pv = partV + (size_t)((k + 1) & 1) * 2 * nblkV;
-      pv[2 * blockIdx.x] = acc[0];
-      pv[2 * blockIdx.x + 1] = acc[1];
-    }
+    double* pv = partV + (size_t)((k + 1) & 1) * 2 * nblkV;
+    pv[2 * blockIdx.x] = acc[0];
+    pv[2 * blockIdx.x + 1] = acc[1];
     if (blockIdx.x == 0) {
       PcgState o = sin;
       o.gamma_prev = gamma; o.alpha_prev = alpha;

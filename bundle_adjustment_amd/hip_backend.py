@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BA_HIP_LIB") or os.path.join(_HERE, "libba_hip.so")   # BA_HIP_LIB: another build of the same ABI
 
 LOSS = {"linear": 0, "huber": 1, "soft_l1": 2, "cauchy": 3, "arctan": 4}    # scipy least_squares' losses (enum ba_loss)
-PRECOND = {"jacobi": 0, "schur_jacobi": 1, "two_level": 2}
+PRECOND = {"jacobi": 0, "schur_jacobi": 1}
 STATUS_NAMES = {0: "max_iters", 1: "ftol", 2: "xtol", 3: "gtol"}
 PROFILE_SLOTS = 16
 K_RESIDUAL, K_LINEARIZE_CAM, K_LINEARIZE_PT, K_POINT_INVERT, K_SCHUR_PT, K_SCHUR_CAM = 1, 2, 3, 4, 5, 6
@@ -34,6 +34,15 @@ def loss_code(loss):
             raise ValueError(f"unknown loss {loss!r}: expected one of {', '.join(map(repr, LOSS))}")
         return LOSS[loss]
     return loss
+
+
+def precond_code(precond):
+    """enum ba_precond value of a preconditioner given by name (or already by value); an unknown name raises ValueError."""
+    if isinstance(precond, str):
+        if precond not in PRECOND:
+            raise ValueError(f"unknown preconditioner {precond!r}: expected one of {', '.join(map(repr, PRECOND))}")
+        return PRECOND[precond]
+    return precond
 
 
 class BAOptions(C.Structure):
@@ -353,7 +362,7 @@ class Solver:
             if k == "loss":
                 v = loss_code(v)
             if k == "preconditioner":
-                v = PRECOND[v] if isinstance(v, str) else v
+                v = precond_code(v)
             if not hasattr(o, k):
                 raise TypeError(f"unknown option {k}")
             setattr(o, k, v)

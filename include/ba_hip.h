@@ -44,13 +44,8 @@ enum ba_status {
  * linear z, huber z <= 1 ? z : 2 sqrt(z) - 1, soft_l1 2 (sqrt(1 + z) - 1), cauchy log(1 + z), arctan atan(z). */
 enum ba_loss { BA_LOSS_LINEAR = 0, BA_LOSS_HUBER = 1, BA_LOSS_SOFT_L1 = 2, BA_LOSS_CAUCHY = 3, BA_LOSS_ARCTAN = 4 };
 /* JACOBI: blocks of Hcc + lambda D.  SCHUR_JACOBI (default): the diagonal blocks of the reduced camera matrix S.
- * TWO_LEVEL: Schur-Jacobi plus an additive coarse correction P E^-1 P^T over aggregates of 16 consecutive cameras,
- * E = P^T S P, for band-structured problems (sequential captures such as BASELINE config 5, where block
- * preconditioners leave the drift modes along the chain): 2-5x fewer PCG iterations at equal damping; the coarse
- * matrix is rebuilt and inverted per damped system, which only pays off when a solve spends hundreds of PCG
- * iterations per LM iteration.  ba_solve returns BA_ERR_STATE when ba_set_problem found no band
- * structure (mean camera span of a track above Nc / 8) or the job has several ranks. */
-enum ba_precond { BA_PRECOND_JACOBI = 0, BA_PRECOND_SCHUR_JACOBI = 1, BA_PRECOND_TWO_LEVEL = 2 };
+ * Any other value is refused by ba_solve and ba_solve_bal (BA_ERR_INVALID). */
+enum ba_precond { BA_PRECOND_JACOBI = 0, BA_PRECOND_SCHUR_JACOBI = 1 /* 2: retired (BA_PRECOND_TWO_LEVEL) */ };
 
 /* Solver knobs.  The reference's literals at src/bundle_adjuster.py:170-174 are
  * loss='huber' (f_scale 1), xtol = ftol = 1e-5, max_nfev = 50. */
@@ -223,8 +218,8 @@ int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64_t n_obs,
  * entries).  fixed_cam holds its camera in addition to the masks.  The masks belong to the handle: they survive
  * ba_set_params and repeated solves; ba_set_problem clears them, and so does ba_set_held(h, NULL, NULL).
  * Bits 9-15 are refused here; bits 6-8 by the pinhole solve / linearisation that meets them (BA_ERR_INVALID).
- * BA_PRECOND_TWO_LEVEL with any mask is refused by ba_solve (BA_ERR_STATE).  Multi-rank jobs: cam_held covers ALL cameras
- * and must be the same on every rank (the caller's obligation); pt_held is per shard, in the shard's local point order. */
+ * Multi-rank jobs: cam_held covers ALL cameras and must be the same on every rank (the caller's obligation); pt_held is
+ * per shard, in the shard's local point order. */
 int ba_set_held(ba_handle* h, const uint16_t* cam_held, const uint8_t* pt_held);
 int ba_set_params(ba_handle* h, const double* cams, const double* pts);
 int ba_get_params(ba_handle* h, double* cams, double* pts);
@@ -260,9 +255,8 @@ int ba_linearize_bal(ba_handle* h, const double* intr, int32_t loss, double f_sc
 /* The solve step for the BAL 9-parameter camera: the SAME kernels and host loop as ba_solve, instantiated for the second
  * camera model of csrc/ba_models.hpp (BalCam; kernels in csrc/ba_kernels.hpp are templates over the model): LM + Schur
  * complement + matrix-free PCG with 9x9 camera blocks, device-side PCG / LM verdicts, speculated linearisation;
- * preconditioner BA_PRECOND_JACOBI (damped 9x9 camera blocks) or Schur-Jacobi (their Schur complements: the default;
- * BA_PRECOND_TWO_LEVEL means Schur-Jacobi here).  Same damping / gain-ratio / stopping rules, options, summary and trace as
- * ba_solve; jacobian_precision is honoured (1 = BASELINE config 5's "fp32 Jacobian + fp64 solve"); small_solver is ignored
+ * preconditioner BA_PRECOND_JACOBI (damped 9x9 camera blocks) or Schur-Jacobi (their Schur complements: the default).
+ * Same damping / gain-ratio / stopping rules, options, summary and trace as ba_solve; jacobian_precision is honoured (1 = BASELINE config 5's "fp32 Jacobian + fp64 solve"); small_solver is ignored
  * (the window solver is built for the reference's pinhole only).  Multi-rank jobs are supported exactly as in ba_solve
  * (landmark shards, the same all-reduces; fold sizes follow the 9-parameter blocks).  Cameras (rvec, t) and points are the
  * handle's (ba_set_params before, ba_get_params after); intr double[Nc][3] = (f, k1, k2) per camera is read AND updated.

@@ -323,7 +323,9 @@ def test_errors_and_clearing(solver):
     with pytest.raises(hip_backend.BAHipError, match="error -1: .*f, k1, k2"):
         solver.linearize("huber")
     solver.set_held(points=np.arange(p.n_pts) % 5 == 0)
-    with pytest.raises(hip_backend.BAHipError, match="error -3: .*two-level"):          # BA_ERR_STATE
+    with pytest.raises(hip_backend.BAHipError, match="error -1: .*unknown preconditioner"):   # BA_ERR_INVALID: value 2 is retired
+        solver.solve(loss="huber", max_iters=3, preconditioner=2, small_solver=1)
+    with pytest.raises(ValueError, match="unknown preconditioner 'two_level'"):
         solver.solve(loss="huber", max_iters=3, preconditioner="two_level", small_solver=1)
     kw = dict(loss="huber", max_iters=8, small_solver=1)
     with hip_backend.Solver(0) as plain:

@@ -50,17 +50,17 @@ json.dump(out, open(os.path.join(%(out)r, f"out_{rank}.json"), "w"))
 s.set_params(sub.cams, sub.pts)
 out2 = s.solve(loss="huber", max_iters=25, ftol=0.0, xtol=0.0, gtol=float(os.environ["TEST_GTOL"]), pcg_tol=1e-3, preconditioner="jacobi")
 json.dump(out2, open(os.path.join(%(out)r, f"out2_{rank}.json"), "w"))
-json.dump(s.stats(), open(os.path.join(%(out)r, f"stats_{rank}.json"), "w"))
+json.dump(dict(s.stats(), build_path=s.debug_layout("scalars")["build_path"]), open(os.path.join(%(out)r, f"stats_{rank}.json"), "w"))
 s.close()
 dist.barrier()
 dist.destroy_process_group()
 """
 
 
-@pytest.mark.parametrize("one_part,ipc", [("0", "0"), ("1", "0"), ("0", "1"), ("1", "1")])
-def test_two_ranks_on_one_gpu_match_single_rank(tmp_path, one_part, ipc):
-    """one_part = 1: every camera's shard-local observations in partition 0 (BA_ONE_PART, an experiment switch of
-    ba_set_problem): partial sums come out folded, no fold kernel runs ahead of the all-reduces.
+@pytest.mark.parametrize("device_setup,ipc", [("0", "0"), ("1", "0"), ("0", "1"), ("1", "1")])
+def test_two_ranks_on_one_gpu_match_single_rank(tmp_path, device_setup, ipc):
+    """device_setup = 1 (BA_SETUP=device): every rank lays out its shard with the device build of ba_set_problem, whose
+    band statistic is a collective like the host build's (the shards here are below the size that picks it by default).
     ipc = 1 (BA_IPC): the per-PCG-iteration exchange of the reduced camera system's product does not go through the
     transport's all-reduce but through IPC-mapped peer buffers -- every rank's fold kernel stores its share and a sequence
     flag into the other rank's receive buffer (hipIpcGetMemHandle / hipIpcOpenMemHandle between the two processes on this
@@ -85,7 +85,7 @@ def test_two_ranks_on_one_gpu_match_single_rank(tmp_path, one_part, ipc):
                 ref2 = cand
                 break
     assert ref2 is not None and ref2["iterations"] < 25
-    env = dict(os.environ, BA_COMM="shm", BA_ONE_PART=one_part, BA_IPC=ipc, TEST_GTOL=repr(gtol))
+    env = dict(os.environ, BA_COMM="shm", BA_SETUP="device" if device_setup == "1" else "host", BA_IPC=ipc, TEST_GTOL=repr(gtol))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", _free_port(), str(script)]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
@@ -98,6 +98,7 @@ def test_two_ranks_on_one_gpu_match_single_rank(tmp_path, one_part, ipc):
     stats = [json.load(open(tmp_path / f"stats_{k}.json")) for k in range(2)]
     for st in stats:                                         # one exchange per PCG iteration went through the peer buffers, or none
         assert (st["ipc_exchanges"] >= outs[0]["pcg_iterations"]) if ipc == "1" else (st["ipc_exchanges"] == 0), st
+        assert st["build_path"] == int(device_setup), st              # 0 host build, 1 device build
     # every rank reports the same global costs / iteration counts
     for key in ("iterations", "accepted", "pcg_iterations", "initial_sse", "final_sse", "final_cost"):
         assert outs[0][key] == outs[1][key], key

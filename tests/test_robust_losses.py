@@ -1,5 +1,5 @@
-"""CPU: the loss names the Python layer accepts, the C enum behind them, and the tests' numpy statement of scipy's losses
-(tests/robust_losses.py) against scipy's own loss functions."""
+"""CPU: the loss (and preconditioner) names the Python layer accepts, the C enums behind them, and the tests' numpy
+statement of scipy's losses (tests/robust_losses.py) against scipy's own loss functions."""
 import importlib
 import os
 import re
@@ -42,6 +42,11 @@ def test_options_reject_unknown_loss_before_any_device_call():
     assert s._options(dict(loss="cauchy")).loss == 3
     with pytest.raises(ValueError):
         s._options(dict(loss="tukey"))
+    assert s._options(dict(preconditioner="jacobi")).preconditioner == 0
+    assert s._options(dict(preconditioner=1)).preconditioner == 1        # by value: passed through, the library validates it
+    for bad in ("two_level", "bogus"):                                    # two_level: retired (enum value 2)
+        with pytest.raises(ValueError, match="'jacobi', 'schur_jacobi'"):
+            s._options(dict(preconditioner=bad))
 
 
 def test_bundle_adjuster_rejects_unknown_loss_at_construction():
@@ -50,6 +55,8 @@ def test_bundle_adjuster_rejects_unknown_loss_at_construction():
         BundleAdjuster(K, loss="bogus")
     for name in rl.LOSSES:
         assert BundleAdjuster(K, loss=name).solver_options["loss"] == name
+    with pytest.raises(ValueError, match="two_level"):
+        BundleAdjuster(K, preconditioner="two_level")
 
 
 def test_header_enum_matches_backend_names():
@@ -58,6 +65,9 @@ def test_header_enum_matches_backend_names():
     body = re.search(r"enum ba_loss \{(.*?)\};", hdr, flags=re.S).group(1)
     enum = {k.lower(): int(v) for k, v in re.findall(r"BA_LOSS_([A-Z_0-9]+)\s*=\s*(\d+)", body)}
     assert enum == hb.LOSS
+    body = re.search(r"enum ba_precond \{(.*?)\};", hdr, flags=re.S).group(1)
+    enum = {k.lower(): int(v) for k, v in re.findall(r"BA_PRECOND_([A-Z_0-9]+)\s*=\s*(\d+)", body)}
+    assert enum == hb.PRECOND
 
 
 @pytest.mark.parametrize("loss", rl.LOSSES[1:])

@@ -2,7 +2,7 @@
 """A rank's share of a multi-GPU job, timed on ONE GPU: a communicator of one rank (BA_COMM_FORCE=1 semantics: every
 all-reduce of the multi-rank control flow is issued) over a shard of C3 -- all 1000 cameras, 100000 / N points.
 
-    python tools/shard_times.py N [N ...]          # BA_ONE_PART=0/1 forces the partition layout
+    python tools/shard_times.py N [N ...]
 """
 import os
 import sys

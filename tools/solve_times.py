@@ -12,13 +12,12 @@ for cfg in (sys.argv[1:] or ["C2", "C3", "C5"]):
     with hb.Solver(0) as s:
         for label, kw in (("reference tolerances", dict()),
                           ("to convergence", dict(max_iters=100, ftol=1e-12, xtol=1e-12, gtol=0.0, pcg_tol=1e-2, pcg_max_iters=1000))):
-            for pc in (("schur_jacobi", "two_level") if cfg == "C5" else ("schur_jacobi",)):
-                s.set_problem(p)
-                s.solve(preconditioner=pc, **kw)               # warm (first launches of each kernel)
-                s.set_problem(p)
-                out = s.solve(preconditioner=pc, **kw)
-                tr = s.trace()
-                print(f"{cfg} {p.n_cams}/{p.n_pts}/{p.n_obs} {label:22s} {pc:13s}: {out['iterations']:3d} LM it ({out['accepted']} accepted), "
-                      f"{out['pcg_iterations']:5d} PCG it, {1e3 * out['seconds_total']:8.2f} ms, status {out['status_name']}, "
-                      f"RMSE {np.sqrt(out['initial_sse'] / p.n_obs):.3f} -> {np.sqrt(out['final_sse'] / p.n_obs):.6f} px, "
-                      f"PCG per LM {[t['pcg_iterations'] for t in tr][:12]}", flush=True)
+            s.set_problem(p)
+            s.solve(**kw)                                  # warm (first launches of each kernel)
+            s.set_problem(p)
+            out = s.solve(**kw)
+            tr = s.trace()
+            print(f"{cfg} {p.n_cams}/{p.n_pts}/{p.n_obs} {label:22s}: {out['iterations']:3d} LM it ({out['accepted']} accepted), "
+                  f"{out['pcg_iterations']:5d} PCG it, {1e3 * out['seconds_total']:8.2f} ms, status {out['status_name']}, "
+                  f"RMSE {np.sqrt(out['initial_sse'] / p.n_obs):.3f} -> {np.sqrt(out['final_sse'] / p.n_obs):.6f} px, "
+                  f"PCG per LM {[t['pcg_iterations'] for t in tr][:12]}", flush=True)
