@@ -152,7 +152,6 @@ struct DBuf {
 struct ba_handle {
   int device = 0;
   int n_cu = 256;              // compute units of the device (hipDeviceAttributeMultiprocessorCount)
-  int xcd_ranges = 1;          // point-pass ranges grouped per XCD (BA_XCD_RANGES=0 turns it off; speed only)
   int model = 0;               // camera model of the running call: 0 = the reference's pinhole (Pinhole), 1 = BAL 9-parameter
                                // (BalCam, ba_models.hpp); every kernel of the loop is instantiated for both
   int lanes = LPP;             // lanes per point in the point passes: 2, or 4 / 8 / 16 for every point of a smaller problem
@@ -227,7 +226,7 @@ struct ba_handle {
   bool banded = false;         // mean camera span of a track <= Nc / 8 (sequential captures): pcg_model_tol's automatic default
   DBuf<double> dev_lam;        // device word a riding k_scalars stores the next damping in; 0 = not yet (ba_kernels.hpp, ScalarsArgs::lam_slot)
   DBuf<double> verdict;        // PCG verdict words {gamma, zeta, finished, -} x 2 iteration parities (point pass -> camera pass, vector kernel)
-  int cam_segl = 64;           // lanes per (camera, partition) segment in the PCG camera pass (BA_CAM_SEGL, tuning)
+  int cam_segl = 64;           // lanes per (camera, partition) segment in the PCG camera pass: 16 or 64
   int nblkP = 1, ppb = 1, nblkV = 1;   // nblkV: camera-vector workgroups of the pinhole (VEC_CAMS cameras each)
   int nblkVm[2] = {1, 1};              // ... per camera model (CM::VC cameras each)
   size_t lds_bytes_m[2] = {0, 0};   // dynamic LDS of the point passes (largest window that fits), per camera model (row strides differ)
@@ -751,19 +750,16 @@ static PtGrid config_point_grid(ba_handle* h, int Nc, int Np, int No) {
   h->nblkP = std::min(want, 4096);
   if (table_fits) h->nblkP = std::min(h->nblkP, h->n_cu * per_cu);
   if (const char* e = getenv("BA_PT_BLOCKS")) h->nblkP = std::max(1, std::min(want, atoi(e)));
-  if (const char* e = getenv("BA_XCD_RANGES")) h->xcd_ranges = atoi(e) != 0;
   // lanes per (camera, partition) segment in the PCG camera pass: a wave, or a 16-lane row when segments are short
   // (config 5: ~48 observations per segment -- a wave would walk it in one step with a quarter of its lanes idle and
   // pay the 64-lane reduction of every sum for it; measured 13.4 -> 12.1 us, C3's ~125-observation segments keep the wave)
   h->cam_segl = (Nc > 0 && (long long)No / Nc / NPART < 64) ? 16 : 64;
-  if (const char* e = getenv("BA_CAM_SEGL")) { const int v = atoi(e); if (v == 16 || v == 32 || v == 64) h->cam_segl = v; }
   h->ppb = std::max(1, (Np + h->nblkP - 1) / h->nblkP);
   return PtGrid{table_fits, per_cu, pts_per_pass, want};
 }
 // part 2a: the track length above which a point gets a 16-lane row of its own (med = element Np / 2 of the sorted lengths)
 static void config_long_threshold(ba_handle* h, int med) {
-  const char* e = getenv("BA_LONG_TRACK");
-  h->long_thr = e ? std::max(1, atoi(e)) : std::max(8, 2 * med);
+  h->long_thr = std::max(8, 2 * med);
   if (h->lanes != LPP) h->long_thr = 0x7fffffff;           // more lanes per point already: no separate long-track rows
 }
 // part 2b: how the long tracks are dealt to workgroups, and -- when ranges plus long-track workgroups would not all be
@@ -855,6 +851,7 @@ static int alloc_solver_buffers(ba_handle* h) {
 // point numbering is kept then); bit-equal to the host build (tests/test_gpu_setup.py).
 constexpr int SETUP_HIST_BINS = 4096;
 constexpr size_t SETUP_PINNED_BYTES = 128 * 1024;
+constexpr long SETUP_DEVICE_MIN_OBS = 50000;   // smallest problem ba_set_problem lays out on the device (unless BA_SETUP says)
 // BA_PIXELS=f64 keeps the pixel streams double2 whatever the values (A / B measurements, tests)
 static bool uv_f32_wanted() {
   const char* e = getenv("BA_PIXELS");
@@ -946,7 +943,7 @@ static int set_problem_device(ba_handle* h, int Nc, int Np, int No, const int32_
     dev_scan(h, S + o_flag, Np, S + o_bsum, S + o_pos);
     BA_LAUNCH(k_setup_long_list, gp, b256, 0, h->stream, (const int*)h->pt_off.p, Np, h->long_thr, (const int*)(S + o_pos), h->long_pts.p);
   }
-  if (h->lanes == LPP && !getenv("BA_NO_BANK_ORDER")) {
+  if (h->lanes == LPP) {
     const long long nthreads = (long long)h->nblkP * ((h->ppb + 15) / 16) * 2;
     BA_LAUNCH(k_setup_bank_order, dim3((unsigned)((nthreads + 255) / 256)), b256, 0, h->stream, (const int*)h->pt_off.p, Np, h->nblkP, h->ppb,
               h->p_cam.p, p_src);
@@ -982,7 +979,6 @@ static int set_problem_device(ba_handle* h, int Nc, int Np, int No, const int32_
   unsigned long long st2[2];
   memcpy(st2, h->h_setup, sizeof st2);
   h->cam_band = st2[1] > st2[0];
-  if (const char* e = getenv("BA_CAM_BAND")) h->cam_band = atoi(e) != 0;
   {
     const int2* win = (const int2*)(h->h_setup + 64);
     size_t max_win[2] = {0, 0};
@@ -1059,15 +1055,14 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
   h->banded_known = false;
   h->uv_f32 = false;
   // Large problems whose camera table fits in LDS are laid out ON THE DEVICE (set_problem_device, ba_setup.hpp: one upload
-  // of the caller's arrays, no host sorts; bit-equal result).  BA_SETUP=host / device forces a path (device: whenever the
-  // problem qualifies at all), BA_SETUP_DEVICE_MIN moves the size from which it is chosen (default 50 000 observations:
-  // the measured crossover is near 40 000 -- 0.23 against 0.27 ms at 48 k, 0.40 against 1.05 ms at 160 k).
+  // of the caller's arrays, no host sorts; bit-equal result) from SETUP_DEVICE_MIN_OBS observations on (the measured
+  // crossover is near 40 000 -- 0.23 against 0.27 ms at 48 k, 0.40 against 1.05 ms at 160 k).  BA_SETUP=host / device
+  // forces a path (device: whenever the problem qualifies at all).
   {
-    static const long dev_min = [] { const char* e = getenv("BA_SETUP_DEVICE_MIN"); return e ? atol(e) : 50000L; }();
     const char* mode = getenv("BA_SETUP");
     bool try_dev = n_obs > 0 && n_pts > 0 && n_cams > MW_MAX_CAMS && (size_t)n_cams * TA * sizeof(double) <= (size_t)LDS_TAB_BYTES;
     if (mode && strcmp(mode, "host") == 0) try_dev = false;
-    else if (!(mode && strcmp(mode, "device") == 0) && n_obs < dev_min) try_dev = false;
+    else if (!(mode && strcmp(mode, "device") == 0) && n_obs < SETUP_DEVICE_MIN_OBS) try_dev = false;
     if (try_dev) {
       h->small_np_pad = -1;
       const int rc = set_problem_device(h, n_cams, n_pts, (int)n_obs, cam_idx, pt_idx, uv, K4, fixed_cam, timed);
@@ -1156,7 +1151,7 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
   // greedily per group of eight points and per step, so that the sixteen rows read together are in distinct classes
   // wherever the data allows.  Pure scheduling: every sum keeps a fixed order, results stay bit-reproducible.
   auto bank_aware_order = [&](std::vector<int>& p_cam, std::vector<int>& p_src, const std::vector<int>& pt_off) {
-    if (h->lanes != LPP || !table_fits || getenv("BA_NO_BANK_ORDER")) return;
+    if (h->lanes != LPP || !table_fits) return;
     // ds_read_b128 is served in groups of SIXTEEN CONSECUTIVE LANES (measured on MI355X, tools/microbench/lds_b128_groups.hip:
     // rows with distinct bank classes inside every 16 consecutive lanes read as fast as a broadcast, 14.3 cycles per
     // instruction against 23.8 for random rows; distinct classes inside the lane sets {0-3,12-15,20-27} / {4-11,16-19,28-31}
@@ -1211,7 +1206,7 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
   }
   // long tracks: one DPP row (16 lanes) per point in a launch of their own
   std::vector<int> long_pts;
-  {   // long = more than max(8, 2 x median track length) observations (BA_LONG_TRACK overrides)
+  {   // long = more than max(8, 2 x median track length) observations
     std::vector<int> len(Np);
     for (int p = 0; p < Np; ++p) len[p] = pt_off[p + 1] - pt_off[p];
     int med = 0;
@@ -1269,7 +1264,6 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
       }
     }
     h->cam_band = in_band > in_partition;
-    if (const char* e = getenv("BA_CAM_BAND")) h->cam_band = atoi(e) != 0;
   }
   stage("partitions + XCD statistic");
   {   // band statistic: mean camera span of a track against the number of cameras (sequential captures: a few
@@ -1370,11 +1364,10 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
   HIPCHECK(h->long_pts.alloc(std::max(h->n_long, 1)));
   if (h->n_long) HIPCHECK(upload(h->long_pts.p, long_pts.data(), h->n_long * sizeof(int)));
   // the multi-workgroup window solver (ba_small_mw.hpp): eight cameras at most, up to 2048 landmarks in ranges of 64, no
-  // landmark seen twice by one camera; every camera's list is ascending in landmark index, so a range is a slice of it
+  // landmark seen twice by one camera; every camera's list is ascending in landmark index, so a range is a slice of it.
+  // No lower limit on landmarks (measured: no slower than k_small_lm even with one or two workgroups).
   h->mw_ok = false;
-  const char* mw_min_env = getenv("BA_SMALL_MW_MIN");            // (tuning: smallest landmark count that goes to k_small_mw)
-  const int mw_min_pts = mw_min_env ? std::max(1, atoi(mw_min_env)) : MW_MIN_PTS;
-  if (!h->multi && Nc <= MW_MAX_CAMS && Np >= mw_min_pts && Np <= MW_MAX_WG * MW_PTS && No > 0) {
+  if (!h->multi && Nc <= MW_MAX_CAMS && Np <= MW_MAX_WG * MW_PTS && No > 0) {
     bool dup = false;
     for (int p = 0; p < Np && !dup; ++p) {
       unsigned seen = 0;
@@ -1732,7 +1725,7 @@ static void launch_lin_finalize(ba_handle* h) {
 #undef CALL_T
 }
 static PtWork pt_work(ba_handle* h) {        // every point; long tracks skipped when they have a launch of their own
-  return PtWork{nullptr, h->Np, h->nblkL ? h->long_thr : 0x7fffffff, 0, h->ppb, h->xcd_ranges};
+  return PtWork{nullptr, h->Np, h->nblkL ? h->long_thr : 0x7fffffff, 0, h->ppb, /*xcd_ranges=*/1};
 }
 static PtWork pt_work_long(ba_handle* h) { return PtWork{h->long_pts.p, h->n_long, 0x7fffffff, h->nblkP, h->long_spb, 0}; }
 // point half at parameter set `w` into point-buffer set `pbuf`, with the damped inverse / y0 at `lambda` fused in
@@ -1819,7 +1812,6 @@ static void launch_cam_schur_t(ba_handle* h, bool robust, bool diag, bool pcg, i
 #define CS_PCG(R, JT)                                                                                       \
   do {                                                                                                      \
     if (segl == 16) BA_LAUNCH((k_cam_schur<CM, R, true, JT, 16>), g, b, 0, h->stream, CS_ARGS);        \
-    else if (segl == 32) BA_LAUNCH((k_cam_schur<CM, R, true, JT, 32>), g, b, 0, h->stream, CS_ARGS);   \
     else BA_LAUNCH((k_cam_schur<CM, R, true, JT, 64>), g, b, 0, h->stream, CS_ARGS);                   \
   } while (0)
   if (diag) {
@@ -2172,13 +2164,12 @@ extern "C" int ba_solve(ba_handle* h, const ba_options* opts, ba_summary* sum) {
 // Sliding-window-sized problems (ba_small.hpp): the whole LM loop in one kernel launch, dense Cholesky of the reduced
 // system instead of PCG.  Same options, summary and trace as the multi-kernel path.
 static bool small_applies(const ba_handle* h, const ba_options* opts) {
-  static const long max_obs = [] { const char* e = getenv("BA_SMALL_MAX_OBS"); return e ? atol(e) : (long)SMALL_DEFAULT_MAX_OBS; }();
   // (the observation limit is the measured crossover of the ONE-workgroup kernel with the multi-kernel path; a window that
   // fits the multi-workgroup kernel -- five cameras, 2048 landmarks: at most 10 k observations -- is far below its own)
   const char* mw_env = getenv("BA_SMALL_MW");
   const bool mw = h->mw_ok && (!mw_env || atoi(mw_env) != 0);
-  return opts->small_solver == 0 && !h->multi && h->Nc <= SMALL_MAX_CAMS && h->Np > 0 && h->Nobs > 0 && (h->Nobs <= max_obs || mw) &&
-         opts->max_iters >= 1 && getenv("BA_NO_SMALL_SOLVER") == nullptr;
+  return opts->small_solver == 0 && !h->multi && h->Nc <= SMALL_MAX_CAMS && h->Np > 0 && h->Nobs > 0 && (h->Nobs <= SMALL_MAX_OBS || mw) &&
+         opts->max_iters >= 1;
 }
 static int small_solve(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   const double t_begin = now_s();
@@ -2472,15 +2463,13 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   }
   // BA_RIDERS: bit 0 = the camera update rides along the back substitution, bit 1 = the scalar fold + verdict rides along
   // the speculated point half (ba_kernels.hpp, "riders"), bit 2 = the PCG probe that finds PCG finished goes on as the back
-  // substitution in the same launch (needs bit 0); BA_NO_RIDERS / BA_RIDERS=0: launches of their own (tuning, tests)
-  const int riders = getenv("BA_NO_RIDERS") ? 0 : (getenv("BA_RIDERS") ? atoi(getenv("BA_RIDERS")) : 7);
+  // substitution in the same launch (needs bit 0); BA_RIDERS=0: launches of their own (tests)
+  const int riders = getenv("BA_RIDERS") ? atoi(getenv("BA_RIDERS")) : 7;
   double lambda = opts->initial_lambda, nu = 2.0;
   int it = 0, status = 0;
   // Schur-Jacobi blocks kept over consecutive damped systems (ba_options.precond_lag): when they were built, how often they
   // have been kept since, and what the inner solves cost with them.  Host-side and deterministic: the rule reads options,
   // dampings and PCG iteration counts only (identical on every rank of a multi-rank job).
-  const bool cap_floor = getenv("BA_NO_CAP_FLOOR") == nullptr;      // (switch for A / B measurements)
-  const int cu_groups = getenv("BA_CU_GROUPS") ? std::min(8, std::max(1, atoi(getenv("BA_CU_GROUPS")))) : CU_GROUPS;
   double lam_floor = 0.0;
   bool have_precond = false;
   double lam_built = 0.0;
@@ -2548,7 +2537,7 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     cu.vx = h->vx.p;
     cu.lam_slot = h->dev_lam.p;
     // (riding workgroups: a multiple of NPART, so that the point workgroups behind them keep their XCD = index mod NPART)
-    cu.n_cams = Nc; cu.fixed_cam = h->fixed; cu.groups = cu_groups;
+    cu.n_cams = Nc; cu.fixed_cam = h->fixed; cu.groups = CU_GROUPS;
     cu.n_blocks = (((nbv(h) + cu.groups - 1) / cu.groups + NPART - 1) / NPART) * NPART;
     const bool ride = (riders & 1) && all_lds_of(h) && h->Np > 0;
     // The probe that finds PCG finished goes on as the back substitution (pt_schur_body, cu.fuse): the camera-update riders
@@ -2636,7 +2625,7 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     // further only buys more capped solves: from here on the damping stays at or above three times the value that
     // hit the cap -- one Nielsen step back, where the solve still converged.  The floor travels with the step's verdict
     // (lm_decide): the speculated point half reads the next damping on the device.
-    if (cap_floor && k >= opts->pcg_max_iters) { lam_floor = std::max(lam_floor, 3.0 * lambda); h->stats[BA_STAT_CAP_FLOOR_RAISES]++; }
+    if (k >= opts->pcg_max_iters) { lam_floor = std::max(lam_floor, 3.0 * lambda); h->stats[BA_STAT_CAP_FLOOR_RAISES]++; }
     // ---- step, trial point, gain-ratio scalars
     Range r_step("step");
     if (!backsub_done) {              // (PCG ran into its iteration cap, or the fused form is off)

@@ -491,8 +491,8 @@ __device__ inline bool pcg_verdict(const double* __restrict__ verdict, int k, do
   return vd[2] != 0.0;
 }
 
-// SEGL lanes per (camera, partition) segment: 64 (a wave), 32 or 16 (one DPP row).  Fewer lanes per segment =
-// fewer waves, so the per-wave prologue and the cross-lane reduction of the six sums are paid for 2 / 4
+// SEGL lanes per (camera, partition) segment: 64 (a wave) or 16 (one DPP row).  Fewer lanes per segment =
+// fewer waves, so the per-wave prologue and the cross-lane reduction of the six sums are paid for 4
 // segments at once (the pass is vector-issue bound: SQ counters, profiles/), at the price of a longer chain
 // of dependent gathers per lane.  Workgroup = 256 / SEGL consecutive cameras of one partition.
 template <int SEGL>
@@ -501,8 +501,10 @@ __device__ inline double seg_sum_dpp(double x) {    // the last lane of every SE
   x += dpp_f64<DPP_ROW_SHR2, 0xf>(x);
   x += dpp_f64<DPP_ROW_SHR4, 0xf>(x);
   x += dpp_f64<DPP_ROW_SHR8, 0xf>(x);
-  if (SEGL >= 32) x += dpp_f64<DPP_ROW_BCAST15, 0xa>(x);
-  if (SEGL == 64) x += dpp_f64<DPP_ROW_BCAST31, 0xc>(x);
+  if (SEGL == 64) {
+    x += dpp_f64<DPP_ROW_BCAST15, 0xa>(x);
+    x += dpp_f64<DPP_ROW_BCAST31, 0xc>(x);
+  }
   return x;
 }
 template <class CM, bool ROBUST, bool PCG, typename JT, int SEGL>
@@ -513,7 +515,7 @@ k_cam_schur(const double* __restrict__ cs, const double* __restrict__ intr, cons
             int kit, const double* __restrict__ verdict, const double* __restrict__ partA, int nblkA,
             double* __restrict__ uy) {
   constexpr int NB = CM::NB;
-  static_assert(SEGL == 16 || SEGL == 32 || SEGL == 64, "16, 32 or 64 lanes per segment");
+  static_assert(SEGL == 16 || SEGL == 64, "16 or 64 lanes per segment");
   constexpr int CPB = 64 * WPB / SEGL;         // cameras per workgroup
   // segment bounds and camera state are fetched before the PCG verdict is known: one round trip
   // less on the way to the first gather (an early-exit launch wastes a few loads)
@@ -600,12 +602,8 @@ k_cam_schur(const double* __restrict__ cs, const double* __restrict__ intr, cons
 // With 27 running sums the 64-lane reduction of the wave-per-segment mapping costs as much as
 // the arithmetic of a ~125-observation segment; a row walks the segment in 8 steps and only
 // needs the 4 in-row shifts.  Workgroup = 16 consecutive cameras of one partition.
-#ifndef BA_ROW_LANES
-#define BA_ROW_LANES 16
-#endif
-constexpr int ROW_LANES = BA_ROW_LANES;          // lanes per (camera, partition) segment: 16 (one DPP row) or 32 (two)
+constexpr int ROW_LANES = 16;                   // lanes per (camera, partition) segment: one DPP row
 constexpr int ROWS = 256 / ROW_LANES;           // segments (= cameras) per 256-thread workgroup
-static_assert(ROW_LANES == 8 || ROW_LANES == 16 || ROW_LANES == 32, "row-form kernels: 8, 16 or 32 lanes per segment");
 struct RowSeg { int c, k, beg, end, l16; bool live; };   // l16: lane inside the segment
 __device__ inline void row_segment(const int* __restrict__ offk, int n_cams, int band, RowSeg& s) {
   int group;
@@ -620,8 +618,7 @@ __device__ inline double row_sum_dpp(double x) {     // the last lane of every s
   x += dpp_f64<DPP_ROW_SHR1, 0xf>(x);
   x += dpp_f64<DPP_ROW_SHR2, 0xf>(x);
   x += dpp_f64<DPP_ROW_SHR4, 0xf>(x);
-  if (ROW_LANES >= 16) x += dpp_f64<DPP_ROW_SHR8, 0xf>(x);
-  if (ROW_LANES == 32) x += dpp_f64<DPP_ROW_BCAST15, 0xa>(x);     // odd rows add the total of the row before
+  x += dpp_f64<DPP_ROW_SHR8, 0xf>(x);
   return x;
 }
 
@@ -804,13 +801,6 @@ __device__ inline void load_cam_row(bool use_lds, const double* __restrict__ tab
 #pragma unroll
   for (int q = 0; q < ROWLEN / 2; ++q) { const double2 t = src[q]; row[2 * q] = t.x; row[2 * q + 1] = t.y; }
 }
-// All of a thread's loads go out before the first LDS store (batches of FILL_BATCH): a load -> wait -> store
-// loop pays one L2 round trip per 16 bytes (measured with in-kernel stamps at C3: 4.3 us for the 144 KB table,
-// 9 dependent round trips per thread).
-constexpr int FILL_BATCH = 9;
-#ifndef BA_FILL_DMA
-#define BA_FILL_DMA 1
-#endif
 // The copy in two halves: fill_cam_table_issue starts it, fill_cam_table_wait ends it (wait + workgroup barrier); what a
 // kernel does in between overlaps the copy's round trips.  SKIP_WAVE0: wave 0 has other work in between (the PCG probe)
 // and takes no share of the copy -- its probe loads would otherwise queue behind its share.
@@ -819,42 +809,24 @@ __device__ inline void fill_cam_table_issue(double* __restrict__ tab, const doub
   static_assert(STRIDE % 2 == 0, "table rows are copied and read 16 bytes at a time");
   const double2* src = (const double2*)(camA + STRIDE * (size_t)lo);
   const int total = n * STRIDE / 2;
-#if BA_FILL_DMA
   // LDS-DMA (global_load_lds_dwordx4, gfx950): 16 bytes per lane straight into LDS at (wave-uniform base) + lane * 16,
   // no staging registers and no ds_write issue slots; a wave copies whole 1 KB pieces, the lanes past the end of the
   // table sit out (an inactive lane neither loads nor stores).  The copy is invisible to the compiler: the explicit
   // vmcnt(0) of fill_cam_table_wait keeps every later LDS read behind it.
-  {
-    // Every workgroup copies the same table at the same time: each starts at a different piece, so that the
-    // workgroups of an XCD are not all on the same L2 channel at any moment.
-    constexpr int NW = BLOCK / 64 - (SKIP_WAVE0 ? 1 : 0);
-    const int wave = (int)(threadIdx.x >> 6) - (SKIP_WAVE0 ? 1 : 0), lane = threadIdx.x & 63;
-    if (SKIP_WAVE0 && wave < 0) return;
-    const int npieces = (total + 63) / 64;
-    const int rot = (int)((blockIdx.x * 37u) % (unsigned)npieces);
-    for (int q = wave; q < npieces; q += NW) {
-      int piece = q + rot;
-      if (piece >= npieces) piece -= npieces;
-      const int i = piece * 64 + lane;
-      if (i < total)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i),
-                                         (__attribute__((address_space(3))) void*)(tab + piece * 128), 16, 0, 0);
-    }
-    return;
-  }
-#endif
-  for (int base = threadIdx.x; base < total; base += BLOCK * FILL_BATCH) {
-    double2 v[FILL_BATCH];
-#pragma unroll
-    for (int u = 0; u < FILL_BATCH; ++u) {
-      const int i = base + u * BLOCK;
-      v[u] = (i < total) ? src[i] : make_double2(0.0, 0.0);
-    }
-#pragma unroll
-    for (int u = 0; u < FILL_BATCH; ++u) {
-      const int i = base + u * BLOCK;
-      if (i < total) ((double2*)tab)[i] = v[u];
-    }
+  // Every workgroup copies the same table at the same time: each starts at a different piece, so that the
+  // workgroups of an XCD are not all on the same L2 channel at any moment.
+  constexpr int NW = BLOCK / 64 - (SKIP_WAVE0 ? 1 : 0);
+  const int wave = (int)(threadIdx.x >> 6) - (SKIP_WAVE0 ? 1 : 0), lane = threadIdx.x & 63;
+  if (SKIP_WAVE0 && wave < 0) return;
+  const int npieces = (total + 63) / 64;
+  const int rot = (int)((blockIdx.x * 37u) % (unsigned)npieces);
+  for (int q = wave; q < npieces; q += NW) {
+    int piece = q + rot;
+    if (piece >= npieces) piece -= npieces;
+    const int i = piece * 64 + lane;
+    if (i < total)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i),
+                                       (__attribute__((address_space(3))) void*)(tab + piece * 128), 16, 0, 0);
   }
 }
 __device__ inline void fill_cam_table_wait() {

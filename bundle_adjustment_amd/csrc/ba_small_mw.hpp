@@ -60,7 +60,6 @@ template <int NT> struct MwDim {
 constexpr int MW_SLABS = 3 * MW_PTS / 16;          // 12 slabs of 16 columns
 constexpr int MW_MSG = MwDim<4>::MSG + 3;          // stride of a workgroup's slot in the exchange buffer (any NT)
 constexpr int MW_SCAL = 8;
-constexpr int MW_MIN_PTS = 1;                     // (measured: no slower than k_small_lm even with one or two workgroups)
 // A barrier gives up after this many ticks of the 100 MHz wall clock (s_memrealtime): 50 ms.  At most three barriers can
 // time out one after the other in one launch (workgroups that were queued behind the ones that gave up arrive later and
 // wait in turn), far below the 20 s the host waits for the result word.

@@ -165,7 +165,7 @@ def test_small_solver_is_bit_reproducible_and_honours_the_options():
         loose = s.solve(loss="huber")                      # the reference's tolerances: stops on ftol
         assert loose["status_name"] in ("ftol", "xtol") and loose["final_cost"] < 0.2 * loose["initial_cost"]      # (2 % gross outliers stay in the Huber cost)
         # nine cameras: not the single-launch solver's case any more.  More than 6144 observations (the ONE-workgroup
-        # kernel's measured crossover, tools/small_crossover.py): still its case while the window fits the multi-workgroup
+        # kernel's measured crossover): still its case while the window fits the multi-workgroup
         # kernel (2048 landmarks), the multi-kernel path beyond that
         q = make_problem(9, 600, 4, seed=1)
         s.set_problem(q)

@@ -52,3 +52,20 @@ def test_error_string_and_kernel_names(lib):
     assert lib.ba_kernel_name(5) == b"schur_pt" and lib.ba_kernel_name(6) == b"schur_cam"
     assert lib.ba_destroy(None) == 0
     assert lib.ba_synchronize(None) == -1 and b"null handle" in lib.ba_last_error()
+
+
+def test_environment_table_lists_every_variable_the_library_reads():
+    """README's table of environment variables names exactly the BA_* variables the library reads: the getenv calls of
+    csrc/ and the os.environ reads of the Python package (BA_HIP_LIB)."""
+    pkg = os.path.join(ROOT, "bundle_adjustment_amd")
+    read = set()
+    for d, pattern in ((os.path.join(pkg, "csrc"), r'getenv\("(BA_[A-Z0-9_]+)"\)'),
+                       (pkg, r'os\.environ(?:\.get\(|\[)"(BA_[A-Z0-9_]+)"')):
+        for f in sorted(os.listdir(d)):
+            if os.path.isfile(os.path.join(d, f)) and f.endswith((".hip", ".hpp", ".c", ".h", ".py")):
+                read |= set(re.findall(pattern, open(os.path.join(d, f)).read()))
+    assert "BA_HIP_LIB" in read and "BA_SETUP" in read, read
+    readme = open(os.path.join(ROOT, "README.md")).read()
+    rows = re.search(r"^\| variable \| effect \|\n\|---\|---\|\n((?:\|.*\n)+)", readme, flags=re.M).group(1)
+    listed = {name for row in rows.splitlines() for name in re.findall(r"`(BA_[A-Z0-9_]+)", row.split("|")[1])}
+    assert listed == read, f"read but not in README: {sorted(read - listed)}; in README but not read: {sorted(listed - read)}"
