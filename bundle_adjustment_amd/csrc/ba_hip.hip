@@ -159,7 +159,7 @@ struct ba_handle {
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;   // second stream: test hook ba_debug_occupy only
   bool have_problem = false, have_params = false, linearized = false;
-  ba_loss lin_loss = BA_LOSS_LINEAR;   // loss and f_scale of the last linearisation (ba_schur_apply, ba_time_kernel)
+  ba_loss lin_loss = BA_LOSS_LINEAR;   // loss and f_scale of the last linearisation (ba_time_kernel)
   double lin_fscale = 1.0;
   int Nc = 0, Np = 0, Nobs = 0, fixed = -1;
   double K4[4] = {1, 1, 0, 0};
@@ -1838,9 +1838,10 @@ static void launch_cam_schur(ba_handle* h, bool robust, bool diag, bool pcg, int
 }
 // point pass with the camera vector in vtil; mode 0 = PCG iteration k, mode 1 = back substitution
 // gmax_out (first PCG probe behind a fresh linearisation): host-mapped word that receives max |gradient|
+// f32: the fp32-Jacobian instantiation (jacobian_precision = 1; mode 0 only -- the back substitution is always fp64)
 template <class CM>
 static void launch_pt_schur_t(ba_handle* h, bool robust, int mode, int k, double tol2, int min_iters, long long flag_base,
-                              double* gmax_out, const CamUpdateArgs& cu) {
+                              double* gmax_out, const CamUpdateArgs& cu, bool f32) {
   const int w = h->cur;
   const int ride = (mode == 1 || cu.fuse) ? cu.n_blocks : 0;      // the camera update as extra workgroups of the back substitution
                                                                   // (or of the PCG point pass that may turn into it: cu.fuse)
@@ -1874,7 +1875,6 @@ static void launch_pt_schur_t(ba_handle* h, bool robust, int mode, int k, double
     else PS_LAUNCH(R, 0, L, double);                                                  \
   } while (0)
   const PtWork wk = pt_work(h), wl = pt_work_long(h);
-  const bool f32 = h->jac_f32 && flag_base > 0;       // only inside the PCG loop of ba_solve
   if (all_lds_of(h)) { if (robust) PS_MODE(true, true); else PS_MODE(false, true); }
   else               { if (robust) PS_MODE(true, false); else PS_MODE(false, false); }
 #undef PS_MODE
@@ -1884,7 +1884,7 @@ static void launch_pt_schur_t(ba_handle* h, bool robust, int mode, int k, double
 #undef PS_TAIL
 }
 static void launch_pt_schur(ba_handle* h, bool robust, int mode, int k, double tol2, int min_iters, long long flag_base = 0,
-                            double* gmax_out = nullptr, const CamUpdateArgs* rider = nullptr) {
+                            double* gmax_out = nullptr, const CamUpdateArgs* rider = nullptr, bool f32 = false) {
   if (h->Np == 0) {
     // an empty landmark shard (multi-rank): no point pass, but the PCG probe's verdict is still owed
     if (mode == 0 && flag_base > 0) {
@@ -1898,7 +1898,7 @@ static void launch_pt_schur(ba_handle* h, bool robust, int mode, int k, double t
   CamUpdateArgs cu;
   if (rider) cu = *rider;
   else memset(&cu, 0, sizeof cu);
-#define CALL_T(CM) launch_pt_schur_t<CM>(h, robust, mode, k, tol2, min_iters, flag_base, gmax_out, cu)
+#define CALL_T(CM) launch_pt_schur_t<CM>(h, robust, mode, k, tol2, min_iters, flag_base, gmax_out, cu, f32)
   BA_BY_MODEL(CALL_T);
 #undef CALL_T
 }
@@ -2069,39 +2069,88 @@ static int damped_system(ba_handle* h, double lambda, bool schur_diag, bool inve
   return BA_OK;
 }
 
-extern "C" int ba_schur_rhs(ba_handle* h, double lambda, double* g) {
-  if (!h || !g) return fail(BA_ERR_INVALID, "null argument");
-  if (!h->linearized) return fail(BA_ERR_STATE, "ba_linearize first");
+static int bal_enter(ba_handle* h, const double* intr);
+static void bal_leave(ba_handle* h);
+// The reduced camera system exactly as one LM iteration of ba_solve forms and uses it: linearisation at the current
+// parameters (camera half, point half with the damped inverses at lambda), then damped_system() for the right-hand side g
+// and the preconditioner blocks Minv, then S v for each of n_vec vectors in the PCG loop's launch form -- the point pass
+// mode 0 (fp32 Jacobian blocks when jacobian_precision = 1), the camera pass k_cam_schur<.., PCG = true, .., cam_segl>
+// behind a "go on" verdict for iteration 0 -- with Hccd v - W y folded per camera by k_schur_combine.
+// precond 2: the blocks are built at lambda_prev and kept for the system at lambda (ba_options.precond_lag: g then comes
+// from the 6-sum camera pass).  intr != NULL: the BAL camera, between bal_enter and bal_leave like ba_linearize_bal.
+extern "C" int ba_schur_system(ba_handle* h, const double* intr, int32_t loss, double f_scale, double lambda, int32_t precond,
+                               double lambda_prev, int32_t jacobian_precision, int32_t n_vec, const double* v, double* sv,
+                               double* g, double* minv) {
+  if (!h) return fail(BA_ERR_INVALID, "null handle");
+  if (n_vec < 0 || (n_vec > 0 && (!v || !sv))) return fail(BA_ERR_INVALID, "n_vec vectors need v and sv");
+  if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
+  if (!intr && (h->cam_held_or & ~0x3fu)) return fail(BA_ERR_INVALID, "camera mask bits 6-8 (f, k1, k2) need the BAL camera model");
+  if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
+  if (!(f_scale > 0)) return fail(BA_ERR_INVALID, "f_scale must be positive");
+  if (precond < 0 || precond > 2) return fail(BA_ERR_INVALID, "precond must be 0 (Jacobi), 1 (Schur-Jacobi) or 2 (Schur-Jacobi kept)");
+  if (jacobian_precision != 0 && jacobian_precision != 1)
+    return fail(BA_ERR_INVALID, "jacobian_precision must be 0 (f64) or 1 (f32 blocks, f64 accumulation)");
   if (set_device(h)) return BA_ERR_HIP;
-  if (int rc = damped_system(h, lambda, true)) return rc;
-  HIPCHECK(hipMemcpyAsync(g, h->gvec.p, 6 * (size_t)h->Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  BA_SYNC(h);
-  return BA_OK;
-}
-
-extern "C" int ba_schur_apply(ba_handle* h, double lambda, const double* v, double* out) {
-  if (!h || !v || !out) return fail(BA_ERR_INVALID, "null argument");
-  if (!h->linearized) return fail(BA_ERR_STATE, "ba_linearize first");
-  if (set_device(h)) return BA_ERR_HIP;
-  if (int rc = damped_system(h, lambda, false)) return rc;       // Hccd, Hppinv
-  HIPCHECK(hipMemcpyAsync(h->vin.p, v, 6 * (size_t)h->Nc * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  {
-    Scope sc(h, BA_K_MISC);
-    BA_LAUNCH(k_vtil, dim3((h->Nc + 63) / 64), dim3(64), 0, h->stream, h->vin.p, h->cs[h->cur].p, h->Nc,
-                       h->fixed, h->camA[h->cur].p, cam_held_ptr(h));
-    BA_LAUNCH(k_pcg_reset, dim3(1), dim3(64), 0, h->stream, h->st.p, h->partV.p, nbv(h));
-  }
-  launch_pt_schur(h, h->lin_loss != BA_LOSS_LINEAR, 0, 0, -1.0, 1 << 30);        // y = Hppinv W^T v into the point table
-  launch_cam_schur(h, h->lin_loss != BA_LOSS_LINEAR, false, false, 0, 0.0, 0);
-  if (int rc = exchange_schur(h)) return rc;
-  {
-    Scope sc(h, BA_K_MISC);
-    BA_LAUNCH(k_schur_combine, dim3((h->Nc + 63) / 64), dim3(64), 0, h->stream, h->Hccd.p, h->vin.p, p6_ptr(h),
-                       nparts_of(h), h->cs[h->cur].p, h->Nc, h->fixed, h->z.p, cam_held_ptr(h));
-  }
-  HIPCHECK(hipMemcpyAsync(out, h->z.p, 6 * (size_t)h->Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  BA_SYNC(h);
-  return BA_OK;
+  if (intr) { if (int rc = bal_enter(h, intr)) { h->model = 0; return rc; } }
+  const bool jac_f32_was = h->jac_f32;
+  auto body = [&]() -> int {
+    const ba_loss ls = (ba_loss)loss;
+    const bool robust = ls != BA_LOSS_LINEAR;
+    const int nb = nb_of(h), nh = nh_of(h);
+    launch_lin_cam(h, h->cur, h->lb, ls, f_scale);
+    if (int rc = exchange_partL(h, h->lb)) return rc;
+    h->lin_loss = ls; h->lin_fscale = f_scale;
+    if (precond == 2) {            // blocks built at lambda_prev (a fresh system), then the same linearisation damped again
+      launch_lin_pt(h, h->cur, h->pb, ls, f_scale, lambda_prev);
+      if (int rc = damped_system(h, lambda_prev, true, false, true, false)) return rc;
+      if (int rc = damped_system(h, lambda, true, true, false, true)) return rc;
+    } else {
+      launch_lin_pt(h, h->cur, h->pb, ls, f_scale, lambda);
+      if (int rc = damped_system(h, lambda, precond == 1, false, true, false)) return rc;
+    }
+    h->linearized = true;
+    if (g) HIPCHECK(hipMemcpyAsync(g, h->gvec.p, nb * (size_t)h->Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (minv) HIPCHECK(hipMemcpyAsync(minv, h->Minv.p, nh * (size_t)h->Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    h->jac_f32 = jacobian_precision == 1;
+    for (int i = 0; i < n_vec; ++i) {
+      const size_t n = nb * (size_t)h->Nc;
+      HIPCHECK(hipMemcpyAsync(h->vin.p, v + i * n, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      {
+        Scope sc(h, BA_K_MISC);
+#define CALL_T(CM) BA_LAUNCH(k_vtil<CM>, dim3((h->Nc + 63) / 64), dim3(64), 0, h->stream, h->vin.p, h->cs[h->cur].p, h->Nc, h->fixed, \
+                             h->camA[h->cur].p, cam_held_ptr(h))
+        BA_BY_MODEL(CALL_T);
+#undef CALL_T
+        // a not-converged PCG state, so that the probe of iteration 0 finds "go on" (tol2 < 0), and the same verdict word
+        // written here for the camera pass (no point pass on an empty landmark shard)
+        BA_LAUNCH(k_pcg_reset, dim3(1), dim3(64), 0, h->stream, h->st.p, h->partV.p, nbv(h));
+        HIPCHECK(hipMemsetAsync(h->verdict.p, 0, 4 * sizeof(double), h->stream));
+      }
+      // flag_base 0: no probe word for the host; y = Hppinv W^T v into the point table, then the camera pass
+      launch_pt_schur(h, robust, 0, 0, -1.0, 1 << 30, 0, nullptr, nullptr, h->jac_f32);
+      launch_cam_schur(h, robust, false, true, 0, 0.0, 0);
+      if (int rc = exchange_schur(h)) return rc;
+      {
+        Scope sc(h, BA_K_MISC);
+#define CALL_T(CM) BA_LAUNCH(k_schur_combine<CM>, dim3((h->Nc + 63) / 64), dim3(64), 0, h->stream, h->Hccd.p, h->vin.p, p6_ptr(h), \
+                             nparts_of(h), h->cs[h->cur].p, h->Nc, h->fixed, h->z.p, cam_held_ptr(h))
+        BA_BY_MODEL(CALL_T);
+#undef CALL_T
+      }
+      HIPCHECK(hipMemcpyAsync(sv + i * n, h->z.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    BA_SYNC(h);
+    return BA_OK;
+  };
+  const int rc = body();
+  h->jac_f32 = jac_f32_was;
+  if (!intr) return rc;
+  const std::string msg = g_err;
+  if (rc != BA_OK) { (void)hipStreamSynchronize(h->stream); h->launch_err = hipSuccess; }
+  bal_leave(h);
+  (void)hipStreamSynchronize(h->stream);
+  g_err = msg;
+  return rc;
 }
 
 // ----------------------------------------------------------------------------- solve
@@ -2558,7 +2607,7 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     auto launch_point_pass = [&](int kk) {
       probe_ev = h->ev_slot.size(); probe_flushes = h->n_flushes;
       launch_pt_schur(h, robust, 0, kk, tol2, opts->pcg_min_iters, base,
-                      (kk == 0 && gtol_pending) ? h->d_scal_host + GMAX_HOST_SLOT : (double*)nullptr, fuse ? &cu : nullptr);
+                      (kk == 0 && gtol_pending) ? h->d_scal_host + GMAX_HOST_SLOT : (double*)nullptr, fuse ? &cu : nullptr, h->jac_f32);
     };
     // BA_IPC: the exchange of the Schur product happens inside k_pcg_step, workgroup by workgroup (ba_kernels.hpp,
     // "device-side all-reduce"); every workgroup's record has to fit its slot of the receive buffers

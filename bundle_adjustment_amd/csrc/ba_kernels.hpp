@@ -771,21 +771,6 @@ k_camrow_schur_diag(const double* __restrict__ cs, const double* __restrict__ in
   }
 }
 
-// Wy[c] = [M^T a ; b] from the NPART partial sums (fixed order)
-__device__ inline void combine_wy(const double* __restrict__ part6, int nparts, int n_cams, int c,
-                                  const double* __restrict__ M, double (&wy)[6]) {
-  double a[6] = {0, 0, 0, 0, 0, 0};
-  for (int k = 0; k < nparts; ++k) {
-    const double* src = part6 + ((size_t)k * n_cams + c) * 6;
-#pragma unroll
-    for (int q = 0; q < 6; ++q) a[q] += src[q];
-  }
-  wy[0] = M[0] * a[0] + M[3] * a[1] + M[6] * a[2];
-  wy[1] = M[1] * a[0] + M[4] * a[1] + M[7] * a[2];
-  wy[2] = M[2] * a[0] + M[5] * a[1] + M[8] * a[2];
-  wy[3] = a[3]; wy[4] = a[4]; wy[5] = a[5];
-}
-
 // -------------------------------------------------------------------------------------
 // point passes: LPP lanes per point, camera table (camA) in LDS when it fits
 // -------------------------------------------------------------------------------------
@@ -2124,29 +2109,39 @@ __global__ void k_pcg_reset(PcgState* __restrict__ st, double* __restrict__ part
   }
 }
 
-// out = Hccd v - Wy   (test hook behind ba_schur_apply; fixed row = identity)
+// out = Hccd v - Wy   (test hook behind ba_schur_system; the fixed camera's and held rows = identity)
+template <class CM>
 __global__ void k_schur_combine(const double* __restrict__ Hccd, const double* __restrict__ v,
                                 const double* __restrict__ part6, int nparts, const double* __restrict__ cs,
                                 int n_cams, int fixed_cam, double* __restrict__ out, const unsigned short* __restrict__ cam_held) {
+  constexpr int NB = CM::NB, NH = CM::NH;
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n_cams) return;
-  double vv[6], w[6], wy[6];
-  for (int q = 0; q < 6; ++q) vv[q] = v[6 * c + q];
-  sym6_mul(Hccd + 21 * c, vv, w);
-  combine_wy(part6, nparts, n_cams, c, cs + CS * c + 12, wy);
+  double vv[NB], w[NB], a[NB], wy[NB];
+  for (int q = 0; q < NB; ++q) { vv[q] = v[NB * (size_t)c + q]; a[q] = 0.0; }
+  symN_mul<NB>(Hccd + NH * (size_t)c, vv, w);
+  for (int k = 0; k < nparts; ++k)
+    for (int q = 0; q < NB; ++q) a[q] += part6[((size_t)k * n_cams + c) * NB + q];
+  const double* M = cs + CS * (size_t)c + 12;          // Wy = [M^T a_r ; a_t ; ..]
+  wy[0] = M[0] * a[0] + M[3] * a[1] + M[6] * a[2];
+  wy[1] = M[1] * a[0] + M[4] * a[1] + M[7] * a[2];
+  wy[2] = M[2] * a[0] + M[5] * a[1] + M[8] * a[2];
+  for (int q = 3; q < NB; ++q) wy[q] = a[q];
   const unsigned held = cam_held_bits(cam_held, c);
-  for (int q = 0; q < 6; ++q) out[6 * c + q] = (c == fixed_cam || ((held >> q) & 1u)) ? vv[q] : w[q] - wy[q];
+  for (int q = 0; q < NB; ++q) out[NB * (size_t)c + q] = (c == fixed_cam || ((held >> q) & 1u)) ? vv[q] : w[q] - wy[q];
 }
 
-// vtil half of camA for an arbitrary camera vector (test hook)
+// vt slot of camA for an arbitrary camera vector (test hook); held entries and the fixed camera enter as zero
+template <class CM>
 __global__ void k_vtil(const double* __restrict__ v, const double* __restrict__ cs, int n_cams, int fixed_cam,
                        double* __restrict__ vtil, const unsigned short* __restrict__ cam_held) {
+  constexpr int NB = CM::NB;
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n_cams) return;
   const unsigned held = cam_held_bits(cam_held, c);
-  double d[6];
-  for (int q = 0; q < 6; ++q) d[q] = (c == fixed_cam || ((held >> q) & 1u)) ? 0.0 : v[6 * c + q];
-  write_vtil(cs + CS * c + 12, d, vtil + TA * c + 12);
+  double d[NB];
+  for (int q = 0; q < NB; ++q) d[q] = (c == fixed_cam || ((held >> q) & 1u)) ? 0.0 : v[NB * (size_t)c + q];
+  write_vtil<NB>(cs + CS * (size_t)c + 12, d, vtil + CM::TA * (size_t)c + CM::VOFF);
 }
 
 }  // namespace ba

@@ -103,8 +103,8 @@ SYMBOLS = {
     "ba_linearize_bal": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.c_double, _DP, _DP, _DP, _DP]),
     "ba_solve_bal": (C.c_int, [C.c_void_p, _DP, C.POINTER(BAOptions), C.POINTER(BASummary)]),
     "ba_linearize": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, _DP, _DP, _DP, _DP]),
-    "ba_schur_rhs": (C.c_int, [C.c_void_p, C.c_double, _DP]),
-    "ba_schur_apply": (C.c_int, [C.c_void_p, C.c_double, _DP, _DP]),
+    "ba_schur_system": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32,
+                                  C.c_int32, _DP, _DP, _DP, _DP]),
     "ba_default_options": (C.c_int, [C.POINTER(BAOptions)]),
     "ba_solve": (C.c_int, [C.c_void_p, C.POINTER(BAOptions), C.POINTER(BASummary)]),
     "ba_get_profile": (C.c_int, [C.c_void_p, C.POINTER(BAProfile)]),
@@ -236,6 +236,7 @@ class Solver:
                                         int(prob.fixed_cam)))
         self.n_cams, self.n_pts, self.n_obs = prob.n_cams, prob.n_pts, prob.n_obs
         self._nb = 6                           # block size a whole-camera mask covers (the BAL uploads set 9)
+        self._lin = None                       # (loss, f_scale) of the last linearize(): what schur_rhs / schur_apply use
         if prob.cam_held is not None or prob.pt_held is not None:
             self.set_held(prob.cam_held, prob.pt_held)
         if with_params:
@@ -286,18 +287,47 @@ class Solver:
         Hcc = np.empty((self.n_cams, 21)); bc = np.empty((self.n_cams, 6))
         Hpp = np.empty((self.n_pts, 6)); bp = np.empty((self.n_pts, 3))
         _check(self._lib.ba_linearize(self._h, loss_code(loss), float(f_scale), _dp(Hcc), _dp(bc), _dp(Hpp), _dp(bp)))
+        self._lin = (loss, float(f_scale))
         return Hcc, bc, Hpp, bp
 
+    def schur_system(self, lam, v=None, loss="linear", f_scale=1.0, intr=None, precond=1, lam_prev=None,
+                     jacobian_precision=0):
+        """ba_schur_system: the reduced camera system of one LM iteration at the current parameters.  intr None: pinhole,
+        else (Nc, 3) (f, k1, k2) of the BAL camera.  v: (Nc, nb) or (n, Nc, nb) vectors, or None.  precond 0 Jacobi,
+        1 Schur-Jacobi, 2 Schur-Jacobi built at lam_prev and kept.  Returns dict(g (Nc, nb), minv (Nc, nh) packed upper
+        triangles, sv shaped like v or None)."""
+        nb = 6 if intr is None else 9
+        nh = nb * (nb + 1) // 2
+        ip = None
+        if intr is not None:
+            intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
+            ip = _dp(intr)
+        vv, shape = None, None
+        if v is not None:
+            shape = np.shape(v)
+            vv = np.ascontiguousarray(v, dtype=np.float64).reshape(-1, self.n_cams, nb)
+        n_vec = 0 if vv is None else vv.shape[0]
+        sv = np.empty_like(vv) if vv is not None else None
+        g = np.empty((self.n_cams, nb)); minv = np.empty((self.n_cams, nh))
+        _check(self._lib.ba_schur_system(self._h, ip, loss_code(loss), float(f_scale), float(lam), int(precond),
+                                         float(lam if lam_prev is None else lam_prev), int(jacobian_precision), n_vec,
+                                         None if vv is None else _dp(vv), None if sv is None else _dp(sv), _dp(g), _dp(minv)))
+        return dict(g=g, minv=minv, sv=None if sv is None else sv.reshape(shape))
+
+    def _last_linearization(self):
+        lin = getattr(self, "_lin", None)
+        if lin is None:
+            raise BAHipError("ba_linearize first: schur_rhs / schur_apply use the loss of the last linearize()")
+        return lin
+
     def schur_rhs(self, lam):
-        g = np.empty((self.n_cams, 6))
-        _check(self._lib.ba_schur_rhs(self._h, float(lam), _dp(g)))
-        return g
+        loss, fs = self._last_linearization()
+        return self.schur_system(lam, loss=loss, f_scale=fs)["g"]
 
     def schur_apply(self, lam, v):
+        loss, fs = self._last_linearization()
         v = np.ascontiguousarray(v, dtype=np.float64).reshape(self.n_cams, 6)
-        out = np.empty((self.n_cams, 6))
-        _check(self._lib.ba_schur_apply(self._h, float(lam), _dp(v), _dp(out)))
-        return out
+        return self.schur_system(lam, v, loss=loss, f_scale=fs, precond=0)["sv"]
 
     # -- solve -------------------------------------------------------------------------
     def default_options(self) -> BAOptions:

@@ -212,8 +212,8 @@ int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64_t n_obs,
  *            coordinates, as the columns of ba_linearize's blocks), and under the BAL model bit 6 f, 7 k1, 8 k2
  *   pt_held  uint8[Np]  or NULL: nonzero = all three coordinates of the point are held
  * A held parameter ends bit-equal to its input; it has zero rows and columns in Hcc | bc (and Hpp = bp = 0 for a held point)
- * as reported by ba_linearize*, identity ones in the damped system, ba_schur_apply and the preconditioner, and a zero
- * right-hand side (ba_schur_rhs) and step.  A held point keeps its observations: they enter the cost and the cameras'
+ * as reported by ba_linearize*, identity ones in the damped system, ba_schur_system's S and the preconditioner, and a zero
+ * right-hand side (ba_schur_system's g) and step.  A held point keeps its observations: they enter the cost and the cameras'
  * blocks.  The stopping tests see the free parameters only (gtol: max |g| over free entries; xtol: |x| and |dx| over free
  * entries).  fixed_cam holds its camera in addition to the masks.  The masks belong to the handle: they survive
  * ba_set_params and repeated solves; ba_set_problem clears them, and so does ba_set_held(h, NULL, NULL).
@@ -274,12 +274,19 @@ int ba_solve_bal(ba_handle* h, double* intr, const ba_options* opts, ba_summary*
 int ba_linearize(ba_handle* h, int32_t loss, double f_scale,
                  double* Hcc, double* bc, double* Hpp, double* bp);
 
-/* K4 test hooks (need a prior ba_linearize): reduced camera system at damping lambda.
- *   ba_schur_rhs:   g = -(bc - W (Hpp+lam Dp)^-1 bp)          double[Nc][6]
- *   ba_schur_apply: out = S v, S = (Hcc+lam Dc) - W (Hpp+lam Dp)^-1 W^T
- * The fixed camera's row is identity / zero. */
-int ba_schur_rhs(ba_handle* h, double lambda, double* g);
-int ba_schur_apply(ba_handle* h, double lambda, const double* v, double* out);
+/* K4 test hook: the reduced camera system of one LM iteration, formed and applied as ba_solve does it.
+ * Linearises at the current parameters (loss, f_scale), damps at lambda and returns
+ *   g    = -(bc - W (Hpp+lam Dp)^-1 bp)                         double[Nc][NB]
+ *   minv = the PCG preconditioner blocks, packed upper triangles  double[Nc][NH]
+ *   sv   = S v for n_vec vectors v (double[n_vec][Nc][NB]), S = (Hcc+lam Dc) - W (Hpp+lam Dp)^-1 W^T,
+ *          in the PCG loop's launch form (fp32 Jacobian blocks when jacobian_precision = 1)
+ * precond: 0 Jacobi, 1 Schur-Jacobi, 2 Schur-Jacobi blocks built at lambda_prev and kept (ba_options.precond_lag).
+ * intr == NULL: the pinhole camera (NB 6, NH 21); else (f, k1, k2)[Nc] of the BAL camera (NB 9, NH 45), the handle
+ * staying in the pinhole layout afterwards.  The fixed camera's and held rows of S are identity, their g entries zero.
+ * g, minv may be NULL. */
+int ba_schur_system(ba_handle* h, const double* intr, int32_t loss, double f_scale, double lambda, int32_t precond,
+                    double lambda_prev, int32_t jacobian_precision, int32_t n_vec, const double* v, double* sv,
+                    double* g, double* minv);
 
 /* K2-K7: the whole LM / Schur / PCG loop on the device; replaces the
  * scipy.optimize.least_squares call at src/bundle_adjuster.py:170-174. */

@@ -762,3 +762,217 @@ def bal_normal_equations(cams9, pts, cam_idx, pt_idx, uv, fixed_cam=-1, loss='li
     np.add.at(bp, pt_idx, np.einsum('nki,nk->ni', Jpw, res))
     W = np.einsum('nki,nkj->nij', Jcw, Jp)
     return dict(Hcc=Hcc, Hpp=Hpp, bc=bc, bp=bp, W=W, res=res, w=w, Jc=Jc, Jp=Jp)
+
+
+# ---------------------------------------------------------------------------
+# The damped reduced camera system under held parameters (ba_schur_system), its componentwise error bound, and a
+# float32 emulation of the PCG passes' Jacobian-recompute path (jacobian_precision = 1)
+# ---------------------------------------------------------------------------
+U64, U32 = 2.0 ** -53, 2.0 ** -24
+
+
+def inv3_batch(A):
+    """Closed-form inverse of (N,3,3) blocks (adjugate / determinant)."""
+    a = A
+    C = np.empty_like(a)
+    C[:, 0, 0] = a[:, 1, 1] * a[:, 2, 2] - a[:, 1, 2] * a[:, 2, 1]
+    C[:, 0, 1] = a[:, 0, 2] * a[:, 2, 1] - a[:, 0, 1] * a[:, 2, 2]
+    C[:, 0, 2] = a[:, 0, 1] * a[:, 1, 2] - a[:, 0, 2] * a[:, 1, 1]
+    C[:, 1, 0] = a[:, 1, 2] * a[:, 2, 0] - a[:, 1, 0] * a[:, 2, 2]
+    C[:, 1, 1] = a[:, 0, 0] * a[:, 2, 2] - a[:, 0, 2] * a[:, 2, 0]
+    C[:, 1, 2] = a[:, 0, 2] * a[:, 1, 0] - a[:, 0, 0] * a[:, 1, 2]
+    C[:, 2, 0] = a[:, 1, 0] * a[:, 2, 1] - a[:, 1, 1] * a[:, 2, 0]
+    C[:, 2, 1] = a[:, 0, 1] * a[:, 2, 0] - a[:, 0, 0] * a[:, 2, 1]
+    C[:, 2, 2] = a[:, 0, 0] * a[:, 1, 1] - a[:, 0, 1] * a[:, 1, 0]
+    det = a[:, 0, 0] * C[:, 0, 0] + a[:, 0, 1] * C[:, 1, 0] + a[:, 0, 2] * C[:, 2, 0]
+    return C / det[:, None, None]
+
+
+class HeldSchur:
+    """The damped reduced camera system of one LM iteration as ba_schur_system forms it, matrix-free, for any camera
+    block size nb and held parameters:
+        S = Hccd - W Hppinv W^T,  Hccd = Hcc + lam diag(max(diag Hcc, 1e-12)),  Hppinv = (Hpp + lam diag(..))^-1,
+    with held camera rows / columns (held_cam (Nc, nb) bool, the fixed camera's whole block included) identity in Hccd,
+    in S and in the preconditioner blocks, zero in g; held points (held_pt (Np,) bool) have Hppinv = 0.
+    ne: normal equations with the held columns zeroed (tests/held_reference.Reduced.normal_equations, or
+    normal_equations / bal_normal_equations with fixed_cam), plus 'absHcc' = sum |Jc|^T |w| |Jc| for the bounds."""
+
+    def __init__(self, ne, cam_idx, pt_idx, lam, held_cam=None, held_pt=None, floor=1e-12, obs_scale=None):
+        self.nc, self.nb = ne['Hcc'].shape[:2]
+        self.np_ = ne['Hpp'].shape[0]
+        self.ci, self.pi = np.asarray(cam_idx), np.asarray(pt_idx)
+        self.W = ne['W']
+        nb = self.nb
+        self.held = np.zeros((self.nc, nb), bool) if held_cam is None else np.asarray(held_cam, bool)
+        self.held_pt = np.zeros(self.np_, bool) if held_pt is None else np.asarray(held_pt, bool)
+        self.Hccd = damp_blocks(ne['Hcc'], lam, floor)
+        Hppd = damp_blocks(ne['Hpp'], lam, floor)
+        self.Hppinv = inv3_batch(Hppd)
+        self.Hppinv[self.held_pt] = 0.0
+        # per-point condition number of the damped 3x3 block (1-norm), 1 for held points
+        self.K = np.abs(Hppd).sum(axis=1).max(axis=1) * np.abs(self.Hppinv).sum(axis=1).max(axis=1)
+        self.K[self.held_pt] = 1.0
+        absH = ne.get('absHcc', np.abs(ne['Hcc']))
+        self.absHccd = absH + np.abs(self.Hccd - ne['Hcc'])
+        for M in (self.Hccd, self.absHccd):
+            self._identity(M)
+        self.bc, self.bp = ne['bc'], ne['bp']
+        self.absbc, self.absbp = ne.get('absbc', np.abs(self.bc)), ne.get('absbp', np.abs(self.bp))
+        self.obs_scale = obs_scale              # default per-observation scale of |W| in the bounds
+
+    def _identity(self, M):
+        """held rows / columns of (Nc, nb, nb) blocks -> identity."""
+        h = self.held
+        M[h[:, :, None] | h[:, None, :]] = 0.0
+        c, q = np.nonzero(h)
+        M[c, q, q] = 1.0
+        return M
+
+    def _w_times(self, W, y):
+        q = np.zeros((self.nc, self.nb))
+        np.add.at(q, self.ci, np.einsum('nij,nj->ni', W, y[self.pi]))
+        return q
+
+    def _wt_times(self, W, v):
+        u = np.zeros((self.np_, 3))
+        np.add.at(u, self.pi, np.einsum('nij,ni->nj', W, v[self.ci]))
+        return u
+
+    def apply(self, v):
+        v = np.asarray(v, dtype=np.float64).reshape(self.nc, self.nb)
+        vz = np.where(self.held, 0.0, v)
+        y = np.einsum('pij,pj->pi', self.Hppinv, self._wt_times(self.W, vz))
+        q = np.einsum('cij,cj->ci', self.Hccd, vz) - self._w_times(self.W, y)
+        return np.where(self.held, v, q)
+
+    def bound(self, v, cond=True, obs_scale=None):
+        """Componentwise magnitudes of the product's two terms, held rows 0:  (|Hccd||v|, |W| K |Hppinv| |W|^T |v|),
+        K = the per-point condition number of the damped 3x3 block (cond=False: K = 1); obs_scale (Nobs,): each
+        observation's |W| scaled by it (default: the one given to the constructor)."""
+        a = np.abs(np.where(self.held, 0.0, np.asarray(v, dtype=np.float64).reshape(self.nc, self.nb)))
+        obs_scale = self.obs_scale if obs_scale is None else obs_scale
+        Wa = np.abs(self.W) if obs_scale is None else np.abs(self.W) * obs_scale[:, None, None]
+        y = np.einsum('pij,pj->pi', np.abs(self.Hppinv), self._wt_times(Wa, a))
+        if cond:
+            y = self.K[:, None] * y
+        b1 = np.einsum('cij,cj->ci', self.absHccd, a)
+        b2 = self._w_times(Wa, y)
+        return np.where(self.held, 0.0, b1), np.where(self.held, 0.0, b2)
+
+    def rhs(self):
+        y0 = np.einsum('pij,pj->pi', self.Hppinv, self.bp)
+        g = -(self.bc - self._w_times(self.W, y0))
+        return np.where(self.held, 0.0, g)
+
+    def rhs_bound(self):
+        """|bc| + |W| K |Hppinv| |bp|, with sum |Jc|^T |w r| for |bc| and sum |Jp|^T |w r| for |bp| where the normal
+        equations carry them ('absbc', 'absbp': the sums cancel near a minimum, their rounding does not)."""
+        y0 = self.K[:, None] * np.einsum('pij,pj->pi', np.abs(self.Hppinv), self.absbp)
+        Wa = np.abs(self.W) if self.obs_scale is None else np.abs(self.W) * self.obs_scale[:, None, None]
+        return np.where(self.held, 0.0, self.absbc + self._w_times(Wa, y0))
+
+    def jacobi_blocks(self):
+        return self.Hccd.copy()
+
+    def schur_jacobi_blocks(self):
+        D = self.Hccd.copy()
+        np.subtract.at(D, self.ci, np.einsum('nij,njk,nlk->nil', self.W, self.Hppinv[self.pi], self.W))
+        return self._identity(D)
+
+
+def unpack_sym(packed, nb):
+    """(N, nb(nb+1)/2) packed upper triangles (row-major) -> (N, nb, nb) symmetric."""
+    iu = np.triu_indices(nb)
+    M = np.zeros((packed.shape[0], nb, nb))
+    M[:, iu[0], iu[1]] = packed
+    M[:, iu[1], iu[0]] = packed
+    return M
+
+
+def _geom_f32(R, t, intr, K4, X):
+    """Per-observation geometry of the fp32 PCG passes (ba_models.hpp, T = float): returns (Pm (n,2,3), jc (n,2,nb)
+    pre-M camera Jacobian rows as functions for the products) -- as explicit float32 arrays."""
+    f32 = np.float32
+    Xc = np.einsum('nij,nj->ni', R, X, dtype=f32).astype(f32) + t
+    iz = (f32(1) / Xc[:, 2]).astype(f32)
+    n = X.shape[0]
+    if intr is None:
+        fx, fy = f32(K4[0]), f32(K4[1])
+        xh, yh = Xc[:, 0] * iz, Xc[:, 1] * iz
+        A = np.zeros((n, 2, 3), f32)
+        A[:, 0, 0] = fx * iz; A[:, 0, 2] = -fx * xh * iz
+        A[:, 1, 1] = fy * iz; A[:, 1, 2] = -fy * yh * iz
+        return dict(A=A, B=np.einsum('nij,njk->nik', A, R).astype(f32))
+    f, k1, k2 = intr[:, 0], intr[:, 1], intr[:, 2]
+    p0, p1 = -Xc[:, 0] * iz, -Xc[:, 1] * iz
+    n2 = p0 * p0 + p1 * p1
+    rad = f32(1) + n2 * (k1 + k2 * n2)
+    drad = k1 + f32(2) * k2 * n2
+    d00 = f * (rad + f32(2) * drad * p0 * p0); d01 = f * f32(2) * drad * p0 * p1; d11 = f * (rad + f32(2) * drad * p1 * p1)
+    A = np.empty((n, 2, 3), f32)
+    A[:, 0, 0] = -iz * d00; A[:, 0, 1] = -iz * d01; A[:, 0, 2] = -iz * (d00 * p0 + d01 * p1)
+    A[:, 1, 0] = -iz * d01; A[:, 1, 1] = -iz * d11; A[:, 1, 2] = -iz * (d01 * p0 + d11 * p1)
+    return dict(A=A, B=np.einsum('nij,njk->nik', A, R).astype(f32), p=np.stack([p0, p1], 1), n2=n2, rad=rad, f=f)
+
+
+def _jc_rows_f32(g, X):
+    """(n, 2, nb) pre-M camera Jacobian rows in float32: [B_row x X | -A_row (BAL) or -dpi_row (pinhole) | intrinsics]."""
+    f32 = np.float32
+    B = g['B']
+    rot = np.cross(B, X[:, None, :]).astype(f32)                  # B_row x X
+    if 'p' not in g:                                               # pinhole: A = dpi
+        return np.concatenate([rot, -g['A']], axis=2)
+    fn = g['f'] * g['n2']
+    intr = np.stack([g['rad'][:, None] * g['p'], fn[:, None] * g['p'], (fn * g['n2'])[:, None] * g['p']], axis=2).astype(f32)
+    return np.concatenate([rot, -g['A'], -intr], axis=2)
+
+
+def schur_apply_f32(cams, intr, pts, cam_idx, pt_idx, K4, w, sys_: HeldSchur, v, mutate=None):
+    """S v as the fp32-Jacobian PCG passes compute it: R, t, (f, k1, k2), X, the camera vector vt = (M v_r, v_t, ..) and the
+    point vector y cast to float32 (load_cam<float>, the point pass's table row), the geometry and each observation's
+    products in float32, every sum over observations and Hppinv u / Hccd v / M^T a in fp64.  cams (Nc, 6) [rvec | t],
+    intr (Nc, 3) or None (pinhole with K4), w (Nobs, 2) the IRLS weights.
+    mutate: 'y_f16' rounds y through float16 in the camera pass; 'wx_both' applies w.x to both components there."""
+    f32 = np.float32
+    nc, nb = sys_.nc, sys_.nb
+    ci, pi = sys_.ci, sys_.pi
+    R64 = rodrigues_batch(cams[:, :3])
+    M = so3_right_jacobian(cams[:, :3])
+    v = np.where(sys_.held, 0.0, np.asarray(v, dtype=np.float64).reshape(nc, nb))
+    vt = v.copy()
+    vt[:, :3] = np.einsum('cij,cj->ci', M, v[:, :3])
+    R = R64.astype(f32)[ci]
+    t = cams[:, 3:6].astype(f32)[ci]
+    X = pts.astype(f32)[pi]
+    g = _geom_f32(R, t, None if intr is None else intr.astype(f32)[ci], K4, X)
+    J = _jc_rows_f32(g, X)
+    wf = w.astype(f32)
+    # point pass: s = w (Jc vt) in float32, u = -sum Pm^T s in fp64, y = Hppinv u
+    s = np.einsum('nkj,nj->nk', J, vt.astype(f32)[ci], dtype=f32).astype(f32) * wf
+    u = np.zeros((sys_.np_, 3))
+    np.add.at(u, pi, -np.einsum('nki,nk->ni', g['B'], s, dtype=f32).astype(np.float64))
+    y = np.einsum('pij,pj->pi', sys_.Hppinv, u)
+    # camera pass: s = -w (Pm y) in float32, a = sum Jc_preM^T s in fp64, Wy = [M^T a_r ; a_t ; ..]
+    Y = y.astype(f32)[pi]
+    if mutate == 'y_f16':
+        Y = Y.astype(np.float16).astype(f32)
+    wc = wf.copy()
+    if mutate == 'wx_both':
+        wc[:, 1] = wc[:, 0]
+    s2 = -np.einsum('nkj,nj->nk', g['B'], Y, dtype=f32).astype(f32) * wc
+    a = np.zeros((nc, nb))
+    np.add.at(a, ci, np.einsum('nkj,nk->nj', J, s2, dtype=f32).astype(np.float64))
+    a[:, :3] = np.einsum('cji,cj->ci', M, a[:, :3])
+    q = np.einsum('cij,cj->ci', sys_.Hccd, v) - a
+    return np.where(sys_.held, np.asarray(v), q)
+
+
+def cancellation_factor(cams, pts, cam_idx, pt_idx):
+    """Per observation, || |R||X| + |t| || / ||R X + t||: how much the float32 rounding of the camera-frame point
+    R X + t is amplified relative to the point itself (>= 1; large where the scene is far from the origin)."""
+    R = rodrigues_batch(cams[:, :3])[cam_idx]
+    X = pts[pt_idx]
+    t = cams[cam_idx, 3:6]
+    num = np.linalg.norm(np.einsum('nij,nj->ni', np.abs(R), np.abs(X)) + np.abs(t), axis=1)
+    den = np.linalg.norm(np.einsum('nij,nj->ni', R, X) + t, axis=1)
+    return np.maximum(1.0, num / np.maximum(den, 1e-300))
