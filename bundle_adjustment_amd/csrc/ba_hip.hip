@@ -20,6 +20,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -147,6 +148,42 @@ struct DBuf {
     p = nullptr;
     n = 0;
   }
+  DBuf() = default;
+  DBuf(const DBuf&) = delete;
+  DBuf& operator=(const DBuf&) = delete;
+  ~DBuf() { release(); }
+};
+
+// Grow-only pinned host buffer the stream copies from (or into) asynchronously.  mark() records the stream's last use of
+// it; wait() blocks until that has landed, so the buffer may be refilled.
+struct PinnedStage {
+  char* p = nullptr;
+  size_t cap = 0;
+  hipEvent_t event = nullptr;
+  bool pending = false;
+  PinnedStage() = default;
+  PinnedStage(const PinnedStage&) = delete;
+  PinnedStage& operator=(const PinnedStage&) = delete;
+  ~PinnedStage() { if (p) (void)hipHostFree(p); if (event) (void)hipEventDestroy(event); }
+  void wait() { if (pending) (void)hipEventSynchronize(event); pending = false; }
+  // at least `need` bytes: a smaller buffer is replaced by one of `grow_to` bytes (after draining `drain`, if given)
+  hipError_t reserve(size_t need, size_t grow_to, hipStream_t drain = nullptr) {
+    wait();
+    if (cap >= need) return hipSuccess;
+    if (p && drain) (void)hipStreamSynchronize(drain);
+    if (p) (void)hipHostFree(p);
+    p = nullptr; cap = 0;
+    const hipError_t e = hipHostMalloc((void**)&p, grow_to, hipHostMallocDefault);
+    if (e != hipSuccess) { p = nullptr; return e; }
+    cap = grow_to;
+    return hipSuccess;
+  }
+  hipError_t mark(hipStream_t stream) {
+    hipError_t e = event ? hipSuccess : hipEventCreateWithFlags(&event, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(event, stream);
+    pending = e == hipSuccess;
+    return e;
+  }
 };
 
 struct ba_handle {
@@ -201,8 +238,7 @@ struct ba_handle {
   DBuf<double> gvec, x, r, p, s, z, vin, vx, scal, rbuf, gather;
   DBuf<PcgState> st;
   DBuf<double> tri;            // staging of ba_triangulate
-  char* h_up = nullptr;        // pinned staging of ba_set_problem's index uploads (small problems: one memcpy + async copies
-  size_t h_up_cap = 0;         //  instead of a blocking staged copy per array; grow-only)
+  PinnedStage up;              // pinned arena of a window-sized problem's uploads (ba_set_problem: one copy, k_unpack_problem)
   char* h_small = nullptr;     // k_small_lm's results, host-mapped: ba_summary | int cur | trace records
   char* d_small_host = nullptr;
   size_t h_small_bytes = 0;
@@ -210,15 +246,13 @@ struct ba_handle {
   DBuf<double> intr[2];        // per-camera intrinsics (f, k1, k2) of the BAL model, current / trial like cams[]
   DBuf<double> small_V, small_gS;   // k_small_lm: V = W L (49 x 3 Np_pad, zero where unwritten), per-wave partial V V^T
   int small_np_pad = -1;
-  char* h_par = nullptr; size_t h_par_cap = 0;   // pinned bounce buffer of ba_set_params / ba_get_params (window-sized problems)
-  hipEvent_t par_event = nullptr; bool par_pending = false;   // the last upload from it (ba_set_params returns without waiting)
+  PinnedStage par;             // pinned bounce buffer of ba_set_params / ba_get_params (window-sized problems)
   // k_small_mw (ba_small_mw.hpp): the window solver on mw_G workgroups; mw_ok: this problem fits its limits
   DBuf<int> mw_woff; DBuf<double> mw_buf; bool mw_ok = false; int mw_G = 0;
   int mw_resident[3] = {-1, -1, -1};   // workgroups of k_small_mw<2 / 3 / 4> the device holds at once (occupancy query, once per handle)
   long long stats[BA_STAT_COUNT] = {0};   // ba_get_stat
   DBuf<int> setup_i;                      // scratch of the device build of ba_set_problem (ba_setup.hpp)
-  DBuf<char> up_dev;                      // device copy of the pinned upload arena of a window-sized problem (k_unpack_problem)
-  hipEvent_t up_event = nullptr; bool up_pending = false;   // ... and its last copy (ba_set_problem returns without waiting for it)
+  DBuf<char> up_dev;                      // device copy of the pinned upload arena `up`
   char* h_setup = nullptr;                // pinned: what that build reads back (track-length histogram, statistics, windows)
   int setup_path = 0;                     // how the current problem's layout was built: 0 host, 1 device
   DBuf<double> stat2;                     // multi-rank: the band statistic (span sum, tracks) summed over the shards
@@ -262,6 +296,9 @@ struct ba_handle {
   size_t ev_used = 0, n_flushes = 0;
   ba_profile prof = {};
   std::vector<float> prof_ms[BA_PROFILE_SLOTS];   // every measured duration, per slot
+  ~ba_handle() {               // (the device buffers and pinned stages free themselves)
+    for (void* q : {(void*)h_setup, (void*)h_small, (void*)h_scal, (void*)h_flags}) if (q) (void)hipHostFree(q);
+  }
 };
 
 // Every kernel launch goes through BA_LAUNCH: a launch the runtime refuses (dynamic LDS above the limit, an empty
@@ -374,44 +411,9 @@ extern "C" int ba_destroy(ba_handle* h) {
   ipc_destroy(h);
   shm_destroy(h);
   for (auto e : h->ev) (void)hipEventDestroy(e);
-  DBuf<int>* ib[] = {&h->offk, &h->c_pt, &h->c_orig, &h->pt_off, &h->p_cam, &h->slot, &h->long_pts, &h->c_ptf[0], &h->c_ptf[1],
-                     &h->p_camf[0], &h->p_camf[1]};
-  for (auto b : ib) b->release();
-  h->blk_win.release();
-  DBuf<double2>* d2[] = {&h->c_uv, &h->p_uv, &h->c_w[0], &h->c_w[1], &h->p_w[0], &h->p_w[1]};
-  for (auto b : d2) b->release();
-  DBuf<double>* db[] = {&h->cams[0], &h->cams[1], &h->cs[0], &h->cs[1], &h->ptab[0], &h->ptab[1], &h->stage,
-                        &h->camA[0], &h->camA[1], &h->HccBc, &h->Hpp[0], &h->Hpp[1], &h->bp[0], &h->bp[1],
-                        &h->Hppinv[0], &h->Hppinv[1], &h->y0[0], &h->y0[1], &h->Hccd, &h->Minv,
-                        &h->partR, &h->partL[0], &h->partL[1], &h->part6, &h->partE, &h->sysmsg, &h->linmsg[0], &h->linmsg[1], &h->partA, &h->partB, &h->partC, &h->partV,
-                        &h->partG[0], &h->partG[1], &h->partGc,
-                        &h->gvec, &h->x, &h->r, &h->p, &h->s, &h->z, &h->vin, &h->vx, &h->scal, &h->rbuf, &h->gather};
-  for (auto b : db) b->release();
-  h->st.release();
-  h->tri.release();
-  h->small_V.release();
-  h->mw_woff.release(); h->mw_buf.release();
-  if (h->h_par) { (void)hipStreamSynchronize(h->stream); (void)hipHostFree(h->h_par); h->h_par = nullptr; h->h_par_cap = 0; }
-  if (h->par_event) { (void)hipEventDestroy(h->par_event); h->par_event = nullptr; }
-  if (h->up_event) { (void)hipEventDestroy(h->up_event); h->up_event = nullptr; }
-  h->up_pending = false;
-  h->par_pending = false;
-  h->intr[0].release(); h->intr[1].release();
-  h->small_gS.release();
-  h->small_np_pad = -1;
-  h->verdict.release();
-  h->dev_lam.release();
-  if (h->h_scal) (void)hipHostFree(h->h_scal);
-  if (h->h_flags) (void)hipHostFree(h->h_flags);
-  if (h->h_small) (void)hipHostFree(h->h_small);
-  if (h->h_up) (void)hipHostFree(h->h_up);
-  if (h->h_setup) (void)hipHostFree(h->h_setup);
-  h->setup_i.release();
-  h->up_dev.release();
-  h->stat2.release();
   if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
   if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;                    // every buffer the handle owns goes with it
   return BA_OK;
 }
 
@@ -736,6 +738,12 @@ static int decide_banded(ba_handle* h, double span_sum, double tracks, int Nc) {
 }
 // Point-pass grid, part 1 (needs the problem's dimensions only): lanes per point, number and length of the point ranges,
 // lanes per segment of the PCG camera pass.  Shared by the host and the device build of ba_set_problem.
+// Point-pass workgroups walk contiguous point ranges, PT_THREADS / LPP points per round.  When the whole camera table fits
+// in LDS (so a wider range cannot overflow it) no more workgroups are started than the chip holds at once -- each then
+// walks several rounds with one table fill (C3 x 10: Schur point pass 133 -> 93 us); with camera windows the ranges stay
+// one round long so that the windows stay narrow.  A smaller problem (a sliding window, a shard of a multi-GPU job) gives
+// every point 4, 8 or 16 lanes instead of 2 -- more workgroups, fewer observations per lane -- the most for which the
+// workgroups are still all resident at once.  BA_PT_BLOCKS / BA_PT_LANES override (tuning only).
 struct PtGrid { bool table_fits; int per_cu, pts_per_pass, want; };
 static PtGrid config_point_grid(ba_handle* h, int Nc, int Np, int No) {
   const size_t full_table = (size_t)Nc * TA * sizeof(double);
@@ -822,7 +830,7 @@ static int alloc_solver_buffers(ba_handle* h) {
     HIPCHECK(h->Hpp[k].alloc(6 * np1)); HIPCHECK(h->bp[k].alloc(3 * np1)); HIPCHECK(h->Hppinv[k].alloc(6 * np1));
     HIPCHECK(h->y0[k].alloc(3 * np1));
   }
-  h->pb = 0;
+  h->pb = h->lb = 0;          // (both halves of the linearisation start in buffer set 0)
   HIPCHECK(h->Hccd.alloc(NHX * (size_t)Nc)); HIPCHECK(h->Minv.alloc(NHX * (size_t)Nc));
   HIPCHECK(h->partR.alloc(2 * (size_t)NPART * Nc));
   HIPCHECK(h->partL[0].alloc(NLX * (size_t)NPART * Nc)); HIPCHECK(h->partL[1].alloc(NLX * (size_t)NPART * Nc));
@@ -845,10 +853,7 @@ static int alloc_solver_buffers(ba_handle* h) {
   return BA_OK;
 }
 
-// ---- ba_set_problem, device build (ba_setup.hpp): one upload of the caller's arrays, every ordering derived by kernels.
-// Returns BA_OK, a negative ba_status, or 1 = "not for this problem" (the caller then runs the host build; nothing the
-// host build relies on has been touched).  Chosen for large problems whose whole camera table fits in LDS (the caller's
-// point numbering is kept then); bit-equal to the host build (tests/test_gpu_setup.py).
+// ---- ba_set_problem: a device build for large problems, the host build for the others (bit-equal where both apply)
 constexpr int SETUP_HIST_BINS = 4096;
 constexpr size_t SETUP_PINNED_BYTES = 128 * 1024;
 constexpr long SETUP_DEVICE_MIN_OBS = 50000;   // smallest problem ba_set_problem lays out on the device (unless BA_SETUP says)
@@ -865,21 +870,51 @@ static int dev_scan(ba_handle* h, const int* in, int n, int* bsum, int* out) {
   BA_LAUNCH(k_scan_final, dim3(nb), dim3(1024), 0, h->stream, in, n, (const int*)bsum, out);
   return BA_OK;
 }
-static int set_problem_device(ba_handle* h, int Nc, int Np, int No, const int32_t* cam_idx, const int32_t* pt_idx, const double* uv,
-                              const double K4[4], int fixed_cam, bool timed) {
-  auto t_prev = std::chrono::steady_clock::now();
-  auto stage = [&](const char* name) {
-    if (!timed) return;
-    (void)hipStreamSynchronize(h->stream);
+// BA_TIME_SETUP=1: one stderr line per stage of ba_set_problem, with the time since the previous line.  A device-build
+// stage drains the stream first.
+struct StageClock {
+  const bool on = getenv("BA_TIME_SETUP") != nullptr;
+  std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
+  void operator()(const char* name, hipStream_t device_stream = nullptr) {
+    if (!on) return;
+    if (device_stream) (void)hipStreamSynchronize(device_stream);
     const auto t = std::chrono::steady_clock::now();
-    fprintf(stderr, "ba_set_problem [device] %-24s %8.3f ms\n", name, std::chrono::duration<double, std::milli>(t - t_prev).count());
+    const double ms = std::chrono::duration<double, std::milli>(t - t_prev).count();
+    fprintf(stderr, "ba_set_problem %s%-*s %8.3f ms\n", device_stream ? "[device] " : "", device_stream ? 24 : 28, name, ms);
     t_prev = t;
-  };
-  if ((size_t)Np + 1 > (size_t)1024 * SETUP_SCAN_BLOCK) return 1;
+  }
+};
+// The part of a problem's state both builds set alike: its dimensions ...
+static void set_dimensions(ba_handle* h, int Nc, int Np, int No, const double K4[4], int fixed_cam) {
   h->Nc = Nc; h->Np = Np; h->Nobs = No; h->fixed = fixed_cam;
   memcpy(h->K4, K4, sizeof h->K4);
   h->nblkV = (Nc + VEC_CAMS - 1) / VEC_CAMS;
   h->nblkVm[0] = (Nc + Pinhole::VC - 1) / Pinhole::VC; h->nblkVm[1] = (Nc + BalCam::VC - 1) / BalCam::VC;
+}
+// ... and the point passes' dynamic LDS, from every point-pass workgroup's camera window (first camera, number of cameras).
+// A window is staged in LDS when its rows fit; the row stride depends on the camera model (18 doubles for the reference's
+// pinhole, 26 for the BAL camera), so the LDS size and the "every window fits" flag are kept per model.
+static void set_window_lds(ba_handle* h, const int2* win, size_t nwin) {
+  const size_t row_bytes[2] = {Pinhole::TA * sizeof(double), BalCam::TA * sizeof(double)};
+  for (int m = 0; m < 2; ++m) {
+    h->lds_bytes_m[m] = 0; h->all_lds_m[m] = true;
+    for (size_t b = 0; b < nwin; ++b) {
+      const size_t bytes = (size_t)win[b].y * row_bytes[m];
+      if (bytes <= (size_t)LDS_TAB_BYTES) h->lds_bytes_m[m] = std::max(h->lds_bytes_m[m], bytes);
+      else h->all_lds_m[m] = false;
+    }
+  }
+}
+// Device build (ba_setup.hpp): one upload of the caller's arrays, every ordering derived by kernels.
+// Returns BA_OK, a negative ba_status, or 1 = "not for this problem" (the caller then runs the host build; nothing the
+// host build relies on has been touched).  Chosen for large problems whose whole camera table fits in LDS (the caller's
+// point numbering is kept then); bit-equal to the host build (tests/test_gpu_setup.py).
+static int set_problem_device(ba_handle* h, int Nc, int Np, int No, const int32_t* cam_idx, const int32_t* pt_idx, const double* uv,
+                              const double K4[4], int fixed_cam) {
+  StageClock clock;
+  auto stage = [&](const char* name) { clock(name, h->stream); };
+  if ((size_t)Np + 1 > (size_t)1024 * SETUP_SCAN_BLOCK) return 1;
+  set_dimensions(h, Nc, Np, No, K4, fixed_cam);
   const PtGrid grid = config_point_grid(h, Nc, Np, No);
   if (!grid.table_fits) return 1;
   if (!h->h_setup) HIPCHECK(hipHostMalloc((void**)&h->h_setup, SETUP_PINNED_BYTES, hipHostMallocDefault));
@@ -973,27 +1008,397 @@ static int set_problem_device(ba_handle* h, int Nc, int Np, int No, const int32_
             h->p_camf[0].p, h->p_camf[1].p);
   BA_LAUNCH(k_setup_iota, gp, b256, 0, h->stream, h->slot.p, Np);
   if (int rc = alloc_solver_buffers(h)) return rc;
-  h->lb = 0;
   BA_SYNC(h);
   stage("camera order, windows, pixels");
   unsigned long long st2[2];
   memcpy(st2, h->h_setup, sizeof st2);
   h->cam_band = st2[1] > st2[0];
-  {
-    const int2* win = (const int2*)(h->h_setup + 64);
-    size_t max_win[2] = {0, 0};
-    const size_t row_bytes[2] = {Pinhole::TA * sizeof(double), BalCam::TA * sizeof(double)};
-    h->all_lds_m[0] = h->all_lds_m[1] = true;
-    for (int b = 0; b < nwin; ++b)
-      for (int m = 0; m < 2; ++m) {
-        const size_t bytes = (size_t)win[b].y * row_bytes[m];
-        if (bytes <= (size_t)LDS_TAB_BYTES) max_win[m] = std::max(max_win[m], bytes);
-        else h->all_lds_m[m] = false;
-      }
-    h->lds_bytes_m[0] = max_win[0]; h->lds_bytes_m[1] = max_win[1];
-  }
+  set_window_lds(h, (const int2*)(h->h_setup + 64), nwin);
   h->setup_path = 1;
   return BA_OK;
+}
+
+// ---- host build: counting sorts of the caller's indices on the host, then one upload.  Same contract as the device build
+// (BA_OK or a negative ba_status).  Each stage below works on plain vectors; only the grid helpers it shares with the
+// device build (config_point_grid, config_long_*) and set_problem_host's last step write the handle.
+
+// k_small_mw's plan: chosen (within its limits, every workgroup resident at once), workgroups, and per range boundary and
+// camera the first observation of the camera's list in the range
+struct MwPlan { bool ok = false; int G = 0; std::vector<int> woff; };
+struct HostLayout {            // point order: pt_off, p_cam, p_src (caller's observation); camera order: cam_off, c_pt, c_orig
+  std::vector<int> slot, pt_off, p_cam, p_src, long_pts, cam_off, c_pt, c_orig, offk;
+  std::vector<int2> win;       // camera window (first camera, number of cameras) of every point-pass workgroup
+  MwPlan mw;
+};
+
+// Internal point numbering (slot[p]: where the caller's point p sits in the point table).  When the whole camera table
+// fits in LDS nothing is gained by moving points, so the caller's order is kept.  Otherwise points are sorted by the mean
+// index of the cameras that observe them: consecutive points are then seen from a narrow window of cameras whenever the
+// data has that locality (and per-camera partitions stay balanced when it has not).  Pure locality: results do not depend
+// on it.
+static std::vector<int> host_point_numbering(int Nc, int Np, int No, const int32_t* cam_idx, const int32_t* pt_idx) {
+  std::vector<int> slot(Np);
+  if ((size_t)Nc * TA * sizeof(double) <= (size_t)LDS_TAB_BYTES) {
+    for (int p = 0; p < Np; ++p) slot[p] = p;
+    return slot;
+  }
+  std::vector<double> sum(Np, 0.0);
+  std::vector<int> n(Np, 0);
+  for (int i = 0; i < No; ++i) { sum[pt_idx[i]] += cam_idx[i]; n[pt_idx[i]]++; }
+  // The order a stable sort of the points by key gives, in two linear steps instead of a comparison sort with an indirect
+  // key load per comparison (config 5: 9 of this stage's 13 ms): the keys lie in [0, Nc], so a stable counting sort by
+  // floor(16 key) -- monotone in the key -- leaves a handful of points per bucket, finished by a stable insertion sort on
+  // the exact keys
+  constexpr int BK = 16;
+  const size_t nbk = (size_t)(Nc + 1) * BK + 2;
+  std::vector<int> bfirst(nbk + 1, 0);
+  std::vector<std::pair<double, int>> order(Np);
+  for (int p = 0; p < Np; ++p) {
+    const double key = n[p] ? sum[p] / n[p] : (double)Nc;
+    sum[p] = key;
+    bfirst[(size_t)(key * BK) + 1]++;
+  }
+  for (size_t q = 0; q < nbk; ++q) bfirst[q + 1] += bfirst[q];
+  {
+    std::vector<int> fill(bfirst.begin(), bfirst.end() - 1);
+    for (int p = 0; p < Np; ++p) order[fill[(size_t)(sum[p] * BK)]++] = std::make_pair(sum[p], p);
+  }
+  for (size_t q = 0; q < nbk; ++q)
+    for (int a = bfirst[q] + 1; a < bfirst[q + 1]; ++a) {
+      const std::pair<double, int> v = order[a];
+      int w = a;
+      while (w > bfirst[q] && order[w - 1].first > v.first) { order[w] = order[w - 1]; --w; }
+      order[w] = v;
+    }
+  for (int r = 0; r < Np; ++r) slot[order[r].second] = r;
+  return slot;
+}
+
+// Point order: stable counting sort by (internal) point, which keeps the caller's order inside a point.  Only the indices
+// are permuted on the host; the pixels follow on the device (k_gather_uv, k_unpack_problem).
+static void host_sort_by_point(int Np, int No, const int32_t* cam_idx, const std::vector<int>& pt, std::vector<int>& pt_off,
+                               std::vector<int>& p_cam, std::vector<int>& p_src) {
+  pt_off.assign(Np + 1, 0);
+  for (int i = 0; i < No; ++i) pt_off[pt[i] + 1]++;
+  for (int p = 0; p < Np; ++p) pt_off[p + 1] += pt_off[p];
+  p_cam.resize(No); p_src.resize(No);
+  std::vector<int> pc(pt_off.begin(), pt_off.end() - 1);
+  for (int i = 0; i < No; ++i) {
+    const int b = pc[pt[i]]++;
+    p_cam[b] = cam_idx[i]; p_src[b] = i;
+  }
+}
+
+// Long tracks -- more than max(8, 2 x median track length) observations -- get one DPP row (16 lanes) per point in a
+// launch of their own.  Completes the point-pass grid (config_long_threshold, config_long_grid).
+static std::vector<int> host_long_tracks(ba_handle* h, const PtGrid& grid, int Np, const std::vector<int>& pt_off) {
+  int med = 0;
+  if (Np > 0) {
+    std::vector<int> len(Np);
+    for (int p = 0; p < Np; ++p) len[p] = pt_off[p + 1] - pt_off[p];
+    std::nth_element(len.begin(), len.begin() + Np / 2, len.end()); med = len[Np / 2];
+  }
+  config_long_threshold(h, med);
+  std::vector<int> long_pts;
+  for (int p = 0; p < Np; ++p) if (pt_off[p + 1] - pt_off[p] > h->long_thr) long_pts.push_back(p);
+  config_long_grid(h, grid, Np, (int)long_pts.size());
+  return long_pts;
+}
+
+// Bank-aware visiting order inside a point (2-lane point passes with the camera table in LDS), laid out for the ranges'
+// final length.  A point pass reads a camera's 144-byte LDS row with nine ds_read_b128; the hardware serves such a read in
+// groups of 16 lanes, and two lanes of a group collide when their rows fall into the same of 16 bank classes (row mod 16:
+// the row stride is 36 dwords).  With random cameras a group sees ~3 lanes per class: SQ_LDS_BANK_CONFLICT was 64 % of
+// the LDS cycles (profiles/).  The ORDER in which a point's observations are visited is free, so it is chosen here,
+// greedily per group of eight points and per step, so that the sixteen rows read together are in distinct classes
+// wherever the data allows.  Pure scheduling: every sum keeps a fixed order, results stay bit-reproducible.
+static void bank_aware_order(const ba_handle* h, int Np, const std::vector<int>& pt_off, std::vector<int>& p_cam, std::vector<int>& p_src) {
+  // ds_read_b128 is served in groups of SIXTEEN CONSECUTIVE LANES (measured on MI355X, tools/microbench/lds_b128_groups.hip:
+  // rows with distinct bank classes inside every 16 consecutive lanes read as fast as a broadcast, 14.3 cycles per
+  // instruction against 23.8 for random rows; distinct classes inside the lane sets {0-3,12-15,20-27} / {4-11,16-19,28-31}
+  // that rounds 1-3 ordered for -- the guide's grouping -- still cost 19.9).  With 2 lanes per point: points 0-7 of a
+  // 16-point chunk are one group, points 8-15 the other
+  static const int group_of_pair[16] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1};
+  for (int b = 0; b < h->nblkP; ++b) {
+    const int p0 = std::min(Np, b * h->ppb), p1 = std::min(Np, (b + 1) * h->ppb);
+    for (int c0 = p0; c0 < p1; c0 += 16) {              // one 32-lane half: 16 points, two groups of 8
+      for (int g = 0; g < 2; ++g) {
+        int pts[8], npts = 0;
+        for (int q = 0; q < 16 && c0 + q < p1; ++q)
+          if (group_of_pair[((c0 - p0) + q) & 15] == g) pts[npts++] = c0 + q;
+        int maxlen = 0;
+        for (int i = 0; i < npts; ++i) maxlen = std::max(maxlen, pt_off[pts[i] + 1] - pt_off[pts[i]]);
+        if (maxlen > 64) continue;                      // (long tracks: their own launch, other mapping)
+        // remaining observations of each point as a small list; at every step each point places up to two
+        int cur[8];
+        for (int i = 0; i < npts; ++i) cur[i] = pt_off[pts[i]];
+        for (int step = 0; 2 * step < maxlen; ++step) {
+          unsigned used = 0;                            // bank classes taken in this step
+          for (int i = 0; i < npts; ++i) {
+            const int end = pt_off[pts[i] + 1];
+            for (int sub = 0; sub < 2 && cur[i] < end; ++sub) {
+              int pick = cur[i];
+              for (int j = cur[i]; j < end; ++j)
+                if (!(used >> (p_cam[j] & 15) & 1u)) { pick = j; break; }
+              used |= 1u << (p_cam[pick] & 15);
+              std::swap(p_cam[pick], p_cam[cur[i]]);
+              std::swap(p_src[pick], p_src[cur[i]]);
+              ++cur[i];
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
+// Camera order: stable counting sort of the POINT-ordered list by camera, so that every camera's observations are
+// ascending in point index (needed by the partition split)
+static void host_sort_by_camera(int Nc, int Np, int No, const int32_t* cam_idx, const std::vector<int>& pt_off,
+                                const std::vector<int>& p_cam, const std::vector<int>& p_src, std::vector<int>& cam_off,
+                                std::vector<int>& c_pt, std::vector<int>& c_orig) {
+  cam_off.assign(Nc + 1, 0);
+  for (int i = 0; i < No; ++i) cam_off[cam_idx[i] + 1]++;
+  for (int c = 0; c < Nc; ++c) cam_off[c + 1] += cam_off[c];
+  c_pt.resize(No); c_orig.resize(No);
+  std::vector<int> cc(cam_off.begin(), cam_off.end() - 1);
+  for (int p = 0; p < Np; ++p)
+    for (int j = pt_off[p]; j < pt_off[p + 1]; ++j) {
+      const int a = cc[p_cam[j]]++;
+      c_pt[a] = p; c_orig[a] = p_src[j];
+    }
+}
+
+// Partition split: every camera's (point-sorted) list is cut into NPART equal-count chunks.  For uniformly spread
+// observations chunk k covers about the k-th eighth of the point table (what keeps it resident in XCD k's L2); for
+// band-structured data the chunks stay balanced and are narrow in point index anyway.
+// Returns cam_band: which workgroup -> XCD assignment of the camera passes keeps an XCD on one slice of the point table
+// (group_of_block), from the observations whose point lies in the slice of their partition, and in the slice of their
+// camera's range.
+static bool host_partitions(int Nc, int Np, const std::vector<int>& cam_off, const std::vector<int>& c_pt, std::vector<int>& offk) {
+  offk.resize((size_t)Nc * (NPART + 1));
+  for (int c = 0; c < Nc; ++c) {
+    const long long n = cam_off[c + 1] - cam_off[c];
+    for (int k = 0; k <= NPART; ++k) offk[(size_t)c * (NPART + 1) + k] = cam_off[c] + (int)((n * k) / NPART);
+  }
+  long long in_partition = 0, in_band = 0;
+  if (Np > 0) {
+    std::vector<unsigned char> slice_of(Np);           // p * NPART / Np without a division per observation
+    for (int k = 0; k < NPART; ++k)
+      for (long long q = ((long long)k * Np + NPART - 1) / NPART; q < ((long long)(k + 1) * Np + NPART - 1) / NPART; ++q)
+        slice_of[q] = (unsigned char)k;
+    for (int c = 0; c < Nc; ++c) {
+      const int cam_slice = (int)(((long long)c * NPART) / Nc);
+      for (int k = 0; k < NPART; ++k)
+        for (int a = offk[(size_t)c * (NPART + 1) + k]; a < offk[(size_t)c * (NPART + 1) + k + 1]; ++a) {
+          const int pt_slice = slice_of[c_pt[a]];
+          in_partition += pt_slice == k;
+          in_band += pt_slice == cam_slice;
+        }
+    }
+  }
+  return in_band > in_partition;
+}
+
+// Band statistic: the summed camera span of the tracks and the number of tracks (sequential captures: a few cameras per
+// track; random visibility: most of the range), for decide_banded
+static void host_band_statistic(int Nc, int Np, const std::vector<int>& pt_off, const std::vector<int>& p_cam, double& span_sum,
+                                double& tracks) {
+  span_sum = tracks = 0.0;
+  for (int p = 0; p < Np; ++p) {
+    if (pt_off[p + 1] == pt_off[p]) continue;
+    int lo = Nc, hi = -1;
+    for (int j = pt_off[p]; j < pt_off[p + 1]; ++j) { lo = std::min(lo, p_cam[j]); hi = std::max(hi, p_cam[j]); }
+    span_sum += hi - lo;
+    tracks += 1.0;
+  }
+}
+
+// The camera window (first camera, number of cameras) of every point-pass workgroup: the ranges, then the long-track
+// workgroups.  A workgroup without observations gets (0, 0).
+static std::vector<int2> host_windows(const ba_handle* h, int Nc, int Np, const std::vector<int>& pt_off, const std::vector<int>& p_cam,
+                                      const std::vector<int>& long_pts) {
+  std::vector<int2> win(h->nblkP + h->nblkL);
+  auto window_of = [](int lo, int hi) { return hi < lo ? make_int2(0, 0) : make_int2(lo, hi - lo + 1); };
+  for (int b = 0; b < h->nblkP; ++b) {
+    const int p0 = std::min(Np, b * h->ppb), p1 = std::min(Np, (b + 1) * h->ppb);
+    int lo = Nc, hi = -1;
+    for (int j = pt_off[p0]; j < pt_off[p1]; ++j) { lo = std::min(lo, p_cam[j]); hi = std::max(hi, p_cam[j]); }
+    win[b] = window_of(lo, hi);
+  }
+  for (int b = 0; b < h->nblkL; ++b) {
+    int lo = Nc, hi = -1;
+    for (int q = b * h->long_spb; q < std::min(h->n_long, (b + 1) * h->long_spb); ++q)
+      for (int j = pt_off[long_pts[q]]; j < pt_off[long_pts[q] + 1]; ++j) { lo = std::min(lo, p_cam[j]); hi = std::max(hi, p_cam[j]); }
+    win[h->nblkP + b] = window_of(lo, hi);
+  }
+  return win;
+}
+
+// The multi-workgroup window solver (ba_small_mw.hpp): eight cameras at most, up to 2048 landmarks in ranges of 64, no
+// landmark seen twice by one camera; every camera's list is ascending in landmark index, so a range is a slice of it.
+// No lower limit on landmarks (measured: no slower than k_small_lm even with one or two workgroups).  An empty plan when
+// the problem is outside those limits.
+static MwPlan host_window_solver_plan(ba_handle* h, int Nc, int Np, int No, const std::vector<int>& pt_off, const std::vector<int>& p_cam,
+                                      const std::vector<int>& cam_off, const std::vector<int>& c_pt) {
+  MwPlan plan;
+  if (h->multi || Nc > MW_MAX_CAMS || Np > MW_MAX_WG * MW_PTS || No == 0) return plan;
+  for (int p = 0; p < Np; ++p) {
+    unsigned seen = 0;
+    for (int j = pt_off[p]; j < pt_off[p + 1]; ++j) {
+      if ((seen >> p_cam[j]) & 1u) return plan;
+      seen |= 1u << p_cam[j];
+    }
+  }
+  plan.G = (Np + MW_PTS - 1) / MW_PTS;
+  plan.woff.assign((size_t)(plan.G + 1) * MW_MAX_CAMS, 0);
+  for (int c = 0; c < MW_MAX_CAMS; ++c)
+    for (int gq = 0; gq <= plan.G; ++gq) {
+      int v = No;
+      if (c < Nc) v = (int)(std::lower_bound(c_pt.begin() + cam_off[c], c_pt.begin() + cam_off[c + 1], gq * MW_PTS) - c_pt.begin());
+      plan.woff[(size_t)gq * MW_MAX_CAMS + c] = v;
+    }
+  // the workgroups of k_small_mw meet at a counter barrier: the kernel is only chosen when the device can hold all of
+  // them at once (occupancy query x compute units, once per handle; the launch itself is an ordinary one, and a barrier
+  // that is not served in time -- somebody else holds the units -- ends in the fall-back of small_solve, not in a hang)
+  const int nt = Nc <= 5 ? 0 : (Nc <= 7 ? 1 : 2);
+  if (h->mw_resident[nt] < 0) {
+    int per_cu = 0;
+    hipError_t e = nt == 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_small_mw<2>, MW_THREADS, 0)
+                 : nt == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_small_mw<3>, MW_THREADS, 0)
+                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_small_mw<4>, MW_THREADS, 0);
+    if (e != hipSuccess) { per_cu = 0; (void)hipGetLastError(); }
+    h->mw_resident[nt] = per_cu * h->n_cu;
+  }
+  plan.ok = h->mw_resident[nt] >= plan.G;
+  return plan;
+}
+
+// The host build's last step: device buffers, then the upload.  A window-sized problem (the reference's own use: a few
+// thousand observations) would send a dozen small arrays, each a blocking staged transfer from pageable memory (~10 us);
+// whenever the arena bound up_need allows, every array goes into ONE pinned arena instead -- one copy, and one
+// k_unpack_problem deals the sections out and fills the pixel streams and flagged index copies -- and the call returns
+// without waiting.  Larger problems (C3: 36 MB) copy every array directly and wait for the copies.
+static int upload_host_layout(ba_handle* h, const HostLayout& L, const double* uv, StageClock& stage) {
+  const int Nc = h->Nc, Np = h->Np, No = h->Nobs;
+  const size_t up_need = (size_t)No * (4 * 4 + 16) + (size_t)Np * 12 + (size_t)Nc * 40 + L.win.size() * 8 + 4096;
+  const bool staged = up_need <= ((size_t)4 << 20);
+  h->up.wait();                // the arena's last upload has landed
+  HIPCHECK(h->offk.alloc(L.offk.size())); HIPCHECK(h->pt_off.alloc(Np + 1)); HIPCHECK(h->slot.alloc(std::max(Np, 1)));
+  HIPCHECK(h->blk_win.alloc(L.win.size())); HIPCHECK(h->long_pts.alloc(std::max(h->n_long, 1)));
+  if (!L.mw.woff.empty()) {
+    HIPCHECK(h->mw_woff.alloc(L.mw.woff.size()));
+    HIPCHECK(h->mw_buf.alloc((size_t)2 * MW_MAX_WG * (MW_MSG + MW_SCAL) + 8));
+  }
+  if (int rc = alloc_solver_buffers(h)) return rc;
+  // every array, in arena order; the observation streams c_pt, c_orig, p_cam come last
+  struct Section { void* dst; const void* src; size_t bytes; };
+  const size_t ob = (size_t)No * sizeof(int);
+  const Section sec[] = {{h->slot.p, L.slot.data(), (size_t)Np * sizeof(int)},       {h->blk_win.p, L.win.data(), L.win.size() * sizeof(int2)},
+                         {h->long_pts.p, L.long_pts.data(), L.long_pts.size() * sizeof(int)}, {h->mw_woff.p, L.mw.woff.data(), L.mw.woff.size() * sizeof(int)},
+                         {h->offk.p, L.offk.data(), L.offk.size() * sizeof(int)},    {h->pt_off.p, L.pt_off.data(), L.pt_off.size() * sizeof(int)},
+                         {h->c_pt.p, L.c_pt.data(), ob}, {h->c_orig.p, L.c_orig.data(), ob}, {h->p_cam.p, L.p_cam.data(), ob}};
+  static_assert(sizeof sec / sizeof sec[0] <= UNPACK_MAX_SECTIONS, "k_unpack_problem's section table");
+  auto padded = [](size_t bytes) { return (bytes + 63) & ~(size_t)63; };   // sections start 64-byte aligned
+  size_t arena = No > 0 ? padded(2 * (size_t)No * sizeof(double)) + padded(ob) : 0;   // (+ the pixels and p_src)
+  for (const Section& x : sec) arena += padded(x.bytes);
+  if (staged) {
+    assert(arena <= up_need);
+    HIPCHECK(h->up.reserve(up_need, std::min<size_t>((size_t)4 << 20, std::max<size_t>(2 * up_need, (size_t)256 << 10))));
+    HIPCHECK(h->up_dev.alloc(arena));
+  } else if (No > 0) {
+    HIPCHECK(h->rbuf.alloc(2 * (size_t)No));
+  }
+  stage("allocations");
+  if (staged) {
+    UnpackArgs ua;
+    memset(&ua, 0, sizeof ua);
+    size_t used = 0;
+    auto put = [&](const void* src, size_t bytes) { memcpy(h->up.p + used, src, bytes); used += padded(bytes); return used - padded(bytes); };
+    for (const Section& x : sec) {
+      if (x.bytes == 0) continue;
+      ua.off[ua.n_sections] = put(x.src, x.bytes); ua.dst[ua.n_sections] = (int*)x.dst; ua.words[ua.n_sections] = (int)(x.bytes / 4);
+      ++ua.n_sections;
+    }
+    if (No > 0) {              // the pixels (caller's order) and p_src are read from the arena only
+      ua.n_obs = No;
+      ua.off_uv = put(uv, 2 * (size_t)No * sizeof(double)); ua.off_psrc = put(L.p_src.data(), ob);
+      ua.off_cpt = ua.off[ua.n_sections - 3]; ua.off_corig = ua.off[ua.n_sections - 2]; ua.off_pcam = ua.off[ua.n_sections - 1];
+      ua.p_uv = h->p_uv.p; ua.c_uv = h->c_uv.p; ua.uv_f32 = h->uv_f32 ? 1 : 0;
+      ua.c_ptf0 = h->c_ptf[0].p; ua.c_ptf1 = h->c_ptf[1].p; ua.p_camf0 = h->p_camf[0].p; ua.p_camf1 = h->p_camf[1].p;
+    }
+    HIPCHECK(hipMemcpyAsync(h->up_dev.p, h->up.p, used, hipMemcpyHostToDevice, h->stream));
+    ua.arena = h->up_dev.p;
+    BA_LAUNCH(k_unpack_problem, dim3((std::max(No, 4096) + 255) / 256), dim3(256), 0, h->stream, ua);
+    // everything the device still reads sits in the pinned arena: no need to wait for the copy and the kernel -- whatever
+    // comes next is ordered behind them on the stream; the arena's next use waits for this mark first
+    HIPCHECK(h->up.mark(h->stream));
+    if (int rc = check_launches(h)) return rc;
+  } else {
+    for (const Section& x : sec)
+      if (x.bytes) HIPCHECK(hipMemcpyAsync(x.dst, x.src, x.bytes, hipMemcpyHostToDevice, h->stream));
+    if (No > 0) {
+      // pixels: uploaded once in the caller's order, permuted into both orderings on the device (staging: the residual
+      // buffer for the pixels, a flagged-index buffer for the point-order permutation)
+      HIPCHECK(hipMemcpyAsync(h->rbuf.p, uv, 2 * (size_t)No * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      HIPCHECK(hipMemcpyAsync(h->c_ptf[0].p, L.p_src.data(), ob, hipMemcpyHostToDevice, h->stream));
+      const dim3 gg((No + 255) / 256), gb(256);
+      BA_LAUNCH(k_gather_uv, gg, gb, 0, h->stream, (const double2*)h->rbuf.p, (const int*)h->c_ptf[0].p, No, h->p_uv.p, (int)h->uv_f32);
+      BA_LAUNCH(k_gather_uv, gg, gb, 0, h->stream, (const double2*)h->rbuf.p, (const int*)h->c_orig.p, No, h->c_uv.p, (int)h->uv_f32);
+      // the flagged copies of the index streams start as the plain streams: a robust linearisation reads them and stores
+      // an entry only where its "weights are not (1, 1)" flag changes
+      BA_LAUNCH(k_init_flagged, gg, gb, 0, h->stream, (const int*)h->c_pt.p, (const int*)h->p_cam.p, No, h->c_ptf[0].p, h->c_ptf[1].p,
+                h->p_camf[0].p, h->p_camf[1].p);
+    }
+    BA_SYNC(h);                // the host vectors go out of scope
+  }
+  stage("upload");
+  return BA_OK;
+}
+
+static int set_problem_host(ba_handle* h, int Nc, int Np, int No, const int32_t* cam_idx, const int32_t* pt_idx, const double* uv,
+                            const double K4[4], int fixed_cam, StageClock& stage) {
+  // float2 pixel streams (UvArr): only problems the window solvers never take (they read double2), and only when every
+  // pixel is a float32 value (branch-free sweep; NaN compares unequal: stays double)
+  bool uv_f32 = false;
+  if (uv_f32_wanted() && Nc > SMALL_MAX_CAMS && No > 0) {
+    int all = 1;
+    for (int64_t i = 0; i < 2 * (int64_t)No; ++i) all &= (int)pixel_is_f32(uv[i]);
+    uv_f32 = all != 0;
+    stage("pixel value sweep");
+  }
+  HostLayout L;
+  L.slot = host_point_numbering(Nc, Np, No, cam_idx, pt_idx);
+  std::vector<int> pt(No);
+  for (int i = 0; i < No; ++i) pt[i] = L.slot[pt_idx[i]];
+  stage("point numbering");
+  const PtGrid grid = config_point_grid(h, Nc, Np, No);
+  host_sort_by_point(Np, No, cam_idx, pt, L.pt_off, L.p_cam, L.p_src);
+  L.long_pts = host_long_tracks(h, grid, Np, L.pt_off);
+  if (h->lanes == LPP && grid.table_fits) bank_aware_order(h, Np, L.pt_off, L.p_cam, L.p_src);
+  stage("sort by point");
+  host_sort_by_camera(Nc, Np, No, cam_idx, L.pt_off, L.p_cam, L.p_src, L.cam_off, L.c_pt, L.c_orig);
+  stage("sort by camera");
+  const bool cam_band = host_partitions(Nc, Np, L.cam_off, L.c_pt, L.offk);
+  stage("partitions + XCD statistic");
+  if (!h->banded_known) {      // (decided already by a device build that handed the problem back)
+    double span_sum, tracks;
+    host_band_statistic(Nc, Np, L.pt_off, L.p_cam, span_sum, tracks);
+    if (int rc = decide_banded(h, span_sum, tracks, Nc)) return rc;
+  }
+  stage("band statistic");
+  L.win = host_windows(h, Nc, Np, L.pt_off, L.p_cam, L.long_pts);
+  stage("long tracks + windows");
+  L.mw = host_window_solver_plan(h, Nc, Np, No, L.pt_off, L.p_cam, L.cam_off, L.c_pt);
+  set_dimensions(h, Nc, Np, No, K4, fixed_cam);
+  set_window_lds(h, L.win.data(), L.win.size());
+  h->cam_band = cam_band; h->uv_f32 = uv_f32;
+  h->mw_ok = L.mw.ok; h->mw_G = L.mw.G;
+  if (stage.on)
+    fprintf(stderr, "ba_set_problem point passes: %d lanes/point, %d range workgroups x %d points + %d long-track workgroups x %d points "
+            "(%d points over %d observations), LDS window %zu / %zu bytes, every window in LDS %d / %d\n", h->lanes, h->nblkP, h->ppb,
+            h->nblkL, h->long_spb, h->n_long, h->long_thr, h->lds_bytes_m[0], h->lds_bytes_m[1], (int)h->all_lds_m[0], (int)h->all_lds_m[1]);
+  return upload_host_layout(h, L, uv, stage);
 }
 
 static void clear_held(ba_handle* h) {
@@ -1013,17 +1418,8 @@ static double held_points_x2(const ba_handle* h, const double* pts) {
   return s;
 }
 extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64_t n_obs, const int32_t* cam_idx,
-                              const int32_t* pt_idx_in, const double* uv, const double K4[4], int32_t fixed_cam) {
-  const int32_t* pt_idx = pt_idx_in;
-  // BA_TIME_SETUP=1: stage times of this call on stderr (host sorts are the bulk of it at C3)
-  const bool timed = getenv("BA_TIME_SETUP") != nullptr;
-  auto t_prev = std::chrono::steady_clock::now();
-  auto stage = [&](const char* name) {
-    if (!timed) return;
-    const auto t = std::chrono::steady_clock::now();
-    fprintf(stderr, "ba_set_problem %-28s %8.3f ms\n", name, std::chrono::duration<double, std::milli>(t - t_prev).count());
-    t_prev = t;
-  };
+                              const int32_t* pt_idx, const double* uv, const double K4[4], int32_t fixed_cam) {
+  StageClock stage;            // (host sorts are the bulk of this call at C3)
   if (!h) return fail(BA_ERR_INVALID, "null handle");
   if (n_cams <= 0 || n_pts < 0 || n_obs < 0 || n_obs > 0x7fffffffLL) return fail(BA_ERR_INVALID, "bad sizes");
   if (n_obs > 0 && (!cam_idx || !pt_idx || !uv)) return fail(BA_ERR_INVALID, "null observation arrays");
@@ -1042,428 +1438,39 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
   }
   if ((n_cams + VEC_CAMS - 1) / VEC_CAMS > 16384) return fail(BA_ERR_INVALID, "more than %d cameras are not supported", 16384 * VEC_CAMS);
   stage("validate");
-  // float2 pixel streams (UvArr): only problems the window solvers never take (they read double2), and only when every
-  // pixel is a float32 value; the device build looks for itself (k_setup_hist), the host build sweeps them below
-  const bool uv_f32_eligible = uv_f32_wanted() && n_cams > SMALL_MAX_CAMS && n_obs > 0;
   if (set_device(h)) return BA_ERR_HIP;
   // From here on the previous problem is gone: should anything below fail (allocation, copy), the handle is left
   // WITHOUT a problem rather than with new sizes over old buffers.
-  h->have_problem = false;
-  h->have_params = false;
-  h->linearized = false;
+  h->have_problem = h->have_params = h->linearized = false;
   h->setup_path = 0;
   h->banded_known = false;
   h->uv_f32 = false;
-  // Large problems whose camera table fits in LDS are laid out ON THE DEVICE (set_problem_device, ba_setup.hpp: one upload
-  // of the caller's arrays, no host sorts; bit-equal result) from SETUP_DEVICE_MIN_OBS observations on (the measured
-  // crossover is near 40 000 -- 0.23 against 0.27 ms at 48 k, 0.40 against 1.05 ms at 160 k).  BA_SETUP=host / device
-  // forces a path (device: whenever the problem qualifies at all).
-  {
-    const char* mode = getenv("BA_SETUP");
-    bool try_dev = n_obs > 0 && n_pts > 0 && n_cams > MW_MAX_CAMS && (size_t)n_cams * TA * sizeof(double) <= (size_t)LDS_TAB_BYTES;
-    if (mode && strcmp(mode, "host") == 0) try_dev = false;
-    else if (!(mode && strcmp(mode, "device") == 0) && n_obs < SETUP_DEVICE_MIN_OBS) try_dev = false;
-    if (try_dev) {
-      h->small_np_pad = -1;
-      const int rc = set_problem_device(h, n_cams, n_pts, (int)n_obs, cam_idx, pt_idx, uv, K4, fixed_cam, timed);
-      if (rc < 0) { const std::string msg = g_err; (void)hipStreamSynchronize(h->stream); h->launch_err = hipSuccess; g_err = msg; return rc; }
-      if (rc == BA_OK) {
-        stage("device build (total)");
-        h->have_problem = true;
-        return BA_OK;
-      }
-      (void)hipStreamSynchronize(h->stream);        // rc == 1: this problem is for the host build
-      h->launch_err = hipSuccess;
-    }
-  }
   // the window solver keeps V = W L resident and only ever writes the columns of points that exist: a new problem on
   // the same handle (fewer landmarks inside the same 16-column padding, or other cameras per point) must not inherit
   // columns of the previous one -> V is cleared again before its next use
   h->small_np_pad = -1;
-  const int Nc = n_cams, Np = n_pts, No = (int)n_obs;
-  h->uv_f32 = false;           // (a device build that handed the problem back may have decided already: decided again here)
-  if (uv_f32_eligible) {       // every pixel a float32 value?  (branch-free sweep; NaN compares unequal: stays double)
-    int all = 1;
-    for (int64_t i = 0; i < 2 * n_obs; ++i) all &= (int)pixel_is_f32(uv[i]);
-    h->uv_f32 = all != 0;
-    stage("pixel value sweep");
-  }
-  // internal point numbering.  When the whole camera table fits in LDS nothing is gained by
-  // moving points, so the caller's order is kept.  Otherwise points are sorted by the mean index of
-  // the cameras that observe them: consecutive points are then seen from a narrow window of cameras
-  // whenever the data has that locality (and per-camera partitions stay balanced when it has not).
-  // Pure locality: results do not depend on it.
-  std::vector<int> slot(Np);
-  if ((size_t)Nc * TA * sizeof(double) <= (size_t)LDS_TAB_BYTES) {
-    for (int p = 0; p < Np; ++p) slot[p] = p;
-  } else {
-    std::vector<double> sum(Np, 0.0);
-    std::vector<int> n(Np, 0);
-    for (int i = 0; i < No; ++i) { sum[pt_idx[i]] += cam_idx[i]; n[pt_idx[i]]++; }
-    // The order a stable sort of the points by key gives, in two linear steps instead of a comparison sort with an indirect
-    // key load per comparison (config 5: 9 of this stage's 13 ms): the keys lie in [0, Nc], so a stable counting sort by
-    // floor(16 key) -- monotone in the key -- leaves a handful of points per bucket, finished by a stable insertion sort on
-    // the exact keys
-    constexpr int BK = 16;
-    const size_t nbk = (size_t)(Nc + 1) * BK + 2;
-    std::vector<int> bfirst(nbk + 1, 0);
-    std::vector<std::pair<double, int>> order(Np);
-    for (int p = 0; p < Np; ++p) {
-      const double key = n[p] ? sum[p] / n[p] : (double)Nc;
-      sum[p] = key;
-      bfirst[(size_t)(key * BK) + 1]++;
-    }
-    for (size_t q = 0; q < nbk; ++q) bfirst[q + 1] += bfirst[q];
-    {
-      std::vector<int> fill(bfirst.begin(), bfirst.end() - 1);
-      for (int p = 0; p < Np; ++p) order[fill[(size_t)(sum[p] * BK)]++] = std::make_pair(sum[p], p);
-    }
-    for (size_t q = 0; q < nbk; ++q)
-      for (int a = bfirst[q] + 1; a < bfirst[q + 1]; ++a) {
-        const std::pair<double, int> v = order[a];
-        int w = a;
-        while (w > bfirst[q] && order[w - 1].first > v.first) { order[w] = order[w - 1]; --w; }
-        order[w] = v;
-      }
-    for (int r = 0; r < Np; ++r) slot[order[r].second] = r;
-  }
-  std::vector<int> pt_new(No);
-  for (int i = 0; i < No; ++i) pt_new[i] = slot[pt_idx[i]];
-  pt_idx = pt_new.data();
-  stage("point numbering");
-  // point-pass workgroups: contiguous point ranges, PT_THREADS / LPP points per round.  When the
-  // whole camera table fits in LDS (so a wider range cannot overflow it) no more workgroups are
-  // started than the chip holds at once -- each then walks several rounds with one table fill
-  // (C3 x 10: Schur point pass 133 -> 93 us); with camera windows the ranges stay one round long
-  // so that the windows stay narrow.  BA_PT_BLOCKS overrides (tuning only).
-  // A smaller problem (a sliding window, a shard of a multi-GPU job) gives every point 4, 8 or 16 lanes
-  // instead of 2 -- more workgroups, fewer observations per lane -- the most for which the
-  // workgroups are still all resident at once.  BA_PT_LANES overrides (tuning only).
-  const PtGrid grid = config_point_grid(h, Nc, Np, No);
-  const bool table_fits = grid.table_fits;
-  const int pts_per_pass = grid.pts_per_pass, want = grid.want;
-  (void)pts_per_pass; (void)want;
-  // ---- bank-aware visiting order inside a point (2-lane point passes with the camera table in LDS).
-  // A point pass reads a camera's 144-byte LDS row with nine ds_read_b128; the hardware serves such a read in groups of
-  // 16 lanes, and two lanes of a group collide when their rows fall into the same of 16 bank classes (row mod 16: the
-  // row stride is 36 dwords).  With random cameras a group sees ~3 lanes per class: SQ_LDS_BANK_CONFLICT was 64 % of
-  // the LDS cycles (profiles/).  The ORDER in which a point's observations are visited is free, so it is chosen here,
-  // greedily per group of eight points and per step, so that the sixteen rows read together are in distinct classes
-  // wherever the data allows.  Pure scheduling: every sum keeps a fixed order, results stay bit-reproducible.
-  auto bank_aware_order = [&](std::vector<int>& p_cam, std::vector<int>& p_src, const std::vector<int>& pt_off) {
-    if (h->lanes != LPP || !table_fits) return;
-    // ds_read_b128 is served in groups of SIXTEEN CONSECUTIVE LANES (measured on MI355X, tools/microbench/lds_b128_groups.hip:
-    // rows with distinct bank classes inside every 16 consecutive lanes read as fast as a broadcast, 14.3 cycles per
-    // instruction against 23.8 for random rows; distinct classes inside the lane sets {0-3,12-15,20-27} / {4-11,16-19,28-31}
-    // that rounds 1-3 ordered for -- the guide's grouping -- still cost 19.9).  With 2 lanes per point: points 0-7 of a
-    // 16-point chunk are one group, points 8-15 the other
-    static const int group_of_pair[16] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1};
-    std::vector<int> tmp_c, tmp_s;
-    for (int b = 0; b < h->nblkP; ++b) {
-      const int p0 = std::min(Np, b * h->ppb), p1 = std::min(Np, (b + 1) * h->ppb);
-      for (int c0 = p0; c0 < p1; c0 += 16) {              // one 32-lane half: 16 points, two groups of 8
-        for (int g = 0; g < 2; ++g) {
-          int pts[8], npts = 0;
-          for (int q = 0; q < 16 && c0 + q < p1; ++q)
-            if (group_of_pair[((c0 - p0) + q) & 15] == g) pts[npts++] = c0 + q;
-          int maxlen = 0;
-          for (int i = 0; i < npts; ++i) maxlen = std::max(maxlen, pt_off[pts[i] + 1] - pt_off[pts[i]]);
-          if (maxlen > 64) continue;                      // (long tracks: their own launch, other mapping)
-          // remaining observations of each point as a small list; at every step each point places up to two
-          int cur[8];
-          for (int i = 0; i < npts; ++i) cur[i] = pt_off[pts[i]];
-          for (int step = 0; 2 * step < maxlen; ++step) {
-            unsigned used = 0;                            // bank classes taken in this step
-            for (int i = 0; i < npts; ++i) {
-              const int end = pt_off[pts[i] + 1];
-              for (int sub = 0; sub < 2 && cur[i] < end; ++sub) {
-                int pick = cur[i];
-                for (int j = cur[i]; j < end; ++j)
-                  if (!(used >> (p_cam[j] & 15) & 1u)) { pick = j; break; }
-                used |= 1u << (p_cam[pick] & 15);
-                std::swap(p_cam[pick], p_cam[cur[i]]);
-                std::swap(p_src[pick], p_src[cur[i]]);
-                ++cur[i];
-              }
-            }
-          }
-        }
-      }
-    }
-  };
-  // point order: stable counting sort by point (keeps the caller's order inside a point)
-  std::vector<int> pt_off(Np + 1, 0);
-  for (int i = 0; i < No; ++i) pt_off[pt_idx[i] + 1]++;
-  for (int p = 0; p < Np; ++p) pt_off[p + 1] += pt_off[p];
-  // (only the indices are permuted on the host; the pixels follow on the device, k_gather_uv)
-  std::vector<int> p_cam(No), p_src(No);
-  {
-    std::vector<int> pc(pt_off.begin(), pt_off.end() - 1);
-    for (int i = 0; i < No; ++i) {
-      const int b = pc[pt_idx[i]]++;
-      p_cam[b] = cam_idx[i]; p_src[b] = i;
+  // Large problems whose camera table fits in LDS are laid out ON THE DEVICE (set_problem_device, ba_setup.hpp: one upload
+  // of the caller's arrays, no host sorts; bit-equal result) from SETUP_DEVICE_MIN_OBS observations on (the measured
+  // crossover is near 40 000 -- 0.23 against 0.27 ms at 48 k, 0.40 against 1.05 ms at 160 k).  BA_SETUP=host / device
+  // forces a path (device: whenever the problem qualifies at all).
+  const char* mode = getenv("BA_SETUP");
+  bool try_dev = n_obs > 0 && n_pts > 0 && n_cams > MW_MAX_CAMS && (size_t)n_cams * TA * sizeof(double) <= (size_t)LDS_TAB_BYTES;
+  if (mode && strcmp(mode, "host") == 0) try_dev = false;
+  else if (!(mode && strcmp(mode, "device") == 0) && n_obs < SETUP_DEVICE_MIN_OBS) try_dev = false;
+  int rc = 1;
+  if (try_dev) {
+    rc = set_problem_device(h, n_cams, n_pts, (int)n_obs, cam_idx, pt_idx, uv, K4, fixed_cam);
+    if (rc < 0) { const std::string msg = g_err; (void)hipStreamSynchronize(h->stream); h->launch_err = hipSuccess; g_err = msg; return rc; }
+    if (rc == BA_OK) {
+      stage("device build (total)");
+    } else {                   // rc == 1: this problem is for the host build
+      (void)hipStreamSynchronize(h->stream);
+      h->launch_err = hipSuccess;
     }
   }
-  // long tracks: one DPP row (16 lanes) per point in a launch of their own
-  std::vector<int> long_pts;
-  {   // long = more than max(8, 2 x median track length) observations
-    std::vector<int> len(Np);
-    for (int p = 0; p < Np; ++p) len[p] = pt_off[p + 1] - pt_off[p];
-    int med = 0;
-    if (Np > 0) { std::nth_element(len.begin(), len.begin() + Np / 2, len.end()); med = len[Np / 2]; }
-    config_long_threshold(h, med);
-  }
-  for (int p = 0; p < Np; ++p) if (pt_off[p + 1] - pt_off[p] > h->long_thr) long_pts.push_back(p);
-  config_long_grid(h, grid, Np, (int)long_pts.size());
-  const int long_per_blk = h->long_spb;
-  // (the visiting order below is laid out for the ranges' final length)
-  bank_aware_order(p_cam, p_src, pt_off);
-  stage("sort by point");
-  // camera order: stable counting sort of the POINT-ordered list by camera, so that every
-  // camera's observations are ascending in point index (needed by the partition split)
-  std::vector<int> cam_off(Nc + 1, 0);
-  for (int i = 0; i < No; ++i) cam_off[cam_idx[i] + 1]++;
-  for (int c = 0; c < Nc; ++c) cam_off[c + 1] += cam_off[c];
-  std::vector<int> c_pt(No), c_orig(No);
-  {
-    std::vector<int> cc(cam_off.begin(), cam_off.end() - 1);
-    for (int p = 0; p < Np; ++p)
-      for (int j = pt_off[p]; j < pt_off[p + 1]; ++j) {
-        const int a = cc[p_cam[j]]++;
-        c_pt[a] = p; c_orig[a] = p_src[j];
-      }
-  }
-  stage("sort by camera");
-  // partition split: every camera's (point-sorted) list is cut into NPART equal-count chunks.  For
-  // uniformly spread observations chunk k covers about the k-th eighth of the point table (what
-  // keeps it resident in XCD k's L2); for band-structured data the chunks stay balanced and are
-  // narrow in point index anyway.
-  std::vector<int> offk((size_t)Nc * (NPART + 1));
-  for (int c = 0; c < Nc; ++c) {
-    const long long n = cam_off[c + 1] - cam_off[c];
-    for (int k = 0; k <= NPART; ++k) offk[(size_t)c * (NPART + 1) + k] = cam_off[c] + (int)((n * k) / NPART);
-  }
-  // which workgroup -> XCD assignment of the camera passes keeps an XCD on one slice of the point table
-  // (group_of_block): count the observations whose point lies in the slice of their partition, and in
-  // the slice of their camera's range
-  {
-    long long in_partition = 0, in_band = 0;
-    if (Np > 0) {
-      std::vector<unsigned char> slice_of(Np);           // p * NPART / Np without a division per observation
-      for (int k = 0; k < NPART; ++k)
-        for (long long q = ((long long)k * Np + NPART - 1) / NPART; q < ((long long)(k + 1) * Np + NPART - 1) / NPART; ++q)
-          slice_of[q] = (unsigned char)k;
-      for (int c = 0; c < Nc; ++c) {
-        const int cam_slice = (int)(((long long)c * NPART) / Nc);
-        for (int k = 0; k < NPART; ++k)
-          for (int a = offk[(size_t)c * (NPART + 1) + k]; a < offk[(size_t)c * (NPART + 1) + k + 1]; ++a) {
-            const int pt_slice = slice_of[c_pt[a]];
-            in_partition += pt_slice == k;
-            in_band += pt_slice == cam_slice;
-          }
-      }
-    }
-    h->cam_band = in_band > in_partition;
-  }
-  stage("partitions + XCD statistic");
-  {   // band statistic: mean camera span of a track against the number of cameras (sequential captures: a few
-      // cameras; random visibility: most of the range)
-    double span_sum = 0.0;
-    long long tracks = 0;
-    for (int p = 0; p < Np; ++p) {
-      if (pt_off[p + 1] == pt_off[p]) continue;
-      int lo = Nc, hi = -1;
-      for (int j = pt_off[p]; j < pt_off[p + 1]; ++j) { lo = std::min(lo, p_cam[j]); hi = std::max(hi, p_cam[j]); }
-      span_sum += hi - lo;
-      ++tracks;
-    }
-    if (!h->banded_known) { if (int rc = decide_banded(h, span_sum, (double)tracks, Nc)) return rc; }
-  }
-  stage("band statistic");
-  h->Nc = Nc; h->Np = Np; h->Nobs = No; h->fixed = fixed_cam;
-  memcpy(h->K4, K4, sizeof h->K4);
-  h->nblkV = (Nc + VEC_CAMS - 1) / VEC_CAMS;
-  h->nblkVm[0] = (Nc + Pinhole::VC - 1) / Pinhole::VC; h->nblkVm[1] = (Nc + BalCam::VC - 1) / BalCam::VC;
-  const size_t nbv_max = (size_t)std::max(h->nblkVm[0], h->nblkVm[1]);
-  std::vector<int2> win(h->nblkP + h->nblkL);
-  // a window is staged in LDS when its rows fit; the row stride depends on the camera model (18 doubles for the
-  // reference's pinhole, 26 for the BAL camera), so the LDS size and the "every window fits" flag are kept per model
-  size_t max_win[2] = {0, 0};
-  const size_t row_bytes[2] = {Pinhole::TA * sizeof(double), BalCam::TA * sizeof(double)};
-  h->all_lds_m[0] = h->all_lds_m[1] = true;
-  auto window_of = [&](int lo, int hi) {
-    if (hi < lo) { lo = 0; hi = -1; }
-    for (int m = 0; m < 2; ++m) {
-      const size_t bytes = (size_t)(hi - lo + 1) * row_bytes[m];
-      if (bytes <= (size_t)LDS_TAB_BYTES) max_win[m] = std::max(max_win[m], bytes);
-      else h->all_lds_m[m] = false;
-    }
-    return make_int2(lo, hi - lo + 1);
-  };
-  for (int b = 0; b < h->nblkP; ++b) {
-    const int p0 = std::min(Np, b * h->ppb), p1 = std::min(Np, (b + 1) * h->ppb);
-    int lo = Nc, hi = -1;
-    for (int j = pt_off[p0]; j < pt_off[p1]; ++j) { lo = std::min(lo, p_cam[j]); hi = std::max(hi, p_cam[j]); }
-    win[b] = window_of(lo, hi);
-  }
-  for (int b = 0; b < h->nblkL; ++b) {
-    int lo = Nc, hi = -1;
-    for (int q = b * long_per_blk; q < std::min(h->n_long, (b + 1) * long_per_blk); ++q)
-      for (int j = pt_off[long_pts[q]]; j < pt_off[long_pts[q] + 1]; ++j) { lo = std::min(lo, p_cam[j]); hi = std::max(hi, p_cam[j]); }
-    win[h->nblkP + b] = window_of(lo, hi);
-  }
-  h->lds_bytes_m[0] = max_win[0]; h->lds_bytes_m[1] = max_win[1];
-  stage("long tracks + windows");
-  if (timed)
-    fprintf(stderr, "ba_set_problem point passes: %d lanes/point, %d range workgroups x %d points + %d long-track workgroups x %d points "
-            "(%d points over %d observations), LDS window %zu / %zu bytes, every window in LDS %d / %d\n", h->lanes, h->nblkP, h->ppb,
-            h->nblkL, h->long_spb, h->n_long, h->long_thr, max_win[0], max_win[1], (int)h->all_lds_m[0], (int)h->all_lds_m[1]);
-  const size_t nobs1 = std::max(No, 1), np1 = std::max(Np, 1);
-  // Index uploads.  A window-sized problem (the reference's own use: a few thousand observations) sends a dozen small
-  // arrays; copied from pageable memory each is a blocking staged transfer (~10 us), so they go through ONE pinned
-  // staging block and truly asynchronous copies.  Large problems (C3: 36 MB) keep the direct path.
-  size_t up_used = 0;
-  const size_t up_need = ((size_t)No * (4 * 4 + 16) + (size_t)Np * 12 + (size_t)Nc * 40 + win.size() * 8 + 4096) * 1;
-  const bool staged = up_need <= ((size_t)4 << 20);
-  if (h->up_pending) { (void)hipEventSynchronize(h->up_event); h->up_pending = false; }      // the arena's last upload has landed
-  if (staged && h->h_up_cap < up_need) {       // grow-only, with headroom: consecutive windows differ a little in size
-    if (h->h_up) { (void)hipHostFree(h->h_up); h->h_up = nullptr; h->h_up_cap = 0; }
-    const size_t cap = std::min<size_t>((size_t)4 << 20, std::max<size_t>(2 * up_need, (size_t)256 << 10));
-    HIPCHECK(hipHostMalloc((void**)&h->h_up, cap, hipHostMallocDefault));
-    h->h_up_cap = cap;
-  }
-  // (staged: the sections are only collected here; ONE copy of the arena and ONE kernel deal them out at the end)
-  UnpackArgs ua;
-  memset(&ua, 0, sizeof ua);
-  bool unstaged = false;       // some array was copied straight from its host vector (not through the arena)
-  auto upload = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-    if (bytes == 0) return hipSuccess;
-    if (staged && up_used + bytes <= h->h_up_cap && ua.n_sections < UNPACK_MAX_SECTIONS && bytes % 4 == 0) {
-      memcpy(h->h_up + up_used, src, bytes);
-      ua.off[ua.n_sections] = up_used; ua.dst[ua.n_sections] = (int*)dst; ua.words[ua.n_sections] = (int)(bytes / 4);
-      ++ua.n_sections;
-      up_used += (bytes + 63) & ~(size_t)63;
-      return hipSuccess;
-    }
-    unstaged = true;
-    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
-  };
-  // a section that only the unpack kernel reads (no array of its own): returns its arena offset, or (size_t)-1
-  auto stash = [&](const void* src, size_t bytes) -> size_t {
-    if (!(staged && up_used + bytes <= h->h_up_cap)) return (size_t)-1;
-    memcpy(h->h_up + up_used, src, bytes);
-    const size_t o = up_used;
-    up_used += (bytes + 63) & ~(size_t)63;
-    return o;
-  };
-  HIPCHECK(h->offk.alloc((size_t)Nc * (NPART + 1))); HIPCHECK(h->pt_off.alloc(Np + 1));
-  HIPCHECK(h->slot.alloc(np1));
-  if (Np > 0) HIPCHECK(upload(h->slot.p, slot.data(), Np * sizeof(int)));
-  HIPCHECK(h->blk_win.alloc(win.size()));
-  HIPCHECK(upload(h->blk_win.p, win.data(), win.size() * sizeof(int2)));
-  HIPCHECK(h->long_pts.alloc(std::max(h->n_long, 1)));
-  if (h->n_long) HIPCHECK(upload(h->long_pts.p, long_pts.data(), h->n_long * sizeof(int)));
-  // the multi-workgroup window solver (ba_small_mw.hpp): eight cameras at most, up to 2048 landmarks in ranges of 64, no
-  // landmark seen twice by one camera; every camera's list is ascending in landmark index, so a range is a slice of it.
-  // No lower limit on landmarks (measured: no slower than k_small_lm even with one or two workgroups).
-  h->mw_ok = false;
-  if (!h->multi && Nc <= MW_MAX_CAMS && Np <= MW_MAX_WG * MW_PTS && No > 0) {
-    bool dup = false;
-    for (int p = 0; p < Np && !dup; ++p) {
-      unsigned seen = 0;
-      for (int j = pt_off[p]; j < pt_off[p + 1]; ++j) { if ((seen >> p_cam[j]) & 1u) { dup = true; break; } seen |= 1u << p_cam[j]; }
-    }
-    if (!dup) {
-      h->mw_G = (Np + MW_PTS - 1) / MW_PTS;
-      std::vector<int> woff((size_t)(h->mw_G + 1) * MW_MAX_CAMS, 0);
-      for (int c = 0; c < MW_MAX_CAMS; ++c)
-        for (int gq = 0; gq <= h->mw_G; ++gq) {
-          int v = No;
-          if (c < Nc) v = (int)(std::lower_bound(c_pt.begin() + cam_off[c], c_pt.begin() + cam_off[c + 1], gq * MW_PTS) - c_pt.begin());
-          woff[(size_t)gq * MW_MAX_CAMS + c] = v;
-        }
-      HIPCHECK(h->mw_woff.alloc(woff.size()));
-      HIPCHECK(upload(h->mw_woff.p, woff.data(), woff.size() * sizeof(int)));
-      HIPCHECK(h->mw_buf.alloc((size_t)2 * MW_MAX_WG * (MW_MSG + MW_SCAL) + 8));
-      // the workgroups of k_small_mw meet at a counter barrier: the kernel is only chosen when the device can hold all of
-      // them at once (occupancy query x compute units; the launch itself is an ordinary one, and a barrier that is not
-      // served in time -- somebody else holds the units -- ends in the fall-back of small_solve, not in a hang)
-      const int nt = Nc <= 5 ? 0 : (Nc <= 7 ? 1 : 2);
-      if (h->mw_resident[nt] < 0) {
-        int per_cu = 0;
-        hipError_t e = nt == 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_small_mw<2>, MW_THREADS, 0)
-                     : nt == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_small_mw<3>, MW_THREADS, 0)
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_small_mw<4>, MW_THREADS, 0);
-        if (e != hipSuccess) { per_cu = 0; (void)hipGetLastError(); }
-        h->mw_resident[nt] = per_cu * h->n_cu;
-      }
-      h->mw_ok = h->mw_resident[nt] >= h->mw_G;
-    }
-  }
-  if (int rc = alloc_solver_buffers(h)) return rc;
-  h->lb = 0;
-  stage("allocations");
-  HIPCHECK(upload(h->offk.p, offk.data(), offk.size() * sizeof(int)));
-  HIPCHECK(upload(h->pt_off.p, pt_off.data(), (Np + 1) * sizeof(int)));
-  bool packed = false;         // the window-sized form: everything through the arena and k_unpack_problem
-  if (No > 0 && staged) {
-    const int s_cpt = ua.n_sections;
-    HIPCHECK(upload(h->c_pt.p, c_pt.data(), No * sizeof(int)));
-    const int s_corig = ua.n_sections;
-    HIPCHECK(upload(h->c_orig.p, c_orig.data(), No * sizeof(int)));
-    const int s_pcam = ua.n_sections;
-    HIPCHECK(upload(h->p_cam.p, p_cam.data(), No * sizeof(int)));
-    const size_t o_uv = stash(uv, 2 * (size_t)No * sizeof(double)), o_psrc = stash(p_src.data(), No * sizeof(int));
-    if (ua.n_sections == s_pcam + 1 && s_pcam == s_corig + 1 && s_corig == s_cpt + 1 && o_uv != (size_t)-1 && o_psrc != (size_t)-1) {
-      ua.n_obs = No; ua.off_uv = o_uv; ua.off_psrc = o_psrc;
-      ua.off_cpt = ua.off[s_cpt]; ua.off_corig = ua.off[s_corig]; ua.off_pcam = ua.off[s_pcam];
-      ua.p_uv = h->p_uv.p; ua.c_uv = h->c_uv.p; ua.uv_f32 = h->uv_f32 ? 1 : 0;
-      ua.c_ptf0 = h->c_ptf[0].p; ua.c_ptf1 = h->c_ptf[1].p; ua.p_camf0 = h->p_camf[0].p; ua.p_camf1 = h->p_camf[1].p;
-      packed = true;
-    } else {
-      return fail(BA_ERR_STATE, "ba_set_problem: the staging arena was sized too small (internal)");
-    }
-  }
-  if (ua.n_sections > 0) {     // the arena's one copy and the one kernel that deals it out
-    HIPCHECK(h->up_dev.alloc(up_used));
-    HIPCHECK(hipMemcpyAsync(h->up_dev.p, h->h_up, up_used, hipMemcpyHostToDevice, h->stream));
-    ua.arena = h->up_dev.p;
-    const int nthreads = std::max(No, 4096);
-    BA_LAUNCH(k_unpack_problem, dim3((nthreads + 255) / 256), dim3(256), 0, h->stream, ua);
-  }
-  if (No > 0 && !packed) {
-    HIPCHECK(upload(h->c_pt.p, c_pt.data(), No * sizeof(int)));
-    HIPCHECK(upload(h->c_orig.p, c_orig.data(), No * sizeof(int)));
-    HIPCHECK(upload(h->p_cam.p, p_cam.data(), No * sizeof(int)));
-    // pixels: uploaded once in the caller's order, permuted into both orderings on the device
-    // (staging: the residual buffer for the pixels, a flagged-index buffer for the point-order permutation)
-    HIPCHECK(h->rbuf.alloc(2 * (size_t)No));
-    HIPCHECK(upload(h->rbuf.p, uv, 2 * (size_t)No * sizeof(double)));
-    HIPCHECK(upload(h->c_ptf[0].p, p_src.data(), No * sizeof(int)));
-    const dim3 gg((No + 255) / 256), gb(256);
-    BA_LAUNCH(k_gather_uv, gg, gb, 0, h->stream, (const double2*)h->rbuf.p, (const int*)h->c_ptf[0].p, No, h->p_uv.p, (int)h->uv_f32);
-    BA_LAUNCH(k_gather_uv, gg, gb, 0, h->stream, (const double2*)h->rbuf.p, (const int*)h->c_orig.p, No, h->c_uv.p, (int)h->uv_f32);
-    // the flagged copies of the index streams start as the plain streams: a robust linearisation reads them and stores
-    // an entry only where its "weights are not (1, 1)" flag changes
-    BA_LAUNCH(k_init_flagged, gg, gb, 0, h->stream, (const int*)h->c_pt.p, (const int*)h->p_cam.p, No, h->c_ptf[0].p, h->c_ptf[1].p,
-              h->p_camf[0].p, h->p_camf[1].p);
-  }
-  if (!unstaged && (packed || (staged && No == 0 && ua.n_sections > 0))) {
-    // everything the device still reads sits in the pinned arena (the host vectors were copied into it, none went to the
-    // device straight from its own memory): no need to wait
-    // for the copy and the kernel -- whatever comes next is ordered behind them on the stream; the arena's next use
-    // (the next ba_set_problem) waits for this event first
-    if (!h->up_event) HIPCHECK(hipEventCreateWithFlags(&h->up_event, hipEventDisableTiming));
-    HIPCHECK(hipEventRecord(h->up_event, h->stream));
-    h->up_pending = true;
-    if (int rc = check_launches(h)) return rc;
-  } else {
-    BA_SYNC(h);   // host vectors go out of scope
-  }
-  stage("upload");
+  if (rc != BA_OK)
+    if ((rc = set_problem_host(h, n_cams, n_pts, (int)n_obs, cam_idx, pt_idx, uv, K4, fixed_cam, stage))) return rc;
   h->have_problem = true;
-  h->have_params = false;
-  h->linearized = false;
   return BA_OK;
 }
 
@@ -1486,13 +1493,7 @@ static int row_grid(ba_handle* h) { return ((h->Nc + ROWS - 1) / ROWS) * NPART; 
 // pinned bounce buffer for parameter transfers of at most 1 MB (grow-only); false: copy from / to the caller's memory
 static bool par_bounce(ba_handle* h, size_t bytes) {
   if (bytes == 0 || bytes > ((size_t)1 << 20)) return false;
-  if (h->par_pending) { (void)hipEventSynchronize(h->par_event); h->par_pending = false; }     // the buffer's last upload has landed
-  if (h->h_par_cap < bytes) {
-    if (h->h_par) { (void)hipStreamSynchronize(h->stream); (void)hipHostFree(h->h_par); h->h_par = nullptr; h->h_par_cap = 0; }
-    const size_t cap = std::max<size_t>(2 * bytes, (size_t)64 << 10);
-    if (hipHostMalloc((void**)&h->h_par, cap, hipHostMallocDefault) != hipSuccess) { h->h_par = nullptr; (void)hipGetLastError(); return false; }
-    h->h_par_cap = cap;
-  }
+  if (h->par.reserve(bytes, std::max<size_t>(2 * bytes, (size_t)64 << 10), h->stream) != hipSuccess) { (void)hipGetLastError(); return false; }
   return true;
 }
 extern "C" int ba_set_params(ba_handle* h, const double* cams, const double* pts) {
@@ -1505,9 +1506,9 @@ extern "C" int ba_set_params(ba_handle* h, const double* cams, const double* pts
   const size_t cb = 6 * (size_t)h->Nc * sizeof(double), pb = 3 * (size_t)h->Np * sizeof(double);
   const double *cams_src = cams, *pts_src = pts;
   if (par_bounce(h, cb + pb)) {
-    memcpy(h->h_par, cams, cb);
-    if (pb) memcpy(h->h_par + cb, pts, pb);
-    cams_src = (const double*)h->h_par; pts_src = (const double*)(h->h_par + cb);
+    memcpy(h->par.p, cams, cb);
+    if (pb) memcpy(h->par.p + cb, pts, pb);
+    cams_src = (const double*)h->par.p; pts_src = (const double*)(h->par.p + cb);
   }
   h->held_x2 = held_points_x2(h, pts);
   HIPCHECK(hipMemcpyAsync(h->cams[0].p, cams_src, cb, hipMemcpyHostToDevice, h->stream));
@@ -1520,9 +1521,7 @@ extern "C" int ba_set_params(ba_handle* h, const double* cams, const double* pts
   if (cams_src != cams) {
     // the caller's arrays are no longer referenced: no need to wait for the two kernels (whatever comes next is ordered
     // behind them on the stream; a launch failure surfaces at the next synchronisation)
-    if (!h->par_event) HIPCHECK(hipEventCreateWithFlags(&h->par_event, hipEventDisableTiming));
-    HIPCHECK(hipEventRecord(h->par_event, h->stream));
-    h->par_pending = true;
+    HIPCHECK(h->par.mark(h->stream));
     if (int rc = check_launches(h)) return rc;
   } else {
     BA_SYNC(h);
@@ -1538,15 +1537,15 @@ extern "C" int ba_get_params(ba_handle* h, double* cams, double* pts) {
   if (set_device(h)) return BA_ERR_HIP;
   const size_t cb = cams ? 6 * (size_t)h->Nc * sizeof(double) : 0, pb = (pts && h->Np > 0) ? 3 * (size_t)h->Np * sizeof(double) : 0;
   const bool bounce = par_bounce(h, cb + pb);
-  if (cams) HIPCHECK(hipMemcpyAsync(bounce ? (void*)h->h_par : (void*)cams, h->cams[h->cur].p, cb, hipMemcpyDeviceToHost, h->stream));
+  if (cams) HIPCHECK(hipMemcpyAsync(bounce ? (void*)h->par.p : (void*)cams, h->cams[h->cur].p, cb, hipMemcpyDeviceToHost, h->stream));
   if (pts && h->Np > 0) {
     BA_LAUNCH(k_unpack_points, dim3((h->Np + 255) / 256), dim3(256), 0, h->stream, h->ptab[h->cur].p, h->slot.p, h->Np, h->stage.p);
-    HIPCHECK(hipMemcpyAsync(bounce ? (void*)(h->h_par + cb) : (void*)pts, h->stage.p, pb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipMemcpyAsync(bounce ? (void*)(h->par.p + cb) : (void*)pts, h->stage.p, pb, hipMemcpyDeviceToHost, h->stream));
   }
   BA_SYNC(h);
   if (bounce) {
-    if (cb) memcpy(cams, h->h_par, cb);
-    if (pb) memcpy(pts, h->h_par + cb, pb);
+    if (cb) memcpy(cams, h->par.p, cb);
+    if (pb) memcpy(pts, h->par.p + cb, pb);
   }
   return BA_OK;
 }
