@@ -148,3 +148,20 @@ def solve(prob: BALProblem, device=0, fixed_cam=-1, hold_intrinsics=False, held_
         summary, cams, pts = s.solve_bal(prob, fixed_cam=fixed_cam, hold_intrinsics=hold_intrinsics,
                                          held_cameras=held_cameras, held_points=held_points, **options)
     return BALProblem(cams, pts, prob.cam_idx.copy(), prob.pt_idx.copy(), prob.uv.copy()), summary
+
+
+def covariance(prob: BALProblem, device=0, fixed_cam=-1, hold_intrinsics=False, held_cameras=None, held_points=None,
+               loss="linear", f_scale=1.0, full=False, rcond=0.0):
+    """Marginal covariances of a BAL problem at ``prob``'s parameters (``ba_covariance``; normally the problem ``solve``
+    returned).  The held-parameter forms are those of ``solve``; a BAL problem with nothing held has a free 7-dof gauge
+    and is refused (hold e.g. ``fixed_cam`` and one translation coordinate of another camera).  Returns
+    ``dict(cams (Nc, 9, 9), points (Np, 3, 3), full (9 Nc, 9 Nc) or None)``, see ``hip_backend.Solver.covariance``."""
+    from . import hip_backend
+    with hip_backend.Solver(device) as s:
+        intr = s._set_bal(prob, fixed_cam)
+        cm = hip_backend.held_camera_mask(held_cameras, s.n_cams, 9)
+        if hold_intrinsics:
+            cm = (np.zeros(s.n_cams, np.uint16) if cm is None else cm) | np.uint16(0x1C0)
+        if cm is not None or held_points is not None:
+            s.set_held(cm, held_points)
+        return s.covariance(loss=loss, f_scale=f_scale, intr=intr, full=full, rcond=rcond)

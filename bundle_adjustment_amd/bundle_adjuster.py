@@ -42,7 +42,7 @@ class BundleAdjuster:
     def __init__(self, camera_matrix, window_size=5, *, fixed_keyframes=1, device_id=0, loss='huber', f_scale=1.0, ftol=1e-5,
                  xtol=1e-5, gtol=1e-8, max_iters=50, pcg_tol=0.1, pcg_max_iters=200, pcg_model_tol=0.0, preconditioner='schur_jacobi',
                  jacobian='f64', comm=None, sparsity_plot_hook=None, verbose=0, reuse_window=True, metrics_path=None,
-                 inplace_writeback=False, reuse_min_obs=20000):
+                 inplace_writeback=False, reuse_min_obs=20000, covariance=False):
         self.camera_matrix = camera_matrix
         self.window_size = window_size
         # the first fixed_keyframes keyframes of the window are held (1: the reference's rule, src/bundle_adjuster.py:141-143:
@@ -50,6 +50,15 @@ class BundleAdjuster:
         if int(fixed_keyframes) != fixed_keyframes or fixed_keyframes < 1:
             raise ValueError("fixed_keyframes must be an integer >= 1")
         self.fixed_keyframes = int(fixed_keyframes)
+        # covariance=True: every run() that adjusts a window leaves the marginal covariances of its adjustable keyframes
+        # and landmarks at the adjusted parameters in last_covariance (ba_covariance).  They exist only with the gauge
+        # fixed: the first keyframe fixes 6 dof, a second held keyframe the window's scale.  Single-rank only.
+        if covariance and self.fixed_keyframes < 2:
+            raise ValueError("covariance=True needs fixed_keyframes >= 2: with one fixed keyframe the window's scale is free")
+        if covariance and comm is not None and comm[1] > 1:
+            raise ValueError("covariance=True is not supported in a multi-rank job")
+        self.covariance = bool(covariance)
+        self.last_covariance = None
         self.device_id = device_id
         hip_backend.loss_code(loss)            # an unknown loss or preconditioner name fails here, not at the first run()
         hip_backend.precond_code(preconditioner)
@@ -190,6 +199,8 @@ class BundleAdjuster:
     def run(self, gmap: Map):
         """Sliding-window / global bundle adjustment, ``src/bundle_adjuster.py:122-193``."""
         print("    --- Running Local Bundle Adjustment ---")
+        if self.covariance:
+            self.last_covariance = None
         all_kf_ids = sorted(gmap.keyframes.keys())
         if len(all_kf_ids) < self.window_size:
             print("    -> LBA Skipped: Not enough keyframes.")
@@ -253,6 +264,11 @@ class BundleAdjuster:
         R = solver.get_rotations()
         x = np.concatenate([cams[k_held:, :3].ravel(), cams[k_held:, 3:].ravel(), pts.ravel()])
         self._update_map(gmap, x, adjustable_kf_ids, local_map_point_ids, rotations=R[k_held:])
+        if self.covariance:
+            cov = solver.covariance(loss=self.solver_options["loss"], f_scale=self.solver_options["f_scale"])
+            self.last_covariance = {
+                "keyframes": {kf_id: cov["cams"][k_held + i] for i, kf_id in enumerate(adjustable_kf_ids)},
+                "points": {int(mp_id): cov["points"][i] for i, mp_id in enumerate(local_map_point_ids)}}
 
         improvement = 100.0 * (initial_cost - final_cost) / (initial_cost + 1e-8)
         print(f"    -> LBA Complete. Initial Cost: {initial_cost:.2f}, Final Cost: {final_cost:.2f}, "

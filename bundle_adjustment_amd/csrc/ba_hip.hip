@@ -36,6 +36,7 @@
 #include "ba_small.hpp"
 #include "ba_small_mw.hpp"
 #include "ba_setup.hpp"
+#include "ba_cov.hpp"
 
 using namespace ba;
 
@@ -2390,6 +2391,140 @@ extern "C" int ba_linearize_bal(ba_handle* h, const double* intr, int32_t loss, 
   const std::string msg = g_err;
   if (rc != BA_OK) { (void)hipStreamSynchronize(h->stream); h->launch_err = hipSuccess; }
   bal_leave(h);
+  (void)hipStreamSynchronize(h->stream);
+  g_err = msg;
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------------- covariances
+// Marginal covariances at the current parameters (csrc/ba_cov.hpp): the camera half and the point half of a linearisation
+// (Hcc, Hpp; the damped point inverses it also writes are not used), S assembled densely from them and the per-observation
+// W blocks, factorised and inverted in place, the points' blocks from the inverse.  One drain in the middle (the pair
+// scan of the point-ordered observations is formed on the host from pt_off), one at the end, where the failure words of
+// the rank tests are read; outputs are copied only when nothing failed.
+static const char* cov_param_name(int q) {
+  static const char* names[9] = {"rvec[0]", "rvec[1]", "rvec[2]", "t[0]", "t[1]", "t[2]", "f", "k1", "k2"};
+  return names[q];
+}
+template <class CM>
+static int cov_impl(ba_handle* h, ba_loss loss, double f_scale, double rcond, double* cam_cov, double* pt_cov, double* cam_full) {
+  constexpr int NB = CM::NB, NH = CM::NH;
+  const int Nc = h->Nc, Np = h->Np, n = NB * Nc;
+  const int npad = ((n + COV_T - 1) / COV_T) * COV_T, nt = npad / COV_T;
+  launch_lin_cam(h, h->cur, h->lb, loss, f_scale);
+  if (int rc = exchange_partL(h, h->lb)) return rc;
+  launch_lin_finalize(h);
+  launch_lin_pt(h, h->cur, h->pb, loss, f_scale, 1.0);
+  h->linearized = true;
+  h->lin_loss = loss;
+  h->lin_fscale = f_scale;
+  // pair numbering: exclusive scan of L_p (L_p + 1) / 2 over the point slots, in 64 bits
+  std::vector<int> off((size_t)Np + 1, 0);
+  std::vector<long long> poff((size_t)Np + 1, 0);
+  if (Np) HIPCHECK(hipMemcpyAsync(off.data(), h->pt_off.p, ((size_t)Np + 1) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  BA_SYNC(h);
+  for (int s = 0; s < Np; ++s) {
+    const long long L = off[s + 1] - off[s];
+    poff[s + 1] = poff[s] + L * (L + 1) / 2;
+  }
+  const long long n_pairs = poff[Np];
+  DBuf<double> A, dS, tinv, P, D, Vinv, Wbuf, ptc, blk;
+  DBuf<long long> dpoff;
+  DBuf<unsigned char> status;
+  DBuf<int> failw;
+  HIPCHECK(A.alloc((size_t)npad * npad));
+  HIPCHECK(dS.alloc(npad)); HIPCHECK(tinv.alloc(COV_T * COV_T)); HIPCHECK(P.alloc((size_t)npad * COV_T)); HIPCHECK(D.alloc(COV_T * COV_T));
+  HIPCHECK(Vinv.alloc(6 * (size_t)std::max(Np, 1))); HIPCHECK(status.alloc(std::max(Np, 1)));
+  HIPCHECK(Wbuf.alloc((size_t)NB * 3 * std::max(h->Nobs, 1))); HIPCHECK(dpoff.alloc((size_t)Np + 1)); HIPCHECK(failw.alloc(2));
+  HIPCHECK(hipMemsetAsync(failw.p, 0x7f, 2 * sizeof(int), h->stream));
+  HIPCHECK(hipMemcpyAsync(dpoff.p, poff.data(), ((size_t)Np + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+  // S = U - W V^-1 W^T, held rows identity
+  if (Np) BA_LAUNCH(k_cov_points, dim3((Np + 255) / 256), dim3(256), 0, h->stream, h->slot.p, h->pt_off.p, h->p_cam.p,
+                    h->Hpp[h->pb].p, pt_held_ptr(h), Np, rcond, status.p, Vinv.p, failw.p);
+  BA_LAUNCH(k_cov_diag<NB>, dim3((NH * Nc + (npad - n) + 255) / 256), dim3(256), 0, h->stream, h->HccBc.p, Nc, npad, A.p);
+  if (Np) {
+    BA_LAUNCH(k_cov_w<CM>, dim3((Np + 3) / 4), dim3(256), 0, h->stream, h->cs[h->cur].p, (const double*)h->intr[h->cur].p,
+              h->ptab[h->cur].p, h->pt_off.p, h->p_cam.p, uv_arr(h, h->p_uv), status.p, Np, h->K4[0], h->K4[1], h->K4[2], h->K4[3],
+              f_scale, (int)loss, Wbuf.p, A.p, npad);
+    if (n_pairs > 0) {
+      const long long g = std::min<long long>((n_pairs + 255) / 256, 64ll * h->n_cu);
+      BA_LAUNCH(k_cov_pairs<NB>, dim3((unsigned)g), dim3(256), 0, h->stream, dpoff.p, Np, h->pt_off.p, h->p_cam.p, status.p, Vinv.p,
+                Wbuf.p, A.p, npad);
+    }
+  }
+  const bool any_held = h->fixed >= 0 || h->any_cam_held;
+  if (any_held) BA_LAUNCH(k_cov_held, dim3(1, n), dim3(256), 0, h->stream, cam_held_ptr(h), h->fixed, NB, n, npad, 1.0, A.p);
+  BA_LAUNCH(k_cov_save_diag, dim3((npad + 255) / 256), dim3(256), 0, h->stream, A.p, npad, dS.p);
+  // potrf
+  for (int kt = 0; kt < nt; ++kt) {
+    const int m = nt - kt - 1;
+    BA_LAUNCH(k_cov_potrf_diag, dim3(1), dim3(256), 0, h->stream, A.p, npad, kt, dS.p, n, rcond, failw.p, tinv.p);
+    if (m == 0) continue;
+    BA_LAUNCH(k_cov_potrf_panel, dim3(m), dim3(256), 0, h->stream, A.p, npad, kt, tinv.p);
+    BA_LAUNCH(k_cov_potrf_update, dim3(m * (m + 1) / 2), dim3(256), 0, h->stream, A.p, npad, kt);
+  }
+  // trtri: L^-1, tile columns last to first
+  for (int jt = nt - 1; jt >= 0; --jt) {
+    const int m = nt - jt - 1;
+    BA_LAUNCH(k_cov_trtri_diag, dim3(1), dim3(256), 0, h->stream, A.p, npad, jt, tinv.p);
+    if (m == 0) continue;
+    BA_LAUNCH(k_cov_trtri_panel, dim3(m), dim3(256), 0, h->stream, (const double*)A.p, npad, jt, (const double*)tinv.p, P.p);
+    BA_LAUNCH(k_cov_trtri_update, dim3(m), dim3(256), 0, h->stream, A.p, npad, jt, (const double*)P.p);
+  }
+  // lauum: L^-T L^-1, tile rows first to last
+  for (int it = 0; it < nt; ++it) {
+    BA_LAUNCH(k_cov_lauum, dim3(it + 1), dim3(256), 0, h->stream, A.p, npad, it, D.p);
+    BA_LAUNCH(k_cov_lauum_copy, dim3(1), dim3(256), 0, h->stream, A.p, npad, it, (const double*)D.p);
+  }
+  if (any_held) BA_LAUNCH(k_cov_held, dim3(1, n), dim3(256), 0, h->stream, cam_held_ptr(h), h->fixed, NB, n, npad, 0.0, A.p);
+  if (pt_cov && Np) {
+    HIPCHECK(ptc.alloc(6 * (size_t)Np));
+    BA_LAUNCH(k_cov_point_cov<NB>, dim3((Np + 3) / 4), dim3(256), 0, h->stream, (const double*)A.p, npad, h->pt_off.p, h->p_cam.p,
+              status.p, Vinv.p, Wbuf.p, Np, ptc.p);
+    HIPCHECK(h->rbuf.alloc(6 * (size_t)Np));
+    BA_LAUNCH(k_unpermute_rows, dim3((Np + 255) / 256), dim3(256), 0, h->stream, ptc.p, h->slot.p, Np, 6, h->rbuf.p);
+  }
+  if (cam_cov) {
+    HIPCHECK(blk.alloc((size_t)NH * Nc));
+    BA_LAUNCH(k_cov_cam_blocks<NB>, dim3((NH * Nc + 255) / 256), dim3(256), 0, h->stream, (const double*)A.p, npad, Nc, blk.p);
+  }
+  if (cam_full) BA_LAUNCH(k_cov_symmetrize, dim3(1, n), dim3(256), 0, h->stream, A.p, npad, n);
+  int fw[2] = {COV_FAIL_NONE, COV_FAIL_NONE};
+  HIPCHECK(hipMemcpyAsync(fw, failw.p, sizeof fw, hipMemcpyDeviceToHost, h->stream));
+  BA_SYNC(h);
+  if (fw[1] >= 0 && fw[1] < Np)
+    return fail(BA_ERR_NUMERIC, "ba_covariance: point %d is not determined by its observations (3x3 block fails the rank test at "
+                "rcond %g: zero parallax?); hold it or remove it", fw[1], rcond);
+  if (fw[0] >= 0 && fw[0] < n)
+    return fail(BA_ERR_NUMERIC, "ba_covariance: the reduced camera matrix is singular at camera %d, parameter %s (Cholesky pivot "
+                "fails the rank test at rcond %g): the gauge must be fixed -- 6 pose dof + scale for the pinhole with fixed_cam "
+                "(hold one more coordinate), 7 dof for a BAL problem with nothing held", fw[0] / NB, cov_param_name(fw[0] % NB), rcond);
+  if (cam_cov) HIPCHECK(hipMemcpyAsync(cam_cov, blk.p, (size_t)NH * Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (pt_cov && Np) HIPCHECK(hipMemcpyAsync(pt_cov, h->rbuf.p, 6 * (size_t)Np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (cam_full)
+    HIPCHECK(hipMemcpy2DAsync(cam_full, (size_t)n * sizeof(double), A.p, (size_t)npad * sizeof(double), (size_t)n * sizeof(double), n,
+                              hipMemcpyDeviceToHost, h->stream));
+  BA_SYNC(h);
+  return BA_OK;
+}
+extern "C" int ba_covariance(ba_handle* h, const double* intr, int32_t loss, double f_scale, double rcond, double* cam_cov,
+                             double* pt_cov, double* cam_full) {
+  if (!h) return fail(BA_ERR_INVALID, "null handle");
+  if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
+  if (h->multi) return fail(BA_ERR_INVALID, "ba_covariance: multi-rank jobs are not supported");
+  if (!intr && (h->cam_held_or & ~0x3fu)) return fail(BA_ERR_INVALID, "camera mask bits 6-8 (f, k1, k2) need the BAL camera model");
+  if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
+  if (!(f_scale > 0)) return fail(BA_ERR_INVALID, "f_scale must be positive");
+  const long long n = (long long)(intr ? BalCam::NB : Pinhole::NB) * h->Nc;
+  if (n > COV_MAX_N) return fail(BA_ERR_INVALID, "ba_covariance: %lld camera parameters, more than the %d the dense inverse takes", n, COV_MAX_N);
+  if (!(rcond > 0)) rcond = COV_RCOND_DEFAULT;
+  if (set_device(h)) return BA_ERR_HIP;
+  if (intr) { if (int rc = bal_enter(h, intr)) { h->model = 0; return rc; } }
+  const int rc = intr ? cov_impl<BalCam>(h, (ba_loss)loss, f_scale, rcond, cam_cov, pt_cov, cam_full)
+                      : cov_impl<Pinhole>(h, (ba_loss)loss, f_scale, rcond, cam_cov, pt_cov, cam_full);
+  const std::string msg = g_err;
+  if (rc != BA_OK) { (void)hipStreamSynchronize(h->stream); h->launch_err = hipSuccess; }
+  if (intr) bal_leave(h);
   (void)hipStreamSynchronize(h->stream);
   g_err = msg;
   return rc;

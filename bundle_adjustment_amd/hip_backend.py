@@ -105,6 +105,7 @@ SYMBOLS = {
     "ba_linearize": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, _DP, _DP, _DP, _DP]),
     "ba_schur_system": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32,
                                   C.c_int32, _DP, _DP, _DP, _DP]),
+    "ba_covariance": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.c_double, C.c_double, _DP, _DP, _DP]),
     "ba_default_options": (C.c_int, [C.POINTER(BAOptions)]),
     "ba_solve": (C.c_int, [C.c_void_p, C.POINTER(BAOptions), C.POINTER(BASummary)]),
     "ba_get_profile": (C.c_int, [C.c_void_p, C.POINTER(BAProfile)]),
@@ -141,6 +142,22 @@ def held_camera_mask(cams, n_cams, nb=6):
     if a.size and (a.min() < 0 or a.max() > 0x1FF):
         raise ValueError("camera mask bits must lie in 0-8 (rvec 0-2, t 3-5, f 6, k1 7, k2 8)")
     return a.astype(np.uint16)
+
+
+def unpack_sym(packed, nb):
+    """(..., nb (nb + 1) / 2) packed upper triangles, row by row (00 01 .. 0nb-1 11 ..), -> (..., nb, nb) symmetric."""
+    packed = np.asarray(packed)
+    iu = np.triu_indices(nb)
+    out = np.zeros(packed.shape[:-1] + (nb, nb), dtype=packed.dtype)
+    out[..., iu[0], iu[1]] = packed
+    out[..., iu[1], iu[0]] = packed
+    return out
+
+
+def pack_sym(full, nb):
+    """Inverse of unpack_sym: the upper triangles of (..., nb, nb), row by row."""
+    iu = np.triu_indices(nb)
+    return np.asarray(full)[..., iu[0], iu[1]]
 
 
 def held_point_mask(points, n_pts):
@@ -313,6 +330,23 @@ class Solver:
                                          float(lam if lam_prev is None else lam_prev), int(jacobian_precision), n_vec,
                                          None if vv is None else _dp(vv), None if sv is None else _dp(sv), _dp(g), _dp(minv)))
         return dict(g=g, minv=minv, sv=None if sv is None else sv.reshape(shape))
+
+    def covariance(self, loss="linear", f_scale=1.0, intr=None, full=False, rcond=0.0):
+        """ba_covariance: marginal covariances of the cameras and points at the current parameters, held parameters (fixed_cam,
+        set_held) conditioned on.  intr None: pinhole (nb 6), else (Nc, 3) (f, k1, k2) of the BAL camera (nb 9).  Returns
+        dict(cams (Nc, nb, nb), points (Np, 3, 3), full (N, N) with N = nb Nc, or None).  Held entries are 0, points seen
+        from one camera only NaN; an undetermined gauge or point raises BAHipError (BA_ERR_NUMERIC)."""
+        nb = 6 if intr is None else 9
+        nh = nb * (nb + 1) // 2
+        ip = None
+        if intr is not None:
+            intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
+            ip = _dp(intr)
+        cam = np.empty((self.n_cams, nh))
+        pts = np.empty((self.n_pts, 6))
+        fm = np.empty((nb * self.n_cams, nb * self.n_cams)) if full else None
+        _check(self._lib.ba_covariance(self._h, ip, loss_code(loss), float(f_scale), float(rcond), _dp(cam), _dp(pts), _dp(fm)))
+        return dict(cams=unpack_sym(cam, nb), points=unpack_sym(pts, 3), full=fm)
 
     def _last_linearization(self):
         lin = getattr(self, "_lin", None)

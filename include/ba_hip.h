@@ -288,6 +288,34 @@ int ba_schur_system(ba_handle* h, const double* intr, int32_t loss, double f_sca
                     double lambda_prev, int32_t jacobian_precision, int32_t n_vec, const double* v, double* sv,
                     double* g, double* minv);
 
+/* Marginal covariances of the cameras and points at the current parameters (normally right after ba_solve / ba_solve_bal;
+ * Ceres' Covariance, g2o's computeMarginals, GTSAM's Marginals; no reference counterpart).  H = J^T diag(w) J is the
+ * Gauss-Newton matrix of `loss` / f_scale (the IRLS weights of the solve, no damping, unit pixel noise: multiply by
+ * 2 cost / (m - n), m residuals and n free parameters, for the variance estimated from the fit).  Free parameters are those
+ * neither fixed_cam nor the ba_set_held masks hold; Sigma = (H_free)^-1, and held parameters get rows and columns that are
+ * exactly 0.0 (the covariance conditional on the held values, like Ceres' constant blocks).  Computed through the Schur
+ * complement S = U - W V^-1 W^T (held rows identity, as in ba_schur_system), Sigma_cams = S^-1 formed densely on the device,
+ * Sigma_p = V_p^-1 + V_p^-1 (sum_{i,j in obs(p)} W_i^T Sigma[c_i, c_j] W_j) V_p^-1.  Held points are left out of S, their
+ * Sigma_p is 0.  A free point seen from one camera only (one observation, or several by the same camera) has an
+ * unobservable depth: it is left out of S with its observations (their information about the camera is exactly what
+ * marginalising the point removes) and its Sigma_p is NaN.
+ *   intr     NULL: the pinhole (NB 6, NH 21); else (f, k1, k2)[Nc] of the BAL camera (NB 9, NH 45), as in ba_schur_system
+ *   rcond    rank test: a Cholesky pivot d_k <= rcond * S_kk (S's own diagonal entry) of S, or of the 3x3 V_p of a free
+ *            point seen from two or more cameras, fails the call with BA_ERR_NUMERIC; ba_last_error() names the first
+ *            camera and parameter (and says the gauge must be fixed: 6 pose dof + scale for the pinhole with fixed_cam,
+ *            7 for a BAL problem with nothing held) or the first point.  rcond <= 0: the library default, 1e-10
+ *            (DESIGN.md 4e).  Nothing is written on failure.
+ *   cam_cov  double[Nc][NH]   packed upper triangles of the cameras' diagonal blocks, Hcc's order
+ *   pt_cov   double[Np][6]    the points' 3x3 blocks, Hpp's order
+ *   cam_full double[N][N]     N = NB Nc, row-major: the whole camera covariance, cross-camera blocks included
+ * Any output may be NULL.  Refused: BA_ERR_STATE before ba_set_params; BA_ERR_INVALID in a multi-rank job, for N > 16384
+ * (the dense matrix, 2 GiB of fp64, is allocated for the call and released before it returns), for ba_schur_system's
+ * argument errors (loss, f_scale, BAL mask bits on the pinhole).  The handle is left as it was found (parameters, masks,
+ * intrinsics; a later ba_solve gives bit-identical results).  S is assembled with fp64 atomics: the covariances are not
+ * bitwise reproducible run to run. */
+int ba_covariance(ba_handle* h, const double* intr, int32_t loss, double f_scale, double rcond, double* cam_cov, double* pt_cov,
+                  double* cam_full);
+
 /* K2-K7: the whole LM / Schur / PCG loop on the device; replaces the
  * scipy.optimize.least_squares call at src/bundle_adjuster.py:170-174. */
 int ba_default_options(ba_options* opts);
