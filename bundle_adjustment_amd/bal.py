@@ -138,23 +138,55 @@ def from_pinhole(prob: BAProblem) -> BALProblem:
     return BALProblem(cams, prob.pts.copy(), prob.cam_idx.copy(), prob.pt_idx.copy(), uv).validate()
 
 
-def solve(prob: BALProblem, device=0, fixed_cam=-1, hold_intrinsics=False, held_cameras=None, held_points=None, **options):
+def _bal_priors(prob, camera_priors, intrinsics_sigma):
+    """camera_priors plus the calibration regulariser: a prior on f, k1, k2 of every camera at their input values with
+    standard deviations intrinsics_sigma = (s_f, s_k1, s_k2), added to the 9 x 9 blocks of camera_priors."""
+    if intrinsics_sigma is None:
+        return camera_priors
+    from .priors import camera_prior_nb, info_from_sigma, pack_priors
+    nc = prob.n_cams
+    mean = np.zeros((nc, 9))
+    info = np.zeros((nc, 9, 9))
+    if camera_priors is not None:
+        nb = camera_prior_nb(camera_priors) or 6
+        m, packed = pack_priors(camera_priors, nc, nb, "camera")
+        iu = np.triu_indices(nb)
+        full = np.zeros((nc, nb, nb))
+        full[:, iu[0], iu[1]] = packed
+        full[:, iu[1], iu[0]] = packed
+        if nb == 9 and full[:, 6:, :].any():
+            raise ValueError("intrinsics_sigma and camera_priors both set information on f, k1, k2")
+        mean[:, :nb] = m
+        info[:, :nb, :nb] = full
+    mean[:, 6:] = prob.cams[:, 6:9]
+    info[:, 6:, 6:] = info_from_sigma(np.asarray(intrinsics_sigma, dtype=np.float64).reshape(3))
+    return mean, info
+
+
+def solve(prob: BALProblem, device=0, fixed_cam=-1, hold_intrinsics=False, held_cameras=None, held_points=None,
+          camera_priors=None, point_priors=None, intrinsics_sigma=None, **options):
     """Adjust a BAL problem on the GPU (``ba_solve_bal``: poses, points AND f / k1 / k2 per camera).  Returns
     ``(BALProblem with the adjusted parameters, summary dict)``; options as ``hip_backend.Solver.solve``.
     hold_intrinsics: keep every camera's f, k1, k2 (calibrated cameras); held_cameras / held_points: parameters kept
-    constant, in the forms of ``hip_backend.Solver.set_held`` (a (Nc, 9) bool array names single BAL parameters)."""
+    constant, in the forms of ``hip_backend.Solver.set_held`` (a (Nc, 9) bool array names single BAL parameters).
+    camera_priors / point_priors: Gaussian priors in the forms of ``hip_backend.Solver.set_priors`` (camera blocks of 6 or
+    9 coordinates); intrinsics_sigma = (s_f, s_k1, s_k2): the calibration regulariser, a prior on f, k1, k2 of every
+    camera at their input values -- the soft form of hold_intrinsics.  With priors ``final_cost`` is the total objective."""
     from . import hip_backend
     with hip_backend.Solver(device) as s:
         summary, cams, pts = s.solve_bal(prob, fixed_cam=fixed_cam, hold_intrinsics=hold_intrinsics,
-                                         held_cameras=held_cameras, held_points=held_points, **options)
+                                         held_cameras=held_cameras, held_points=held_points,
+                                         camera_priors=_bal_priors(prob, camera_priors, intrinsics_sigma),
+                                         point_priors=point_priors, **options)
     return BALProblem(cams, pts, prob.cam_idx.copy(), prob.pt_idx.copy(), prob.uv.copy()), summary
 
 
 def covariance(prob: BALProblem, device=0, fixed_cam=-1, hold_intrinsics=False, held_cameras=None, held_points=None,
-               loss="linear", f_scale=1.0, full=False, rcond=0.0):
+               loss="linear", f_scale=1.0, full=False, rcond=0.0, camera_priors=None, point_priors=None, intrinsics_sigma=None):
     """Marginal covariances of a BAL problem at ``prob``'s parameters (``ba_covariance``; normally the problem ``solve``
     returned).  The held-parameter forms are those of ``solve``; a BAL problem with nothing held has a free 7-dof gauge
-    and is refused (hold e.g. ``fixed_cam`` and one translation coordinate of another camera).  Returns
+    and is refused (hold e.g. ``fixed_cam`` and one translation coordinate of another camera) unless priors
+    (camera_priors / point_priors / intrinsics_sigma, as in ``solve``) fix it: Sigma = (H + L)^-1.  Returns
     ``dict(cams (Nc, 9, 9), points (Np, 3, 3), full (9 Nc, 9 Nc) or None)``, see ``hip_backend.Solver.covariance``."""
     from . import hip_backend
     with hip_backend.Solver(device) as s:
@@ -164,4 +196,7 @@ def covariance(prob: BALProblem, device=0, fixed_cam=-1, hold_intrinsics=False, 
             cm = (np.zeros(s.n_cams, np.uint16) if cm is None else cm) | np.uint16(0x1C0)
         if cm is not None or held_points is not None:
             s.set_held(cm, held_points)
+        cp = _bal_priors(prob, camera_priors, intrinsics_sigma)
+        if cp is not None or point_priors is not None:
+            s.set_priors(cp, point_priors)
         return s.covariance(loss=loss, f_scale=f_scale, intr=intr, full=full, rcond=rcond)

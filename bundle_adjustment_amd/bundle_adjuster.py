@@ -42,7 +42,7 @@ class BundleAdjuster:
     def __init__(self, camera_matrix, window_size=5, *, fixed_keyframes=1, device_id=0, loss='huber', f_scale=1.0, ftol=1e-5,
                  xtol=1e-5, gtol=1e-8, max_iters=50, pcg_tol=0.1, pcg_max_iters=200, pcg_model_tol=0.0, preconditioner='schur_jacobi',
                  jacobian='f64', comm=None, sparsity_plot_hook=None, verbose=0, reuse_window=True, metrics_path=None,
-                 inplace_writeback=False, reuse_min_obs=20000, covariance=False):
+                 inplace_writeback=False, reuse_min_obs=20000, covariance=False, keyframe_priors=None, point_priors=None):
         self.camera_matrix = camera_matrix
         self.window_size = window_size
         # the first fixed_keyframes keyframes of the window are held (1: the reference's rule, src/bundle_adjuster.py:141-143:
@@ -59,6 +59,13 @@ class BundleAdjuster:
             raise ValueError("covariance=True is not supported in a multi-rank job")
         self.covariance = bool(covariance)
         self.last_covariance = None
+        # Gaussian priors (ba_set_priors), plain attributes the caller may change between run()s: keyframe id -> (rvec | t
+        # mean (6,), 6 x 6 information), map point id -> (mean (3,), 3 x 3 information).  Entries outside the window are
+        # ignored; every run() applies the ones inside it (also when the uploaded window is reused) and removes them from the
+        # solver once the dicts hold none.  With covariance=True the covariances include them.
+        self.keyframe_priors = {} if keyframe_priors is None else keyframe_priors
+        self.point_priors = {} if point_priors is None else point_priors
+        self._priors_applied = False
         self.device_id = device_id
         hip_backend.loss_code(loss)            # an unknown loss or preconditioner name fails here, not at the first run()
         hip_backend.precond_code(preconditioner)
@@ -195,6 +202,23 @@ class BundleAdjuster:
         if self.fixed_keyframes > 1:
             solver.set_held(cams=np.arange(n_cams) < self.fixed_keyframes)
 
+    def _apply_priors(self, solver, local_kf_ids, local_map_point_ids, p_begin, p_end):
+        """The priors of the window's keyframes and of the landmarks [p_begin, p_end) this rank owns -> the solver; a
+        solver that carries priors from an earlier run() and gets none now is cleared."""
+        cams, points = {}, {}
+        if self.keyframe_priors:
+            cams = {i: self.keyframe_priors[k] for i, k in enumerate(local_kf_ids) if k in self.keyframe_priors}
+        if self.point_priors:
+            for i, mp in enumerate(np.asarray(local_map_point_ids).tolist()):
+                if p_begin <= i < p_end and mp in self.point_priors:
+                    points[i - p_begin] = self.point_priors[mp]
+        if cams or points:
+            solver.set_priors(cams=cams or None, points=points or None)
+            self._priors_applied = True
+        elif self._priors_applied:
+            solver.set_priors()
+            self._priors_applied = False
+
     # -- the solve step -------------------------------------------------------------------
     def run(self, gmap: Map):
         """Sliding-window / global bundle adjustment, ``src/bundle_adjuster.py:122-193``."""
@@ -242,12 +266,18 @@ class BundleAdjuster:
             else:
                 shard, _ = extract_shard(prob, p_begin, p_end)
                 solver.set_problem(shard)
+                self._priors_applied = False   # (a new problem starts without priors)
                 self._hold_keyframes(solver, prob.n_cams)
         elif same_structure:
             solver.set_params(prob.cams, prob.pts)
         else:
             solver.set_problem(prob)
+            self._priors_applied = False
             self._hold_keyframes(solver, prob.n_cams)
+        if world > 1:
+            self._apply_priors(solver, local_kf_ids, local_map_point_ids, p_begin, p_end)
+        else:
+            self._apply_priors(solver, local_kf_ids, local_map_point_ids, 0, prob.n_pts)
         self._uploaded_token = token
         summary = solver.solve(**self.solver_options)          # costs / verdicts are global on every rank
         self.last_summary = summary

@@ -36,12 +36,13 @@ __device__ inline double cov_sym(const double* __restrict__ A, size_t ld, int r,
 
 // ------------------------------------------------------------------------------------------------ per point
 // Thread per point (caller order pc, slot s = slot[pc]): status, V^-1 (packed 00 01 02 11 12 22) and the rank test of V
-// for a free point seen from two or more cameras: a Cholesky pivot d_k <= rcond V_kk fails, the smallest such caller
+// for a free point seen from two or more cameras (or from one, with a prior: pt_info, nullable): a Cholesky pivot d_k <= rcond V_kk fails, the smallest such caller
 // index goes to fail[1].
 __global__ void __launch_bounds__(256)
 k_cov_points(const int* __restrict__ slot, const int* __restrict__ pt_off, const int* __restrict__ p_cam,
              const double* __restrict__ Hpp, const unsigned char* __restrict__ pt_held, int n_pts, double rcond,
-             unsigned char* __restrict__ status, double* __restrict__ Vinv, int* __restrict__ fail) {
+             unsigned char* __restrict__ status, double* __restrict__ Vinv, int* __restrict__ fail,
+             const double* __restrict__ pt_info) {
   const int pc = blockIdx.x * 256 + threadIdx.x;
   if (pc >= n_pts) return;
   const int s = slot[pc];
@@ -52,6 +53,11 @@ k_cov_points(const int* __restrict__ slot, const int* __restrict__ pt_off, const
   } else {
     bool one = true;
     for (int j = beg + 1; j < end; ++j) one = one && p_cam[j] == p_cam[beg];
+    if (one && pt_info) {                // a non-zero prior block (ba_set_priors, slot order) fixes the depth: an ordinary point
+      bool prior = false;
+      for (int q = 0; q < 6; ++q) prior = prior || pt_info[6 * (size_t)s + q] != 0.0;
+      one = !prior;
+    }
     if (one) st = COV_PT_ONECAM;
   }
   double inv[6] = {0, 0, 0, 0, 0, 0};

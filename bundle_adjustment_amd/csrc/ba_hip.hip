@@ -212,6 +212,14 @@ struct ba_handle {
   std::vector<unsigned char> h_pt_held;
   double held_x2 = 0.0;
   DBuf<double> held_red;           // multi-rank: held_x2 summed over the shards (one all-reduce per solve)
+  // Gaussian priors (ba_set_priors): camera blocks in camera order, point blocks in point-slot order; the kernels get null
+  // pointers while none are set.  Means of zero blocks are uploaded as 0 (they are never read by the caller's rule, and the
+  // kernels then need no flag per block).  fold_prior_rows: PRIOR_ROWS while a solve folds the prior rows behind partR.
+  DBuf<double> cam_info, cam_mean, pt_info, pt_mean, prior_in, prior_rows;
+  bool any_cam_prior = false, any_pt_prior = false;
+  int prior_nb = 0;
+  long long prior_blocks = 0;
+  int fold_prior_rows = 0;
   // observation lists (camera order, point order)
   DBuf<int> offk, c_pt, c_orig, pt_off, p_cam, slot, long_pts;
   DBuf<int> c_ptf[2], p_camf[2];  // index streams with the "weights are not (1, 1)" flag (robust loss; c_ptf pairs with c_w, p_camf with p_w)
@@ -833,7 +841,7 @@ static int alloc_solver_buffers(ba_handle* h) {
   }
   h->pb = h->lb = 0;          // (both halves of the linearisation start in buffer set 0)
   HIPCHECK(h->Hccd.alloc(NHX * (size_t)Nc)); HIPCHECK(h->Minv.alloc(NHX * (size_t)Nc));
-  HIPCHECK(h->partR.alloc(2 * (size_t)NPART * Nc));
+  HIPCHECK(h->partR.alloc(2 * (size_t)NPART * Nc + 2 * PRIOR_ROWS));   // + the prior rows of a solve with priors (k_prior_cost)
   HIPCHECK(h->partL[0].alloc(NLX * (size_t)NPART * Nc)); HIPCHECK(h->partL[1].alloc(NLX * (size_t)NPART * Nc));
   HIPCHECK(h->part6.alloc(NBX * (size_t)NPART * Nc + 8));   // + the u.y word: one all-reduce carries both
   HIPCHECK(h->partE.alloc(NHX * (size_t)NPART * Nc));
@@ -1402,6 +1410,11 @@ static int set_problem_host(ba_handle* h, int Nc, int Np, int No, const int32_t*
   return upload_host_layout(h, L, uv, stage);
 }
 
+static void clear_priors(ba_handle* h) {
+  h->any_cam_prior = h->any_pt_prior = false;
+  h->prior_nb = 0;
+  h->prior_blocks = 0;
+}
 static void clear_held(ba_handle* h) {
   h->any_cam_held = h->any_pt_held = false;
   h->cam_held_or = 0;
@@ -1427,6 +1440,7 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
   if (!K4) return fail(BA_ERR_INVALID, "null intrinsics");
   if (fixed_cam < -1 || fixed_cam >= n_cams) return fail(BA_ERR_INVALID, "fixed_cam %d out of range", fixed_cam);
   clear_held(h);                     // a new problem starts with nothing held beyond its fixed camera
+  clear_priors(h);                   // ... and without priors
   {   // index ranges, before anything is touched (a rejected call keeps the previous problem): branch-free sweep first
     int ok = 1;
     for (int64_t i = 0; i < n_obs; ++i)
@@ -1592,6 +1606,149 @@ extern "C" int ba_set_held(ba_handle* h, const uint16_t* cam_held, const uint8_t
   return BA_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------ priors
+// eigenvalues of a packed symmetric n x n block (n <= 9) by cyclic Jacobi rotations: smallest and largest
+static void sym_eig_range(const double* packed, int n, double* lo, double* hi) {
+  double A[9][9];
+  for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) A[i][j] = packed[ST(n, i, j)];
+  for (int sweep = 0; sweep < 64; ++sweep) {
+    double off = 0.0, diag = 0.0;
+    for (int i = 0; i < n; ++i) { diag += A[i][i] * A[i][i]; for (int j = i + 1; j < n; ++j) off += A[i][j] * A[i][j]; }
+    if (off <= 1e-60 || off <= 1e-34 * diag) break;
+    for (int p = 0; p < n; ++p)
+      for (int q = p + 1; q < n; ++q) {
+        if (A[p][q] == 0.0) continue;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
+        const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
+        for (int k = 0; k < n; ++k) { const double akp = A[k][p], akq = A[k][q]; A[k][p] = c * akp - sn * akq; A[k][q] = sn * akp + c * akq; }
+        for (int k = 0; k < n; ++k) { const double apk = A[p][k], aqk = A[q][k]; A[p][k] = c * apk - sn * aqk; A[q][k] = sn * apk + c * aqk; }
+      }
+  }
+  *lo = *hi = A[0][0];
+  for (int i = 1; i < n; ++i) { *lo = std::min(*lo, A[i][i]); *hi = std::max(*hi, A[i][i]); }
+}
+// one block of a prior: 0 = zero block (no prior), 1 = fine, < 0 = refused (the message is set)
+static int check_prior_block(const char* what, int idx, const double* info, const double* mean, int n) {
+  const int nh = n * (n + 1) / 2;
+  bool any = false;
+  for (int q = 0; q < nh; ++q) {
+    if (!std::isfinite(info[q])) return fail(BA_ERR_INVALID, "ba_set_priors: %s %d: non-finite entry in the information block", what, idx);
+    any |= info[q] != 0.0;
+  }
+  if (!any) return 0;
+  for (int q = 0; q < n; ++q)
+    if (!std::isfinite(mean[q])) return fail(BA_ERR_INVALID, "ba_set_priors: %s %d: non-finite mean under a non-zero information block", what, idx);
+  double lo, hi;
+  sym_eig_range(info, n, &lo, &hi);
+  if (lo < -1e-12 * hi || !(hi > 0.0))
+    return fail(BA_ERR_INVALID, "ba_set_priors: %s %d: the information block is not positive semidefinite (eigenvalues %g .. %g)", what, idx, lo, hi);
+  return 1;
+}
+// Gaussian priors: validated on the host (caller's orders), uploaded in the problem's orders (point blocks through the
+// point -> slot permutation of ba_set_problem).  NULL pairs / all-zero blocks set nothing.
+extern "C" int ba_set_priors(ba_handle* h, int32_t nb, const double* cam_mean, const double* cam_info, const double* pt_mean,
+                             const double* pt_info) {
+  if (!h) return fail(BA_ERR_INVALID, "null handle");
+  if (!h->have_problem) return fail(BA_ERR_STATE, "ba_set_problem has not been called");
+  if ((cam_mean == nullptr) != (cam_info == nullptr) || (pt_mean == nullptr) != (pt_info == nullptr))
+    return fail(BA_ERR_INVALID, "ba_set_priors: a mean and its information array come together (both or neither NULL)");
+  if (cam_info && nb != 6 && nb != 9) return fail(BA_ERR_INVALID, "ba_set_priors: nb must be 6 (rvec | t) or 9 (rvec | t | f k1 k2), not %d", nb);
+  const int Nc = h->Nc, Np = h->Np;
+  const int nh = nb * (nb + 1) / 2;
+  long long nc_blocks = 0, np_blocks = 0;
+  std::vector<double> cm, pm;
+  if (cam_info) {
+    cm.assign(cam_mean, cam_mean + (size_t)nb * Nc);
+    for (int c = 0; c < Nc; ++c) {
+      const int k = check_prior_block("camera", c, cam_info + (size_t)nh * c, cam_mean + (size_t)nb * c, nb);
+      if (k < 0) return k;
+      if (k) ++nc_blocks;
+      else for (int q = 0; q < nb; ++q) cm[(size_t)nb * c + q] = 0.0;
+    }
+  }
+  if (pt_info) {
+    pm.assign(pt_mean, pt_mean + 3 * (size_t)Np);
+    for (int p = 0; p < Np; ++p) {
+      const int k = check_prior_block("point", p, pt_info + 6 * (size_t)p, pt_mean + 3 * (size_t)p, 3);
+      if (k < 0) return k;
+      if (k) ++np_blocks;
+      else for (int q = 0; q < 3; ++q) pm[3 * (size_t)p + q] = 0.0;
+    }
+  }
+  if (set_device(h)) return BA_ERR_HIP;
+  clear_priors(h);
+  h->linearized = false;
+  if (nc_blocks) {
+    HIPCHECK(h->cam_info.alloc((size_t)nh * Nc)); HIPCHECK(h->cam_mean.alloc((size_t)nb * Nc));
+    HIPCHECK(hipMemcpyAsync(h->cam_info.p, cam_info, (size_t)nh * Nc * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(h->cam_mean.p, cm.data(), (size_t)nb * Nc * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  }
+  if (np_blocks) {
+    HIPCHECK(h->pt_info.alloc(6 * (size_t)Np)); HIPCHECK(h->pt_mean.alloc(3 * (size_t)Np)); HIPCHECK(h->prior_in.alloc(9 * (size_t)Np));
+    HIPCHECK(hipMemcpyAsync(h->prior_in.p, pt_info, 6 * (size_t)Np * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(h->prior_in.p + 6 * (size_t)Np, pm.data(), 3 * (size_t)Np * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    BA_LAUNCH(k_scatter_rows, dim3((Np + 255) / 256), dim3(256), 0, h->stream, (const double*)h->prior_in.p, h->slot.p, Np, 6, h->pt_info.p);
+    BA_LAUNCH(k_scatter_rows, dim3((Np + 255) / 256), dim3(256), 0, h->stream, (const double*)(h->prior_in.p + 6 * (size_t)Np), h->slot.p, Np, 3,
+              h->pt_mean.p);
+  }
+  BA_SYNC(h);                       // (the host copies above go out of scope)
+  h->any_cam_prior = nc_blocks > 0;
+  h->any_pt_prior = np_blocks > 0;
+  h->prior_nb = nc_blocks ? nb : 0;
+  h->prior_blocks = nc_blocks + np_blocks;
+  return BA_OK;
+}
+static bool any_prior(const ba_handle* h) { return h->any_cam_prior || h->any_pt_prior; }
+// camera priors at parameter set `which` (info == null: none set, or `with_cams` false)
+static CamPriors cam_priors(const ba_handle* h, int which, bool with_cams = true) {
+  CamPriors pr;
+  const bool on = with_cams && h->any_cam_prior;
+  pr.info = on ? h->cam_info.p : nullptr; pr.mean = on ? h->cam_mean.p : nullptr;
+  pr.cams = h->cams[which].p; pr.intr = h->intr[which].p; pr.nb = h->prior_nb;
+  return pr;
+}
+// the prior rows behind partR at parameter set `which` (a solve with priors: the next scalar fold adds them to the cost);
+// the camera sum counts once per job: rank 0's
+static void launch_prior_cost(ba_handle* h, int which) {
+  if (!h->fold_prior_rows) return;
+  BA_LAUNCH(k_prior_cost, dim3(PRIOR_ROWS), dim3(256), 0, h->stream, cam_priors(h, which, h->rank == 0), h->Nc,
+            h->any_pt_prior ? (const double*)h->pt_info.p : (const double*)nullptr, (const double*)h->pt_mean.p, (const double*)h->ptab[which].p,
+            h->Np, h->partR.p + 2 * (size_t)NPART * h->Nc);
+}
+static const char* kPriorNeedsBal = "camera priors with nb = 9 (f, k1, k2) need the BAL camera model";
+extern "C" int ba_prior_cost(ba_handle* h, const double* intr, double* cam_cost, double* pt_cost) {
+  if (!h) return fail(BA_ERR_INVALID, "null handle");
+  if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
+  if (!intr && h->prior_nb == 9) return fail(BA_ERR_INVALID, "%s", kPriorNeedsBal);
+  if (set_device(h)) return BA_ERR_HIP;
+  double sums[2] = {0.0, 0.0};
+  if (any_prior(h)) {
+    if (intr) {
+      HIPCHECK(h->tri.alloc(3 * (size_t)h->Nc + 8));
+      HIPCHECK(hipMemcpyAsync(h->tri.p, intr, 3 * (size_t)h->Nc * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHECK(h->prior_rows.alloc(4 * PRIOR_ROWS));
+    CamPriors pr = cam_priors(h, h->cur);
+    pr.intr = intr ? h->tri.p : nullptr;
+    CamPriors none = pr;
+    none.info = nullptr;
+    BA_LAUNCH(k_prior_cost, dim3(PRIOR_ROWS), dim3(256), 0, h->stream, pr, h->Nc, (const double*)nullptr, (const double*)nullptr,
+              (const double*)h->ptab[h->cur].p, 0, h->prior_rows.p);
+    BA_LAUNCH(k_prior_cost, dim3(PRIOR_ROWS), dim3(256), 0, h->stream, none, h->Nc,
+              h->any_pt_prior ? (const double*)h->pt_info.p : (const double*)nullptr, (const double*)h->pt_mean.p, (const double*)h->ptab[h->cur].p,
+              h->Np, h->prior_rows.p + 2 * PRIOR_ROWS);
+    double rows[4 * PRIOR_ROWS];
+    HIPCHECK(hipMemcpyAsync(rows, h->prior_rows.p, sizeof rows, hipMemcpyDeviceToHost, h->stream));
+    BA_SYNC(h);
+    for (int k = 0; k < 2; ++k)
+      for (int b = 0; b < PRIOR_ROWS; ++b) sums[k] += rows[2 * (k * PRIOR_ROWS + b) + 1];
+  }
+  if (cam_cost) *cam_cost = 0.5 * sums[0];
+  if (pt_cost) *pt_cost = 0.5 * sums[1];
+  return BA_OK;
+}
+
 // multi-rank: every rank ends up with the points of all shards (its own at [p_begin, p_begin + Np)):
 // zero-filled buffer + own slice, summed over the ranks with the solver's all-reduce
 extern "C" int ba_allgather_points(ba_handle* h, int64_t p_begin, int64_t n_total, double* pts_all) {
@@ -1654,7 +1811,7 @@ static ScalarsArgs scalars_args(ba_handle* h, bool with_step, int k, double tol2
                                 double lambda, double lam_floor = 0.0) {
   const bool direct = with_step && !h->multi;         // results straight into host-mapped memory + sequence word
   ScalarsArgs a;
-  a.partR = h->partR.p; a.nR = NPART * h->Nc;
+  a.partR = h->partR.p; a.nR = NPART * h->Nc + h->fold_prior_rows;   // (+ the prior rows right behind: a solve with priors)
   a.partB = h->partB.p; a.nB = (with_step && h->Np > 0) ? h->nblkP + h->nblkL : 0;
   a.partC = h->partC.p; a.nC = with_step ? nbv(h) : 0;
   a.kit = k;
@@ -1720,7 +1877,7 @@ static void launch_lin_cam(ba_handle* h, int which, int buf, ba_loss loss, doubl
 static void launch_lin_finalize(ba_handle* h) {
   Scope sc(h, BA_K_MISC);
 #define CALL_T(CM) BA_LAUNCH(k_lin_finalize<CM::NB>, dim3(h->nblkV), dim3(VEC_BLOCK), 0, h->stream, partL_of(h, h->lb), \
-                             nparts_of(h), h->cs[h->cur].p, h->Nc, h->fixed, h->HccBc.p, bc_ptr(h), cam_held_ptr(h))
+                             nparts_of(h), h->cs[h->cur].p, h->Nc, h->fixed, h->HccBc.p, bc_ptr(h), cam_held_ptr(h), cam_priors(h, h->cur))
   BA_BY_MODEL(CALL_T);
 #undef CALL_T
 }
@@ -1774,6 +1931,10 @@ static void launch_lin_pt(ba_handle* h, int w, int pbuf, ba_loss loss, double fs
 #define CALL_T(CM) launch_lin_pt_t<CM>(h, w, pbuf, loss, fscale, lambda, lam_dev, sa)
   BA_BY_MODEL(CALL_T);
 #undef CALL_T
+  // point priors: L_p into Hpp | bp, the damped inverse, y0 and the gtol maxima redone (at the damping the pass used)
+  if (h->any_pt_prior)
+    BA_LAUNCH(k_prior_points, dim3(h->nblkP + h->nblkL), dim3(256), 0, h->stream, (const double*)h->pt_info.p, (const double*)h->pt_mean.p,
+              h->Np, lambda, lam_dev, h->Hpp[pbuf].p, h->bp[pbuf].p, h->Hppinv[pbuf].p, h->y0[pbuf].p, h->ptab[w].p, h->partG[pbuf].p);
   // held points: their blocks and inverses zeroed, the gtol maxima redone without them (the point pass itself is not
   // told about held points: its observation loop and registers stay those of an unmasked solve)
   if (h->any_pt_held)
@@ -1955,7 +2116,7 @@ static void launch_pcg_setup(ba_handle* h, double lambda, int precond, bool fina
 #define SU_ARGS partL_of(h, h->lb), h->HccBc.p, bc_ptr(h), sys_p6(h), sys_E(h), nparts_of(h), h->cs[h->cur].p, lambda,           \
                 precond, h->Nc, h->fixed, h->Hccd.p, h->Minv.p, h->gvec.p, h->x.p, h->r.p, h->p.p, h->s.p,     \
                 h->z.p, h->camA[h->cur].p, h->partV.p, h->st.p, h->partGc.p, h->vx.p, \
-                cam_held_ptr(h)
+                cam_held_ptr(h), cam_priors(h, h->cur, finalize)
 #define CALL_T(CM)                                                                                               \
   do {                                                                                                           \
     if (finalize) BA_LAUNCH((k_pcg_setup<CM, true>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, SU_ARGS);    \
@@ -2026,6 +2187,7 @@ extern "C" int ba_linearize(ba_handle* h, int32_t loss, double f_scale, double* 
   if (!h) return fail(BA_ERR_INVALID, "null handle");
   if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
   if (h->cam_held_or & ~0x3fu) return fail(BA_ERR_INVALID, "camera mask bits 6-8 (f, k1, k2) need the BAL camera model");
+  if (h->prior_nb == 9) return fail(BA_ERR_INVALID, "%s", kPriorNeedsBal);
   if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
   if (!(f_scale > 0)) return fail(BA_ERR_INVALID, "f_scale must be positive");
   if (set_device(h)) return BA_ERR_HIP;
@@ -2085,6 +2247,7 @@ extern "C" int ba_schur_system(ba_handle* h, const double* intr, int32_t loss, d
   if (n_vec < 0 || (n_vec > 0 && (!v || !sv))) return fail(BA_ERR_INVALID, "n_vec vectors need v and sv");
   if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
   if (!intr && (h->cam_held_or & ~0x3fu)) return fail(BA_ERR_INVALID, "camera mask bits 6-8 (f, k1, k2) need the BAL camera model");
+  if (!intr && h->prior_nb == 9) return fail(BA_ERR_INVALID, "%s", kPriorNeedsBal);
   if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
   if (!(f_scale > 0)) return fail(BA_ERR_INVALID, "f_scale must be positive");
   if (precond < 0 || precond > 2) return fail(BA_ERR_INVALID, "precond must be 0 (Jacobi), 1 (Schur-Jacobi) or 2 (Schur-Jacobi kept)");
@@ -2185,6 +2348,7 @@ static double now_s() {
 
 static int eval_cost(ba_handle* h, int which, ba_loss loss, double fscale, double* sse, double* cost) {
   launch_residual(h, which, loss, fscale, nullptr);
+  launch_prior_cost(h, which);
   launch_scalars(h, false);
   if (int rc = allreduce(h, h->scal.p, 2)) return rc;
   HIPCHECK(hipMemcpyAsync(h->h_scal, h->scal.p, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2198,6 +2362,7 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum);
 extern "C" int ba_solve(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   if (!h || !opts || !sum) return fail(BA_ERR_INVALID, "null argument");
   const int rc = solve_impl(h, opts, sum);
+  h->fold_prior_rows = 0;        // (ba_residuals* and the test hooks fold the reprojection rows only)
   if (rc != BA_OK) {             // leave the handle usable: nothing queued, no per-solve mode left on
     const std::string msg = g_err;
     (void)hipStreamSynchronize(h->stream);
@@ -2217,6 +2382,7 @@ static bool small_applies(const ba_handle* h, const ba_options* opts) {
   // fits the multi-workgroup kernel -- five cameras, 2048 landmarks: at most 10 k observations -- is far below its own)
   const char* mw_env = getenv("BA_SMALL_MW");
   const bool mw = h->mw_ok && (!mw_env || atoi(mw_env) != 0);
+  if (any_prior(h)) return false;      // priors: the multi-kernel path (the window kernels do not know them; ba_hip.h)
   return opts->small_solver == 0 && !h->multi && h->Nc <= SMALL_MAX_CAMS && h->Np > 0 && h->Nobs > 0 && (h->Nobs <= SMALL_MAX_OBS || mw) &&
          opts->max_iters >= 1;
 }
@@ -2440,7 +2606,8 @@ static int cov_impl(ba_handle* h, ba_loss loss, double f_scale, double rcond, do
   HIPCHECK(hipMemcpyAsync(dpoff.p, poff.data(), ((size_t)Np + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
   // S = U - W V^-1 W^T, held rows identity
   if (Np) BA_LAUNCH(k_cov_points, dim3((Np + 255) / 256), dim3(256), 0, h->stream, h->slot.p, h->pt_off.p, h->p_cam.p,
-                    h->Hpp[h->pb].p, pt_held_ptr(h), Np, rcond, status.p, Vinv.p, failw.p);
+                    h->Hpp[h->pb].p, pt_held_ptr(h), Np, rcond, status.p, Vinv.p, failw.p,
+                    h->any_pt_prior ? (const double*)h->pt_info.p : (const double*)nullptr);
   BA_LAUNCH(k_cov_diag<NB>, dim3((NH * Nc + (npad - n) + 255) / 256), dim3(256), 0, h->stream, h->HccBc.p, Nc, npad, A.p);
   if (Np) {
     BA_LAUNCH(k_cov_w<CM>, dim3((Np + 3) / 4), dim3(256), 0, h->stream, h->cs[h->cur].p, (const double*)h->intr[h->cur].p,
@@ -2513,6 +2680,7 @@ extern "C" int ba_covariance(ba_handle* h, const double* intr, int32_t loss, dou
   if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
   if (h->multi) return fail(BA_ERR_INVALID, "ba_covariance: multi-rank jobs are not supported");
   if (!intr && (h->cam_held_or & ~0x3fu)) return fail(BA_ERR_INVALID, "camera mask bits 6-8 (f, k1, k2) need the BAL camera model");
+  if (!intr && h->prior_nb == 9) return fail(BA_ERR_INVALID, "%s", kPriorNeedsBal);
   if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
   if (!(f_scale > 0)) return fail(BA_ERR_INVALID, "f_scale must be positive");
   const long long n = (long long)(intr ? BalCam::NB : Pinhole::NB) * h->Nc;
@@ -2577,9 +2745,11 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   if (opts->precond_lag < 0) return fail(BA_ERR_INVALID, "precond_lag must not be negative");
   if (h->model == 0 && (h->cam_held_or & ~0x3fu))
     return fail(BA_ERR_INVALID, "camera mask bits 6-8 (f, k1, k2) need the BAL camera model");
+  if (h->model == 0 && h->prior_nb == 9) return fail(BA_ERR_INVALID, "%s", kPriorNeedsBal);
   if (set_device(h)) return BA_ERR_HIP;
   memset(sum, 0, sizeof *sum);
   h->trace.clear();
+  h->fold_prior_rows = any_prior(h) ? PRIOR_ROWS : 0;      // cost = reprojection + priors in every fold of this solve
   // single rank, every parameter held: nothing to adjust
   if (!h->multi && all_held(h)) {
     double sse = 0, cost = 0;
@@ -2829,6 +2999,7 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     const bool speculated = (it + 1 < opts->max_iters);
     if (speculated) launch_lin_cam(h, 1 - h->cur, 1 - h->lb, loss, fs, true);
     else            launch_residual(h, 1 - h->cur, loss, fs, nullptr);
+    launch_prior_cost(h, 1 - h->cur);          // (priors set: their terms at the trial point, behind the reprojection rows)
     if (debug_poison) BA_LAUNCH(k_poison, dim3(1), dim3(64), 0, h->stream, h->partR.p);
     const long long seq = ++h->step_seq;
     // the step's scalar fold + verdict: single rank with a speculated point half behind it -> workgroup 0 of that launch
@@ -2919,7 +3090,8 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
 
 // ------------------------------------------------------------------ counters, test hooks
 extern "C" int ba_get_stat(ba_handle* h, int32_t which, int64_t* value) {
-  if (!h || !value || which < 0 || which >= BA_STAT_COUNT) return fail(BA_ERR_INVALID, "bad argument");
+  if (!h || !value || which < 0 || which >= BA_STAT_END) return fail(BA_ERR_INVALID, "bad argument");
+  if (which == BA_STAT_PRIOR_BLOCKS) { *value = h->have_problem ? h->prior_blocks : 0; return BA_OK; }
   if (which == BA_STAT_HELD_PARAMS) {
     *value = h->have_problem ? held_params(h, (h->cam_held_or & ~0x3fu) ? BalCam::NB : Pinhole::NB) : 0;
     return BA_OK;

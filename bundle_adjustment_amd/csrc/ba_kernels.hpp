@@ -399,12 +399,35 @@ __device__ inline void held_identity(unsigned held, double* __restrict__ H) {   
       if (((held >> i) | (held >> j)) & 1u) H[UT(NB, i, j)] = (i == j) ? 1.0 : 0.0;
 }
 
+// Gaussian priors (ba_set_priors): 0.5 (x - mu)^T L (x - mu) per camera block and per point, x the caller's additive
+// coordinates.  Camera side: info[c] = packed upper triangle of L_c (nb (nb + 1) / 2 entries, Hcc's order), mean[c] (nb), nb = 6
+// (pose only) or 9; cams / intr = the raw parameters of the linearisation point.  info == null: no camera priors.
+struct CamPriors { const double* info; const double* mean; const double* cams; const double* intr; int nb; };
+// H += L_c, b += L_c (x_c - mu_c) for camera c, in the caller's coordinates (behind the M congruence)
+template <int NB>
+__device__ inline void cam_prior_add(const CamPriors& pr, int c, double* __restrict__ H, double* __restrict__ b) {
+  const int nb = pr.nb < NB ? pr.nb : NB;
+  const double* __restrict__ L = pr.info + (size_t)(pr.nb * (pr.nb + 1) / 2) * c;
+  const double* __restrict__ mu = pr.mean + (size_t)pr.nb * c;
+  double d[NB];
+  for (int q = 0; q < nb; ++q) d[q] = (q < 6 ? pr.cams[6 * (size_t)c + q] : pr.intr[3 * (size_t)c + (q - 6)]) - mu[q];
+  for (int i = 0; i < nb; ++i)
+    for (int j = i; j < nb; ++j) {
+      const double l = L[UT(pr.nb, i, j)];
+      H[UT(NB, i, j)] += l;
+      b[i] += l * d[j];
+      if (j > i) b[j] += l * d[i];
+    }
+}
+
 // Combine the NPART partial sums of k_camrow_linearize (fixed order), apply M:
 //   Hcc[c] (NH) = Jc^T w Jc,  bc[c] (NB) = Jc^T w r  (zero for the fixed camera; zero rows / columns for held parameters).
 // a[NH + NB] = the camera's pre-M sums (NH of Jc^T w Jc, upper triangle; NB of Jc^T w r), M from its state
 template <int NB>
+// pr (nullable) / c: the camera's prior is added behind M and ahead of the held zeroing
 __device__ inline void lin_finalize_sums(const double* __restrict__ a, const double* __restrict__ M, bool fixed,
-                                         double* __restrict__ H, double* __restrict__ b, unsigned held = 0u) {
+                                         double* __restrict__ H, double* __restrict__ b, unsigned held = 0u,
+                                         const CamPriors* pr = nullptr, int c = 0) {
   constexpr int NH = NB * (NB + 1) / 2;
   if (fixed) {
     for (int q = 0; q < NH; ++q) H[q] = 0.0;
@@ -419,6 +442,7 @@ __device__ inline void lin_finalize_sums(const double* __restrict__ a, const dou
   b[1] = M[1] * a[NH] + M[4] * a[NH + 1] + M[7] * a[NH + 2];
   b[2] = M[2] * a[NH] + M[5] * a[NH + 1] + M[8] * a[NH + 2];
   for (int q = 3; q < NB; ++q) b[q] = a[NH + q];
+  if (pr && pr->info) cam_prior_add<NB>(*pr, c, H, b);
   if (held) {
     for (int i = 0; i < NB; ++i) {
       if ((held >> i) & 1u) b[i] = 0.0;
@@ -429,7 +453,8 @@ __device__ inline void lin_finalize_sums(const double* __restrict__ a, const dou
 }
 template <int NB>
 __device__ inline void lin_finalize_camera(const double* __restrict__ partL, int nparts, const double* __restrict__ cam, int n_cams,
-                                           int c, int fixed_cam, double* __restrict__ H, double* __restrict__ b, unsigned held) {
+                                           int c, int fixed_cam, double* __restrict__ H, double* __restrict__ b, unsigned held,
+                                           const CamPriors& pr) {
   constexpr int NL = NB * (NB + 1) / 2 + NB;
   double a[NL];
   for (int q = 0; q < NL; ++q) a[q] = 0.0;
@@ -439,17 +464,17 @@ __device__ inline void lin_finalize_camera(const double* __restrict__ partL, int
       for (int q = 0; q < NL; ++q) a[q] += src[q];
     }
   }
-  lin_finalize_sums<NB>(a, cam + 12, c == fixed_cam, H, b, held);
+  lin_finalize_sums<NB>(a, cam + 12, c == fixed_cam, H, b, held, &pr, c);
 }
 // stand-alone form (multi-rank jobs all-reduce Hcc|bc between this and k_pcg_setup; test hook)
 template <int NB>
 __global__ void __launch_bounds__(VEC_BLOCK)
 k_lin_finalize(const double* __restrict__ partL, int nparts, const double* __restrict__ cs, int n_cams, int fixed_cam,
-               double* __restrict__ Hcc, double* __restrict__ bc, const unsigned short* __restrict__ cam_held) {
+               double* __restrict__ Hcc, double* __restrict__ bc, const unsigned short* __restrict__ cam_held, CamPriors pr) {
   const int c = vec_camera(n_cams);
   if (c >= n_cams) return;
   lin_finalize_camera<NB>(partL, nparts, cs + CS * c, n_cams, c, fixed_cam, Hcc + (NB * (NB + 1) / 2) * (size_t)c, bc + NB * (size_t)c,
-                          cam_held_bits(cam_held, c));
+                          cam_held_bits(cam_held, c), pr);
 }
 
 // K4b: camera pass of the Schur product, pre-M:  part6[(k*Nc + c)*6 + ..] = sum Jc^T w (Jp y_p)
@@ -1138,6 +1163,86 @@ k_held_points(const unsigned char* __restrict__ pt_held, int n_pts, double* __re
   if (threadIdx.x == 0) partG[blockIdx.x] = nanmax(nanmax(smg[0], smg[1]), nanmax(smg[2], smg[3]));
 }
 
+// Point priors (ba_set_priors) after a point half of the linearisation, which knows nothing of them (the shape of
+// k_held_points, and ahead of it where both apply): Hpp += L_p, bp += L_p (X_p - mu_p), then the damped inverse, y0 and the
+// point table's y slot redone at the damping the point half used (lam_dev != null: the device word a speculated pass read
+// it from), and the gtol maxima redone.  info / mean in point-slot order; a zero block leaves its point untouched.
+// Launched only while point priors are set.
+__global__ void __launch_bounds__(256)
+k_prior_points(const double* __restrict__ info, const double* __restrict__ mean, int n_pts, double lambda_arg,
+               const double* __restrict__ lam_dev, double* __restrict__ Hpp, double* __restrict__ bp, double* __restrict__ Hppinv,
+               double* __restrict__ y0, double* __restrict__ ptab, double* __restrict__ partG) {
+  __shared__ double smg[4];
+  const double lambda = lam_dev ? lam_dev[0] : lambda_arg;
+  double gm = 0.0;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < n_pts; p += gridDim.x * 256) {
+    double L[6];
+    bool any = false;
+    for (int q = 0; q < 6; ++q) { L[q] = info[6 * (size_t)p + q]; any = any || L[q] != 0.0; }
+    if (any) {
+      double d[3], Ld[3], h[6], b[3], inv[6], y[3];
+      for (int q = 0; q < 3; ++q) d[q] = ptab[PT * (size_t)p + q] - mean[3 * (size_t)p + q];
+      sym3_mul(L, d, Ld);
+      for (int q = 0; q < 6; ++q) { h[q] = Hpp[6 * (size_t)p + q] + L[q]; Hpp[6 * (size_t)p + q] = h[q]; }
+      for (int q = 0; q < 3; ++q) { b[q] = bp[3 * (size_t)p + q] + Ld[q]; bp[3 * (size_t)p + q] = b[q]; }
+      h[0] += lambda * fmax(h[0], DIAG_FLOOR);
+      h[3] += lambda * fmax(h[3], DIAG_FLOOR);
+      h[5] += lambda * fmax(h[5], DIAG_FLOOR);
+      sym3_inverse(h, inv);
+      sym3_mul(inv, b, y);
+      for (int q = 0; q < 6; ++q) Hppinv[6 * (size_t)p + q] = inv[q];
+      for (int q = 0; q < 3; ++q) { y0[3 * (size_t)p + q] = y[q]; ptab[PT * (size_t)p + 4 + q] = y[q]; }
+    }
+    for (int q = 0; q < 3; ++q) gm = nanmax(gm, fabs(bp[3 * (size_t)p + q]));
+  }
+  gm = wave_nanmax(gm);
+  if ((threadIdx.x & 63) == 0) smg[threadIdx.x >> 6] = gm;
+  __syncthreads();
+  if (threadIdx.x == 0) partG[blockIdx.x] = nanmax(nanmax(smg[0], smg[1]), nanmax(smg[2], smg[3]));
+}
+
+// The prior terms of the objective at one parameter set, as PRIOR_ROWS extra rows of the residual partials:
+// rows[b] = {0, sum (x - mu)^T L (x - mu)} over workgroup b's cameras and points (grid-stride, fixed order), so the scalar
+// fold that adds nR + PRIOR_ROWS rows finds the total cost in its rho sum and the reprojection sse unchanged.
+// pr.info == null: no camera part (also rank > 0 of a multi-rank job: the camera sum counts once); pt_info == null: no point part.
+constexpr int PRIOR_ROWS = 32;
+__global__ void __launch_bounds__(256)
+k_prior_cost(CamPriors pr, int n_cams, const double* __restrict__ pt_info, const double* __restrict__ pt_mean,
+             const double* __restrict__ ptab, int n_pts, double* __restrict__ rows) {
+  __shared__ double sm[4];
+  double acc = 0.0;
+  if (pr.info) {
+    const int nb = pr.nb, nh = nb * (nb + 1) / 2;
+    for (int c = blockIdx.x * 256 + threadIdx.x; c < n_cams; c += gridDim.x * 256) {
+      const double* __restrict__ L = pr.info + (size_t)nh * c;
+      double d[9];
+      for (int q = 0; q < nb; ++q) d[q] = (q < 6 ? pr.cams[6 * (size_t)c + q] : pr.intr[3 * (size_t)c + (q - 6)]) - pr.mean[(size_t)nb * c + q];
+      double s = 0.0;
+      for (int i = 0; i < nb; ++i)
+        for (int j = i; j < nb; ++j) s += (j > i ? 2.0 : 1.0) * L[UT(nb, i, j)] * d[i] * d[j];
+      acc += s;
+    }
+  }
+  if (pt_info) {
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < n_pts; p += gridDim.x * 256) {
+      double d[3], Ld[3];
+      for (int q = 0; q < 3; ++q) d[q] = ptab[PT * (size_t)p + q] - pt_mean[3 * (size_t)p + q];
+      sym3_mul(pt_info + 6 * (size_t)p, d, Ld);
+      acc += d[0] * Ld[0] + d[1] * Ld[1] + d[2] * Ld[2];
+    }
+  }
+  acc = wave_total_dpp(acc);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) { rows[2 * blockIdx.x] = 0.0; rows[2 * blockIdx.x + 1] = (sm[0] + sm[1]) + (sm[2] + sm[3]); }
+}
+// rows in the caller's point order -> point slots (ba_set_priors): out[slot[p]][0..W) = in[p][0..W)
+__global__ void k_scatter_rows(const double* __restrict__ in, const int* __restrict__ slot, int n_pts, int width, double* __restrict__ out) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_pts) return;
+  for (int q = 0; q < width; ++q) out[(size_t)slot[p] * width + q] = in[(size_t)p * width + q];
+}
+
 // K4a / K6: point pass of the Schur product.  u = sum_o Jp^T w (Jc v_c) with
 //   Jc v = P (X x vt_r) - dpi vt_t,  vt = (M v_r, v_t) = camA[c][12..17].
 // MODE 0 (PCG): y[p] = Hppinv u into the point table, partA[block] = sum u.y; early exit when done.
@@ -1546,7 +1651,7 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
             double* __restrict__ gvec, double* __restrict__ x, double* __restrict__ r, double* __restrict__ p,
             double* __restrict__ s, double* __restrict__ z, double* __restrict__ vtil,
             double* __restrict__ partV, PcgState* __restrict__ st, double* __restrict__ partGc,
-            double* __restrict__ vx, const unsigned short* __restrict__ cam_held) {
+            double* __restrict__ vx, const unsigned short* __restrict__ cam_held, CamPriors pr) {
   constexpr int NB = CM::NB, NH = CM::NH, NL = CM::NL, VC = CM::VC;
   // LDS image of the workgroup's VC cameras.  Inputs: partition-folded sums (a: NL of the linearisation when
   // FINALIZE, e: NH Schur-Jacobi, w6: NB of W y0), Hcc | bc (when not FINALIZE), cs.  Outputs staged for a
@@ -1619,7 +1724,7 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
     const double* M = l_cs + CS * t + 12;
     const bool fixed = c == fixed_cam;
     const unsigned held = cam_held_bits(cam_held, c);
-    if (FINALIZE) lin_finalize_sums<NB>(l_a + NL * t, M, fixed, l_hcc + NH * t, l_bc + NB * t, held);
+    if (FINALIZE) lin_finalize_sums<NB>(l_a + NL * t, M, fixed, l_hcc + NH * t, l_bc + NB * t, held, &pr, c);
     double h[NH], m[NH], inv[NH];
     for (int q = 0; q < NH; ++q) h[q] = l_hcc[NH * t + q];
     if (fixed) {

@@ -94,6 +94,8 @@ SYMBOLS = {
     "ba_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ba_set_problem": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, _IP, _IP, _DP, _DP, C.c_int32]),
     "ba_set_held": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)]),
+    "ba_set_priors": (C.c_int, [C.c_void_p, C.c_int32, _DP, _DP, _DP, _DP]),
+    "ba_prior_cost": (C.c_int, [C.c_void_p, _DP, _DP, _DP]),
     "ba_set_params": (C.c_int, [C.c_void_p, _DP, _DP]),
     "ba_get_params": (C.c_int, [C.c_void_p, _DP, _DP]),
     "ba_get_rotations": (C.c_int, [C.c_void_p, _DP]),
@@ -119,7 +121,8 @@ SYMBOLS = {
 }
 # enum ba_stat (include/ba_hip.h)
 STATS = {"window_mw_launches": 0, "window_lm_launches": 1, "window_fallbacks": 2, "precond_builds": 3, "precond_reuses": 4, "banded": 5,
-         "cap_floor_raises": 6, "ipc_exchanges": 7, "pixels_f32": 8, "held_params": 9}
+         "cap_floor_raises": 6, "ipc_exchanges": 7, "pixels_f32": 8, "held_params": 9,
+         "prior_blocks": 10}
 
 
 def held_camera_mask(cams, n_cams, nb=6):
@@ -256,8 +259,33 @@ class Solver:
         self._lin = None                       # (loss, f_scale) of the last linearize(): what schur_rhs / schur_apply use
         if prob.cam_held is not None or prob.pt_held is not None:
             self.set_held(prob.cam_held, prob.pt_held)
+        if prob.cam_prior is not None or prob.pt_prior is not None:
+            self.set_priors(prob.cam_prior, prob.pt_prior)
         if with_params:
             self.set_params(prob.cams, prob.pts)
+
+    def set_priors(self, cams=None, points=None):
+        """ba_set_priors: Gaussian priors 0.5 (x - mean)^T info (x - mean) added to the objective.  cams: (mean (Nc, nb),
+        info (Nc, nb, nb)) or a dict camera -> (mean (nb,), info (nb, nb)), nb = 6 (rvec | t) or 9 (| f k1 k2, BAL solves);
+        points: (mean (Np, 3), info (Np, 3, 3)) or a dict point -> (mean, info).  A zero block is no prior.  set_priors()
+        clears both.  The priors stay with the handle across set_params and solves; set_problem clears them.  Bad specs
+        raise ValueError (priors.pack_priors)."""
+        from .priors import camera_prior_nb, pack_priors
+        nb = camera_prior_nb(cams) or 6
+        if nb not in (6, 9):
+            raise ValueError(f"camera priors are written in 6 (rvec | t) or 9 (rvec | t | f k1 k2) coordinates, not {nb}")
+        cp = pack_priors(cams, self.n_cams, nb, "camera")
+        pp = pack_priors(points, self.n_pts, 3, "point")
+        _check(self._lib.ba_set_priors(self._h, nb, None if cp is None else _dp(cp[0]), None if cp is None else _dp(cp[1]),
+                                       None if pp is None else _dp(pp[0]), None if pp is None else _dp(pp[1])))
+
+    def prior_cost(self, intr=None):
+        """ba_prior_cost: (camera sum, point sum) of the prior terms at the current parameters; intr (Nc, 3) for nb = 9 priors."""
+        if intr is not None:
+            intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
+        cc, pc = C.c_double(0), C.c_double(0)
+        _check(self._lib.ba_prior_cost(self._h, _dp(intr), C.byref(cc), C.byref(pc)))
+        return cc.value, pc.value
 
     def set_held(self, cams=None, points=None):
         """ba_set_held: parameters the solves keep constant.  cams: bool (Nc,) (whole cameras), bool (Nc, 6 | 9) (per block
@@ -335,7 +363,8 @@ class Solver:
         """ba_covariance: marginal covariances of the cameras and points at the current parameters, held parameters (fixed_cam,
         set_held) conditioned on.  intr None: pinhole (nb 6), else (Nc, 3) (f, k1, k2) of the BAL camera (nb 9).  Returns
         dict(cams (Nc, nb, nb), points (Np, 3, 3), full (N, N) with N = nb Nc, or None).  Held entries are 0, points seen
-        from one camera only NaN; an undetermined gauge or point raises BAHipError (BA_ERR_NUMERIC)."""
+        from one camera only NaN (unless they carry a prior); an undetermined gauge or point raises BAHipError
+        (BA_ERR_NUMERIC).  Priors (set_priors) are part of the system: Sigma = (H + L)^-1 over the free parameters."""
         nb = 6 if intr is None else 9
         nh = nb * (nb + 1) // 2
         ip = None
@@ -432,11 +461,14 @@ class Solver:
             setattr(o, k, v)
         return o
 
-    def solve_bal(self, bal, fixed_cam=-1, hold_intrinsics=False, held_cameras=None, held_points=None, **kw):
+    def solve_bal(self, bal, fixed_cam=-1, hold_intrinsics=False, held_cameras=None, held_points=None, camera_priors=None,
+                  point_priors=None, **kw):
         """ba_solve_bal on a bal.BALProblem (9-parameter cameras, f / k1 / k2 adjusted with the pose): returns
         (summary dict, cams (Nc,9), pts (Np,3)).  hold_intrinsics: keep every camera's f, k1, k2; held_cameras /
-        held_points: as set_held (added to hold_intrinsics).  kw as for solve()."""
+        held_points: as set_held (added to hold_intrinsics); camera_priors / point_priors: as set_priors.  kw as for solve()."""
         intr = self._set_bal(bal, fixed_cam)
+        if camera_priors is not None or point_priors is not None:
+            self.set_priors(camera_priors, point_priors)
         cm = held_camera_mask(held_cameras, self.n_cams, 9)
         if hold_intrinsics:
             cm = (np.zeros(self.n_cams, np.uint16) if cm is None else cm) | np.uint16(0x1C0)

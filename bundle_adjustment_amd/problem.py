@@ -33,6 +33,8 @@ class BAProblem:
     fixed_cam: int = 0      # index into cams, -1 = none fixed
     cam_held: np.ndarray | None = None   # optional held camera parameters (hip_backend.held_camera_mask forms; ba_set_held)
     pt_held: np.ndarray | None = None    # optional (Np,) bool: held points
+    cam_prior: object = None             # optional camera priors (hip_backend.Solver.set_priors forms; ba_set_priors)
+    pt_prior: object = None              # optional point priors: (mean (Np, 3), info (Np, 3, 3)) or a dict point -> (mean, info)
 
     @property
     def n_cams(self):
@@ -64,7 +66,29 @@ class BAProblem:
             from .hip_backend import held_camera_mask, held_point_mask
             held_camera_mask(self.cam_held, nc)
             held_point_mask(self.pt_held, npt)
+        if self.cam_prior is not None or self.pt_prior is not None:
+            from .priors import camera_prior_nb, pack_priors
+            pack_priors(self.cam_prior, nc, camera_prior_nb(self.cam_prior) or 6, "camera")
+            pack_priors(self.pt_prior, npt, 3, "point")
         return self
+
+
+def _shard_point_prior(spec, p_begin, p_end):
+    """The point priors of points [p_begin, p_end), re-indexed from 0 (the shard that owns a point carries its prior)."""
+    if spec is None:
+        return None
+    if isinstance(spec, dict):
+        return {int(i) - p_begin: (np.array(m, copy=True), np.array(L, copy=True)) for i, (m, L) in spec.items() if p_begin <= i < p_end}
+    m, L = spec
+    return np.array(np.asarray(m)[p_begin:p_end], copy=True), np.array(np.asarray(L)[p_begin:p_end], copy=True)
+
+
+def _copy_prior(spec):
+    if spec is None:
+        return None
+    if isinstance(spec, dict):
+        return {i: (np.array(m, copy=True), np.array(L, copy=True)) for i, (m, L) in spec.items()}
+    return tuple(np.array(a, copy=True) for a in spec)
 
 
 def gather_window(gmap, local_kf_ids):
@@ -216,13 +240,15 @@ def shard_by_landmark(problem: BAProblem, n_shards: int):
 def extract_shard(problem: BAProblem, p_begin: int, p_end: int):
     """Sub-problem holding points [p_begin, p_end) (re-indexed from 0), their
     observations in the original relative order, and ALL cameras.  Also returns the
-    positions of those observations in the full list."""
+    positions of those observations in the full list.  Camera priors go to every shard (the library counts them once),
+    point priors to the shard that owns the point."""
     sel = np.nonzero((problem.pt_idx >= p_begin) & (problem.pt_idx < p_end))[0]
     sub = BAProblem(problem.cams.copy(), problem.pts[p_begin:p_end].copy(),
                     problem.cam_idx[sel].copy(), (problem.pt_idx[sel] - p_begin).astype(np.int32),
                     problem.uv[sel].copy(), problem.K4.copy(), problem.fixed_cam,
                     None if problem.cam_held is None else np.array(problem.cam_held, copy=True),
-                    None if problem.pt_held is None else np.array(problem.pt_held[p_begin:p_end], copy=True))
+                    None if problem.pt_held is None else np.array(problem.pt_held[p_begin:p_end], copy=True),
+                    _copy_prior(problem.cam_prior), _shard_point_prior(problem.pt_prior, p_begin, p_end))
     return sub, sel
 
 

@@ -68,7 +68,8 @@ typedef struct ba_options {
   int32_t small_solver;    /* 0 = problems of at most 8 cameras and 6144 observations on one rank (the reference's sliding
                               window, src/pipeline.py:39 window_size 5) are solved by the single-launch window solver
                               (csrc/ba_small.hpp: whole LM loop in one kernel, reduced system formed by fp64 MFMA and
-                              factorised exactly); 1 = always the multi-kernel LM / Schur / PCG path */
+                              factorised exactly); 1 = always the multi-kernel LM / Schur / PCG path.  A problem with priors
+                              (ba_set_priors) always takes the multi-kernel path: the window kernels do not know them */
   double pcg_model_tol;    /* second PCG stopping test, on the quadratic model q(x) = 1/2 x^T S x - g^T x the iteration
                               minimises: stop after iteration i >= pcg_model_min_iters when i (q_{i-1} - q_i) <= pcg_model_tol |q_i|
                               (Nash & Sofer's truncated-Newton test; 0.5 is their value; 0 = off).  On ill-conditioned
@@ -161,7 +162,9 @@ enum ba_stat {
                                        8 bytes per observation and pass less (BA_PIXELS=f64 switches it off) */
   BA_STAT_HELD_PARAMS = 9,          /* held scalar parameters of the current problem (ba_set_held), fixed_cam's whole block included
                                        (6 parameters, or 9 once a camera mask sets a BAL bit); 3 per held point */
-  BA_STAT_COUNT = 10
+  BA_STAT_COUNT = 10,               /* statistics 0 - 9: the set callers of earlier releases size their arrays by */
+  BA_STAT_PRIOR_BLOCKS = 10,        /* cameras + points of the calling rank that carry a non-zero prior block (ba_set_priors) */
+  BA_STAT_END = 11                  /* one past the last statistic ba_get_stat answers */
 };
 
 const char* ba_last_error(void);
@@ -221,6 +224,41 @@ int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64_t n_obs,
  * Multi-rank jobs: cam_held covers ALL cameras and must be the same on every rank (the caller's obligation); pt_held is
  * per shard, in the shard's local point order. */
 int ba_set_held(ba_handle* h, const uint16_t* cam_held, const uint8_t* pt_held);
+/* Gaussian priors: soft knowledge of camera blocks and points (Ceres residual blocks on one parameter block, g2o unary
+ * edges, GTSAM PriorFactor, ground-control points; no reference counterpart).  The objective ba_solve / ba_solve_bal
+ * minimise becomes
+ *   cost(x) = 0.5 sum_i f_scale^2 rho((r_i / f_scale)^2)  +  0.5 sum_c (x_c - mu_c)^T L_c (x_c - mu_c)  +  0.5 sum_p (X_p - mu_p)^T L_p (X_p - mu_p)
+ * with x_c the caller's additive coordinates rvec | t (| f k1 k2), the ones ba_linearize, ba_set_held and ba_covariance
+ * speak.  L is an information matrix (inverse covariance): symmetric positive SEMIdefinite, so a prior on t alone is a block
+ * with zeros elsewhere.  A block of zeros is "no prior"; its mean is not read.  The robust loss is never applied to the
+ * prior terms.
+ *   nb        6 (rvec | t) or 9 (rvec | t | f k1 k2: BAL solves only)
+ *   cam_mean  double[Nc][nb]             cam_info double[Nc][nb (nb + 1) / 2]  packed upper triangles, Hcc's order
+ *   pt_mean   double[Np][3]              pt_info  double[Np][6]  Hpp's order; both in the caller's point order
+ * Either pair may be NULL.  The priors belong to the handle like the held masks: they survive ba_set_params and repeated
+ * solves; ba_set_problem clears them, and so does ba_set_priors with both pairs NULL or with every block zero.
+ * Refused with BA_ERR_INVALID, naming the first offending camera or point: a non-finite entry in a block, or in the mean of a
+ * non-zero block; a block that is not positive semidefinite (smallest eigenvalue below -1e-12 times the largest); nb other
+ * than 6 / 9.  nb = 9 priors are refused by the pinhole solve / linearisation that meets them; nb = 6 priors on a BAL solve
+ * are fine (the intrinsics get none).
+ * With priors set: ba_linearize*, ba_schur_system and ba_covariance report the system the solve uses -- Hcc += L_c,
+ * bc += L_c (x_c - mu_c), Hpp += L_p, bp += L_p (X_p - mu_p), ahead of the held zeroing and of the damping (the Marquardt
+ * diagonal, the Schur-Jacobi blocks and the gain ratio's model all see H + L); a held parameter's prior only adds its
+ * constant to the cost, the fixed camera's block stays zero.  ba_covariance: Sigma = (H_free + L_free)^-1 -- a prior can
+ * fix the gauge that the observations leave free; a free point seen from one camera only is an ordinary point once it
+ * carries a non-zero prior.  ba_summary.initial_cost / final_cost, the trace's cost / cost_trial and the ftol test are the
+ * TOTAL objective; initial_sse / final_sse / sse_trial and everything ba_residuals* returns stay reprojection-only.  gtol
+ * sees the total gradient; xtol is untouched.  A window-sized problem with priors takes the multi-kernel path (see
+ * ba_options.small_solver): the window kernels do not know priors.
+ * Multi-rank jobs: the camera arrays cover ALL cameras and must be the same on every rank (counted once); the point arrays
+ * are per shard, in the shard's local point order.
+ * Not offered: information that couples two cameras or a camera and a point (a dense marginalisation prior), and a prior on
+ * the camera CENTRE -R^T t (a nonlinear factor of its own, not a quadratic in these coordinates). */
+int ba_set_priors(ba_handle* h, int32_t nb, const double* cam_mean, const double* cam_info, const double* pt_mean,
+                  const double* pt_info);
+/* The two prior sums of the objective at the current parameters (intr: (f, k1, k2)[Nc] for nb = 9 priors, else NULL; either
+ * output may be NULL).  Multi-rank: the camera sum as on one rank, the point sum of the calling rank's shard. */
+int ba_prior_cost(ba_handle* h, const double* intr, double* cam_cost, double* pt_cost);
 int ba_set_params(ba_handle* h, const double* cams, const double* pts);
 int ba_get_params(ba_handle* h, double* cams, double* pts);
 /* 3x3 rotation matrices of the current cameras, double[Nc][9] row-major: the
