@@ -138,9 +138,27 @@ def from_pinhole(prob: BAProblem) -> BALProblem:
     return BALProblem(cams, prob.pts.copy(), prob.cam_idx.copy(), prob.pt_idx.copy(), uv).validate()
 
 
-def _bal_priors(prob, camera_priors, intrinsics_sigma):
+def _shared_start(prob, labels, shared_init):
+    """prob with every group's (f, k1, k2) set to ONE value: the members' median (shared_init 'median'), or the members'
+    own when they already agree ('given': raises ValueError when they do not)."""
+    if shared_init not in ("median", "given"):
+        raise ValueError(f"shared_init must be 'median' or 'given', not {shared_init!r}")
+    cams = prob.cams.copy()
+    for g in np.unique(labels[labels >= 0]):
+        m = np.nonzero(labels == g)[0]
+        if shared_init == "given":
+            if (cams[m, 6:9] != cams[m[0], 6:9]).any():
+                bad = m[(cams[m, 6:9] != cams[m[0], 6:9]).any(axis=1)][0]
+                raise ValueError(f"shared_init='given': camera {int(bad)} of group {int(g)} does not start with the f, k1, k2 of camera {int(m[0])}")
+        else:
+            cams[m, 6:9] = np.median(cams[m, 6:9], axis=0)
+    return BALProblem(cams, prob.pts, prob.cam_idx, prob.pt_idx, prob.uv)
+
+
+def _bal_priors(prob, camera_priors, intrinsics_sigma, labels=None):
     """camera_priors plus the calibration regulariser: a prior on f, k1, k2 of every camera at their input values with
-    standard deviations intrinsics_sigma = (s_f, s_k1, s_k2), added to the 9 x 9 blocks of camera_priors."""
+    standard deviations intrinsics_sigma = (s_f, s_k1, s_k2), added to the 9 x 9 blocks of camera_priors.  labels (shared
+    intrinsics): a group carries the regulariser once, on its leader (the member with the lowest index)."""
     if intrinsics_sigma is None:
         return camera_priors
     from .priors import camera_prior_nb, info_from_sigma, pack_priors
@@ -160,35 +178,57 @@ def _bal_priors(prob, camera_priors, intrinsics_sigma):
         info[:, :nb, :nb] = full
     mean[:, 6:] = prob.cams[:, 6:9]
     info[:, 6:, 6:] = info_from_sigma(np.asarray(intrinsics_sigma, dtype=np.float64).reshape(3))
+    if labels is not None:
+        for g in np.unique(labels[labels >= 0]):
+            m = np.nonzero(labels == g)[0]
+            info[m[1:], 6:, 6:] = 0.0
     return mean, info
 
 
 def solve(prob: BALProblem, device=0, fixed_cam=-1, hold_intrinsics=False, held_cameras=None, held_points=None,
-          camera_priors=None, point_priors=None, intrinsics_sigma=None, **options):
+          camera_priors=None, point_priors=None, intrinsics_sigma=None, shared_intrinsics=None, shared_init="median",
+          **options):
     """Adjust a BAL problem on the GPU (``ba_solve_bal``: poses, points AND f / k1 / k2 per camera).  Returns
     ``(BALProblem with the adjusted parameters, summary dict)``; options as ``hip_backend.Solver.solve``.
     hold_intrinsics: keep every camera's f, k1, k2 (calibrated cameras); held_cameras / held_points: parameters kept
     constant, in the forms of ``hip_backend.Solver.set_held`` (a (Nc, 9) bool array names single BAL parameters).
     camera_priors / point_priors: Gaussian priors in the forms of ``hip_backend.Solver.set_priors`` (camera blocks of 6 or
     9 coordinates); intrinsics_sigma = (s_f, s_k1, s_k2): the calibration regulariser, a prior on f, k1, k2 of every
-    camera at their input values -- the soft form of hold_intrinsics.  With priors ``final_cost`` is the total objective."""
+    camera at their input values -- the soft form of hold_intrinsics.  With priors ``final_cost`` is the total objective.
+    shared_intrinsics: cameras that share ONE f, k1, k2 (``hip_backend.camera_groups`` forms: True = all cameras, a label
+    array, a list of index lists) -- self-calibration of a few physical cameras.  shared_init: 'median' starts every group
+    from its members' median, 'given' requires equal members.  A grouped ``fixed_cam`` has its POSE held (the group's
+    intrinsics stay free); intrinsics_sigma then acts once per group.  The members come back bit-equal."""
     from . import hip_backend
+    labels = hip_backend.camera_groups(shared_intrinsics, prob.n_cams)
+    if labels is not None:
+        prob = _shared_start(prob, labels, shared_init)
+        if fixed_cam >= 0 and labels[fixed_cam] >= 0 and np.count_nonzero(labels == labels[fixed_cam]) > 1:
+            cm = hip_backend.held_camera_mask(held_cameras, prob.n_cams, 9)
+            cm = np.zeros(prob.n_cams, np.uint16) if cm is None else cm.copy()
+            cm[fixed_cam] |= np.uint16(0x3F)
+            held_cameras, fixed_cam = cm, -1
     with hip_backend.Solver(device) as s:
         summary, cams, pts = s.solve_bal(prob, fixed_cam=fixed_cam, hold_intrinsics=hold_intrinsics,
                                          held_cameras=held_cameras, held_points=held_points,
-                                         camera_priors=_bal_priors(prob, camera_priors, intrinsics_sigma),
-                                         point_priors=point_priors, **options)
+                                         camera_priors=_bal_priors(prob, camera_priors, intrinsics_sigma, labels),
+                                         point_priors=point_priors, shared_intrinsics=labels, **options)
     return BALProblem(cams, pts, prob.cam_idx.copy(), prob.pt_idx.copy(), prob.uv.copy()), summary
 
 
 def covariance(prob: BALProblem, device=0, fixed_cam=-1, hold_intrinsics=False, held_cameras=None, held_points=None,
-               loss="linear", f_scale=1.0, full=False, rcond=0.0, camera_priors=None, point_priors=None, intrinsics_sigma=None):
+               loss="linear", f_scale=1.0, full=False, rcond=0.0, camera_priors=None, point_priors=None, intrinsics_sigma=None,
+               shared_intrinsics=None):
     """Marginal covariances of a BAL problem at ``prob``'s parameters (``ba_covariance``; normally the problem ``solve``
     returned).  The held-parameter forms are those of ``solve``; a BAL problem with nothing held has a free 7-dof gauge
     and is refused (hold e.g. ``fixed_cam`` and one translation coordinate of another camera) unless priors
     (camera_priors / point_priors / intrinsics_sigma, as in ``solve``) fix it: Sigma = (H + L)^-1.  Returns
-    ``dict(cams (Nc, 9, 9), points (Np, 3, 3), full (9 Nc, 9 Nc) or None)``, see ``hip_backend.Solver.covariance``."""
+    ``dict(cams (Nc, 9, 9), points (Np, 3, 3), full (9 Nc, 9 Nc) or None)``, see ``hip_backend.Solver.covariance``.
+    Covariances of shared intrinsics are not offered: shared_intrinsics that name a group raise ValueError."""
     from . import hip_backend
+    labels = hip_backend.camera_groups(shared_intrinsics, prob.n_cams)
+    if labels is not None and (np.bincount(labels[labels >= 0]) > 1).any():
+        raise ValueError("bal.covariance: covariances of shared intrinsics are not offered")
     with hip_backend.Solver(device) as s:
         intr = s._set_bal(prob, fixed_cam)
         cm = hip_backend.held_camera_mask(held_cameras, s.n_cams, 9)

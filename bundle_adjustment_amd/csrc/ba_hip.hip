@@ -212,6 +212,16 @@ struct ba_handle {
   std::vector<unsigned char> h_pt_held;
   double held_x2 = 0.0;
   DBuf<double> held_red;           // multi-rank: held_x2 summed over the shards (one all-reduce per solve)
+  // shared intrinsics (ba_set_shared_intrinsics): groups of >= 2 cameras, numbered by their lowest member.  h_cam_gl[c] = -1
+  // (own intrinsics) or 2 * group + (1: c is the group's leader, its lowest member); member lists CSR by group, members
+  // ascending.  shared_on: a BAL solve is running with them (the kernels get null pointers otherwise).
+  // The per-iteration fold cuts a group into chunks of SHARED_BLOCK members: h_chunk_rng[2 k], [2 k + 1] = chunk k's range in
+  // h_grp_mem, h_grp_chunk[g] .. [g + 1] = the chunks of group g.
+  std::vector<int> h_cam_gl, h_grp_off, h_grp_mem, h_chunk_rng, h_grp_chunk;
+  DBuf<int> cam_gl, grp_off, grp_mem, chunk_rng, grp_chunk;
+  DBuf<double> grp_rec, grp_w;     // k_shared_sum's record per group, k_shared_fold's sums per chunk
+  int n_shared = 0, n_shared_chunks = 0;
+  bool shared_on = false;
   // Gaussian priors (ba_set_priors): camera blocks in camera order, point blocks in point-slot order; the kernels get null
   // pointers while none are set.  Means of zero blocks are uploaded as 0 (they are never read by the caller's rule, and the
   // kernels then need no flag per block).  fold_prior_rows: PRIOR_ROWS while a solve folds the prior rows behind partR.
@@ -1415,6 +1425,11 @@ static void clear_priors(ba_handle* h) {
   h->prior_nb = 0;
   h->prior_blocks = 0;
 }
+static void clear_shared(ba_handle* h) {
+  h->n_shared = h->n_shared_chunks = 0;
+  h->shared_on = false;
+  h->h_cam_gl.clear(); h->h_grp_off.clear(); h->h_grp_mem.clear(); h->h_chunk_rng.clear(); h->h_grp_chunk.clear();
+}
 static void clear_held(ba_handle* h) {
   h->any_cam_held = h->any_pt_held = false;
   h->cam_held_or = 0;
@@ -1441,6 +1456,7 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
   if (fixed_cam < -1 || fixed_cam >= n_cams) return fail(BA_ERR_INVALID, "fixed_cam %d out of range", fixed_cam);
   clear_held(h);                     // a new problem starts with nothing held beyond its fixed camera
   clear_priors(h);                   // ... and without priors
+  clear_shared(h);                   // ... and every camera with its own intrinsics
   {   // index ranges, before anything is touched (a rejected call keeps the previous problem): branch-free sweep first
     int ok = 1;
     for (int64_t i = 0; i < n_obs; ++i)
@@ -1606,6 +1622,71 @@ extern "C" int ba_set_held(ba_handle* h, const uint16_t* cam_held, const uint8_t
   return BA_OK;
 }
 
+// Shared intrinsics: labels -> groups of two or more members (a group of one is an ungrouped camera), numbered by their
+// lowest member; the member lists are built here once and uploaded.
+extern "C" int ba_set_shared_intrinsics(ba_handle* h, const int32_t* cam_group) {
+  if (!h) return fail(BA_ERR_INVALID, "null handle");
+  if (!h->have_problem) return fail(BA_ERR_STATE, "ba_set_problem has not been called");
+  const int Nc = h->Nc;
+  if (cam_group)
+    for (int c = 0; c < Nc; ++c)
+      if (cam_group[c] < -1) return fail(BA_ERR_INVALID, "ba_set_shared_intrinsics: camera %d: label %d (labels are -1 or non-negative)", c, cam_group[c]);
+  clear_shared(h);
+  h->linearized = false;
+  if (!cam_group) return BA_OK;
+  std::vector<std::pair<int32_t, int>> by_label;          // (label, camera), sorted: members ascending within a label
+  for (int c = 0; c < Nc; ++c) if (cam_group[c] >= 0) by_label.emplace_back(cam_group[c], c);
+  std::sort(by_label.begin(), by_label.end());
+  std::vector<std::pair<int, int>> runs;                  // (leader, first index in by_label) of labels with >= 2 members
+  for (size_t i = 0; i < by_label.size();) {
+    size_t j = i;
+    while (j < by_label.size() && by_label[j].first == by_label[i].first) ++j;
+    if (j - i >= 2) runs.emplace_back(by_label[i].second, (int)i);
+    i = j;
+  }
+  if (runs.empty()) return BA_OK;
+  std::sort(runs.begin(), runs.end());                    // groups in the order of their leaders
+  h->h_cam_gl.assign((size_t)Nc, -1);
+  h->h_grp_off.assign(1, 0);
+  for (size_t g = 0; g < runs.size(); ++g) {
+    const int32_t label = by_label[(size_t)runs[g].second].first;
+    for (size_t i = (size_t)runs[g].second; i < by_label.size() && by_label[i].first == label; ++i) {
+      const int c = by_label[i].second;
+      h->h_cam_gl[(size_t)c] = 2 * (int)g + (c == runs[g].first ? 1 : 0);
+      h->h_grp_mem.push_back(c);
+    }
+    h->h_grp_off.push_back((int)h->h_grp_mem.size());
+  }
+  const int G = (int)runs.size();
+  h->h_grp_chunk.assign(1, 0);
+  for (int g = 0; g < G; ++g) {
+    for (int b = h->h_grp_off[g]; b < h->h_grp_off[g + 1]; b += SHARED_BLOCK) {
+      h->h_chunk_rng.push_back(b);
+      h->h_chunk_rng.push_back(std::min(b + SHARED_BLOCK, h->h_grp_off[g + 1]));
+    }
+    h->h_grp_chunk.push_back((int)(h->h_chunk_rng.size() / 2));
+  }
+  const int n_chunks = h->h_grp_chunk.back();
+  if (set_device(h)) { clear_shared(h); return BA_ERR_HIP; }
+  auto up = [&](DBuf<int>& d, const std::vector<int>& v) -> hipError_t {
+    hipError_t e = d.alloc(v.size());
+    return e != hipSuccess ? e : hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, h->stream);
+  };
+  hipError_t e = up(h->cam_gl, h->h_cam_gl);
+  if (e == hipSuccess) e = up(h->grp_off, h->h_grp_off);
+  if (e == hipSuccess) e = up(h->grp_mem, h->h_grp_mem);
+  if (e == hipSuccess) e = up(h->chunk_rng, h->h_chunk_rng);
+  if (e == hipSuccess) e = up(h->grp_chunk, h->h_grp_chunk);
+  if (e == hipSuccess) e = h->grp_rec.alloc((size_t)SHARED_REC * G);
+  if (e == hipSuccess) e = h->grp_w.alloc(3 * (size_t)n_chunks);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) { clear_shared(h); return fail(BA_ERR_HIP, "ba_set_shared_intrinsics: %s", hipGetErrorString(e)); }
+  h->n_shared = G;
+  h->n_shared_chunks = n_chunks;
+  return BA_OK;
+}
+static const int* cam_gl_ptr(const ba_handle* h) { return h->shared_on ? h->cam_gl.p : nullptr; }
+
 // ------------------------------------------------------------------------------------------------------ priors
 // eigenvalues of a packed symmetric n x n block (n <= 9) by cyclic Jacobi rotations: smallest and largest
 static void sym_eig_range(const double* packed, int n, double* lo, double* hi) {
@@ -1716,6 +1797,7 @@ static void launch_prior_cost(ba_handle* h, int which) {
             h->any_pt_prior ? (const double*)h->pt_info.p : (const double*)nullptr, (const double*)h->pt_mean.p, (const double*)h->ptab[which].p,
             h->Np, h->partR.p + 2 * (size_t)NPART * h->Nc);
 }
+static const char* kSharedNeedsBal = "shared intrinsics (ba_set_shared_intrinsics) need the BAL camera model: clear them with a NULL argument";
 static const char* kPriorNeedsBal = "camera priors with nb = 9 (f, k1, k2) need the BAL camera model";
 extern "C" int ba_prior_cost(ba_handle* h, const double* intr, double* cam_cost, double* pt_cost) {
   if (!h) return fail(BA_ERR_INVALID, "null handle");
@@ -2116,7 +2198,7 @@ static void launch_pcg_setup(ba_handle* h, double lambda, int precond, bool fina
 #define SU_ARGS partL_of(h, h->lb), h->HccBc.p, bc_ptr(h), sys_p6(h), sys_E(h), nparts_of(h), h->cs[h->cur].p, lambda,           \
                 precond, h->Nc, h->fixed, h->Hccd.p, h->Minv.p, h->gvec.p, h->x.p, h->r.p, h->p.p, h->s.p,     \
                 h->z.p, h->camA[h->cur].p, h->partV.p, h->st.p, h->partGc.p, h->vx.p, \
-                cam_held_ptr(h), cam_priors(h, h->cur, finalize)
+                cam_held_ptr(h), cam_priors(h, h->cur, finalize), cam_gl_ptr(h)
 #define CALL_T(CM)                                                                                               \
   do {                                                                                                           \
     if (finalize) BA_LAUNCH((k_pcg_setup<CM, true>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, SU_ARGS);    \
@@ -2125,6 +2207,16 @@ static void launch_pcg_setup(ba_handle* h, double lambda, int precond, bool fina
   BA_BY_MODEL(CALL_T);
 #undef CALL_T
 #undef SU_ARGS
+  // shared intrinsics: the group sums of the preconditioner's 3 x 3 blocks, of g and of bc, then the members' rows 6-8
+  // and the workgroups' partials with the leader rule (ba_kernels.hpp, "shared intrinsics")
+  if (h->shared_on) {
+    const int keep = precond == 2 ? 1 : 0;
+    BA_LAUNCH(k_shared_sum<BalCam>, dim3(h->n_shared), dim3(SHARED_BLOCK), 0, h->stream, (const int*)h->grp_off.p, (const int*)h->grp_mem.p,
+              keep, (const double*)h->Minv.p, (const double*)h->gvec.p, (const double*)bc_ptr(h), h->grp_rec.p);
+    BA_LAUNCH(k_shared_finish<BalCam>, dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, (const int*)h->cam_gl.p, (const double*)h->grp_rec.p,
+              keep, h->Nc, (const double*)h->Hccd.p, (const double*)bc_ptr(h), h->Minv.p, h->gvec.p, h->r.p, h->z.p, h->camA[h->cur].p,
+              h->partV.p, h->partGc.p);
+  }
 }
 
 // --------------------------------------------------------------------- K1 entry point
@@ -2187,6 +2279,7 @@ extern "C" int ba_linearize(ba_handle* h, int32_t loss, double f_scale, double* 
   if (!h) return fail(BA_ERR_INVALID, "null handle");
   if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
   if (h->cam_held_or & ~0x3fu) return fail(BA_ERR_INVALID, "camera mask bits 6-8 (f, k1, k2) need the BAL camera model");
+  if (h->n_shared) return fail(BA_ERR_INVALID, "%s", kSharedNeedsBal);
   if (h->prior_nb == 9) return fail(BA_ERR_INVALID, "%s", kPriorNeedsBal);
   if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
   if (!(f_scale > 0)) return fail(BA_ERR_INVALID, "f_scale must be positive");
@@ -2363,6 +2456,7 @@ extern "C" int ba_solve(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   if (!h || !opts || !sum) return fail(BA_ERR_INVALID, "null argument");
   const int rc = solve_impl(h, opts, sum);
   h->fold_prior_rows = 0;        // (ba_residuals* and the test hooks fold the reprojection rows only)
+  h->shared_on = false;          // (... and report per-camera quantities)
   if (rc != BA_OK) {             // leave the handle usable: nothing queued, no per-solve mode left on
     const std::string msg = g_err;
     (void)hipStreamSynchronize(h->stream);
@@ -2679,6 +2773,9 @@ extern "C" int ba_covariance(ba_handle* h, const double* intr, int32_t loss, dou
   if (!h) return fail(BA_ERR_INVALID, "null handle");
   if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
   if (h->multi) return fail(BA_ERR_INVALID, "ba_covariance: multi-rank jobs are not supported");
+  if (h->n_shared)
+    return fail(BA_ERR_INVALID, "ba_covariance: covariances of shared intrinsics are not offered (camera %d shares its f, k1, k2; "
+                "clear the groups with ba_set_shared_intrinsics(h, NULL))", h->h_grp_mem[0]);
   if (!intr && (h->cam_held_or & ~0x3fu)) return fail(BA_ERR_INVALID, "camera mask bits 6-8 (f, k1, k2) need the BAL camera model");
   if (!intr && h->prior_nb == 9) return fail(BA_ERR_INVALID, "%s", kPriorNeedsBal);
   if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
@@ -2703,6 +2800,21 @@ extern "C" int ba_solve_bal(ba_handle* h, double* intr, const ba_options* opts, 
   if (!h || !intr || !opts || !sum) return fail(BA_ERR_INVALID, "null argument");
   if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
   if (set_device(h)) return BA_ERR_HIP;
+  // shared intrinsics: the members start from ONE f, k1, k2, hold the same of them, and none is the fixed camera
+  for (int g = 0; g < h->n_shared; ++g) {
+    const int lead = h->h_grp_mem[(size_t)h->h_grp_off[g]];
+    for (int i = h->h_grp_off[g]; i < h->h_grp_off[g + 1]; ++i) {
+      const int c = h->h_grp_mem[(size_t)i];
+      if (c == h->fixed)
+        return fail(BA_ERR_INVALID, "ba_solve_bal: camera %d is fixed_cam and shares its intrinsics with camera %d: fixed_cam holds the "
+                    "whole 9-parameter block; hold the camera's pose with ba_set_held bits 0-5 instead", c, c == lead ? h->h_grp_mem[(size_t)h->h_grp_off[g] + 1] : lead);
+      if (memcmp(intr + 3 * (size_t)c, intr + 3 * (size_t)lead, 3 * sizeof(double)) != 0)
+        return fail(BA_ERR_INVALID, "ba_solve_bal: camera %d does not start with the f, k1, k2 of camera %d, whose intrinsics it shares", c, lead);
+      const unsigned hc = h->any_cam_held ? (h->h_cam_held[(size_t)c] & 0x1c0u) : 0u, hl = h->any_cam_held ? (h->h_cam_held[(size_t)lead] & 0x1c0u) : 0u;
+      if (hc != hl)
+        return fail(BA_ERR_INVALID, "ba_solve_bal: camera %d holds other intrinsics (mask bits 6-8: 0x%x) than camera %d (0x%x), whose intrinsics it shares", c, hc, lead, hl);
+    }
+  }
   if (int rc = bal_enter(h, intr)) { h->model = 0; return rc; }
   int rc = ba_solve(h, opts, sum);            // (ba_solve drains the stream and clears the per-solve modes on failure)
   const std::string msg = g_err;
@@ -2746,7 +2858,9 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   if (h->model == 0 && (h->cam_held_or & ~0x3fu))
     return fail(BA_ERR_INVALID, "camera mask bits 6-8 (f, k1, k2) need the BAL camera model");
   if (h->model == 0 && h->prior_nb == 9) return fail(BA_ERR_INVALID, "%s", kPriorNeedsBal);
+  if (h->model == 0 && h->n_shared) return fail(BA_ERR_INVALID, "%s", kSharedNeedsBal);
   if (set_device(h)) return BA_ERR_HIP;
+  h->shared_on = h->model != 0 && h->n_shared > 0;
   memset(sum, 0, sizeof *sum);
   h->trace.clear();
   h->fold_prior_rows = any_prior(h) ? PRIOR_ROWS : 0;      // cost = reprojection + priors in every fold of this solve
@@ -2802,7 +2916,7 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     BA_SYNC(h);
     for (int c = 0; c < Nc; ++c)
       for (int q = 0; q < nb; ++q)
-        if ((h->h_cam_held[c] >> q) & 1u) {
+        if (((h->h_cam_held[c] >> q) & 1u) && !(q >= 6 && h->shared_on && h->h_cam_gl[c] >= 0 && !(h->h_cam_gl[c] & 1))) {   // (a shared entry once)
           const double v = q < 6 ? cams[6 * (size_t)c + q] : intr[3 * (size_t)c + q - 6];
           held_cam_x2 += v * v;
         }
@@ -2888,6 +3002,7 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     cu.cs = h->cs[h->cur].p; cu.cams_trial = h->cams[1 - h->cur].p; cu.intr_trial = h->intr[1 - h->cur].p; cu.cs_trial = h->cs[1 - h->cur].p;
     cu.vtil = h->camA[h->cur].p; cu.camA_trial = h->camA[1 - h->cur].p; cu.partC = h->partC.p;
     cu.vx = h->vx.p;
+    cu.cam_gl = cam_gl_ptr(h);
     cu.lam_slot = h->dev_lam.p;
     // (riding workgroups: a multiple of NPART, so that the point workgroups behind them keep their XCD = index mod NPART)
     cu.n_cams = Nc; cu.fixed_cam = h->fixed; cu.groups = CU_GROUPS;
@@ -2915,7 +3030,8 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     };
     // BA_IPC: the exchange of the Schur product happens inside k_pcg_step, workgroup by workgroup (ba_kernels.hpp,
     // "device-side all-reduce"); every workgroup's record has to fit its slot of the receive buffers
-    const bool use_ipc = h->ipc && h->multi && nbv(h) <= IPC_MAX_BLOCKS &&
+    // (shared intrinsics: the group fold runs on the all-reduced product, between the exchange and k_pcg_step -- base transport)
+    const bool use_ipc = h->ipc && h->multi && !h->shared_on && nbv(h) <= IPC_MAX_BLOCKS &&
                          (size_t)nbv(h) * (2 + (size_t)nb_of(h) * (h->model ? BalCam::VC : Pinhole::VC)) <= IpcComm::STRIDE;
     auto launch_rest = [&](int kk) -> int {
       launch_cam_schur(h, robust, false, true, kk, tol2, opts->pcg_min_iters);
@@ -2934,11 +3050,16 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
       Scope sc(h, BA_K_PCG_UPDATE);
       // (device-side exchange: k_cam_schur's raw partitions, folded inside the kernel; else partition 0 holds the all-reduced sums)
       const int step_parts = use_ipc ? NPART : nparts_of(h);
+      if (h->shared_on)                 // rows 6-8 of w summed over the members, a workgroup per chunk of a group
+        BA_LAUNCH(k_shared_fold<BalCam>, dim3(h->n_shared_chunks), dim3(SHARED_BLOCK), 0, h->stream, (const int*)h->chunk_rng.p, (const int*)h->grp_mem.p,
+                  (const double*)h->Hccd.p, (const double*)h->z.p, (const double*)p6_ptr(h), step_parts, Nc, h->grp_w.p);
 #define STEP_ARGS kk, (const double*)p6_ptr(h), step_parts, (const double*)uy_ptr(h), h->Hccd.p, h->Minv.p, h->cs[h->cur].p, Nc, h->fixed, tol2,       \
                   opts->pcg_min_iters, h->x.p, h->r.p, h->p.p, h->s.p, h->z.p, h->camA[h->cur].p, h->partV.p, nbv(h), h->st.p, \
                   h->d_flags, base, (const double*)h->verdict.p, h->vx.p, model_tol, opts->pcg_model_min_iters, ipc, h->d_flags + 6,        \
-                  cam_held_ptr(h)
-      if (h->model) BA_LAUNCH((k_pcg_step<BalCam>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS);
+                  cam_held_ptr(h), cam_gl_ptr(h), (const double*)(h->shared_on ? h->grp_w.p : nullptr),                                 \
+                  (const int*)(h->shared_on ? h->grp_chunk.p : nullptr)
+      if (h->shared_on) BA_LAUNCH((k_pcg_step<BalCam, true>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS);
+      else if (h->model) BA_LAUNCH((k_pcg_step<BalCam>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS);
       else          BA_LAUNCH((k_pcg_step<Pinhole>), dim3(h->nblkV), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS);
 #undef STEP_ARGS
       return BA_OK;
@@ -3092,6 +3213,7 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
 extern "C" int ba_get_stat(ba_handle* h, int32_t which, int64_t* value) {
   if (!h || !value || which < 0 || which >= BA_STAT_END) return fail(BA_ERR_INVALID, "bad argument");
   if (which == BA_STAT_PRIOR_BLOCKS) { *value = h->have_problem ? h->prior_blocks : 0; return BA_OK; }
+  if (which == BA_STAT_SHARED_GROUPS) { *value = h->have_problem ? h->n_shared : 0; return BA_OK; }
   if (which == BA_STAT_HELD_PARAMS) {
     *value = h->have_problem ? held_params(h, (h->cam_held_or & ~0x3fu) ? BalCam::NB : Pinhole::NB) : 0;
     return BA_OK;

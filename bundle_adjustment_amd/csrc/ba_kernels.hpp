@@ -899,6 +899,7 @@ struct CamUpdateArgs {
   int groups;                    // camera groups (of CM::VC cameras, one wave each) per riding 1024-thread workgroup (CU_GROUPS; <= 16)
   int fuse;                      // a PCG point pass (MODE 0) that finds PCG finished goes on as the back substitution in the SAME launch
                                  // (n_blocks camera-update workgroups ride in front, as in a MODE 1 launch): see pt_schur_body
+  const int* cam_gl;             // shared intrinsics (null = none): dc.r_pcg, |dc|^2 and |cams|^2 count a shared entry at its leader only
 };
 struct ScalarsArgs {
   const double* partR; int nR;
@@ -1651,7 +1652,10 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
             double* __restrict__ gvec, double* __restrict__ x, double* __restrict__ r, double* __restrict__ p,
             double* __restrict__ s, double* __restrict__ z, double* __restrict__ vtil,
             double* __restrict__ partV, PcgState* __restrict__ st, double* __restrict__ partGc,
-            double* __restrict__ vx, const unsigned short* __restrict__ cam_held, CamPriors pr) {
+            double* __restrict__ vx, const unsigned short* __restrict__ cam_held, CamPriors pr,
+            const int* __restrict__ cam_gl) {
+  // cam_gl (shared intrinsics, null = none): a grouped camera leaves its per-camera terms here and k_shared_sum /
+  // k_shared_finish behind this kernel put the group sums in their place (see "shared intrinsics" below)
   constexpr int NB = CM::NB, NH = CM::NH, NL = CM::NL, VC = CM::VC;
   // LDS image of the workgroup's VC cameras.  Inputs: partition-folded sums (a: NL of the linearisation when
   // FINALIZE, e: NH Schur-Jacobi, w6: NB of W y0), Hcc | bc (when not FINALIZE), cs.  Outputs staged for a
@@ -1745,7 +1749,24 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
         for (int i = 0; i < NB; ++i) for (int j = i; j < NB; ++j) m[UT(NB, i, j)] -= A[i][j];
         if (held) held_identity<NB>(held, m);
       }
+      // member of a group (shared intrinsics): the pose block alone is inverted -- coupling 0 and an identity in the 3 x 3
+      // corner, which the Cholesky factors keep apart -- and the corner's own entries go out in its place for the group sum
+      double m3[6];
+      bool grouped = false;
+      if constexpr (NB > 6) {
+        grouped = cam_gl && cam_gl[c] >= 0;
+        if (grouped) {
+          for (int i = 0; i < 3; ++i) for (int j = i; j < 3; ++j) { m3[U3(i, j)] = m[UT(NB, 6 + i, 6 + j)]; m[UT(NB, 6 + i, 6 + j)] = (i == j) ? 1.0 : 0.0; }
+          for (int i = 0; i < 6; ++i) for (int j = 6; j < NB; ++j) m[UT(NB, i, j)] = 0.0;
+        }
+      }
       spdN_inverse<NB>(m, inv);
+      if constexpr (NB > 6) {
+        if (grouped) {
+          for (int i = 0; i < 3; ++i) for (int j = i; j < 3; ++j) inv[UT(NB, 6 + i, 6 + j)] = m3[U3(i, j)];
+          for (int i = 0; i < 6; ++i) for (int j = 6; j < NB; ++j) inv[UT(NB, i, j)] = 0.0;
+        }
+      }
       for (int q = 0; q < NH; ++q) l_mi[NH * t + q] = inv[q];
     }
     double wy[NB], g[NB], zz[NB], hz[NB];
@@ -1798,6 +1819,158 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
   }
 }
 
+// ---- shared intrinsics (ba_set_shared_intrinsics) ----------------------------------------------------------------
+// Cameras of a group share ONE f, k1, k2: with x = E y (E replicates a group's three entries into rows 6-8 of every
+// member) the damped reduced system is (E^T S E) y = E^T g.  Every PCG vector stays in its (Nc, 9) array in replicated
+// form -- rows 6-8 of every member hold the group's value, bit for bit -- so no observation-loop kernel changes.  What
+// changes is the camera-vector stage: rows 6-8 of the product, of the right-hand side and of the preconditioner's
+// 3 x 3 block are SUMS over a group's members (these kernels), and inner products count a shared entry once, at the
+// group's leader (its lowest member).  cam_gl[c] = -1: camera c has its own intrinsics, else 2 * group + (1: leader).
+// Member lists: CSR (grp_off, grp_mem), members ascending.  Every sum below runs in one fixed order -- a thread's
+// members ascending, then the lanes of a wave, then the waves -- over all-reduced inputs: every rank gets the same bits.
+constexpr int SHARED_BLOCK = 256;        // threads of a group's reducing workgroup (groups of any size: members are strided)
+constexpr int SHARED_REC = 16;           // doubles per group of k_shared_sum's record: inv3[6] | g3[3] | z3[3] | max |bc3| | pad
+template <int N>
+__device__ inline void shared_block_sum(double (&a)[N], double* __restrict__ lds) {   // lds: N * SHARED_BLOCK / 64 doubles; total in every thread
+  constexpr int NW = SHARED_BLOCK / 64;
+  const int wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < N; ++q) a[q] = wave_total_dpp(a[q]);
+  if ((threadIdx.x & 63) == 0)
+    for (int q = 0; q < N; ++q) lds[N * wv + q] = a[q];
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < N; ++q) {
+    double t = lds[q];
+    for (int w = 1; w < NW; ++w) t += lds[N * w + q];
+    a[q] = t;
+  }
+}
+// Once per damped system, behind k_pcg_setup (one workgroup per group): sum of the members' 3 x 3 preconditioner entries
+// (k_pcg_setup left them in Minv's corner; keep: the blocks are kept, the corner already holds the group's inverse), of
+// rows 6-8 of g and of bc; then the group's inverse, g and z = inverse g into the group's record.
+template <class CM>
+__global__ void __launch_bounds__(SHARED_BLOCK)
+k_shared_sum(const int* __restrict__ grp_off, const int* __restrict__ grp_mem, int keep, const double* __restrict__ Minv,
+             const double* __restrict__ gvec, const double* __restrict__ bc, double* __restrict__ rec) {
+  constexpr int NB = CM::NB, NH = CM::NH;
+  static_assert(NB == 9, "shared intrinsics: rows 6-8 of a 9-parameter camera block");
+  __shared__ double lds[12 * SHARED_BLOCK / 64];
+  const int g = blockIdx.x;
+  const int beg = grp_off[g], end = grp_off[g + 1];
+  double a[12];
+#pragma unroll
+  for (int q = 0; q < 12; ++q) a[q] = 0.0;
+  for (int i = beg + (int)threadIdx.x; i < end; i += SHARED_BLOCK) {
+    const int c = grp_mem[i];
+    if (!keep) {
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int j = r; j < 3; ++j) a[U3(r, j)] += Minv[NH * (size_t)c + UT(NB, 6 + r, 6 + j)];
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { a[6 + q] += gvec[NB * (size_t)c + 6 + q]; a[9 + q] += bc[NB * (size_t)c + 6 + q]; }
+  }
+  shared_block_sum<12>(a, lds);
+  if (threadIdx.x == 0) {
+    double inv[6], z3[3];
+    if (keep) {
+      const int lead = grp_mem[beg];
+      for (int r = 0; r < 3; ++r) for (int j = r; j < 3; ++j) inv[U3(r, j)] = Minv[NH * (size_t)lead + UT(NB, 6 + r, 6 + j)];
+    } else spdN_inverse<3>(a, inv);
+    sym3_mul(inv, a + 6, z3);
+    double* o = rec + SHARED_REC * (size_t)g;
+    for (int q = 0; q < 6; ++q) o[q] = inv[q];
+    for (int q = 0; q < 3; ++q) { o[6 + q] = a[6 + q]; o[9 + q] = z3[q]; }
+    o[12] = nanmax(nanmax(fabs(a[9]), fabs(a[10])), fabs(a[11]));
+  }
+}
+// ... and behind that, in k_pcg_setup's geometry: the members' rows 6-8 of g = r, z, vtil and (unless kept) the corner of
+// Minv take the group's values, and the workgroup's partials are written again with the leader rule: gamma = r.z counts a
+// shared entry once, zeta = z.Hccd z is the expanded operator's quadratic form (a full sum), max |bc| sees the group sum.
+template <class CM>
+__global__ void __launch_bounds__(VEC_BLOCK)
+k_shared_finish(const int* __restrict__ cam_gl, const double* __restrict__ rec, int keep, int n_cams, const double* __restrict__ Hccd,
+                const double* __restrict__ bc, double* __restrict__ Minv, double* __restrict__ gvec, double* __restrict__ r,
+                double* __restrict__ z, double* __restrict__ vtil, double* __restrict__ partV, double* __restrict__ partGc) {
+  constexpr int NB = CM::NB, NH = CM::NH, VC = CM::VC;
+  const int c = vec_camera<VC>(n_cams);
+  double acc[2] = {0, 0};
+  double gmc = 0.0;
+  if (c < n_cams) {
+    const int gl = cam_gl[c];
+    double g[NB], zz[NB], hz[NB];
+#pragma unroll
+    for (int q = 0; q < NB; ++q) { g[q] = gvec[NB * (size_t)c + q]; zz[q] = z[NB * (size_t)c + q]; }
+    if (gl >= 0) {
+      const double* o = rec + SHARED_REC * (size_t)(gl >> 1);
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        g[6 + q] = o[6 + q]; zz[6 + q] = o[9 + q];
+        gvec[NB * (size_t)c + 6 + q] = g[6 + q]; r[NB * (size_t)c + 6 + q] = g[6 + q]; z[NB * (size_t)c + 6 + q] = zz[6 + q];
+        vtil[CM::TA * (size_t)c + CM::VOFF + 6 + q] = zz[6 + q];        // (write_vtil passes rows 3.. through)
+      }
+      if (!keep)
+        for (int i = 0; i < 3; ++i) for (int j = i; j < 3; ++j) Minv[NH * (size_t)c + UT(NB, 6 + i, 6 + j)] = o[U3(i, j)];
+      gmc = (gl & 1) ? o[12] : 0.0;
+    }
+    symN_mul<NB>(Hccd + NH * (size_t)c, zz, hz);
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+      const bool once = q < 6 || gl < 0 || (gl & 1);
+      if (once) acc[0] += g[q] * zz[q];
+      acc[1] += zz[q] * hz[q];
+      if (q < 6 || gl < 0) gmc = nanmax(gmc, fabs(bc[NB * (size_t)c + q]));
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 2; ++q) acc[q] = wave_total_dpp(acc[q]);
+  gmc = wave_nanmax(gmc);
+  if (threadIdx.x == 0) {
+    partV[2 * blockIdx.x] = acc[0];
+    partV[2 * blockIdx.x + 1] = acc[1];
+    partGc[blockIdx.x] = gmc;
+  }
+}
+// Once per PCG iteration, between k_cam_schur (and the all-reduce of a multi-rank job) and k_pcg_step: rows 6-8 of
+// w_c = Hccd_c z_c - (W y)_c summed over a group's members.  A group is cut into chunks of SHARED_BLOCK consecutive members
+// (chunk_rng[2 k], [2 k + 1]: the chunk's range in grp_mem; a group's chunks are consecutive: grp_chunk[g] .. grp_chunk[g + 1]),
+// one workgroup and one member per thread each, so that a group of every camera is spread over the chip instead of
+// walked by one workgroup; k_pcg_step adds a group's chunk sums in chunk order for rows 6-8 of every member's w.
+template <class CM>
+__global__ void __launch_bounds__(SHARED_BLOCK)
+k_shared_fold(const int* __restrict__ chunk_rng, const int* __restrict__ grp_mem, const double* __restrict__ Hccd,
+              const double* __restrict__ z, const double* __restrict__ part6, int nparts, int n_cams, double* __restrict__ gw) {
+  constexpr int NB = CM::NB, NH = CM::NH;
+  static_assert(NB == 9, "shared intrinsics: rows 6-8 of a 9-parameter camera block");
+  __shared__ double lds[3 * SHARED_BLOCK / 64];
+  const int g = blockIdx.x;
+  const int beg = chunk_rng[2 * g], end = chunk_rng[2 * g + 1];
+  const size_t p6_stride = (size_t)n_cams * NB;
+  double a[3] = {0, 0, 0};
+  for (int i = beg + (int)threadIdx.x; i < end; i += SHARED_BLOCK) {      // (one pass: a chunk has at most SHARED_BLOCK members)
+    const int c = grp_mem[i];
+    double zz[NB], wy[3] = {0, 0, 0};
+#pragma unroll
+    for (int q = 0; q < NB; ++q) zz[q] = z[NB * (size_t)c + q];
+    for (int kk = 0; kk < nparts; ++kk) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) wy[q] += part6[(size_t)kk * p6_stride + NB * (size_t)c + 6 + q];
+    }
+    const double* h = Hccd + NH * (size_t)c;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      double t = 0;
+#pragma unroll
+      for (int j = 0; j < NB; ++j) t += h[ST(NB, 6 + q, j)] * zz[j];
+      a[q] += t - wy[q];
+    }
+  }
+  shared_block_sum<3>(a, lds);
+  if (threadIdx.x < 3) gw[3 * (size_t)g + threadIdx.x] = a[threadIdx.x];
+}
+
 // K5: one PCG iteration's vector work (Chronopoulos-Gear single-reduction CG).  With z the
 // preconditioned residual and w = S z:
 //   gamma = r.z (partials of the previous step), delta = z.Hccd z - u.y,
@@ -1806,7 +1979,9 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
 // Every workgroup recomputes the scalars from the same words; workgroup 0 publishes the
 // next state into the other parity slot.  uy_src: the u.y word (folded by k_cam_schur's
 // extra workgroup, or all-reduced in a multi-rank job).
-template <class CM>
+// SHARED (shared intrinsics, BalCam only): an instantiation of its own, so that the ungrouped kernel keeps its registers
+// (248 VGPRs, two waves per SIMD; the three extra pointers and the group index cost the grouped one the second wave).
+template <class CM, bool SHARED = false>
 __global__ void __launch_bounds__(VEC_BLOCK)
 k_pcg_step(int k, const double* __restrict__ part6, int nparts, const double* __restrict__ uy_src,
            const double* __restrict__ Hccd, const double* __restrict__ Minv, const double* __restrict__ cs,
@@ -1816,7 +1991,9 @@ k_pcg_step(int k, const double* __restrict__ part6, int nparts, const double* __
            PcgState* __restrict__ st, long long* __restrict__ host_flag, long long flag_base,
            const double* __restrict__ verdict, double* __restrict__ vx,
            double model_tol, int model_min_iters, IpcStep ipc, long long* __restrict__ err_flag,
-           const unsigned short* __restrict__ cam_held) {
+           const unsigned short* __restrict__ cam_held, const int* __restrict__ cam_gl, const double* __restrict__ gw,
+           const int* __restrict__ grp_chunk) {
+  // cam_gl / gw / grp_chunk (shared intrinsics, null = none): rows 6-8 of a grouped camera's w are k_shared_fold's sums
   // ipc.on (multi-rank, device-side exchange): part6 / uy_src are this rank's own sums; the other ranks' arrive in the
   // receive buffer while the kernel runs (see "device-side all-reduce" above)
   constexpr int NB = CM::NB, NH = CM::NH, VC = CM::VC;
@@ -1949,6 +2126,18 @@ k_pcg_step(int k, const double* __restrict__ part6, int nparts, const double* __
     }
     symN_mul<NB>(h, zz, w);
     const unsigned held = cam_held_bits(cam_held, c);      // held rows of S: identity, so that r, z, p, s, x stay 0 there
+    int gl = -1;
+    if constexpr (SHARED) {
+      gl = cam_gl[c];
+      if (gl >= 0) {                                       // E^T S E: the group's sum, the same bits in every member
+#pragma unroll
+        for (int q = 6; q < NB; ++q) { w[q] = 0.0; wy[q] = 0.0; }
+        for (int ch = grp_chunk[gl >> 1]; ch < grp_chunk[(gl >> 1) + 1]; ++ch) {      // chunk order: the same sum in every member
+#pragma unroll
+          for (int q = 6; q < NB; ++q) w[q] += gw[3 * (size_t)ch + (q - 6)];
+        }
+      }
+    }
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
       w[q] = ((held >> q) & 1u) ? 0.0 : w[q] - wy[q];
@@ -1963,7 +2152,7 @@ k_pcg_step(int k, const double* __restrict__ part6, int nparts, const double* __
     for (int q = 0; q < NB; ++q) {
       l_v[0][NB * t + q] = zz[q]; l_v[1][NB * t + q] = pp[q]; l_v[2][NB * t + q] = ss[q];
       l_v[3][NB * t + q] = rr[q]; l_v[4][NB * t + q] = xx[q];
-      acc[0] += rr[q] * zz[q];
+      if (!SHARED || q < 6 || gl < 0 || (gl & 1)) acc[0] += rr[q] * zz[q];       // (a shared entry counts once, at the group's leader)
       acc[1] += zz[q] * hz[q];
     }
     write_vtil<NB>(M, zz, vtil + CM::TA * (size_t)c + CM::VOFF);
@@ -2045,15 +2234,18 @@ __device__ void cam_update_body(const CamUpdateArgs& a, int blk, bool active, do
     double d[NB];
     for (int q = 0; q < NB; ++q) d[q] = (c == fixed_cam) ? 0.0 : l_in[NB * t + q];
     double it3[3] = {0.0, 0.0, 0.0};                   // trial intrinsics (models with per-camera intrinsics)
+    const int gl = (NB > 6 && a.cam_gl) ? a.cam_gl[c] : -1;
     for (int q = 0; q < NB; ++q) {
       const double xq = q < 6 ? l_cam[6 * t + q] : a.intr[3 * (size_t)c + (q - 6)];
       if (q < 6) l_ct[6 * t + q] = xq + d[q];
       else it3[q - 6] = xq + d[q];
       acc[0] += l_in[2 * NB * VC + NB * t + q] * d[q];
       acc[1] += fmax(l_hcc[NH * t + UT(NB, q, q)], DIAG_FLOOR) * d[q] * d[q];
-      acc[2] += d[q] * ((c == fixed_cam) ? 0.0 : l_in[NB * VC + NB * t + q]);
-      acc[3] += d[q] * d[q];
-      acc[4] += xq * xq;
+      if (q < 6 || gl < 0 || (gl & 1)) {               // (the y problem's sums: a shared entry once)
+        acc[2] += d[q] * ((c == fixed_cam) ? 0.0 : l_in[NB * VC + NB * t + q]);
+        acc[3] += d[q] * d[q];
+        acc[4] += xq * xq;
+      }
     }
     if (NB > 6) {
       for (int q = 0; q < NB - 6; ++q) a.intr_trial[3 * (size_t)c + q] = it3[q];

@@ -94,6 +94,7 @@ SYMBOLS = {
     "ba_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ba_set_problem": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, _IP, _IP, _DP, _DP, C.c_int32]),
     "ba_set_held": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)]),
+    "ba_set_shared_intrinsics": (C.c_int, [C.c_void_p, _IP]),
     "ba_set_priors": (C.c_int, [C.c_void_p, C.c_int32, _DP, _DP, _DP, _DP]),
     "ba_prior_cost": (C.c_int, [C.c_void_p, _DP, _DP, _DP]),
     "ba_set_params": (C.c_int, [C.c_void_p, _DP, _DP]),
@@ -122,7 +123,7 @@ SYMBOLS = {
 # enum ba_stat (include/ba_hip.h)
 STATS = {"window_mw_launches": 0, "window_lm_launches": 1, "window_fallbacks": 2, "precond_builds": 3, "precond_reuses": 4, "banded": 5,
          "cap_floor_raises": 6, "ipc_exchanges": 7, "pixels_f32": 8, "held_params": 9,
-         "prior_blocks": 10}
+         "prior_blocks": 10, "shared_groups": 11}
 
 
 def held_camera_mask(cams, n_cams, nb=6):
@@ -145,6 +146,38 @@ def held_camera_mask(cams, n_cams, nb=6):
     if a.size and (a.min() < 0 or a.max() > 0x1FF):
         raise ValueError("camera mask bits must lie in 0-8 (rvec 0-2, t 3-5, f 6, k1 7, k2 8)")
     return a.astype(np.uint16)
+
+
+def camera_groups(spec, n_cams):
+    """Normalise a shared-intrinsics spec to ba_set_shared_intrinsics' int32 (Nc,) labels (cameras with the same label
+    >= 0 share one f, k1, k2; -1: the camera's own): True (one group of all cameras), a label array (Nc,), or a list of
+    index lists (group i gets label i).  None / False -> None.  Raises ValueError for an index out of range, a camera in
+    two lists or a wrong length (a label below -1 is the library's to refuse: it names the camera)."""
+    if spec is None or spec is False:
+        return None
+    if spec is True:
+        return np.zeros(n_cams, dtype=np.int32)
+    if isinstance(spec, np.ndarray) or (len(spec) > 0 and all(np.ndim(g) == 0 for g in spec)):
+        a = np.asarray(spec)
+        if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"camera group labels must be integers, not {a.dtype}")
+        if a.shape != (n_cams,):
+            raise ValueError(f"a camera group label array must be ({n_cams},), not {a.shape}")
+        if a.size and (a.min() < np.iinfo(np.int32).min or a.max() > np.iinfo(np.int32).max):
+            raise ValueError("camera group labels must fit int32")
+        return a.astype(np.int32)
+    labels = np.full(n_cams, -1, dtype=np.int32)
+    for g, members in enumerate(spec):
+        m = np.asarray(members)
+        if m.ndim != 1 or (m.size and not np.issubdtype(m.dtype, np.integer)):
+            raise ValueError(f"camera group {g} must be a list of camera indices")
+        m = m.astype(np.int64)
+        if m.size and (m.min() < 0 or m.max() >= n_cams):
+            raise ValueError(f"camera group {g}: index out of range [0, {n_cams})")
+        if np.unique(m).size != m.size or (labels[m] >= 0).any():
+            raise ValueError(f"camera group {g}: a camera is listed twice")
+        labels[m] = g
+    return labels
 
 
 def unpack_sym(packed, nb):
@@ -261,6 +294,8 @@ class Solver:
             self.set_held(prob.cam_held, prob.pt_held)
         if prob.cam_prior is not None or prob.pt_prior is not None:
             self.set_priors(prob.cam_prior, prob.pt_prior)
+        if getattr(prob, "cam_group", None) is not None:
+            self.set_shared_intrinsics(prob.cam_group)
         if with_params:
             self.set_params(prob.cams, prob.pts)
 
@@ -298,6 +333,14 @@ class Solver:
         pm = None if pm is None else np.ascontiguousarray(pm)
         _check(self._lib.ba_set_held(self._h, None if cm is None else cm.ctypes.data_as(C.POINTER(C.c_uint16)),
                                      None if pm is None else pm.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def set_shared_intrinsics(self, groups=None):
+        """ba_set_shared_intrinsics: cameras that share ONE f, k1, k2 in BAL solves.  groups: True (all cameras), a label
+        array (Nc,) (-1: own intrinsics), a list of index lists, or None (clear) -- see camera_groups.  The groups stay with
+        the handle across set_params and solves; set_problem clears them."""
+        lab = camera_groups(groups, self.n_cams)
+        lab = None if lab is None else np.ascontiguousarray(lab, dtype=np.int32)
+        _check(self._lib.ba_set_shared_intrinsics(self._h, None if lab is None else lab.ctypes.data_as(_IP)))
 
     def set_params(self, cams, pts):
         cams = np.ascontiguousarray(cams, dtype=np.float64).reshape(self.n_cams, 6)
@@ -462,11 +505,14 @@ class Solver:
         return o
 
     def solve_bal(self, bal, fixed_cam=-1, hold_intrinsics=False, held_cameras=None, held_points=None, camera_priors=None,
-                  point_priors=None, **kw):
+                  point_priors=None, shared_intrinsics=None, **kw):
         """ba_solve_bal on a bal.BALProblem (9-parameter cameras, f / k1 / k2 adjusted with the pose): returns
         (summary dict, cams (Nc,9), pts (Np,3)).  hold_intrinsics: keep every camera's f, k1, k2; held_cameras /
-        held_points: as set_held (added to hold_intrinsics); camera_priors / point_priors: as set_priors.  kw as for solve()."""
+        held_points: as set_held (added to hold_intrinsics); camera_priors / point_priors: as set_priors;
+        shared_intrinsics: as set_shared_intrinsics (the members' f, k1, k2 must be equal on entry).  kw as for solve()."""
         intr = self._set_bal(bal, fixed_cam)
+        if shared_intrinsics is not None:
+            self.set_shared_intrinsics(shared_intrinsics)
         if camera_priors is not None or point_priors is not None:
             self.set_priors(camera_priors, point_priors)
         cm = held_camera_mask(held_cameras, self.n_cams, 9)

@@ -35,6 +35,7 @@ class BAProblem:
     pt_held: np.ndarray | None = None    # optional (Np,) bool: held points
     cam_prior: object = None             # optional camera priors (hip_backend.Solver.set_priors forms; ba_set_priors)
     pt_prior: object = None              # optional point priors: (mean (Np, 3), info (Np, 3, 3)) or a dict point -> (mean, info)
+    cam_group: object = None             # optional shared intrinsics of BAL solves (hip_backend.camera_groups forms; ba_set_shared_intrinsics)
 
     @property
     def n_cams(self):
@@ -70,6 +71,9 @@ class BAProblem:
             from .priors import camera_prior_nb, pack_priors
             pack_priors(self.cam_prior, nc, camera_prior_nb(self.cam_prior) or 6, "camera")
             pack_priors(self.pt_prior, npt, 3, "point")
+        if self.cam_group is not None:
+            from .hip_backend import camera_groups
+            camera_groups(self.cam_group, nc)
         return self
 
 
@@ -81,6 +85,15 @@ def _shard_point_prior(spec, p_begin, p_end):
         return {int(i) - p_begin: (np.array(m, copy=True), np.array(L, copy=True)) for i, (m, L) in spec.items() if p_begin <= i < p_end}
     m, L = spec
     return np.array(np.asarray(m)[p_begin:p_end], copy=True), np.array(np.asarray(L)[p_begin:p_end], copy=True)
+
+
+def _copy_groups(spec):
+    """Camera groups go to every shard whole (all cameras are replicated)."""
+    if spec is None or isinstance(spec, bool):
+        return spec
+    if isinstance(spec, np.ndarray):
+        return spec.copy()
+    return [g.copy() if isinstance(g, np.ndarray) else (list(g) if np.ndim(g) else g) for g in spec]
 
 
 def _copy_prior(spec):
@@ -248,7 +261,8 @@ def extract_shard(problem: BAProblem, p_begin: int, p_end: int):
                     problem.uv[sel].copy(), problem.K4.copy(), problem.fixed_cam,
                     None if problem.cam_held is None else np.array(problem.cam_held, copy=True),
                     None if problem.pt_held is None else np.array(problem.pt_held[p_begin:p_end], copy=True),
-                    _copy_prior(problem.cam_prior), _shard_point_prior(problem.pt_prior, p_begin, p_end))
+                    _copy_prior(problem.cam_prior), _shard_point_prior(problem.pt_prior, p_begin, p_end),
+                    _copy_groups(problem.cam_group))
     return sub, sel
 
 

@@ -251,6 +251,54 @@ def make_bal_problem(n_cams=1723, n_pts=156502, n_obs_target=678718, seed=0, pix
     return BALProblem(cams_0, start.pts.copy(), start.cam_idx.copy(), start.pt_idx.copy(), uv).validate()
 
 
+def make_shared_bal_problem(groups, n_cams, n_pts, n_obs_target, seed=0, outlier_frac=0.0):
+    """A BAL problem whose data come from a SHARED truth: the chain topology and true poses / points of
+    ``make_bal_problem``, with the true (f, k1, k2) of every camera group (``hip_backend.camera_groups`` forms) set to the
+    members' median.  Pixels: the truth projected through the BAL model plus N(0, 0.5) noise, rounded to float32; for
+    ``outlier_frac`` of them N(0, 20) on top.  Start: rvec off by 0.005, t by 0.02, points by 0.05; per group (and per
+    ungrouped camera) f times 1 + N(0, 0.005), k1 plus N(0, 0.005), k2 = 0 -- the members of a group start equal.
+    (``make_bal_problem`` has distinct true intrinsics per camera: forced to share, it has no sharp minimiser.)
+    Returns ``(bal.BALProblem, labels (Nc,) int32)``."""
+    from .bal import BALProblem, from_pinhole
+    from .hip_backend import camera_groups
+    labels = camera_groups(groups, n_cams)
+    labels = np.full(n_cams, -1, dtype=np.int32) if labels is None else labels
+    focal = 900.0
+    K4 = np.array([focal, focal, 640.0, 360.0])
+    start_pin, cams_true, pts_true = make_bal_like(n_cams, n_pts, n_obs_target, seed=seed, K4=K4, pixel_sigma=0.0,
+                                                   return_truth=True)
+    truth = from_pinhole(BAProblem(cams_true, pts_true, start_pin.cam_idx, start_pin.pt_idx, start_pin.uv, K4, 0))
+    rng = np.random.default_rng(seed + 104729)
+    cams_t = truth.cams.copy()
+    cams_t[:, 6] = focal * (1.0 + 0.02 * rng.normal(size=n_cams))
+    cams_t[:, 7] = -0.03 + 0.01 * rng.normal(size=n_cams)
+    cams_t[:, 8] = 0.003 * rng.normal(size=n_cams)
+    # one block of intrinsics per group; an ungrouped camera is a block of its own
+    block = labels.astype(np.int64).copy()
+    free = block < 0
+    block[free] = (block.max() + 1 if block.size else 0) + np.arange(int(free.sum()))
+    _, block = np.unique(block, return_inverse=True)
+    for b in range(int(block.max()) + 1 if block.size else 0):
+        m = block == b
+        cams_t[m, 6:9] = np.median(cams_t[m, 6:9], axis=0)
+    uv = bal_project(cams_t, pts_true, truth.cam_idx, truth.pt_idx)
+    uv = uv + rng.normal(0.0, 0.5, size=uv.shape)
+    if outlier_frac > 0.0:
+        nout = int(round(outlier_frac * uv.shape[0]))
+        idx = rng.choice(uv.shape[0], size=nout, replace=False)
+        uv[idx] += rng.normal(0.0, 20.0, size=(nout, 2))
+    uv = uv.astype(np.float32).astype(np.float64)
+    cams_0 = cams_t.copy()
+    cams_0[1:, :3] += rng.normal(0.0, 0.005, size=(n_cams - 1, 3))
+    cams_0[1:, 3:6] += rng.normal(0.0, 0.02, size=(n_cams - 1, 3))
+    nb = int(block.max()) + 1 if block.size else 0
+    cams_0[:, 6] = cams_t[:, 6] * (1.0 + 0.005 * rng.normal(size=nb))[block]
+    cams_0[:, 7] = cams_t[:, 7] + (0.005 * rng.normal(size=nb))[block]
+    cams_0[:, 8] = 0.0
+    pts_0 = pts_true + rng.normal(0.0, 0.05, size=pts_true.shape)
+    return BALProblem(cams_0, pts_0, truth.cam_idx.copy(), truth.pt_idx.copy(), uv).validate(), labels
+
+
 def problem_to_map(prob: BAProblem, extra_newest=True):
     """Build a ``Map`` whose window (``all_kf_ids[-(w+1):-1]`` with w = Nc,
     ``src/bundle_adjuster.py:139``) reproduces ``prob``: keyframe i <-> camera i, map

@@ -164,7 +164,8 @@ enum ba_stat {
                                        (6 parameters, or 9 once a camera mask sets a BAL bit); 3 per held point */
   BA_STAT_COUNT = 10,               /* statistics 0 - 9: the set callers of earlier releases size their arrays by */
   BA_STAT_PRIOR_BLOCKS = 10,        /* cameras + points of the calling rank that carry a non-zero prior block (ba_set_priors) */
-  BA_STAT_END = 11                  /* one past the last statistic ba_get_stat answers */
+  BA_STAT_SHARED_GROUPS = 11,       /* groups of two or more cameras that share their intrinsics (ba_set_shared_intrinsics) */
+  BA_STAT_END = 12                  /* one past the last statistic ba_get_stat answers */
 };
 
 const char* ba_last_error(void);
@@ -224,6 +225,29 @@ int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64_t n_obs,
  * Multi-rank jobs: cam_held covers ALL cameras and must be the same on every rank (the caller's obligation); pt_held is
  * per shard, in the shard's local point order. */
 int ba_set_held(ba_handle* h, const uint16_t* cam_held, const uint8_t* pt_held);
+/* Shared intrinsics: cameras that are ONE physical camera (Ceres / COLMAP / g2o: the same intrinsics block passed to many
+ * observations; no reference counterpart).  BAL solves only.
+ *   cam_group int32[Nc] or NULL: cameras with the same label >= 0 share ONE f, k1, k2; -1 = the camera's own.
+ * Labels are arbitrary non-negative int32; a label below -1 is refused (BA_ERR_INVALID, naming the camera).  A group of one
+ * member is an ungrouped camera.  The groups belong to the handle like the held masks and priors: they survive ba_set_params
+ * and repeated solves; ba_set_problem clears them, and so does a NULL argument or an assignment in which no group has two
+ * members.  BA_STAT_SHARED_GROUPS = groups with two or more members.
+ * ba_solve_bal then adjusts y = (6 pose entries per camera, 3 entries per group, 3 per ungrouped camera) with x = E y, E
+ * replicating a group's entries into every member: the damped reduced system is (E^T S E) y = E^T g, the Marquardt diagonal of
+ * a shared entry the sum of the members' (floored per camera), the preconditioner a member's 6 x 6 pose block and the SUM of
+ * the members' 3 x 3 intrinsics blocks (no coupling), and gain ratio, gtol, xtol and the trace's step_norm are those of the y
+ * problem (a shared entry counts once).  On entry ba_solve_bal refuses with BA_ERR_INVALID, naming the first offending camera:
+ * members whose intr rows are not bit-equal; members whose held bits 6-8 differ; fixed_cam inside a group (fixed_cam holds the
+ * whole 9-parameter block, which contradicts a free shared block: hold the camera's pose with ba_set_held bits 0-5 instead).
+ * On exit the members' intr rows are bit-equal.  nb = 9 priors on members simply add: the sum of the members' blocks is the
+ * group's prior.
+ * With groups set: ba_solve and ba_linearize (pinhole) refuse, as they do for held bits 6-8; ba_covariance refuses by name
+ * (covariances of shared intrinsics are not offered); ba_linearize_bal, ba_schur_system, ba_residuals_bal and ba_prior_cost
+ * keep reporting per-camera quantities -- E^T of them (the sum over a group's members) is the caller's.
+ * Multi-rank jobs: cam_group covers ALL cameras and must be the same on every rank, like cam_held; the group sums run on the
+ * all-reduced product in a fixed order, so every rank computes the same bits.  The in-kernel IPC exchange (BA_IPC=1) is not
+ * used by such solves: the base transport serves them and BA_STAT_IPC_EXCHANGES stays 0. */
+int ba_set_shared_intrinsics(ba_handle* h, const int32_t* cam_group);
 /* Gaussian priors: soft knowledge of camera blocks and points (Ceres residual blocks on one parameter block, g2o unary
  * edges, GTSAM PriorFactor, ground-control points; no reference counterpart).  The objective ba_solve / ba_solve_bal
  * minimise becomes
@@ -299,7 +323,8 @@ int ba_linearize_bal(ba_handle* h, const double* intr, int32_t loss, double f_sc
  * (landmark shards, the same all-reduces; fold sizes follow the 9-parameter blocks).  Cameras (rvec, t) and points are the
  * handle's (ba_set_params before, ba_get_params after); intr double[Nc][3] = (f, k1, k2) per camera is read AND updated.
  * fixed_cam of ba_set_problem is honoured (-1: no camera held; the damping carries the gauge), and so are the masks of
- * ba_set_held, bits 6-8 included: a held intrinsic comes back in intr unchanged, bit for bit. */
+ * ba_set_held, bits 6-8 included: a held intrinsic comes back in intr unchanged, bit for bit; and the groups of
+ * ba_set_shared_intrinsics (see there for what is refused on entry). */
 int ba_solve_bal(ba_handle* h, double* intr, const ba_options* opts, ba_summary* sum);
 
 /* K2/K3: linearise at the current parameters.  Outputs (any may be NULL):
