@@ -240,3 +240,19 @@ def covariance(prob: BALProblem, device=0, fixed_cam=-1, hold_intrinsics=False, 
         if cp is not None or point_priors is not None:
             s.set_priors(cp, point_priors)
         return s.covariance(loss=loss, f_scale=f_scale, intr=intr, full=full, rcond=rcond)
+
+
+def triangulate(prob: BALProblem, device=0, write=False, **opts):
+    """Triangulate every point of a BAL problem from all of its observations and ``prob``'s cameras, f / k1 / k2 included
+    (``ba_triangulate_tracks``; opts as ``hip_backend.Solver.triangulate_tracks``: loss, refine_iters, f_scale,
+    min_angle_deg, max_reproj_px, min_depth).  Returns dict(xyz, status, angle_deg, rms_px, max_px) in ``prob``'s point order;
+    with ``write=True`` also a copy of ``prob`` whose OK points carry the triangulated positions -- what
+    ``triangulation.filter_tracks`` and the next ``solve`` take."""
+    from . import hip_backend
+    with hip_backend.Solver(device) as s:
+        intr = s._set_bal(prob)
+        out = s.triangulate_tracks(intr=intr, write_points=int(bool(write)), **opts)
+        pts = s.get_params()[1] if write else None
+    if not write:
+        return out
+    return out, BALProblem(prob.cams.copy(), pts, prob.cam_idx.copy(), prob.pt_idx.copy(), prob.uv.copy())

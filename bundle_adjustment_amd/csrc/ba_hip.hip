@@ -37,6 +37,7 @@
 #include "ba_small_mw.hpp"
 #include "ba_setup.hpp"
 #include "ba_cov.hpp"
+#include "ba_tracks.hpp"
 
 using namespace ba;
 
@@ -65,7 +66,7 @@ extern "C" const char* ba_last_error(void) { return g_err.c_str(); }
 
 static const char* kKernelNames[BA_PROFILE_SLOTS] = {
     "cam_prepare", "residual_cam", "linearize_cam", "linearize_pt", "point_invert", "schur_pt",
-    "schur_cam", "pcg_step", "precond", "backsub_pt", "misc", "allreduce", "schur_pt_then_backsub", "", "", ""};
+    "schur_cam", "pcg_step", "precond", "backsub_pt", "misc", "allreduce", "schur_pt_then_backsub", "tracks", "", ""};
 extern "C" const char* ba_kernel_name(int slot) {
   return (slot >= 0 && slot < BA_PROFILE_SLOTS) ? kKernelNames[slot] : "";
 }
@@ -257,6 +258,12 @@ struct ba_handle {
   DBuf<double> gvec, x, r, p, s, z, vin, vx, scal, rbuf, gather;
   DBuf<PcgState> st;
   DBuf<double> tri;            // staging of ba_triangulate
+  // ba_triangulate_tracks: per-slot results, camera centres, the BAL intrinsics of the call, caller-order outputs; the
+  // launch arguments of the last call (what ba_time_kernel(BA_K_TRACKS) repeats; forgotten by ba_set_problem)
+  DBuf<double> trk_out, trk_ctr, trk_intr, trk_res;
+  DBuf<unsigned char> trk_status;
+  TrackArgs trk_args = {};
+  bool trk_valid = false, trk_bal = false;
   PinnedStage up;              // pinned arena of a window-sized problem's uploads (ba_set_problem: one copy, k_unpack_problem)
   char* h_small = nullptr;     // k_small_lm's results, host-mapped: ba_summary | int cur | trace records
   char* d_small_host = nullptr;
@@ -1457,6 +1464,7 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
   clear_held(h);                     // a new problem starts with nothing held beyond its fixed camera
   clear_priors(h);                   // ... and without priors
   clear_shared(h);                   // ... and every camera with its own intrinsics
+  h->trk_valid = false;
   {   // index ranges, before anything is touched (a rejected call keeps the previous problem): branch-free sweep first
     int ok = 1;
     for (int64_t i = 0; i < n_obs; ++i)
@@ -3327,10 +3335,91 @@ extern "C" int ba_get_trace(ba_handle* h, ba_iter_record* out, int32_t capacity,
   return BA_OK;
 }
 
+// ------------------------------------------------------------------------------------------------- tracks
+// ba_triangulate_tracks (csrc/ba_tracks.hpp): camera centres, the short-track launch over every point slot, the long-track
+// launch over long_pts, results back in the caller's point order.  Local to the rank: no collective.
+static void launch_tracks(ba_handle* h) {
+  h->trk_args.cs = h->cs[h->cur].p;
+  const TrackArgs& a = h->trk_args;
+  BA_LAUNCH(k_track_centres, dim3((h->Nc + 255) / 256), dim3(256), 0, h->stream, a.cs, h->Nc, h->trk_ctr.p);
+  if (h->Np == 0) return;
+  const int tpb = TRK_THREADS / TRK_G;
+  if (h->trk_bal) BA_LAUNCH(k_tracks_short<BalCam>, dim3((h->Np + tpb - 1) / tpb), dim3(TRK_THREADS), 0, h->stream, a);
+  else BA_LAUNCH(k_tracks_short<Pinhole>, dim3((h->Np + tpb - 1) / tpb), dim3(TRK_THREADS), 0, h->stream, a);
+  if (h->n_long > 0) {
+    TrackArgs b = a;
+    b.list = h->long_pts.p; b.n_items = h->n_long;
+    if (h->trk_bal) BA_LAUNCH(k_tracks_long<BalCam>, dim3(h->n_long), dim3(64), 0, h->stream, b);
+    else BA_LAUNCH(k_tracks_long<Pinhole>, dim3(h->n_long), dim3(64), 0, h->stream, b);
+  }
+}
+extern "C" int ba_default_track_options(ba_track_options* o) {
+  if (!o) return fail(BA_ERR_INVALID, "null argument");
+  memset(o, 0, sizeof *o);
+  o->loss = BA_LOSS_LINEAR;
+  o->refine_iters = 20;
+  o->f_scale = 1.0;
+  return BA_OK;
+}
+extern "C" int ba_triangulate_tracks(ba_handle* h, const double* intr, const ba_track_options* opts, double* xyz, uint8_t* status,
+                                     double* angle_deg, double* rms_px, double* max_px) {
+  if (!h || !opts) return fail(BA_ERR_INVALID, "null argument");
+  if (!h->have_problem || !h->have_params) return fail(BA_ERR_STATE, "ba_triangulate_tracks: ba_set_problem / ba_set_params first");
+  if (!loss_valid(opts->loss)) return fail(BA_ERR_INVALID, "ba_triangulate_tracks: unknown loss %d", opts->loss);
+  if (!(opts->f_scale > 0)) return fail(BA_ERR_INVALID, "ba_triangulate_tracks: f_scale must be positive");
+  if (opts->refine_iters < 0) return fail(BA_ERR_INVALID, "ba_triangulate_tracks: refine_iters must not be negative");
+  if (opts->reserved0 != 0) return fail(BA_ERR_INVALID, "ba_triangulate_tracks: reserved0 must be 0");
+  if (set_device(h)) return BA_ERR_HIP;
+  const int Nc = h->Nc, Np = h->Np;
+  const size_t np1 = (size_t)std::max(Np, 1);
+  HIPCHECK(h->trk_out.alloc(TRK_OUT * np1)); HIPCHECK(h->trk_ctr.alloc(4 * (size_t)Nc)); HIPCHECK(h->trk_res.alloc(6 * np1));
+  HIPCHECK(h->trk_status.alloc(np1));
+  if (intr) {
+    HIPCHECK(h->trk_intr.alloc(3 * (size_t)Nc));
+    HIPCHECK(hipMemcpyAsync(h->trk_intr.p, intr, 3 * (size_t)Nc * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  }
+  TrackArgs& a = h->trk_args;
+  a.cs = h->cs[h->cur].p; a.intr = intr ? h->trk_intr.p : nullptr; a.ctr = h->trk_ctr.p;
+  a.pt_off = h->pt_off.p; a.p_cam = h->p_cam.p; a.uv = uv_arr(h, h->p_uv);
+  a.list = nullptr; a.n_items = Np; a.thr = h->n_long > 0 ? h->long_thr : 0x7fffffff;
+  a.fx = h->K4[0]; a.fy = h->K4[1]; a.cx = h->K4[2]; a.cy = h->K4[3];
+  a.loss = opts->loss; a.iters = opts->refine_iters;
+  a.fscale = opts->f_scale; a.min_angle = opts->min_angle_deg; a.max_px = opts->max_reproj_px; a.min_depth = opts->min_depth;
+  a.out = h->trk_out.p;
+  h->trk_bal = intr != nullptr;
+  h->trk_valid = true;
+  launch_tracks(h);
+  if (Np > 0) {
+    BA_LAUNCH(k_tracks_unpermute, dim3((Np + 255) / 256), dim3(256), 0, h->stream, (const double*)h->trk_out.p, (const int*)h->slot.p, Np,
+              h->trk_res.p, h->trk_res.p + 3 * (size_t)Np, h->trk_status.p);
+    if (xyz) HIPCHECK(hipMemcpyAsync(xyz, h->trk_res.p, 3 * (size_t)Np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    double* const meas[3] = {angle_deg, rms_px, max_px};
+    for (int q = 0; q < 3; ++q)
+      if (meas[q]) HIPCHECK(hipMemcpyAsync(meas[q], h->trk_res.p + (3 + q) * (size_t)Np, (size_t)Np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (status) HIPCHECK(hipMemcpyAsync(status, h->trk_status.p, (size_t)Np, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (opts->write_points) {
+    // what ba_set_params(cameras as they are, merged points) leaves behind: parameter set 0 current, the point table
+    // rebuilt, the camera state recomputed from the same rvec | t, the linearisation forgotten
+    if (Np > 0)
+      BA_LAUNCH(k_tracks_merge, dim3((Np + 255) / 256), dim3(256), 0, h->stream, (const double*)h->trk_out.p, pt_held_ptr(h),
+                (const double*)h->ptab[h->cur].p, Np, h->ptab[0].p);
+    if (h->cur != 0)
+      HIPCHECK(hipMemcpyAsync(h->cams[0].p, h->cams[h->cur].p, 6 * (size_t)Nc * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    h->cur = 0;
+    BA_LAUNCH(k_cam_prepare<Pinhole>, dim3((Nc + 63) / 64), dim3(64), 0, h->stream, h->cams[0].p, (const double*)h->intr[0].p,
+              h->cs[0].p, h->camA[0].p, Nc);
+    h->linearized = false;
+  }
+  BA_SYNC(h);
+  return BA_OK;
+}
+
 // ------------------------------------------------------------------------ bench hook
 extern "C" int ba_time_kernel(ba_handle* h, int slot, int reps, double* mean_us) {
   if (!h || !mean_us || reps < 1) return fail(BA_ERR_INVALID, "bad argument");
   if (!h->have_params) return fail(BA_ERR_STATE, "no parameters set");
+  if (slot == BA_K_TRACKS && !h->trk_valid) return fail(BA_ERR_STATE, "BA_K_TRACKS repeats the last ba_triangulate_tracks: call it first");
   if (set_device(h)) return BA_ERR_HIP;
   const bool saved = h->profile;
   h->profile = false;
@@ -3354,6 +3443,7 @@ extern "C" int ba_time_kernel(ba_handle* h, int slot, int reps, double* mean_us)
       case BA_K_SCHUR_CAM: launch_cam_schur(h, robust, false, false, 0, 0.0, 0); break;
       case BA_K_PRECOND: launch_cam_schur(h, robust, true, false, 0, 0.0, 0); break;
       case BA_K_POINT_INVERT: launch_point_invert(h, 1e-4); break;
+      case BA_K_TRACKS: launch_tracks(h); break;
       default: break;
     }
   };

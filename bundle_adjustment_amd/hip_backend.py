@@ -78,6 +78,14 @@ class BAProfile(C.Structure):
                 ("working_launches", C.c_int32 * PROFILE_SLOTS), ("working_ms", C.c_double * PROFILE_SLOTS)]
 
 
+class BATrackOptions(C.Structure):
+    _fields_ = [("loss", C.c_int32), ("refine_iters", C.c_int32), ("f_scale", C.c_double), ("min_angle_deg", C.c_double),
+                ("max_reproj_px", C.c_double), ("min_depth", C.c_double), ("write_points", C.c_int32), ("reserved0", C.c_int32)]
+
+
+TRACK_STATUS = {"ok": 0, "few_views": 1, "degenerate": 2, "behind": 3, "low_angle": 4, "high_error": 5}   # enum ba_track_status
+K_TRACKS = 13
+
 _lib = None
 
 # name -> (restype, argtypes); every symbol include/ba_hip.h declares
@@ -115,6 +123,8 @@ SYMBOLS = {
     "ba_reset_profile": (C.c_int, [C.c_void_p]),
     "ba_time_kernel": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _DP]),
     "ba_triangulate": (C.c_int, [C.c_void_p, _DP, _DP, _DP, C.c_int64, _DP, _DP, _DP, C.POINTER(C.c_uint8)]),
+    "ba_default_track_options": (C.c_int, [C.POINTER(BATrackOptions)]),
+    "ba_triangulate_tracks": (C.c_int, [C.c_void_p, _DP, C.POINTER(BATrackOptions), _DP, C.POINTER(C.c_uint8), _DP, _DP, _DP]),
     "ba_get_trace": (C.c_int, [C.c_void_p, C.POINTER(BAIterRecord), C.c_int32, C.POINTER(C.c_int32)]),
     "ba_get_stat": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
     "ba_debug_occupy": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double]),
@@ -539,6 +549,39 @@ class Solver:
         _check(self._lib.ba_triangulate(self._h, _dp(K), _dp(R), _dp(t), n, _dp(p1), _dp(p2), _dp(xyz),
                                         valid.ctypes.data_as(C.POINTER(C.c_uint8))))
         return xyz, valid.astype(bool)
+
+    def track_options(self, **kw) -> BATrackOptions:
+        """ba_default_track_options overlaid with kw (loss by name or by value, any other ba_track_options field)."""
+        o = BATrackOptions()
+        _check(self._lib.ba_default_track_options(C.byref(o)))
+        for k, v in kw.items():
+            if k == "loss":
+                v = loss_code(v)
+            if not hasattr(o, k):
+                raise TypeError(f"unknown option {k}")
+            setattr(o, k, v)
+        return o
+
+    def triangulate_tracks(self, intr=None, want=True, **opts):
+        """ba_triangulate_tracks: every point of the resident problem triangulated from all of its observations and the
+        current cameras (intr None: pinhole; else (Nc, 3) (f, k1, k2) of the BAL camera), refined, measured and classified.
+        opts: loss, refine_iters, f_scale, min_angle_deg, max_reproj_px, min_depth, write_points.  Returns dict(xyz (Np, 3),
+        status (Np,) uint8 (TRACK_STATUS), angle_deg, rms_px, max_px (Np,)), the caller's point order; want=False asks for no
+        output arrays (timing, or write_points alone) and returns None."""
+        ip = None
+        if intr is not None:
+            intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
+            ip = _dp(intr)
+        o = self.track_options(**opts)
+        if not want:
+            _check(self._lib.ba_triangulate_tracks(self._h, ip, C.byref(o), None, None, None, None, None))
+            return None
+        n = self.n_pts
+        out = dict(xyz=np.empty((n, 3)), status=np.empty(n, dtype=np.uint8), angle_deg=np.empty(n), rms_px=np.empty(n),
+                   max_px=np.empty(n))
+        _check(self._lib.ba_triangulate_tracks(self._h, ip, C.byref(o), _dp(out["xyz"]), out["status"].ctypes.data_as(C.POINTER(C.c_uint8)),
+                                               _dp(out["angle_deg"]), _dp(out["rms_px"]), _dp(out["max_px"])))
+        return out
 
     def trace(self):
         """Per-iteration records of the last solve (ba_get_trace): list of dicts."""

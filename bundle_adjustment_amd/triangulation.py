@@ -6,6 +6,11 @@ Mirrors ``VisualOdometryPipeline._triangulate_points`` (``src/pipeline.py:315-33
 split of a keyframe's inlier matches into re-observations and new points (``src/pipeline.py:248-282``) as array code.
 ``cv2.triangulatePoints`` is restated from OpenCV's published DLT; the sign of its singular vector is fixed as
 ``w >= 0`` (parity unpinned at the cv2 boundary).  No CPU fallback: without the library / a GPU the call raises.
+
+``triangulate_tracks`` is the N-view step between two adjustments (``ba_triangulate_tracks``: every point from all of its
+observations and the problem's cameras, refined, with triangulation angle, reprojection errors and a status), and
+``filter_tracks`` the host-side bookkeeping that drops the rejected points: together the loop
+*solve -> triangulate -> filter_tracks -> solve* of an SfM / SLAM pipeline.
 """
 from __future__ import annotations
 
@@ -55,3 +60,49 @@ def split_reobservations(last_kf_observations, query_idx, train_idx):
     pos_c = np.minimum(pos, kp_u.size - 1)
     hit = kp_u[pos_c] == q
     return hit, np.where(hit, mp_u[pos_c], -1)
+
+
+def triangulate_tracks(prob, solver=None, write=False, **opts):
+    """Triangulate every point of a ``BAProblem`` from all of its observations and ``prob.cams`` (``ba_triangulate_tracks``;
+    opts as ``hip_backend.Solver.triangulate_tracks``: loss, refine_iters, f_scale, min_angle_deg, max_reproj_px, min_depth).
+    Returns dict(xyz, status, angle_deg, rms_px, max_px) in ``prob``'s point order; with ``write=True`` also a copy of
+    ``prob`` whose OK points that are not held carry the triangulated positions.  ``solver``: a ``hip_backend.Solver`` to
+    upload into (its resident problem is replaced); default: one on device 0 for the call."""
+    import dataclasses
+    own = solver is None
+    s = hip_backend.Solver(0) if own else solver
+    try:
+        s.set_problem(prob)
+        out = s.triangulate_tracks(write_points=int(bool(write)), **opts)
+        pts = s.get_params()[1] if write else None
+    finally:
+        if own:
+            s.close()
+    if not write:
+        return out
+    return out, dataclasses.replace(prob, pts=pts)
+
+
+def filter_tracks(prob, keep):
+    """Drop the points where ``keep`` (bool (Np,)) is false together with their observations and renumber ``pt_idx``; the
+    remaining observations keep their order.  ``prob``: a ``BAProblem`` or a ``bal.BALProblem``.  Returns
+    ``(new_problem, old_index_of_new_point)``.  Held flags and point priors given as arrays follow their points; a dict of
+    point priors is re-keyed.  Pure numpy."""
+    import dataclasses
+    keep = np.asarray(keep)
+    if keep.dtype != np.bool_ or keep.shape != (prob.n_pts,):
+        raise ValueError(f"keep must be a bool array of shape ({prob.n_pts},), not {keep.dtype} {keep.shape}")
+    old = np.nonzero(keep)[0]
+    new_of_old = np.full(prob.n_pts, -1, dtype=np.int64)
+    new_of_old[old] = np.arange(old.size)
+    sel = keep[prob.pt_idx]
+    changes = dict(pts=prob.pts[old].copy(), cam_idx=prob.cam_idx[sel].copy(),
+                   pt_idx=new_of_old[prob.pt_idx[sel]].astype(np.int32), uv=prob.uv[sel].copy())
+    if getattr(prob, "pt_held", None) is not None:
+        changes["pt_held"] = np.asarray(prob.pt_held)[old].copy()
+    prior = getattr(prob, "pt_prior", None)
+    if isinstance(prior, dict):
+        changes["pt_prior"] = {int(new_of_old[i]): v for i, v in prior.items() if keep[i]}
+    elif prior is not None:
+        changes["pt_prior"] = tuple(np.asarray(a)[old].copy() for a in prior)
+    return dataclasses.replace(prob, **changes), old

@@ -142,7 +142,8 @@ enum ba_kernel_slot {
   BA_K_CAM_PREPARE = 0, BA_K_RESIDUAL = 1, BA_K_LINEARIZE_CAM = 2, BA_K_LINEARIZE_PT = 3,
   BA_K_POINT_INVERT = 4, BA_K_SCHUR_PT = 5, BA_K_SCHUR_CAM = 6, BA_K_PCG_UPDATE = 7,
   BA_K_PRECOND = 8, BA_K_BACKSUB = 9, BA_K_MISC = 10, BA_K_ALLREDUCE = 11,
-  BA_K_SCHUR_PT_BACKSUB = 12   /* launches of the PCG point pass that found PCG finished and went on as the back substitution */
+  BA_K_SCHUR_PT_BACKSUB = 12,  /* launches of the PCG point pass that found PCG finished and went on as the back substitution */
+  BA_K_TRACKS = 13             /* ba_time_kernel only: the kernels of the last ba_triangulate_tracks call, with its options */
 };
 
 /* Event counters of a handle (ba_get_stat): which implementation served the window-sized solves, how often the
@@ -187,6 +188,50 @@ int ba_debug_layout(ba_handle* h, int32_t which, void* out, int64_t capacity, in
  * Needs no ba_set_problem. */
 int ba_triangulate(ba_handle* h, const double K[9], const double R_rel[9], const double t_rel[3], int64_t n,
                    const double* pts1, const double* pts2, double* xyz, uint8_t* valid);
+/* N-view triangulation and filtering of whole tracks: the step between two adjustments of an SfM / SLAM loop (adjust ->
+ * re-triangulate -> filter by angle, depth and reprojection error -> adjust; COLMAP's Retriangulate / FilterPoints3D, the point
+ * culling of OpenMVG and ORB-SLAM; no reference counterpart: src/pipeline.py only triangulates pairs, see ba_triangulate).
+ * Every point is triangulated from ALL of its observations and the handle's CURRENT cameras, which are treated as known:
+ * held masks, fixed_cam, priors and shared-intrinsics groups play no part, and the handle's points are not read.
+ *   intr   NULL: the pinhole with the handle's K4; else (f, k1, k2)[Nc] of the BAL camera, as in ba_residuals_bal
+ *   xyz double[Np][3], status uint8[Np] (ba_track_status), angle_deg, rms_px, max_px double[Np]: the caller's point order;
+ *   any may be NULL
+ * Per point: (1) bearings -- pinhole ((u - cx) / fx, (v - cy) / fy, 1); BAL: the radial model inverted by Newton (r_d = |uv| / f,
+ * r (1 + k1 r^2 + k2 r^4) = r_d from r = r_d; at most 25 steps to |dr| <= 1e-15 r; no convergence or a derivative <= 0 on the
+ * way makes the track DEGENERATE), ray (p0, p1, -1).  (2) The homogeneous N-view DLT on the rows x (R2 X + t2) - (R0 X + t0),
+ * y (R2 X + t2) - (R1 X + t1), centred on the mean camera centre of the track's observations, through the ten fp64 sums of
+ * A^T A and a 4 x 4 Jacobi eigen-solve, w >= 0; |w| <= 1e-12 |X_h| or a non-finite entry: DEGENERATE.  (3) At most refine_iters
+ * Marquardt-damped Gauss-Newton steps on the track's own cost 0.5 sum f_scale^2 rho((r / f_scale)^2) (IRLS with the weights
+ * the solve uses; damping from 1e-4, / 10 after a step that does not raise the cost, * 10 after one that does, which is
+ * dropped but counted; "does not raise" is cost_trial <= cost (1 + 1e-12), the rounding of the two sums; stop at
+ * |dx| <= 1e-14 |X|); a 3 x 3 matrix that is not positive definite: DEGENERATE.  (4) At the final
+ * point: angle_deg, the largest angle over all pairs of views between the unit vectors from the point to the two camera
+ * centres (COLMAP's triangulation angle); rms_px = sqrt(sum |r_i|^2 / n_obs); max_px = the largest |r_i|.  (5) status = the first
+ * failing test in enum order: FEW_VIEWS fewer than two DISTINCT cameras (no observation, one, or several by one camera: xyz and
+ * the measures are NaN); DEGENERATE as above (found in (1) or (2): xyz and the measures are NaN; in (3): the last accepted point
+ * and its measures); BEHIND a view with depth <= min_depth; LOW_ANGLE angle_deg < min_angle_deg; HIGH_ERROR max_px >
+ * max_reproj_px.  For BEHIND, LOW_ANGLE, HIGH_ERROR and OK xyz and the measures are written.
+ * write_points = 1 stores xyz of the OK points that are NOT held (ba_set_held) into the handle's current points, as if
+ * ba_set_params had been called with the current cameras and the merged points (the linearisation is forgotten; masks,
+ * priors, groups stay); write_points = 0 leaves the handle exactly as found.
+ * BA_ERR_STATE before ba_set_problem / ba_set_params; BA_ERR_INVALID for an unknown loss, f_scale <= 0, refine_iters < 0,
+ * reserved0 != 0.  Multi-rank jobs: the call is local to the calling rank's shard (its points, all cameras), no collective;
+ * untested on more than one rank. */
+enum ba_track_status { BA_TRACK_OK = 0, BA_TRACK_FEW_VIEWS = 1, BA_TRACK_DEGENERATE = 2,
+                       BA_TRACK_BEHIND = 3, BA_TRACK_LOW_ANGLE = 4, BA_TRACK_HIGH_ERROR = 5 };
+typedef struct ba_track_options {
+  int32_t loss;            /* ba_loss of the refinement */
+  int32_t refine_iters;    /* most damped Gauss-Newton steps; 0 = the linear solution only */
+  double f_scale;
+  double min_angle_deg;    /* <= 0: no test */
+  double max_reproj_px;    /* <= 0: no test; compared with the track's LARGEST per-observation error */
+  double min_depth;        /* a view fails when depth <= min_depth */
+  int32_t write_points;
+  int32_t reserved0;       /* must be 0 */
+} ba_track_options;
+int ba_default_track_options(ba_track_options* opts);   /* linear, 20, 1.0, 0, 0, 0.0, 0 */
+int ba_triangulate_tracks(ba_handle* h, const double* intr, const ba_track_options* opts, double* xyz, uint8_t* status,
+                          double* angle_deg, double* rms_px, double* max_px);
 /* Copies up to `capacity` records of the last ba_solve into out (may be NULL to ask for the count only);
  * *n = number of LM iterations recorded. */
 int ba_get_trace(ba_handle* h, ba_iter_record* out, int32_t capacity, int32_t* n);
@@ -387,7 +432,8 @@ int ba_get_profile(ba_handle* h, ba_profile* out);
 int ba_reset_profile(ba_handle* h);
 
 /* Bench hook: run one kernel `reps` times back to back on the solver stream between two
- * HIP events and return the mean duration in microseconds (state left as it was). */
+ * HIP events and return the mean duration in microseconds (state left as it was).  BA_K_TRACKS: every kernel of the last
+ * ba_triangulate_tracks call (BA_ERR_STATE without one since ba_set_problem), at the current cameras. */
 int ba_time_kernel(ba_handle* h, int slot, int reps, double* mean_us);
 
 #ifdef __cplusplus

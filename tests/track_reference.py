@@ -1,0 +1,255 @@
+"""numpy restatement of ba_triangulate_tracks (include/ba_hip.h), one point at a time: the yardstick of the track tests.
+
+Steps as in the header: (1) bearings, (2) N-view DLT centred on the track's mean camera centre through A^T A and a cyclic
+Jacobi eigen-solve, (3) Marquardt-damped Gauss-Newton with IRLS weights, (4) angle / rms / max at the final point,
+(5) status = first failing test in enum order.  Camera conventions: pinhole ``K4 = (fx, fy, cx, cy)``, camera looking down
++z; BAL ``intr = (f, k1, k2)`` per camera, looking down -z, pixels relative to the image centre.
+"""
+import numpy as np
+
+from bundle_adjustment_amd.rotations import rvecs_to_matrices
+
+OK, FEW_VIEWS, DEGENERATE, BEHIND, LOW_ANGLE, HIGH_ERROR = range(6)
+NEWTON_ITERS = 25
+COST_SLACK = 1e-12      # a step "does not raise the cost" within the rounding of the two sums
+
+
+def bal_undistort(uv, f, k1, k2):
+    """Invert r_d = r (1 + k1 r^2 + k2 r^4) by Newton from r = r_d: -> (p0, p1, ok) with uv = f rad(|p|) p."""
+    qx, qy = uv[0] / f, uv[1] / f
+    rd = np.sqrt(qx * qx + qy * qy)
+    r, ok = rd, False
+    for _ in range(NEWTON_ITERS):
+        r2 = r * r
+        dF = 1.0 + r2 * (3.0 * k1 + 5.0 * k2 * r2)
+        if not dF > 0.0:
+            break
+        dr = (r * (1.0 + r2 * (k1 + k2 * r2)) - rd) / dF
+        r -= dr
+        if abs(dr) <= 1e-15 * abs(r):
+            ok = True
+            break
+    r2 = r * r
+    ok = ok and (1.0 + r2 * (3.0 * k1 + 5.0 * k2 * r2) > 0.0) and r >= 0.0
+    sc = r / rd if rd > 0.0 else 1.0
+    return qx * sc, qy * sc, ok
+
+
+def jacobi_eig4(M):
+    """Cyclic Jacobi on a symmetric 4 x 4, the device's rotation order and stopping rule: (eigenvalues, eigenvectors)."""
+    A = np.array(M, dtype=np.float64)
+    V = np.eye(4)
+    for _ in range(16):
+        rotated = False
+        for p in range(3):
+            for q in range(p + 1, 4):
+                apq = A[p, q]
+                if not abs(apq) > 1e-17 * np.sqrt(abs(A[p, p] * A[q, q])):
+                    continue
+                rotated = True
+                zeta = (A[q, q] - A[p, p]) / (2.0 * apq)
+                t = (1.0 if zeta >= 0.0 else -1.0) / (abs(zeta) + np.sqrt(zeta * zeta + 1.0))
+                c = 1.0 / np.sqrt(t * t + 1.0)
+                s = t * c
+                J = np.eye(4)
+                J[p, p] = c; J[q, q] = c; J[p, q] = s; J[q, p] = -s
+                A = J.T @ (A @ J)
+                V = V @ J
+        if not rotated:
+            break
+    return np.diag(A).copy(), V
+
+
+def loss_terms(loss, f, C):
+    """(C^2 rho((f / C)^2), rho') per scalar residual: scipy least_squares' losses, the weights of the solve."""
+    f = np.asarray(f, dtype=np.float64)
+    if loss == "linear":
+        return f * f, np.ones_like(f)
+    a = np.abs(f)
+    if loss == "huber":
+        inl = a <= C
+        return np.where(inl, f * f, 2.0 * C * a - C * C), np.where(inl, 1.0, C / np.where(a > 0, a, 1.0))
+    z = (f / C) ** 2
+    if loss == "soft_l1":
+        return C * C * 2.0 * z / (np.sqrt(1.0 + z) + 1.0), 1.0 / np.sqrt(1.0 + z)
+    if loss == "cauchy":
+        return C * C * np.log1p(z), 1.0 / (1.0 + z)
+    if loss == "arctan":
+        return C * C * np.arctan(z), 1.0 / (1.0 + z * z)
+    raise ValueError(loss)
+
+
+class Views:
+    """The observations of one track: rotations (n, 3, 3), translations (n, 3), pixels (n, 2), camera indices, model."""
+
+    def __init__(self, R, t, uv, cam, K4=None, intr=None):
+        self.R, self.t, self.uv, self.cam, self.K4, self.intr = R, t, uv, cam, K4, intr
+        self.centres = -np.einsum("nji,nj->ni", R, t)
+
+    def bearings(self):
+        """-> (xy (n, 2) with the ray (x, y, 1) up to sign, all_ok)."""
+        if self.intr is None:
+            fx, fy, cx, cy = self.K4
+            return np.stack([(self.uv[:, 0] - cx) / fx, (self.uv[:, 1] - cy) / fy], axis=1), True
+        xy, ok = np.empty_like(self.uv), True
+        for i in range(len(self.uv)):
+            p0, p1, good = bal_undistort(self.uv[i], *self.intr[i])
+            xy[i] = (-p0, -p1)
+            ok = ok and good
+        return xy, ok
+
+    def project(self, X):
+        """-> (residuals (n, 2), Pm (n, 2, 3) = -d residual / d X, depth (n,))."""
+        P = self.R @ X + self.t
+        z = np.where(P[:, 2] != 0.0, P[:, 2], 1.0)
+        n = len(P)
+        D = np.zeros((n, 2, 3))
+        if self.intr is None:
+            fx, fy, cx, cy = self.K4
+            xh, yh = P[:, 0] / z, P[:, 1] / z
+            r = self.uv - np.stack([xh * fx + cx, yh * fy + cy], axis=1)
+            D[:, 0, 0] = fx / z; D[:, 0, 2] = -fx * xh / z
+            D[:, 1, 1] = fy / z; D[:, 1, 2] = -fy * yh / z
+            depth = P[:, 2]
+        else:
+            f, k1, k2 = self.intr.T
+            p = -P[:, :2] / z[:, None]
+            n2 = (p * p).sum(axis=1)
+            rad = 1.0 + n2 * (k1 + k2 * n2)
+            drad = k1 + 2.0 * k2 * n2
+            r = self.uv - (f * rad)[:, None] * p
+            # d proj / d p = f (rad I + 2 drad p p^T); d p / d P = -1/z [I | p]
+            dpp = f[:, None, None] * (rad[:, None, None] * np.eye(2) + 2.0 * drad[:, None, None] * p[:, :, None] * p[:, None, :])
+            dpP = np.zeros((n, 2, 3))
+            dpP[:, 0, 0] = 1.0; dpP[:, 1, 1] = 1.0; dpP[:, :, 2] = p
+            D = dpp @ (-dpP / z[:, None, None])
+            depth = -P[:, 2]
+        return r, D @ self.R, depth
+
+
+def dlt(v, xy, method="jacobi"):
+    """Centred homogeneous DLT: -> (X or None, X_h).  method 'jacobi' (A^T A + Jacobi, the device's), 'svd' (LAPACK on A)."""
+    Cm = v.centres.sum(axis=0) / len(xy)
+    rows = np.empty((2 * len(xy), 4))
+    for r in range(2):
+        a = xy[:, r, None] * v.R[:, 2, :] - v.R[:, r, :]
+        rows[r::2, :3] = a
+        rows[r::2, 3] = (xy[:, r] * v.t[:, 2] - v.t[:, r]) + a @ Cm
+    if method == "svd":
+        Xh = np.linalg.svd(rows)[2][-1]
+    else:
+        lam, V = jacobi_eig4(rows.T @ rows)
+        Xh = V[:, int(np.argmin(lam))]
+    if Xh[3] < 0.0:
+        Xh = -Xh
+    nrm = np.sqrt((Xh * Xh).sum())
+    if not np.isfinite(nrm) or not Xh[3] > 1e-12 * nrm:
+        return None, Xh
+    return Cm + Xh[:3] / Xh[3], Xh
+
+
+def sums_at(v, X, loss, f_scale, min_depth):
+    r, Pm, depth = v.project(X)
+    term, w = loss_terms(loss, r, f_scale)
+    H = np.einsum("nri,nr,nrj->ij", Pm, w, Pm)
+    g = -np.einsum("nri,nr->i", Pm, w * r)
+    e2 = (r * r).sum(axis=1)
+    return dict(H=H, g=g, cost=term.sum(), sse=e2.sum(), max2=e2.max(), behind=int((~(depth > min_depth)).sum()))
+
+
+def refine(v, X, loss="linear", f_scale=1.0, iters=20, min_depth=0.0):
+    """-> (X, sums at X, degenerate)."""
+    cur = sums_at(v, X, loss, f_scale, min_depth)
+    lam = 1e-4
+    for _ in range(iters):
+        Hd = cur["H"] + lam * np.diag(np.diag(cur["H"]))
+        try:
+            with np.errstate(all="ignore"):
+                if not np.all(np.isfinite(Hd)):
+                    raise np.linalg.LinAlgError
+                L = np.linalg.cholesky(Hd)
+        except np.linalg.LinAlgError:
+            return X, cur, True
+        dx = -np.linalg.solve(L.T, np.linalg.solve(L, cur["g"]))
+        Xt = X + dx
+        small = np.sqrt((dx * dx).sum()) <= 1e-14 * np.sqrt((X * X).sum())
+        trial = sums_at(v, Xt, loss, f_scale, min_depth)
+        if trial["cost"] <= cur["cost"] * (1.0 + COST_SLACK):
+            X, cur, lam = Xt, trial, max(0.1 * lam, 1e-12)
+        else:
+            lam *= 10.0
+        if small:
+            break
+    return X, cur, False
+
+
+def max_angle_deg(centres, X):
+    u = centres - X
+    u = u / np.sqrt((u * u).sum(axis=1))[:, None]
+    d = u[:, None, :] - u[None, :, :]
+    d2 = float((d * d).sum(axis=2).max())
+    return 2.0 * np.arctan2(np.sqrt(d2), np.sqrt(max(4.0 - d2, 0.0))) * (180.0 / np.pi)
+
+
+def measures_at(v, X, min_depth=0.0):
+    """(angle_deg, rms_px, max_px, views behind) at X."""
+    s = sums_at(v, X, "linear", 1.0, min_depth)
+    return max_angle_deg(v.centres, X), np.sqrt(s["sse"] / len(v.uv)), np.sqrt(s["max2"]), s["behind"]
+
+
+def track(v, loss="linear", f_scale=1.0, refine_iters=20, min_angle_deg=0.0, max_reproj_px=0.0, min_depth=0.0, x0=None,
+          dlt_method="jacobi"):
+    """One track: dict(xyz, status, angle_deg, rms_px, max_px).  x0: start the refinement there instead of at the DLT."""
+    nan3 = np.full(3, np.nan)
+    bad = dict(xyz=nan3, angle_deg=np.nan, rms_px=np.nan, max_px=np.nan)
+    if len(v.uv) == 0 or np.all(v.cam == v.cam[0]):
+        return dict(bad, status=FEW_VIEWS)
+    xy, ok = v.bearings()
+    X, _ = dlt(v, xy, dlt_method)
+    if not ok or X is None:
+        return dict(bad, status=DEGENERATE)
+    if x0 is not None:
+        X = np.asarray(x0, dtype=np.float64)
+    X, cur, degenerate = refine(v, X, loss, f_scale, refine_iters, min_depth)
+    angle = max_angle_deg(v.centres, X)
+    rms, emax = np.sqrt(cur["sse"] / len(v.uv)), np.sqrt(cur["max2"])
+    status = OK
+    if degenerate:
+        status = DEGENERATE
+    elif cur["behind"] > 0:
+        status = BEHIND
+    elif min_angle_deg > 0.0 and angle < min_angle_deg:
+        status = LOW_ANGLE
+    elif max_reproj_px > 0.0 and emax > max_reproj_px:
+        status = HIGH_ERROR
+    return dict(xyz=X, status=status, angle_deg=angle, rms_px=rms, max_px=emax)
+
+
+def views_of(prob, p, R=None, order=None):
+    """The Views of point p of a BAProblem (pinhole) or a BALProblem (cams (Nc, 9))."""
+    sel = np.nonzero(prob.pt_idx == p)[0] if order is None else order[p]
+    cam = prob.cam_idx[sel]
+    if R is None:
+        R = rvecs_to_matrices(prob.cams[:, :3])
+    if prob.cams.shape[1] == 9:
+        return Views(R[cam], prob.cams[cam, 3:6], prob.uv[sel], cam, intr=prob.cams[cam, 6:9])
+    return Views(R[cam], prob.cams[cam, 3:6], prob.uv[sel], cam, K4=np.asarray(prob.K4, dtype=np.float64))
+
+
+def observations_by_point(prob):
+    """List of observation index arrays per point (caller's observation order within a point)."""
+    order = np.argsort(prob.pt_idx, kind="stable")
+    counts = np.bincount(prob.pt_idx, minlength=prob.n_pts)
+    return np.split(order, np.cumsum(counts)[:-1])
+
+
+def triangulate_tracks(prob, points=None, **opts):
+    """Every point (or the listed ones) of a problem: dict of arrays xyz (n, 3), status, angle_deg, rms_px, max_px."""
+    R = rvecs_to_matrices(prob.cams[:, :3])
+    by_pt = observations_by_point(prob)
+    pts = range(prob.n_pts) if points is None else points
+    x0 = opts.pop("x0", None)
+    res = [track(views_of(prob, p, R, by_pt), x0=None if x0 is None else x0[p], **opts) for p in pts]
+    return dict(xyz=np.array([r["xyz"] for r in res]).reshape(-1, 3), status=np.array([r["status"] for r in res], dtype=np.uint8),
+                angle_deg=np.array([r["angle_deg"] for r in res]), rms_px=np.array([r["rms_px"] for r in res]),
+                max_px=np.array([r["max_px"] for r in res]))
