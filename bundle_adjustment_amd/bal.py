@@ -256,3 +256,18 @@ def triangulate(prob: BALProblem, device=0, write=False, **opts):
     if not write:
         return out
     return out, BALProblem(prob.cams.copy(), pts, prob.cam_idx.copy(), prob.pt_idx.copy(), prob.uv.copy())
+
+
+def align(prob: BALProblem, cam_ref=None, pt_ref=None, cam_w=None, pt_w=None, loss="linear", f_scale=1.0, iters=10,
+          with_scale=True, device=0):
+    """Align a BAL problem to reference positions: the similarity ``X' = s R X + t`` that brings its camera centres
+    (cam_ref (Nc, 3)) and / or points (pt_ref (Np, 3)) onto them, weighted and robust (``ba_align`` with apply = 1;
+    arguments as ``hip_backend.Solver.align``).  Returns ``(result dict, transformed BALProblem)``; f, k1, k2 are left
+    alone and every residual stays where it was.  When the status is not OK the problem comes back unchanged."""
+    from . import hip_backend
+    with hip_backend.Solver(device) as s:
+        intr = s._set_bal(prob)
+        res = s.align(cam_ref=cam_ref, pt_ref=pt_ref, cam_w=cam_w, pt_w=pt_w, loss=loss, f_scale=f_scale, iters=iters,
+                      with_scale=with_scale, apply=True)
+        cams6, pts = s.get_params()
+    return res, BALProblem(np.concatenate([cams6, intr], axis=1), pts, prob.cam_idx.copy(), prob.pt_idx.copy(), prob.uv.copy())

@@ -38,6 +38,7 @@
 #include "ba_setup.hpp"
 #include "ba_cov.hpp"
 #include "ba_tracks.hpp"
+#include "ba_similarity.hpp"
 
 using namespace ba;
 
@@ -264,6 +265,10 @@ struct ba_handle {
   DBuf<unsigned char> trk_status;
   TrackArgs trk_args = {};
   bool trk_valid = false, trk_bal = false;
+  // ba_transform / ba_align / ba_get_centres (ba_similarity.hpp): correspondences a | b | w | u | err (9 doubles each), the
+  // per-workgroup partial rows, the device record (similarity, centroids, status)
+  DBuf<double> sim_buf, sim_part;
+  DBuf<SimRec> sim_rec;
   PinnedStage up;              // pinned arena of a window-sized problem's uploads (ba_set_problem: one copy, k_unpack_problem)
   char* h_small = nullptr;     // k_small_lm's results, host-mapped: ba_summary | int cur | trace records
   char* d_small_host = nullptr;
@@ -3412,6 +3417,182 @@ extern "C" int ba_triangulate_tracks(ba_handle* h, const double* intr, const ba_
     h->linearized = false;
   }
   BA_SYNC(h);
+  return BA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- similarity
+// ba_get_centres, ba_transform, ba_align (csrc/ba_similarity.hpp).  Local to the rank: no collective.
+extern "C" int ba_get_centres(ba_handle* h, double* centres) {
+  if (!h || !centres) return fail(BA_ERR_INVALID, "null argument");
+  if (!h->have_problem || !h->have_params) return fail(BA_ERR_STATE, "ba_get_centres: ba_set_problem / ba_set_params first");
+  if (set_device(h)) return BA_ERR_HIP;
+  const int Nc = h->Nc;
+  HIPCHECK(h->sim_buf.alloc(3 * (size_t)Nc));
+  BA_LAUNCH(k_sim_centres, dim3((Nc + 255) / 256), dim3(256), 0, h->stream, (const double*)h->cs[h->cur].p, Nc, h->sim_buf.p);
+  HIPCHECK(hipMemcpyAsync(centres, h->sim_buf.p, 3 * (size_t)Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  BA_SYNC(h);
+  return BA_OK;
+}
+
+static const char* kSimPriors = "%s: priors are set (ba_set_priors) and their means live in the old frame: align first, set the priors afterwards";
+// What ba_set_params(transformed cameras, transformed points) leaves behind, from the similarity in the device record:
+// parameter set 0 written from set `cur`, its point table and camera state rebuilt.  A record that is not OK makes every
+// kernel a no-op.  The caller drains the stream, reads the record's status and, when it is OK, calls commit_transform
+// (set 0 current, the linearisation forgotten, held_x2 from held_pts, where the held points' new positions were copied).
+static int launch_transform(ba_handle* h, std::vector<double>* held_pts) {
+  const int Nc = h->Nc, Np = h->Np;
+  if (Np > 0)
+    BA_LAUNCH(k_sim_transform_points, dim3((Np + 255) / 256), dim3(256), 0, h->stream, (const SimRec*)h->sim_rec.p,
+              (const double*)h->ptab[h->cur].p, Np, h->ptab[0].p);
+  BA_LAUNCH(k_sim_transform_cams, dim3((Nc + 63) / 64), dim3(64), 0, h->stream, (const SimRec*)h->sim_rec.p,
+            (const double*)h->cs[h->cur].p, Nc, h->cams[0].p);
+  BA_LAUNCH(k_sim_cam_prepare, dim3((Nc + 63) / 64), dim3(64), 0, h->stream, (const SimRec*)h->sim_rec.p, (const double*)h->cams[0].p,
+            (const double*)h->intr[0].p, h->cs[0].p, h->camA[0].p, Nc);
+  if (h->any_pt_held && Np > 0) {
+    held_pts->resize(3 * (size_t)Np);
+    BA_LAUNCH(k_unpack_points, dim3((Np + 255) / 256), dim3(256), 0, h->stream, h->ptab[0].p, h->slot.p, Np, h->stage.p);
+    HIPCHECK(hipMemcpyAsync(held_pts->data(), h->stage.p, 3 * (size_t)Np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  return BA_OK;
+}
+static void commit_transform(ba_handle* h, const std::vector<double>& held_pts) {
+  h->cur = 0;
+  h->linearized = false;
+  if (!held_pts.empty()) h->held_x2 = held_points_x2(h, held_pts.data());
+}
+
+extern "C" int ba_transform(ba_handle* h, const ba_similarity* sim) {
+  if (!h || !sim) return fail(BA_ERR_INVALID, "null argument");
+  if (!h->have_problem || !h->have_params) return fail(BA_ERR_STATE, "ba_transform: ba_set_problem / ba_set_params first");
+  if (any_prior(h)) return fail(BA_ERR_STATE, kSimPriors, "ba_transform");
+  if (!std::isfinite(sim->s) || !(sim->s > 0)) return fail(BA_ERR_INVALID, "ba_transform: the scale s must be finite and positive");
+  for (int i = 0; i < 9; ++i) if (!std::isfinite(sim->R[i])) return fail(BA_ERR_INVALID, "ba_transform: R is not finite");
+  for (int i = 0; i < 3; ++i) if (!std::isfinite(sim->t[i])) return fail(BA_ERR_INVALID, "ba_transform: t is not finite");
+  const double* R = sim->R;
+  double dev = 0.0;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j)
+      dev = std::max(dev, std::fabs(R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1] + R[3 * i + 2] * R[3 * j + 2] - (i == j ? 1.0 : 0.0)));
+  if (!(dev <= 1e-9)) return fail(BA_ERR_INVALID, "ba_transform: R is not orthogonal (max |R R^T - I| = %.3g > 1e-9)", dev);
+  const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+  if (det < 0) return fail(BA_ERR_INVALID, "ba_transform: R is a reflection (det R = %.3g < 0)", det);
+  if (set_device(h)) return BA_ERR_HIP;
+  HIPCHECK(h->sim_rec.alloc(1));
+  SimRec rec = {};
+  rec.s = sim->s;
+  memcpy(rec.R, sim->R, sizeof rec.R);
+  memcpy(rec.t, sim->t, sizeof rec.t);
+  rec.status = SIM_OK;
+  BA_LAUNCH(k_sim_set, dim3(1), dim3(64), 0, h->stream, rec, h->sim_rec.p);
+  std::vector<double> held_pts;
+  if (int rc = launch_transform(h, &held_pts)) return rc;
+  BA_SYNC(h);
+  commit_transform(h, held_pts);
+  return BA_OK;
+}
+
+extern "C" int ba_default_align_options(ba_align_options* o) {
+  if (!o) return fail(BA_ERR_INVALID, "null argument");
+  memset(o, 0, sizeof *o);
+  o->loss = BA_LOSS_LINEAR;
+  o->iters = 10;
+  o->f_scale = 1.0;
+  o->with_scale = 1;
+  o->apply = 0;
+  return BA_OK;
+}
+
+extern "C" int ba_align(ba_handle* h, const ba_align_options* opts, const double* cam_ref, const double* cam_w, const double* pt_ref,
+                        const double* pt_w, ba_align_result* out, double* cam_err, double* pt_err) {
+  if (!h || !opts || !out) return fail(BA_ERR_INVALID, "null argument");
+  if (!h->have_problem || !h->have_params) return fail(BA_ERR_STATE, "ba_align: ba_set_problem / ba_set_params first");
+  if (!loss_valid(opts->loss)) return fail(BA_ERR_INVALID, "ba_align: unknown loss %d", opts->loss);
+  if (!(opts->f_scale > 0)) return fail(BA_ERR_INVALID, "ba_align: f_scale must be positive");
+  if (opts->iters < 0) return fail(BA_ERR_INVALID, "ba_align: iters must not be negative");
+  if (!cam_ref && !pt_ref) return fail(BA_ERR_INVALID, "ba_align: no reference positions (cam_ref and pt_ref are both NULL)");
+  if (opts->apply && any_prior(h)) return fail(BA_ERR_STATE, kSimPriors, "ba_align with apply = 1");
+  const int Nc = h->Nc, Np = h->Np;
+  const int n_cam = cam_ref ? Nc : 0, n_pt = pt_ref ? Np : 0;
+  const size_t n = (size_t)n_cam + (size_t)n_pt;
+  if (n > 0x7fffffffULL) return fail(BA_ERR_INVALID, "ba_align: too many correspondences");
+  // references and weights in correspondence order (cameras, then points); a row without a reference is uploaded as it is
+  // (it may hold NaN) and never enters a sum
+  std::vector<double> bw(4 * std::max<size_t>(n, 1));
+  double* hb = bw.data();
+  double* hw = hb + 3 * n;
+  int n_used = 0;
+  for (int part = 0; part < 2; ++part) {
+    const double* ref = part ? pt_ref : cam_ref;
+    const double* w = part ? pt_w : cam_w;
+    const int m = part ? n_pt : n_cam, off = part ? n_cam : 0;
+    if (!ref) continue;
+    memcpy(hb + 3 * (size_t)off, ref, 3 * (size_t)m * sizeof(double));
+    for (int i = 0; i < m; ++i) {
+      const double wi = w ? w[i] : 1.0;
+      if (!std::isfinite(wi) || wi < 0) return fail(BA_ERR_INVALID, "ba_align: %s weight %d is negative or not finite", part ? "point" : "camera", i);
+      hw[off + i] = wi;
+      n_used += wi > 0;
+    }
+  }
+  const double nan = std::nan("");
+  memset(out, 0, sizeof *out);
+  out->sim.s = 1.0;
+  out->sim.R[0] = out->sim.R[4] = out->sim.R[8] = 1.0;
+  out->rms = out->max = nan;
+  out->n_used = n_used;
+  if (n_used < 3) {
+    out->status = BA_ALIGN_TOO_FEW;
+    if (cam_err) for (int i = 0; i < n_cam; ++i) cam_err[i] = nan;
+    if (pt_err) for (int i = 0; i < n_pt; ++i) pt_err[i] = nan;
+    return BA_OK;
+  }
+  if (set_device(h)) return BA_ERR_HIP;
+  const int nn = (int)n;
+  const int nblk = std::min((nn + SIM_THREADS - 1) / SIM_THREADS, SIM_MAX_BLOCKS);      // from the correspondence count alone
+  HIPCHECK(h->sim_buf.alloc(9 * n));
+  HIPCHECK(h->sim_part.alloc((size_t)SIM_PART * SIM_MAX_BLOCKS));
+  HIPCHECK(h->sim_rec.alloc(1));
+  double* const a = h->sim_buf.p;
+  double* const b = a + 3 * n;
+  double* const w = b + 3 * n;
+  double* const u = w + n;
+  double* const err = u + n;
+  HIPCHECK(hipMemcpyAsync(b, hb, 4 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  SimRec rec = {};
+  rec.s = 1.0;
+  rec.R[0] = rec.R[4] = rec.R[8] = 1.0;
+  rec.status = SIM_OK;
+  BA_LAUNCH(k_sim_set, dim3(1), dim3(64), 0, h->stream, rec, h->sim_rec.p);
+  BA_LAUNCH(k_sim_gather, dim3((nn + 255) / 256), dim3(256), 0, h->stream, (const double*)h->cs[h->cur].p, n_cam,
+            (const double*)h->ptab[h->cur].p, (const int*)h->slot.p, n_pt, a);
+  // every round on the stream, no host synchronisation in between: the fold kernels leave the similarity and the status
+  // in the device record, which the next pass reads
+  const double inv_f2 = 1.0 / (opts->f_scale * opts->f_scale);
+  for (int round = 0; round <= opts->iters; ++round) {
+    BA_LAUNCH(k_sim_pass_a, dim3(nblk), dim3(SIM_THREADS), 0, h->stream, (const SimRec*)h->sim_rec.p, nn, (const double*)a,
+              (const double*)b, (const double*)w, round > 0 ? 1 : 0, (int)opts->loss, inv_f2, u, h->sim_part.p);
+    BA_LAUNCH(k_sim_centroid, dim3(1), dim3(64), 0, h->stream, (const double*)h->sim_part.p, nblk, h->sim_rec.p);
+    BA_LAUNCH(k_sim_pass_b, dim3(nblk), dim3(SIM_THREADS), 0, h->stream, (const SimRec*)h->sim_rec.p, nn, (const double*)a,
+              (const double*)b, (const double*)u, h->sim_part.p);
+    BA_LAUNCH(k_sim_solve, dim3(1), dim3(64), 0, h->stream, (const double*)h->sim_part.p, nblk, opts->with_scale ? 1 : 0, h->sim_rec.p);
+  }
+  BA_LAUNCH(k_sim_errors, dim3(nblk), dim3(SIM_THREADS), 0, h->stream, (const SimRec*)h->sim_rec.p, nn, (const double*)a,
+            (const double*)b, (const double*)w, err, h->sim_part.p);
+  BA_LAUNCH(k_sim_finish, dim3(1), dim3(64), 0, h->stream, (const double*)h->sim_part.p, nblk, n_used, h->sim_rec.p);
+  HIPCHECK(hipMemcpyAsync(&rec, h->sim_rec.p, sizeof rec, hipMemcpyDeviceToHost, h->stream));
+  if (cam_err && n_cam > 0) HIPCHECK(hipMemcpyAsync(cam_err, err, (size_t)n_cam * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (pt_err && n_pt > 0) HIPCHECK(hipMemcpyAsync(pt_err, err + n_cam, (size_t)n_pt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  std::vector<double> held_pts;
+  if (opts->apply)      // reads the similarity from the device record; a status that is not OK makes the kernels no-ops
+    if (int rc = launch_transform(h, &held_pts)) return rc;
+  BA_SYNC(h);
+  if (opts->apply && rec.status == SIM_OK) commit_transform(h, held_pts);   // else the handle stays exactly as found
+  out->status = rec.status;
+  out->sim.s = rec.s;
+  memcpy(out->sim.R, rec.R, sizeof rec.R);
+  memcpy(out->sim.t, rec.t, sizeof rec.t);
+  out->rms = rec.rms;
+  out->max = rec.max;
   return BA_OK;
 }
 

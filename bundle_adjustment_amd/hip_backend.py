@@ -83,6 +83,19 @@ class BATrackOptions(C.Structure):
                 ("max_reproj_px", C.c_double), ("min_depth", C.c_double), ("write_points", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class BASimilarity(C.Structure):
+    _fields_ = [("s", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3)]
+
+
+class BAAlignOptions(C.Structure):
+    _fields_ = [("loss", C.c_int32), ("iters", C.c_int32), ("f_scale", C.c_double), ("with_scale", C.c_int32), ("apply", C.c_int32)]
+
+
+class BAAlignResult(C.Structure):
+    _fields_ = [("sim", BASimilarity), ("rms", C.c_double), ("max", C.c_double), ("n_used", C.c_int32), ("status", C.c_int32)]
+
+
+ALIGN_STATUS = {"ok": 0, "too_few": 1, "degenerate": 2}   # enum ba_align_status
 TRACK_STATUS = {"ok": 0, "few_views": 1, "degenerate": 2, "behind": 3, "low_angle": 4, "high_error": 5}   # enum ba_track_status
 K_TRACKS = 13
 
@@ -125,6 +138,10 @@ SYMBOLS = {
     "ba_triangulate": (C.c_int, [C.c_void_p, _DP, _DP, _DP, C.c_int64, _DP, _DP, _DP, C.POINTER(C.c_uint8)]),
     "ba_default_track_options": (C.c_int, [C.POINTER(BATrackOptions)]),
     "ba_triangulate_tracks": (C.c_int, [C.c_void_p, _DP, C.POINTER(BATrackOptions), _DP, C.POINTER(C.c_uint8), _DP, _DP, _DP]),
+    "ba_get_centres": (C.c_int, [C.c_void_p, _DP]),
+    "ba_transform": (C.c_int, [C.c_void_p, C.POINTER(BASimilarity)]),
+    "ba_default_align_options": (C.c_int, [C.POINTER(BAAlignOptions)]),
+    "ba_align": (C.c_int, [C.c_void_p, C.POINTER(BAAlignOptions), _DP, _DP, _DP, _DP, C.POINTER(BAAlignResult), _DP, _DP]),
     "ba_get_trace": (C.c_int, [C.c_void_p, C.POINTER(BAIterRecord), C.c_int32, C.POINTER(C.c_int32)]),
     "ba_get_stat": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
     "ba_debug_occupy": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double]),
@@ -471,6 +488,14 @@ class Solver:
                                           _dp(r), C.byref(sse), C.byref(cost)))
         return r, sse.value, cost.value
 
+    def _residuals_bal_resident(self, intr, loss="linear", f_scale=1.0, want_vector=True):
+        """ba_residuals_bal on the problem the handle already holds (set_problem_bal) at its current parameters: (r, sse, cost)."""
+        intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
+        r = np.empty((self.n_obs, 2)) if want_vector else None
+        sse, cost = C.c_double(0), C.c_double(0)
+        _check(self._lib.ba_residuals_bal(self._h, _dp(intr), loss_code(loss), float(f_scale), _dp(r), C.byref(sse), C.byref(cost)))
+        return r, sse.value, cost.value
+
     def _set_bal(self, bal, fixed_cam=-1):
         from .problem import BAProblem
         self.set_problem(BAProblem(np.ascontiguousarray(bal.cams[:, :6]), bal.pts, bal.cam_idx, bal.pt_idx, bal.uv,
@@ -582,6 +607,43 @@ class Solver:
         _check(self._lib.ba_triangulate_tracks(self._h, ip, C.byref(o), _dp(out["xyz"]), out["status"].ctypes.data_as(C.POINTER(C.c_uint8)),
                                                _dp(out["angle_deg"]), _dp(out["rms_px"]), _dp(out["max_px"])))
         return out
+
+    def centres(self):
+        """ba_get_centres: (Nc, 3) camera centres -R_c^T t_c of the current cameras."""
+        out = np.empty((self.n_cams, 3))
+        _check(self._lib.ba_get_centres(self._h, _dp(out)))
+        return out
+
+    def transform(self, s=1.0, R=None, t=None):
+        """ba_transform: X' = s R X + t applied to every point and camera of the current parameters (held ones included;
+        residuals unchanged).  R (3, 3) defaults to the identity, t (3,) to zero.  Refused while priors are set."""
+        sim = BASimilarity()
+        sim.s = float(s)
+        sim.R[:] = list(np.asarray(np.eye(3) if R is None else R, dtype=np.float64).reshape(9))
+        sim.t[:] = list(np.asarray(np.zeros(3) if t is None else t, dtype=np.float64).reshape(3))
+        _check(self._lib.ba_transform(self._h, C.byref(sim)))
+
+    def align(self, cam_ref=None, pt_ref=None, cam_w=None, pt_w=None, loss="linear", f_scale=1.0, iters=10, with_scale=True,
+              apply=False):
+        """ba_align: the similarity that brings the current camera centres (cam_ref (Nc, 3)) and / or points (pt_ref (Np, 3))
+        onto reference positions, weighted (cam_w, pt_w; 0 = no reference, the row may be NaN) and robust (loss / f_scale in
+        the references' unit, `iters` IRLS rounds); apply=True also transforms the handle's parameters.  Returns dict(s, R
+        (3, 3), t (3,), rms, max, n_used, status (ALIGN_STATUS), cam_err (Nc,) or None, pt_err (Np,) or None)."""
+        o = BAAlignOptions()
+        _check(self._lib.ba_default_align_options(C.byref(o)))
+        o.loss, o.iters, o.f_scale, o.with_scale, o.apply = loss_code(loss), int(iters), float(f_scale), int(bool(with_scale)), int(bool(apply))
+
+        def arr(a, shape):
+            return None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(shape)
+        cam_ref, cam_w = arr(cam_ref, (self.n_cams, 3)), arr(cam_w, (self.n_cams,))
+        pt_ref, pt_w = arr(pt_ref, (self.n_pts, 3)), arr(pt_w, (self.n_pts,))
+        cam_err = None if cam_ref is None else np.empty(self.n_cams)
+        pt_err = None if pt_ref is None else np.empty(self.n_pts)
+        res = BAAlignResult()
+        _check(self._lib.ba_align(self._h, C.byref(o), _dp(cam_ref), _dp(cam_w), _dp(pt_ref), _dp(pt_w), C.byref(res),
+                                  _dp(cam_err), _dp(pt_err)))
+        return dict(s=res.sim.s, R=np.array(res.sim.R[:]).reshape(3, 3), t=np.array(res.sim.t[:]), rms=res.rms, max=res.max,
+                    n_used=res.n_used, status=res.status, cam_err=cam_err, pt_err=pt_err)
 
     def trace(self):
         """Per-iteration records of the last solve (ba_get_trace): list of dicts."""

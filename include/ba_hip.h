@@ -232,6 +232,59 @@ typedef struct ba_track_options {
 int ba_default_track_options(ba_track_options* opts);   /* linear, 20, 1.0, 0, 0, 0.0, 0 */
 int ba_triangulate_tracks(ba_handle* h, const double* intr, const ba_track_options* opts, double* xyz, uint8_t* status,
                           double* angle_deg, double* rms_px, double* max_px);
+/* Similarity transform of the reconstruction and robust alignment to reference positions: the step after an adjustment that
+ * moves the result into the frame its user needs (georegistration onto GPS / surveyed camera positions or ground-control
+ * points -- COLMAP's model_aligner; the comparison of two gauge-free solves; re-centring / re-scaling).  No reference
+ * counterpart.  Conventions: X' = s R X + t, R row-major 3x3, s > 0.  A world-to-camera pose (R_c, t_c) becomes
+ * R_c' = R_c R^T, t_c' = s t_c - R_c' t: camera-frame coordinates are s times the old ones and both camera models divide by
+ * depth, so every residual is unchanged and f, k1, k2 / K4 are not touched.  rvec' is the log map of R_c R^T through the unit
+ * quaternion (Shepperd's choice of the largest of trace and diagonal entries, w >= 0, theta = 2 atan2(|v|, w)), exact to
+ * rounding at every angle from 0 to pi.
+ * Precision: fp64 in a far-away frame costs residual precision (|t| = 5e6 at s = 1 moves residuals by ~3e-7 px, |t| <= 100 by
+ * ~2e-12 px): subtract a local origin from UTM-like references.
+ * ba_transform applies the similarity to EVERY point and camera of the handle's current parameters, held ones included (a
+ * change of frame is not an adjustment); masks, fixed_cam and shared-intrinsics groups stay and hold the new values.  It
+ * leaves the handle exactly as ba_set_params(transformed cameras, transformed points) would.  BA_ERR_STATE before
+ * ba_set_problem / parameters, and (naming "priors") while ba_set_priors blocks are set: their means live in the old frame,
+ * so align first and set priors afterwards.  BA_ERR_INVALID for s not finite or <= 0, max |R R^T - I| > 1e-9, det R < 0, a
+ * non-finite t.  A refused call leaves the handle as found.  Multi-rank jobs: local to the rank, every rank must pass the
+ * same similarity; untested on more than one rank. */
+typedef struct ba_similarity { double s; double R[9]; double t[3]; } ba_similarity;
+
+int ba_get_centres(ba_handle* h, double* centres);            /* double[Nc][3]: -R_c^T t_c of the current cameras */
+int ba_transform(ba_handle* h, const ba_similarity* sim);
+
+/* ba_align: the similarity that brings a_i = the current camera centres (where cam_ref is given), then the current points
+ * (where pt_ref is given, the caller's point order) onto the reference positions b_i.  A NULL weight vector is all ones;
+ * w_i = 0 means "no reference" (that row may hold NaN and enters no sum); a negative or non-finite weight is BA_ERR_INVALID.
+ * Weighted Umeyama with the current weights u_i: centroids mu_a, mu_b; Sigma = sum u_i (b_i - mu_b)(a_i - mu_a)^T / W from
+ * sums centred in a second pass (which also recovers what the first pass's rounding left out of mu_b); Sigma = U D V^T, R = U diag(1, 1, det U det V) V^T; s = tr(D diag(...)) / var_a (1 when
+ * with_scale = 0); t = mu_b - s R mu_a.  Then `iters` rounds of u_i = w_i rho'(w_i d_i^2 / f_scale^2), d_i = |b_i - (s R a_i + t)|,
+ * rho' of the solve's losses, each followed by the same closed form.  n_used = correspondences with w_i > 0; rms and max over
+ * those, of the unweighted d_i at the final similarity; cam_err / pt_err = d_i, NaN without a reference.
+ * status TOO_FEW: n_used < 3.  DEGENERATE: W = 0, var_a = 0, second singular value <= 1e-12 x the first (coincident or
+ * collinear positions), or a non-finite sum.  In both cases the call returns BA_OK, sim is the identity, rms, max and the
+ * errors are NaN and nothing is applied even with apply = 1.
+ * BA_ERR_INVALID for an unknown loss, f_scale <= 0, iters < 0, both reference arrays NULL; BA_ERR_STATE as ba_transform
+ * (the priors refusal only with apply = 1).  All rounds run on the device without a host synchronisation in between; the sums
+ * use no atomics and a fixed order: results are bit-reproducible from call to call.  Local to the rank, no collective:
+ * callers of multi-rank jobs align on camera references, which are replicated. */
+enum ba_align_status { BA_ALIGN_OK = 0, BA_ALIGN_TOO_FEW = 1, BA_ALIGN_DEGENERATE = 2 };
+typedef struct ba_align_options {
+  int32_t loss;        /* ba_loss, ONE rho per correspondence, on its 3-D distance */
+  int32_t iters;       /* IRLS re-weightings after the least-squares fit; 0 = least squares only */
+  double  f_scale;     /* in the unit of the reference positions */
+  int32_t with_scale;  /* 1: similarity; 0: rigid, s = 1 */
+  int32_t apply;       /* 1: ba_transform(h, result) in the same call when status is OK */
+} ba_align_options;
+typedef struct ba_align_result {
+  ba_similarity sim; double rms; double max; int32_t n_used; int32_t status;
+} ba_align_result;
+int ba_default_align_options(ba_align_options* o);            /* linear, 10, 1.0, 1, 0 */
+int ba_align(ba_handle* h, const ba_align_options* opts,
+             const double* cam_ref, const double* cam_w,      /* [Nc][3], [Nc]; either pair may be NULL */
+             const double* pt_ref,  const double* pt_w,       /* [Np][3], [Np] */
+             ba_align_result* out, double* cam_err, double* pt_err);   /* errors may be NULL */
 /* Copies up to `capacity` records of the last ba_solve into out (may be NULL to ask for the count only);
  * *n = number of LM iterations recorded. */
 int ba_get_trace(ba_handle* h, ba_iter_record* out, int32_t capacity, int32_t* n);
