@@ -258,6 +258,19 @@ def triangulate(prob: BALProblem, device=0, write=False, **opts):
     return out, BALProblem(prob.cams.copy(), pts, prob.cam_idx.copy(), prob.pt_idx.copy(), prob.uv.copy())
 
 
+def resect(prob: BALProblem, device=0, write=True, cams=None, known_points=None, **opts):
+    """Resect the cameras of a BAL problem from ``prob.pts``, taken as known, with each camera's own f / k1 / k2
+    (``ba_resect``; cams, known_points and opts as ``hip_backend.Solver.resect``).  Returns ``(out, problem)``:
+    dict(poses, status, n_inliers, rms_px, max_px) and a copy of ``prob`` with the merged cameras (``write=True``: the
+    selected cameras that are OK carry their resected poses; f, k1, k2 are left alone)."""
+    from . import hip_backend
+    with hip_backend.Solver(device) as s:
+        intr = s._set_bal(prob)
+        out = s.resect(intr=intr, cams=cams, known_points=known_points, write_cams=int(bool(write)), **opts)
+        cams6 = s.get_params()[0]
+    return out, BALProblem(np.concatenate([cams6, intr], axis=1), prob.pts.copy(), prob.cam_idx.copy(), prob.pt_idx.copy(), prob.uv.copy())
+
+
 def align(prob: BALProblem, cam_ref=None, pt_ref=None, cam_w=None, pt_w=None, loss="linear", f_scale=1.0, iters=10,
           with_scale=True, device=0):
     """Align a BAL problem to reference positions: the similarity ``X' = s R X + t`` that brings its camera centres

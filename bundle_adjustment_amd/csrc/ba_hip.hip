@@ -39,6 +39,7 @@
 #include "ba_cov.hpp"
 #include "ba_tracks.hpp"
 #include "ba_similarity.hpp"
+#include "ba_resect.hpp"
 
 using namespace ba;
 
@@ -67,7 +68,7 @@ extern "C" const char* ba_last_error(void) { return g_err.c_str(); }
 
 static const char* kKernelNames[BA_PROFILE_SLOTS] = {
     "cam_prepare", "residual_cam", "linearize_cam", "linearize_pt", "point_invert", "schur_pt",
-    "schur_cam", "pcg_step", "precond", "backsub_pt", "misc", "allreduce", "schur_pt_then_backsub", "tracks", "", ""};
+    "schur_cam", "pcg_step", "precond", "backsub_pt", "misc", "allreduce", "schur_pt_then_backsub", "tracks", "resect", ""};
 extern "C" const char* ba_kernel_name(int slot) {
   return (slot >= 0 && slot < BA_PROFILE_SLOTS) ? kKernelNames[slot] : "";
 }
@@ -265,6 +266,12 @@ struct ba_handle {
   DBuf<unsigned char> trk_status;
   TrackArgs trk_args = {};
   bool trk_valid = false, trk_bal = false;
+  // ba_resect (ba_resect.hpp): per-camera results, the BAL intrinsics of the call, pt_known as given and in point-slot
+  // order, cam_sel; the launch arguments of the last call (what ba_time_kernel(BA_K_RESECT) repeats)
+  DBuf<double> rs_out, rs_intr;
+  DBuf<unsigned char> rs_known_in, rs_known, rs_sel;
+  ResectArgs rs_args = {};
+  bool rs_valid = false, rs_bal = false;
   // ba_transform / ba_align / ba_get_centres (ba_similarity.hpp): correspondences a | b | w | u | err (9 doubles each), the
   // per-workgroup partial rows, the device record (similarity, centroids, status)
   DBuf<double> sim_buf, sim_part;
@@ -1470,6 +1477,7 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
   clear_priors(h);                   // ... and without priors
   clear_shared(h);                   // ... and every camera with its own intrinsics
   h->trk_valid = false;
+  h->rs_valid = false;
   {   // index ranges, before anything is touched (a rejected call keeps the previous problem): branch-free sweep first
     int ok = 1;
     for (int64_t i = 0; i < n_obs; ++i)
@@ -3420,6 +3428,97 @@ extern "C" int ba_triangulate_tracks(ba_handle* h, const double* intr, const ba_
   return BA_OK;
 }
 
+// ------------------------------------------------------------------------------------------------- resection
+// ba_resect (csrc/ba_resect.hpp): one workgroup per camera over the camera-ordered list.  Local to the rank: no collective.
+static void launch_resect(ba_handle* h) {
+  ResectArgs& a = h->rs_args;
+  a.t.cs = h->cs[h->cur].p; a.cams = h->cams[h->cur].p; a.ptab = h->ptab[h->cur].p;
+  if (h->Nc == 0) return;
+  if (h->rs_bal) BA_LAUNCH(k_resect<BalCam>, dim3(h->Nc), dim3(RS_THREADS), 0, h->stream, a);
+  else BA_LAUNCH(k_resect<Pinhole>, dim3(h->Nc), dim3(RS_THREADS), 0, h->stream, a);
+}
+extern "C" int ba_default_resect_options(ba_resect_options* o) {
+  if (!o) return fail(BA_ERR_INVALID, "null argument");
+  memset(o, 0, sizeof *o);
+  o->loss = BA_LOSS_LINEAR;
+  o->refine_iters = 20;
+  o->f_scale = 1.0;
+  o->init = BA_RESECT_INIT_DLT;
+  o->min_inliers = 6;
+  return BA_OK;
+}
+extern "C" int ba_resect(ba_handle* h, const double* intr, const ba_resect_options* opts, const uint8_t* cam_sel, const uint8_t* pt_known,
+                         double* poses, uint8_t* status, int32_t* n_inliers, double* rms_px, double* max_px) {
+  if (!h || !opts) return fail(BA_ERR_INVALID, "null argument");
+  if (!h->have_problem || !h->have_params) return fail(BA_ERR_STATE, "ba_resect: ba_set_problem / ba_set_params first");
+  if (!loss_valid(opts->loss)) return fail(BA_ERR_INVALID, "ba_resect: unknown loss %d", opts->loss);
+  if (opts->init != BA_RESECT_INIT_DLT && opts->init != BA_RESECT_INIT_CURRENT) return fail(BA_ERR_INVALID, "ba_resect: unknown init %d", opts->init);
+  if (!(opts->f_scale > 0)) return fail(BA_ERR_INVALID, "ba_resect: f_scale must be positive");
+  if (opts->refine_iters < 0) return fail(BA_ERR_INVALID, "ba_resect: refine_iters must not be negative");
+  if (opts->min_inliers < 0) return fail(BA_ERR_INVALID, "ba_resect: min_inliers must not be negative");
+  if (opts->reserved0 != 0) return fail(BA_ERR_INVALID, "ba_resect: reserved0 must be 0");
+  if (opts->write_cams && any_prior(h))
+    return fail(BA_ERR_STATE, "ba_resect with write_cams = 1: priors are set (ba_set_priors) and their means were set for the old poses: "
+                              "resect first, set the priors afterwards");
+  if (set_device(h)) return BA_ERR_HIP;
+  const int Nc = h->Nc, Np = h->Np;
+  const size_t nc1 = (size_t)std::max(Nc, 1), np1 = (size_t)std::max(Np, 1);
+  HIPCHECK(h->rs_out.alloc(RS_OUT * nc1));
+  if (intr) {
+    HIPCHECK(h->rs_intr.alloc(3 * nc1));
+    HIPCHECK(hipMemcpyAsync(h->rs_intr.p, intr, 3 * (size_t)Nc * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  }
+  if (cam_sel) {
+    HIPCHECK(h->rs_sel.alloc(nc1));
+    HIPCHECK(hipMemcpyAsync(h->rs_sel.p, cam_sel, (size_t)Nc, hipMemcpyHostToDevice, h->stream));
+  }
+  if (pt_known && Np > 0) {
+    HIPCHECK(h->rs_known_in.alloc(np1)); HIPCHECK(h->rs_known.alloc(np1));
+    HIPCHECK(hipMemcpyAsync(h->rs_known_in.p, pt_known, (size_t)Np, hipMemcpyHostToDevice, h->stream));
+    BA_LAUNCH(k_resect_known, dim3((Np + 255) / 256), dim3(256), 0, h->stream, (const unsigned char*)h->rs_known_in.p, (const int*)h->slot.p, Np,
+              h->rs_known.p);
+  }
+  ResectArgs& a = h->rs_args;
+  a = ResectArgs{};
+  a.t.intr = intr ? h->rs_intr.p : nullptr;
+  a.t.uv = uv_arr(h, h->c_uv);
+  a.t.fx = h->K4[0]; a.t.fy = h->K4[1]; a.t.cx = h->K4[2]; a.t.cy = h->K4[3];
+  a.t.loss = opts->loss; a.t.iters = opts->refine_iters;
+  a.t.fscale = opts->f_scale; a.t.max_px = opts->max_reproj_px; a.t.min_depth = opts->min_depth;
+  a.offk = h->offk.p; a.c_pt = h->c_pt.p;
+  a.known = (pt_known && Np > 0) ? h->rs_known.p : nullptr;
+  a.sel = cam_sel ? h->rs_sel.p : nullptr;
+  a.init = opts->init; a.min_inliers = opts->min_inliers; a.max_rms = opts->max_rms_px;
+  a.out = h->rs_out.p;
+  h->rs_bal = intr != nullptr;
+  h->rs_valid = true;
+  launch_resect(h);
+  std::vector<double> res(RS_OUT * (size_t)Nc);
+  if (Nc > 0) HIPCHECK(hipMemcpyAsync(res.data(), h->rs_out.p, res.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (opts->write_cams) {
+    // what ba_set_params(merged cameras, points as they are) leaves behind: parameter set 0 current, the point table
+    // rebuilt, the camera state recomputed, the linearisation forgotten (held_x2 stays: no point moves)
+    const int nmax = std::max(Nc, Np);
+    if (nmax > 0)
+      BA_LAUNCH(k_resect_merge, dim3((nmax + 255) / 256), dim3(256), 0, h->stream, (const double*)h->rs_out.p, a.sel, cam_held_ptr(h), h->fixed,
+                (const double*)h->cams[h->cur].p, Nc, h->cams[0].p, (const double*)h->ptab[h->cur].p, Np, h->ptab[0].p);
+    h->cur = 0;
+    BA_LAUNCH(k_cam_prepare<Pinhole>, dim3((Nc + 63) / 64), dim3(64), 0, h->stream, h->cams[0].p, (const double*)h->intr[0].p,
+              h->cs[0].p, h->camA[0].p, Nc);
+    h->linearized = false;
+  }
+  BA_SYNC(h);
+  for (int c = 0; c < Nc; ++c) {
+    const double* r = res.data() + RS_OUT * (size_t)c;
+    if (poses) memcpy(poses + 6 * (size_t)c, r, 6 * sizeof(double));
+    if (status) status[c] = (uint8_t)(int)r[6];
+    if (n_inliers) n_inliers[c] = (int32_t)r[7];
+    if (rms_px) rms_px[c] = r[8];
+    if (max_px) max_px[c] = r[9];
+  }
+  return BA_OK;
+}
+
 // ------------------------------------------------------------------------------------------------- similarity
 // ba_get_centres, ba_transform, ba_align (csrc/ba_similarity.hpp).  Local to the rank: no collective.
 extern "C" int ba_get_centres(ba_handle* h, double* centres) {
@@ -3601,6 +3700,7 @@ extern "C" int ba_time_kernel(ba_handle* h, int slot, int reps, double* mean_us)
   if (!h || !mean_us || reps < 1) return fail(BA_ERR_INVALID, "bad argument");
   if (!h->have_params) return fail(BA_ERR_STATE, "no parameters set");
   if (slot == BA_K_TRACKS && !h->trk_valid) return fail(BA_ERR_STATE, "BA_K_TRACKS repeats the last ba_triangulate_tracks: call it first");
+  if (slot == BA_K_RESECT && !h->rs_valid) return fail(BA_ERR_STATE, "BA_K_RESECT repeats the last ba_resect: call it first");
   if (set_device(h)) return BA_ERR_HIP;
   const bool saved = h->profile;
   h->profile = false;
@@ -3625,6 +3725,7 @@ extern "C" int ba_time_kernel(ba_handle* h, int slot, int reps, double* mean_us)
       case BA_K_PRECOND: launch_cam_schur(h, robust, true, false, 0, 0.0, 0); break;
       case BA_K_POINT_INVERT: launch_point_invert(h, 1e-4); break;
       case BA_K_TRACKS: launch_tracks(h); break;
+      case BA_K_RESECT: launch_resect(h); break;
       default: break;
     }
   };

@@ -83,6 +83,12 @@ class BATrackOptions(C.Structure):
                 ("max_reproj_px", C.c_double), ("min_depth", C.c_double), ("write_points", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class BAResectOptions(C.Structure):
+    _fields_ = [("loss", C.c_int32), ("refine_iters", C.c_int32), ("f_scale", C.c_double), ("init", C.c_int32),
+                ("min_inliers", C.c_int32), ("max_reproj_px", C.c_double), ("max_rms_px", C.c_double), ("min_depth", C.c_double),
+                ("write_cams", C.c_int32), ("reserved0", C.c_int32)]
+
+
 class BASimilarity(C.Structure):
     _fields_ = [("s", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3)]
 
@@ -97,7 +103,10 @@ class BAAlignResult(C.Structure):
 
 ALIGN_STATUS = {"ok": 0, "too_few": 1, "degenerate": 2}   # enum ba_align_status
 TRACK_STATUS = {"ok": 0, "few_views": 1, "degenerate": 2, "behind": 3, "low_angle": 4, "high_error": 5}   # enum ba_track_status
+RESECT_STATUS = {"ok": 0, "few_points": 1, "degenerate": 2, "behind": 3, "few_inliers": 4, "high_error": 5}   # enum ba_resect_status
+RESECT_INIT = {"dlt": 0, "current": 1}   # enum ba_resect_init
 K_TRACKS = 13
+K_RESECT = 14
 
 _lib = None
 
@@ -138,6 +147,9 @@ SYMBOLS = {
     "ba_triangulate": (C.c_int, [C.c_void_p, _DP, _DP, _DP, C.c_int64, _DP, _DP, _DP, C.POINTER(C.c_uint8)]),
     "ba_default_track_options": (C.c_int, [C.POINTER(BATrackOptions)]),
     "ba_triangulate_tracks": (C.c_int, [C.c_void_p, _DP, C.POINTER(BATrackOptions), _DP, C.POINTER(C.c_uint8), _DP, _DP, _DP]),
+    "ba_default_resect_options": (C.c_int, [C.POINTER(BAResectOptions)]),
+    "ba_resect": (C.c_int, [C.c_void_p, _DP, C.POINTER(BAResectOptions), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _DP,
+                            C.POINTER(C.c_uint8), _IP, _DP, _DP]),
     "ba_get_centres": (C.c_int, [C.c_void_p, _DP]),
     "ba_transform": (C.c_int, [C.c_void_p, C.POINTER(BASimilarity)]),
     "ba_default_align_options": (C.c_int, [C.POINTER(BAAlignOptions)]),
@@ -606,6 +618,54 @@ class Solver:
                    max_px=np.empty(n))
         _check(self._lib.ba_triangulate_tracks(self._h, ip, C.byref(o), _dp(out["xyz"]), out["status"].ctypes.data_as(C.POINTER(C.c_uint8)),
                                                _dp(out["angle_deg"]), _dp(out["rms_px"]), _dp(out["max_px"])))
+        return out
+
+    def resect_options(self, **kw) -> BAResectOptions:
+        """ba_default_resect_options overlaid with kw (loss and init by name or by value, any other ba_resect_options field)."""
+        o = BAResectOptions()
+        _check(self._lib.ba_default_resect_options(C.byref(o)))
+        for k, v in kw.items():
+            if k == "loss":
+                v = loss_code(v)
+            if k == "init" and isinstance(v, str):
+                if v not in RESECT_INIT:
+                    raise ValueError(f"unknown init {v!r}: one of {sorted(RESECT_INIT)}")
+                v = RESECT_INIT[v]
+            if not hasattr(o, k):
+                raise TypeError(f"unknown option {k}")
+            setattr(o, k, v)
+        return o
+
+    def resect(self, intr=None, cams=None, known_points=None, **opts):
+        """ba_resect: the pose of every selected camera of the resident problem from its observations of the known points,
+        the current points taken as they are (intr None: pinhole; else (Nc, 3) (f, k1, k2) of the BAL camera).  cams: bool
+        (Nc,) mask or a list of camera indices, None = every camera; known_points: bool (Np,) mask or a list of point
+        indices, None = every point.  opts: loss, refine_iters, f_scale, init ("dlt" / "current"), min_inliers,
+        max_reproj_px, max_rms_px, min_depth, write_cams.  Returns dict(poses (Nc, 6) rvec | t, status (Nc,) uint8
+        (RESECT_STATUS), n_inliers (Nc,) int32, rms_px, max_px (Nc,))."""
+        ip = None
+        if intr is not None:
+            intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
+            ip = _dp(intr)
+
+        def mask(m, n):
+            if m is None:
+                return None, None
+            m = np.asarray(m)
+            if m.dtype != np.bool_:
+                idx, m = m.astype(np.int64).reshape(-1), np.zeros(n, dtype=bool)
+                m[idx] = True
+            a = np.ascontiguousarray(m.reshape(n), dtype=np.uint8)
+            return a, a.ctypes.data_as(C.POINTER(C.c_uint8))
+        sel, selp = mask(cams, self.n_cams)
+        known, knownp = mask(known_points, self.n_pts)
+        o = self.resect_options(**opts)
+        n = self.n_cams
+        out = dict(poses=np.empty((n, 6)), status=np.empty(n, dtype=np.uint8), n_inliers=np.empty(n, dtype=np.int32),
+                   rms_px=np.empty(n), max_px=np.empty(n))
+        _check(self._lib.ba_resect(self._h, ip, C.byref(o), selp, knownp, _dp(out["poses"]),
+                                   out["status"].ctypes.data_as(C.POINTER(C.c_uint8)), out["n_inliers"].ctypes.data_as(_IP),
+                                   _dp(out["rms_px"]), _dp(out["max_px"])))
         return out
 
     def centres(self):

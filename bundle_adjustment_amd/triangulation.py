@@ -83,6 +83,26 @@ def triangulate_tracks(prob, solver=None, write=False, **opts):
     return out, dataclasses.replace(prob, pts=pts)
 
 
+def resect_cameras(prob, solver=None, write=True, cams=None, known_points=None, **opts):
+    """Resect the cameras of a pinhole ``BAProblem`` from ``prob.pts``, taken as known (``ba_resect``; cams, known_points
+    and opts as ``hip_backend.Solver.resect``: loss, refine_iters, f_scale, init, min_inliers, max_reproj_px, max_rms_px,
+    min_depth).  Returns ``(out, problem)``: dict(poses, status, n_inliers, rms_px, max_px) in ``prob``'s camera order and a
+    copy of ``prob`` with the merged cameras -- with ``write=True`` the selected cameras that are OK, not the fixed camera and
+    have no pose parameter held carry their resected poses; with ``write=False`` the cameras are ``prob``'s.  ``solver``: a
+    ``hip_backend.Solver`` to upload into (its resident problem is replaced); default: one on device 0 for the call."""
+    import dataclasses
+    own = solver is None
+    s = hip_backend.Solver(0) if own else solver
+    try:
+        s.set_problem(prob)
+        out = s.resect(cams=cams, known_points=known_points, write_cams=int(bool(write)), **opts)
+        merged = s.get_params()[0]
+    finally:
+        if own:
+            s.close()
+    return out, dataclasses.replace(prob, cams=merged)
+
+
 def filter_tracks(prob, keep):
     """Drop the points where ``keep`` (bool (Np,)) is false together with their observations and renumber ``pt_idx``; the
     remaining observations keep their order.  ``prob``: a ``BAProblem`` or a ``bal.BALProblem``.  Returns

@@ -143,7 +143,8 @@ enum ba_kernel_slot {
   BA_K_POINT_INVERT = 4, BA_K_SCHUR_PT = 5, BA_K_SCHUR_CAM = 6, BA_K_PCG_UPDATE = 7,
   BA_K_PRECOND = 8, BA_K_BACKSUB = 9, BA_K_MISC = 10, BA_K_ALLREDUCE = 11,
   BA_K_SCHUR_PT_BACKSUB = 12,  /* launches of the PCG point pass that found PCG finished and went on as the back substitution */
-  BA_K_TRACKS = 13             /* ba_time_kernel only: the kernels of the last ba_triangulate_tracks call, with its options */
+  BA_K_TRACKS = 13,            /* ba_time_kernel only: the kernels of the last ba_triangulate_tracks call, with its options */
+  BA_K_RESECT = 14             /* ba_time_kernel only: the kernel of the last ba_resect call, with its options and masks */
 };
 
 /* Event counters of a handle (ba_get_stat): which implementation served the window-sized solves, how often the
@@ -232,6 +233,63 @@ typedef struct ba_track_options {
 int ba_default_track_options(ba_track_options* opts);   /* linear, 20, 1.0, 0, 0, 0.0, 0 */
 int ba_triangulate_tracks(ba_handle* h, const double* intr, const ba_track_options* opts, double* xyz, uint8_t* status,
                           double* angle_deg, double* rms_px, double* max_px);
+/* Resection: the pose of every selected camera from the points it sees, the mirror image of ba_triangulate_tracks (COLMAP's
+ * image registration, OpenMVG's resection, the tracking / relocalisation pose of ORB-SLAM; no reference counterpart).  The
+ * points are the handle's CURRENT points and are treated as known: held masks, fixed_cam, priors and shared-intrinsics groups
+ * play no part in the estimate.  No RANSAC and no minimal solver: a linear start on all observations, then a robust refinement.
+ *   intr      NULL: the pinhole with the handle's K4; else (f, k1, k2)[Nc] of the BAL camera, as in ba_triangulate_tracks;
+ *             read, never changed
+ *   cam_sel   uint8[Nc] or NULL = every camera: which cameras to resect.  A camera that is not selected gets its current
+ *             pose in poses, status OK, n_inliers 0 and NaN measures.
+ *   pt_known  uint8[Np] in the caller's point order, or NULL = every point: which points count as known
+ *   poses double[Nc][6] (rvec | t), status uint8[Nc] (ba_resect_status), n_inliers int32[Nc], rms_px, max_px double[Nc]; any
+ *   may be NULL
+ * Per selected camera, over its n observations of known points: (1) bearings as in ba_triangulate_tracks (the BAL radial
+ * model inverted by Newton); an observation whose bearing fails is dropped from n and is never an inlier.  (2) The start:
+ * INIT_CURRENT the handle's pose (n >= 3), INIT_DLT (n >= 6) the DLT on the rows x (p3.X~) - p1.X~ = 0, y (p3.X~) - p2.X~ = 0
+ * with X~ = ((X - mean) / sigma, 1), sigma^2 = mean |X - mean|^2 / 3 (Hartley normalisation, from centred values).  The 12 x 12
+ * matrix is not formed: with S = sum X~X~^T, Sx = sum x X~X~^T, Sy = sum y X~X~^T, Sq = sum (x^2 + y^2) X~X~^T (forty fp64
+ * sums), eliminating p1, p2 leaves M = Sq - Sx S^-1 Sx - Sy S^-1 Sy (4 x 4); p3 is its eigenvector of the smallest eigenvalue
+ * (cyclic Jacobi), p1 = S^-1 Sx p3, p2 = S^-1 Sy p3.  S is factorised by a Cholesky of S / n: a pivot <= 1e-8 (coplanar,
+ * collinear or coincident points) or a non-finite entry is DEGENERATE.  With A the left 3 x 3 of [p1; p2; p3] and b its last
+ * column: P changes sign if det A < 0; R = U V^T of A's SVD; t = b / mean(singular values), then t <- sigma t - R mean;
+ * sigma_3 <= 1e-6 sigma_1 is DEGENERATE; rvec is the quaternion log map of R (as in ba_transform).  Below the counts above the
+ * status is FEW_POINTS.  For FEW_POINTS and a DEGENERATE start the pose is the current one, n_inliers 0 and the measures NaN.
+ * (3) At most refine_iters Marquardt-damped Gauss-Newton steps on 0.5 sum f_scale^2 rho((r / f_scale)^2) over the six pose
+ * parameters in the additive coordinates rvec | t, with the analytic Jacobian and IRLS weights of the solve: (H + lambda diag H)
+ * dx = -g by a 6 x 6 Cholesky (a pivot <= 0: DEGENERATE with the last accepted pose and its measures); lambda from 1e-4, / 10
+ * (floor 1e-12) after a step that does not raise the cost (cost_trial <= cost (1 + 1e-12)), * 10 after one that does, which is
+ * dropped but counted; stop at |dx| <= 1e-14 |x|.  An observation behind the camera at a pass's pose is left out of that pass's
+ * sums.  (4) At the final pose: inliers are the observations in front with |r_i| <= max_reproj_px; rms_px and max_px are taken
+ * over the inliers, or over all observations in front when there are none.  (5) status = the first failing test in enum order:
+ * FEW_POINTS, DEGENERATE as above; BEHIND more than half of the n observations are behind; FEW_INLIERS n_inliers <
+ * min_inliers; HIGH_ERROR rms_px > max_rms_px.
+ * write_cams = 1 stores the pose of every camera that is selected, OK, not fixed_cam and has none of the held bits 0-5 set
+ * (ba_set_held), and leaves the handle exactly as ba_set_params(merged cameras, current points) would (the linearisation is
+ * forgotten; masks, groups stay); write_cams = 0 leaves the handle exactly as found.
+ * BA_ERR_STATE before ba_set_problem / ba_set_params, and (naming "priors") with write_cams = 1 while ba_set_priors blocks are
+ * set: their means were set for the old poses.  BA_ERR_INVALID for an unknown loss or init, f_scale <= 0, refine_iters < 0,
+ * min_inliers < 0, reserved0 != 0.  One workgroup per camera, sums in a fixed order and without atomics: results are
+ * bit-reproducible from call to call.  Multi-rank jobs: the call is local to the calling rank's shard (all cameras, its
+ * observations and points), no collective; untested on more than one rank. */
+enum ba_resect_status { BA_RESECT_OK = 0, BA_RESECT_FEW_POINTS = 1, BA_RESECT_DEGENERATE = 2,
+                        BA_RESECT_BEHIND = 3, BA_RESECT_FEW_INLIERS = 4, BA_RESECT_HIGH_ERROR = 5 };
+enum ba_resect_init   { BA_RESECT_INIT_DLT = 0, BA_RESECT_INIT_CURRENT = 1 };
+typedef struct ba_resect_options {
+  int32_t loss;          /* ba_loss of the refinement */
+  int32_t refine_iters;  /* most damped Gauss-Newton steps; 0 = the start only */
+  double  f_scale;
+  int32_t init;          /* ba_resect_init */
+  int32_t min_inliers;   /* FEW_INLIERS below this; default 6 */
+  double  max_reproj_px; /* inlier test on |r_i|; <= 0: every observation in front of the camera is an inlier */
+  double  max_rms_px;    /* HIGH_ERROR when the inliers' rms exceeds it; <= 0: no test */
+  double  min_depth;     /* an observation is "behind" when its depth (sign of the model: +z pinhole, -z BAL) <= min_depth */
+  int32_t write_cams;
+  int32_t reserved0;     /* must be 0 */
+} ba_resect_options;
+int ba_default_resect_options(ba_resect_options* opts);   /* linear, 20, 1.0, DLT, 6, 0, 0, 0.0, 0 */
+int ba_resect(ba_handle* h, const double* intr, const ba_resect_options* opts, const uint8_t* cam_sel, const uint8_t* pt_known,
+              double* poses, uint8_t* status, int32_t* n_inliers, double* rms_px, double* max_px);
 /* Similarity transform of the reconstruction and robust alignment to reference positions: the step after an adjustment that
  * moves the result into the frame its user needs (georegistration onto GPS / surveyed camera positions or ground-control
  * points -- COLMAP's model_aligner; the comparison of two gauge-free solves; re-centring / re-scaling).  No reference
@@ -486,7 +544,8 @@ int ba_reset_profile(ba_handle* h);
 
 /* Bench hook: run one kernel `reps` times back to back on the solver stream between two
  * HIP events and return the mean duration in microseconds (state left as it was).  BA_K_TRACKS: every kernel of the last
- * ba_triangulate_tracks call (BA_ERR_STATE without one since ba_set_problem), at the current cameras. */
+ * ba_triangulate_tracks call (BA_ERR_STATE without one since ba_set_problem), at the current cameras.  BA_K_RESECT: the same
+ * for the last ba_resect call (its write-back is not repeated). */
 int ba_time_kernel(ba_handle* h, int slot, int reps, double* mean_us);
 
 #ifdef __cplusplus

@@ -1,0 +1,273 @@
+"""numpy restatement of ba_resect (include/ba_hip.h), one camera at a time: the yardstick of the resection tests.
+
+Steps as in the header: (1) bearings, (2) the start -- the current pose, or the Hartley-normalised DLT, here through the SVD
+of the full 2n x 12 matrix (``method='svd'``; ``'reduced'`` is the device's 4 x 4 form, kept to test the reduction against
+the other), (3) Marquardt-damped Gauss-Newton on the six additive parameters rvec | t with the analytic Jacobian and IRLS
+weights, (4) inliers / rms / max at the final pose, (5) status = first failing test in enum order.  Camera conventions as in
+tests/track_reference.py: pinhole ``K4``, looking down +z; BAL ``intr = (f, k1, k2)``, looking down -z.
+"""
+import numpy as np
+
+from bundle_adjustment_amd.rotations import rvecs_to_matrices
+from tests.track_reference import COST_SLACK, bal_undistort, jacobi_eig4, loss_terms
+
+OK, FEW_POINTS, DEGENERATE, BEHIND, FEW_INLIERS, HIGH_ERROR = range(6)
+PIVOT_MIN, RANK_TOL = 1e-8, 1e-6
+
+
+def pose_diff(a, b):
+    """Largest difference of two poses over the entries of R and t, relative to max(1, |t|)."""
+    a, b = np.atleast_2d(a), np.atleast_2d(b)
+    dR = np.abs(rvecs_to_matrices(a[:, :3]) - rvecs_to_matrices(b[:, :3])).max(axis=(1, 2))
+    dt = np.abs(a[:, 3:] - b[:, 3:]).max(axis=1) / np.maximum(1.0, np.abs(b[:, 3:]).max(axis=1))
+    return np.maximum(dR, dt)
+
+
+def right_jacobian(rvec):
+    """M = J_r(rvec) of the additive rotation-vector update (csrc/ba_device.hpp camera_state): I - b [r]x + d [r]x^2."""
+    r = np.asarray(rvec, dtype=np.float64)
+    t2 = float(r @ r)
+    th = np.sqrt(t2)
+    if th < 0.05:
+        b = 0.5 - t2 / 24.0 + t2 * t2 / 720.0 - t2 ** 3 / 40320.0
+        d = 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0 - t2 ** 3 / 362880.0
+    else:
+        b = (1.0 - np.cos(th)) / t2
+        d = (th - np.sin(th)) / (t2 * th)
+    K = np.array([[0.0, -r[2], r[1]], [r[2], 0.0, -r[0]], [-r[1], r[0], 0.0]])
+    return np.eye(3) - b * K + d * (K @ K)
+
+
+def log_map(R):
+    """Rotation matrix -> rotation vector through the unit quaternion (csrc/ba_similarity.hpp sim_log_map)."""
+    R = np.asarray(R, dtype=np.float64)
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    if tr >= R[0, 0] and tr >= R[1, 1] and tr >= R[2, 2]:
+        q = np.array([1.0 + tr, R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    elif R[0, 0] >= R[1, 1] and R[0, 0] >= R[2, 2]:
+        q = np.array([R[2, 1] - R[1, 2], 1.0 + R[0, 0] - R[1, 1] - R[2, 2], R[0, 1] + R[1, 0], R[0, 2] + R[2, 0]])
+    elif R[1, 1] >= R[2, 2]:
+        q = np.array([R[0, 2] - R[2, 0], R[0, 1] + R[1, 0], 1.0 + R[1, 1] - R[0, 0] - R[2, 2], R[1, 2] + R[2, 1]])
+    else:
+        q = np.array([R[1, 0] - R[0, 1], R[0, 2] + R[2, 0], R[1, 2] + R[2, 1], 1.0 + R[2, 2] - R[0, 0] - R[1, 1]])
+    q = q / np.sqrt(q @ q)
+    if q[0] < 0.0:
+        q = -q
+    vn = np.sqrt(q[1:] @ q[1:])
+    k = 2.0 / q[0] if vn < 1e-10 else 2.0 * np.arctan2(vn, q[0]) / vn
+    return k * q[1:]
+
+
+class Obs:
+    """The observations of one camera: points (n, 3), pixels (n, 2), the model (K4, or intr = (f, k1, k2))."""
+
+    def __init__(self, X, uv, K4=None, intr=None):
+        self.X, self.uv, self.K4, self.intr = np.asarray(X, dtype=np.float64), np.asarray(uv, dtype=np.float64), K4, intr
+
+    def bearings(self):
+        """-> (xy (n, 2) with the ray (x, y, 1) up to sign, ok (n,))."""
+        if self.intr is None:
+            fx, fy, cx, cy = self.K4
+            return np.stack([(self.uv[:, 0] - cx) / fx, (self.uv[:, 1] - cy) / fy], axis=1), np.ones(len(self.uv), dtype=bool)
+        xy, ok = np.empty_like(self.uv), np.empty(len(self.uv), dtype=bool)
+        for i in range(len(self.uv)):
+            p0, p1, ok[i] = bal_undistort(self.uv[i], *self.intr)
+            xy[i] = (-p0, -p1)
+        return xy, ok
+
+    def keep(self, mask):
+        return Obs(self.X[mask], self.uv[mask], self.K4, self.intr)
+
+    def project(self, pose):
+        """-> (residuals (n, 2), J (n, 2, 6) = d residual / d (rvec | t), depth (n,))."""
+        pose = np.asarray(pose, dtype=np.float64)
+        R = rvecs_to_matrices(pose[None, :3])[0]
+        P = self.X @ R.T + pose[3:]
+        z = np.where(P[:, 2] != 0.0, P[:, 2], 1.0)
+        n = len(P)
+        D = np.zeros((n, 2, 3))
+        if self.intr is None:
+            fx, fy, cx, cy = self.K4
+            xh, yh = P[:, 0] / z, P[:, 1] / z
+            r = self.uv - np.stack([xh * fx + cx, yh * fy + cy], axis=1)
+            D[:, 0, 0] = fx / z; D[:, 0, 2] = -fx * xh / z
+            D[:, 1, 1] = fy / z; D[:, 1, 2] = -fy * yh / z
+            depth = P[:, 2]
+        else:
+            f, k1, k2 = self.intr
+            p = -P[:, :2] / z[:, None]
+            n2 = (p * p).sum(axis=1)
+            rad = 1.0 + n2 * (k1 + k2 * n2)
+            drad = k1 + 2.0 * k2 * n2
+            r = self.uv - (f * rad)[:, None] * p
+            dpp = f * (rad[:, None, None] * np.eye(2) + 2.0 * drad[:, None, None] * p[:, :, None] * p[:, None, :])
+            dpP = np.zeros((n, 2, 3))
+            dpP[:, 0, 0] = 1.0; dpP[:, 1, 1] = 1.0; dpP[:, :, 2] = p
+            D = dpp @ (-dpP / z[:, None, None])
+            depth = -P[:, 2]
+        Pm = D @ R                                                     # d proj / d X
+        J = np.empty((n, 2, 6))
+        J[:, :, :3] = np.cross(Pm, self.X[:, None, :]) @ right_jacobian(pose[:3])      # (Pm_row x X) M
+        J[:, :, 3:] = -D
+        return r, J, depth
+
+
+def dlt_rows(o, xy):
+    """Hartley-normalised points X~ (n, 4), mean, sigma."""
+    mean = o.X.sum(axis=0) / len(o.X)
+    e = o.X - mean
+    sigma = np.sqrt((e * e).sum() / (3.0 * len(o.X)))
+    with np.errstate(all="ignore"):
+        Xt = np.concatenate([e / sigma, np.ones((len(o.X), 1))], axis=1)
+    return Xt, mean, sigma
+
+
+def chol4(S):
+    """The device's Cholesky of S / n with its pivot test: L, or None (coplanar, collinear or coincident points)."""
+    L = np.zeros((4, 4))
+    for j in range(4):
+        s = S[j, j] - L[j, :j] @ L[j, :j]
+        if not s > PIVOT_MIN:
+            return None
+        L[j, j] = np.sqrt(s)
+        for i in range(j + 1, 4):
+            L[i, j] = (S[i, j] - L[i, :j] @ L[j, :j]) / L[j, j]
+    return L
+
+
+def dlt_matrix(Xt, xy, method):
+    """P (3, 4) in the normalised coordinates, or None (reduced form: S is not positive definite enough)."""
+    n = len(Xt)
+    if method == "svd":
+        A = np.zeros((2 * n, 12))
+        A[0::2, 0:4] = -Xt; A[0::2, 8:12] = xy[:, 0, None] * Xt
+        A[1::2, 4:8] = -Xt; A[1::2, 8:12] = xy[:, 1, None] * Xt
+        return np.linalg.svd(A)[2][-1].reshape(3, 4)
+    S = Xt.T @ Xt / n
+    Sx = (Xt * xy[:, 0, None]).T @ Xt / n
+    Sy = (Xt * xy[:, 1, None]).T @ Xt / n
+    Sq = (Xt * (xy * xy).sum(axis=1)[:, None]).T @ Xt / n
+    L = chol4(S)
+    if L is None:
+        return None
+    Wx, Wy = np.linalg.solve(L, Sx), np.linalg.solve(L, Sy)
+    lam, V = jacobi_eig4(Sq - Wx.T @ Wx - Wy.T @ Wy)
+    p3 = V[:, int(np.argmin(lam))]
+    return np.stack([np.linalg.solve(L.T, Wx @ p3), np.linalg.solve(L.T, Wy @ p3), p3])
+
+
+def dlt_pose(o, xy, method="svd"):
+    """The start of step 2: pose (6,) or None (DEGENERATE)."""
+    Xt, mean, sigma = dlt_rows(o, xy)
+    if not np.all(np.isfinite(Xt)):
+        return None
+    if chol4(Xt.T @ Xt / len(Xt)) is None:         # the pivot test defines DEGENERATE for both methods
+        return None
+    P = dlt_matrix(Xt, xy, method)
+    if P is None or not np.all(np.isfinite(P)):
+        return None
+    if np.linalg.det(P[:, :3]) < 0.0:
+        P = -P
+    U, s, Vt = np.linalg.svd(P[:, :3])
+    if not s[2] > RANK_TOL * s[0]:
+        return None
+    R = U @ Vt
+    t = sigma * (P[:, 3] / s.mean()) - R @ mean
+    pose = np.concatenate([log_map(R), t])
+    return pose if np.all(np.isfinite(pose)) else None
+
+
+def sums_at(o, pose, loss, f_scale, min_depth):
+    """H, g, cost over the observations in front of the camera at ``pose``."""
+    r, J, depth = o.project(pose)
+    front = depth > min_depth
+    r, J = r[front], J[front]
+    term, w = loss_terms(loss, r, f_scale)
+    H = np.einsum("nri,nr,nrj->ij", J, w, J)
+    g = np.einsum("nri,nr->i", J, w * r)
+    return dict(H=H, g=g, cost=float(term.sum()), absgrad=np.einsum("nri,nr->i", np.abs(J), np.abs(w * r)))
+
+
+def refine(o, pose, loss="linear", f_scale=1.0, iters=20, min_depth=0.0):
+    """-> (pose, sums at pose, degenerate)."""
+    x = np.asarray(pose, dtype=np.float64)
+    cur = sums_at(o, x, loss, f_scale, min_depth)
+    lam = 1e-4
+    for _ in range(iters):
+        Hd = cur["H"] + lam * np.diag(np.diag(cur["H"]))
+        try:
+            with np.errstate(all="ignore"):
+                if not np.all(np.isfinite(Hd)) or not np.all(np.diag(Hd) > 0.0):
+                    raise np.linalg.LinAlgError
+                L = np.linalg.cholesky(Hd)
+        except np.linalg.LinAlgError:
+            return x, cur, True
+        dx = -np.linalg.solve(L.T, np.linalg.solve(L, cur["g"]))
+        xt = x + dx
+        small = np.sqrt(dx @ dx) <= 1e-14 * np.sqrt(x @ x)
+        trial = sums_at(o, xt, loss, f_scale, min_depth)
+        if trial["cost"] <= cur["cost"] * (1.0 + COST_SLACK):
+            x, cur, lam = xt, trial, max(0.1 * lam, 1e-12)
+        else:
+            lam *= 10.0
+        if small:
+            break
+    return x, cur, False
+
+
+def resect(o, current, loss="linear", f_scale=1.0, refine_iters=20, init="dlt", min_inliers=6, max_reproj_px=0.0,
+           max_rms_px=0.0, min_depth=0.0, x0=None, dlt_method="svd"):
+    """One camera: dict(pose, status, n_inliers, rms_px, max_px).  x0: start the refinement there instead of at the DLT."""
+    current = np.asarray(current, dtype=np.float64)
+    bad = dict(pose=current, n_inliers=0, rms_px=np.nan, max_px=np.nan)
+    xy, ok = o.bearings()
+    o, xy = o.keep(ok), xy[ok]
+    n = len(o.uv)
+    if n < (6 if init == "dlt" else 3):
+        return dict(bad, status=FEW_POINTS)
+    if init == "dlt":
+        pose = dlt_pose(o, xy, dlt_method)
+        if pose is None:
+            return dict(bad, status=DEGENERATE)
+    else:
+        pose = current
+    if x0 is not None:
+        pose = np.asarray(x0, dtype=np.float64)
+    pose, _, degenerate = refine(o, pose, loss, f_scale, refine_iters, min_depth)
+    r, _, depth = o.project(pose)
+    front = depth > min_depth
+    e = np.sqrt((r * r).sum(axis=1))
+    inl = front & (e <= max_reproj_px) if max_reproj_px > 0.0 else front
+    over = inl if inl.any() else front
+    rms = np.sqrt((e[over] ** 2).sum() / over.sum()) if over.any() else np.nan
+    emax = e[over].max() if over.any() else np.nan
+    status = OK
+    if degenerate:
+        status = DEGENERATE
+    elif 2 * int((~front).sum()) > n:
+        status = BEHIND
+    elif int(inl.sum()) < min_inliers:
+        status = FEW_INLIERS
+    elif max_rms_px > 0.0 and not rms <= max_rms_px:
+        status = HIGH_ERROR
+    return dict(pose=pose, status=status, n_inliers=int(inl.sum()), rms_px=rms, max_px=emax)
+
+
+def obs_of(prob, c, known=None):
+    """The Obs of camera c of a BAProblem (pinhole) or a BALProblem (cams (Nc, 9)), over the known points."""
+    sel = prob.cam_idx == c
+    if known is not None:
+        sel &= np.asarray(known, dtype=bool)[prob.pt_idx]
+    X, uv = prob.pts[prob.pt_idx[sel]], prob.uv[sel]
+    if prob.cams.shape[1] == 9:
+        return Obs(X, uv, intr=prob.cams[c, 6:9])
+    return Obs(X, uv, K4=np.asarray(prob.K4, dtype=np.float64))
+
+
+def resect_cameras(prob, cams=None, known=None, x0=None, **opts):
+    """Every camera (or the listed ones) of a problem: dict of arrays poses (n, 6), status, n_inliers, rms_px, max_px."""
+    cs = range(prob.n_cams) if cams is None else cams
+    res = [resect(obs_of(prob, c, known), prob.cams[c, :6], x0=None if x0 is None else x0[c], **opts) for c in cs]
+    return dict(poses=np.array([r["pose"] for r in res]).reshape(-1, 6), status=np.array([r["status"] for r in res], dtype=np.uint8),
+                n_inliers=np.array([r["n_inliers"] for r in res], dtype=np.int32), rms_px=np.array([r["rms_px"] for r in res]),
+                max_px=np.array([r["max_px"] for r in res]))
