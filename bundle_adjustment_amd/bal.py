@@ -271,6 +271,18 @@ def resect(prob: BALProblem, device=0, write=True, cams=None, known_points=None,
     return out, BALProblem(np.concatenate([cams6, intr], axis=1), prob.pts.copy(), prob.cam_idx.copy(), prob.pt_idx.copy(), prob.uv.copy())
 
 
+def resect_ransac(prob: BALProblem, device=0, write=True, cams=None, known_points=None, **opts):
+    """Resect the cameras of a BAL problem from raw matches (``ba_resect_ransac``; cams, known_points and opts as
+    ``hip_backend.Solver.resect_ransac``).  Returns ``(out, problem)`` like ``resect``; ``out["obs_inlier"]`` is the consensus
+    set in ``prob``'s observation order, what ``triangulation.filter_observations`` takes."""
+    from . import hip_backend
+    with hip_backend.Solver(device) as s:
+        intr = s._set_bal(prob)
+        out = s.resect_ransac(intr=intr, cams=cams, known_points=known_points, write_cams=int(bool(write)), **opts)
+        cams6 = s.get_params()[0]
+    return out, BALProblem(np.concatenate([cams6, intr], axis=1), prob.pts.copy(), prob.cam_idx.copy(), prob.pt_idx.copy(), prob.uv.copy())
+
+
 def align(prob: BALProblem, cam_ref=None, pt_ref=None, cam_w=None, pt_w=None, loss="linear", f_scale=1.0, iters=10,
           with_scale=True, device=0):
     """Align a BAL problem to reference positions: the similarity ``X' = s R X + t`` that brings its camera centres

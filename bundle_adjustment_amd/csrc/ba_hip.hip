@@ -40,6 +40,7 @@
 #include "ba_tracks.hpp"
 #include "ba_similarity.hpp"
 #include "ba_resect.hpp"
+#include "ba_ransac.hpp"
 
 using namespace ba;
 
@@ -68,7 +69,7 @@ extern "C" const char* ba_last_error(void) { return g_err.c_str(); }
 
 static const char* kKernelNames[BA_PROFILE_SLOTS] = {
     "cam_prepare", "residual_cam", "linearize_cam", "linearize_pt", "point_invert", "schur_pt",
-    "schur_cam", "pcg_step", "precond", "backsub_pt", "misc", "allreduce", "schur_pt_then_backsub", "tracks", "resect", ""};
+    "schur_cam", "pcg_step", "precond", "backsub_pt", "misc", "allreduce", "schur_pt_then_backsub", "tracks", "resect", "resect_ransac"};
 extern "C" const char* ba_kernel_name(int slot) {
   return (slot >= 0 && slot < BA_PROFILE_SLOTS) ? kKernelNames[slot] : "";
 }
@@ -272,6 +273,15 @@ struct ba_handle {
   DBuf<unsigned char> rs_known_in, rs_known, rs_sel;
   ResectArgs rs_args = {};
   bool rs_valid = false, rs_bal = false;
+  // ba_resect_ransac (ba_ransac.hpp): the usable observations' records and their count per camera, the score blocks' best
+  // hypotheses, the consensus bytes (camera order), obs_inlier (caller's order), and its own copies of what ba_resect keeps
+  // (results, BAL intrinsics, pt_known in point-slot order, cam_sel; rs_known_in is staging and shared); the launch
+  // arguments of the last call (what ba_time_kernel(BA_K_RESECT_RANSAC) repeats)
+  DBuf<double> rn_rec, rn_best, rn_out, rn_intr;
+  DBuf<int> rn_cnt;
+  DBuf<unsigned char> rn_cons, rn_inl, rn_known, rn_sel;
+  RansacArgs rn_args = {};
+  bool rn_valid = false, rn_bal = false;
   // ba_transform / ba_align / ba_get_centres (ba_similarity.hpp): correspondences a | b | w | u | err (9 doubles each), the
   // per-workgroup partial rows, the device record (similarity, centroids, status)
   DBuf<double> sim_buf, sim_part;
@@ -1478,6 +1488,7 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
   clear_shared(h);                   // ... and every camera with its own intrinsics
   h->trk_valid = false;
   h->rs_valid = false;
+  h->rn_valid = false;
   {   // index ranges, before anything is touched (a rejected call keeps the previous problem): branch-free sweep first
     int ok = 1;
     for (int64_t i = 0; i < n_obs; ++i)
@@ -3519,6 +3530,117 @@ extern "C" int ba_resect(ba_handle* h, const double* intr, const ba_resect_optio
   return BA_OK;
 }
 
+// ------------------------------------------------------------------------------------------------- RANSAC resection
+// ba_resect_ransac (csrc/ba_ransac.hpp): usable observations, hypotheses and scores, local optimisation.  Local to the rank.
+static int launch_ransac(ba_handle* h) {
+  RansacArgs& a = h->rn_args;
+  a.r.t.cs = h->cs[h->cur].p; a.r.cams = h->cams[h->cur].p; a.r.ptab = h->ptab[h->cur].p;
+  if (h->Nc == 0) return BA_OK;
+  if (a.inl && h->Nobs > 0) HIPCHECK(hipMemsetAsync(a.inl, 0, (size_t)h->Nobs, h->stream));
+  const dim3 gc(h->Nc), gs(h->Nc, a.n_blk), b(RN_THREADS);
+  if (h->rn_bal) {
+    BA_LAUNCH(k_ransac_prep<BalCam>, gc, b, 0, h->stream, a);
+    BA_LAUNCH(k_ransac_score<BalCam>, gs, b, 0, h->stream, a);
+    BA_LAUNCH(k_ransac_lo<BalCam>, gc, b, 0, h->stream, a);
+  } else {
+    BA_LAUNCH(k_ransac_prep<Pinhole>, gc, b, 0, h->stream, a);
+    BA_LAUNCH(k_ransac_score<Pinhole>, gs, b, 0, h->stream, a);
+    BA_LAUNCH(k_ransac_lo<Pinhole>, gc, b, 0, h->stream, a);
+  }
+  return BA_OK;
+}
+extern "C" int ba_default_ransac_options(ba_ransac_options* o) {
+  if (!o) return fail(BA_ERR_INVALID, "null argument");
+  memset(o, 0, sizeof *o);
+  o->n_hyp = 256;
+  o->lo_rounds = 2;
+  o->max_reproj_px = 4.0;
+  o->loss = BA_LOSS_LINEAR;
+  o->refine_iters = 20;
+  o->f_scale = 1.0;
+  o->min_inliers = 6;
+  return BA_OK;
+}
+extern "C" int ba_resect_ransac(ba_handle* h, const double* intr, const ba_ransac_options* opts, const uint8_t* cam_sel, const uint8_t* pt_known,
+                                double* poses, uint8_t* status, int32_t* n_inliers, double* rms_px, double* max_px, uint8_t* obs_inlier) {
+  if (!h || !opts) return fail(BA_ERR_INVALID, "null argument");
+  if (!h->have_problem || !h->have_params) return fail(BA_ERR_STATE, "ba_resect_ransac: ba_set_problem / ba_set_params first");
+  if (opts->n_hyp < 1 || opts->n_hyp > RN_MAX_HYP) return fail(BA_ERR_INVALID, "ba_resect_ransac: n_hyp %d is outside 1 .. %d", opts->n_hyp, RN_MAX_HYP);
+  if (opts->lo_rounds < 0) return fail(BA_ERR_INVALID, "ba_resect_ransac: lo_rounds must not be negative");
+  if (!(opts->max_reproj_px > 0)) return fail(BA_ERR_INVALID, "ba_resect_ransac: max_reproj_px must be positive");
+  if (!loss_valid(opts->loss)) return fail(BA_ERR_INVALID, "ba_resect_ransac: unknown loss %d", opts->loss);
+  if (!(opts->f_scale > 0)) return fail(BA_ERR_INVALID, "ba_resect_ransac: f_scale must be positive");
+  if (opts->refine_iters < 0) return fail(BA_ERR_INVALID, "ba_resect_ransac: refine_iters must not be negative");
+  if (opts->min_inliers < 0) return fail(BA_ERR_INVALID, "ba_resect_ransac: min_inliers must not be negative");
+  if (opts->write_cams && any_prior(h))
+    return fail(BA_ERR_STATE, "ba_resect_ransac with write_cams = 1: priors are set (ba_set_priors) and their means were set for the old poses: "
+                              "resect first, set the priors afterwards");
+  if (set_device(h)) return BA_ERR_HIP;
+  const int Nc = h->Nc, Np = h->Np;
+  const size_t nc1 = (size_t)std::max(Nc, 1), np1 = (size_t)std::max(Np, 1), no1 = (size_t)std::max<long long>(h->Nobs, 1);
+  const int n_blk = (opts->n_hyp + RN_THREADS - 1) / RN_THREADS;
+  HIPCHECK(h->rn_out.alloc(RS_OUT * nc1));
+  HIPCHECK(h->rn_rec.alloc(RN_REC * no1)); HIPCHECK(h->rn_cnt.alloc(nc1)); HIPCHECK(h->rn_best.alloc(RN_BEST * nc1 * n_blk));
+  HIPCHECK(h->rn_cons.alloc(no1)); HIPCHECK(h->rn_inl.alloc(no1));
+  if (intr) {
+    HIPCHECK(h->rn_intr.alloc(3 * nc1));
+    HIPCHECK(hipMemcpyAsync(h->rn_intr.p, intr, 3 * (size_t)Nc * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  }
+  if (cam_sel) {
+    HIPCHECK(h->rn_sel.alloc(nc1));
+    HIPCHECK(hipMemcpyAsync(h->rn_sel.p, cam_sel, (size_t)Nc, hipMemcpyHostToDevice, h->stream));
+  }
+  if (pt_known && Np > 0) {
+    HIPCHECK(h->rs_known_in.alloc(np1)); HIPCHECK(h->rn_known.alloc(np1));
+    HIPCHECK(hipMemcpyAsync(h->rs_known_in.p, pt_known, (size_t)Np, hipMemcpyHostToDevice, h->stream));
+    BA_LAUNCH(k_resect_known, dim3((Np + 255) / 256), dim3(256), 0, h->stream, (const unsigned char*)h->rs_known_in.p, (const int*)h->slot.p, Np,
+              h->rn_known.p);
+  }
+  RansacArgs& a = h->rn_args;
+  a = RansacArgs{};
+  a.r.t.intr = intr ? h->rn_intr.p : nullptr;
+  a.r.t.uv = uv_arr(h, h->c_uv);
+  a.r.t.fx = h->K4[0]; a.r.t.fy = h->K4[1]; a.r.t.cx = h->K4[2]; a.r.t.cy = h->K4[3];
+  a.r.t.loss = opts->loss; a.r.t.iters = opts->refine_iters;
+  a.r.t.fscale = opts->f_scale; a.r.t.max_px = opts->max_reproj_px; a.r.t.min_depth = opts->min_depth;
+  a.r.offk = h->offk.p; a.r.c_pt = h->c_pt.p;
+  a.r.known = (pt_known && Np > 0) ? h->rn_known.p : nullptr;
+  a.r.sel = cam_sel ? h->rn_sel.p : nullptr;
+  a.r.init = RS_INIT_CURRENT; a.r.min_inliers = opts->min_inliers; a.r.max_rms = opts->max_rms_px;
+  a.r.out = h->rn_out.p;
+  a.n_hyp = opts->n_hyp; a.lo_rounds = opts->lo_rounds; a.n_blk = n_blk; a.seed = opts->seed;
+  a.rec = h->rn_rec.p; a.cnt = h->rn_cnt.p; a.best = h->rn_best.p; a.cons = h->rn_cons.p;
+  a.c_orig = h->c_orig.p; a.inl = h->rn_inl.p;
+  h->rn_bal = intr != nullptr;
+  h->rn_valid = true;
+  if (int rc = launch_ransac(h)) return rc;
+  std::vector<double> res(RS_OUT * (size_t)Nc);
+  if (Nc > 0) HIPCHECK(hipMemcpyAsync(res.data(), h->rn_out.p, res.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (obs_inlier && Nc > 0 && h->Nobs > 0) HIPCHECK(hipMemcpyAsync(obs_inlier, h->rn_inl.p, (size_t)h->Nobs, hipMemcpyDeviceToHost, h->stream));
+  if (opts->write_cams) {
+    // as ba_resect: what ba_set_params(merged cameras, points as they are) leaves behind
+    const int nmax = std::max(Nc, Np);
+    if (nmax > 0)
+      BA_LAUNCH(k_resect_merge, dim3((nmax + 255) / 256), dim3(256), 0, h->stream, (const double*)h->rn_out.p, a.r.sel, cam_held_ptr(h), h->fixed,
+                (const double*)h->cams[h->cur].p, Nc, h->cams[0].p, (const double*)h->ptab[h->cur].p, Np, h->ptab[0].p);
+    h->cur = 0;
+    BA_LAUNCH(k_cam_prepare<Pinhole>, dim3((Nc + 63) / 64), dim3(64), 0, h->stream, h->cams[0].p, (const double*)h->intr[0].p,
+              h->cs[0].p, h->camA[0].p, Nc);
+    h->linearized = false;
+  }
+  BA_SYNC(h);
+  if (obs_inlier && (Nc == 0) && h->Nobs > 0) memset(obs_inlier, 0, (size_t)h->Nobs);
+  for (int c = 0; c < Nc; ++c) {
+    const double* r = res.data() + RS_OUT * (size_t)c;
+    if (poses) memcpy(poses + 6 * (size_t)c, r, 6 * sizeof(double));
+    if (status) status[c] = (uint8_t)(int)r[6];
+    if (n_inliers) n_inliers[c] = (int32_t)r[7];
+    if (rms_px) rms_px[c] = r[8];
+    if (max_px) max_px[c] = r[9];
+  }
+  return BA_OK;
+}
+
 // ------------------------------------------------------------------------------------------------- similarity
 // ba_get_centres, ba_transform, ba_align (csrc/ba_similarity.hpp).  Local to the rank: no collective.
 extern "C" int ba_get_centres(ba_handle* h, double* centres) {
@@ -3701,6 +3823,7 @@ extern "C" int ba_time_kernel(ba_handle* h, int slot, int reps, double* mean_us)
   if (!h->have_params) return fail(BA_ERR_STATE, "no parameters set");
   if (slot == BA_K_TRACKS && !h->trk_valid) return fail(BA_ERR_STATE, "BA_K_TRACKS repeats the last ba_triangulate_tracks: call it first");
   if (slot == BA_K_RESECT && !h->rs_valid) return fail(BA_ERR_STATE, "BA_K_RESECT repeats the last ba_resect: call it first");
+  if (slot == BA_K_RESECT_RANSAC && !h->rn_valid) return fail(BA_ERR_STATE, "BA_K_RESECT_RANSAC repeats the last ba_resect_ransac: call it first");
   if (set_device(h)) return BA_ERR_HIP;
   const bool saved = h->profile;
   h->profile = false;
@@ -3726,6 +3849,7 @@ extern "C" int ba_time_kernel(ba_handle* h, int slot, int reps, double* mean_us)
       case BA_K_POINT_INVERT: launch_point_invert(h, 1e-4); break;
       case BA_K_TRACKS: launch_tracks(h); break;
       case BA_K_RESECT: launch_resect(h); break;
+      case BA_K_RESECT_RANSAC: (void)launch_ransac(h); break;
       default: break;
     }
   };

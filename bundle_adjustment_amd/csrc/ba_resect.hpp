@@ -257,13 +257,16 @@ __device__ __forceinline__ void rs_pose(const double (&x)[6], double (&cam)[CM::
   for (int q = 0; q < 9; ++q) M[q] = st[12 + q];
 }
 
-// the sums of a refinement pass at the pose in cam / M: H, g (in the additive coordinates rvec | t) and the cost
-template <class CM>
+// the sums of a refinement pass at the pose in cam / M: H, g (in the additive coordinates rvec | t) and the cost.  CONS (the
+// local optimisation of ba_ransac.hpp): over the observations j with cons[j] != 0 only; ba_resect's own passes have no such test
+template <class CM, bool CONS = false>
 __device__ __forceinline__ void rs_pass(const ResectArgs& a, const double (&cam)[CM::CAM], const double (&M)[9], const int beg,
-                                        const int end, double (&acc)[RS_NSUM], double* __restrict__ lds) {
+                                        const int end, double (&acc)[RS_NSUM], double* __restrict__ lds,
+                                        const unsigned char* __restrict__ cons = nullptr) {
 #pragma unroll
   for (int q = 0; q < RS_NSUM; ++q) acc[q] = 0.0;
   for (int j = beg + (int)threadIdx.x; j < end; j += RS_THREADS) {
+    if constexpr (CONS) { if (!cons[j]) continue; }
     double X[3], bx, by;
     double2 uv;
     if (!rs_obs<CM>(a, cam, j, X, uv, bx, by)) continue;

@@ -89,6 +89,12 @@ class BAResectOptions(C.Structure):
                 ("write_cams", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class BARansacOptions(C.Structure):
+    _fields_ = [("n_hyp", C.c_int32), ("lo_rounds", C.c_int32), ("seed", C.c_uint64), ("max_reproj_px", C.c_double),
+                ("loss", C.c_int32), ("refine_iters", C.c_int32), ("f_scale", C.c_double), ("min_inliers", C.c_int32),
+                ("write_cams", C.c_int32), ("max_rms_px", C.c_double), ("min_depth", C.c_double)]
+
+
 class BASimilarity(C.Structure):
     _fields_ = [("s", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3)]
 
@@ -107,6 +113,7 @@ RESECT_STATUS = {"ok": 0, "few_points": 1, "degenerate": 2, "behind": 3, "few_in
 RESECT_INIT = {"dlt": 0, "current": 1}   # enum ba_resect_init
 K_TRACKS = 13
 K_RESECT = 14
+K_RESECT_RANSAC = 15
 
 _lib = None
 
@@ -150,6 +157,9 @@ SYMBOLS = {
     "ba_default_resect_options": (C.c_int, [C.POINTER(BAResectOptions)]),
     "ba_resect": (C.c_int, [C.c_void_p, _DP, C.POINTER(BAResectOptions), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _DP,
                             C.POINTER(C.c_uint8), _IP, _DP, _DP]),
+    "ba_default_ransac_options": (C.c_int, [C.POINTER(BARansacOptions)]),
+    "ba_resect_ransac": (C.c_int, [C.c_void_p, _DP, C.POINTER(BARansacOptions), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _DP,
+                                   C.POINTER(C.c_uint8), _IP, _DP, _DP, C.POINTER(C.c_uint8)]),
     "ba_get_centres": (C.c_int, [C.c_void_p, _DP]),
     "ba_transform": (C.c_int, [C.c_void_p, C.POINTER(BASimilarity)]),
     "ba_default_align_options": (C.c_int, [C.POINTER(BAAlignOptions)]),
@@ -636,6 +646,18 @@ class Solver:
             setattr(o, k, v)
         return o
 
+    @staticmethod
+    def _mask(m, n):
+        """A bool (n,) mask or a list of indices -> (uint8 array, its pointer); None -> (None, None)."""
+        if m is None:
+            return None, None
+        m = np.asarray(m)
+        if m.dtype != np.bool_:
+            idx, m = m.astype(np.int64).reshape(-1), np.zeros(n, dtype=bool)
+            m[idx] = True
+        a = np.ascontiguousarray(m.reshape(n), dtype=np.uint8)
+        return a, a.ctypes.data_as(C.POINTER(C.c_uint8))
+
     def resect(self, intr=None, cams=None, known_points=None, **opts):
         """ba_resect: the pose of every selected camera of the resident problem from its observations of the known points,
         the current points taken as they are (intr None: pinhole; else (Nc, 3) (f, k1, k2) of the BAL camera).  cams: bool
@@ -647,18 +669,8 @@ class Solver:
         if intr is not None:
             intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
             ip = _dp(intr)
-
-        def mask(m, n):
-            if m is None:
-                return None, None
-            m = np.asarray(m)
-            if m.dtype != np.bool_:
-                idx, m = m.astype(np.int64).reshape(-1), np.zeros(n, dtype=bool)
-                m[idx] = True
-            a = np.ascontiguousarray(m.reshape(n), dtype=np.uint8)
-            return a, a.ctypes.data_as(C.POINTER(C.c_uint8))
-        sel, selp = mask(cams, self.n_cams)
-        known, knownp = mask(known_points, self.n_pts)
+        sel, selp = self._mask(cams, self.n_cams)
+        known, knownp = self._mask(known_points, self.n_pts)
         o = self.resect_options(**opts)
         n = self.n_cams
         out = dict(poses=np.empty((n, 6)), status=np.empty(n, dtype=np.uint8), n_inliers=np.empty(n, dtype=np.int32),
@@ -666,6 +678,42 @@ class Solver:
         _check(self._lib.ba_resect(self._h, ip, C.byref(o), selp, knownp, _dp(out["poses"]),
                                    out["status"].ctypes.data_as(C.POINTER(C.c_uint8)), out["n_inliers"].ctypes.data_as(_IP),
                                    _dp(out["rms_px"]), _dp(out["max_px"])))
+        return out
+
+    def ransac_options(self, **kw) -> BARansacOptions:
+        """ba_default_ransac_options overlaid with kw (loss by name or by value, any other ba_ransac_options field)."""
+        o = BARansacOptions()
+        _check(self._lib.ba_default_ransac_options(C.byref(o)))
+        for k, v in kw.items():
+            if k == "loss":
+                v = loss_code(v)
+            if not hasattr(o, k):
+                raise TypeError(f"unknown option {k}")
+            setattr(o, k, v)
+        return o
+
+    def resect_ransac(self, intr=None, cams=None, known_points=None, **opts):
+        """ba_resect_ransac: the pose of every selected camera from raw matches -- n_hyp minimal P3P samples per camera scored
+        on all of its observations of the known points, then lo_rounds of (consensus, refinement on it).  intr, cams and
+        known_points as ``resect``.  opts: n_hyp, lo_rounds, seed, max_reproj_px, loss, refine_iters, f_scale, min_inliers,
+        write_cams, max_rms_px, min_depth.  Returns ``resect``'s dict plus obs_inlier (n_obs,) bool in the order of the
+        problem's observations: the final consensus set, what to keep for the next solve
+        (``triangulation.filter_observations``)."""
+        ip = None
+        if intr is not None:
+            intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
+            ip = _dp(intr)
+        sel, selp = self._mask(cams, self.n_cams)
+        known, knownp = self._mask(known_points, self.n_pts)
+        o = self.ransac_options(**opts)
+        n = self.n_cams
+        out = dict(poses=np.empty((n, 6)), status=np.empty(n, dtype=np.uint8), n_inliers=np.empty(n, dtype=np.int32),
+                   rms_px=np.empty(n), max_px=np.empty(n))
+        inl = np.zeros(self.n_obs, dtype=np.uint8)
+        _check(self._lib.ba_resect_ransac(self._h, ip, C.byref(o), selp, knownp, _dp(out["poses"]),
+                                          out["status"].ctypes.data_as(C.POINTER(C.c_uint8)), out["n_inliers"].ctypes.data_as(_IP),
+                                          _dp(out["rms_px"]), _dp(out["max_px"]), inl.ctypes.data_as(C.POINTER(C.c_uint8))))
+        out["obs_inlier"] = inl.astype(bool)
         return out
 
     def centres(self):

@@ -103,6 +103,36 @@ def resect_cameras(prob, solver=None, write=True, cams=None, known_points=None, 
     return out, dataclasses.replace(prob, cams=merged)
 
 
+def resect_cameras_ransac(prob, solver=None, write=True, cams=None, known_points=None, **opts):
+    """Resect the cameras of a pinhole ``BAProblem`` from raw matches (``ba_resect_ransac``; cams, known_points and opts as
+    ``hip_backend.Solver.resect_ransac``: n_hyp, lo_rounds, seed, max_reproj_px, loss, refine_iters, f_scale, min_inliers,
+    max_rms_px, min_depth).  Returns ``(out, problem)`` like ``resect_cameras``; ``out["obs_inlier"]`` is the consensus set in
+    ``prob``'s observation order, what ``filter_observations`` takes."""
+    import dataclasses
+    own = solver is None
+    s = hip_backend.Solver(0) if own else solver
+    try:
+        s.set_problem(prob)
+        out = s.resect_ransac(cams=cams, known_points=known_points, write_cams=int(bool(write)), **opts)
+        merged = s.get_params()[0]
+    finally:
+        if own:
+            s.close()
+    return out, dataclasses.replace(prob, cams=merged)
+
+
+def filter_observations(prob, keep):
+    """Drop the observations where ``keep`` (bool (n_obs,)) is false; the others keep their order, and cameras and points keep
+    their numbers (a point may be left with fewer than two observations: ``filter_tracks`` is the call for that).  ``prob``: a
+    ``BAProblem`` or a ``bal.BALProblem``.  Returns ``(new_problem, old_index_of_new_observation)``.  Pure numpy."""
+    import dataclasses
+    keep = np.asarray(keep)
+    if keep.dtype != np.bool_ or keep.shape != (prob.n_obs,):
+        raise ValueError(f"keep must be a bool array of shape ({prob.n_obs},), not {keep.dtype} {keep.shape}")
+    old = np.nonzero(keep)[0]
+    return dataclasses.replace(prob, cam_idx=prob.cam_idx[old].copy(), pt_idx=prob.pt_idx[old].copy(), uv=prob.uv[old].copy()), old
+
+
 def filter_tracks(prob, keep):
     """Drop the points where ``keep`` (bool (Np,)) is false together with their observations and renumber ``pt_idx``; the
     remaining observations keep their order.  ``prob``: a ``BAProblem`` or a ``bal.BALProblem``.  Returns

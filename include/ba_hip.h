@@ -144,7 +144,8 @@ enum ba_kernel_slot {
   BA_K_PRECOND = 8, BA_K_BACKSUB = 9, BA_K_MISC = 10, BA_K_ALLREDUCE = 11,
   BA_K_SCHUR_PT_BACKSUB = 12,  /* launches of the PCG point pass that found PCG finished and went on as the back substitution */
   BA_K_TRACKS = 13,            /* ba_time_kernel only: the kernels of the last ba_triangulate_tracks call, with its options */
-  BA_K_RESECT = 14             /* ba_time_kernel only: the kernel of the last ba_resect call, with its options and masks */
+  BA_K_RESECT = 14,            /* ba_time_kernel only: the kernel of the last ba_resect call, with its options and masks */
+  BA_K_RESECT_RANSAC = 15      /* ba_time_kernel only: the three kernels of the last ba_resect_ransac call, likewise */
 };
 
 /* Event counters of a handle (ba_get_stat): which implementation served the window-sized solves, how often the
@@ -237,6 +238,7 @@ int ba_triangulate_tracks(ba_handle* h, const double* intr, const ba_track_optio
  * image registration, OpenMVG's resection, the tracking / relocalisation pose of ORB-SLAM; no reference counterpart).  The
  * points are the handle's CURRENT points and are treated as known: held masks, fixed_cam, priors and shared-intrinsics groups
  * play no part in the estimate.  No RANSAC and no minimal solver: a linear start on all observations, then a robust refinement.
+ * (ba_resect_ransac below is the call for raw matches: minimal samples, consensus, then this refinement on the consensus set.)
  *   intr      NULL: the pinhole with the handle's K4; else (f, k1, k2)[Nc] of the BAL camera, as in ba_triangulate_tracks;
  *             read, never changed
  *   cam_sel   uint8[Nc] or NULL = every camera: which cameras to resect.  A camera that is not selected gets its current
@@ -290,6 +292,55 @@ typedef struct ba_resect_options {
 int ba_default_resect_options(ba_resect_options* opts);   /* linear, 20, 1.0, DLT, 6, 0, 0, 0.0, 0 */
 int ba_resect(ba_handle* h, const double* intr, const ba_resect_options* opts, const uint8_t* cam_sel, const uint8_t* pt_known,
               double* poses, uint8_t* status, int32_t* n_inliers, double* rms_px, double* max_px);
+/* RANSAC resection: the pose of every selected camera from raw matches, a share of which may be wrong (the reference's
+ * estimate_pose_pnp: cv2.solvePnPRansac; the image registration of COLMAP, OpenMVG, ORB-SLAM).  intr, cam_sel, pt_known, poses,
+ * status (ba_resect_status), n_inliers, rms_px, max_px and the rule for a camera that is not selected are ba_resect's.
+ *   obs_inlier  uint8[n_obs] in the caller's observation order (that of ba_residuals), or NULL: 1 for the observations of the
+ *               final consensus set -- the inliers counted in n_inliers -- and 0 for every other one: observations of cameras
+ *               that are not selected, of points that are not known, those whose bearing failed, and those of a camera whose
+ *               status is FEW_POINTS or DEGENERATE without a pose.  What a pipeline deletes before the next solve.
+ * Per selected camera, over its n usable observations (point known, bearing exists), indexed 0 .. n - 1 in the handle's
+ * camera-ordered list (within a camera: the caller's order):
+ * (1) n < 4: FEW_POINTS (three points reproduce themselves; a fourth chooses among P3P's solutions).
+ * (2) Hypothesis h = 0 .. n_hyp - 1 draws three distinct indices.  mix(z) is the splitmix64 finaliser: z ^= z >> 30;
+ * z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31.  With G = 0x9E3779B97F4A7C15 and everything
+ * modulo 2^64: k = mix(mix(mix(seed + G) + camera) + h), draw_d = mix(k + (d + 1) G) for d = 0, 1, 2, and
+ * i_d = floor(draw_d (n - d) / 2^64).  Then i_1 += 1 if i_1 >= i_0; i_2 += 1 if i_2 >= min(i_0, i_1), and again if then
+ * i_2 >= max(i_0, i_1).  No state is carried between hypotheses and nothing is retried: the samples are a pure function of
+ * (seed, camera index, h, n).
+ * (3) P3P on the three unit rays ((x, y, 1) of the bearing, normalised, towards the scene) and points, by Lambda Twist (Persson &
+ * Nordberg 2018): a cubic (closed form and four Newton steps), the eigen-decomposition of a singular symmetric 3 x 3 (cyclic
+ * Jacobi), two quadratics, three Newton steps on the three cosine-law equations per root, in fp64.  Up to four poses, numbered
+ * 2 * plane + root; a pose is kept when its three depths are > min_depth.  A triple with |d12 x d13| <= 1e-6 max |d_ij|^2
+ * (collinear or coincident), a vanishing cubic term or no real solution makes the hypothesis void.
+ * (4) Every pose is scored on all n observations through the camera model's own projection: sum of min(|r_i|^2, thr^2), thr =
+ * max_reproj_px, an observation at depth <= min_depth costs thr^2.  The lowest cost wins; ties go to the lower h, then to the
+ * lower pose number.  Every hypothesis void: DEGENERATE with the current pose, 0 inliers and NaN measures.
+ * (5) lo_rounds times: the consensus set = the usable observations in front of the camera with |r_i| <= thr at the round's
+ * starting pose; ba_resect's step (3) on that set only (loss, f_scale, refine_iters apply within it).  An empty set ends the
+ * rounds; a failed 6 x 6 pivot gives DEGENERATE with the last accepted pose and its measures.
+ * (6) ba_resect's steps (4) and (5) at the final pose with max_reproj_px = thr.
+ * write_cams as in ba_resect (the same merge, the same state afterwards, refused with BA_ERR_STATE naming "priors" while priors
+ * are set).  BA_ERR_STATE before ba_set_problem / ba_set_params.  BA_ERR_INVALID, naming the field: n_hyp outside 1 .. 4096,
+ * lo_rounds < 0, max_reproj_px not > 0, an unknown loss, f_scale not > 0, refine_iters < 0, min_inliers < 0.  Results are
+ * bit-reproducible from call to call (fixed-order sums, no atomics, one lexicographic arg-min).  Multi-rank jobs: local to the
+ * calling rank's shard, no collective; untested on more than one rank. */
+typedef struct ba_ransac_options {
+  int32_t  n_hyp;          /* minimal samples per camera, 1 .. 4096; default 256 */
+  int32_t  lo_rounds;      /* rounds of (consensus at the current pose, refinement on it); default 2; 0 = the best raw hypothesis */
+  uint64_t seed;           /* default 0 */
+  double   max_reproj_px;  /* consensus and inlier threshold; must be > 0; default 4.0 */
+  int32_t  loss;           /* ba_loss of the refinement ON THE CONSENSUS SET; default linear */
+  int32_t  refine_iters;   /* per round; default 20 */
+  double   f_scale;        /* default 1.0 */
+  int32_t  min_inliers;    /* default 6 */
+  int32_t  write_cams;     /* as ba_resect */
+  double   max_rms_px;     /* as ba_resect; <= 0: no test */
+  double   min_depth;      /* as ba_resect */
+} ba_ransac_options;
+int ba_default_ransac_options(ba_ransac_options* opts);   /* 256, 2, 0, 4.0, linear, 20, 1.0, 6, 0, 0.0, 0.0 */
+int ba_resect_ransac(ba_handle* h, const double* intr, const ba_ransac_options* opts, const uint8_t* cam_sel, const uint8_t* pt_known,
+                     double* poses, uint8_t* status, int32_t* n_inliers, double* rms_px, double* max_px, uint8_t* obs_inlier);
 /* Similarity transform of the reconstruction and robust alignment to reference positions: the step after an adjustment that
  * moves the result into the frame its user needs (georegistration onto GPS / surveyed camera positions or ground-control
  * points -- COLMAP's model_aligner; the comparison of two gauge-free solves; re-centring / re-scaling).  No reference
@@ -545,7 +596,7 @@ int ba_reset_profile(ba_handle* h);
 /* Bench hook: run one kernel `reps` times back to back on the solver stream between two
  * HIP events and return the mean duration in microseconds (state left as it was).  BA_K_TRACKS: every kernel of the last
  * ba_triangulate_tracks call (BA_ERR_STATE without one since ba_set_problem), at the current cameras.  BA_K_RESECT: the same
- * for the last ba_resect call (its write-back is not repeated). */
+ * for the last ba_resect call (its write-back is not repeated), and BA_K_RESECT_RANSAC for the last ba_resect_ransac call. */
 int ba_time_kernel(ba_handle* h, int slot, int reps, double* mean_us);
 
 #ifdef __cplusplus
