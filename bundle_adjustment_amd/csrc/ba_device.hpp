@@ -68,6 +68,13 @@ __device__ inline void camera_state(const double* __restrict__ cam, double* __re
   cs[21] = 0; cs[22] = 0; cs[23] = 0;
 }
 
+// camera centre -R^T t from a camera's state
+__device__ inline void cam_centre(const double* __restrict__ cs_c, double* __restrict__ o3) {
+  o3[0] = -(cs_c[0] * cs_c[9] + cs_c[3] * cs_c[10] + cs_c[6] * cs_c[11]);
+  o3[1] = -(cs_c[1] * cs_c[9] + cs_c[4] * cs_c[10] + cs_c[7] * cs_c[11]);
+  o3[2] = -(cs_c[2] * cs_c[9] + cs_c[5] * cs_c[10] + cs_c[8] * cs_c[11]);
+}
+
 // ---- per-observation geometry ------------------------------------------------------
 // T = double everywhere except the PCG passes of jacobian_precision = 1 (config 5: Jacobian
 // blocks in fp32, every accumulation in fp64).

@@ -47,4 +47,31 @@ __device__ inline double wave_total_dpp(double x) {
   return __hiloint2double(hi, lo);
 }
 
+// Maximum / minimum of the wave, the same bits in every lane.  A lane without a source keeps its own value (`old` of the DPP
+// move): max(x, x) = min(x, x) = x, so one move serves both and neither needs a fill value or a sign of its inputs.
+template <int CTRL, int ROW_MASK>
+__device__ inline double dpp_keep_f64(double x) {
+  const int xl = __double2loint(x), xh = __double2hiint(x);
+  const int lo = __builtin_amdgcn_update_dpp(xl, xl, CTRL, ROW_MASK, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(xh, xh, CTRL, ROW_MASK, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+template <bool MAX, int CTRL, int ROW_MASK>
+__device__ inline double dpp_extremum_step(double x) {
+  const double y = dpp_keep_f64<CTRL, ROW_MASK>(x);
+  return MAX ? fmax(x, y) : fmin(x, y);
+}
+template <bool MAX>
+__device__ inline double wave_extremum_dpp(double x) {
+  x = dpp_extremum_step<MAX, DPP_ROW_SHR1, 0xf>(x);
+  x = dpp_extremum_step<MAX, DPP_ROW_SHR2, 0xf>(x);
+  x = dpp_extremum_step<MAX, DPP_ROW_SHR4, 0xf>(x);
+  x = dpp_extremum_step<MAX, DPP_ROW_SHR8, 0xf>(x);
+  x = dpp_extremum_step<MAX, DPP_ROW_BCAST15, 0xa>(x);
+  x = dpp_extremum_step<MAX, DPP_ROW_BCAST31, 0xc>(x);
+  return readlane_f64(x, 63);
+}
+__device__ inline double wave_max_dpp(double x) { return wave_extremum_dpp<true>(x); }
+__device__ inline double wave_min_dpp(double x) { return wave_extremum_dpp<false>(x); }
+
 }  // namespace ba

@@ -267,21 +267,23 @@ struct ba_handle {
   DBuf<unsigned char> trk_status;
   TrackArgs trk_args = {};
   bool trk_valid = false, trk_bal = false;
-  // ba_resect (ba_resect.hpp): per-camera results, the BAL intrinsics of the call, pt_known as given and in point-slot
-  // order, cam_sel; the launch arguments of the last call (what ba_time_kernel(BA_K_RESECT) repeats)
-  DBuf<double> rs_out, rs_intr;
-  DBuf<unsigned char> rs_known_in, rs_known, rs_sel;
-  ResectArgs rs_args = {};
-  bool rs_valid = false, rs_bal = false;
-  // ba_resect_ransac (ba_ransac.hpp): the usable observations' records and their count per camera, the score blocks' best
-  // hypotheses, the consensus bytes (camera order), obs_inlier (caller's order), and its own copies of what ba_resect keeps
-  // (results, BAL intrinsics, pt_known in point-slot order, cam_sel; rs_known_in is staging and shared); the launch
-  // arguments of the last call (what ba_time_kernel(BA_K_RESECT_RANSAC) repeats)
-  DBuf<double> rn_rec, rn_best, rn_out, rn_intr;
+  // What ba_resect (ba_resect.hpp) and ba_resect_ransac (ba_ransac.hpp) each keep of their last call: per-camera results, the
+  // BAL intrinsics of the call, pt_known in point-slot order, cam_sel, and the launch arguments (what
+  // ba_time_kernel(BA_K_RESECT / BA_K_RESECT_RANSAC) repeats).  rs_known_in, pt_known as given, is staging and shared.
+  struct ResectSet {
+    DBuf<double> out, intr;
+    DBuf<unsigned char> known, sel;
+    ResectArgs args = {};
+    bool valid = false, bal = false;
+  };
+  ResectSet rs, rn;
+  DBuf<unsigned char> rs_known_in;
+  // ba_resect_ransac's own: the usable observations' records and their count per camera, the score blocks' best hypotheses,
+  // the consensus bytes (camera order), obs_inlier (caller's order); rn_args.r is rn.args with the launch's pointers
+  DBuf<double> rn_rec, rn_best;
   DBuf<int> rn_cnt;
-  DBuf<unsigned char> rn_cons, rn_inl, rn_known, rn_sel;
+  DBuf<unsigned char> rn_cons, rn_inl;
   RansacArgs rn_args = {};
-  bool rn_valid = false, rn_bal = false;
   // ba_transform / ba_align / ba_get_centres (ba_similarity.hpp): correspondences a | b | w | u | err (9 doubles each), the
   // per-workgroup partial rows, the device record (similarity, centroids, status)
   DBuf<double> sim_buf, sim_part;
@@ -363,6 +365,13 @@ static void note_launch(ba_handle* h, const char* what) {
   do {                                        \
     hipLaunchKernelGGL(kern, __VA_ARGS__);    \
     note_launch(h, #kern);                    \
+  } while (0)
+// kern<BalCam> when bal, else kern<Pinhole>: the launches of the stand-alone features (tracks, resection), whose camera
+// model travels with the call
+#define BA_LAUNCH_CM(bal, kern, ...)                   \
+  do {                                                 \
+    if (bal) BA_LAUNCH(kern<BalCam>, __VA_ARGS__);     \
+    else BA_LAUNCH(kern<Pinhole>, __VA_ARGS__);        \
   } while (0)
 static int check_launches(ba_handle* h);
 // drain the stream, then report the first launch that failed since the last check (a refused launch leaves the
@@ -1487,8 +1496,8 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
   clear_priors(h);                   // ... and without priors
   clear_shared(h);                   // ... and every camera with its own intrinsics
   h->trk_valid = false;
-  h->rs_valid = false;
-  h->rn_valid = false;
+  h->rs.valid = false;
+  h->rn.valid = false;
   {   // index ranges, before anything is touched (a rejected call keeps the previous problem): branch-free sweep first
     int ok = 1;
     for (int64_t i = 0; i < n_obs; ++i)
@@ -3359,6 +3368,17 @@ extern "C" int ba_get_trace(ba_handle* h, ba_iter_record* out, int32_t capacity,
   return BA_OK;
 }
 
+// The end of every write_* / apply: parameter set 0, which the caller has just filled (cameras rvec | t and the point table),
+// becomes what ba_set_params would have left behind -- current, its camera state recomputed (prepared: already done, by
+// k_sim_cam_prepare), the linearisation forgotten
+static void adopt_set0(ba_handle* h, bool prepared = false) {
+  h->cur = 0;
+  if (!prepared)
+    BA_LAUNCH(k_cam_prepare<Pinhole>, dim3((h->Nc + 63) / 64), dim3(64), 0, h->stream, h->cams[0].p, (const double*)h->intr[0].p,
+              h->cs[0].p, h->camA[0].p, h->Nc);
+  h->linearized = false;
+}
+
 // ------------------------------------------------------------------------------------------------- tracks
 // ba_triangulate_tracks (csrc/ba_tracks.hpp): camera centres, the short-track launch over every point slot, the long-track
 // launch over long_pts, results back in the caller's point order.  Local to the rank: no collective.
@@ -3368,13 +3388,11 @@ static void launch_tracks(ba_handle* h) {
   BA_LAUNCH(k_track_centres, dim3((h->Nc + 255) / 256), dim3(256), 0, h->stream, a.cs, h->Nc, h->trk_ctr.p);
   if (h->Np == 0) return;
   const int tpb = TRK_THREADS / TRK_G;
-  if (h->trk_bal) BA_LAUNCH(k_tracks_short<BalCam>, dim3((h->Np + tpb - 1) / tpb), dim3(TRK_THREADS), 0, h->stream, a);
-  else BA_LAUNCH(k_tracks_short<Pinhole>, dim3((h->Np + tpb - 1) / tpb), dim3(TRK_THREADS), 0, h->stream, a);
+  BA_LAUNCH_CM(h->trk_bal, k_tracks_short, dim3((h->Np + tpb - 1) / tpb), dim3(TRK_THREADS), 0, h->stream, a);
   if (h->n_long > 0) {
     TrackArgs b = a;
     b.list = h->long_pts.p; b.n_items = h->n_long;
-    if (h->trk_bal) BA_LAUNCH(k_tracks_long<BalCam>, dim3(h->n_long), dim3(64), 0, h->stream, b);
-    else BA_LAUNCH(k_tracks_long<Pinhole>, dim3(h->n_long), dim3(64), 0, h->stream, b);
+    BA_LAUNCH_CM(h->trk_bal, k_tracks_long, dim3(h->n_long), dim3(64), 0, h->stream, b);
   }
 }
 extern "C" int ba_default_track_options(ba_track_options* o) {
@@ -3423,17 +3441,13 @@ extern "C" int ba_triangulate_tracks(ba_handle* h, const double* intr, const ba_
     if (status) HIPCHECK(hipMemcpyAsync(status, h->trk_status.p, (size_t)Np, hipMemcpyDeviceToHost, h->stream));
   }
   if (opts->write_points) {
-    // what ba_set_params(cameras as they are, merged points) leaves behind: parameter set 0 current, the point table
-    // rebuilt, the camera state recomputed from the same rvec | t, the linearisation forgotten
+    // what ba_set_params(cameras as they are, merged points) leaves behind: the point table rebuilt, then adopt_set0
     if (Np > 0)
       BA_LAUNCH(k_tracks_merge, dim3((Np + 255) / 256), dim3(256), 0, h->stream, (const double*)h->trk_out.p, pt_held_ptr(h),
                 (const double*)h->ptab[h->cur].p, Np, h->ptab[0].p);
     if (h->cur != 0)
       HIPCHECK(hipMemcpyAsync(h->cams[0].p, h->cams[h->cur].p, 6 * (size_t)Nc * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    h->cur = 0;
-    BA_LAUNCH(k_cam_prepare<Pinhole>, dim3((Nc + 63) / 64), dim3(64), 0, h->stream, h->cams[0].p, (const double*)h->intr[0].p,
-              h->cs[0].p, h->camA[0].p, Nc);
-    h->linearized = false;
+    adopt_set0(h);
   }
   BA_SYNC(h);
   return BA_OK;
@@ -3442,11 +3456,82 @@ extern "C" int ba_triangulate_tracks(ba_handle* h, const double* intr, const ba_
 // ------------------------------------------------------------------------------------------------- resection
 // ba_resect (csrc/ba_resect.hpp): one workgroup per camera over the camera-ordered list.  Local to the rank: no collective.
 static void launch_resect(ba_handle* h) {
-  ResectArgs& a = h->rs_args;
+  ResectArgs& a = h->rs.args;
   a.t.cs = h->cs[h->cur].p; a.cams = h->cams[h->cur].p; a.ptab = h->ptab[h->cur].p;
   if (h->Nc == 0) return;
-  if (h->rs_bal) BA_LAUNCH(k_resect<BalCam>, dim3(h->Nc), dim3(RS_THREADS), 0, h->stream, a);
-  else BA_LAUNCH(k_resect<Pinhole>, dim3(h->Nc), dim3(RS_THREADS), 0, h->stream, a);
+  BA_LAUNCH_CM(h->rs.bal, k_resect, dim3(h->Nc), dim3(RS_THREADS), 0, h->stream, a);
+}
+// What ba_resect and ba_resect_ransac (`who` in the messages) do alike before their launches: the checks of the options they
+// share -- o is ba_resect's struct for both; ba_resect_ransac fills one from its own, init = CURRENT --, the uploads of intr,
+// cam_sel and pt_known into the caller's set s, and its ResectArgs
+static int resect_begin(ba_handle* h, const char* who, const double* intr, const uint8_t* cam_sel, const uint8_t* pt_known,
+                        const ba_resect_options& o, ba_handle::ResectSet& s) {
+  if (!loss_valid(o.loss)) return fail(BA_ERR_INVALID, "%s: unknown loss %d", who, o.loss);
+  if (!(o.f_scale > 0)) return fail(BA_ERR_INVALID, "%s: f_scale must be positive", who);
+  if (o.refine_iters < 0) return fail(BA_ERR_INVALID, "%s: refine_iters must not be negative", who);
+  if (o.min_inliers < 0) return fail(BA_ERR_INVALID, "%s: min_inliers must not be negative", who);
+  if (o.write_cams && any_prior(h))
+    return fail(BA_ERR_STATE, "%s with write_cams = 1: priors are set (ba_set_priors) and their means were set for the old poses: "
+                              "resect first, set the priors afterwards", who);
+  if (set_device(h)) return BA_ERR_HIP;
+  const int Nc = h->Nc, Np = h->Np;
+  const size_t nc1 = (size_t)std::max(Nc, 1), np1 = (size_t)std::max(Np, 1);
+  HIPCHECK(s.out.alloc(RS_OUT * nc1));
+  if (intr) {
+    HIPCHECK(s.intr.alloc(3 * nc1));
+    HIPCHECK(hipMemcpyAsync(s.intr.p, intr, 3 * (size_t)Nc * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  }
+  if (cam_sel) {
+    HIPCHECK(s.sel.alloc(nc1));
+    HIPCHECK(hipMemcpyAsync(s.sel.p, cam_sel, (size_t)Nc, hipMemcpyHostToDevice, h->stream));
+  }
+  if (pt_known && Np > 0) {
+    HIPCHECK(h->rs_known_in.alloc(np1)); HIPCHECK(s.known.alloc(np1));
+    HIPCHECK(hipMemcpyAsync(h->rs_known_in.p, pt_known, (size_t)Np, hipMemcpyHostToDevice, h->stream));
+    BA_LAUNCH(k_resect_known, dim3((Np + 255) / 256), dim3(256), 0, h->stream, (const unsigned char*)h->rs_known_in.p, (const int*)h->slot.p, Np,
+              s.known.p);
+  }
+  ResectArgs& a = s.args;
+  a = ResectArgs{};
+  a.t.intr = intr ? s.intr.p : nullptr;
+  a.t.uv = uv_arr(h, h->c_uv);
+  a.t.fx = h->K4[0]; a.t.fy = h->K4[1]; a.t.cx = h->K4[2]; a.t.cy = h->K4[3];
+  a.t.loss = o.loss; a.t.iters = o.refine_iters;
+  a.t.fscale = o.f_scale; a.t.max_px = o.max_reproj_px; a.t.min_depth = o.min_depth;
+  a.offk = h->offk.p; a.c_pt = h->c_pt.p;
+  a.known = (pt_known && Np > 0) ? s.known.p : nullptr;
+  a.sel = cam_sel ? s.sel.p : nullptr;
+  a.init = o.init; a.min_inliers = o.min_inliers; a.max_rms = o.max_rms_px;
+  a.out = s.out.p;
+  s.bal = intr != nullptr;
+  s.valid = true;
+  return BA_OK;
+}
+// ... and behind them: the rows of s.out back, write_cams, the sync, the rows into the caller's arrays
+static int resect_end(ba_handle* h, ba_handle::ResectSet& s, int write_cams, double* poses, uint8_t* status, int32_t* n_inliers,
+                      double* rms_px, double* max_px) {
+  const int Nc = h->Nc, Np = h->Np;
+  std::vector<double> res(RS_OUT * (size_t)Nc);
+  if (Nc > 0) HIPCHECK(hipMemcpyAsync(res.data(), s.out.p, res.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (write_cams) {
+    // what ba_set_params(merged cameras, points as they are) leaves behind: the cameras merged and the point table rebuilt,
+    // then adopt_set0 (held_x2 stays: no point moves)
+    const int nmax = std::max(Nc, Np);
+    if (nmax > 0)
+      BA_LAUNCH(k_resect_merge, dim3((nmax + 255) / 256), dim3(256), 0, h->stream, (const double*)s.out.p, s.args.sel, cam_held_ptr(h), h->fixed,
+                (const double*)h->cams[h->cur].p, Nc, h->cams[0].p, (const double*)h->ptab[h->cur].p, Np, h->ptab[0].p);
+    adopt_set0(h);
+  }
+  BA_SYNC(h);
+  for (int c = 0; c < Nc; ++c) {
+    const double* r = res.data() + RS_OUT * (size_t)c;
+    if (poses) memcpy(poses + 6 * (size_t)c, r, 6 * sizeof(double));
+    if (status) status[c] = (uint8_t)(int)r[6];
+    if (n_inliers) n_inliers[c] = (int32_t)r[7];
+    if (rms_px) rms_px[c] = r[8];
+    if (max_px) max_px[c] = r[9];
+  }
+  return BA_OK;
 }
 extern "C" int ba_default_resect_options(ba_resect_options* o) {
   if (!o) return fail(BA_ERR_INVALID, "null argument");
@@ -3462,72 +3547,11 @@ extern "C" int ba_resect(ba_handle* h, const double* intr, const ba_resect_optio
                          double* poses, uint8_t* status, int32_t* n_inliers, double* rms_px, double* max_px) {
   if (!h || !opts) return fail(BA_ERR_INVALID, "null argument");
   if (!h->have_problem || !h->have_params) return fail(BA_ERR_STATE, "ba_resect: ba_set_problem / ba_set_params first");
-  if (!loss_valid(opts->loss)) return fail(BA_ERR_INVALID, "ba_resect: unknown loss %d", opts->loss);
   if (opts->init != BA_RESECT_INIT_DLT && opts->init != BA_RESECT_INIT_CURRENT) return fail(BA_ERR_INVALID, "ba_resect: unknown init %d", opts->init);
-  if (!(opts->f_scale > 0)) return fail(BA_ERR_INVALID, "ba_resect: f_scale must be positive");
-  if (opts->refine_iters < 0) return fail(BA_ERR_INVALID, "ba_resect: refine_iters must not be negative");
-  if (opts->min_inliers < 0) return fail(BA_ERR_INVALID, "ba_resect: min_inliers must not be negative");
   if (opts->reserved0 != 0) return fail(BA_ERR_INVALID, "ba_resect: reserved0 must be 0");
-  if (opts->write_cams && any_prior(h))
-    return fail(BA_ERR_STATE, "ba_resect with write_cams = 1: priors are set (ba_set_priors) and their means were set for the old poses: "
-                              "resect first, set the priors afterwards");
-  if (set_device(h)) return BA_ERR_HIP;
-  const int Nc = h->Nc, Np = h->Np;
-  const size_t nc1 = (size_t)std::max(Nc, 1), np1 = (size_t)std::max(Np, 1);
-  HIPCHECK(h->rs_out.alloc(RS_OUT * nc1));
-  if (intr) {
-    HIPCHECK(h->rs_intr.alloc(3 * nc1));
-    HIPCHECK(hipMemcpyAsync(h->rs_intr.p, intr, 3 * (size_t)Nc * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  }
-  if (cam_sel) {
-    HIPCHECK(h->rs_sel.alloc(nc1));
-    HIPCHECK(hipMemcpyAsync(h->rs_sel.p, cam_sel, (size_t)Nc, hipMemcpyHostToDevice, h->stream));
-  }
-  if (pt_known && Np > 0) {
-    HIPCHECK(h->rs_known_in.alloc(np1)); HIPCHECK(h->rs_known.alloc(np1));
-    HIPCHECK(hipMemcpyAsync(h->rs_known_in.p, pt_known, (size_t)Np, hipMemcpyHostToDevice, h->stream));
-    BA_LAUNCH(k_resect_known, dim3((Np + 255) / 256), dim3(256), 0, h->stream, (const unsigned char*)h->rs_known_in.p, (const int*)h->slot.p, Np,
-              h->rs_known.p);
-  }
-  ResectArgs& a = h->rs_args;
-  a = ResectArgs{};
-  a.t.intr = intr ? h->rs_intr.p : nullptr;
-  a.t.uv = uv_arr(h, h->c_uv);
-  a.t.fx = h->K4[0]; a.t.fy = h->K4[1]; a.t.cx = h->K4[2]; a.t.cy = h->K4[3];
-  a.t.loss = opts->loss; a.t.iters = opts->refine_iters;
-  a.t.fscale = opts->f_scale; a.t.max_px = opts->max_reproj_px; a.t.min_depth = opts->min_depth;
-  a.offk = h->offk.p; a.c_pt = h->c_pt.p;
-  a.known = (pt_known && Np > 0) ? h->rs_known.p : nullptr;
-  a.sel = cam_sel ? h->rs_sel.p : nullptr;
-  a.init = opts->init; a.min_inliers = opts->min_inliers; a.max_rms = opts->max_rms_px;
-  a.out = h->rs_out.p;
-  h->rs_bal = intr != nullptr;
-  h->rs_valid = true;
+  if (int rc = resect_begin(h, "ba_resect", intr, cam_sel, pt_known, *opts, h->rs)) return rc;
   launch_resect(h);
-  std::vector<double> res(RS_OUT * (size_t)Nc);
-  if (Nc > 0) HIPCHECK(hipMemcpyAsync(res.data(), h->rs_out.p, res.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (opts->write_cams) {
-    // what ba_set_params(merged cameras, points as they are) leaves behind: parameter set 0 current, the point table
-    // rebuilt, the camera state recomputed, the linearisation forgotten (held_x2 stays: no point moves)
-    const int nmax = std::max(Nc, Np);
-    if (nmax > 0)
-      BA_LAUNCH(k_resect_merge, dim3((nmax + 255) / 256), dim3(256), 0, h->stream, (const double*)h->rs_out.p, a.sel, cam_held_ptr(h), h->fixed,
-                (const double*)h->cams[h->cur].p, Nc, h->cams[0].p, (const double*)h->ptab[h->cur].p, Np, h->ptab[0].p);
-    h->cur = 0;
-    BA_LAUNCH(k_cam_prepare<Pinhole>, dim3((Nc + 63) / 64), dim3(64), 0, h->stream, h->cams[0].p, (const double*)h->intr[0].p,
-              h->cs[0].p, h->camA[0].p, Nc);
-    h->linearized = false;
-  }
-  BA_SYNC(h);
-  for (int c = 0; c < Nc; ++c) {
-    const double* r = res.data() + RS_OUT * (size_t)c;
-    if (poses) memcpy(poses + 6 * (size_t)c, r, 6 * sizeof(double));
-    if (status) status[c] = (uint8_t)(int)r[6];
-    if (n_inliers) n_inliers[c] = (int32_t)r[7];
-    if (rms_px) rms_px[c] = r[8];
-    if (max_px) max_px[c] = r[9];
-  }
-  return BA_OK;
+  return resect_end(h, h->rs, opts->write_cams, poses, status, n_inliers, rms_px, max_px);
 }
 
 // ------------------------------------------------------------------------------------------------- RANSAC resection
@@ -3538,15 +3562,9 @@ static int launch_ransac(ba_handle* h) {
   if (h->Nc == 0) return BA_OK;
   if (a.inl && h->Nobs > 0) HIPCHECK(hipMemsetAsync(a.inl, 0, (size_t)h->Nobs, h->stream));
   const dim3 gc(h->Nc), gs(h->Nc, a.n_blk), b(RN_THREADS);
-  if (h->rn_bal) {
-    BA_LAUNCH(k_ransac_prep<BalCam>, gc, b, 0, h->stream, a);
-    BA_LAUNCH(k_ransac_score<BalCam>, gs, b, 0, h->stream, a);
-    BA_LAUNCH(k_ransac_lo<BalCam>, gc, b, 0, h->stream, a);
-  } else {
-    BA_LAUNCH(k_ransac_prep<Pinhole>, gc, b, 0, h->stream, a);
-    BA_LAUNCH(k_ransac_score<Pinhole>, gs, b, 0, h->stream, a);
-    BA_LAUNCH(k_ransac_lo<Pinhole>, gc, b, 0, h->stream, a);
-  }
+  BA_LAUNCH_CM(h->rn.bal, k_ransac_prep, gc, b, 0, h->stream, a);
+  BA_LAUNCH_CM(h->rn.bal, k_ransac_score, gs, b, 0, h->stream, a);
+  BA_LAUNCH_CM(h->rn.bal, k_ransac_lo, gc, b, 0, h->stream, a);
   return BA_OK;
 }
 extern "C" int ba_default_ransac_options(ba_ransac_options* o) {
@@ -3568,77 +3586,27 @@ extern "C" int ba_resect_ransac(ba_handle* h, const double* intr, const ba_ransa
   if (opts->n_hyp < 1 || opts->n_hyp > RN_MAX_HYP) return fail(BA_ERR_INVALID, "ba_resect_ransac: n_hyp %d is outside 1 .. %d", opts->n_hyp, RN_MAX_HYP);
   if (opts->lo_rounds < 0) return fail(BA_ERR_INVALID, "ba_resect_ransac: lo_rounds must not be negative");
   if (!(opts->max_reproj_px > 0)) return fail(BA_ERR_INVALID, "ba_resect_ransac: max_reproj_px must be positive");
-  if (!loss_valid(opts->loss)) return fail(BA_ERR_INVALID, "ba_resect_ransac: unknown loss %d", opts->loss);
-  if (!(opts->f_scale > 0)) return fail(BA_ERR_INVALID, "ba_resect_ransac: f_scale must be positive");
-  if (opts->refine_iters < 0) return fail(BA_ERR_INVALID, "ba_resect_ransac: refine_iters must not be negative");
-  if (opts->min_inliers < 0) return fail(BA_ERR_INVALID, "ba_resect_ransac: min_inliers must not be negative");
-  if (opts->write_cams && any_prior(h))
-    return fail(BA_ERR_STATE, "ba_resect_ransac with write_cams = 1: priors are set (ba_set_priors) and their means were set for the old poses: "
-                              "resect first, set the priors afterwards");
-  if (set_device(h)) return BA_ERR_HIP;
-  const int Nc = h->Nc, Np = h->Np;
-  const size_t nc1 = (size_t)std::max(Nc, 1), np1 = (size_t)std::max(Np, 1), no1 = (size_t)std::max<long long>(h->Nobs, 1);
+  ba_resect_options common = {};
+  common.loss = opts->loss; common.refine_iters = opts->refine_iters; common.f_scale = opts->f_scale;
+  common.init = BA_RESECT_INIT_CURRENT; common.min_inliers = opts->min_inliers; common.write_cams = opts->write_cams;
+  common.max_reproj_px = opts->max_reproj_px; common.max_rms_px = opts->max_rms_px; common.min_depth = opts->min_depth;
+  if (int rc = resect_begin(h, "ba_resect_ransac", intr, cam_sel, pt_known, common, h->rn)) return rc;
+  const size_t nc1 = (size_t)std::max(h->Nc, 1), no1 = (size_t)std::max<long long>(h->Nobs, 1);
   const int n_blk = (opts->n_hyp + RN_THREADS - 1) / RN_THREADS;
-  HIPCHECK(h->rn_out.alloc(RS_OUT * nc1));
   HIPCHECK(h->rn_rec.alloc(RN_REC * no1)); HIPCHECK(h->rn_cnt.alloc(nc1)); HIPCHECK(h->rn_best.alloc(RN_BEST * nc1 * n_blk));
   HIPCHECK(h->rn_cons.alloc(no1)); HIPCHECK(h->rn_inl.alloc(no1));
-  if (intr) {
-    HIPCHECK(h->rn_intr.alloc(3 * nc1));
-    HIPCHECK(hipMemcpyAsync(h->rn_intr.p, intr, 3 * (size_t)Nc * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  }
-  if (cam_sel) {
-    HIPCHECK(h->rn_sel.alloc(nc1));
-    HIPCHECK(hipMemcpyAsync(h->rn_sel.p, cam_sel, (size_t)Nc, hipMemcpyHostToDevice, h->stream));
-  }
-  if (pt_known && Np > 0) {
-    HIPCHECK(h->rs_known_in.alloc(np1)); HIPCHECK(h->rn_known.alloc(np1));
-    HIPCHECK(hipMemcpyAsync(h->rs_known_in.p, pt_known, (size_t)Np, hipMemcpyHostToDevice, h->stream));
-    BA_LAUNCH(k_resect_known, dim3((Np + 255) / 256), dim3(256), 0, h->stream, (const unsigned char*)h->rs_known_in.p, (const int*)h->slot.p, Np,
-              h->rn_known.p);
-  }
   RansacArgs& a = h->rn_args;
   a = RansacArgs{};
-  a.r.t.intr = intr ? h->rn_intr.p : nullptr;
-  a.r.t.uv = uv_arr(h, h->c_uv);
-  a.r.t.fx = h->K4[0]; a.r.t.fy = h->K4[1]; a.r.t.cx = h->K4[2]; a.r.t.cy = h->K4[3];
-  a.r.t.loss = opts->loss; a.r.t.iters = opts->refine_iters;
-  a.r.t.fscale = opts->f_scale; a.r.t.max_px = opts->max_reproj_px; a.r.t.min_depth = opts->min_depth;
-  a.r.offk = h->offk.p; a.r.c_pt = h->c_pt.p;
-  a.r.known = (pt_known && Np > 0) ? h->rn_known.p : nullptr;
-  a.r.sel = cam_sel ? h->rn_sel.p : nullptr;
-  a.r.init = RS_INIT_CURRENT; a.r.min_inliers = opts->min_inliers; a.r.max_rms = opts->max_rms_px;
-  a.r.out = h->rn_out.p;
+  a.r = h->rn.args;
   a.n_hyp = opts->n_hyp; a.lo_rounds = opts->lo_rounds; a.n_blk = n_blk; a.seed = opts->seed;
   a.rec = h->rn_rec.p; a.cnt = h->rn_cnt.p; a.best = h->rn_best.p; a.cons = h->rn_cons.p;
   a.c_orig = h->c_orig.p; a.inl = h->rn_inl.p;
-  h->rn_bal = intr != nullptr;
-  h->rn_valid = true;
   if (int rc = launch_ransac(h)) return rc;
-  std::vector<double> res(RS_OUT * (size_t)Nc);
-  if (Nc > 0) HIPCHECK(hipMemcpyAsync(res.data(), h->rn_out.p, res.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (obs_inlier && Nc > 0 && h->Nobs > 0) HIPCHECK(hipMemcpyAsync(obs_inlier, h->rn_inl.p, (size_t)h->Nobs, hipMemcpyDeviceToHost, h->stream));
-  if (opts->write_cams) {
-    // as ba_resect: what ba_set_params(merged cameras, points as they are) leaves behind
-    const int nmax = std::max(Nc, Np);
-    if (nmax > 0)
-      BA_LAUNCH(k_resect_merge, dim3((nmax + 255) / 256), dim3(256), 0, h->stream, (const double*)h->rn_out.p, a.r.sel, cam_held_ptr(h), h->fixed,
-                (const double*)h->cams[h->cur].p, Nc, h->cams[0].p, (const double*)h->ptab[h->cur].p, Np, h->ptab[0].p);
-    h->cur = 0;
-    BA_LAUNCH(k_cam_prepare<Pinhole>, dim3((Nc + 63) / 64), dim3(64), 0, h->stream, h->cams[0].p, (const double*)h->intr[0].p,
-              h->cs[0].p, h->camA[0].p, Nc);
-    h->linearized = false;
+  if (obs_inlier && h->Nobs > 0) {
+    if (h->Nc > 0) HIPCHECK(hipMemcpyAsync(obs_inlier, h->rn_inl.p, (size_t)h->Nobs, hipMemcpyDeviceToHost, h->stream));
+    else memset(obs_inlier, 0, (size_t)h->Nobs);
   }
-  BA_SYNC(h);
-  if (obs_inlier && (Nc == 0) && h->Nobs > 0) memset(obs_inlier, 0, (size_t)h->Nobs);
-  for (int c = 0; c < Nc; ++c) {
-    const double* r = res.data() + RS_OUT * (size_t)c;
-    if (poses) memcpy(poses + 6 * (size_t)c, r, 6 * sizeof(double));
-    if (status) status[c] = (uint8_t)(int)r[6];
-    if (n_inliers) n_inliers[c] = (int32_t)r[7];
-    if (rms_px) rms_px[c] = r[8];
-    if (max_px) max_px[c] = r[9];
-  }
-  return BA_OK;
+  return resect_end(h, h->rn, opts->write_cams, poses, status, n_inliers, rms_px, max_px);
 }
 
 // ------------------------------------------------------------------------------------------------- similarity
@@ -3677,8 +3645,7 @@ static int launch_transform(ba_handle* h, std::vector<double>* held_pts) {
   return BA_OK;
 }
 static void commit_transform(ba_handle* h, const std::vector<double>& held_pts) {
-  h->cur = 0;
-  h->linearized = false;
+  adopt_set0(h, true);
   if (!held_pts.empty()) h->held_x2 = held_points_x2(h, held_pts.data());
 }
 
@@ -3822,8 +3789,8 @@ extern "C" int ba_time_kernel(ba_handle* h, int slot, int reps, double* mean_us)
   if (!h || !mean_us || reps < 1) return fail(BA_ERR_INVALID, "bad argument");
   if (!h->have_params) return fail(BA_ERR_STATE, "no parameters set");
   if (slot == BA_K_TRACKS && !h->trk_valid) return fail(BA_ERR_STATE, "BA_K_TRACKS repeats the last ba_triangulate_tracks: call it first");
-  if (slot == BA_K_RESECT && !h->rs_valid) return fail(BA_ERR_STATE, "BA_K_RESECT repeats the last ba_resect: call it first");
-  if (slot == BA_K_RESECT_RANSAC && !h->rn_valid) return fail(BA_ERR_STATE, "BA_K_RESECT_RANSAC repeats the last ba_resect_ransac: call it first");
+  if (slot == BA_K_RESECT && !h->rs.valid) return fail(BA_ERR_STATE, "BA_K_RESECT repeats the last ba_resect: call it first");
+  if (slot == BA_K_RESECT_RANSAC && !h->rn.valid) return fail(BA_ERR_STATE, "BA_K_RESECT_RANSAC repeats the last ba_resect_ransac: call it first");
   if (set_device(h)) return BA_ERR_HIP;
   const bool saved = h->profile;
   h->profile = false;

@@ -12,8 +12,8 @@
 //                       broadcast) and adds to its own four MSAC costs.  No cross-lane traffic until the arg-min of
 //                       (cost, 4 h + slot): two DPP min-reductions per wave, the four waves through LDS in wave order.
 //   k_ransac_lo<CM>     one workgroup per camera: the lowest (cost, 4 h + slot) of the score blocks, then lo_rounds times
-//                       {consensus bytes at the frozen pose; ba_resect's refinement (rs_pass<CM, true>, rs_step, rs_pose) on
-//                       them}, then ba_resect's measures and status, and obs_inlier through c_orig in the caller's order.
+//                       {consensus bytes at the frozen pose; ba_resect's refinement (rs_refine<CM, true>) on them}, then
+//                       ba_resect's measures and status (rs_finish), and obs_inlier through c_orig in the caller's order.
 //
 // Generator (step 2): mix(z) = the splitmix64 finaliser (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27,
 // z *= 0x94D049BB133111EB, z ^= z >> 31); draw(d) = mix(mix(mix(mix(seed + G) + camera) + h) + (d + 1) G), G = 0x9E3779B97F4A7C15,
@@ -67,63 +67,6 @@ __device__ __forceinline__ void rn_sample(const unsigned long long seed, const i
   const int lo = min(i0, i1), hi = max(i0, i1);
   if (i2 >= lo) ++i2;
   if (i2 >= hi) ++i2;
-}
-
-// min over the wave, the same bits in every lane.  A lane without a source keeps its own value (`old` of the DPP move).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double rn_dpp_keep(double x) {
-  const int xl = __double2loint(x), xh = __double2hiint(x);
-  const int lo = __builtin_amdgcn_update_dpp(xl, xl, CTRL, ROW_MASK, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(xh, xh, CTRL, ROW_MASK, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double rn_wave_min(double x) {
-  x = fmin(x, rn_dpp_keep<DPP_ROW_SHR1, 0xf>(x));
-  x = fmin(x, rn_dpp_keep<DPP_ROW_SHR2, 0xf>(x));
-  x = fmin(x, rn_dpp_keep<DPP_ROW_SHR4, 0xf>(x));
-  x = fmin(x, rn_dpp_keep<DPP_ROW_SHR8, 0xf>(x));
-  x = fmin(x, rn_dpp_keep<DPP_ROW_BCAST15, 0xa>(x));
-  x = fmin(x, rn_dpp_keep<DPP_ROW_BCAST31, 0xc>(x));
-  return readlane_f64(x, 63);
-}
-
-// Cyclic Jacobi on a symmetric 3 x 3 (the criterion of jacobi_eig4)
-__device__ inline void rn_eig3(double (&A)[3][3], double (&V)[3][3]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 12; ++sweep) {
-    bool rotated = false;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < 3; ++q) {
-        const double apq = A[p][q];
-        if (!(fabs(apq) > 1e-17 * sqrt(fabs(A[p][p] * A[q][q])))) continue;
-        rotated = true;
-        const double zeta = (A[q][q] - A[p][p]) / (2.0 * apq);
-        const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
-        const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const double ap = A[k][p], aq = A[k][q];
-          A[k][p] = c * ap - s * aq;
-          A[k][q] = s * ap + c * aq;
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const double ap = A[p][k], aq = A[q][k];
-          A[p][k] = c * ap - s * aq;
-          A[q][k] = s * ap + c * aq;
-          const double vp = V[k][p], vq = V[k][q];
-          V[k][p] = c * vp - s * vq;
-          V[k][q] = s * vp + c * vq;
-        }
-      }
-    }
-    if (!rotated) break;
-  }
 }
 
 // packed symmetric 3 x 3: 00 01 02 11 12 22
@@ -281,7 +224,7 @@ __device__ inline int rn_p3p(const double* __restrict__ r0, const double* __rest
   double A[3][3], V[3][3];
   A[0][0] = D1[0] + g * D2[0]; A[0][1] = A[1][0] = D1[1] + g * D2[1]; A[0][2] = A[2][0] = D1[2] + g * D2[2];
   A[1][1] = D1[3] + g * D2[3]; A[1][2] = A[2][1] = D1[4] + g * D2[4]; A[2][2] = D1[5] + g * D2[5];
-  rn_eig3(A, V);
+  jacobi_eig<3, 12>(A, V);
   // the eigenvalue of the smallest magnitude is the zero one; the other two must differ in sign (selection by value, not by index)
   const double l0 = A[0][0], l1 = A[1][1], l2 = A[2][2];
   const double m0 = fabs(l0), m1 = fabs(l1), m2 = fabs(l2);
@@ -438,8 +381,8 @@ __global__ void __launch_bounds__(RN_THREADS) k_ransac_score(const RansacArgs a)
 #pragma unroll
   for (int k = 0; k < 4; ++k)
     if ((mask >> k & 1) && cost[k] < bc) { bc = cost[k]; bk = (double)(4 * h + k); }
-  const double wc = rn_wave_min(bc);
-  const double wk = rn_wave_min(bc == wc ? bk : RN_INF);
+  const double wc = wave_min_dpp(bc);
+  const double wk = wave_min_dpp(bc == wc ? bk : RN_INF);
   if (lane == 0) { red[2 * wv] = wc; red[2 * wv + 1] = wk; }
   __syncthreads();
   double gc = red[0], gk = red[1];
@@ -473,15 +416,11 @@ __global__ void __launch_bounds__(RS_THREADS) k_ransac_lo(const RansacArgs a) {
   __shared__ double lds[RS_WAVES * RS_NSUM];
   const ResectArgs& ra = a.r;
   const int c = blockIdx.x, tid = threadIdx.x;
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
   double* o = ra.out + RS_OUT * (size_t)c;
   double x[6];
 #pragma unroll
   for (int q = 0; q < 6; ++q) x[q] = ra.cams[6 * (size_t)c + q];
-  if (ra.sel && !ra.sel[c]) {                     // (workgroup-uniform, like every branch below)
-    if (tid == 0) { for (int q = 0; q < 6; ++q) o[q] = x[q]; o[6] = (double)RS_OK; o[7] = 0.0; o[8] = nan; o[9] = nan; }
-    return;
-  }
+  if (ra.sel && !ra.sel[c]) { rs_write_unrefined(o, x, RS_OK); return; }   // (workgroup-uniform, like every branch below)
   const int beg = ra.offk[c * (NPART + 1)], end = ra.offk[c * (NPART + 1) + NPART];
   const double n = (double)a.cnt[c];
   int status = RS_OK;
@@ -511,10 +450,7 @@ __global__ void __launch_bounds__(RS_THREADS) k_ransac_lo(const RansacArgs a) {
       }
     }
   }
-  if (status != RS_OK) {                          // the current pose, no measures
-    if (tid == 0) { for (int q = 0; q < 6; ++q) o[q] = x[q]; o[6] = (double)status; o[7] = 0.0; o[8] = nan; o[9] = nan; }
-    return;
-  }
+  if (status != RS_OK) { rs_write_unrefined(o, x, status); return; }   // the current pose
   double cam[CM::CAM], M[9];
   CM::load_cam_vec(ra.t.cs, ra.t.intr, c, cam);   // (the BAL intrinsics; rs_pose overwrites R | t)
   for (int round = 0; round < a.lo_rounds && status == RS_OK; ++round) {
@@ -522,94 +458,20 @@ __global__ void __launch_bounds__(RS_THREADS) k_ransac_lo(const RansacArgs a) {
     rs_pose<CM>(x, cam, M);
     double cn[1] = {0.0};
     for (int j = beg + tid; j < end; j += RS_THREADS) {
-      double X[3], bx, by;
+      double X[3], ru, rv;
       double2 uv;
-      unsigned char in = 0;
-      if (rs_obs<CM>(ra, cam, j, X, uv, bx, by)) {
-        const double pz = cam[6] * X[0] + cam[7] * X[1] + cam[8] * X[2] + cam[11];
-        if ((CM::ID == 0 ? pz : -pz) > ra.t.min_depth) {
-          typename CM::template Obs<double> g;
-          CM::template geom<false, double, double>(cam, X[0], X[1], X[2], ra.t.fx, ra.t.fy, g);
-          double ru, rv;
-          CM::residual(g, uv.x, uv.y, ra.t.fx, ra.t.fy, ra.t.cx, ra.t.cy, ru, rv);
-          in = sqrt(ru * ru + rv * rv) <= ra.t.max_px ? 1 : 0;
-        }
-      }
+      typename CM::template Obs<double> g;
+      const bool front = rs_residual<CM>(ra, cam, j, ru, rv, uv, X, g) > 0;
+      const unsigned char in = front && sqrt(ru * ru + rv * rv) <= ra.t.max_px ? 1 : 0;
       a.cons[j] = in;
       cn[0] += (double)in;
     }
     rs_block_sums<1>(cn, lds);
     if (!(cn[0] > 0.0)) break;
-    // ba_resect's step 3 on the set
-    double acc[RS_NSUM], cur[RS_NSUM], xt[6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) xt[q] = x[q];
-#pragma unroll
-    for (int q = 0; q < RS_NSUM; ++q) cur[q] = 0.0;
-    double lam = 1e-4;
-    bool first = true, small = false;
-    int it = 0;
-    for (;;) {
-      rs_pose<CM>(xt, cam, M);
-      rs_pass<CM, true>(ra, cam, M, beg, end, acc, lds, a.cons);
-      if (first || acc[27] <= cur[27] * (1.0 + TRK_COST_SLACK)) {
-#pragma unroll
-        for (int q = 0; q < RS_NSUM; ++q) cur[q] = acc[q];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) x[q] = xt[q];
-        if (!first) lam = fmax(0.1 * lam, 1e-12);
-      } else {
-        lam *= 10.0;
-      }
-      first = false;
-      if (small || it >= ra.t.iters) break;
-      ++it;
-      double dx[6];
-      if (!rs_step(cur, lam, dx)) { status = RS_DEGENERATE; break; }
-      double d2 = 0.0, x2 = 0.0;
-#pragma unroll
-      for (int q = 0; q < 6; ++q) { xt[q] = x[q] + dx[q]; d2 += dx[q] * dx[q]; x2 += x[q] * x[q]; }
-      small = sqrt(d2) <= 1e-14 * sqrt(x2);
-    }
+    rs_refine<CM, true>(ra, cam, M, beg, end, x, status, lds, a.cons);   // ba_resect's step 3 on the set
   }
-  // measures at the final pose (ba_resect's steps 4 and 5); obs_inlier is the same test
-  rs_pose<CM>(x, cam, M);
-  double m5[5] = {0, 0, 0, 0, 0};     // in front | behind | inliers | sse of the inliers | sse of those in front
-  double mx_in = 0.0, mx_fr = 0.0;
-  for (int j = beg + tid; j < end; j += RS_THREADS) {
-    double X[3], bx, by;
-    double2 uv;
-    if (!rs_obs<CM>(ra, cam, j, X, uv, bx, by)) continue;
-    const double pz = cam[6] * X[0] + cam[7] * X[1] + cam[8] * X[2] + cam[11];
-    if (!((CM::ID == 0 ? pz : -pz) > ra.t.min_depth)) { m5[1] += 1.0; continue; }
-    typename CM::template Obs<double> g;
-    CM::template geom<false, double, double>(cam, X[0], X[1], X[2], ra.t.fx, ra.t.fy, g);
-    double ru, rv;
-    CM::residual(g, uv.x, uv.y, ra.t.fx, ra.t.fy, ra.t.cx, ra.t.cy, ru, rv);
-    const double e2 = ru * ru + rv * rv;
-    m5[0] += 1.0; m5[4] += e2;
-    mx_fr = fmax(mx_fr, e2);
-    if (sqrt(e2) <= ra.t.max_px) {
-      m5[2] += 1.0; m5[3] += e2; mx_in = fmax(mx_in, e2);
-      if (a.inl) a.inl[a.c_orig[j]] = 1;
-    }
-  }
-  rs_block_sums<5>(m5, lds);
-  mx_in = rs_block_max(mx_in, lds);
-  mx_fr = rs_block_max(mx_fr, lds);
-  if (tid == 0) {
-    const bool inl = m5[2] > 0.0;
-    const double cnt = inl ? m5[2] : m5[0];
-    const double rms = cnt > 0.0 ? sqrt((inl ? m5[3] : m5[4]) / cnt) : nan;
-    const double emax = cnt > 0.0 ? sqrt(inl ? mx_in : mx_fr) : nan;
-    if (status == RS_OK) {
-      if (2.0 * m5[1] > n) status = RS_BEHIND;
-      else if (m5[2] < (double)ra.min_inliers) status = RS_FEW_INLIERS;
-      else if (ra.max_rms > 0.0 && !(rms <= ra.max_rms)) status = RS_HIGH_ERROR;
-    }
-    for (int q = 0; q < 6; ++q) o[q] = x[q];
-    o[6] = (double)status; o[7] = m5[2]; o[8] = rms; o[9] = emax;
-  }
+  // ba_resect's steps 4 and 5; obs_inlier is the inlier test of its measures
+  rs_finish<CM>(ra, cam, M, beg, end, x, n, status, lds, o, a.inl, a.c_orig);
 }
 
 }  // namespace ba

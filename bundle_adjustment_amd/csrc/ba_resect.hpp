@@ -14,10 +14,10 @@
 //                 y (p3.X~) - p2.X~ = 0 with X~ = ((X - mean) / sigma, 1), sigma^2 = mean |X - mean|^2 / 3 from centred values.
 //                 The 12 x 12 normal matrix is never formed: its blocks are S = sum X~X~^T, Sx = sum x X~X~^T, Sy, Sq =
 //                 sum (x^2 + y^2) X~X~^T (forty sums, two passes of twenty), all divided by n; eliminating p1, p2 leaves
-//                 M = Sq - Sx S^-1 Sx - Sy S^-1 Sy, p3 = its eigenvector of the smallest eigenvalue (jacobi_eig4),
+//                 M = Sq - Sx S^-1 Sx - Sy S^-1 Sy, p3 = its eigenvector of the smallest eigenvalue (jacobi_eig),
 //                 p1 = S^-1 Sx p3, p2 = S^-1 Sy p3 through the Cholesky factor of S (a pivot <= 1e-8 -- coplanar, collinear
 //                 or coincident points -- or a non-finite sum: DEGENERATE).  A = the left 3 x 3 of [p1; p2; p3], sign of P
-//                 so that det A > 0, R = U V^T of A's SVD (jacobi_svd3), t = b / mean(singular values), then
+//                 so that det A > 0, R = U V^T of A's SVD (jacobi_svd), t = b / mean(singular values), then
 //                 t <- sigma t - R mean; sigma_3 <= 1e-6 sigma_1: DEGENERATE.  rvec = sim_log_map(R).
 //   3 refinement  Marquardt-damped Gauss-Newton on 0.5 sum C^2 rho((r / C)^2) over the six additive parameters rvec | t:
 //                 the model's pre-M Jacobian rows (jac_rows), summed, then the congruence with diag(M, I) (M = J_r(rvec) of
@@ -29,7 +29,7 @@
 //                 that is <= 0); rms and max over the inliers, or over all in front when there are none.
 //   5 status      the first failing test in enum order (ba_resect_status).
 #pragma once
-#include "ba_similarity.hpp"
+#include "ba_linalg.hpp"
 #include "ba_tracks.hpp"
 
 namespace ba {
@@ -75,9 +75,9 @@ __device__ __forceinline__ void rs_block_sums(double (&v)[N], double* __restrict
 #pragma unroll
   for (int j = 0; j < N; ++j) v[j] = ((lds[j] + lds[N + j]) + lds[2 * N + j]) + lds[3 * N + j];
 }
-__device__ __forceinline__ double rs_block_max(double x, double* __restrict__ lds) {   // of non-negative numbers
+__device__ __forceinline__ double rs_block_max(double x, double* __restrict__ lds) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  x = trk_max<64>(x);
+  x = wave_max_dpp(x);
   __syncthreads();
   if (lane == 0) lds[wv] = x;
   __syncthreads();
@@ -94,6 +94,20 @@ __device__ __forceinline__ bool rs_obs(const ResectArgs& a, const double (&cam)[
   X[0] = Xd.x; X[1] = Xd.y; X[2] = Xd.z;
   uv = a.t.uv[(size_t)j];
   return trk_bearing<CM>(cam, uv, a.t, bx, by);
+}
+
+// observation j at the pose in cam: 0 when it is not usable (rs_obs), -1 when its point is behind the camera, 1 when it is in
+// front, with its residual and what the Jacobian rows are made of
+template <class CM>
+__device__ __forceinline__ int rs_residual(const ResectArgs& a, const double (&cam)[CM::CAM], const int j, double& ru, double& rv,
+                                           double2& uv, double (&X)[3], typename CM::template Obs<double>& g) {
+  double bx, by;
+  if (!rs_obs<CM>(a, cam, j, X, uv, bx, by)) return 0;
+  const double pz = cam[6] * X[0] + cam[7] * X[1] + cam[8] * X[2] + cam[11];
+  if (!((CM::ID == 0 ? pz : -pz) > a.t.min_depth)) return -1;
+  CM::template geom<false, double, double>(cam, X[0], X[1], X[2], a.t.fx, a.t.fy, g);
+  CM::residual(g, uv.x, uv.y, a.t.fx, a.t.fy, a.t.cx, a.t.cy, ru, rv);
+  return 1;
 }
 
 // The start of step 2 from the forty sums (sa: S | Sx, sb: Sy | Sq, packed upper 4 x 4 each); false: DEGENERATE
@@ -151,7 +165,7 @@ __device__ inline bool rs_dlt_pose(const double (&sa)[20], const double (&sb)[20
       Mq[p][q] -= s;
     }
   double V[4][4];
-  jacobi_eig4(Mq, V);
+  jacobi_eig<4, 16>(Mq, V);
   int best = 0;
   double lo = Mq[0][0];
   if (Mq[1][1] < lo) { lo = Mq[1][1]; best = 1; }
@@ -187,7 +201,7 @@ __device__ inline bool rs_dlt_pose(const double (&sa)[20], const double (&sb)[20
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) U[i][j] = sg * P[i][j];
-  jacobi_svd3(U, W);
+  jacobi_svd<3, 24>(U, W);
   double n2[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) n2[k] = U[0][k] * U[0][k] + U[1][k] * U[1][k] + U[2][k] * U[2][k];
@@ -267,15 +281,10 @@ __device__ __forceinline__ void rs_pass(const ResectArgs& a, const double (&cam)
   for (int q = 0; q < RS_NSUM; ++q) acc[q] = 0.0;
   for (int j = beg + (int)threadIdx.x; j < end; j += RS_THREADS) {
     if constexpr (CONS) { if (!cons[j]) continue; }
-    double X[3], bx, by;
+    double X[3], ru, rv;
     double2 uv;
-    if (!rs_obs<CM>(a, cam, j, X, uv, bx, by)) continue;
-    const double pz = cam[6] * X[0] + cam[7] * X[1] + cam[8] * X[2] + cam[11];
-    if (!((CM::ID == 0 ? pz : -pz) > a.t.min_depth)) continue;
     typename CM::template Obs<double> g;
-    CM::template geom<false, double, double>(cam, X[0], X[1], X[2], a.t.fx, a.t.fy, g);
-    double ru, rv;
-    CM::residual(g, uv.x, uv.y, a.t.fx, a.t.fy, a.t.cx, a.t.cy, ru, rv);
+    if (rs_residual<CM>(a, cam, j, ru, rv, uv, X, g) <= 0) continue;
     double J0[CM::NB], J1[CM::NB];
     CM::jac_rows(g, X[0], X[1], X[2], J0, J1);
     double w0 = 1.0, w1 = 1.0, t0 = ru * ru, t1 = rv * rv;
@@ -312,19 +321,103 @@ __device__ __forceinline__ void rs_pass(const ResectArgs& a, const double (&cam)
   for (int b = 0; b < 3; ++b) acc[21 + b] = g3[b];
 }
 
+// a camera without a refinement (not selected, or failed before it): the pose x, no measures
+__device__ __forceinline__ void rs_write_unrefined(double* __restrict__ o, const double (&x)[6], const int status) {
+  if (threadIdx.x != 0) return;
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  for (int q = 0; q < 6; ++q) o[q] = x[q];
+  o[6] = (double)status; o[7] = 0.0; o[8] = nan; o[9] = nan;
+}
+
+// step 3 from the pose x, which ends as the last accepted one; status becomes DEGENERATE on a failed pivot.  CONS: as rs_pass
+template <class CM, bool CONS>
+__device__ __forceinline__ void rs_refine(const ResectArgs& a, double (&cam)[CM::CAM], double (&M)[9], const int beg, const int end,
+                                          double (&x)[6], int& status, double* __restrict__ lds,
+                                          const unsigned char* __restrict__ cons = nullptr) {
+  double acc[RS_NSUM], cur[RS_NSUM], xt[6];
+#pragma unroll
+  for (int q = 0; q < 6; ++q) xt[q] = x[q];
+#pragma unroll
+  for (int q = 0; q < RS_NSUM; ++q) cur[q] = 0.0;
+  double lam = 1e-4;
+  bool first = true, small = false;
+  int it = 0;
+  for (;;) {
+    rs_pose<CM>(xt, cam, M);
+    rs_pass<CM, CONS>(a, cam, M, beg, end, acc, lds, cons);
+    if (first || acc[27] <= cur[27] * (1.0 + TRK_COST_SLACK)) {
+#pragma unroll
+      for (int q = 0; q < RS_NSUM; ++q) cur[q] = acc[q];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) x[q] = xt[q];
+      if (!first) lam = fmax(0.1 * lam, 1e-12);
+    } else {
+      lam *= 10.0;
+    }
+    first = false;
+    if (small || it >= a.t.iters) break;
+    ++it;
+    double dx[6];
+    if (!rs_step(cur, lam, dx)) { status = RS_DEGENERATE; break; }
+    double d2 = 0.0, x2 = 0.0;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) { xt[q] = x[q] + dx[q]; d2 += dx[q] * dx[q]; x2 += x[q] * x[q]; }
+    small = sqrt(d2) <= 1e-14 * sqrt(x2);
+  }
+}
+
+// steps 4 and 5 at the final pose x of a camera with n usable observations, and its output row.  inl (ba_resect_ransac's
+// obs_inlier, else null): the inliers' bytes, through c_orig in the caller's order
+template <class CM>
+__device__ __forceinline__ void rs_finish(const ResectArgs& a, double (&cam)[CM::CAM], double (&M)[9], const int beg, const int end,
+                                          const double (&x)[6], const double n, int status, double* __restrict__ lds,
+                                          double* __restrict__ o, unsigned char* __restrict__ inl, const int* __restrict__ c_orig) {
+  rs_pose<CM>(x, cam, M);
+  double m5[5] = {0, 0, 0, 0, 0};     // in front | behind | inliers | sse of the inliers | sse of those in front
+  double mx_in = 0.0, mx_fr = 0.0;
+  for (int j = beg + (int)threadIdx.x; j < end; j += RS_THREADS) {
+    double X[3], ru, rv;
+    double2 uv;
+    typename CM::template Obs<double> g;
+    const int front = rs_residual<CM>(a, cam, j, ru, rv, uv, X, g);
+    if (front < 0) m5[1] += 1.0;
+    if (front <= 0) continue;
+    const double e2 = ru * ru + rv * rv;
+    m5[0] += 1.0; m5[4] += e2;
+    mx_fr = fmax(mx_fr, e2);
+    if (!(a.t.max_px > 0.0) || sqrt(e2) <= a.t.max_px) {
+      m5[2] += 1.0; m5[3] += e2; mx_in = fmax(mx_in, e2);
+      if (inl) inl[c_orig[j]] = 1;
+    }
+  }
+  rs_block_sums<5>(m5, lds);
+  mx_in = rs_block_max(mx_in, lds);
+  mx_fr = rs_block_max(mx_fr, lds);
+  if (threadIdx.x == 0) {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const bool any_in = m5[2] > 0.0;
+    const double cnt = any_in ? m5[2] : m5[0];
+    const double rms = cnt > 0.0 ? sqrt((any_in ? m5[3] : m5[4]) / cnt) : nan;
+    const double emax = cnt > 0.0 ? sqrt(any_in ? mx_in : mx_fr) : nan;
+    if (status == RS_OK) {
+      if (2.0 * m5[1] > n) status = RS_BEHIND;
+      else if (m5[2] < (double)a.min_inliers) status = RS_FEW_INLIERS;
+      else if (a.max_rms > 0.0 && !(rms <= a.max_rms)) status = RS_HIGH_ERROR;
+    }
+    for (int q = 0; q < 6; ++q) o[q] = x[q];
+    o[6] = (double)status; o[7] = m5[2]; o[8] = rms; o[9] = emax;
+  }
+}
+
 template <class CM>
 __global__ void __launch_bounds__(RS_THREADS) k_resect(const ResectArgs a) {
   __shared__ double lds[RS_WAVES * RS_NSUM];
   const int c = blockIdx.x, tid = threadIdx.x;
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
   double* o = a.out + RS_OUT * (size_t)c;
   double x[6];
 #pragma unroll
   for (int q = 0; q < 6; ++q) x[q] = a.cams[6 * (size_t)c + q];
-  if (a.sel && !a.sel[c]) {                       // (workgroup-uniform, like every branch below)
-    if (tid == 0) { for (int q = 0; q < 6; ++q) o[q] = x[q]; o[6] = (double)RS_OK; o[7] = 0.0; o[8] = nan; o[9] = nan; }
-    return;
-  }
+  if (a.sel && !a.sel[c]) { rs_write_unrefined(o, x, RS_OK); return; }   // (workgroup-uniform, like every branch below)
   const int beg = a.offk[c * (NPART + 1)], end = a.offk[c * (NPART + 1) + NPART];
   double cam[CM::CAM], M[9];
   CM::load_cam_vec(a.t.cs, a.t.intr, c, cam);
@@ -394,78 +487,9 @@ __global__ void __launch_bounds__(RS_THREADS) k_resect(const ResectArgs a) {
       status = RS_DEGENERATE;
     }
   }
-  if (status != RS_OK) {                          // the current pose, no measures
-    if (tid == 0) { for (int q = 0; q < 6; ++q) o[q] = x[q]; o[6] = (double)status; o[7] = 0.0; o[8] = nan; o[9] = nan; }
-    return;
-  }
-  // refinement
-  {
-    double acc[RS_NSUM], cur[RS_NSUM], xt[6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) xt[q] = x[q];
-#pragma unroll
-    for (int q = 0; q < RS_NSUM; ++q) cur[q] = 0.0;
-    double lam = 1e-4;
-    bool first = true, small = false;
-    int it = 0;
-    for (;;) {
-      rs_pose<CM>(xt, cam, M);
-      rs_pass<CM>(a, cam, M, beg, end, acc, lds);
-      if (first || acc[27] <= cur[27] * (1.0 + TRK_COST_SLACK)) {
-#pragma unroll
-        for (int q = 0; q < RS_NSUM; ++q) cur[q] = acc[q];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) x[q] = xt[q];
-        if (!first) lam = fmax(0.1 * lam, 1e-12);
-      } else {
-        lam *= 10.0;
-      }
-      first = false;
-      if (small || it >= a.t.iters) break;
-      ++it;
-      double dx[6];
-      if (!rs_step(cur, lam, dx)) { status = RS_DEGENERATE; break; }
-      double d2 = 0.0, x2 = 0.0;
-#pragma unroll
-      for (int q = 0; q < 6; ++q) { xt[q] = x[q] + dx[q]; d2 += dx[q] * dx[q]; x2 += x[q] * x[q]; }
-      small = sqrt(d2) <= 1e-14 * sqrt(x2);
-    }
-  }
-  // measures at the final pose
-  rs_pose<CM>(x, cam, M);
-  double m5[5] = {0, 0, 0, 0, 0};     // in front | behind | inliers | sse of the inliers | sse of those in front
-  double mx_in = 0.0, mx_fr = 0.0;
-  for (int j = beg + tid; j < end; j += RS_THREADS) {
-    double X[3], bx, by;
-    double2 uv;
-    if (!rs_obs<CM>(a, cam, j, X, uv, bx, by)) continue;
-    const double pz = cam[6] * X[0] + cam[7] * X[1] + cam[8] * X[2] + cam[11];
-    if (!((CM::ID == 0 ? pz : -pz) > a.t.min_depth)) { m5[1] += 1.0; continue; }
-    typename CM::template Obs<double> g;
-    CM::template geom<false, double, double>(cam, X[0], X[1], X[2], a.t.fx, a.t.fy, g);
-    double ru, rv;
-    CM::residual(g, uv.x, uv.y, a.t.fx, a.t.fy, a.t.cx, a.t.cy, ru, rv);
-    const double e2 = ru * ru + rv * rv;
-    m5[0] += 1.0; m5[4] += e2;
-    mx_fr = fmax(mx_fr, e2);
-    if (!(a.t.max_px > 0.0) || sqrt(e2) <= a.t.max_px) { m5[2] += 1.0; m5[3] += e2; mx_in = fmax(mx_in, e2); }
-  }
-  rs_block_sums<5>(m5, lds);
-  mx_in = rs_block_max(mx_in, lds);
-  mx_fr = rs_block_max(mx_fr, lds);
-  if (tid == 0) {
-    const bool inl = m5[2] > 0.0;
-    const double cnt = inl ? m5[2] : m5[0];
-    const double rms = cnt > 0.0 ? sqrt((inl ? m5[3] : m5[4]) / cnt) : nan;
-    const double emax = cnt > 0.0 ? sqrt(inl ? mx_in : mx_fr) : nan;
-    if (status == RS_OK) {
-      if (2.0 * m5[1] > n) status = RS_BEHIND;
-      else if (m5[2] < (double)a.min_inliers) status = RS_FEW_INLIERS;
-      else if (a.max_rms > 0.0 && !(rms <= a.max_rms)) status = RS_HIGH_ERROR;
-    }
-    for (int q = 0; q < 6; ++q) o[q] = x[q];
-    o[6] = (double)status; o[7] = m5[2]; o[8] = rms; o[9] = emax;
-  }
+  if (status != RS_OK) { rs_write_unrefined(o, x, status); return; }   // the current pose
+  rs_refine<CM, false>(a, cam, M, beg, end, x, status, lds);
+  rs_finish<CM>(a, cam, M, beg, end, x, n, status, lds, o, nullptr, nullptr);
 }
 
 // write_cams: the cameras and the point table ba_set_params would build from the merged cameras and the current points

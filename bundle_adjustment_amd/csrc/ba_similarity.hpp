@@ -18,7 +18,7 @@
 //                centred sum is what is left of it (lo), and the distances of the IRLS weights use mu_b + lo unrounded --
 //                without it the ulp reaches every weight (f_scale 0.15) and the non-convex losses amplify it to 1e-8 in R
 //                between two summation orders.  A one-wave kernel folds the per-workgroup partials in index order, runs a one-sided Jacobi SVD of
-//                the 3 x 3 Sigma (jacobi_svd4 of ba_triangulate.hpp is the model) and writes s, R, t and the status into the
+//                the 3 x 3 Sigma (jacobi_svd<3, 24> of ba_linalg.hpp) and writes s, R, t and the status into the
 //                device record the next pass reads.  IRLS rounds recompute u_i = w_i rho'(w_i d_i^2 / f_scale^2) inside pass A.
 //                A last pass writes the errors d_i and folds their sum of squares and maximum.
 // Sums: a grid-stride loop in a fixed order, wave_total_dpp inside a wave, the four waves through LDS in wave order, one
@@ -26,6 +26,7 @@
 // correspondence count alone.
 #pragma once
 #include "ba_kernels.hpp"
+#include "ba_linalg.hpp"
 
 namespace ba {
 
@@ -44,8 +45,6 @@ struct SimRec {
   int status, pad;
 };
 
-__host__ __device__ __forceinline__ bool sim_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN
-
 // rho'(z) of the solve's losses (ba_loss), z >= 0
 __device__ inline double sim_rho_prime(const int loss, const double z) {
   if (loss == LOSS_HUBER) return z <= 1.0 ? 1.0 : 1.0 / sqrt(z);
@@ -53,28 +52,6 @@ __device__ inline double sim_rho_prime(const int loss, const double z) {
   if (loss == LOSS_CAUCHY) return 1.0 / (1.0 + z);
   if (loss == LOSS_ARCTAN) return 1.0 / (1.0 + z * z);
   return 1.0;
-}
-
-// rotation matrix (row-major, orthogonal to rounding) -> rotation vector, |rvec| <= pi
-__host__ __device__ inline void sim_log_map(const double* __restrict__ R, double* __restrict__ rvec) {
-  const double tr = R[0] + R[4] + R[8];
-  double w, x, y, z;
-  if (tr >= R[0] && tr >= R[4] && tr >= R[8]) {
-    w = 1.0 + tr; x = R[7] - R[5]; y = R[2] - R[6]; z = R[3] - R[1];
-  } else if (R[0] >= R[4] && R[0] >= R[8]) {
-    w = R[7] - R[5]; x = 1.0 + R[0] - R[4] - R[8]; y = R[1] + R[3]; z = R[2] + R[6];
-  } else if (R[4] >= R[8]) {
-    w = R[2] - R[6]; x = R[1] + R[3]; y = 1.0 + R[4] - R[0] - R[8]; z = R[5] + R[7];
-  } else {
-    w = R[3] - R[1]; x = R[2] + R[6]; y = R[5] + R[7]; z = 1.0 + R[8] - R[0] - R[4];
-  }
-  // (each case is 4 q_k q times the quaternion, q_k its largest component: the common factor goes with the normalisation)
-  const double in = 1.0 / sqrt(w * w + x * x + y * y + z * z);
-  w *= in; x *= in; y *= in; z *= in;
-  if (w < 0.0) { w = -w; x = -x; y = -y; z = -z; }
-  const double vn = sqrt(x * x + y * y + z * z);
-  const double k = (vn < 1e-10) ? 2.0 / w : 2.0 * atan2(vn, w) / vn;
-  rvec[0] = k * x; rvec[1] = k * y; rvec[2] = k * z;
 }
 
 // ---- transform ------------------------------------------------------------------------------------------------------
@@ -136,10 +113,7 @@ __global__ void k_sim_gather(const double* __restrict__ cs, int n_cam, const dou
   if (i >= n_cam + n_pt) return;
   double* o = a + 3 * (size_t)i;
   if (i < n_cam) {
-    const double* s = cs + CS * (size_t)i;
-    o[0] = -(s[0] * s[9] + s[3] * s[10] + s[6] * s[11]);
-    o[1] = -(s[1] * s[9] + s[4] * s[10] + s[7] * s[11]);
-    o[2] = -(s[2] * s[9] + s[5] * s[10] + s[8] * s[11]);
+    cam_centre(cs + CS * (size_t)i, o);
   } else {
     const double* q = ptab + PT * (size_t)slot[i - n_cam];
     o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
@@ -244,52 +218,6 @@ k_sim_pass_b(const SimRec* __restrict__ rec, int n, const double* __restrict__ a
   sim_block_sums<13>(v, lds, part + SIM_PART * (size_t)blockIdx.x);
 }
 
-// One-sided (Hestenes) Jacobi SVD of a 3 x 3 matrix: U <- U V with mutually orthogonal columns (see jacobi_svd4)
-__host__ __device__ inline void jacobi_svd3(double (&U)[3][3], double (&V)[3][3]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 24; ++sweep) {
-    bool rotated = false;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < 3; ++q) {
-        double al = 0.0, be = 0.0, ga = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { al += U[k][p] * U[k][p]; be += U[k][q] * U[k][q]; ga += U[k][p] * U[k][q]; }
-        if (!(fabs(ga) > 1e-17 * sqrt(al * be))) continue;
-        rotated = true;
-        const double zeta = (be - al) / (2.0 * ga);
-        const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
-        const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const double up = U[k][p], uq = U[k][q];
-          U[k][p] = c * up - s * uq;
-          U[k][q] = s * up + c * uq;
-          const double vp = V[k][p], vq = V[k][q];
-          V[k][p] = c * vp - s * vq;
-          V[k][q] = s * vp + c * vq;
-        }
-      }
-    }
-    if (!rotated) break;
-  }
-}
-
-template <int P, int Q>
-__host__ __device__ __forceinline__ void sim_order(double (&U)[3][3], double (&V)[3][3], double (&n2)[3]) {   // larger norm first
-  if (n2[P] >= n2[Q]) return;
-  const double t = n2[P]; n2[P] = n2[Q]; n2[Q] = t;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double a = U[k][P]; U[k][P] = U[k][Q]; U[k][Q] = a;
-    const double b = V[k][P]; V[k][P] = V[k][Q]; V[k][Q] = b;
-  }
-}
-
 // The closed form from the centred sums sh (Sigma W row-major, var_a W, lo W) and the record's W, mu_a, mu_b:
 // Sigma = U D V^T, R = U diag(1, 1, det U det V) V^T, s = tr(D diag) / var_a, t = (mu_b - s R mu_a) + lo, written into the record;
 // else the record's status becomes DEGENERATE.  The third left vector is formed as u1 x u2 (a rank-2 Sigma -- coplanar
@@ -305,7 +233,7 @@ __host__ __device__ inline void sim_closed_form(const double* __restrict__ sh, i
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) U[i][j] = sh[3 * i + j] / W;
-  jacobi_svd3(U, V);
+  jacobi_svd<3, 24>(U, V);
   double n2[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) n2[k] = U[0][k] * U[0][k] + U[1][k] * U[1][k] + U[2][k] * U[2][k];
@@ -405,10 +333,7 @@ __global__ void __launch_bounds__(64) k_sim_finish(const double* __restrict__ pa
 __global__ void k_sim_centres(const double* __restrict__ cs, int n_cams, double* __restrict__ out) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n_cams) return;
-  const double* s = cs + CS * (size_t)c;
-  out[3 * (size_t)c] = -(s[0] * s[9] + s[3] * s[10] + s[6] * s[11]);
-  out[3 * (size_t)c + 1] = -(s[1] * s[9] + s[4] * s[10] + s[7] * s[11]);
-  out[3 * (size_t)c + 2] = -(s[2] * s[9] + s[5] * s[10] + s[8] * s[11]);
+  cam_centre(cs + CS * (size_t)c, out + 3 * (size_t)c);
 }
 
 }  // namespace ba

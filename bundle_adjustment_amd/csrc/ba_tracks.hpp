@@ -31,6 +31,7 @@
 // wave per track of long_pts (DPP wave sums; the unit vectors of TRK_STAGE views at a time staged in LDS).
 #pragma once
 #include "ba_kernels.hpp"
+#include "ba_linalg.hpp"
 
 namespace ba {
 
@@ -61,16 +62,13 @@ struct TrackArgs {
 __global__ void k_track_centres(const double* __restrict__ cs, int n_cams, double* __restrict__ ctr) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n_cams) return;
-  const double* s = cs + CS * (size_t)c;
   double* o = ctr + 4 * (size_t)c;
-  o[0] = -(s[0] * s[9] + s[3] * s[10] + s[6] * s[11]);
-  o[1] = -(s[1] * s[9] + s[4] * s[10] + s[7] * s[11]);
-  o[2] = -(s[2] * s[9] + s[5] * s[10] + s[8] * s[11]);
+  cam_centre(cs + CS * (size_t)c, o);
   o[3] = 0.0;
 }
 
 // sums / maxima over the lanes of a track's group, the same bits in every lane.  8 lanes: two quad permutes and the
-// half-row mirror (a butterfly: every lane adds the same two numbers at every level); 64: ba_dpp.hpp's wave total.
+// half-row mirror (a butterfly: every lane adds the same two numbers at every level); 64: ba_dpp.hpp's wave total / maximum.
 constexpr int DPP_QUAD_1032 = 0xB1, DPP_QUAD_2301 = 0x4E, DPP_ROW_HALF_MIRROR = 0x141;
 template <int G> __device__ __forceinline__ double trk_sum(double x);
 template <> __device__ __forceinline__ double trk_sum<8>(double x) {
@@ -80,63 +78,15 @@ template <> __device__ __forceinline__ double trk_sum<8>(double x) {
   return x;
 }
 template <> __device__ __forceinline__ double trk_sum<64>(double x) { return wave_total_dpp(x); }
-// (of non-negative numbers: a lane without a source reads 0)
 template <int G> __device__ __forceinline__ double trk_max(double x);
+// (of non-negative numbers: a lane without a source reads 0)
 template <> __device__ __forceinline__ double trk_max<8>(double x) {
   x = fmax(x, dpp_f64<DPP_QUAD_1032, 0xf>(x));
   x = fmax(x, dpp_f64<DPP_QUAD_2301, 0xf>(x));
   x = fmax(x, dpp_f64<DPP_ROW_HALF_MIRROR, 0xf>(x));
   return x;
 }
-template <> __device__ __forceinline__ double trk_max<64>(double x) {
-  x = fmax(x, dpp_f64<DPP_ROW_SHR1, 0xf>(x));
-  x = fmax(x, dpp_f64<DPP_ROW_SHR2, 0xf>(x));
-  x = fmax(x, dpp_f64<DPP_ROW_SHR4, 0xf>(x));
-  x = fmax(x, dpp_f64<DPP_ROW_SHR8, 0xf>(x));
-  x = fmax(x, dpp_f64<DPP_ROW_BCAST15, 0xa>(x));
-  x = fmax(x, dpp_f64<DPP_ROW_BCAST31, 0xc>(x));
-  return readlane_f64(x, 63);
-}
-
-// Cyclic Jacobi on a symmetric 4 x 4 (full storage): A <- V^T A V diagonal, columns of V the eigenvectors.  A rotation is
-// skipped once |a_pq| <= 1e-17 sqrt(|a_pp a_qq|) (the relative criterion: the small eigenvalue keeps its digits).
-__device__ inline void jacobi_eig4(double (&A)[4][4], double (&V)[4][4]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 16; ++sweep) {
-    bool rotated = false;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < 4; ++q) {
-        const double apq = A[p][q];
-        if (!(fabs(apq) > 1e-17 * sqrt(fabs(A[p][p] * A[q][q])))) continue;
-        rotated = true;
-        const double zeta = (A[q][q] - A[p][p]) / (2.0 * apq);
-        const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
-        const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const double ap = A[k][p], aq = A[k][q];
-          A[k][p] = c * ap - s * aq;
-          A[k][q] = s * ap + c * aq;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const double ap = A[p][k], aq = A[q][k];
-          A[p][k] = c * ap - s * aq;
-          A[q][k] = s * ap + c * aq;
-          const double vp = V[k][p], vq = V[k][q];
-          V[k][p] = c * vp - s * vq;
-          V[k][q] = s * vp + c * vq;
-        }
-      }
-    }
-    if (!rotated) break;
-  }
-}
+template <> __device__ __forceinline__ double trk_max<64>(double x) { return wave_max_dpp(x); }
 
 // the view's (x, y) of step 1; false: the BAL inversion failed
 template <class CM>
@@ -235,7 +185,7 @@ __device__ __forceinline__ void track_solve(const TrackArgs& a, const int s, con
     for (int p = 0; p < 4; ++p)
 #pragma unroll
       for (int q = 0; q < 4; ++q) A[p][q] = m[ST(4, p, q)];
-    jacobi_eig4(A, V);
+    jacobi_eig<4, 16>(A, V);
     int best = 0;
     double lo = A[0][0];
     if (A[1][1] < lo) { lo = A[1][1]; best = 1; }

@@ -7,55 +7,17 @@
 // cv2.triangulatePoints (OpenCV, not installed here: restated from its published algorithm) stacks, per point,
 //     A = [x1 P1[2] - P1[0];  y1 P1[2] - P1[1];  x2 P2[2] - P2[0];  y2 P2[2] - P2[1]]        (4x4)
 // and returns the right singular vector of A's smallest singular value.  Here: thread per point, one-sided Jacobi SVD of
-// the 4x4 A itself (jacobi_svd4), column of V that belongs to the smallest singular value.  The sign of a singular vector
+// the 4x4 A itself (jacobi_svd of ba_linalg.hpp), column of V that belongs to the smallest singular value.  The sign of a singular vector
 // is arbitrary (and the reference's "+ 1e-6" makes its result depend on it at the 1e-6 level): this kernel and the
 // oracle fix it as X_h[3] >= 0.  Parity unpinned at the cv2 boundary, like every other cv2 call of the path.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "ba_linalg.hpp"
 
 namespace ba {
 
 struct TriView { double P1[12], P2[12], R[9], t[3]; };
-
-// One-sided (Hestenes) Jacobi SVD of the 4x4 A itself: plane rotations from the right make the columns of U = A V mutually
-// orthogonal; their norms are then the singular values and the columns of V the right singular vectors.  Working on A
-// rather than on A^T A keeps the conditioning of the problem (A^T A squares it: for a low-parallax pair -- a new keyframe
-// right after the last one -- the eigenvector of the smallest eigenvalue of A^T A loses half the digits; measured against
-// LAPACK's SVD at a 1 mm baseline: 7e-8 relative through A^T A, 3e-10 through A).
-__device__ inline void jacobi_svd4(double (&U)[4][4], double (&V)[4][4]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 16; ++sweep) {
-    bool rotated = false;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < 4; ++q) {
-        double al = 0.0, be = 0.0, ga = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { al += U[k][p] * U[k][p]; be += U[k][q] * U[k][q]; ga += U[k][p] * U[k][q]; }
-        if (!(fabs(ga) > 1e-17 * sqrt(al * be))) continue;            // already orthogonal to round-off
-        rotated = true;
-        const double zeta = (be - al) / (2.0 * ga);
-        const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
-        const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const double up = U[k][p], uq = U[k][q];
-          U[k][p] = c * up - s * uq;
-          U[k][q] = s * up + c * uq;
-          const double vp = V[k][p], vq = V[k][q];
-          V[k][p] = c * vp - s * vq;
-          V[k][q] = s * vp + c * vq;
-        }
-      }
-    }
-    if (!rotated) break;
-  }
-}
 
 __global__ void __launch_bounds__(256)
 k_triangulate(TriView v, int64_t n, const double2* __restrict__ pts1, const double2* __restrict__ pts2,
@@ -72,7 +34,7 @@ k_triangulate(TriView v, int64_t n, const double2* __restrict__ pts1, const doub
     A[3][k] = b.y * v.P2[8 + k] - v.P2[4 + k];
   }
   double V[4][4];
-  jacobi_svd4(A, V);                        // A <- A V: column norms = singular values
+  jacobi_svd<4, 16>(A, V);                     // A <- A V: column norms = singular values
   double sv[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) sv[k] = A[0][k] * A[0][k] + A[1][k] * A[1][k] + A[2][k] * A[2][k] + A[3][k] * A[3][k];

@@ -45,6 +45,21 @@ def precond_code(precond):
     return precond
 
 
+def _options(struct_type, default_fn, kw, names=None):
+    """A struct_type filled by the library's default_fn and overlaid with kw.  names: option -> the function that turns a
+    value given by name into its code (default: loss alone); an option the struct does not have raises TypeError."""
+    names = {"loss": loss_code} if names is None else names
+    o = struct_type()
+    _check(default_fn(C.byref(o)))
+    for k, v in kw.items():
+        if k in names:
+            v = names[k](v)
+        if not hasattr(o, k):
+            raise TypeError(f"unknown option {k}")
+        setattr(o, k, v)
+    return o
+
+
 class BAOptions(C.Structure):
     _fields_ = [("loss", C.c_int32), ("max_iters", C.c_int32), ("f_scale", C.c_double), ("ftol", C.c_double),
                 ("xtol", C.c_double), ("gtol", C.c_double), ("initial_lambda", C.c_double), ("pcg_tol", C.c_double),
@@ -111,6 +126,17 @@ ALIGN_STATUS = {"ok": 0, "too_few": 1, "degenerate": 2}   # enum ba_align_status
 TRACK_STATUS = {"ok": 0, "few_views": 1, "degenerate": 2, "behind": 3, "low_angle": 4, "high_error": 5}   # enum ba_track_status
 RESECT_STATUS = {"ok": 0, "few_points": 1, "degenerate": 2, "behind": 3, "few_inliers": 4, "high_error": 5}   # enum ba_resect_status
 RESECT_INIT = {"dlt": 0, "current": 1}   # enum ba_resect_init
+
+
+def resect_init_code(init):
+    """enum ba_resect_init value of a start given by name (or already by value); an unknown name raises ValueError."""
+    if isinstance(init, str):
+        if init not in RESECT_INIT:
+            raise ValueError(f"unknown init {init!r}: one of {sorted(RESECT_INIT)}")
+        return RESECT_INIT[init]
+    return init
+
+
 K_TRACKS = 13
 K_RESECT = 14
 K_RESECT_RANSAC = 15
@@ -599,15 +625,7 @@ class Solver:
 
     def track_options(self, **kw) -> BATrackOptions:
         """ba_default_track_options overlaid with kw (loss by name or by value, any other ba_track_options field)."""
-        o = BATrackOptions()
-        _check(self._lib.ba_default_track_options(C.byref(o)))
-        for k, v in kw.items():
-            if k == "loss":
-                v = loss_code(v)
-            if not hasattr(o, k):
-                raise TypeError(f"unknown option {k}")
-            setattr(o, k, v)
-        return o
+        return _options(BATrackOptions, self._lib.ba_default_track_options, kw)
 
     def triangulate_tracks(self, intr=None, want=True, **opts):
         """ba_triangulate_tracks: every point of the resident problem triangulated from all of its observations and the
@@ -632,19 +650,7 @@ class Solver:
 
     def resect_options(self, **kw) -> BAResectOptions:
         """ba_default_resect_options overlaid with kw (loss and init by name or by value, any other ba_resect_options field)."""
-        o = BAResectOptions()
-        _check(self._lib.ba_default_resect_options(C.byref(o)))
-        for k, v in kw.items():
-            if k == "loss":
-                v = loss_code(v)
-            if k == "init" and isinstance(v, str):
-                if v not in RESECT_INIT:
-                    raise ValueError(f"unknown init {v!r}: one of {sorted(RESECT_INIT)}")
-                v = RESECT_INIT[v]
-            if not hasattr(o, k):
-                raise TypeError(f"unknown option {k}")
-            setattr(o, k, v)
-        return o
+        return _options(BAResectOptions, self._lib.ba_default_resect_options, kw, names={"loss": loss_code, "init": resect_init_code})
 
     @staticmethod
     def _mask(m, n):
@@ -658,6 +664,19 @@ class Solver:
         a = np.ascontiguousarray(m.reshape(n), dtype=np.uint8)
         return a, a.ctypes.data_as(C.POINTER(C.c_uint8))
 
+    def _resect_head(self, intr, cams, known_points):
+        """What resect and resect_ransac pass alike: the pointers of intr, the camera selection and the known-point mask (a
+        pointer keeps its array alive), the output dict, and the pointers of its arrays in the order of the C arguments."""
+        if intr is not None:
+            intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
+        selp, knownp = self._mask(cams, self.n_cams)[1], self._mask(known_points, self.n_pts)[1]
+        n = self.n_cams
+        out = dict(poses=np.empty((n, 6)), status=np.empty(n, dtype=np.uint8), n_inliers=np.empty(n, dtype=np.int32),
+                   rms_px=np.empty(n), max_px=np.empty(n))
+        outp = (_dp(out["poses"]), out["status"].ctypes.data_as(C.POINTER(C.c_uint8)), out["n_inliers"].ctypes.data_as(_IP),
+                _dp(out["rms_px"]), _dp(out["max_px"]))
+        return (_dp(intr), selp, knownp), out, outp
+
     def resect(self, intr=None, cams=None, known_points=None, **opts):
         """ba_resect: the pose of every selected camera of the resident problem from its observations of the known points,
         the current points taken as they are (intr None: pinhole; else (Nc, 3) (f, k1, k2) of the BAL camera).  cams: bool
@@ -665,32 +684,14 @@ class Solver:
         indices, None = every point.  opts: loss, refine_iters, f_scale, init ("dlt" / "current"), min_inliers,
         max_reproj_px, max_rms_px, min_depth, write_cams.  Returns dict(poses (Nc, 6) rvec | t, status (Nc,) uint8
         (RESECT_STATUS), n_inliers (Nc,) int32, rms_px, max_px (Nc,))."""
-        ip = None
-        if intr is not None:
-            intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
-            ip = _dp(intr)
-        sel, selp = self._mask(cams, self.n_cams)
-        known, knownp = self._mask(known_points, self.n_pts)
+        (ip, selp, knownp), out, outp = self._resect_head(intr, cams, known_points)
         o = self.resect_options(**opts)
-        n = self.n_cams
-        out = dict(poses=np.empty((n, 6)), status=np.empty(n, dtype=np.uint8), n_inliers=np.empty(n, dtype=np.int32),
-                   rms_px=np.empty(n), max_px=np.empty(n))
-        _check(self._lib.ba_resect(self._h, ip, C.byref(o), selp, knownp, _dp(out["poses"]),
-                                   out["status"].ctypes.data_as(C.POINTER(C.c_uint8)), out["n_inliers"].ctypes.data_as(_IP),
-                                   _dp(out["rms_px"]), _dp(out["max_px"])))
+        _check(self._lib.ba_resect(self._h, ip, C.byref(o), selp, knownp, *outp))
         return out
 
     def ransac_options(self, **kw) -> BARansacOptions:
         """ba_default_ransac_options overlaid with kw (loss by name or by value, any other ba_ransac_options field)."""
-        o = BARansacOptions()
-        _check(self._lib.ba_default_ransac_options(C.byref(o)))
-        for k, v in kw.items():
-            if k == "loss":
-                v = loss_code(v)
-            if not hasattr(o, k):
-                raise TypeError(f"unknown option {k}")
-            setattr(o, k, v)
-        return o
+        return _options(BARansacOptions, self._lib.ba_default_ransac_options, kw)
 
     def resect_ransac(self, intr=None, cams=None, known_points=None, **opts):
         """ba_resect_ransac: the pose of every selected camera from raw matches -- n_hyp minimal P3P samples per camera scored
@@ -699,20 +700,10 @@ class Solver:
         write_cams, max_rms_px, min_depth.  Returns ``resect``'s dict plus obs_inlier (n_obs,) bool in the order of the
         problem's observations: the final consensus set, what to keep for the next solve
         (``triangulation.filter_observations``)."""
-        ip = None
-        if intr is not None:
-            intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
-            ip = _dp(intr)
-        sel, selp = self._mask(cams, self.n_cams)
-        known, knownp = self._mask(known_points, self.n_pts)
+        (ip, selp, knownp), out, outp = self._resect_head(intr, cams, known_points)
         o = self.ransac_options(**opts)
-        n = self.n_cams
-        out = dict(poses=np.empty((n, 6)), status=np.empty(n, dtype=np.uint8), n_inliers=np.empty(n, dtype=np.int32),
-                   rms_px=np.empty(n), max_px=np.empty(n))
         inl = np.zeros(self.n_obs, dtype=np.uint8)
-        _check(self._lib.ba_resect_ransac(self._h, ip, C.byref(o), selp, knownp, _dp(out["poses"]),
-                                          out["status"].ctypes.data_as(C.POINTER(C.c_uint8)), out["n_inliers"].ctypes.data_as(_IP),
-                                          _dp(out["rms_px"]), _dp(out["max_px"]), inl.ctypes.data_as(C.POINTER(C.c_uint8))))
+        _check(self._lib.ba_resect_ransac(self._h, ip, C.byref(o), selp, knownp, *outp, inl.ctypes.data_as(C.POINTER(C.c_uint8))))
         out["obs_inlier"] = inl.astype(bool)
         return out
 

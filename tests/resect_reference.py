@@ -9,7 +9,7 @@ tests/track_reference.py: pinhole ``K4``, looking down +z; BAL ``intr = (f, k1, 
 import numpy as np
 
 from bundle_adjustment_amd.rotations import rvecs_to_matrices
-from tests.track_reference import COST_SLACK, bal_undistort, jacobi_eig4, loss_terms
+from tests.track_reference import COST_SLACK, bal_undistort, jacobi_eig, loss_terms
 
 OK, FEW_POINTS, DEGENERATE, BEHIND, FEW_INLIERS, HIGH_ERROR = range(6)
 PIVOT_MIN, RANK_TOL = 1e-8, 1e-6
@@ -151,7 +151,7 @@ def dlt_matrix(Xt, xy, method):
     if L is None:
         return None
     Wx, Wy = np.linalg.solve(L, Sx), np.linalg.solve(L, Sy)
-    lam, V = jacobi_eig4(Sq - Wx.T @ Wx - Wy.T @ Wy)
+    lam, V = jacobi_eig(Sq - Wx.T @ Wx - Wy.T @ Wy)
     p3 = V[:, int(np.argmin(lam))]
     return np.stack([np.linalg.solve(L.T, Wx @ p3), np.linalg.solve(L.T, Wy @ p3), p3])
 

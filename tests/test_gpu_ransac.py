@@ -281,6 +281,29 @@ def test_two_calls_give_identical_bits_and_another_seed_the_same_outcome(model):
     assert np.array_equal(other["obs_inlier"], a["obs_inlier"])
 
 
+def test_resect_and_resect_ransac_interleaved_keep_their_own_state():
+    """ba_resect and ba_resect_ransac go through one upload path and one staging buffer for pt_known: a ba_resect_ransac with
+    another mask, another selection and other intrinsics between two identical ba_resect calls leaves the second as the
+    first, bit for bit, and is itself what a fresh handle gives."""
+    base, cams_true, pts_true = make_problem(6, 60, 4, K4=K4, return_truth=True)
+    prob, _ = R.in_model("bal", cams_true, pts_true, base.cam_idx, base.pt_idx, base.cams, pts_true, np.random.default_rng(3))
+    known_a, known_b = np.arange(60) % 3 != 0, np.arange(60) % 4 != 1
+    sel_a, sel_b = np.array([1, 1, 0, 1, 1, 0], dtype=bool), np.array([0, 1, 1, 1, 0, 1], dtype=bool)
+    with hip_backend.Solver(0) as s:
+        intr_a = upload(s, prob)
+        intr_b = intr_a * np.array([1.002, 0.9, 1.1])
+        first = s.resect(intr=intr_a, cams=sel_a, known_points=known_a)
+        second = s.resect_ransac(intr=intr_b, cams=sel_b, known_points=known_b, n_hyp=64)
+        third = s.resect(intr=intr_a, cams=sel_a, known_points=known_a)
+    with hip_backend.Solver(0) as s:
+        upload(s, prob)
+        fresh = s.resect_ransac(intr=intr_b, cams=sel_b, known_points=known_b, n_hyp=64)
+    print(f"resect status {first['status']}, resect_ransac status {second['status']}, inliers {second['n_inliers']}")
+    assert (first["status"][sel_a] == R.OK).all()        # (every selected camera sees 22 or more of the known points)
+    assert same(first, third)
+    assert same(second, fresh)
+
+
 # ------------------------------------------------------------------------------------------------ 8 handle hygiene
 SOLVE = dict(loss="huber", max_iters=6, small_solver=1)
 SAME = ("final_cost", "final_sse", "iterations", "pcg_iterations", "final_lambda")

@@ -35,7 +35,7 @@ def bal_undistort(uv, f, k1, k2):
     return qx * sc, qy * sc, ok
 
 
-def jacobi_eig4(M):
+def jacobi_eig(M):
     """Cyclic Jacobi on a symmetric 4 x 4, the device's rotation order and stopping rule: (eigenvalues, eigenvectors)."""
     A = np.array(M, dtype=np.float64)
     V = np.eye(4)
@@ -138,7 +138,7 @@ def dlt(v, xy, method="jacobi"):
     if method == "svd":
         Xh = np.linalg.svd(rows)[2][-1]
     else:
-        lam, V = jacobi_eig4(rows.T @ rows)
+        lam, V = jacobi_eig(rows.T @ rows)
         Xh = V[:, int(np.argmin(lam))]
     if Xh[3] < 0.0:
         Xh = -Xh
