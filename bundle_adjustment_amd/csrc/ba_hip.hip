@@ -311,8 +311,8 @@ struct ba_handle {
   DBuf<double> dev_lam;        // device word a riding k_scalars stores the next damping in; 0 = not yet (ba_kernels.hpp, ScalarsArgs::lam_slot)
   DBuf<double> verdict;        // PCG verdict words {gamma, zeta, finished, -} x 2 iteration parities (point pass -> camera pass, vector kernel)
   int cam_segl = 64;           // lanes per (camera, partition) segment in the PCG camera pass: 16 or 64
-  int nblkP = 1, ppb = 1, nblkV = 1;   // nblkV: camera-vector workgroups of the pinhole (VEC_CAMS cameras each)
-  int nblkVm[2] = {1, 1};              // ... per camera model (CM::VC cameras each)
+  int nblkP = 1, ppb = 1;
+  int nblkVm[2] = {1, 1};      // camera-vector workgroups per camera model (CM::VC cameras each; [0] also k_lin_finalize's, VEC_CAMS each)
   size_t lds_bytes_m[2] = {0, 0};   // dynamic LDS of the point passes (largest window that fits), per camera model (row strides differ)
   bool jac_f32 = false;        // PCG passes recompute the Jacobian blocks in fp32 (ba_options.jacobian_precision = 1)
   bool all_lds_m[2] = {true, true};  // every point-pass workgroup's camera window fits in LDS, per camera model
@@ -351,6 +351,11 @@ struct ba_handle {
   }
 };
 
+// What the host needs of a camera model (ba_models.hpp), indexed like ba_handle::model
+struct ModelDims { int nb, nh, nl, vc; };
+static constexpr ModelDims kModel[2] = {{Pinhole::NB, Pinhole::NH, Pinhole::NL, Pinhole::VC}, {BalCam::NB, BalCam::NH, BalCam::NL, BalCam::VC}};
+static_assert(Pinhole::ID == 0 && BalCam::ID == 1 && VEC_CAMS == Pinhole::VC, "kModel / nblkVm are indexed by the model's ID");
+
 // Every kernel launch goes through BA_LAUNCH: a launch the runtime refuses (dynamic LDS above the limit, an empty
 // grid, ...) is not reported by a later stream synchronise, so the error is picked up right here and kept in the
 // handle until the next check_launches().
@@ -366,12 +371,13 @@ static void note_launch(ba_handle* h, const char* what) {
     hipLaunchKernelGGL(kern, __VA_ARGS__);    \
     note_launch(h, #kern);                    \
   } while (0)
-// kern<BalCam> when bal, else kern<Pinhole>: the launches of the stand-alone features (tracks, resection), whose camera
-// model travels with the call
-#define BA_LAUNCH_CM(bal, kern, ...)                   \
+// The statement (one call or one launch) with CM = BalCam when bal, else with CM = Pinhole: how every launch and launch helper picks the
+// instantiation of its camera model (ba_models.hpp) -- h->model inside the loop, the call's own flag in the stand-alone
+// features (tracks, resection)
+#define BA_BY_MODEL(bal, ...)                          \
   do {                                                 \
-    if (bal) BA_LAUNCH(kern<BalCam>, __VA_ARGS__);     \
-    else BA_LAUNCH(kern<Pinhole>, __VA_ARGS__);        \
+    if (bal) { using CM = BalCam; __VA_ARGS__; }       \
+    else { using CM = Pinhole; __VA_ARGS__; }          \
   } while (0)
 static int check_launches(ba_handle* h);
 // drain the stream, then report the first launch that failed since the last check (a refused launch leaves the
@@ -945,8 +951,7 @@ struct StageClock {
 static void set_dimensions(ba_handle* h, int Nc, int Np, int No, const double K4[4], int fixed_cam) {
   h->Nc = Nc; h->Np = Np; h->Nobs = No; h->fixed = fixed_cam;
   memcpy(h->K4, K4, sizeof h->K4);
-  h->nblkV = (Nc + VEC_CAMS - 1) / VEC_CAMS;
-  h->nblkVm[0] = (Nc + Pinhole::VC - 1) / Pinhole::VC; h->nblkVm[1] = (Nc + BalCam::VC - 1) / BalCam::VC;
+  for (int m = 0; m < 2; ++m) h->nblkVm[m] = (Nc + kModel[m].vc - 1) / kModel[m].vc;
 }
 // ... and the point passes' dynamic LDS, from every point-pass workgroup's camera window (first camera, number of cameras).
 // A window is staged in LDS when its rows fit; the row stride depends on the camera model (18 doubles for the reference's
@@ -1547,15 +1552,15 @@ extern "C" int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64
 }
 
 // block sizes of the running camera model
-static int nb_of(const ba_handle* h) { return h->model ? BalCam::NB : Pinhole::NB; }
+static int nb_of(const ba_handle* h) { return kModel[h->model].nb; }
 // partitions a consumer of the camera passes' partial sums adds up: all of them on one rank; in a multi-rank job the
 // arrays arrive folded into partition 0 and all-reduced (fold_and_reduce), the other partitions are stale
 static int nparts_of(const ba_handle* h) { return h->multi ? 1 : NPART; }
 // the camera half's running sums a consumer reads: all partitions on one rank; the folded, all-reduced message otherwise
 static const double* partL_of(const ba_handle* h, int buf) { return h->multi ? h->linmsg[buf].p + 8 : h->partL[buf].p; }
 static int nbv(const ba_handle* h) { return h->nblkVm[h->model]; }      // camera-vector workgroups of the active model
-static int nh_of(const ba_handle* h) { return h->model ? BalCam::NH : Pinhole::NH; }
-static int nl_of(const ba_handle* h) { return h->model ? BalCam::NL : Pinhole::NL; }
+static int nh_of(const ba_handle* h) { return kModel[h->model].nh; }
+static int nl_of(const ba_handle* h) { return kModel[h->model].nl; }
 static size_t lds_of(const ba_handle* h) { return h->lds_bytes_m[h->model]; }
 static bool all_lds_of(const ba_handle* h) { return h->all_lds_m[h->model]; }
 static double* bc_ptr(ba_handle* h) { return h->HccBc.p + nh_of(h) * (size_t)h->Nc; }
@@ -1904,21 +1909,17 @@ extern "C" int ba_get_rotations(ba_handle* h, double* R) {
 }
 
 // ---------------------------------------------------------------------- launch helpers
-// Every helper dispatches on the camera model of the running call (h->model): the same kernel templates, instantiated
-// for the reference's pinhole and for the BAL camera (ba_models.hpp).
-#define BA_BY_MODEL(CALL_T)                      \
-  do {                                           \
-    if (h->model) CALL_T(BalCam);                \
-    else CALL_T(Pinhole);                        \
-  } while (0)
-
-static void launch_residual(ba_handle* h, int which, ba_loss loss, double fscale, double* r_out) {
+// Every helper dispatches on the camera model of the running call (BA_BY_MODEL(h->model, ..)): the same kernel
+// templates, instantiated for the reference's pinhole and for the BAL camera (ba_models.hpp).
+// intr: the BAL camera on the pinhole state with these device (f, k1, k2) (ba_residuals_bal stages them in h->tri
+// without switching the model); null: the model of the running call with the intrinsics of parameter set `which`
+static void launch_residual(ba_handle* h, int which, ba_loss loss, double fscale, double* r_out, const double* intr = nullptr) {
   Scope sc(h, BA_K_RESIDUAL);
   const bool robust = loss != BA_LOSS_LINEAR;
-  if (h->model) {
+  if (h->model || intr) {                // (the two residual kernels predate the models and are no template of CM: no BA_BY_MODEL)
     auto kern = robust ? k_cam_residual_bal<true> : k_cam_residual_bal<false>;
-    BA_LAUNCH(kern, dim3(cam_grid(h)), dim3(64 * WPB), 0, h->stream, h->cs[which].p, (const double*)h->intr[which].p, h->ptab[which].p,
-              h->offk.p, h->c_pt.p, uv_arr(h, h->c_uv), h->c_orig.p, fscale, (int)loss, h->Nc, h->cam_band, r_out, h->partR.p);
+    BA_LAUNCH(kern, dim3(cam_grid(h)), dim3(64 * WPB), 0, h->stream, h->cs[which].p, intr ? intr : (const double*)h->intr[which].p,
+              h->ptab[which].p, h->offk.p, h->c_pt.p, uv_arr(h, h->c_uv), h->c_orig.p, fscale, (int)loss, h->Nc, h->cam_band, r_out, h->partR.p);
     return;
   }
   auto kern = robust ? k_cam_residual<true> : k_cam_residual<false>;
@@ -1993,16 +1994,13 @@ static void launch_lin_cam_t(ba_handle* h, int which, int buf, ba_loss loss, dou
 }
 static void launch_lin_cam(ba_handle* h, int which, int buf, ba_loss loss, double fscale, bool cost = false) {
   Scope sc(h, BA_K_LINEARIZE_CAM);
-#define CALL_T(CM) launch_lin_cam_t<CM>(h, which, buf, loss, fscale, cost)
-  BA_BY_MODEL(CALL_T);
-#undef CALL_T
+  BA_BY_MODEL(h->model, launch_lin_cam_t<CM>(h, which, buf, loss, fscale, cost));
 }
 static void launch_lin_finalize(ba_handle* h) {
   Scope sc(h, BA_K_MISC);
-#define CALL_T(CM) BA_LAUNCH(k_lin_finalize<CM::NB>, dim3(h->nblkV), dim3(VEC_BLOCK), 0, h->stream, partL_of(h, h->lb), \
-                             nparts_of(h), h->cs[h->cur].p, h->Nc, h->fixed, h->HccBc.p, bc_ptr(h), cam_held_ptr(h), cam_priors(h, h->cur))
-  BA_BY_MODEL(CALL_T);
-#undef CALL_T
+  // (VEC_CAMS cameras per workgroup for either model: nblkVm[0])
+  BA_BY_MODEL(h->model, BA_LAUNCH(k_lin_finalize<CM::NB>, dim3(h->nblkVm[0]), dim3(VEC_BLOCK), 0, h->stream, partL_of(h, h->lb), nparts_of(h),
+                                  h->cs[h->cur].p, h->Nc, h->fixed, h->HccBc.p, bc_ptr(h), cam_held_ptr(h), cam_priors(h, h->cur)));
 }
 static PtWork pt_work(ba_handle* h) {        // every point; long tracks skipped when they have a launch of their own
   return PtWork{nullptr, h->Np, h->nblkL ? h->long_thr : 0x7fffffff, 0, h->ppb, /*xcd_ranges=*/1};
@@ -2051,9 +2049,7 @@ static void launch_lin_pt(ba_handle* h, int w, int pbuf, ba_loss loss, double fs
   ScalarsArgs sa;
   if (rider) sa = *rider;
   else { memset(&sa, 0, sizeof sa); }
-#define CALL_T(CM) launch_lin_pt_t<CM>(h, w, pbuf, loss, fscale, lambda, lam_dev, sa)
-  BA_BY_MODEL(CALL_T);
-#undef CALL_T
+  BA_BY_MODEL(h->model, launch_lin_pt_t<CM>(h, w, pbuf, loss, fscale, lambda, lam_dev, sa));
   // point priors: L_p into Hpp | bp, the damped inverse, y0 and the gtol maxima redone (at the damping the pass used)
   if (h->any_pt_prior)
     BA_LAUNCH(k_prior_points, dim3(h->nblkP + h->nblkL), dim3(256), 0, h->stream, (const double*)h->pt_info.p, (const double*)h->pt_mean.p,
@@ -2116,9 +2112,7 @@ static void launch_cam_schur_t(ba_handle* h, bool robust, bool diag, bool pcg, i
 static void launch_cam_schur(ba_handle* h, bool robust, bool diag, bool pcg, int k, double tol2, int min_iters) {
   Scope sc(h, diag ? BA_K_PRECOND : BA_K_SCHUR_CAM);
   (void)tol2; (void)min_iters;
-#define CALL_T(CM) launch_cam_schur_t<CM>(h, robust, diag, pcg, k)
-  BA_BY_MODEL(CALL_T);
-#undef CALL_T
+  BA_BY_MODEL(h->model, launch_cam_schur_t<CM>(h, robust, diag, pcg, k));
 }
 // point pass with the camera vector in vtil; mode 0 = PCG iteration k, mode 1 = back substitution
 // gmax_out (first PCG probe behind a fresh linearisation): host-mapped word that receives max |gradient|
@@ -2182,9 +2176,7 @@ static void launch_pt_schur(ba_handle* h, bool robust, int mode, int k, double t
   CamUpdateArgs cu;
   if (rider) cu = *rider;
   else memset(&cu, 0, sizeof cu);
-#define CALL_T(CM) launch_pt_schur_t<CM>(h, robust, mode, k, tol2, min_iters, flag_base, gmax_out, cu, f32)
-  BA_BY_MODEL(CALL_T);
-#undef CALL_T
+  BA_BY_MODEL(h->model, launch_pt_schur_t<CM>(h, robust, mode, k, tol2, min_iters, flag_base, gmax_out, cu, f32));
 }
 
 // multi-rank: a buffer of NPART per-partition partial sums is folded in place (partition 0 <- the sum
@@ -2240,13 +2232,8 @@ static void launch_pcg_setup(ba_handle* h, double lambda, int precond, bool fina
                 precond, h->Nc, h->fixed, h->Hccd.p, h->Minv.p, h->gvec.p, h->x.p, h->r.p, h->p.p, h->s.p,     \
                 h->z.p, h->camA[h->cur].p, h->partV.p, h->st.p, h->partGc.p, h->vx.p, \
                 cam_held_ptr(h), cam_priors(h, h->cur, finalize), cam_gl_ptr(h)
-#define CALL_T(CM)                                                                                               \
-  do {                                                                                                           \
-    if (finalize) BA_LAUNCH((k_pcg_setup<CM, true>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, SU_ARGS);    \
-    else          BA_LAUNCH((k_pcg_setup<CM, false>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, SU_ARGS);   \
-  } while (0)
-  BA_BY_MODEL(CALL_T);
-#undef CALL_T
+  if (finalize) BA_BY_MODEL(h->model, BA_LAUNCH((k_pcg_setup<CM, true>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, SU_ARGS));
+  else          BA_BY_MODEL(h->model, BA_LAUNCH((k_pcg_setup<CM, false>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, SU_ARGS));
 #undef SU_ARGS
   // shared intrinsics: the group sums of the preconditioner's 3 x 3 blocks, of g and of bc, then the members' rows 6-8
   // and the workgroups' partials with the leader rule (ba_kernels.hpp, "shared intrinsics")
@@ -2260,19 +2247,78 @@ static void launch_pcg_setup(ba_handle* h, double lambda, int precond, bool fina
   }
 }
 
-// --------------------------------------------------------------------- K1 entry point
-extern "C" int ba_residuals(ba_handle* h, int32_t loss, double f_scale, double* r, double* sse, double* cost) {
-  if (!h) return fail(BA_ERR_INVALID, "null handle");
+// ------------------------------------------------------------------------------------------------------------------
+// bal_enter / bal_leave: the two ends of with_model() below, the scope in which every entry point that takes `intr` runs
+// its body with the BAL 9-parameter camera [rvec | t | f k1 k2] (BASELINE config 5 is stated
+// on a BAL problem; the reference's only camera is cv2.projectPoints(..., distCoeffs=None), src/bundle_adjuster.py:67).
+// Cameras (rvec, t) and points are the handle's (ba_set_params / ba_get_params); the per-camera (f, k1, k2) travel with the call.  K4 of
+// ba_set_problem is not used.  The entry points switch the handle to the BalCam instantiation of every kernel
+// (ba_models.hpp) for the duration of the call: same LM / Schur / PCG loop, same device-side verdicts and speculation,
+// same multi-rank exchange, 9x9 camera blocks.
+static int bal_enter(ba_handle* h, const double* intr) {
+  HIPCHECK(hipMemcpyAsync(h->intr[h->cur].p, intr, 3 * (size_t)h->Nc * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  h->model = 1;
+  h->linearized = false;
+  BA_LAUNCH(k_cam_prepare<BalCam>, dim3((h->Nc + 63) / 64), dim3(64), 0, h->stream, h->cams[h->cur].p, (const double*)h->intr[h->cur].p,
+            h->cs[h->cur].p, h->camA[h->cur].p, h->Nc);
+  return BA_OK;
+}
+// back to the pinhole layout of the camera table (what every other entry point reads), at the current parameters
+static void bal_leave(ba_handle* h) {
+  h->model = 0;
+  h->linearized = false;                      // the linearisation buffers hold 9-parameter blocks
+  BA_LAUNCH(k_cam_prepare<Pinhole>, dim3((h->Nc + 63) / 64), dim3(64), 0, h->stream, h->cams[h->cur].p, (const double*)h->intr[h->cur].p,
+            h->cs[h->cur].p, h->camA[h->cur].p, h->Nc);
+}
+// The model scope: body() with the BAL camera of `intr` (null: the pinhole, no switch).  Whatever way body() ends, the
+// handle is the pinhole's again and idle: after a failure the stream is drained and a refused launch forgotten (the
+// failure that is reported is the first one, whose text is kept), then the pinhole camera state is rebuilt at the current
+// parameters -- a failure in the middle of a solve may have left it behind them -- and the stream drained.
+template <class Body>
+static int with_model(ba_handle* h, const double* intr, Body body) {
+  if (intr) if (int rc = bal_enter(h, intr)) { h->model = 0; return rc; }
+  int rc = body();
+  const std::string msg = g_err;
+  if (rc != BA_OK) { (void)hipStreamSynchronize(h->stream); h->launch_err = hipSuccess; }
+  if (intr) {
+    bal_leave(h);
+    if (hipStreamSynchronize(h->stream) != hipSuccess && rc == BA_OK) return fail(BA_ERR_HIP, "stream synchronise failed");
+  }
+  g_err = msg;
+  return rc;
+}
+
+// What the evaluating entry points (ba_residuals*, ba_linearize*, ba_schur_system, ba_covariance) check alike, behind their
+// own null-argument test.  pinhole_refuses: what a call with the pinhole camera cannot honour -- CK_BAL_BITS: held f, k1, k2
+// and 9-parameter priors, CK_SHARED: shared intrinsics; 0 for a BAL call and for the residual, which reads neither.
+enum { CK_BAL_BITS = 1, CK_SHARED = 2 };
+static int check_eval(const ba_handle* h, int32_t loss, double f_scale, int pinhole_refuses) {
   if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
+  if ((pinhole_refuses & CK_BAL_BITS) && (h->cam_held_or & ~0x3fu))
+    return fail(BA_ERR_INVALID, "camera mask bits 6-8 (f, k1, k2) need the BAL camera model");
+  if ((pinhole_refuses & CK_SHARED) && h->n_shared) return fail(BA_ERR_INVALID, "%s", kSharedNeedsBal);
+  if ((pinhole_refuses & CK_BAL_BITS) && h->prior_nb == 9) return fail(BA_ERR_INVALID, "%s", kPriorNeedsBal);
   if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
   if (!(f_scale > 0)) return fail(BA_ERR_INVALID, "f_scale must be positive");
+  return BA_OK;
+}
+
+// --------------------------------------------------------------------- K1 entry points
+// intr != NULL: the BAL 9-parameter camera (row f2) on the same problem upload and row order, the cameras' (f, k1, k2)
+// handed over per call and staged in h->tri; the handle's K4 is then not used.
+static int residuals_impl(ba_handle* h, const double* intr, int32_t loss, double f_scale, double* r, double* sse, double* cost) {
+  if (int rc = check_eval(h, loss, f_scale, 0)) return rc;
   if (set_device(h)) return BA_ERR_HIP;
+  if (intr) {
+    HIPCHECK(h->tri.alloc(3 * (size_t)h->Nc + 8));
+    HIPCHECK(hipMemcpyAsync(h->tri.p, intr, 3 * (size_t)h->Nc * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  }
   double* rdev = nullptr;
   if (r && h->Nobs > 0) {
     HIPCHECK(h->rbuf.alloc(2 * (size_t)h->Nobs));
     rdev = h->rbuf.p;
   }
-  launch_residual(h, h->cur, (ba_loss)loss, f_scale, rdev);
+  launch_residual(h, h->cur, (ba_loss)loss, f_scale, rdev, intr ? h->tri.p : nullptr);
   launch_scalars(h, false);
   if (int rc = allreduce(h, h->scal.p, 2)) return rc;
   HIPCHECK(hipMemcpyAsync(h->h_scal, h->scal.p, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2282,71 +2328,55 @@ extern "C" int ba_residuals(ba_handle* h, int32_t loss, double f_scale, double* 
   if (cost) *cost = 0.5 * h->h_scal[1];
   return BA_OK;
 }
-
-// K1 for the BAL 9-parameter camera (row f2): same problem upload and row order as ba_residuals, the cameras'
-// (f, k1, k2) handed over per call; the handle's K4 is not used.
+extern "C" int ba_residuals(ba_handle* h, int32_t loss, double f_scale, double* r, double* sse, double* cost) {
+  if (!h) return fail(BA_ERR_INVALID, "null handle");
+  return residuals_impl(h, nullptr, loss, f_scale, r, sse, cost);
+}
 extern "C" int ba_residuals_bal(ba_handle* h, const double* intr, int32_t loss, double f_scale, double* r, double* sse,
                                 double* cost) {
   if (!h || !intr) return fail(BA_ERR_INVALID, "null argument");
-  if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
-  if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
-  if (!(f_scale > 0)) return fail(BA_ERR_INVALID, "f_scale must be positive");
-  if (set_device(h)) return BA_ERR_HIP;
-  HIPCHECK(h->tri.alloc(3 * (size_t)h->Nc + 8));
-  HIPCHECK(hipMemcpyAsync(h->tri.p, intr, 3 * (size_t)h->Nc * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  double* rdev = nullptr;
-  if (r && h->Nobs > 0) {
-    HIPCHECK(h->rbuf.alloc(2 * (size_t)h->Nobs));
-    rdev = h->rbuf.p;
-  }
-  {
-    Scope sc(h, BA_K_RESIDUAL);
-    auto kern = loss != BA_LOSS_LINEAR ? k_cam_residual_bal<true> : k_cam_residual_bal<false>;
-    BA_LAUNCH(kern, dim3(cam_grid(h)), dim3(64 * WPB), 0, h->stream, h->cs[h->cur].p, (const double*)h->tri.p, h->ptab[h->cur].p,
-              h->offk.p, h->c_pt.p, uv_arr(h, h->c_uv), h->c_orig.p, f_scale, (int)loss, h->Nc, h->cam_band, rdev, h->partR.p);
-  }
-  launch_scalars(h, false);
-  if (int rc = allreduce(h, h->scal.p, 2)) return rc;
-  HIPCHECK(hipMemcpyAsync(h->h_scal, h->scal.p, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (rdev) HIPCHECK(hipMemcpyAsync(r, rdev, 2 * (size_t)h->Nobs * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  BA_SYNC(h);
-  if (sse) *sse = h->h_scal[0];
-  if (cost) *cost = 0.5 * h->h_scal[1];
-  return BA_OK;
+  return residuals_impl(h, intr, loss, f_scale, r, sse, cost);
 }
 
-// --------------------------------------------------------------------- K2 entry point
+// --------------------------------------------------------------------- K2 entry points
+// per-point blocks back in the caller's point order: `width` doubles per point of src, through `tmp`, to the host
+static int copy_point_rows(ba_handle* h, const double* src, int width, double* tmp, double* host) {
+  if (!host || !h->Np) return BA_OK;
+  BA_LAUNCH(k_unpermute_rows, dim3((h->Np + 255) / 256), dim3(256), 0, h->stream, src, h->slot.p, h->Np, width, tmp);
+  HIPCHECK(hipMemcpyAsync(host, tmp, width * (size_t)h->Np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  return BA_OK;
+}
+// intr != NULL: the BAL camera, 45 + 9 doubles per camera in Hcc | bc
+static int linearize_impl(ba_handle* h, const double* intr, int32_t loss, double f_scale, double* Hcc, double* bc, double* Hpp, double* bp) {
+  if (int rc = check_eval(h, loss, f_scale, intr ? 0 : CK_BAL_BITS | CK_SHARED)) return rc;
+  if (set_device(h)) return BA_ERR_HIP;
+  return with_model(h, intr, [&]() -> int {
+    launch_lin_cam(h, h->cur, h->lb, (ba_loss)loss, f_scale);
+    if (int rc = exchange_partL(h, h->lb)) return rc;
+    launch_lin_finalize(h);
+    launch_lin_pt(h, h->cur, h->pb, (ba_loss)loss, f_scale, 1.0);
+    if (!intr) {                  // (a BAL linearisation does not outlive its scope)
+      h->linearized = true;
+      h->lin_loss = (ba_loss)loss;
+      h->lin_fscale = f_scale;
+    }
+    if (Hcc) HIPCHECK(hipMemcpyAsync(Hcc, h->HccBc.p, nh_of(h) * (size_t)h->Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (bc) HIPCHECK(hipMemcpyAsync(bc, bc_ptr(h), nb_of(h) * (size_t)h->Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if ((Hpp || bp) && h->Np) HIPCHECK(h->rbuf.alloc(6 * (size_t)h->Np));
+    if (int rc = copy_point_rows(h, h->Hpp[h->pb].p, 6, h->rbuf.p, Hpp)) return rc;
+    if (int rc = copy_point_rows(h, h->bp[h->pb].p, 3, h->stage.p, bp)) return rc;
+    BA_SYNC(h);
+    return BA_OK;
+  });
+}
 extern "C" int ba_linearize(ba_handle* h, int32_t loss, double f_scale, double* Hcc, double* bc, double* Hpp, double* bp) {
   if (!h) return fail(BA_ERR_INVALID, "null handle");
-  if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
-  if (h->cam_held_or & ~0x3fu) return fail(BA_ERR_INVALID, "camera mask bits 6-8 (f, k1, k2) need the BAL camera model");
-  if (h->n_shared) return fail(BA_ERR_INVALID, "%s", kSharedNeedsBal);
-  if (h->prior_nb == 9) return fail(BA_ERR_INVALID, "%s", kPriorNeedsBal);
-  if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
-  if (!(f_scale > 0)) return fail(BA_ERR_INVALID, "f_scale must be positive");
-  if (set_device(h)) return BA_ERR_HIP;
-  launch_lin_cam(h, h->cur, h->lb, (ba_loss)loss, f_scale);
-  if (int rc = exchange_partL(h, h->lb)) return rc;
-  launch_lin_finalize(h);
-  launch_lin_pt(h, h->cur, h->pb, (ba_loss)loss, f_scale, 1.0);
-  h->linearized = true;
-  h->lin_loss = (ba_loss)loss;
-  h->lin_fscale = f_scale;
-  if (Hcc) HIPCHECK(hipMemcpyAsync(Hcc, h->HccBc.p, 21 * (size_t)h->Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (bc) HIPCHECK(hipMemcpyAsync(bc, bc_ptr(h), 6 * (size_t)h->Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if ((Hpp || bp) && h->Np) {          // per-point blocks back in the caller's point order
-    HIPCHECK(h->rbuf.alloc(6 * (size_t)h->Np));
-    if (Hpp) {
-      BA_LAUNCH(k_unpermute_rows, dim3((h->Np + 255) / 256), dim3(256), 0, h->stream, h->Hpp[h->pb].p, h->slot.p, h->Np, 6, h->rbuf.p);
-      HIPCHECK(hipMemcpyAsync(Hpp, h->rbuf.p, 6 * (size_t)h->Np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    }
-    if (bp) {
-      BA_LAUNCH(k_unpermute_rows, dim3((h->Np + 255) / 256), dim3(256), 0, h->stream, h->bp[h->pb].p, h->slot.p, h->Np, 3, h->stage.p);
-      HIPCHECK(hipMemcpyAsync(bp, h->stage.p, 3 * (size_t)h->Np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    }
-  }
-  BA_SYNC(h);
-  return BA_OK;
+  return linearize_impl(h, nullptr, loss, f_scale, Hcc, bc, Hpp, bp);
+}
+extern "C" int ba_linearize_bal(ba_handle* h, const double* intr, int32_t loss, double f_scale, double* Hcc, double* bc,
+                                double* Hpp, double* bp) {
+  if (!h || !intr) return fail(BA_ERR_INVALID, "null argument");
+  return linearize_impl(h, intr, loss, f_scale, Hcc, bc, Hpp, bp);
 }
 
 // --------------------------------------------------------------------- K4 test hooks
@@ -2365,32 +2395,25 @@ static int damped_system(ba_handle* h, double lambda, bool schur_diag, bool inve
   return BA_OK;
 }
 
-static int bal_enter(ba_handle* h, const double* intr);
-static void bal_leave(ba_handle* h);
 // The reduced camera system exactly as one LM iteration of ba_solve forms and uses it: linearisation at the current
 // parameters (camera half, point half with the damped inverses at lambda), then damped_system() for the right-hand side g
 // and the preconditioner blocks Minv, then S v for each of n_vec vectors in the PCG loop's launch form -- the point pass
 // mode 0 (fp32 Jacobian blocks when jacobian_precision = 1), the camera pass k_cam_schur<.., PCG = true, .., cam_segl>
 // behind a "go on" verdict for iteration 0 -- with Hccd v - W y folded per camera by k_schur_combine.
 // precond 2: the blocks are built at lambda_prev and kept for the system at lambda (ba_options.precond_lag: g then comes
-// from the 6-sum camera pass).  intr != NULL: the BAL camera, between bal_enter and bal_leave like ba_linearize_bal.
+// from the 6-sum camera pass).  intr != NULL: the BAL camera (with_model).
 extern "C" int ba_schur_system(ba_handle* h, const double* intr, int32_t loss, double f_scale, double lambda, int32_t precond,
                                double lambda_prev, int32_t jacobian_precision, int32_t n_vec, const double* v, double* sv,
                                double* g, double* minv) {
   if (!h) return fail(BA_ERR_INVALID, "null handle");
   if (n_vec < 0 || (n_vec > 0 && (!v || !sv))) return fail(BA_ERR_INVALID, "n_vec vectors need v and sv");
-  if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
-  if (!intr && (h->cam_held_or & ~0x3fu)) return fail(BA_ERR_INVALID, "camera mask bits 6-8 (f, k1, k2) need the BAL camera model");
-  if (!intr && h->prior_nb == 9) return fail(BA_ERR_INVALID, "%s", kPriorNeedsBal);
-  if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
-  if (!(f_scale > 0)) return fail(BA_ERR_INVALID, "f_scale must be positive");
+  if (int rc = check_eval(h, loss, f_scale, intr ? 0 : CK_BAL_BITS)) return rc;
   if (precond < 0 || precond > 2) return fail(BA_ERR_INVALID, "precond must be 0 (Jacobi), 1 (Schur-Jacobi) or 2 (Schur-Jacobi kept)");
   if (jacobian_precision != 0 && jacobian_precision != 1)
     return fail(BA_ERR_INVALID, "jacobian_precision must be 0 (f64) or 1 (f32 blocks, f64 accumulation)");
   if (set_device(h)) return BA_ERR_HIP;
-  if (intr) { if (int rc = bal_enter(h, intr)) { h->model = 0; return rc; } }
   const bool jac_f32_was = h->jac_f32;
-  auto body = [&]() -> int {
+  const int rc = with_model(h, intr, [&]() -> int {
     const ba_loss ls = (ba_loss)loss;
     const bool robust = ls != BA_LOSS_LINEAR;
     const int nb = nb_of(h), nh = nh_of(h);
@@ -2414,10 +2437,8 @@ extern "C" int ba_schur_system(ba_handle* h, const double* intr, int32_t loss, d
       HIPCHECK(hipMemcpyAsync(h->vin.p, v + i * n, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
       {
         Scope sc(h, BA_K_MISC);
-#define CALL_T(CM) BA_LAUNCH(k_vtil<CM>, dim3((h->Nc + 63) / 64), dim3(64), 0, h->stream, h->vin.p, h->cs[h->cur].p, h->Nc, h->fixed, \
-                             h->camA[h->cur].p, cam_held_ptr(h))
-        BA_BY_MODEL(CALL_T);
-#undef CALL_T
+        BA_BY_MODEL(h->model, BA_LAUNCH(k_vtil<CM>, dim3((h->Nc + 63) / 64), dim3(64), 0, h->stream, h->vin.p, h->cs[h->cur].p, h->Nc, h->fixed,
+                                        h->camA[h->cur].p, cam_held_ptr(h)));
         // a not-converged PCG state, so that the probe of iteration 0 finds "go on" (tol2 < 0), and the same verdict word
         // written here for the camera pass (no point pass on an empty landmark shard)
         BA_LAUNCH(k_pcg_reset, dim3(1), dim3(64), 0, h->stream, h->st.p, h->partV.p, nbv(h));
@@ -2429,24 +2450,15 @@ extern "C" int ba_schur_system(ba_handle* h, const double* intr, int32_t loss, d
       if (int rc = exchange_schur(h)) return rc;
       {
         Scope sc(h, BA_K_MISC);
-#define CALL_T(CM) BA_LAUNCH(k_schur_combine<CM>, dim3((h->Nc + 63) / 64), dim3(64), 0, h->stream, h->Hccd.p, h->vin.p, p6_ptr(h), \
-                             nparts_of(h), h->cs[h->cur].p, h->Nc, h->fixed, h->z.p, cam_held_ptr(h))
-        BA_BY_MODEL(CALL_T);
-#undef CALL_T
+        BA_BY_MODEL(h->model, BA_LAUNCH(k_schur_combine<CM>, dim3((h->Nc + 63) / 64), dim3(64), 0, h->stream, h->Hccd.p, h->vin.p, p6_ptr(h),
+                                        nparts_of(h), h->cs[h->cur].p, h->Nc, h->fixed, h->z.p, cam_held_ptr(h)));
       }
       HIPCHECK(hipMemcpyAsync(sv + i * n, h->z.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     }
     BA_SYNC(h);
     return BA_OK;
-  };
-  const int rc = body();
+  });
   h->jac_f32 = jac_f32_was;
-  if (!intr) return rc;
-  const std::string msg = g_err;
-  if (rc != BA_OK) { (void)hipStreamSynchronize(h->stream); h->launch_err = hipSuccess; }
-  bal_leave(h);
-  (void)hipStreamSynchronize(h->stream);
-  g_err = msg;
   return rc;
 }
 
@@ -2636,67 +2648,6 @@ static int small_solve(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   return BA_OK;
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// BAL 9-parameter camera [rvec | t | f k1 k2] (BASELINE config 5 is stated on a BAL problem; the
-// reference's only camera is cv2.projectPoints(..., distCoeffs=None), src/bundle_adjuster.py:67).  Cameras (rvec, t) and
-// points are the handle's (ba_set_params / ba_get_params); the per-camera (f, k1, k2) travel with the call.  K4 of
-// ba_set_problem is not used.  The entry points switch the handle to the BalCam instantiation of every kernel
-// (ba_models.hpp) for the duration of the call: same LM / Schur / PCG loop, same device-side verdicts and speculation,
-// same multi-rank exchange, 9x9 camera blocks.
-static int bal_enter(ba_handle* h, const double* intr) {
-  HIPCHECK(hipMemcpyAsync(h->intr[h->cur].p, intr, 3 * (size_t)h->Nc * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  h->model = 1;
-  h->linearized = false;
-  BA_LAUNCH(k_cam_prepare<BalCam>, dim3((h->Nc + 63) / 64), dim3(64), 0, h->stream, h->cams[h->cur].p, (const double*)h->intr[h->cur].p,
-            h->cs[h->cur].p, h->camA[h->cur].p, h->Nc);
-  return BA_OK;
-}
-// back to the pinhole layout of the camera table (what every other entry point reads), at the current parameters
-static void bal_leave(ba_handle* h) {
-  h->model = 0;
-  h->linearized = false;                      // the linearisation buffers hold 9-parameter blocks
-  BA_LAUNCH(k_cam_prepare<Pinhole>, dim3((h->Nc + 63) / 64), dim3(64), 0, h->stream, h->cams[h->cur].p, (const double*)h->intr[h->cur].p,
-            h->cs[h->cur].p, h->camA[h->cur].p, h->Nc);
-}
-
-extern "C" int ba_linearize_bal(ba_handle* h, const double* intr, int32_t loss, double f_scale, double* Hcc, double* bc,
-                                double* Hpp, double* bp) {
-  if (!h || !intr) return fail(BA_ERR_INVALID, "null argument");
-  if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
-  if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
-  if (!(f_scale > 0)) return fail(BA_ERR_INVALID, "f_scale must be positive");
-  if (set_device(h)) return BA_ERR_HIP;
-  if (int rc = bal_enter(h, intr)) return rc;
-  auto body = [&]() -> int {
-    launch_lin_cam(h, h->cur, h->lb, (ba_loss)loss, f_scale);
-    if (int rc = exchange_partL(h, h->lb)) return rc;
-    launch_lin_finalize(h);
-    launch_lin_pt(h, h->cur, h->pb, (ba_loss)loss, f_scale, 1.0);
-    if (Hcc) HIPCHECK(hipMemcpyAsync(Hcc, h->HccBc.p, BalCam::NH * (size_t)h->Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (bc) HIPCHECK(hipMemcpyAsync(bc, bc_ptr(h), BalCam::NB * (size_t)h->Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if ((Hpp || bp) && h->Np) {
-      HIPCHECK(h->rbuf.alloc(6 * (size_t)h->Np));
-      if (Hpp) {
-        BA_LAUNCH(k_unpermute_rows, dim3((h->Np + 255) / 256), dim3(256), 0, h->stream, h->Hpp[h->pb].p, h->slot.p, h->Np, 6, h->rbuf.p);
-        HIPCHECK(hipMemcpyAsync(Hpp, h->rbuf.p, 6 * (size_t)h->Np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      }
-      if (bp) {
-        BA_LAUNCH(k_unpermute_rows, dim3((h->Np + 255) / 256), dim3(256), 0, h->stream, h->bp[h->pb].p, h->slot.p, h->Np, 3, h->stage.p);
-        HIPCHECK(hipMemcpyAsync(bp, h->stage.p, 3 * (size_t)h->Np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      }
-    }
-    BA_SYNC(h);
-    return BA_OK;
-  };
-  const int rc = body();
-  const std::string msg = g_err;
-  if (rc != BA_OK) { (void)hipStreamSynchronize(h->stream); h->launch_err = hipSuccess; }
-  bal_leave(h);
-  (void)hipStreamSynchronize(h->stream);
-  g_err = msg;
-  return rc;
-}
-
 // ------------------------------------------------------------------------------------------------- covariances
 // Marginal covariances at the current parameters (csrc/ba_cov.hpp): the camera half and the point half of a linearisation
 // (Hcc, Hpp; the damped point inverses it also writes are not used), S assembled densely from them and the per-observation
@@ -2812,28 +2763,20 @@ static int cov_impl(ba_handle* h, ba_loss loss, double f_scale, double rcond, do
 extern "C" int ba_covariance(ba_handle* h, const double* intr, int32_t loss, double f_scale, double rcond, double* cam_cov,
                              double* pt_cov, double* cam_full) {
   if (!h) return fail(BA_ERR_INVALID, "null handle");
-  if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
+  if (int rc = check_eval(h, loss, f_scale, intr ? 0 : CK_BAL_BITS)) return rc;
   if (h->multi) return fail(BA_ERR_INVALID, "ba_covariance: multi-rank jobs are not supported");
   if (h->n_shared)
     return fail(BA_ERR_INVALID, "ba_covariance: covariances of shared intrinsics are not offered (camera %d shares its f, k1, k2; "
                 "clear the groups with ba_set_shared_intrinsics(h, NULL))", h->h_grp_mem[0]);
-  if (!intr && (h->cam_held_or & ~0x3fu)) return fail(BA_ERR_INVALID, "camera mask bits 6-8 (f, k1, k2) need the BAL camera model");
-  if (!intr && h->prior_nb == 9) return fail(BA_ERR_INVALID, "%s", kPriorNeedsBal);
-  if (!loss_valid(loss)) return fail(BA_ERR_INVALID, "unknown loss %d", loss);
-  if (!(f_scale > 0)) return fail(BA_ERR_INVALID, "f_scale must be positive");
-  const long long n = (long long)(intr ? BalCam::NB : Pinhole::NB) * h->Nc;
+  const long long n = (long long)kModel[intr ? 1 : 0].nb * h->Nc;
   if (n > COV_MAX_N) return fail(BA_ERR_INVALID, "ba_covariance: %lld camera parameters, more than the %d the dense inverse takes", n, COV_MAX_N);
   if (!(rcond > 0)) rcond = COV_RCOND_DEFAULT;
   if (set_device(h)) return BA_ERR_HIP;
-  if (intr) { if (int rc = bal_enter(h, intr)) { h->model = 0; return rc; } }
-  const int rc = intr ? cov_impl<BalCam>(h, (ba_loss)loss, f_scale, rcond, cam_cov, pt_cov, cam_full)
-                      : cov_impl<Pinhole>(h, (ba_loss)loss, f_scale, rcond, cam_cov, pt_cov, cam_full);
-  const std::string msg = g_err;
-  if (rc != BA_OK) { (void)hipStreamSynchronize(h->stream); h->launch_err = hipSuccess; }
-  if (intr) bal_leave(h);
-  (void)hipStreamSynchronize(h->stream);
-  g_err = msg;
-  return rc;
+  return with_model(h, intr, [&]() -> int {
+    int rc = BA_OK;
+    BA_BY_MODEL(h->model, rc = cov_impl<CM>(h, (ba_loss)loss, f_scale, rcond, cam_cov, pt_cov, cam_full));
+    return rc;
+  });
 }
 
 static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum);
@@ -2856,18 +2799,14 @@ extern "C" int ba_solve_bal(ba_handle* h, double* intr, const ba_options* opts, 
         return fail(BA_ERR_INVALID, "ba_solve_bal: camera %d holds other intrinsics (mask bits 6-8: 0x%x) than camera %d (0x%x), whose intrinsics it shares", c, hc, lead, hl);
     }
   }
-  if (int rc = bal_enter(h, intr)) { h->model = 0; return rc; }
-  int rc = ba_solve(h, opts, sum);            // (ba_solve drains the stream and clears the per-solve modes on failure)
-  const std::string msg = g_err;
-  // the adjusted (f, k1, k2) of the accepted parameter set -- also after a failed solve: the last accepted step stands
-  if (hipMemcpyAsync(intr, h->intr[h->cur].p, 3 * (size_t)h->Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess && rc == BA_OK)
-    rc = fail(BA_ERR_HIP, "copying the intrinsics back failed");
-  // a failure in the middle of the loop may have left the camera state of the current set behind its parameters
-  // (k_cam_update writes both for the TRIAL set; the current set is always complete) -- rebuilt here either way
-  bal_leave(h);
-  if (hipStreamSynchronize(h->stream) != hipSuccess && rc == BA_OK) rc = fail(BA_ERR_HIP, "stream synchronise failed");
-  if (rc != BA_OK && !msg.empty()) g_err = msg;
-  return rc;
+  return with_model(h, intr, [&]() -> int {
+    int rc = ba_solve(h, opts, sum);          // (ba_solve drains the stream and clears the per-solve modes on failure)
+    // the adjusted (f, k1, k2) of the accepted parameter set -- also after a failed solve: the last accepted step stands
+    // (k_cam_update writes parameters and camera state for the TRIAL set; the current set is always complete)
+    if (hipMemcpyAsync(intr, h->intr[h->cur].p, 3 * (size_t)h->Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess && rc == BA_OK)
+      rc = fail(BA_ERR_HIP, "copying the intrinsics back failed");
+    return rc;
+  });
 }
 
 static int64_t held_params(const ba_handle* h, int nb) {       // held scalar parameters, the fixed camera's whole block included
@@ -2882,7 +2821,7 @@ static int64_t held_params(const ba_handle* h, int nb) {       // held scalar pa
   return n;
 }
 static bool all_held(const ba_handle* h) {
-  const int nb = h->model ? BalCam::NB : Pinhole::NB;
+  const int nb = nb_of(h);
   return held_params(h, nb) == (int64_t)nb * h->Nc + 3 * (int64_t)h->Np;
 }
 static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
@@ -3073,7 +3012,7 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     // "device-side all-reduce"); every workgroup's record has to fit its slot of the receive buffers
     // (shared intrinsics: the group fold runs on the all-reduced product, between the exchange and k_pcg_step -- base transport)
     const bool use_ipc = h->ipc && h->multi && !h->shared_on && nbv(h) <= IPC_MAX_BLOCKS &&
-                         (size_t)nbv(h) * (2 + (size_t)nb_of(h) * (h->model ? BalCam::VC : Pinhole::VC)) <= IpcComm::STRIDE;
+                         (size_t)nbv(h) * (2 + (size_t)nb_of(h) * kModel[h->model].vc) <= IpcComm::STRIDE;
     auto launch_rest = [&](int kk) -> int {
       launch_cam_schur(h, robust, false, true, kk, tol2, opts->pcg_min_iters);
       // the Schur product of the reduced camera system, summed over the ranks: device-side stores into every peer's receive
@@ -3100,8 +3039,7 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
                   cam_held_ptr(h), cam_gl_ptr(h), (const double*)(h->shared_on ? h->grp_w.p : nullptr),                                 \
                   (const int*)(h->shared_on ? h->grp_chunk.p : nullptr)
       if (h->shared_on) BA_LAUNCH((k_pcg_step<BalCam, true>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS);
-      else if (h->model) BA_LAUNCH((k_pcg_step<BalCam>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS);
-      else          BA_LAUNCH((k_pcg_step<Pinhole>), dim3(h->nblkV), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS);
+      else BA_BY_MODEL(h->model, BA_LAUNCH((k_pcg_step<CM>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS));
 #undef STEP_ARGS
       return BA_OK;
     };
@@ -3147,8 +3085,7 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
       cu.fuse = 0;
       if (!ride) {
         Scope sc(h, BA_K_MISC);
-        if (h->model) BA_LAUNCH(k_cam_update<BalCam>, dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, cu);
-        else          BA_LAUNCH(k_cam_update<Pinhole>, dim3(h->nblkV), dim3(VEC_BLOCK), 0, h->stream, cu);
+        BA_BY_MODEL(h->model, BA_LAUNCH(k_cam_update<CM>, dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, cu));
         cu.n_blocks = 0;              // (the arguments still travel: the launch clears the riding verdict's damping word)
       }
       launch_pt_schur(h, robust, 1, 0, 0.0, 0, 0, nullptr, &cu);
@@ -3388,11 +3325,11 @@ static void launch_tracks(ba_handle* h) {
   BA_LAUNCH(k_track_centres, dim3((h->Nc + 255) / 256), dim3(256), 0, h->stream, a.cs, h->Nc, h->trk_ctr.p);
   if (h->Np == 0) return;
   const int tpb = TRK_THREADS / TRK_G;
-  BA_LAUNCH_CM(h->trk_bal, k_tracks_short, dim3((h->Np + tpb - 1) / tpb), dim3(TRK_THREADS), 0, h->stream, a);
+  BA_BY_MODEL(h->trk_bal, BA_LAUNCH(k_tracks_short<CM>, dim3((h->Np + tpb - 1) / tpb), dim3(TRK_THREADS), 0, h->stream, a));
   if (h->n_long > 0) {
     TrackArgs b = a;
     b.list = h->long_pts.p; b.n_items = h->n_long;
-    BA_LAUNCH_CM(h->trk_bal, k_tracks_long, dim3(h->n_long), dim3(64), 0, h->stream, b);
+    BA_BY_MODEL(h->trk_bal, BA_LAUNCH(k_tracks_long<CM>, dim3(h->n_long), dim3(64), 0, h->stream, b));
   }
 }
 extern "C" int ba_default_track_options(ba_track_options* o) {
@@ -3459,7 +3396,7 @@ static void launch_resect(ba_handle* h) {
   ResectArgs& a = h->rs.args;
   a.t.cs = h->cs[h->cur].p; a.cams = h->cams[h->cur].p; a.ptab = h->ptab[h->cur].p;
   if (h->Nc == 0) return;
-  BA_LAUNCH_CM(h->rs.bal, k_resect, dim3(h->Nc), dim3(RS_THREADS), 0, h->stream, a);
+  BA_BY_MODEL(h->rs.bal, BA_LAUNCH(k_resect<CM>, dim3(h->Nc), dim3(RS_THREADS), 0, h->stream, a));
 }
 // What ba_resect and ba_resect_ransac (`who` in the messages) do alike before their launches: the checks of the options they
 // share -- o is ba_resect's struct for both; ba_resect_ransac fills one from its own, init = CURRENT --, the uploads of intr,
@@ -3562,9 +3499,9 @@ static int launch_ransac(ba_handle* h) {
   if (h->Nc == 0) return BA_OK;
   if (a.inl && h->Nobs > 0) HIPCHECK(hipMemsetAsync(a.inl, 0, (size_t)h->Nobs, h->stream));
   const dim3 gc(h->Nc), gs(h->Nc, a.n_blk), b(RN_THREADS);
-  BA_LAUNCH_CM(h->rn.bal, k_ransac_prep, gc, b, 0, h->stream, a);
-  BA_LAUNCH_CM(h->rn.bal, k_ransac_score, gs, b, 0, h->stream, a);
-  BA_LAUNCH_CM(h->rn.bal, k_ransac_lo, gc, b, 0, h->stream, a);
+  BA_BY_MODEL(h->rn.bal, BA_LAUNCH(k_ransac_prep<CM>, gc, b, 0, h->stream, a));
+  BA_BY_MODEL(h->rn.bal, BA_LAUNCH(k_ransac_score<CM>, gs, b, 0, h->stream, a));
+  BA_BY_MODEL(h->rn.bal, BA_LAUNCH(k_ransac_lo<CM>, gc, b, 0, h->stream, a));
   return BA_OK;
 }
 extern "C" int ba_default_ransac_options(ba_ransac_options* o) {

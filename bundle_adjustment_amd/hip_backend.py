@@ -391,8 +391,7 @@ class Solver:
 
     def prior_cost(self, intr=None):
         """ba_prior_cost: (camera sum, point sum) of the prior terms at the current parameters; intr (Nc, 3) for nb = 9 priors."""
-        if intr is not None:
-            intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
+        intr = self._intr(intr)
         cc, pc = C.c_double(0), C.c_double(0)
         _check(self._lib.ba_prior_cost(self._h, _dp(intr), C.byref(cc), C.byref(pc)))
         return cc.value, pc.value
@@ -439,6 +438,10 @@ class Solver:
         _check(self._lib.ba_get_rotations(self._h, _dp(R)))
         return R
 
+    def _intr(self, intr):
+        """The (Nc, 3) float64 (f, k1, k2) array a C call reads, or None (pinhole) as it is."""
+        return None if intr is None else np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
+
     # -- kernels behind the parity entry points ----------------------------------------
     def residuals(self, loss="linear", f_scale=1.0, want_vector=True):
         r = np.empty((self.n_obs, 2)) if want_vector else None
@@ -461,10 +464,8 @@ class Solver:
         triangles, sv shaped like v or None)."""
         nb = 6 if intr is None else 9
         nh = nb * (nb + 1) // 2
-        ip = None
-        if intr is not None:
-            intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
-            ip = _dp(intr)
+        intr = self._intr(intr)
+        ip = _dp(intr)
         vv, shape = None, None
         if v is not None:
             shape = np.shape(v)
@@ -485,10 +486,8 @@ class Solver:
         (BA_ERR_NUMERIC).  Priors (set_priors) are part of the system: Sigma = (H + L)^-1 over the free parameters."""
         nb = 6 if intr is None else 9
         nh = nb * (nb + 1) // 2
-        ip = None
-        if intr is not None:
-            intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
-            ip = _dp(intr)
+        intr = self._intr(intr)
+        ip = _dp(intr)
         cam = np.empty((self.n_cams, nh))
         pts = np.empty((self.n_pts, 6))
         fm = np.empty((nb * self.n_cams, nb * self.n_cams)) if full else None
@@ -526,19 +525,11 @@ class Solver:
 
     def residuals_bal(self, bal, loss="linear", f_scale=1.0, want_vector=True):
         """BAL 9-parameter camera residuals (bal.BALProblem) on the GPU: uploads the problem, returns (r, sse, cost)."""
-        from .problem import BAProblem
-        self.set_problem(BAProblem(np.ascontiguousarray(bal.cams[:, :6]), bal.pts, bal.cam_idx, bal.pt_idx, bal.uv,
-                                   np.array([1.0, 1.0, 0.0, 0.0]), -1))
-        intr = np.ascontiguousarray(bal.cams[:, 6:9], dtype=np.float64)
-        r = np.empty((self.n_obs, 2)) if want_vector else None
-        sse, cost = C.c_double(0), C.c_double(0)
-        _check(self._lib.ba_residuals_bal(self._h, _dp(intr), loss_code(loss), float(f_scale),
-                                          _dp(r), C.byref(sse), C.byref(cost)))
-        return r, sse.value, cost.value
+        return self._residuals_bal_resident(self._set_bal(bal), loss, f_scale, want_vector)
 
     def _residuals_bal_resident(self, intr, loss="linear", f_scale=1.0, want_vector=True):
         """ba_residuals_bal on the problem the handle already holds (set_problem_bal) at its current parameters: (r, sse, cost)."""
-        intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
+        intr = self._intr(intr)
         r = np.empty((self.n_obs, 2)) if want_vector else None
         sse, cost = C.c_double(0), C.c_double(0)
         _check(self._lib.ba_residuals_bal(self._h, _dp(intr), loss_code(loss), float(f_scale), _dp(r), C.byref(sse), C.byref(cost)))
@@ -568,7 +559,7 @@ class Solver:
     def solve_bal_resident(self, intr, **kw):
         """ba_solve_bal on the problem the handle already holds: intr (Nc,3) = (f, k1, k2) per camera at the start, adjusted
         in place.  Returns the summary dict."""
-        intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
+        intr = self._intr(intr)
         o = self._options(kw)
         s = BASummary()
         _check(self._lib.ba_solve_bal(self._h, _dp(intr), C.byref(o), C.byref(s)))
@@ -633,10 +624,8 @@ class Solver:
         opts: loss, refine_iters, f_scale, min_angle_deg, max_reproj_px, min_depth, write_points.  Returns dict(xyz (Np, 3),
         status (Np,) uint8 (TRACK_STATUS), angle_deg, rms_px, max_px (Np,)), the caller's point order; want=False asks for no
         output arrays (timing, or write_points alone) and returns None."""
-        ip = None
-        if intr is not None:
-            intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
-            ip = _dp(intr)
+        intr = self._intr(intr)
+        ip = _dp(intr)
         o = self.track_options(**opts)
         if not want:
             _check(self._lib.ba_triangulate_tracks(self._h, ip, C.byref(o), None, None, None, None, None))
@@ -667,8 +656,7 @@ class Solver:
     def _resect_head(self, intr, cams, known_points):
         """What resect and resect_ransac pass alike: the pointers of intr, the camera selection and the known-point mask (a
         pointer keeps its array alive), the output dict, and the pointers of its arrays in the order of the C arguments."""
-        if intr is not None:
-            intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(self.n_cams, 3)
+        intr = self._intr(intr)
         selp, knownp = self._mask(cams, self.n_cams)[1], self._mask(known_points, self.n_pts)[1]
         n = self.n_cams
         out = dict(poses=np.empty((n, 6)), status=np.empty(n, dtype=np.uint8), n_inliers=np.empty(n, dtype=np.int32),

@@ -111,3 +111,62 @@ def test_bal_path_reports_its_failures_like_ba_solve():
             s.solve_bal(BALProblem(p.cams, p.pts, p.cam_idx, p.pt_idx, uv))
         again, _, _ = s.solve_bal(p, max_iters=3)                  # the handle survived
         assert again["final_cost"] == out["final_cost"]
+
+
+def test_every_way_out_of_a_bal_call_leaves_the_pinhole_state():
+    """The entry points that take `intr` switch the handle to the BAL camera for the call.  Whichever way such a call
+    ends -- done, refused, failed in the middle -- the pinhole calls behind it must see the handle as it was: residuals
+    and linearisation bit-equal to those recorded before (the same kernels on the same inputs, order-fixed sums).
+    6 cameras / 60 points / 4 observations per point; the BAL twin reads the same resident data with its own f, k1, k2
+    per camera.  A solve with max_iters = 0 evaluates the cost and leaves the parameters alone (checked)."""
+    import ctypes as C
+    p = make_problem(6, 60, 4, seed=11)
+    rng = np.random.default_rng(12)
+    intr = np.stack([p.K4[0] * (1.0 + 0.02 * rng.normal(size=6)), -0.05 + 0.02 * rng.normal(size=6), 0.01 * rng.normal(size=6)], axis=1)
+    held = np.zeros(6, np.uint16)
+    held[1] = 1 << 3                     # with fixed_cam 0: the gauge ba_covariance needs, as in test_gpu_covariance.py
+
+    def upload(s, prob):
+        s.set_problem(prob)
+        s.set_held(cams=held)
+
+    def pinhole(s):
+        r, sse, cost = s.residuals("huber")
+        return (r, np.array([sse, cost])) + tuple(s.linearize("huber"))
+
+    with hip_backend.Solver(0) as s:
+        upload(s, p)
+        ref = pinhole(s)
+        assert all(np.isfinite(a).all() for a in ref)
+
+        def check(what):
+            for name, a, b in zip(("r", "sse, cost", "Hcc", "bc", "Hpp", "bp"), ref, pinhole(s)):
+                assert a.tobytes() == b.tobytes(), f"{name} differs after {what}"
+
+        out = [np.empty((6, 45)), np.empty((6, 9)), np.empty((60, 6)), np.empty((60, 3))]
+        assert s._lib.ba_linearize_bal(s._h, hip_backend._dp(intr), hip_backend.loss_code("huber"), 1.0, *map(hip_backend._dp, out)) == 0
+        assert all(np.isfinite(a).all() for a in out)
+        check("ba_linearize_bal")
+        sysm = s.schur_system(1e-3, rng.normal(size=(6, 9)), loss="huber", intr=intr)
+        assert np.isfinite(sysm["sv"]).all()
+        check("ba_schur_system with intr")
+        cov = s.covariance(loss="huber", intr=intr, full=True)
+        assert np.isfinite(cov["full"]).all()
+        check("ba_covariance with intr")
+        moved = intr.copy()
+        sol = s.solve_bal_resident(moved, loss="huber", max_iters=0)
+        assert sol["iterations"] == 0 and sol["final_cost"] == sol["initial_cost"] and np.array_equal(moved, intr)
+        cams, pts = s.get_params()
+        assert np.array_equal(cams, p.cams) and np.array_equal(pts, p.pts)
+        check("ba_solve_bal with max_iters = 0")
+        with pytest.raises(hip_backend.BAHipError, match="unknown loss"):
+            s.solve_bal_resident(intr.copy(), loss=7)
+        check("a refused ba_solve_bal")
+        uv = p.uv.copy()
+        uv[5, 0] = np.nan
+        upload(s, type(p)(p.cams, p.pts, p.cam_idx, p.pt_idx, uv, p.K4, 0))
+        with pytest.raises(hip_backend.BAHipError, match="non-finite cost at the initial parameters") as ei:
+            s.solve_bal_resident(intr.copy(), loss="huber", max_iters=3)
+        assert "error -4" in str(ei.value)                        # BA_ERR_NUMERIC
+        upload(s, p)
+        check("ba_solve_bal failing on a NaN pixel")
