@@ -3779,9 +3779,9 @@ extern "C" int ba_debug_mode(ba_handle* h, int mode) {
   HIPCHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_mode), &mode, sizeof(int)));
   return BA_OK;
 }
-// copy the stamps of the last launch of kind 0 (PCG point pass), 1 (PCG camera pass), 2 (k_pcg_step)
+// copy the stamps of the last launch of kind 0 (PCG point pass), 1 (PCG camera pass), 2 (k_pcg_step), 3 (k_pcg_setup)
 extern "C" int ba_debug_stamps(ba_handle* h, int kind, unsigned long long* out, int n_blocks) {
-  if (!h || !out || kind < 0 || kind > 2 || n_blocks < 1 || n_blocks > STAMP_BLOCKS) return fail(BA_ERR_INVALID, "bad argument");
+  if (!h || !out || kind < 0 || kind > 3 || n_blocks < 1 || n_blocks > STAMP_BLOCKS) return fail(BA_ERR_INVALID, "bad argument");
   if (set_device(h)) return BA_ERR_HIP;
   BA_SYNC(h);
   HIPCHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), (size_t)n_blocks * 8 * sizeof(unsigned long long),

@@ -39,7 +39,7 @@ namespace ba {
 // (shader clock) at the stages marked in the kernels.  The product build compiles none of it.
 #ifdef BA_STAMPS
 constexpr int STAMP_BLOCKS = 8192;
-__device__ unsigned long long g_stamps[3][STAMP_BLOCKS * 8];
+__device__ unsigned long long g_stamps[4][STAMP_BLOCKS * 8];
 __device__ int g_dbg_mode;      // diagnostic variants of the camera pass's gather (tools/stamp_timeline.py): 0 = product path
 #define BA_STAMP(kind, slot)                                                                              \
   do {                                                                                                    \
@@ -1370,13 +1370,30 @@ pt_schur_body(const double* __restrict__ camA, double* __restrict__ ptab, const 
     }
     if (!table_ready) {
       if (MODE == 0 && cu.fuse) {
-        fill_cam_table_wait();                           // (its barrier also makes s_fin visible)
-        if (s_fin) {
+        // The verdict is known long before the table has landed (wave 0's probe: ~1 us, the copy: ~4 us after entry).  One
+        // barrier that waits for LDS only -- not for the copy, not for the index loads in flight -- hands s_fin to every
+        // wave, and the launch that finished fetches the first four words per thread of its window's vx slice while the
+        // copy is still under way, as MODE 1 does; they go into the rows once the copy has landed.
+        constexpr int NBm = CM::NB;
+        const int nw = win.y * NBm;
+        const double* __restrict__ src = cu.vx + NBm * (size_t)win.x;
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        const bool fin = s_fin != 0;
+        // (the thread's index as a value born here: the addresses below are then computed here, where they are used once,
+        // and not ahead of the slot loop, where they were kept live across the first index loads and spilled)
+        int tid = (int)threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        double v0[4] = {0.0, 0.0, 0.0, 0.0};
+        if (fin) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) { const int e = tid + q * PT_THREADS; if (e < nw) v0[q] = src[e]; }
+        }
+        fill_cam_table_wait();
+        if (fin) {
           back = true;
-          constexpr int NBm = CM::NB;
-          const int nw = win.y * NBm;
-          const double* __restrict__ src = cu.vx + NBm * (size_t)win.x;
-          for (int e0 = threadIdx.x; e0 < nw; e0 += 4 * PT_THREADS) {      // four loads in flight per thread
+#pragma unroll
+          for (int q = 0; q < 4; ++q) { const int e = tid + q * PT_THREADS; if (e < nw) tab[CM::TA * (e / NBm) + CM::VOFF + e % NBm] = v0[q]; }
+          for (int e0 = tid + 4 * PT_THREADS; e0 < nw; e0 += 4 * PT_THREADS) {      // four loads in flight per thread
             double v[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) { const int e = e0 + q * PT_THREADS; v[q] = e < nw ? src[e] : 0.0; }
@@ -1633,6 +1650,28 @@ __device__ inline void slice_write_back(double* __restrict__ dst, const double* 
     else dst[2 * i] = lds[2 * i];
   }
 }
+// The same in ONE round: every LDS read is issued before the first store (slice_write_back's loop waits for each read in
+// turn: one LDS round trip per 64 double2, 13 of them at the end of k_pcg_setup)
+template <int NL>
+__device__ inline void slice_load_lds(const double* __restrict__ lds, int cap, double2 (&v)[NL]) {   // cap: doubles reserved (even)
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int u = 0; u < NL; ++u) {
+    const int i = u * 64 + lane;
+    v[u] = make_double2(0.0, 0.0);
+    if (2 * i < cap) v[u] = ((const double2*)lds)[i];
+  }
+}
+template <int NL>
+__device__ inline void slice_store(double* __restrict__ dst, int len, const double2 (&v)[NL]) {     // len doubles to dst (16-byte aligned)
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int u = 0; u < NL; ++u) {
+    const int i = u * 64 + lane;
+    if (2 * i + 1 < len) ((double2*)dst)[i] = v[u];
+    else if (2 * i < len) dst[2 * i] = v[u].x;
+  }
+}
 static_assert(BalCam::VC == 16 || BalCam::VC == 8 || BalCam::VC == 4, "camera-vector workgroups: 4, 8 or 16 cameras per wave");
 constexpr int slice_chunks(int doubles) { return (doubles + 127) / 128; }      // double2 per lane that cover a slice
 
@@ -1666,6 +1705,7 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
   const int nc = min(VC, n_cams - c0);
   const int c = vec_camera<VC>(n_cams);
   const int lane = threadIdx.x;
+  BA_STAMP(3, 0); BA_STAMP(3, 1);
   // ---- cooperative loads: every word of the workgroup's slices, lane-strided and coalesced; the partition
   // sums run k = 0, 1, ... in every element (the same fixed order as a thread-per-camera loop)
   {
@@ -1689,24 +1729,50 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
 #pragma unroll
     for (int j = 0; j < NW; ++j) sw[j] = 0.0;
     const int la = NL * nc, le = NH * nc, lw = NB * nc;
-#pragma unroll 2
+    // ONE round of loads: every partition's words are requested before the first add.  The kernel is a single wave
+    // lifetime of cold loads (the partitions were written from other XCDs one launch earlier), so each round of loads
+    // that is waited for is a trip to memory on its critical path; a wave per workgroup has the registers for all
+    // NPART * (NA + NE + NW) words in flight.  The loads carry no predicate -- a predicated load sits in a branch of its
+    // own, and the compiler waits for it there: a lane past the end of the slice reads the slice's last word, a
+    // partition past nparts reads partition 0 (both in bounds, both discarded), and the predicate selects afterwards.
+    double ta[NPART][NA], te[NPART][NE], tw[NPART][NW];
+#pragma unroll
     for (int k = 0; k < NPART; ++k) {
-      double ta[NA], te[NE], tw[NW];
-      const double* pa = partL + ((size_t)k * n_cams + c0) * NL;
-      const double* pe = partE + ((size_t)k * n_cams + c0) * NH;
-      const double* pw = part6 + ((size_t)k * n_cams + c0) * NB;
+      const size_t row0 = (size_t)(k < nparts ? k : 0) * n_cams + c0;
+      if (FINALIZE) {
+        const double* pa = partL + row0 * NL;
 #pragma unroll
-      for (int j = 0; j < NA; ++j) { const int i = j * 64 + lane; ta[j] = (FINALIZE && k < nparts && i < la) ? pa[i] : 0.0; }
+        for (int j = 0; j < NA; ++j) ta[k][j] = pa[min(j * 64 + lane, la - 1)];
+      }
+      const double* pw = part6 + row0 * NB;
 #pragma unroll
-      for (int j = 0; j < NE; ++j) { const int i = j * 64 + lane; te[j] = (use_schur_diag == 1 && k < nparts && i < le) ? pe[i] : 0.0; }
+      for (int j = 0; j < NW; ++j) tw[k][j] = pw[min(j * 64 + lane, lw - 1)];
+    }
+    if (use_schur_diag == 1) {
 #pragma unroll
-      for (int j = 0; j < NW; ++j) { const int i = j * 64 + lane; tw[j] = (k < nparts && i < lw) ? pw[i] : 0.0; }
+      for (int k = 0; k < NPART; ++k) {
+        const double* pe = partE + ((size_t)(k < nparts ? k : 0) * n_cams + c0) * NH;
 #pragma unroll
-      for (int j = 0; j < NA; ++j) sa[j] += ta[j];
+        for (int j = 0; j < NE; ++j) te[k][j] = pe[min(j * 64 + lane, le - 1)];
+      }
+    }
 #pragma unroll
-      for (int j = 0; j < NE; ++j) se[j] += te[j];
+    for (int k = 0; k < NPART; ++k) {
 #pragma unroll
-      for (int j = 0; j < NW; ++j) sw[j] += tw[j];
+      for (int j = 0; j < NA; ++j) ta[k][j] = (FINALIZE && k < nparts && j * 64 + lane < la) ? ta[k][j] : 0.0;
+#pragma unroll
+      for (int j = 0; j < NE; ++j) te[k][j] = (use_schur_diag == 1 && k < nparts && j * 64 + lane < le) ? te[k][j] : 0.0;
+#pragma unroll
+      for (int j = 0; j < NW; ++j) tw[k][j] = (k < nparts && j * 64 + lane < lw) ? tw[k][j] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < NPART; ++k) {                  // k = 0, 1, ... into a zero, in every element
+#pragma unroll
+      for (int j = 0; j < NA; ++j) sa[j] += ta[k][j];
+#pragma unroll
+      for (int j = 0; j < NE; ++j) se[j] += te[k][j];
+#pragma unroll
+      for (int j = 0; j < NW; ++j) sw[j] += tw[k][j];
     }
 #pragma unroll
     for (int j = 0; j < NA; ++j) { const int i = j * 64 + lane; if (i < NL * VC) l_a[i] = sa[j]; }
@@ -1720,6 +1786,7 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
       slice_store_lds(l_bc, NB * VC, vb);
     }
   }
+  BA_STAMP(3, 2);
   __syncthreads();
   double acc[2] = {0, 0};
   double gmc = 0.0;
@@ -1789,17 +1856,30 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
     }
     write_vtil<NB>(M, zz, vtil + CM::TA * (size_t)c + CM::VOFF);
   }
+  BA_STAMP(3, 3);
   __syncthreads();
   // ---- coalesced write-back
-  if (FINALIZE) {
-    slice_write_back(Hcc + NH * (size_t)c0, l_hcc, NH * nc);
-    slice_write_back(bc + NB * (size_t)c0, l_bc, NB * nc);
+  {
+    double2 wh[slice_chunks(NH * VC)], wb[slice_chunks(NB * VC)], wd[slice_chunks(NH * VC)], wm[slice_chunks(NH * VC)],
+        wg[slice_chunks(NB * VC)], wz[slice_chunks(NB * VC)];
+    if (FINALIZE) {
+      slice_load_lds(l_hcc, NH * VC, wh);
+      slice_load_lds(l_bc, NB * VC, wb);
+    }
+    slice_load_lds(l_hd, NH * VC, wd);
+    slice_load_lds(l_mi, NH * VC, wm);
+    slice_load_lds(l_g, NB * VC, wg);
+    slice_load_lds(l_z, NB * VC, wz);
+    if (FINALIZE) {
+      slice_store(Hcc + NH * (size_t)c0, NH * nc, wh);
+      slice_store(bc + NB * (size_t)c0, NB * nc, wb);
+    }
+    slice_store(Hccd + NH * (size_t)c0, NH * nc, wd);
+    if (use_schur_diag != 2) slice_store(Minv + NH * (size_t)c0, NH * nc, wm);
+    slice_store(gvec + NB * (size_t)c0, NB * nc, wg);
+    slice_store(r + NB * (size_t)c0, NB * nc, wg);
+    slice_store(z + NB * (size_t)c0, NB * nc, wz);
   }
-  slice_write_back(Hccd + NH * (size_t)c0, l_hd, NH * nc);
-  if (use_schur_diag != 2) slice_write_back(Minv + NH * (size_t)c0, l_mi, NH * nc);
-  slice_write_back(gvec + NB * (size_t)c0, l_g, NB * nc);
-  slice_write_back(r + NB * (size_t)c0, l_g, NB * nc);
-  slice_write_back(z + NB * (size_t)c0, l_z, NB * nc);
   for (int i = lane; i < NB * nc; i += 64) {
     x[NB * (size_t)c0 + i] = 0.0; p[NB * (size_t)c0 + i] = 0.0; s[NB * (size_t)c0 + i] = 0.0;
     vx[NB * (size_t)c0 + i] = 0.0;                       // the iterate in the point passes' form (see k_pcg_step)
@@ -1817,6 +1897,7 @@ k_pcg_setup(const double* __restrict__ partL, double* __restrict__ Hcc, double* 
       st[1] = s0;
     }
   }
+  BA_STAMP(3, 6); BA_STAMP(3, 7);
 }
 
 // ---- shared intrinsics (ba_set_shared_intrinsics) ----------------------------------------------------------------
@@ -2251,8 +2332,24 @@ __device__ void cam_update_body(const CamUpdateArgs& a, int blk, bool active, do
       for (int q = 0; q < NB - 6; ++q) a.intr_trial[3 * (size_t)c + q] = it3[q];
     }
     write_vtil<NB>(l_cs + CS * t + 12, d, a.vtil + CM::TA * (size_t)c + CM::VOFF);
+    // The five sums and the trial intrinsics are not touched by camera_state, which alone fills the 128 registers of a
+    // 1024-thread launch: kept live across it they were spilled to scratch, and a point-pass launch with riders had a
+    // private segment for their sake.  They wait in this camera's own dc | rpcg rows instead, which nobody reads again.
+    double* park = l_in + NB * t;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) park[q] = acc[q];
+    if (NB > 6) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) park[NB * VC + q] = it3[q];
+    }
     camera_state(l_ct + 6 * t, l_cst + CS * t);
+    if (NB > 6) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) it3[q] = park[NB * VC + q];
+    }
     CM::table_row(l_cst + CS * t, it3, a.camA_trial + CM::TA * (size_t)c);
+#pragma unroll
+    for (int q = 0; q < 5; ++q) acc[q] = park[q];
   }
   __syncthreads();
   if (w0) {

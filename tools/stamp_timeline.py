@@ -25,6 +25,7 @@ STAGES = {
     0: ("k_pt_schur<MODE 0>", ["entry", "verdict known", "table filled", "main loop done", "points stored (pre block sum)", "exit"], [1, 2, 3, 4, 5, 6]),
     1: ("k_cam_schur<PCG>", ["entry", "verdict known", "main loop done", "exit"], [1, 2, 3, 6]),
     2: ("k_pcg_step", ["entry", "verdict known", "update done", "exit"], [1, 2, 3, 6]),
+    3: ("k_pcg_setup", ["entry", "partitions folded", "block algebra done", "exit"], [1, 2, 3, 6]),
 }
 
 
@@ -49,7 +50,7 @@ def main():
     else:
         s.solve(**kw)
     vc = 8 if bal is not None else 16
-    nblk = {0: min(8192, (p.n_pts + 511) // 512 + 64), 1: min(8192, ((p.n_cams + 3) // 4) * 8), 2: (p.n_cams + vc - 1) // vc}
+    nblk = {0: min(8192, (p.n_pts + 511) // 512 + 64), 1: min(8192, ((p.n_cams + 3) // 4) * 8), 2: (p.n_cams + vc - 1) // vc, 3: (p.n_cams + vc - 1) // vc}
     for kind, (name, labels, slots) in STAGES.items():
         n = nblk[kind]
         buf = (C.c_uint64 * (n * 8))()
