@@ -2109,9 +2109,8 @@ static void launch_cam_schur_t(ba_handle* h, bool robust, bool diag, bool pcg, i
 #undef CS_PCG
 #undef CS_ARGS
 }
-static void launch_cam_schur(ba_handle* h, bool robust, bool diag, bool pcg, int k, double tol2, int min_iters) {
+static void launch_cam_schur(ba_handle* h, bool robust, bool diag, bool pcg, int k) {
   Scope sc(h, diag ? BA_K_PRECOND : BA_K_SCHUR_CAM);
-  (void)tol2; (void)min_iters;
   BA_BY_MODEL(h->model, launch_cam_schur_t<CM>(h, robust, diag, pcg, k));
 }
 // point pass with the camera vector in vtil; mode 0 = PCG iteration k, mode 1 = back substitution
@@ -2388,7 +2387,7 @@ extern "C" int ba_linearize_bal(ba_handle* h, const double* intr, int32_t loss, 
 static int damped_system(ba_handle* h, double lambda, bool schur_diag, bool invert = true, bool finalize = false, bool keep = false) {
   if (invert) launch_point_invert(h, lambda);
   const bool diag_pass = schur_diag && !keep;
-  launch_cam_schur(h, h->lin_loss != BA_LOSS_LINEAR, diag_pass, false, 0, 0.0, 0);
+  launch_cam_schur(h, h->lin_loss != BA_LOSS_LINEAR, diag_pass, false, 0);
   if (int rc = exchange_system(h, diag_pass)) return rc;
   launch_pcg_setup(h, lambda, schur_diag ? (keep ? 2 : 1) : 0, finalize);
   if (schur_diag) h->stats[keep ? BA_STAT_PRECOND_REUSES : BA_STAT_PRECOND_BUILDS]++;
@@ -2446,7 +2445,7 @@ extern "C" int ba_schur_system(ba_handle* h, const double* intr, int32_t loss, d
       }
       // flag_base 0: no probe word for the host; y = Hppinv W^T v into the point table, then the camera pass
       launch_pt_schur(h, robust, 0, 0, -1.0, 1 << 30, 0, nullptr, nullptr, h->jac_f32);
-      launch_cam_schur(h, robust, false, true, 0, 0.0, 0);
+      launch_cam_schur(h, robust, false, true, 0);
       if (int rc = exchange_schur(h)) return rc;
       {
         Scope sc(h, BA_K_MISC);
@@ -2508,27 +2507,49 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum);
 extern "C" int ba_solve(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   if (!h || !opts || !sum) return fail(BA_ERR_INVALID, "null argument");
   const int rc = solve_impl(h, opts, sum);
-  h->fold_prior_rows = 0;        // (ba_residuals* and the test hooks fold the reprojection rows only)
-  h->shared_on = false;          // (... and report per-camera quantities)
-  if (rc != BA_OK) {             // leave the handle usable: nothing queued, no per-solve mode left on
+  if (rc != BA_OK) {             // leave the handle usable: nothing queued, no launch remembered as refused
     const std::string msg = g_err;
     (void)hipStreamSynchronize(h->stream);
     h->launch_err = hipSuccess;
-    if (h->profile) flush_profile(h);
-    h->profile = false;
-    h->jac_f32 = false;
     h->linearized = false;
     g_err = msg;
   }
+  // the per-solve modes (solve_impl sets them in one place), off again behind every exit, successful or not
+  if (h->profile) flush_profile(h);
+  h->profile = false;
+  h->jac_f32 = false;
+  h->fold_prior_rows = 0;        // (ba_residuals* and the test hooks fold the reprojection rows only)
+  h->shared_on = false;          // (... and report per-camera quantities)
   return rc;
 }
 // Sliding-window-sized problems (ba_small.hpp): the whole LM loop in one kernel launch, dense Cholesky of the reduced
 // system instead of PCG.  Same options, summary and trace as the multi-kernel path.
+static bool small_mw_wanted(const ba_handle* h) {          // BA_SMALL_MW=0: always the one-workgroup kernel
+  const char* mw_env = getenv("BA_SMALL_MW");
+  return h->mw_ok && (!mw_env || atoi(mw_env) != 0);
+}
+// diagnostic stamps of LM iteration 2 (BA_SMALL_STAMPS), as either window kernel left them
+static int report_small_stamps(const long long* stamps, bool used_mw) {
+  long long st[16];
+  HIPCHECK(hipMemcpy(st, stamps, sizeof st, hipMemcpyDeviceToHost));
+  if (used_mw) {
+    static const char* names[] = {"C1 camera half (slices)", "P1 point half + V (8 lanes / landmark)", "G  [V;z][V;z]^T (MFMA, LDS) + message",
+                                  "exchange 1 (barrier + gather)", "S, g", "elimination + back substitution", "camera update + P2", "C3 trial cost (slices)", "exchange 2"};
+    for (int k = 0; k < 9; ++k) fprintf(stderr, "[k_small_mw, LM iteration 2, workgroup 0] %-40s %7.2f us\n", names[k], (st[k + 1] - st[k]) * 0.01);
+    fprintf(stderr, "[k_small_mw] elimination %.2f us, back substitution %.2f us\n", (st[13] - st[12]) * 0.01, (st[6] - st[13]) * 0.01);
+  } else {
+    static const char* names[] = {"C1 camera half", "P1 point half + V", "G  [V;z][V;z]^T (MFMA)", "S, g from the tiles", "Cholesky + solves (1 wave)",
+                                  "camera update", "P2 back substitution", "C3 trial cost"};
+    for (int k = 0; k < 8; ++k) fprintf(stderr, "[k_small_lm, LM iteration 2] %-28s %7.2f us\n", names[k], (st[k + 1] - st[k]) * 0.01);
+    fprintf(stderr, "[k_small_lm] wave 0: factor %.2f us, forward %.2f us, backward %.2f us\n", (st[13] - st[4]) * 0.01, (st[14] - st[13]) * 0.01, (st[5] - st[14]) * 0.01);
+    fprintf(stderr, "[k_small_lm] shader clock over the iteration: %.2f GHz\n", (double)(st[10] - st[9]) / ((st[8] - st[0]) * 10.0));
+  }
+  return BA_OK;
+}
 static bool small_applies(const ba_handle* h, const ba_options* opts) {
   // (the observation limit is the measured crossover of the ONE-workgroup kernel with the multi-kernel path; a window that
   // fits the multi-workgroup kernel -- five cameras, 2048 landmarks: at most 10 k observations -- is far below its own)
-  const char* mw_env = getenv("BA_SMALL_MW");
-  const bool mw = h->mw_ok && (!mw_env || atoi(mw_env) != 0);
+  const bool mw = small_mw_wanted(h);
   if (any_prior(h)) return false;      // priors: the multi-kernel path (the window kernels do not know them; ba_hip.h)
   return opts->small_solver == 0 && !h->multi && h->Nc <= SMALL_MAX_CAMS && h->Np > 0 && h->Nobs > 0 && (h->Nobs <= SMALL_MAX_OBS || mw) &&
          opts->max_iters >= 1;
@@ -2550,8 +2571,7 @@ static int small_solve(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   A.Hpp = h->Hpp[h->pb].p; A.bp = h->bp[h->pb].p; A.Lf = h->Hppinv[h->pb].p; A.y0 = h->y0[h->pb].p;
   A.Np_pad = (h->Np + 15) & ~15;
   A.Kp = 3 * A.Np_pad;
-  const char* mw_env = getenv("BA_SMALL_MW");           // BA_SMALL_MW=0: always the one-workgroup kernel
-  bool used_mw = h->mw_ok && (!mw_env || atoi(mw_env) != 0);
+  bool used_mw = small_mw_wanted(h);
   HIPCHECK(h->small_gS.alloc((size_t)SMALL_WAVES * SMALL_TILES * 256 + 16));        // + 16 words of diagnostic stamps
   A.gS = h->small_gS.p;
   A.n_cams = h->Nc; A.n_pts = h->Np; A.fixed_cam = h->fixed; A.loss = opts->loss;
@@ -2564,7 +2584,6 @@ static int small_solve(ba_handle* h, const ba_options* opts, ba_summary* sum) {
   A.cur_out = (int*)(h->d_small_host + off_cur);
   A.trace = (ba_iter_record*)(h->d_small_host + off_trace);
   A.host_flag = h->d_flags + 4;
-  h->profile = opts->profile != 0;
   A.stamps = getenv("BA_SMALL_STAMPS") ? (long long*)(h->small_gS.p + (size_t)SMALL_WAVES * SMALL_TILES * 256) : nullptr;   // device memory: a host store would stall the wave
   // one launch of either kernel and the wait for its result word: the kernel's last act is a system-scope release of the
   // sequence word -- summary, parameter set and trace are in host memory by then, and whatever the caller queues next on
@@ -2614,8 +2633,6 @@ static int small_solve(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     used_mw = false;
     if (int rc = run_once(false)) return rc;
   }
-  if (h->profile) flush_profile(h);
-  h->profile = false;
   if (sum->status == BA_ERR_HIP) return fail(BA_ERR_HIP, "the window solver reported a device-side failure");
   if (sum->status == BA_ERR_NUMERIC)
     return fail(BA_ERR_NUMERIC, sum->iterations == 0 ? "non-finite cost at the initial parameters"
@@ -2625,22 +2642,8 @@ static int small_solve(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     memcpy(h->trace.data(), h->h_small + off_trace, sizeof(ba_iter_record) * (size_t)sum->iterations);
   }
   memcpy(&h->cur, h->h_small + off_cur, sizeof(int));
-  if (A.stamps && used_mw) {
-    long long st[16];
-    HIPCHECK(hipMemcpy(st, A.stamps, sizeof st, hipMemcpyDeviceToHost));
-    static const char* names[] = {"C1 camera half (slices)", "P1 point half + V (8 lanes / landmark)", "G  [V;z][V;z]^T (MFMA, LDS) + message",
-                                  "exchange 1 (barrier + gather)", "S, g", "elimination + back substitution", "camera update + P2", "C3 trial cost (slices)", "exchange 2"};
-    for (int k = 0; k < 9; ++k) fprintf(stderr, "[k_small_mw, LM iteration 2, workgroup 0] %-40s %7.2f us\n", names[k], (st[k + 1] - st[k]) * 0.01);
-    fprintf(stderr, "[k_small_mw] elimination %.2f us, back substitution %.2f us\n", (st[13] - st[12]) * 0.01, (st[6] - st[13]) * 0.01);
-  } else if (A.stamps) {
-    long long st[16];
-    HIPCHECK(hipMemcpy(st, A.stamps, sizeof st, hipMemcpyDeviceToHost));
-    static const char* names[] = {"C1 camera half", "P1 point half + V", "G  [V;z][V;z]^T (MFMA)", "S, g from the tiles", "Cholesky + solves (1 wave)",
-                                  "camera update", "P2 back substitution", "C3 trial cost"};
-    for (int k = 0; k < 8; ++k) fprintf(stderr, "[k_small_lm, LM iteration 2] %-28s %7.2f us\n", names[k], (st[k + 1] - st[k]) * 0.01);
-    fprintf(stderr, "[k_small_lm] wave 0: factor %.2f us, forward %.2f us, backward %.2f us\n", (st[13] - st[4]) * 0.01, (st[14] - st[13]) * 0.01, (st[5] - st[14]) * 0.01);
-    fprintf(stderr, "[k_small_lm] shader clock over the iteration: %.2f GHz\n", (double)(st[10] - st[9]) / ((st[8] - st[0]) * 10.0));
-  }
+  if (A.stamps)
+    if (int rc = report_small_stamps(A.stamps, used_mw)) return rc;
   h->linearized = false;
   sum->seconds_total = now_s() - t_begin;
   const double per = sum->iterations ? sum->seconds_total / sum->iterations : 0.0;
@@ -2824,7 +2827,10 @@ static bool all_held(const ba_handle* h) {
   const int nb = nb_of(h);
   return held_params(h, nb) == (int64_t)nb * h->Nc + 3 * (int64_t)h->Np;
 }
-static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
+// The LM driver.  solve_impl is the skeleton; what is fixed for one solve sits in SolvePlan, what the iterations change in
+// LmState and PrecondLag, and the stages of one iteration are functions of their own: linearize, run_pcg (the inner solve),
+// queue_step_and_verdict (everything queued behind it) and apply_verdict (the host's half of accepting or rejecting the step).
+static int check_solve_options(const ba_handle* h, const ba_options* opts) {
   if (!h->have_params) return fail(BA_ERR_STATE, "ba_set_problem / ba_set_params first");
   if (!loss_valid(opts->loss)) return fail(BA_ERR_INVALID, "unknown loss %d", opts->loss);
   if (!(opts->f_scale > 0) || opts->max_iters < 0 || opts->pcg_max_iters < 1 || !(opts->initial_lambda > 0))
@@ -2839,57 +2845,83 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
     return fail(BA_ERR_INVALID, "camera mask bits 6-8 (f, k1, k2) need the BAL camera model");
   if (h->model == 0 && h->prior_nb == 9) return fail(BA_ERR_INVALID, "%s", kPriorNeedsBal);
   if (h->model == 0 && h->n_shared) return fail(BA_ERR_INVALID, "%s", kSharedNeedsBal);
-  if (set_device(h)) return BA_ERR_HIP;
-  h->shared_on = h->model != 0 && h->n_shared > 0;
-  memset(sum, 0, sizeof *sum);
-  h->trace.clear();
-  h->fold_prior_rows = any_prior(h) ? PRIOR_ROWS : 0;      // cost = reprojection + priors in every fold of this solve
-  // single rank, every parameter held: nothing to adjust
-  if (!h->multi && all_held(h)) {
-    double sse = 0, cost = 0;
-    if (int rc = eval_cost(h, h->cur, (ba_loss)opts->loss, opts->f_scale, &sse, &cost)) return rc;
-    sum->initial_sse = sum->final_sse = sse; sum->initial_cost = sum->final_cost = cost; sum->final_lambda = opts->initial_lambda;
-    return BA_OK;
-  }
-  // window-sized problems: one launch, exact reduced solve -- no PCG, so preconditioner / jacobian_precision (validated
-  // above) have nothing to act on, and no per-solve mode of the multi-kernel path is left switched on behind it
-  h->jac_f32 = false;
-  if (h->model == 0 && small_applies(h, opts)) return small_solve(h, opts, sum);
-  h->jac_f32 = opts->jacobian_precision == 1;
-  roctx_load();
-  Range r_solve("ba_solve");
-  const ba_loss loss = (ba_loss)opts->loss;
-  const bool robust = loss != BA_LOSS_LINEAR;        // (the Schur passes only read the weights: the same for every non-linear loss)
-  const bool schur_diag = opts->preconditioner != BA_PRECOND_JACOBI;
-  const double fs = opts->f_scale;
-  const int Nc = h->Nc;
-  h->profile = opts->profile != 0;
-  const double tol2 = opts->pcg_tol * opts->pcg_tol;
+  return BA_OK;
+}
+struct SolvePlan {               // fixed for one solve: read from the options, the environment and the handle once
+  const ba_options* opts;
+  ba_loss loss;
+  bool robust, schur_diag;       // (robust: the Schur passes only read the weights -- the same for every non-linear loss)
+  double fs, tol2, model_tol;
+  int lag, riders;               // precond_lag, 0 where there are no Schur-Jacobi blocks to keep; BA_RIDERS
+  bool debug_poison, use_ipc;    // (debug_poison, tests: every trial cost comes out NaN)
+};
+static SolvePlan solve_plan(const ba_handle* h, const ba_options* opts) {
+  SolvePlan P;
+  P.opts = opts;
+  P.loss = (ba_loss)opts->loss; P.robust = P.loss != BA_LOSS_LINEAR; P.fs = opts->f_scale;
+  P.schur_diag = opts->preconditioner != BA_PRECOND_JACOBI; P.lag = P.schur_diag ? opts->precond_lag : 0;
+  P.tol2 = opts->pcg_tol * opts->pcg_tol;
   // (automatic: the model test trades inner accuracy for outer iterations -- on band-structured problems a large gain at
   // loose outer tolerances like the reference's ftol = 1e-5, a loss where the caller asks for tight convergence)
-  const double model_tol = opts->pcg_model_tol >= 0.0 ? opts->pcg_model_tol : ((h->banded && opts->ftol >= 1e-6) ? 0.5 : 0.0);
-
-  BA_SYNC(h);
-  const double t_begin = now_s();
-  double sse = 0, cost = 0;
-  if (int rc = eval_cost(h, h->cur, loss, fs, &sse, &cost)) return rc;
-  if (!std::isfinite(cost)) return fail(BA_ERR_NUMERIC, "non-finite cost at the initial parameters");
-  sum->initial_sse = sse;
-  sum->initial_cost = cost;
-  // nothing to adjust.  Single rank only: a rank of a multi-rank job whose landmark shard is empty still has to
-  // join every collective of the loop below (with zero partials), or the other ranks wait for it forever.
-  if (!h->multi && (h->Np == 0 || h->Nobs == 0)) {
-    sum->final_sse = sse; sum->final_cost = cost; sum->final_lambda = opts->initial_lambda;
-    sum->seconds_total = now_s() - t_begin;
-    h->profile = false;
-    return BA_OK;
+  P.model_tol = opts->pcg_model_tol >= 0.0 ? opts->pcg_model_tol : ((h->banded && opts->ftol >= 1e-6) ? 0.5 : 0.0);
+  // BA_RIDERS: bit 0 = the camera update rides along the back substitution, bit 1 = the scalar fold + verdict rides along
+  // the speculated point half (ba_kernels.hpp, "riders"), bit 2 = the PCG probe that finds PCG finished goes on as the back
+  // substitution in the same launch (needs bit 0); BA_RIDERS=0: launches of their own (tests)
+  P.riders = getenv("BA_RIDERS") ? atoi(getenv("BA_RIDERS")) : 7;
+  P.debug_poison = getenv("BA_DEBUG_POISON_TRIAL") != nullptr;
+  // BA_IPC: the exchange of the Schur product happens inside k_pcg_step, workgroup by workgroup (ba_kernels.hpp,
+  // "device-side all-reduce"); every workgroup's record has to fit its slot of the receive buffers
+  // (shared intrinsics: the group fold runs on the all-reduced product, between the exchange and k_pcg_step -- base transport)
+  P.use_ipc = h->ipc && h->multi && !h->shared_on && nbv(h) <= IPC_MAX_BLOCKS &&
+              (size_t)nbv(h) * (2 + (size_t)nb_of(h) * kModel[h->model].vc) <= IpcComm::STRIDE;
+  return P;
+}
+struct LmState {                 // what the LM iterations change
+  double lambda, nu = 2.0, lam_floor = 0.0, cost = 0.0, sse = 0.0;
+  int it = 0, status = 0;
+  bool stop = false;
+  explicit LmState(double lambda0) : lambda(lambda0) {}
+  bool need_linearize = true;    // a linearisation at the current parameters is needed before the next damped system
+  bool have_lin = false;         // ... and buffer sets [lb] / [pb] already hold it (speculated at the trial point that was accepted)
+};
+// Schur-Jacobi blocks kept over consecutive damped systems (ba_options.precond_lag): when they were built, how often they
+// have been kept since, and what the inner solves cost with them.  Host-side and deterministic: the rule reads options,
+// dampings and PCG iteration counts only (identical on every rank of a multi-rank job).
+struct PrecondLag {
+  int lag, kept = 0, pcg_at_build = -1, pcg_last = -1;
+  bool have = false;
+  double lam_built = 0.0, last_decrease = 1.0;      // (last_decrease: relative cost decrease of the last accepted step)
+  explicit PrecondLag(int lag_) : lag(lag_) {}
+  // (!fresh: the same linearisation damped again after a rejected step; else the point the blocks were built at has moved by
+  // a step that lowered the cost by no more than 1 % -- early, large steps always rebuild: there a stale preconditioner
+  // costs more PCG iterations, at three passes each, than the one 27-sum pass it saves)
+  bool keep(double lambda, bool fresh) const {
+    return lag > 0 && have && kept < lag && lambda <= 10.0 * lam_built && lambda >= 0.1 * lam_built &&
+           (pcg_at_build < 0 || pcg_last <= pcg_at_build + pcg_at_build / 2 + 2) && (!fresh || last_decrease <= 1e-2);
   }
-  const bool debug_poison = getenv("BA_DEBUG_POISON_TRIAL") != nullptr;     // tests: every trial cost comes out NaN
-  // the held parameters' share of |x|^2 (xtol test): the held points' over every shard of a multi-rank job, the held camera
-  // parameters' read from the current cameras (the camera update adds their zero step and keeps their share in its sum)
-  double held_x2 = h->held_x2, held_cam_x2 = 0.0;
+  void built(double lambda) { have = true; lam_built = lambda; kept = 0; pcg_at_build = -1; }
+  void kept_once() { ++kept; }
+  void inner_solve_done(int n) { pcg_last = n; if (pcg_at_build < 0) pcg_at_build = n; }      // (< 0: the first with freshly built blocks)
+  void accepted(double rel_decrease) { last_decrease = rel_decrease; }
+};
+static int initial_cost(ba_handle* h, const SolvePlan& P, LmState* st, ba_summary* sum) {
+  if (int rc = eval_cost(h, h->cur, P.loss, P.fs, &st->sse, &st->cost)) return rc;
+  sum->initial_sse = st->sse; sum->initial_cost = st->cost;
+  return BA_OK;
+}
+static int finish_solve(ba_summary* sum, const LmState& st, double t_begin) {      // every successful way out of solve_impl
+  sum->seconds_total = now_s() - t_begin;
+  sum->iterations = st.it; sum->status = st.status;
+  sum->final_sse = st.sse; sum->final_cost = st.cost; sum->final_lambda = st.lambda;
+  return BA_OK;
+}
+// the held parameters' share of |x|^2 (xtol test): the held points' over every shard of a multi-rank job, the held camera
+// parameters' read from the current cameras (the camera update adds their zero step and keeps their share in its sum)
+static int held_norms(ba_handle* h, double* held_x2, double* held_cam_x2) {
+  *held_x2 = h->held_x2;
+  *held_cam_x2 = 0.0;
   if (h->any_cam_held) {
-    const int nb = nb_of(h);
+    const int nb = nb_of(h), Nc = h->Nc;
     std::vector<double> cams(6 * (size_t)Nc), intr(nb > 6 ? 3 * (size_t)Nc : 0);
     HIPCHECK(hipMemcpyAsync(cams.data(), h->cams[h->cur].p, cams.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (nb > 6) HIPCHECK(hipMemcpyAsync(intr.data(), h->intr[h->cur].p, intr.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2898,293 +2930,315 @@ static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
       for (int q = 0; q < nb; ++q)
         if (((h->h_cam_held[c] >> q) & 1u) && !(q >= 6 && h->shared_on && h->h_cam_gl[c] >= 0 && !(h->h_cam_gl[c] & 1))) {   // (a shared entry once)
           const double v = q < 6 ? cams[6 * (size_t)c + q] : intr[3 * (size_t)c + q - 6];
-          held_cam_x2 += v * v;
+          *held_cam_x2 += v * v;
         }
   }
   if (h->multi) {
     HIPCHECK(h->held_red.alloc(1));
-    HIPCHECK(hipMemcpyAsync(h->held_red.p, &held_x2, sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(h->held_red.p, held_x2, sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (int rc = allreduce(h, h->held_red.p, 1)) return rc;
-    HIPCHECK(hipMemcpyAsync(&held_x2, h->held_red.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipMemcpyAsync(held_x2, h->held_red.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     BA_SYNC(h);
   }
-  // BA_RIDERS: bit 0 = the camera update rides along the back substitution, bit 1 = the scalar fold + verdict rides along
-  // the speculated point half (ba_kernels.hpp, "riders"), bit 2 = the PCG probe that finds PCG finished goes on as the back
-  // substitution in the same launch (needs bit 0); BA_RIDERS=0: launches of their own (tests)
-  const int riders = getenv("BA_RIDERS") ? atoi(getenv("BA_RIDERS")) : 7;
-  double lambda = opts->initial_lambda, nu = 2.0;
-  int it = 0, status = 0;
-  // Schur-Jacobi blocks kept over consecutive damped systems (ba_options.precond_lag): when they were built, how often they
-  // have been kept since, and what the inner solves cost with them.  Host-side and deterministic: the rule reads options,
-  // dampings and PCG iteration counts only (identical on every rank of a multi-rank job).
-  double lam_floor = 0.0;
-  bool have_precond = false;
-  double lam_built = 0.0;
-  double last_decrease = 1.0;      // relative cost decrease of the last accepted step
-  int kept = 0, pcg_at_build = -1, pcg_last = -1;
-  const int lag = schur_diag ? opts->precond_lag : 0;
-  bool need_linearize = true;      // a linearisation at the current parameters is needed before the next damped system
-  bool have_lin = false;           // ... and buffer sets [lb] / [pb] already hold it (speculated at the trial point that was accepted)
-  h->linearized = false;
-
-  while (it < opts->max_iters) {
-    double t0 = now_s();
-    bool fresh = false;
-    Range r_iter("lm_iteration");
-    if (need_linearize) {
-      Range r_lin("linearize");
-      if (!have_lin) {
-        launch_lin_cam(h, h->cur, h->lb, loss, fs);
-        launch_lin_pt(h, h->cur, h->pb, loss, fs, lambda);          // also Hpp^-1, y0 at this lambda
-        // multi-rank: the camera-half partials of a pass launched here still have to be all-reduced
-        // (a speculated pass was reduced right behind its launch)
-        if (int rc = exchange_partL(h, h->lb)) return rc;
-      }
-      h->lin_loss = loss; h->lin_fscale = fs;
-      need_linearize = false;
-      have_lin = false;
-      fresh = true;
-    }
-    // ---- damped system, right-hand side, preconditioner, first PCG vectors
-    // (!fresh: the same linearisation damped again after a rejected step; else the point the blocks were built at has moved by
-    // a step that lowered the cost by no more than 1 % -- early, large steps always rebuild: there a stale preconditioner
-    // costs more PCG iterations, at three passes each, than the one 27-sum pass it saves)
-    const bool keep = lag > 0 && have_precond && kept < lag && lambda <= 10.0 * lam_built && lambda >= 0.1 * lam_built &&
-                      (pcg_at_build < 0 || pcg_last <= pcg_at_build + pcg_at_build / 2 + 2) && (!fresh || last_decrease <= 1e-2);
-    { Range r_damp("damped_system"); if (int rc = damped_system(h, lambda, schur_diag, !fresh, fresh, keep)) return rc; }
-    if (keep) ++kept;
-    else { have_precond = schur_diag; lam_built = lambda; kept = 0; pcg_at_build = -1; }
-    bool gtol_pending = false;     // single rank: max |gradient| lands in host-mapped memory, read at the first PCG verdict
-    if (fresh && opts->gtol > 0) {
-      // max |gradient| = max(|bc|, |bp|): per-workgroup maxima come out of the point half (partG) and of
-      // k_pcg_setup (partGc); single rank: the first PCG probe folds them into host-mapped memory
-      gtol_pending = true;
-      // (multi-rank: bc is all-reduced, identical on every rank; bp is shard-local -- every rank's maximum came with the
-      // damped system's message, exchange_system, and the probe folds those instead of partG)
-    }
-    double t1 = now_s();
-    sum->seconds_linearize += t1 - t0;
-    // ---- PCG.  The point pass of iteration k is the probe: it publishes the verdict for k (go on /
-    // converged after n iterations) in host-mapped memory when it STARTS.  Only after a "go on" are
-    // the camera pass and the vector kernel of k queued (the point pass is still running then),
-    // followed at once by the probe of k+1.  Convergence costs one early-exit point pass.  The rule
-    // only depends on the (deterministic, rank-identical) verdicts, never on timing.
-    int k = 0, pcg_done_iters = -1;
-    bool gtol_stop = false;
-    const long long base = h->flag_base;
-    h->flag_base += opts->pcg_max_iters + 8;
-    // K7a + K6 arguments.  The camera update does not feed the back substitution except through the step's vt, which the point
-    // workgroups drop into the rows of their LDS windows themselves (vx): it rides along the same launch as extra
-    // workgroups (ba_kernels.hpp, "riders") whenever every window is staged in LDS; else it is a launch of its own.
-    CamUpdateArgs cu;
-    memset(&cu, 0, sizeof cu);
-    cu.cams = h->cams[h->cur].p; cu.intr = h->intr[h->cur].p; cu.dc = h->x.p; cu.rpcg = h->r.p; cu.Hcc = h->HccBc.p; cu.bc = bc_ptr(h);
-    cu.cs = h->cs[h->cur].p; cu.cams_trial = h->cams[1 - h->cur].p; cu.intr_trial = h->intr[1 - h->cur].p; cu.cs_trial = h->cs[1 - h->cur].p;
-    cu.vtil = h->camA[h->cur].p; cu.camA_trial = h->camA[1 - h->cur].p; cu.partC = h->partC.p;
-    cu.vx = h->vx.p;
-    cu.cam_gl = cam_gl_ptr(h);
-    cu.lam_slot = h->dev_lam.p;
-    // (riding workgroups: a multiple of NPART, so that the point workgroups behind them keep their XCD = index mod NPART)
-    cu.n_cams = Nc; cu.fixed_cam = h->fixed; cu.groups = CU_GROUPS;
-    cu.n_blocks = (((nbv(h) + cu.groups - 1) / cu.groups + NPART - 1) / NPART) * NPART;
-    const bool ride = (riders & 1) && all_lds_of(h) && h->Np > 0;
-    // The probe that finds PCG finished goes on as the back substitution (pt_schur_body, cu.fuse): the camera-update riders
-    // then sit behind the point workgroups of EVERY PCG point pass (they only run in the launch that finds PCG finished), so
-    // only where they do not add a round of workgroups to those launches -- a point-pass workgroup has a compute unit to
-    // itself (config 5: 256 workgroups, one round; 16 more would be a second one in each of ~100 launches per LM iteration);
-    // fp64 blocks only (the back substitution is never computed with the PCG passes' fp32 blocks).  Nothing in the launch
-    // waits for a rider, so residency is a matter of speed, not of correctness.
-    const int pt_wgs = h->nblkP + h->nblkL;
-    // ... and where the inner solves are short: every PCG point pass carries the riders (0.6 us each at C3), the launch they
-    // save comes once per LM iteration (5 - 8 us) -- beyond ~16 PCG iterations per LM iteration the separate launch is cheaper
-    // (decided from the last inner solve's count: host-side, deterministic, identical on every rank; the bits do not depend on it)
-    const bool fuse = ride && (riders & 4) && !h->jac_f32 && (pcg_last < 0 || pcg_last <= 16) &&
-                      (pt_wgs + cu.n_blocks + h->n_cu - 1) / h->n_cu == (pt_wgs + h->n_cu - 1) / h->n_cu;
-    cu.fuse = fuse ? 1 : 0;
-    bool backsub_done = false;
-    size_t probe_ev = (size_t)-1, probe_flushes = 0;
-    auto launch_point_pass = [&](int kk) {
-      probe_ev = h->ev_slot.size(); probe_flushes = h->n_flushes;
-      launch_pt_schur(h, robust, 0, kk, tol2, opts->pcg_min_iters, base,
-                      (kk == 0 && gtol_pending) ? h->d_scal_host + GMAX_HOST_SLOT : (double*)nullptr, fuse ? &cu : nullptr, h->jac_f32);
-    };
-    // BA_IPC: the exchange of the Schur product happens inside k_pcg_step, workgroup by workgroup (ba_kernels.hpp,
-    // "device-side all-reduce"); every workgroup's record has to fit its slot of the receive buffers
-    // (shared intrinsics: the group fold runs on the all-reduced product, between the exchange and k_pcg_step -- base transport)
-    const bool use_ipc = h->ipc && h->multi && !h->shared_on && nbv(h) <= IPC_MAX_BLOCKS &&
-                         (size_t)nbv(h) * (2 + (size_t)nb_of(h) * kModel[h->model].vc) <= IpcComm::STRIDE;
-    auto launch_rest = [&](int kk) -> int {
-      launch_cam_schur(h, robust, false, true, kk, tol2, opts->pcg_min_iters);
-      // the Schur product of the reduced camera system, summed over the ranks: device-side stores into every peer's receive
-      // buffer (inside k_pcg_step), or fold + all-reduce on the base transport
-      IpcStep ipc;
-      memset(&ipc, 0, sizeof ipc);
-      if (use_ipc) {
-        IpcComm* c = h->ipc;
-        ipc.P = c->peers; ipc.on = 1; ipc.rank = c->rank; ipc.world = c->world;
-        ipc.seq = ++c->seq;
-        ipc.parity = (int)(ipc.seq & 1);
-        ipc.stride = IpcComm::STRIDE;
-        h->stats[BA_STAT_IPC_EXCHANGES]++;
-      } else if (int rc = exchange_schur(h)) return rc;
-      Scope sc(h, BA_K_PCG_UPDATE);
-      // (device-side exchange: k_cam_schur's raw partitions, folded inside the kernel; else partition 0 holds the all-reduced sums)
-      const int step_parts = use_ipc ? NPART : nparts_of(h);
-      if (h->shared_on)                 // rows 6-8 of w summed over the members, a workgroup per chunk of a group
-        BA_LAUNCH(k_shared_fold<BalCam>, dim3(h->n_shared_chunks), dim3(SHARED_BLOCK), 0, h->stream, (const int*)h->chunk_rng.p, (const int*)h->grp_mem.p,
-                  (const double*)h->Hccd.p, (const double*)h->z.p, (const double*)p6_ptr(h), step_parts, Nc, h->grp_w.p);
-#define STEP_ARGS kk, (const double*)p6_ptr(h), step_parts, (const double*)uy_ptr(h), h->Hccd.p, h->Minv.p, h->cs[h->cur].p, Nc, h->fixed, tol2,       \
-                  opts->pcg_min_iters, h->x.p, h->r.p, h->p.p, h->s.p, h->z.p, h->camA[h->cur].p, h->partV.p, nbv(h), h->st.p, \
-                  h->d_flags, base, (const double*)h->verdict.p, h->vx.p, model_tol, opts->pcg_model_min_iters, ipc, h->d_flags + 6,        \
+  return BA_OK;
+}
+static int linearize(ba_handle* h, const SolvePlan& P, LmState* st) {
+  Range r_lin("linearize");
+  if (!st->have_lin) {
+    launch_lin_cam(h, h->cur, h->lb, P.loss, P.fs);
+    launch_lin_pt(h, h->cur, h->pb, P.loss, P.fs, st->lambda);          // also Hpp^-1, y0 at this lambda
+    // multi-rank: the camera-half partials of a pass launched here still have to be all-reduced
+    // (a speculated pass was reduced right behind its launch)
+    if (int rc = exchange_partL(h, h->lb)) return rc;
+  }
+  h->lin_loss = P.loss; h->lin_fscale = P.fs;
+  st->need_linearize = false;
+  st->have_lin = false;
+  return BA_OK;
+}
+// K7a + K6 arguments.  The camera update does not feed the back substitution except through the step's vt, which the point
+// workgroups drop into the rows of their LDS windows themselves (vx): it rides along the same launch as extra
+// workgroups (ba_kernels.hpp, "riders") whenever every window is staged in LDS; else it is a launch of its own.
+static CamUpdateArgs cam_update_args(ba_handle* h) {
+  CamUpdateArgs cu;
+  memset(&cu, 0, sizeof cu);
+  cu.cams = h->cams[h->cur].p; cu.intr = h->intr[h->cur].p; cu.dc = h->x.p; cu.rpcg = h->r.p; cu.Hcc = h->HccBc.p; cu.bc = bc_ptr(h);
+  cu.cs = h->cs[h->cur].p; cu.cams_trial = h->cams[1 - h->cur].p; cu.intr_trial = h->intr[1 - h->cur].p; cu.cs_trial = h->cs[1 - h->cur].p;
+  cu.vtil = h->camA[h->cur].p; cu.camA_trial = h->camA[1 - h->cur].p; cu.partC = h->partC.p;
+  cu.vx = h->vx.p;
+  cu.cam_gl = cam_gl_ptr(h);
+  cu.lam_slot = h->dev_lam.p;
+  // (riding workgroups: a multiple of NPART, so that the point workgroups behind them keep their XCD = index mod NPART)
+  cu.n_cams = h->Nc; cu.fixed_cam = h->fixed; cu.groups = CU_GROUPS;
+  cu.n_blocks = (((nbv(h) + cu.groups - 1) / cu.groups + NPART - 1) / NPART) * NPART;
+  return cu;
+}
+struct RiderPlan { bool ride, fuse; };        // of one LM iteration: the camera update rides / the finishing probe goes on as back substitution
+static RiderPlan rider_plan(const ba_handle* h, const SolvePlan& P, const CamUpdateArgs& cu, int pcg_last) {
+  RiderPlan rp;
+  rp.ride = (P.riders & 1) && all_lds_of(h) && h->Np > 0;
+  // The probe that finds PCG finished goes on as the back substitution (pt_schur_body, cu.fuse): the camera-update riders
+  // then sit behind the point workgroups of EVERY PCG point pass (they only run in the launch that finds PCG finished), so
+  // only where they do not add a round of workgroups to those launches -- a point-pass workgroup has a compute unit to
+  // itself (config 5: 256 workgroups, one round; 16 more would be a second one in each of ~100 launches per LM iteration);
+  // fp64 blocks only (the back substitution is never computed with the PCG passes' fp32 blocks).  Nothing in the launch
+  // waits for a rider, so residency is a matter of speed, not of correctness.
+  const int pt_wgs = h->nblkP + h->nblkL;
+  // ... and where the inner solves are short: every PCG point pass carries the riders (0.6 us each at C3), the launch they
+  // save comes once per LM iteration (5 - 8 us) -- beyond ~16 PCG iterations per LM iteration the separate launch is cheaper
+  // (decided from the last inner solve's count: host-side, deterministic, identical on every rank; the bits do not depend on it)
+  rp.fuse = rp.ride && (P.riders & 4) && !h->jac_f32 && (pcg_last < 0 || pcg_last <= 16) &&
+            (pt_wgs + cu.n_blocks + h->n_cu - 1) / h->n_cu == (pt_wgs + h->n_cu - 1) / h->n_cu;
+  return rp;
+}
+// the vector kernel of PCG iteration kk (behind the shared intrinsics' group fold, where there is one)
+static void launch_pcg_step(ba_handle* h, const SolvePlan& P, int kk, long long base, const IpcStep& ipc) {
+  Scope sc(h, BA_K_PCG_UPDATE);
+  // (device-side exchange: k_cam_schur's raw partitions, folded inside the kernel; else partition 0 holds the all-reduced sums)
+  const int step_parts = P.use_ipc ? NPART : nparts_of(h);
+  if (h->shared_on)                 // rows 6-8 of w summed over the members, a workgroup per chunk of a group
+    BA_LAUNCH(k_shared_fold<BalCam>, dim3(h->n_shared_chunks), dim3(SHARED_BLOCK), 0, h->stream, (const int*)h->chunk_rng.p, (const int*)h->grp_mem.p,
+              (const double*)h->Hccd.p, (const double*)h->z.p, (const double*)p6_ptr(h), step_parts, h->Nc, h->grp_w.p);
+#define STEP_ARGS kk, (const double*)p6_ptr(h), step_parts, (const double*)uy_ptr(h), h->Hccd.p, h->Minv.p, h->cs[h->cur].p, h->Nc, h->fixed, P.tol2,  \
+                  P.opts->pcg_min_iters, h->x.p, h->r.p, h->p.p, h->s.p, h->z.p, h->camA[h->cur].p, h->partV.p, nbv(h), h->st.p, \
+                  h->d_flags, base, (const double*)h->verdict.p, h->vx.p, P.model_tol, P.opts->pcg_model_min_iters, ipc, h->d_flags + 6,    \
                   cam_held_ptr(h), cam_gl_ptr(h), (const double*)(h->shared_on ? h->grp_w.p : nullptr),                                 \
                   (const int*)(h->shared_on ? h->grp_chunk.p : nullptr)
-      if (h->shared_on) BA_LAUNCH((k_pcg_step<BalCam, true>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS);
-      else BA_BY_MODEL(h->model, BA_LAUNCH((k_pcg_step<CM>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS));
+  if (h->shared_on) BA_LAUNCH((k_pcg_step<BalCam, true>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS);
+  else BA_BY_MODEL(h->model, BA_LAUNCH((k_pcg_step<CM>), dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, STEP_ARGS));
 #undef STEP_ARGS
-      return BA_OK;
-    };
-    Range* r_pcg = new Range("pcg");
-    struct RangeGuard { Range*& r; ~RangeGuard() { delete r; r = nullptr; } } r_pcg_guard{r_pcg};
-    launch_point_pass(0);
-    while (true) {
-      if (int rc = wait_flag(h, 0, base + k + 1)) return rc;
-      if (h->h_flags[6] == 2) { h->h_flags[6] = 0; return fail(BA_ERR_COMM, "LM iteration %d: a peer's share of the reduced camera system's product did not arrive (BA_IPC)", it); }
-      // the gradient maximum was written by a kernel ahead of this probe: visible now
-      if (gtol_pending) {
-        gtol_pending = false;
-        const double gmax = h->h_scal[GMAX_HOST_SLOT];
-        if (!std::isfinite(gmax)) return fail(BA_ERR_NUMERIC, "non-finite gradient at LM iteration %d", it);
-        if (gmax <= opts->gtol) { gtol_stop = true; break; }
-      }
-      const long long payload = h->h_flags[1];
-      if (payload > 0) {
-        pcg_done_iters = (int)payload - 1;
-        if (fuse) {                   // the launch that published this verdict is doing the back substitution
-          backsub_done = true;
-          if (h->profile && probe_flushes == h->n_flushes && probe_ev < h->ev_slot.size()) h->ev_slot[probe_ev] = BA_K_SCHUR_PT_BACKSUB;
-        }
-        break;
-      }
-      if (int rc = launch_rest(k)) return rc;
-      ++k;
-      if (k >= opts->pcg_max_iters) break;
-      launch_point_pass(k);
+}
+// ---- PCG.  The point pass of iteration k is the probe: it publishes the verdict for k (go on /
+// converged after n iterations) in host-mapped memory when it STARTS.  Only after a "go on" are
+// the camera pass and the vector kernel of k queued (the point pass is still running then),
+// followed at once by the probe of k+1.  Convergence costs one early-exit point pass.  The rule
+// only depends on the (deterministic, rank-identical) verdicts, never on timing.
+struct PcgOutcome {
+  int k = 0;                     // iterations queued
+  int done_iters = -1;           // ... and the count a probe reported, where one found PCG finished
+  bool gtol_stop = false, backsub_done = false;
+};
+// gtol_pending (single rank): max |gradient| lands in host-mapped memory, read at the first PCG verdict
+static int run_pcg(ba_handle* h, const SolvePlan& P, const RiderPlan& rp, CamUpdateArgs& cu, bool gtol_pending, int it, PcgOutcome* out) {
+  const ba_options* opts = P.opts;
+  Range r_pcg("pcg");
+  const long long base = h->flag_base;
+  h->flag_base += opts->pcg_max_iters + 8;
+  int& k = out->k;
+  while (true) {
+    const size_t probe_ev = h->ev_slot.size(), probe_flushes = h->n_flushes;
+    launch_pt_schur(h, P.robust, 0, k, P.tol2, opts->pcg_min_iters, base,
+                    (k == 0 && gtol_pending) ? h->d_scal_host + GMAX_HOST_SLOT : (double*)nullptr, rp.fuse ? &cu : nullptr, h->jac_f32);
+    if (int rc = wait_flag(h, 0, base + k + 1)) return rc;
+    if (h->h_flags[6] == 2) { h->h_flags[6] = 0; return fail(BA_ERR_COMM, "LM iteration %d: a peer's share of the reduced camera system's product did not arrive (BA_IPC)", it); }
+    // the gradient maximum was written by a kernel ahead of this probe: visible now
+    if (gtol_pending) {
+      gtol_pending = false;
+      const double gmax = h->h_scal[GMAX_HOST_SLOT];
+      if (!std::isfinite(gmax)) return fail(BA_ERR_NUMERIC, "non-finite gradient at LM iteration %d", it);
+      if (gmax <= opts->gtol) { out->gtol_stop = true; break; }
     }
-    delete r_pcg; r_pcg = nullptr;
-    if (gtol_stop) { status = 3; break; }      // converged by gradient: no step (the queued probe exits on its own)
+    const long long payload = h->h_flags[1];
+    if (payload > 0) {
+      out->done_iters = (int)payload - 1;
+      if (rp.fuse) {                // the launch that published this verdict is doing the back substitution
+        out->backsub_done = true;
+        if (h->profile && probe_flushes == h->n_flushes && probe_ev < h->ev_slot.size()) h->ev_slot[probe_ev] = BA_K_SCHUR_PT_BACKSUB;
+      }
+      break;
+    }
+    launch_cam_schur(h, P.robust, false, true, k);
+    // the Schur product of the reduced camera system, summed over the ranks: device-side stores into every peer's receive
+    // buffer (inside k_pcg_step), or fold + all-reduce on the base transport
+    IpcStep ipc;
+    memset(&ipc, 0, sizeof ipc);
+    if (P.use_ipc) {
+      IpcComm* c = h->ipc;
+      ipc.P = c->peers; ipc.on = 1; ipc.rank = c->rank; ipc.world = c->world;
+      ipc.seq = ++c->seq;
+      ipc.parity = (int)(ipc.seq & 1);
+      ipc.stride = IpcComm::STRIDE;
+      h->stats[BA_STAT_IPC_EXCHANGES]++;
+    } else if (int rc = exchange_schur(h)) return rc;
+    launch_pcg_step(h, P, k, base, ipc);
+    if (++k >= opts->pcg_max_iters) break;
+  }
+  return BA_OK;
+}
+// ---- step, trial point, gain-ratio scalars: everything that is queued between the inner solve and the host's wait for the
+// step's verdict (flag 2 reaching h->step_seq).  Speculation: unless this is the last iteration, the cost at the trial point
+// comes out of the camera half of the NEXT linearisation computed there (one pass instead of two), into the other c_w / partL
+// buffers; the step's verdict (gain ratio, next damping) is computed on the device right behind it, and while the host reads
+// it the GPU already runs the point half at the trial point with that damping, into the other point buffers.  An accepted
+// step finds its linearisation done; a rejected one ignores both.
+static int queue_step_and_verdict(ba_handle* h, const SolvePlan& P, const RiderPlan& rp, CamUpdateArgs& cu, const PcgOutcome& pcg,
+                                  const LmState& st, bool speculated) {
+  const ba_options* opts = P.opts;
+  if (!pcg.backsub_done) {          // (PCG ran into its iteration cap, or the fused form is off)
+    cu.fuse = 0;
+    if (!rp.ride) {
+      Scope sc(h, BA_K_MISC);
+      BA_BY_MODEL(h->model, BA_LAUNCH(k_cam_update<CM>, dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, cu));
+      cu.n_blocks = 0;              // (the arguments still travel: the launch clears the riding verdict's damping word)
+    }
+    launch_pt_schur(h, P.robust, 1, 0, 0.0, 0, 0, nullptr, &cu);
+  }
+  if (speculated) launch_lin_cam(h, 1 - h->cur, 1 - h->lb, P.loss, P.fs, true);
+  else            launch_residual(h, 1 - h->cur, P.loss, P.fs, nullptr);
+  launch_prior_cost(h, 1 - h->cur);          // (priors set: their terms at the trial point, behind the reprojection rows)
+  if (P.debug_poison) BA_LAUNCH(k_poison, dim3(1), dim3(64), 0, h->stream, h->partR.p);
+  const long long seq = ++h->step_seq;
+  // the step's scalar fold + verdict: single rank with a speculated point half behind it -> workgroup 0 of that launch
+  // (the point workgroups pick the next damping up through a device word); else a launch of its own
+  const bool ride_scalars = (P.riders & 2) && speculated && !h->multi && h->Np > 0;
+  if (!ride_scalars) launch_scalars(h, true, pcg.k, P.tol2, opts->pcg_min_iters, seq, st.cost, st.lambda, st.lam_floor);
+  if (h->multi) {
+    // the six sums over ranks, then the verdict on the all-reduced block (same host-mapped mirror + word).  A speculated
+    // camera half has to be all-reduced anyway: the six words travel in the header of that message, one collective
+    const double* reduced6 = nullptr;
+    if (speculated) {
+      if (int rc = exchange_partL(h, 1 - h->lb, true)) return rc;
+      reduced6 = h->linmsg[1 - h->lb].p;
+    } else if (int rc = allreduce(h, h->scal.p, 6)) return rc;
+    Scope sc(h, BA_K_MISC);
+    BA_LAUNCH(k_decide, dim3(1), dim3(64), 0, h->stream, h->scal.p, reduced6, st.cost, st.lambda, st.lam_floor, h->d_scal_host, h->d_flags + 2, seq);
+  }
+  if (speculated) {
+    ScalarsArgs sa = scalars_args(h, true, pcg.k, P.tol2, opts->pcg_min_iters, seq, st.cost, st.lambda, st.lam_floor);
+    sa.on = 1; sa.lam_slot = h->dev_lam.p; sa.err_flag = h->d_flags + 6;
+    launch_lin_pt(h, 1 - h->cur, 1 - h->pb, P.loss, P.fs, 0.0, h->scal.p + S_LAM_NEXT, ride_scalars ? &sa : nullptr);
+  }
+  return BA_OK;
+}
+// The host's half of the verdict, pure host code: the scalars of the step are in h->h_scal (gain ratio and next damping were
+// decided on the device, lm_decide).  Records the iteration, accepts or rejects the step, tests ftol and xtol.
+static int apply_verdict(ba_handle* h, const SolvePlan& P, LmState* st, PrecondLag* lag, ba_summary* sum, int pcg_done_iters,
+                         bool speculated, double held_x2, double held_cam_x2, double t0) {
+  const ba_options* opts = P.opts;
+  const double* S = h->h_scal;
+  const double sse_new = S[S_SSE], cost_new = 0.5 * S[S_RHO];
+  const double step2 = S[S_PT_DD] + S[S_CAM_DD];
+  const double x2 = (held_x2 != 0.0 || held_cam_x2 != 0.0)
+                        ? std::max(0.0, S[S_PT_XX] - held_x2) + std::max(0.0, S[S_CAM_XX] - held_cam_x2)
+                        : S[S_PT_XX] + S[S_CAM_XX];
+  const double rho = S[S_GAIN];
+  const bool accept = rho > 0 && std::isfinite(cost_new);
+  const int it = ++st->it;
+  if (opts->verbose)
+    fprintf(stderr, "[ba] it %3d cost %.9e -> %.9e lambda %.3e rho %+.3f pcg %d |step| %.3e\n", it, st->cost, cost_new,
+            st->lambda, rho, pcg_done_iters, std::sqrt(step2));
+  ba_iter_record rec = {};
+  rec.iteration = it; rec.accepted = accept ? 1 : 0; rec.pcg_iterations = pcg_done_iters;
+  rec.cost = st->cost; rec.cost_trial = cost_new; rec.sse_trial = sse_new; rec.lambda = st->lambda; rec.gain_ratio = rho;
+  rec.step_norm = std::sqrt(step2); rec.seconds = now_s() - t0;
+  h->trace.push_back(rec);
+  if (accept) {
+    const double dcost = st->cost - cost_new;
+    lag->accepted(cost_new > 0.0 ? dcost / cost_new : 1.0);
+    h->cur = 1 - h->cur;
+    if (speculated) { h->lb = 1 - h->lb; h->pb = 1 - h->pb; st->have_lin = true; }
+    st->cost = cost_new;
+    st->sse = sse_new;
+    sum->accepted++;
+    st->lambda = S[S_LAM_NEXT];
+    st->nu = 2.0;
+    st->need_linearize = true;
+    if (dcost <= opts->ftol * st->cost) { st->status = 1; st->stop = true; }
+  } else {
+    // a trial cost that is not finite even at the largest damping the loop allows cannot be stepped away from
+    if (!std::isfinite(cost_new) && st->lambda >= 1e12)
+      return fail(BA_ERR_NUMERIC, "non-finite cost at the trial point of LM iteration %d with the damping at its cap", it);
+    st->lambda = std::min(st->lambda * st->nu, 1e12);
+    st->nu *= 2.0;
+  }
+  if (!st->stop && std::sqrt(step2) <= opts->xtol * (opts->xtol + std::sqrt(x2))) { st->status = 2; st->stop = true; }
+  return BA_OK;
+}
+static int solve_impl(ba_handle* h, const ba_options* opts, ba_summary* sum) {
+  if (int rc = check_solve_options(h, opts)) return rc;
+  if (set_device(h)) return BA_ERR_HIP;
+  memset(sum, 0, sizeof *sum);
+  h->trace.clear();
+  // the per-solve modes: switched on here, switched off by ba_solve behind every exit of this function
+  h->shared_on = h->model != 0 && h->n_shared > 0;
+  h->fold_prior_rows = any_prior(h) ? PRIOR_ROWS : 0;      // cost = reprojection + priors in every fold of this solve
+  h->profile = opts->profile != 0;
+  h->jac_f32 = opts->jacobian_precision == 1;              // (read by the PCG passes only: the window solver has none)
+  const SolvePlan P = solve_plan(h, opts);
+  LmState st(opts->initial_lambda);
+  double t_begin = now_s();
+  // single rank, every parameter held: nothing to adjust
+  if (!h->multi && all_held(h)) {
+    if (int rc = initial_cost(h, P, &st, sum)) return rc;
+    return finish_solve(sum, st, t_begin);
+  }
+  // window-sized problems: one launch, exact reduced solve -- no PCG, so preconditioner / jacobian_precision (validated
+  // above) have nothing to act on
+  if (h->model == 0 && small_applies(h, opts)) return small_solve(h, opts, sum);
+  roctx_load();
+  Range r_solve("ba_solve");
+  BA_SYNC(h);
+  t_begin = now_s();
+  if (int rc = initial_cost(h, P, &st, sum)) return rc;
+  if (!std::isfinite(st.cost)) return fail(BA_ERR_NUMERIC, "non-finite cost at the initial parameters");
+  // nothing to adjust.  Single rank only: a rank of a multi-rank job whose landmark shard is empty still has to
+  // join every collective of the loop below (with zero partials), or the other ranks wait for it forever.
+  if (!h->multi && (h->Np == 0 || h->Nobs == 0)) return finish_solve(sum, st, t_begin);
+  double held_x2 = 0.0, held_cam_x2 = 0.0;
+  if (int rc = held_norms(h, &held_x2, &held_cam_x2)) return rc;
+  PrecondLag lag(P.lag);
+  h->linearized = false;
+
+  while (st.it < opts->max_iters && !st.stop) {
+    const double t0 = now_s();
+    Range r_iter("lm_iteration");
+    const bool fresh = st.need_linearize;
+    if (fresh)
+      if (int rc = linearize(h, P, &st)) return rc;
+    // ---- damped system, right-hand side, preconditioner, first PCG vectors
+    const bool keep = lag.keep(st.lambda, fresh);
+    { Range r_damp("damped_system"); if (int rc = damped_system(h, st.lambda, P.schur_diag, !fresh, fresh, keep)) return rc; }
+    if (keep) lag.kept_once();
+    else lag.built(st.lambda);
+    // max |gradient| = max(|bc|, |bp|): per-workgroup maxima come out of the point half (partG) and of
+    // k_pcg_setup (partGc); single rank: the first PCG probe folds them into host-mapped memory
+    // (multi-rank: bc is all-reduced, identical on every rank; bp is shard-local -- every rank's maximum came with the
+    // damped system's message, exchange_system, and the probe folds those instead of partG)
+    const bool gtol_pending = fresh && opts->gtol > 0;
+    const double t1 = now_s();
+    sum->seconds_linearize += t1 - t0;
+    // ---- the inner solve
+    CamUpdateArgs cu = cam_update_args(h);
+    const RiderPlan rp = rider_plan(h, P, cu, lag.pcg_last);
+    cu.fuse = rp.fuse ? 1 : 0;
+    PcgOutcome pcg;
+    if (int rc = run_pcg(h, P, rp, cu, gtol_pending, st.it, &pcg)) return rc;
+    if (pcg.gtol_stop) { st.status = 3; break; }      // converged by gradient: no step (the queued probe exits on its own)
     // Cap-aware damping.  An inner solve that runs into pcg_max_iters says that at this damping the reduced system is
     // beyond what the preconditioned iteration resolves within its budget (long camera chains at small damping: the drift
     // modes; BASELINE config 5).  The step it leaves is still a descent step (truncated CG), but letting the damping fall
     // further only buys more capped solves: from here on the damping stays at or above three times the value that
     // hit the cap -- one Nielsen step back, where the solve still converged.  The floor travels with the step's verdict
     // (lm_decide): the speculated point half reads the next damping on the device.
-    if (k >= opts->pcg_max_iters) { lam_floor = std::max(lam_floor, 3.0 * lambda); h->stats[BA_STAT_CAP_FLOOR_RAISES]++; }
-    // ---- step, trial point, gain-ratio scalars
+    if (pcg.k >= opts->pcg_max_iters) { st.lam_floor = std::max(st.lam_floor, 3.0 * st.lambda); h->stats[BA_STAT_CAP_FLOOR_RAISES]++; }
     Range r_step("step");
-    if (!backsub_done) {              // (PCG ran into its iteration cap, or the fused form is off)
-      cu.fuse = 0;
-      if (!ride) {
-        Scope sc(h, BA_K_MISC);
-        BA_BY_MODEL(h->model, BA_LAUNCH(k_cam_update<CM>, dim3(nbv(h)), dim3(VEC_BLOCK), 0, h->stream, cu));
-        cu.n_blocks = 0;              // (the arguments still travel: the launch clears the riding verdict's damping word)
-      }
-      launch_pt_schur(h, robust, 1, 0, 0.0, 0, 0, nullptr, &cu);
-    }
-    // Speculation: unless this is the last iteration, the cost at the trial point comes out of the camera half of
-    // the NEXT linearisation computed there (one pass instead of two), into the other c_w / partL buffers; the step's
-    // verdict (gain ratio, next damping) is computed on the device right behind it, and while the host reads it the
-    // GPU already runs the point half at the trial point with that damping, into the other point buffers.  An accepted
-    // step finds its linearisation done; a rejected one ignores both.
-    const bool speculated = (it + 1 < opts->max_iters);
-    if (speculated) launch_lin_cam(h, 1 - h->cur, 1 - h->lb, loss, fs, true);
-    else            launch_residual(h, 1 - h->cur, loss, fs, nullptr);
-    launch_prior_cost(h, 1 - h->cur);          // (priors set: their terms at the trial point, behind the reprojection rows)
-    if (debug_poison) BA_LAUNCH(k_poison, dim3(1), dim3(64), 0, h->stream, h->partR.p);
-    const long long seq = ++h->step_seq;
-    // the step's scalar fold + verdict: single rank with a speculated point half behind it -> workgroup 0 of that launch
-    // (the point workgroups pick the next damping up through a device word); else a launch of its own
-    const bool ride_scalars = (riders & 2) && speculated && !h->multi && h->Np > 0;
-    if (!ride_scalars) launch_scalars(h, true, k, tol2, opts->pcg_min_iters, seq, cost, lambda, lam_floor);
-    if (h->multi) {
-      // the six sums over ranks, then the verdict on the all-reduced block (same host-mapped mirror + word).  A speculated
-      // camera half has to be all-reduced anyway: the six words travel in the header of that message, one collective
-      const double* reduced6 = nullptr;
-      if (speculated) {
-        if (int rc = exchange_partL(h, 1 - h->lb, true)) return rc;
-        reduced6 = h->linmsg[1 - h->lb].p;
-      } else if (int rc = allreduce(h, h->scal.p, 6)) return rc;
-      Scope sc(h, BA_K_MISC);
-      BA_LAUNCH(k_decide, dim3(1), dim3(64), 0, h->stream, h->scal.p, reduced6, cost, lambda, lam_floor, h->d_scal_host, h->d_flags + 2, seq);
-    }
-    if (speculated) {
-      ScalarsArgs sa = scalars_args(h, true, k, tol2, opts->pcg_min_iters, seq, cost, lambda, lam_floor);
-      sa.on = 1; sa.lam_slot = h->dev_lam.p; sa.err_flag = h->d_flags + 6;
-      launch_lin_pt(h, 1 - h->cur, 1 - h->pb, loss, fs, 0.0, h->scal.p + S_LAM_NEXT, ride_scalars ? &sa : nullptr);
-    }
-    if (int rc = wait_flag(h, 2, seq)) return rc;
+    const bool speculated = st.it + 1 < opts->max_iters;      // the next linearisation is computed at the trial point
+    if (int rc = queue_step_and_verdict(h, P, rp, cu, pcg, st, speculated)) return rc;
+    if (int rc = wait_flag(h, 2, h->step_seq)) return rc;
     if (h->h_flags[6] != 0) {          // a point workgroup of the speculated pass waited RIDER_WAIT_TICKS for the riding verdict
       h->h_flags[6] = 0;
-      return fail(BA_ERR_HIP, "LM iteration %d: the point workgroups of the speculated linearisation were not served by the riding scalar fold", it);
+      return fail(BA_ERR_HIP, "LM iteration %d: the point workgroups of the speculated linearisation were not served by the riding scalar fold", st.it);
     }
-    if (pcg_done_iters < 0) pcg_done_iters = (h->h_scal[S_PCG_FIN] != 0.0) ? (int)h->h_scal[S_PCG_ITERS] : k;
-    sum->pcg_iterations += pcg_done_iters;
-    pcg_last = pcg_done_iters;
-    if (pcg_at_build < 0) pcg_at_build = pcg_done_iters;      // the first inner solve with freshly built blocks
-    double t2 = now_s();
+    if (pcg.done_iters < 0) pcg.done_iters = (h->h_scal[S_PCG_FIN] != 0.0) ? (int)h->h_scal[S_PCG_ITERS] : pcg.k;
+    sum->pcg_iterations += pcg.done_iters;
+    lag.inner_solve_done(pcg.done_iters);
+    const double t2 = now_s();
     sum->seconds_pcg += t2 - t1;
-    const double* S = h->h_scal;
-    const double sse_new = S[S_SSE], cost_new = 0.5 * S[S_RHO];
-    const double step2 = S[S_PT_DD] + S[S_CAM_DD];
-    const double x2 = (held_x2 != 0.0 || held_cam_x2 != 0.0)
-                          ? std::max(0.0, S[S_PT_XX] - held_x2) + std::max(0.0, S[S_CAM_XX] - held_cam_x2)
-                          : S[S_PT_XX] + S[S_CAM_XX];
-    const double rho = S[S_GAIN];               // gain ratio and next damping: decided on the device (lm_decide)
-    ++it;
-    if (opts->verbose)
-      fprintf(stderr, "[ba] it %3d cost %.9e -> %.9e lambda %.3e rho %+.3f pcg %d |step| %.3e\n", it, cost, cost_new,
-              lambda, rho, pcg_done_iters, std::sqrt(step2));
-    {
-      ba_iter_record rec = {};
-      rec.iteration = it; rec.accepted = (rho > 0 && std::isfinite(cost_new)) ? 1 : 0; rec.pcg_iterations = pcg_done_iters;
-      rec.cost = cost; rec.cost_trial = cost_new; rec.sse_trial = sse_new; rec.lambda = lambda; rec.gain_ratio = rho;
-      rec.step_norm = std::sqrt(step2); rec.seconds = now_s() - t0;
-      h->trace.push_back(rec);
-    }
-    bool stop = false;
-    if (rho > 0 && std::isfinite(cost_new)) {
-      const double dcost = cost - cost_new;
-      last_decrease = cost_new > 0.0 ? dcost / cost_new : 1.0;
-      h->cur = 1 - h->cur;
-      if (speculated) { h->lb = 1 - h->lb; h->pb = 1 - h->pb; have_lin = true; }
-      cost = cost_new;
-      sse = sse_new;
-      sum->accepted++;
-      lambda = S[S_LAM_NEXT];
-      nu = 2.0;
-      need_linearize = true;
-      if (dcost <= opts->ftol * cost) { status = 1; stop = true; }
-    } else {
-      // a trial cost that is not finite even at the largest damping the loop allows cannot be stepped away from
-      if (!std::isfinite(cost_new) && lambda >= 1e12)
-        return fail(BA_ERR_NUMERIC, "non-finite cost at the trial point of LM iteration %d with the damping at its cap", it);
-      lambda = std::min(lambda * nu, 1e12);
-      nu *= 2.0;
-    }
-    if (!stop && std::sqrt(step2) <= opts->xtol * (opts->xtol + std::sqrt(x2))) { status = 2; stop = true; }
+    if (int rc = apply_verdict(h, P, &st, &lag, sum, pcg.done_iters, speculated, held_x2, held_cam_x2, t0)) return rc;
     sum->seconds_update += now_s() - t2;
-    if (stop) break;
   }
   BA_SYNC(h);
-  sum->seconds_total = now_s() - t_begin;
-  sum->iterations = it;
-  sum->status = status;
-  sum->final_sse = sse;
-  sum->final_cost = cost;
-  sum->final_lambda = lambda;
-  if (h->profile) flush_profile(h);
-  h->profile = false;
-  h->jac_f32 = false;
-  return BA_OK;
+  return finish_solve(sum, st, t_begin);
 }
 
 // ------------------------------------------------------------------ counters, test hooks
@@ -3748,8 +3802,8 @@ extern "C" int ba_time_kernel(ba_handle* h, int slot, int reps, double* mean_us)
       case BA_K_LINEARIZE_CAM: launch_lin_cam(h, h->cur, h->lb, loss, h->lin_fscale); break;
       case BA_K_LINEARIZE_PT: launch_lin_pt(h, h->cur, h->pb, loss, h->lin_fscale, 1e-4); break;
       case BA_K_SCHUR_PT: launch_pt_schur(h, robust, 0, 0, -1.0, 1 << 30); break;
-      case BA_K_SCHUR_CAM: launch_cam_schur(h, robust, false, false, 0, 0.0, 0); break;
-      case BA_K_PRECOND: launch_cam_schur(h, robust, true, false, 0, 0.0, 0); break;
+      case BA_K_SCHUR_CAM: launch_cam_schur(h, robust, false, false, 0); break;
+      case BA_K_PRECOND: launch_cam_schur(h, robust, true, false, 0); break;
       case BA_K_POINT_INVERT: launch_point_invert(h, 1e-4); break;
       case BA_K_TRACKS: launch_tracks(h); break;
       case BA_K_RESECT: launch_resect(h); break;
