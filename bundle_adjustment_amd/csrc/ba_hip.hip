@@ -41,6 +41,7 @@
 #include "ba_similarity.hpp"
 #include "ba_resect.hpp"
 #include "ba_ransac.hpp"
+#include "ba_relpose.hpp"
 
 using namespace ba;
 
@@ -284,6 +285,12 @@ struct ba_handle {
   DBuf<int> rn_cnt;
   DBuf<unsigned char> rn_cons, rn_inl;
   RansacArgs rn_args = {};
+  // ba_relative_pose (ba_relpose.hpp): staging of the call -- both views' pixels, the pair offsets, the hypotheses' slots and
+  // masks, the score blocks' best candidates, consensus and inlier bytes per match, the per-pair results
+  DBuf<double> rp_pts, rp_E, rp_best, rp_out;
+  DBuf<long long> rp_off;
+  DBuf<unsigned> rp_mask;
+  DBuf<unsigned char> rp_cons, rp_inl;
   // ba_transform / ba_align / ba_get_centres (ba_similarity.hpp): correspondences a | b | w | u | err (9 doubles each), the
   // per-workgroup partial rows, the device record (similarity, centroids, status)
   DBuf<double> sim_buf, sim_part;
@@ -3598,6 +3605,88 @@ extern "C" int ba_resect_ransac(ba_handle* h, const double* intr, const ba_ransa
     else memset(obs_inlier, 0, (size_t)h->Nobs);
   }
   return resect_end(h, h->rn, opts->write_cams, poses, status, n_inliers, rms_px, max_px);
+}
+
+// ------------------------------------------------------------------------------------------------- two-view relative pose
+// ba_relative_pose (csrc/ba_relpose.hpp): five-point hypotheses, scores, decomposition and local optimisation.  Needs no problem.
+static_assert(RP_OK == BA_RELPOSE_OK && RP_FEW_MATCHES == BA_RELPOSE_FEW_MATCHES && RP_DEGENERATE == BA_RELPOSE_DEGENERATE &&
+              RP_BEHIND == BA_RELPOSE_BEHIND && RP_FEW_INLIERS == BA_RELPOSE_FEW_INLIERS && RP_LOW_PARALLAX == BA_RELPOSE_LOW_PARALLAX &&
+              sizeof(ba_relpose_options) == 48, "device status codes (ba_relpose.hpp)");
+extern "C" int ba_default_relpose_options(ba_relpose_options* o) {
+  if (!o) return fail(BA_ERR_INVALID, "null argument");
+  memset(o, 0, sizeof *o);
+  o->n_hyp = 256;
+  o->lo_rounds = 2;
+  o->max_epi_px = 3.0;
+  o->refine_iters = 20;
+  o->min_inliers = 8;
+  o->max_depth = 50.0;
+  return BA_OK;
+}
+extern "C" int ba_relative_pose(ba_handle* h, const double K[9], int32_t n_pairs, const int64_t* pair_off, const double* pts1, const double* pts2,
+                                const ba_relpose_options* opts, double* R, double* t, uint8_t* status, int32_t* n_inliers, double* rms_px,
+                                double* parallax_deg, int32_t* best_hyp, uint8_t* match_inlier) {
+  if (!h || !K || !opts) return fail(BA_ERR_INVALID, "null argument");
+  if (n_pairs < 0 || n_pairs > 65535) return fail(BA_ERR_INVALID, "ba_relative_pose: n_pairs %d is outside 0 .. 65535", n_pairs);
+  if (opts->n_hyp < 1 || opts->n_hyp > RN_MAX_HYP) return fail(BA_ERR_INVALID, "ba_relative_pose: n_hyp %d is outside 1 .. %d", opts->n_hyp, RN_MAX_HYP);
+  if (opts->lo_rounds < 0) return fail(BA_ERR_INVALID, "ba_relative_pose: lo_rounds must not be negative");
+  if (!(opts->max_epi_px > 0)) return fail(BA_ERR_INVALID, "ba_relative_pose: max_epi_px must be positive");
+  if (opts->refine_iters < 0) return fail(BA_ERR_INVALID, "ba_relative_pose: refine_iters must not be negative");
+  if (opts->min_inliers < 0) return fail(BA_ERR_INVALID, "ba_relative_pose: min_inliers must not be negative");
+  if (!(K[0] > 0 && K[4] > 0 && std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) && std::isfinite(K[5])) || K[1] != 0 || K[3] != 0 ||
+      K[6] != 0 || K[7] != 0 || K[8] != 1)
+    return fail(BA_ERR_INVALID, "ba_relative_pose: K must be the pinhole matrix [fx 0 cx; 0 fy cy; 0 0 1] with fx, fy > 0");
+  if (n_pairs == 0) return BA_OK;
+  if (!pair_off) return fail(BA_ERR_INVALID, "ba_relative_pose: null pair_off");
+  if (pair_off[0] != 0) return fail(BA_ERR_INVALID, "ba_relative_pose: pair_off[0] must be 0");
+  for (int32_t p = 0; p < n_pairs; ++p) {
+    if (pair_off[p + 1] < pair_off[p]) return fail(BA_ERR_INVALID, "ba_relative_pose: pair_off decreases at pair %d", p);
+    if (pair_off[p + 1] - pair_off[p] > 0x7fffffffLL) return fail(BA_ERR_INVALID, "ba_relative_pose: pair_off: pair %d has too many matches", p);
+  }
+  const size_t nm = (size_t)pair_off[n_pairs], np = (size_t)n_pairs;
+  if (nm > 0 && (!pts1 || !pts2)) return fail(BA_ERR_INVALID, "ba_relative_pose: null point arrays");
+  if (set_device(h)) return BA_ERR_HIP;
+  const int n_blk = (RP_SLOTS * opts->n_hyp + RP_THREADS - 1) / RP_THREADS;
+  const size_t nm1 = std::max<size_t>(nm, 1);
+  HIPCHECK(h->rp_pts.alloc(4 * nm1)); HIPCHECK(h->rp_off.alloc(np + 1)); HIPCHECK(h->rp_E.alloc(9 * (size_t)RP_SLOTS * np * opts->n_hyp));
+  HIPCHECK(h->rp_mask.alloc(np * opts->n_hyp)); HIPCHECK(h->rp_best.alloc(RP_BEST * np * n_blk)); HIPCHECK(h->rp_out.alloc(RP_OUT * np));
+  HIPCHECK(h->rp_cons.alloc(nm1)); HIPCHECK(h->rp_inl.alloc(nm1));
+  RelposeArgs a = {};
+  a.fx = K[0]; a.fy = K[4]; a.cx = K[2]; a.cy = K[5];
+  a.fbar = 0.5 * (K[0] + K[4]); a.thr = opts->max_epi_px / a.fbar;
+  a.max_depth = opts->max_depth; a.min_parallax = opts->min_parallax_deg;
+  a.n_hyp = opts->n_hyp; a.lo_rounds = opts->lo_rounds; a.iters = opts->refine_iters; a.min_inliers = opts->min_inliers;
+  a.n_blk = n_blk; a.seed = opts->seed;
+  a.off = h->rp_off.p; a.p1 = (const double2*)h->rp_pts.p; a.p2 = (const double2*)(h->rp_pts.p + 2 * nm1);
+  a.E = h->rp_E.p; a.mask = h->rp_mask.p; a.best = h->rp_best.p; a.cons = h->rp_cons.p; a.inl = h->rp_inl.p; a.out = h->rp_out.p;
+  static_assert(sizeof(long long) == sizeof(int64_t), "pair_off is uploaded as it is");
+  HIPCHECK(hipMemcpyAsync(h->rp_off.p, pair_off, (np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  if (nm > 0) {
+    HIPCHECK(hipMemcpyAsync(h->rp_pts.p, pts1, 2 * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(h->rp_pts.p + 2 * nm1, pts2, 2 * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemsetAsync(h->rp_inl.p, 0, nm, h->stream));
+  }
+  const dim3 b(RP_THREADS);
+  BA_LAUNCH(k_relpose_solve, dim3(n_pairs, (opts->n_hyp + RP_TEAMS - 1) / RP_TEAMS), b, 0, h->stream, a);
+  BA_LAUNCH(k_relpose_score, dim3(n_pairs, n_blk), b, 0, h->stream, a);
+  BA_LAUNCH(k_relpose_lo, dim3(n_pairs), b, 0, h->stream, a);
+  const bool want = R || t || status || n_inliers || rms_px || parallax_deg || best_hyp;
+  std::vector<double> res(want ? RP_OUT * np : 0);
+  if (want) HIPCHECK(hipMemcpyAsync(res.data(), h->rp_out.p, RP_OUT * np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (match_inlier && nm > 0) HIPCHECK(hipMemcpyAsync(match_inlier, h->rp_inl.p, nm, hipMemcpyDeviceToHost, h->stream));
+  BA_SYNC(h);
+  if (want)
+    for (size_t p = 0; p < np; ++p) {
+      const double* r = res.data() + RP_OUT * p;
+      if (R) memcpy(R + 9 * p, r, 9 * sizeof(double));
+      if (t) memcpy(t + 3 * p, r + 9, 3 * sizeof(double));
+      if (status) status[p] = (uint8_t)r[12];
+      if (n_inliers) n_inliers[p] = (int32_t)r[13];
+      if (rms_px) rms_px[p] = r[14];
+      if (parallax_deg) parallax_deg[p] = r[15];
+      if (best_hyp) best_hyp[p] = (int32_t)r[16];
+    }
+  return BA_OK;
 }
 
 // ------------------------------------------------------------------------------------------------- similarity

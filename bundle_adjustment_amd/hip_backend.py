@@ -110,6 +110,11 @@ class BARansacOptions(C.Structure):
                 ("write_cams", C.c_int32), ("max_rms_px", C.c_double), ("min_depth", C.c_double)]
 
 
+class BARelposeOptions(C.Structure):
+    _fields_ = [("n_hyp", C.c_int32), ("lo_rounds", C.c_int32), ("seed", C.c_uint64), ("max_epi_px", C.c_double),
+                ("refine_iters", C.c_int32), ("min_inliers", C.c_int32), ("min_parallax_deg", C.c_double), ("max_depth", C.c_double)]
+
+
 class BASimilarity(C.Structure):
     _fields_ = [("s", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3)]
 
@@ -126,6 +131,7 @@ ALIGN_STATUS = {"ok": 0, "too_few": 1, "degenerate": 2}   # enum ba_align_status
 TRACK_STATUS = {"ok": 0, "few_views": 1, "degenerate": 2, "behind": 3, "low_angle": 4, "high_error": 5}   # enum ba_track_status
 RESECT_STATUS = {"ok": 0, "few_points": 1, "degenerate": 2, "behind": 3, "few_inliers": 4, "high_error": 5}   # enum ba_resect_status
 RESECT_INIT = {"dlt": 0, "current": 1}   # enum ba_resect_init
+RELPOSE_STATUS = {"ok": 0, "few_matches": 1, "degenerate": 2, "behind": 3, "few_inliers": 4, "low_parallax": 5}   # enum ba_relpose_status
 
 
 def resect_init_code(init):
@@ -186,6 +192,9 @@ SYMBOLS = {
     "ba_default_ransac_options": (C.c_int, [C.POINTER(BARansacOptions)]),
     "ba_resect_ransac": (C.c_int, [C.c_void_p, _DP, C.POINTER(BARansacOptions), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _DP,
                                    C.POINTER(C.c_uint8), _IP, _DP, _DP, C.POINTER(C.c_uint8)]),
+    "ba_default_relpose_options": (C.c_int, [C.POINTER(BARelposeOptions)]),
+    "ba_relative_pose": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.POINTER(C.c_int64), _DP, _DP, C.POINTER(BARelposeOptions), _DP, _DP,
+                                   C.POINTER(C.c_uint8), _IP, _DP, _DP, _IP, C.POINTER(C.c_uint8)]),
     "ba_get_centres": (C.c_int, [C.c_void_p, _DP]),
     "ba_transform": (C.c_int, [C.c_void_p, C.POINTER(BASimilarity)]),
     "ba_default_align_options": (C.c_int, [C.POINTER(BAAlignOptions)]),
@@ -693,6 +702,38 @@ class Solver:
         inl = np.zeros(self.n_obs, dtype=np.uint8)
         _check(self._lib.ba_resect_ransac(self._h, ip, C.byref(o), selp, knownp, *outp, inl.ctypes.data_as(C.POINTER(C.c_uint8))))
         out["obs_inlier"] = inl.astype(bool)
+        return out
+
+    def relpose_options(self, **kw) -> BARelposeOptions:
+        """ba_default_relpose_options overlaid with kw (any ba_relpose_options field; an unknown one raises TypeError)."""
+        return _options(BARelposeOptions, self._lib.ba_default_relpose_options, kw, names={})
+
+    def relative_pose(self, K, pts1, pts2, pair_off=None, **opts):
+        """ba_relative_pose: R | t (x2 ~ K (R x1 + t), |t| = 1) of every pair from raw pixel matches -- n_hyp five-point samples
+        per pair scored on all of its matches, then lo_rounds of (consensus, refinement).  pts1 / pts2 (n, 2) pixels; pair_off
+        (n_pairs + 1,) offsets into them (None: one pair of all matches).  opts: n_hyp, lo_rounds, seed, max_epi_px,
+        refine_iters, min_inliers, min_parallax_deg, max_depth.  Returns dict(R (P, 3, 3), t (P, 3), status (P,) uint8
+        (RELPOSE_STATUS), n_inliers, rms_px, parallax_deg, best_hyp (P,), match_inlier (n,) bool).  Needs no problem and
+        leaves a resident one as it is."""
+        Km = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
+        p1 = np.ascontiguousarray(pts1, dtype=np.float64).reshape(-1, 2)
+        p2 = np.ascontiguousarray(pts2, dtype=np.float64).reshape(-1, 2)
+        if p1.shape[0] != p2.shape[0]:
+            raise ValueError("pts1 and pts2 must list the same number of points")
+        off = np.array([0, p1.shape[0]], dtype=np.int64) if pair_off is None else np.ascontiguousarray(pair_off, dtype=np.int64).ravel()
+        if off.size < 1 or (off.size > 1 and off[-1] != p1.shape[0]):
+            raise ValueError("pair_off must have n_pairs + 1 entries and end at the number of matches")
+        o = self.relpose_options(**opts)
+        P, n = off.size - 1, p1.shape[0]
+        out = dict(R=np.empty((P, 3, 3)), t=np.empty((P, 3)), status=np.empty(P, dtype=np.uint8), n_inliers=np.empty(P, dtype=np.int32),
+                   rms_px=np.empty(P), parallax_deg=np.empty(P), best_hyp=np.empty(P, dtype=np.int32))
+        inl = np.zeros(n, dtype=np.uint8)
+        u8 = C.POINTER(C.c_uint8)
+        _check(self._lib.ba_relative_pose(self._h, _dp(Km), P, off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(p1), _dp(p2), C.byref(o),
+                                          _dp(out["R"]), _dp(out["t"]), out["status"].ctypes.data_as(u8), out["n_inliers"].ctypes.data_as(_IP),
+                                          _dp(out["rms_px"]), _dp(out["parallax_deg"]), out["best_hyp"].ctypes.data_as(_IP),
+                                          inl.ctypes.data_as(u8)))
+        out["match_inlier"] = inl.astype(bool)
         return out
 
     def centres(self):

@@ -341,6 +341,71 @@ typedef struct ba_ransac_options {
 int ba_default_ransac_options(ba_ransac_options* opts);   /* 256, 2, 0, 4.0, linear, 20, 1.0, 6, 0, 0.0, 0.0 */
 int ba_resect_ransac(ba_handle* h, const double* intr, const ba_ransac_options* opts, const uint8_t* cam_sel, const uint8_t* pt_known,
                      double* poses, uint8_t* status, int32_t* n_inliers, double* rms_px, double* max_px, uint8_t* obs_inlier);
+/* Two-view relative pose: R | t of the second view against the first from raw pixel matches, a share of which may be wrong (the
+ * reference's estimate_pose: cv2.findEssentialMat(RANSAC, 0.999, 3.0) then cv2.recoverPose).  Convention x2 ~ K (R x1 + t), P1 =
+ * K [I | 0], |t| = 1: what comes back goes straight into ba_triangulate.  Needs no ba_set_problem and leaves a resident problem
+ * untouched; the staging buffers live on the handle and are reused.  n_pairs pairs in one call; pair p owns the matches
+ * pair_off[p] .. pair_off[p + 1] - 1 of pts1 / pts2 (double[.][2], pixels).  K is the pinhole matrix (fx, fy > 0, no skew, last row
+ * 0 0 1), shared by both views and all pairs; users of the BAL camera pass undistorted bearings with K = I and max_epi_px in
+ * normalised units.  Outputs, any of them NULL: R double[n_pairs][9] row-major, t double[n_pairs][3], status uint8
+ * (ba_relpose_status), n_inliers, rms_px, parallax_deg, best_hyp int32 (the winning hypothesis, -1 when there is none),
+ * match_inlier uint8[pair_off[n_pairs]].  n_pairs = 0 is a no-op.
+ * Per pair with n matches:
+ * (0) x~ = ((u - cx) / fx, (v - cy) / fy, 1) in both views; fbar = (fx + fy) / 2, thr = max_epi_px / fbar.
+ * (1) n < 6: FEW_MATCHES (five matches reproduce themselves; a sixth chooses among the solutions); R = I, t = 0.
+ * (2) Hypothesis h = 0 .. n_hyp - 1 draws five distinct indices with ba_resect_ransac's generator: k = mix(mix(mix(seed + G) +
+ * pair) + h), draw_d = mix(k + (d + 1) G) for d = 0 .. 4, i_d = floor(draw_d (n - d) / 2^64), then i_d is raised by one for each
+ * earlier index that is <= it, the earlier indices taken in ascending order.  A pure function of (seed, pair index in the
+ * call, h, n); nothing is retried.
+ * (3) Five-point solver (Nister 2004, the polynomial route, fp64).  The rows kron((x2~), (x1~)) form A (5 x 9); Gauss-Jordan, the
+ * pivot of each row its largest entry among the columns not used yet, gives the null-space basis N0 .. N3 (free column k: N_k = 1
+ * there, minus the reduced row entries at the pivot columns), E = x N0 + y N1 + z N2 + N3; a pivot <= 1e-12 times the largest
+ * entry of A voids the hypothesis.  The nine entries of E E^T E - tr(E E^T) E / 2 and det E are ten cubics in (x, y, z), a 10 x 20
+ * matrix with the columns x3 y3 x2y xy2 x2z x2 y2z y2 xyz xy | xz2 xz x yz2 yz y z3 z2 z 1, built by polynomial products;
+ * Gauss-Jordan on the first ten columns with row pivoting (a pivot <= 1e-12 of the column's largest magnitude over the ten rows:
+ * void).  Rows 4 - z 5, 6 - z 7, 8 - z 9 form B(z), 3 x 3 on (x, y, 1), degrees 3, 3, 4; det B(z) has degree 10.  Its real roots
+ * inside the Cauchy bound B = 1 + max |c_i / c_10| (not finite: void): the roots of each derivative, from the ninth down, split
+ * [-B, B] into intervals of which every one with a sign change is bisected 64 times; then two Newton steps on the polynomial,
+ * kept inside the bracket.  At most ten roots, numbered by ascending z: the slot.  Per root (x, y, 1) is the longest cross
+ * product of two rows of B(z) (third component 0: void slot), polished by two Gauss-Newton steps of (x, y, z) on the ten
+ * eliminated rows (3 x 3 normal equations); E has unit Frobenius norm; a non-finite entry voids the slot.
+ * (4) Every E is scored on all n matches: sum of min(r^2, thr^2), r = x2~^T E x1~ / sqrt((E x1~)_0^2 + (E x1~)_1^2 + (E^T x2~)_0^2
+ * + (E^T x2~)_1^2) (Sampson), a zero denominator costs thr^2.  The lowest (cost, 10 h + slot) wins, ties go to the lower key.
+ * Every slot void: DEGENERATE, R = I, t = 0, 0 inliers, NaN measures, best_hyp = -1.
+ * (5) E = U diag V^T (one-sided Jacobi; u3 = u1 x u2, v3 = v1 x v2, so det U = det V = +1).  R_a = U W V^T, R_b = U W^T V^T, W =
+ * [0 -1 0; 1 0 0; 0 0 1], t = +-u3; candidates (R_a, +t), (R_a, -t), (R_b, +t), (R_b, -t).  The depths of lambda2 x2~ = lambda1 R
+ * x1~ + t in least squares (2 x 2; none when the Gram determinant is <= 1e-24 |a|^2 |b|^2).  The matches with |r| <= thr at the
+ * winning E vote for every candidate that puts both depths in (0, max_depth]; most votes win, ties go to the lower number; no
+ * vote at all: BEHIND with candidate 0 and its measures.  (Matches of a pure rotation have no finite depth: BEHIND unless
+ * max_depth <= 0.)
+ * (6) lo_rounds times: the consensus set = the matches with |r| <= thr and both depths in range at the round's starting pose, r
+ * from E = [t]x R; an empty set ends the rounds.  Then at most refine_iters Marquardt-damped Gauss-Newton steps on 0.5 sum r^2
+ * over the set in five local parameters, R <- exp([w]x) R, t <- normalise(t + tau1 b1 + tau2 b2), b1 = normalise(e_k x t) with k the
+ * index of the smallest |t_k|, b2 = t x b1; analytic Jacobian; damping, acceptance and lambda limits as ba_resect's step (3); |dx| <=
+ * 1e-14 ends it; a 5 x 5 Cholesky pivot <= 0: DEGENERATE with the last accepted pose and its measures.
+ * (7) At the final pose: match_inlier = |r| <= thr with both depths in range, n_inliers their count, rms_px = fbar sqrt(mean r^2)
+ * and parallax_deg = the mean angle between R x1~ and x2~ over them (NaN without inliers).  Status: the first failing test in
+ * enum order; FEW_INLIERS: n_inliers < min_inliers; LOW_PARALLAX: min_parallax_deg > 0 and parallax_deg below it.
+ * BA_ERR_INVALID, naming the field: K not as above, n_pairs outside 0 .. 65535, n_hyp outside 1 .. 4096, lo_rounds < 0, max_epi_px
+ * not > 0, refine_iters < 0, min_inliers < 0, pair_off[0] != 0, a decreasing pair_off.  Results are bit-reproducible from call
+ * to call, and a pair's result depends on its index in the call (the samples) but not on the other pairs.  Local to the rank. */
+enum ba_relpose_status { BA_RELPOSE_OK = 0, BA_RELPOSE_FEW_MATCHES = 1, BA_RELPOSE_DEGENERATE = 2,
+                         BA_RELPOSE_BEHIND = 3, BA_RELPOSE_FEW_INLIERS = 4, BA_RELPOSE_LOW_PARALLAX = 5 };
+typedef struct ba_relpose_options {
+  int32_t  n_hyp;            /* minimal samples per pair, 1 .. 4096; default 256 */
+  int32_t  lo_rounds;        /* rounds of (consensus, refinement); default 2; 0 = the best raw hypothesis, decomposed */
+  uint64_t seed;             /* default 0 */
+  double   max_epi_px;       /* Sampson threshold in pixels, > 0; default 3.0 (the reference's) */
+  int32_t  refine_iters;     /* per round; default 20 */
+  int32_t  min_inliers;      /* default 8 */
+  double   min_parallax_deg; /* <= 0: no test; default 0 */
+  double   max_depth;        /* a match votes / is in front when both depths are in (0, max_depth], unit = |t| = 1;
+                                <= 0: no upper limit; default 50 (cv2.recoverPose's distanceThresh) */
+} ba_relpose_options;
+int ba_default_relpose_options(ba_relpose_options* opts);   /* 256, 2, 0, 3.0, 20, 8, 0.0, 50.0 */
+int ba_relative_pose(ba_handle* h, const double K[9], int32_t n_pairs, const int64_t* pair_off, const double* pts1, const double* pts2,
+                     const ba_relpose_options* opts, double* R, double* t, uint8_t* status, int32_t* n_inliers, double* rms_px,
+                     double* parallax_deg, int32_t* best_hyp, uint8_t* match_inlier);
 /* Similarity transform of the reconstruction and robust alignment to reference positions: the step after an adjustment that
  * moves the result into the frame its user needs (georegistration onto GPS / surveyed camera positions or ground-control
  * points -- COLMAP's model_aligner; the comparison of two gauge-free solves; re-centring / re-scaling).  No reference
