@@ -491,8 +491,9 @@ int ba_set_problem(ba_handle* h, int32_t n_cams, int32_t n_pts, int64_t n_obs,
  * as reported by ba_linearize*, identity ones in the damped system, ba_schur_system's S and the preconditioner, and a zero
  * right-hand side (ba_schur_system's g) and step.  A held point keeps its observations: they enter the cost and the cameras'
  * blocks.  The stopping tests see the free parameters only (gtol: max |g| over free entries; xtol: |x| and |dx| over free
- * entries).  fixed_cam holds its camera in addition to the masks.  The masks belong to the handle: they survive
- * ba_set_params and repeated solves; ba_set_problem clears them, and so does ba_set_held(h, NULL, NULL).
+ * entries).  fixed_cam holds its camera in addition to the masks; its block, unlike the masks' entries, keeps its share of
+ * xtol's |x| (with or without masks: |x| of a solve with fixed_cam alone counts every camera).  The masks belong to the
+ * handle: they survive ba_set_params and repeated solves; ba_set_problem clears them, and so does ba_set_held(h, NULL, NULL).
  * Bits 9-15 are refused here; bits 6-8 by the pinhole solve / linearisation that meets them (BA_ERR_INVALID).
  * Multi-rank jobs: cam_held covers ALL cameras and must be the same on every rank (the caller's obligation); pt_held is
  * per shard, in the shard's local point order. */

@@ -405,12 +405,15 @@ class SchurOperator:
         return -np.einsum('pij,pj->pi', self.Hppinv, self.bp + u)
 
 
-def pcg(op, rhs, Minv, tol, max_iters, min_iters=0, model_tol=0.0, model_min_iters=5):
+def pcg(op, rhs, Minv, tol, max_iters, min_iters=0, model_tol=0.0, model_min_iters=5, info=None):
     """Preconditioned CG on S x = rhs with block-Jacobi Minv (Nc,6,6), or any callable r -> M^-1 r.
     Stops when sqrt(rz / rz0) <= tol (after min_iters), at max_iters, or -- model_tol > 0 -- by Nash & Sofer's
     truncated-Newton test on the quadratic model q(x) = 1/2 x^T S x - rhs^T x that CG minimises: iteration i lowers q by
     1/2 alpha_i (r.z)_{i-1}; stop after iteration i >= model_min_iters when i times that is <= model_tol of the whole decrease
-    (the device: ba_options.pcg_model_tol, k_pcg_step).  Returns x (Nc,6), iterations, final residual vector."""
+    (the device: ba_options.pcg_model_tol, k_pcg_step).  Returns x (Nc,6), iterations, final residual vector.
+    info (a dict, optional) receives how the loop ended: 'stop' ('residual', 'model', 'cap', 'curvature' or 'zero_rhs') and
+    'ratio_prev', 'ratio_last' = sqrt(rz / rz0) / tol after the last but one and the last iteration (the residual test stops
+    at the first ratio <= 1; ratio_prev is 1 / tol where there was one iteration only)."""
     if not callable(Minv):
         blocks = Minv
         Minv = lambda r_: np.einsum('cij,cj->ci', blocks, r_)          # noqa: E731
@@ -422,12 +425,17 @@ def pcg(op, rhs, Minv, tol, max_iters, min_iters=0, model_tol=0.0, model_min_ite
     rz0 = rz
     it = 0
     q_tot = 0.0
+    ratios = [1.0 / tol if tol > 0 else np.inf]
+    stop = 'cap'
+    if info is not None:
+        info.update(stop='zero_rhs', ratio_prev=np.inf, ratio_last=np.inf)
     if rz0 <= 0:
         return x, 0, r
     while it < max_iters:
         q = op.apply(p)
         pq = float((p * q).sum())
         if not (pq > 0):
+            stop = 'curvature'
             break
         alpha = rz / pq
         x += alpha * p
@@ -437,15 +445,20 @@ def pcg(op, rhs, Minv, tol, max_iters, min_iters=0, model_tol=0.0, model_min_ite
         it += 1
         dq = 0.5 * alpha * rz
         q_tot += dq
+        ratios.append(np.sqrt(max(rz_new, 0.0) / rz0) / tol if tol > 0 else np.inf)
         if it >= min_iters and rz_new <= tol * tol * rz0:
             rz = rz_new
+            stop = 'residual'
             break
         if model_tol > 0 and it >= model_min_iters and it * dq <= model_tol * q_tot:
             rz = rz_new
+            stop = 'model'
             break
         beta = rz_new / rz
         rz = rz_new
         p = z + beta * p
+    if info is not None:
+        info.update(stop=stop, ratio_prev=ratios[-2] if len(ratios) > 1 else np.inf, ratio_last=ratios[-1])
     return x, it, r
 
 
@@ -467,7 +480,7 @@ def band_structured(cam_idx, pt_idx, n_cams):
 def lm_solve(cams, pts, cam_idx, pt_idx, uv, K4, fixed_cam=-1, loss='linear',
              max_iters=50, ftol=1e-10, xtol=1e-10, gtol=1e-10, lam0=1e-4,
              pcg_tol=1e-1, pcg_max_iters=200, precond='schur_jacobi', verbose=False, linear_solver='pcg', model='pinhole',
-             pcg_model_tol=-1.0, pcg_model_min_iters=5, precond_lag=3, cap_floor=True):
+             pcg_model_tol=-1.0, pcg_model_min_iters=5, precond_lag=3, cap_floor=True, mutate=None, held_cam=None, held_pt=None):
     """CPU mirror of the device LM / Schur / PCG loop (same formulas, same update
     rules, same stopping tests) -- see ba_solve in bundle_adjustment_amd/csrc/ba_hip.hip.
     precond_lag (Schur-Jacobi only; the device's ba_options.precond_lag, same default and same rule): up to that many
@@ -478,8 +491,18 @@ def lm_solve(cams, pts, cam_idx, pt_idx, uv, K4, fixed_cam=-1, loss='linear',
     single-launch solver for window-sized problems does (csrc/ba_small.hpp).
     model='bal': the 9-parameter BAL camera [rvec | t | f k1 k2] (bal_residuals, bal_normal_equations; K4 is ignored) --
     the mirror of ba_solve_bal (the BalCam instantiation of the loop, csrc/ba_models.hpp); same loop, 9x9 camera blocks.
-    Returns dict(cams, pts, iterations, accepted, sse0, sse, cost0, cost, pcg_iters,
-    history)."""
+    held_cam (Nc, nb) bool / held_pt (Np,) bool: parameters kept constant (ba_set_held; fixed_cam's block is added to
+    held_cam).  Their columns leave the normal equations, the damped system is HeldSchur's, and -- include/ba_hip.h, "the
+    stopping tests see the free parameters only" -- gtol, |x| and |dx| of xtol run over the entries the masks leave free
+    (fixed_cam's block, a constant, stays in |x| with or without masks: every solver of the library counts it).
+    mutate (tests of the tests: each is a fault of the driver that still converges): 'model_half' -- the model decrease
+    without its factor 0.5; 'gtd_points' -- the points' share of g^T d left out; 'nu_kept' -- nu not back at 2 after an
+    accepted step; 'no_floor' -- the damping floor of capped inner solves ignored.
+    Each history record: it, cost, cost_new, lam, rho, pcg, step, and what the stopping tests saw -- gmax (max |g|), xnorm
+    (|x|), pcg_stop / pcg_ratio_prev / pcg_ratio_last (pcg's info).
+    Returns dict(cams, pts, iterations, accepted, sse0, sse, cost0, cost, pcg_iters, status, history, lam, gmax)."""
+    if mutate not in (None, 'model_half', 'gtd_points', 'nu_kept', 'no_floor'):
+        raise ValueError(f"unknown mutant {mutate!r}")
     nb = 9 if model == 'bal' else 6
     if pcg_model_tol < 0:           # the device's automatic default (ba_options.pcg_model_tol = -1): on for band-structured
         # problems solved to a loose outer tolerance (ftol >= 1e-6)
@@ -487,6 +510,15 @@ def lm_solve(cams, pts, cam_idx, pt_idx, uv, K4, fixed_cam=-1, loss='linear',
     cams = np.array(cams, dtype=np.float64).reshape(-1, nb)
     pts = np.array(pts, dtype=np.float64).reshape(-1, 3)
     lam, nu = lam0, 2.0
+    held = held_cam is not None or held_pt is not None
+    if held:
+        if linear_solver == 'dense':
+            raise ValueError("held parameters: the mirror has the matrix-free system only")
+        hc = np.zeros(cams.shape, bool) if held_cam is None else np.array(held_cam, bool).reshape(cams.shape)
+        hp = np.zeros(pts.shape[0], bool) if held_pt is None else np.array(held_pt, bool).reshape(pts.shape[0])
+        hx = hc.copy()                      # |x| of the xtol test: without the masks' entries; fixed_cam's block keeps its share
+        if fixed_cam >= 0:
+            hc[fixed_cam] = True
     if model == 'bal':
         def residuals(c_, p_, ci_, pi_, uv_, K4_):                       # noqa: F811  (shadows the pinhole residual)
             return bal_residuals(c_, p_, ci_, pi_, uv_)
@@ -505,14 +537,17 @@ def lm_solve(cams, pts, cam_idx, pt_idx, uv, K4, fixed_cam=-1, loss='linear',
     lag = precond_lag if (precond == 'schur_jacobi' and linear_solver != 'dense') else 0
     Minv_kept, lam_built, kept, pcg_at_build, pcg_last = None, 0.0, 0, -1, -1
     last_decrease, fresh = 1.0, True
+    gmax = float('nan')                 # max |g| of the last linearisation (returned: what a gtol exit saw)
     lam_floor = 0.0                     # cap-aware damping (ba_solve): 3 x the damping at which an inner solve last hit pcg_max_iters
     while it < max_iters:
         ne = normal_equations(cams, pts, cam_idx, pt_idx, uv, K4, fixed_cam, loss)
+        if held:
+            ne = hold_columns(ne, cam_idx, pt_idx, hc, hp)
         gmax = max(np.abs(ne['bc']).max(), np.abs(ne['bp']).max())
         if gmax <= gtol:
             status = 'gtol'
             break
-        op = SchurOperator(ne, cam_idx, pt_idx, lam, fixed_cam)
+        op = HeldSchur(ne, cam_idx, pt_idx, lam, hc, hp) if held else SchurOperator(ne, cam_idx, pt_idx, lam, fixed_cam)
         rhs = op.rhs()
         keep = (lag > 0 and Minv_kept is not None and kept < lag and lam <= 10.0 * lam_built and lam >= 0.1 * lam_built
                 and (pcg_at_build < 0 or pcg_last <= pcg_at_build + pcg_at_build // 2 + 2)
@@ -521,39 +556,47 @@ def lm_solve(cams, pts, cam_idx, pt_idx, uv, K4, fixed_cam=-1, loss='linear',
             Minv = Minv_kept
             kept += 1
         else:
-            D = op.Hccd.copy() if precond == 'jacobi' else op.schur_diag_blocks()
+            D = op.Hccd.copy() if precond == 'jacobi' else (op.schur_jacobi_blocks() if held else op.schur_diag_blocks())
             if fixed_cam >= 0:
                 D[fixed_cam] = np.eye(nb)
             Minv = np.linalg.inv(D)
             Minv_kept, lam_built, kept, pcg_at_build = (Minv if precond == 'schur_jacobi' else None), lam, 0, -1
+        pcg_info = {}
         if linear_solver == 'dense':
             S_, g_, _, _ = schur_dense(ne, cam_idx, pt_idx, lam, fixed_cam)
             dc, k, rfin = np.linalg.solve(S_, g_).reshape(-1, nb), 0, np.zeros_like(rhs)
         else:
-            dc, k, rfin = pcg(op, rhs, Minv, pcg_tol, pcg_max_iters, model_tol=pcg_model_tol, model_min_iters=pcg_model_min_iters)
+            dc, k, rfin = pcg(op, rhs, Minv, pcg_tol, pcg_max_iters, model_tol=pcg_model_tol, model_min_iters=pcg_model_min_iters,
+                              info=pcg_info)
         pcg_total += k
-        if cap_floor and linear_solver != 'dense' and k >= pcg_max_iters:
+        if cap_floor and mutate != 'no_floor' and linear_solver != 'dense' and k >= pcg_max_iters:
             lam_floor = max(lam_floor, 3.0 * lam)
         pcg_last = k
         if pcg_at_build < 0:
             pcg_at_build = k
-        dp = op.back_substitute(dc)
+        if held:                            # dp = -(Hpp + lam D)^-1 (bp + W^T dc), zero for a held point
+            dp = -np.einsum('pij,pj->pi', op.Hppinv, ne['bp'] + op._wt_times(op.W, dc))
+        else:
+            dp = op.back_substitute(dc)
         # model decrease of the damped, inexactly solved system (LM section)
         dcd = np.maximum(ne['Hcc'][:, np.arange(nb), np.arange(nb)], 1e-12)
         dpd = np.maximum(ne['Hpp'][:, np.arange(3), np.arange(3)], 1e-12)
         if fixed_cam >= 0:
             dcd[fixed_cam] = 0
-        gTd = float((ne['bc'] * dc).sum() + (ne['bp'] * dp).sum())
+        if held:
+            dcd[hc], dpd[hp] = 0, 0
+        gTd = float((ne['bc'] * dc).sum() + (0.0 if mutate == 'gtd_points' else (ne['bp'] * dp).sum()))
         dDd = float((dcd * dc * dc).sum() + (dpd * dp * dp).sum())
-        model = 0.5 * (lam * dDd - gTd + float((dc * rfin).sum()))
+        model = (1.0 if mutate == 'model_half' else 0.5) * (lam * dDd - gTd + float((dc * rfin).sum()))
         cams_new, pts_new = cams + dc, pts + dp
         res_new = residuals(cams_new, pts_new, cam_idx, pt_idx, uv, K4)
         cost_new = robust_cost(res_new, loss)
         rho = (cost - cost_new) / model if model > 0 else -1.0
         step = np.sqrt(float((dc * dc).sum() + (dp * dp).sum()))
-        xnorm = np.sqrt(float((cams * cams).sum() + (pts * pts).sum()))
+        xnorm = np.sqrt(float((cams[~hx] ** 2).sum() + (pts[~hp] ** 2).sum()) if held else float((cams * cams).sum() + (pts * pts).sum()))
         it += 1
-        hist.append(dict(it=it, cost=cost, cost_new=cost_new, lam=lam, rho=rho, pcg=k, step=step))
+        hist.append(dict(it=it, cost=cost, cost_new=cost_new, lam=lam, rho=rho, pcg=k, step=step, gmax=float(gmax), xnorm=xnorm,
+                         pcg_stop=pcg_info.get('stop'), pcg_ratio_prev=pcg_info.get('ratio_prev'), pcg_ratio_last=pcg_info.get('ratio_last')))
         if verbose:
             print(hist[-1])
         if rho > 0 and np.isfinite(cost_new):
@@ -564,7 +607,8 @@ def lm_solve(cams, pts, cam_idx, pt_idx, uv, K4, fixed_cam=-1, loss='linear',
             acc += 1
             lam = lam * max(1.0 / 3.0, 1.0 - (2.0 * rho - 1.0) ** 3)
             lam = max(lam, 1e-12, lam_floor)
-            nu = 2.0
+            if mutate != 'nu_kept':
+                nu = 2.0
             if dcost <= ftol * cost:
                 status = 'ftol'
                 break
@@ -578,7 +622,7 @@ def lm_solve(cams, pts, cam_idx, pt_idx, uv, K4, fixed_cam=-1, loss='linear',
     res = residuals(cams, pts, cam_idx, pt_idx, uv, K4)
     return dict(cams=cams, pts=pts, iterations=it, accepted=acc, sse0=sse0,
                 sse=float((res * res).sum()), cost0=cost0, cost=cost, pcg_iters=pcg_total,
-                status=status, history=hist, lam=lam)
+                status=status, history=hist, lam=lam, gmax=gmax)
 
 
 # ---------------------------------------------------------------------------
@@ -786,6 +830,21 @@ def inv3_batch(A):
     C[:, 2, 2] = a[:, 0, 0] * a[:, 1, 1] - a[:, 0, 1] * a[:, 1, 0]
     det = a[:, 0, 0] * C[:, 0, 0] + a[:, 0, 1] * C[:, 1, 0] + a[:, 0, 2] * C[:, 2, 0]
     return C / det[:, None, None]
+
+
+def hold_columns(ne, cam_idx, pt_idx, held_cam, held_pt):
+    """normal_equations' / bal_normal_equations' result with the held columns taken out: Jc columns where held_cam (Nc, nb),
+    Jp of the points where held_pt (Np,) -- zero rows and columns in Hcc | bc, Hpp = bp = 0 for a held point (ba_set_held)."""
+    Jc = ne['Jc'] * (~held_cam[cam_idx])[:, None, :]
+    Jp = ne['Jp'] * (~held_pt[pt_idx])[:, None, None]
+    res, w = ne['res'], ne['w']
+    Jcw, Jpw = Jc * w[:, :, None], Jp * w[:, :, None]
+    Hcc, Hpp, bc, bp = (np.zeros_like(ne[k]) for k in ('Hcc', 'Hpp', 'bc', 'bp'))
+    np.add.at(Hcc, cam_idx, np.einsum('nki,nkj->nij', Jcw, Jc))
+    np.add.at(Hpp, pt_idx, np.einsum('nki,nkj->nij', Jpw, Jp))
+    np.add.at(bc, cam_idx, np.einsum('nki,nk->ni', Jcw, res))
+    np.add.at(bp, pt_idx, np.einsum('nki,nk->ni', Jpw, res))
+    return dict(Hcc=Hcc, Hpp=Hpp, bc=bc, bp=bp, W=np.einsum('nki,nkj->nij', Jcw, Jp), res=res, w=w, Jc=Jc, Jp=Jp)
 
 
 class HeldSchur:

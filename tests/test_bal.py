@@ -10,6 +10,7 @@ import pytest
 from bundle_adjustment_amd.bal import BALProblem, from_pinhole, read_bal, to_pinhole, write_bal
 from oracle import ba_oracle as o
 from tests.helpers import GOLDEN
+from tests.lm_trace import check_self_consistent
 
 TINY = os.path.join(GOLDEN, "tiny_bal.txt")
 
@@ -195,6 +196,7 @@ def test_device_bal_solve_follows_the_oracle_lm(case, precond):
         out, cams, pts = s.solve_bal(p, fixed_cam=fixed, loss=loss, max_iters=iters, ftol=0.0, xtol=0.0, gtol=0.0, pcg_tol=1e-2,
                                      pcg_max_iters=300, pcg_min_iters=0, preconditioner=precond)
         tr = s.trace()
+    check_self_consistent(out, tr, dict(pcg_max_iters=300))
     assert out["iterations"] == iters == len(ref["history"])
     assert abs(out["initial_cost"] - ref["cost0"]) <= 1e-10 * ref["cost0"]
     compared = 0
@@ -312,6 +314,8 @@ def test_config5_bal_fp32_jacobian_mode_follows_the_fp64_descent():
         tr_ref = s.trace()
         out, cams, pts = s.solve_bal(p, jacobian_precision=1, **kw)
         tr_out = s.trace()
+    check_self_consistent(ref, tr_ref, kw)
+    check_self_consistent(out, tr_out, kw)
     # same verdicts while the steps still matter (past the noise floor accept / reject is decided by round-off)
     compared = 0
     for a, b in zip(tr_out, tr_ref):
@@ -342,7 +346,9 @@ def test_bal_fp32_jacobian_mode_reaches_the_fp64_solution():
     kw = dict(fixed_cam=0, loss="huber", max_iters=60, ftol=1e-12, xtol=1e-12, gtol=0.0, pcg_tol=1e-2, pcg_max_iters=400)
     with hip_backend.Solver(0) as s:
         a, ca, pa = s.solve_bal(p, **kw)
+        check_self_consistent(a, s.trace(), kw)
         b, cb, pb = s.solve_bal(p, jacobian_precision=1, **kw)
+        check_self_consistent(b, s.trace(), kw)
     assert abs(a["final_cost"] - b["final_cost"]) <= 1e-10 * a["final_cost"]
     # (only camera 0 is held: the scale of the scene is free, the minimiser is a one-parameter family and the two runs
     # stop at different members of it -- rotations, focal lengths and distortion are scale-free and agree)

@@ -13,6 +13,7 @@ from bundle_adjustment_amd import hip_backend
 from bundle_adjustment_amd.synthetic import make_bal_like, make_config, make_problem
 from oracle import ba_oracle as o
 from tests.helpers import golden_flat_problem, load_golden
+from tests.lm_trace import check_self_consistent
 
 pytestmark = pytest.mark.gpu
 
@@ -180,6 +181,7 @@ def test_solve_matches_cpu_mirror(solver, loss, precond):
     solver.set_problem(p)
     kw = dict(max_iters=40, ftol=1e-13, xtol=1e-13, gtol=0.0, pcg_tol=1e-4, pcg_max_iters=400)
     out = solver.solve(loss=loss, preconditioner=precond, **kw)
+    check_self_consistent(out, solver.trace(), kw)
     ref = o.lm_solve(p.cams, p.pts, p.cam_idx, p.pt_idx, p.uv, p.K4, 0, loss, precond=precond, **kw)
     assert abs(out["final_cost"] - ref["cost"]) <= 1e-9 * ref["cost"]
     cams, pts = solver.get_params()
@@ -209,6 +211,7 @@ def test_kept_preconditioner_blocks_follow_the_oracle_and_reach_the_same_minimis
             out = s.solve(loss=loss, precond_lag=lag, **kw)
             st1 = s.stats()
             res[lag] = (out, s.trace(), s.get_params(), {k: st1[k] - st0[k] for k in st1})
+            check_self_consistent(out, res[lag][1], kw)
     out, tr, (cams, pts), st = res[3]
     ref = o.lm_solve(p.cams, p.pts, p.cam_idx, p.pt_idx, p.uv, p.K4, 0, loss, precond_lag=3, **kw)
     assert st["precond_reuses"] >= 5 and st["precond_builds"] + st["precond_reuses"] == out["iterations"] == 25
@@ -418,6 +421,7 @@ def test_pcg_model_test_follows_the_oracle(solver):
     solver.set_problem(p)
     out = solver.solve(loss="huber", initial_lambda=1e-7, pcg_model_tol=0.5, pcg_min_iters=0, **kw)
     tr = solver.trace()
+    check_self_consistent(out, tr, dict(kw, initial_lambda=1e-7))
     assert out["iterations"] == len(ref["history"])
     for t, h in zip(tr, ref["history"]):
         assert abs(t["pcg_iterations"] - h["pcg"]) <= max(1, 0.1 * h["pcg"]), (t, h)
@@ -438,6 +442,7 @@ def test_camera_windows_that_do_not_fit_in_lds_follow_the_oracle(solver):
     ref = o.lm_solve(p.cams, p.pts, p.cam_idx, p.pt_idx, p.uv, p.K4, fixed_cam=0, loss="huber", **kw)
     out = solver.solve(loss="huber", pcg_min_iters=0, **kw)
     tr = solver.trace()
+    check_self_consistent(out, tr, kw)
     assert out["iterations"] == len(ref["history"]) == 5
     for t, h in zip(tr, ref["history"]):
         assert abs(t["pcg_iterations"] - h["pcg"]) <= max(1, 0.1 * h["pcg"]), (t, h)
@@ -468,6 +473,7 @@ def test_chain_with_long_tracks_and_camera_windows_follows_the_oracle(monkeypatc
         assert np.abs(r - o.residuals(p.cams, p.pts, p.cam_idx, p.pt_idx, p.uv, p.K4)).max() <= 1e-9
         out = s.solve(loss="huber", pcg_min_iters=0, **kw)
         tr = s.trace()
+    check_self_consistent(out, tr, kw)
     assert out["iterations"] == len(ref["history"]) == 3
     for t, h in zip(tr, ref["history"]):
         assert abs(t["pcg_iterations"] - h["pcg"]) <= max(1, 0.1 * h["pcg"]), (t, h)

@@ -9,6 +9,7 @@ import pytest
 
 from bundle_adjustment_amd import hip_backend
 from bundle_adjustment_amd.synthetic import make_problem
+from tests.lm_trace import check_self_consistent
 
 pytestmark = pytest.mark.gpu
 
@@ -22,6 +23,7 @@ def _solve(p, monkeypatch, riders, **kw):
         trace = s.trace()
         out["cap_floor_raises"] = s.stats()["cap_floor_raises"]
         out["kernels"] = s.profile(reset=True)
+    check_self_consistent(out, trace, kw)
     return out, cams, pts, trace
 
 

@@ -11,6 +11,7 @@ from bundle_adjustment_amd import hip_backend
 from bundle_adjustment_amd.synthetic import make_problem
 from oracle import ba_oracle as o
 from tests.helpers import golden_flat_problem, load_golden
+from tests.lm_trace import check_self_consistent
 
 pytestmark = pytest.mark.gpu
 TIGHT = dict(max_iters=60, ftol=1e-14, xtol=1e-14, gtol=0.0)
@@ -105,6 +106,7 @@ def test_small_solver_follows_the_oracles_dense_lm_step_by_step(n_cams, n_pts, k
         out = s.solve(loss=loss, max_iters=iters, ftol=0.0, xtol=0.0, gtol=0.0)
         tr = s.trace()
         cams, pts = s.get_params()
+    check_self_consistent(out, tr, {})
     assert out["pcg_iterations"] == 0 and out["iterations"] == iters == len(ref["history"])
     for t, h in zip(tr, ref["history"]):
         assert abs(t["cost"] - h["cost"]) <= 1e-9 * h["cost"]
