@@ -42,6 +42,7 @@
 #include "ba_resect.hpp"
 #include "ba_ransac.hpp"
 #include "ba_relpose.hpp"
+#include "ba_match.hpp"
 
 using namespace ba;
 
@@ -291,6 +292,14 @@ struct ba_handle {
   DBuf<long long> rp_off;
   DBuf<unsigned> rp_mask;
   DBuf<unsigned char> rp_cons, rp_inl;
+  // ba_match_descriptors (ba_match.hpp): staging of the call -- every set's descriptors, the pair table, the splits' (k1, k2),
+  // best | second | dist1 | dist2 by row, the good bytes, the per-pair counts
+  DBuf<unsigned long long> mt_desc;
+  DBuf<MatchPair> mt_pairs;
+  DBuf<uint2> mt_part;
+  DBuf<int> mt_out, mt_ngood;
+  DBuf<unsigned char> mt_good;
+  int debug_match_splits = 0;  // BA_DEBUG_MATCH_SPLITS: train splits asked for per pair instead of match_plan's own choice (tests)
   // ba_transform / ba_align / ba_get_centres (ba_similarity.hpp): correspondences a | b | w | u | err (9 doubles each), the
   // per-workgroup partial rows, the device record (similarity, centroids, status)
   DBuf<double> sim_buf, sim_part;
@@ -446,6 +455,7 @@ static int create_impl(ba_handle* h, int device_id) {
 #undef BA_BIG_LDS_LIN
 #undef BA_BIG_LDS
   if (const char* e = getenv("BA_DEBUG_LDS_EXTRA")) h->debug_lds_extra = atoi(e);
+  if (const char* e = getenv("BA_DEBUG_MATCH_SPLITS")) h->debug_match_splits = atoi(e);
   return BA_OK;
 }
 extern "C" int ba_destroy(ba_handle* h);
@@ -3686,6 +3696,127 @@ extern "C" int ba_relative_pose(ba_handle* h, const double K[9], int32_t n_pairs
       if (parallax_deg) parallax_deg[p] = r[15];
       if (best_hyp) best_hyp[p] = (int32_t)r[16];
     }
+  return BA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- descriptor matching
+// ba_match_descriptors (csrc/ba_match.hpp): Hamming 2-NN of every pair, ratio / distance / mutual tests.  Needs no problem.
+static_assert(sizeof(ba_match_options) == 16, "ba_match_options (include/ba_hip.h)");
+extern "C" int ba_default_match_options(ba_match_options* o) {
+  if (!o) return fail(BA_ERR_INVALID, "null argument");
+  memset(o, 0, sizeof *o);
+  o->ratio = 0.75;
+  o->max_distance = -1;
+  return BA_OK;
+}
+// Train splits of one entry.  `want` splits are asked for (the call-wide wish, or the test hook's number); a split is whole
+// tiles and at least MT_MIN_SPLIT descriptors unless it is the whole set; at most MT_MAX_SPLITS.
+static void match_plan(MatchPair& e, int want) {
+  if (e.nt == 0 || e.nq == 0) { e.split_len = MT_TILE; e.n_splits = 0; return; }   // nothing to launch for the entry
+  const int tiles = (e.nt + MT_TILE - 1) / MT_TILE;
+  const int n = std::max(1, std::min({want, MT_MAX_SPLITS, tiles / (MT_MIN_SPLIT / MT_TILE)}));
+  e.split_len = (tiles + n - 1) / n * MT_TILE;
+  e.n_splits = (e.nt + e.split_len - 1) / e.split_len;
+}
+template <int W>
+static void launch_match_partial(ba_handle* h, dim3 grid, const MatchArgs& a) {
+  BA_LAUNCH(k_match_partial<W>, grid, dim3(MT_THREADS), 0, h->stream, a);
+}
+extern "C" int ba_match_descriptors(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc,
+                                    int32_t n_pairs, const int32_t* pair_query, const int32_t* pair_train, const ba_match_options* opts,
+                                    int64_t* row_off, int32_t* best, int32_t* second, int32_t* dist1, int32_t* dist2,
+                                    uint8_t* good, int32_t* n_good) {
+  if (!h || !opts) return fail(BA_ERR_INVALID, "null argument");
+  if (desc_bytes < 8 || desc_bytes > 8 * MT_MAX_WORDS || desc_bytes % 8 != 0)
+    return fail(BA_ERR_INVALID, "ba_match_descriptors: desc_bytes %d is not a multiple of 8 in 8 .. %d", desc_bytes, 8 * MT_MAX_WORDS);
+  if (n_sets < 0 || n_sets > 65535) return fail(BA_ERR_INVALID, "ba_match_descriptors: n_sets %d is outside 0 .. 65535", n_sets);
+  if (n_pairs < 0 || n_pairs > 65535) return fail(BA_ERR_INVALID, "ba_match_descriptors: n_pairs %d is outside 0 .. 65535", n_pairs);
+  if (!std::isfinite(opts->ratio)) return fail(BA_ERR_INVALID, "ba_match_descriptors: ratio must be finite");
+  if (!set_off) return fail(BA_ERR_INVALID, "ba_match_descriptors: null set_off");
+  if (set_off[0] != 0) return fail(BA_ERR_INVALID, "ba_match_descriptors: set_off[0] must be 0");
+  for (int32_t s = 0; s < n_sets; ++s) {
+    if (set_off[s + 1] < set_off[s]) return fail(BA_ERR_INVALID, "ba_match_descriptors: set_off decreases at set %d", s);
+    if (set_off[s + 1] - set_off[s] > (1LL << MT_IDX_BITS))
+      return fail(BA_ERR_INVALID, "ba_match_descriptors: set_off: set %d holds %lld descriptors, more than %d", s,
+                  (long long)(set_off[s + 1] - set_off[s]), 1 << MT_IDX_BITS);
+  }
+  const size_t n_desc = (size_t)set_off[n_sets], np = (size_t)n_pairs, W = (size_t)desc_bytes / 8;
+  if (n_desc > 0 && !desc) return fail(BA_ERR_INVALID, "ba_match_descriptors: null desc");
+  if (n_pairs > 0 && !pair_query) return fail(BA_ERR_INVALID, "ba_match_descriptors: null pair_query");
+  if (n_pairs > 0 && !pair_train) return fail(BA_ERR_INVALID, "ba_match_descriptors: null pair_train");
+  for (int32_t p = 0; p < n_pairs; ++p) {
+    if (pair_query[p] < 0 || pair_query[p] >= n_sets)
+      return fail(BA_ERR_INVALID, "ba_match_descriptors: pair_query[%d] = %d is outside 0 .. n_sets - 1", p, pair_query[p]);
+    if (pair_train[p] < 0 || pair_train[p] >= n_sets)
+      return fail(BA_ERR_INVALID, "ba_match_descriptors: pair_train[%d] = %d is outside 0 .. n_sets - 1", p, pair_train[p]);
+  }
+  // the pair table: the call's pairs, then (mutual) the same pairs with the roles swapped
+  const bool mutual = opts->mutual != 0;
+  std::vector<MatchPair> tab((mutual ? 2 : 1) * np);
+  long long rows = 0, wave_rows = 0;
+  int max_qb = 0, max_splits = 0;
+  for (size_t p = 0; p < np; ++p) {
+    MatchPair& e = tab[p];
+    e.q0 = set_off[pair_query[p]]; e.nq = (int)(set_off[pair_query[p] + 1] - e.q0);
+    e.t0 = set_off[pair_train[p]]; e.nt = (int)(set_off[pair_train[p] + 1] - e.t0);
+    e.row0 = rows;
+    if (row_off) row_off[p] = rows;
+    rows += e.nq;
+    wave_rows += (e.nq + 63) / 64;
+    if (mutual) {
+      MatchPair& r = tab[np + p];
+      r.q0 = e.t0; r.nq = e.nt; r.t0 = e.q0; r.nt = e.nq; r.row0 = 0;
+      wave_rows += (r.nq + 63) / 64;
+    }
+  }
+  if (row_off) row_off[np] = rows;
+  if (n_good) memset(n_good, 0, np * sizeof(int32_t));
+  if (rows == 0) return BA_OK;     // no query anywhere: nothing to compute, and every output is already well-formed
+  if (set_device(h)) return BA_ERR_HIP;
+  // two waves per SIMD over the whole call: want = ceil(8 n_cu / wave rows of the call)
+  const long long target = 8LL * h->n_cu;
+  const int want = h->debug_match_splits > 0 ? h->debug_match_splits : (int)std::min<long long>(MT_MAX_SPLITS, (target + wave_rows - 1) / wave_rows);
+  long long n_part = 0;
+  for (MatchPair& e : tab) {
+    match_plan(e, want);
+    e.part0 = n_part;
+    n_part += (long long)e.nq * e.n_splits;
+    if (e.n_splits > 0) max_qb = std::max(max_qb, (e.nq + MT_THREADS - 1) / MT_THREADS);
+    max_splits = std::max(max_splits, e.n_splits);
+  }
+  const size_t nr = (size_t)rows;
+  HIPCHECK(h->mt_desc.alloc(n_desc * W)); HIPCHECK(h->mt_pairs.alloc(tab.size())); HIPCHECK(h->mt_part.alloc(std::max<size_t>((size_t)n_part, 1)));
+  HIPCHECK(h->mt_out.alloc(4 * nr)); HIPCHECK(h->mt_good.alloc(nr)); HIPCHECK(h->mt_ngood.alloc(np));
+  MatchArgs a = {};
+  a.desc = h->mt_desc.p; a.pairs = h->mt_pairs.p; a.part = h->mt_part.p;
+  a.n_pairs = n_pairs; a.mutual = mutual ? 1 : 0; a.max_distance = opts->max_distance; a.ratio = opts->ratio;
+  a.best = h->mt_out.p; a.second = h->mt_out.p + nr; a.dist1 = h->mt_out.p + 2 * nr; a.dist2 = h->mt_out.p + 3 * nr;
+  a.good = h->mt_good.p; a.n_good = h->mt_ngood.p;
+  HIPCHECK(hipMemcpyAsync(h->mt_desc.p, desc, n_desc * (size_t)desc_bytes, hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(h->mt_pairs.p, tab.data(), tab.size() * sizeof(MatchPair), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemsetAsync(h->mt_ngood.p, 0, np * sizeof(int), h->stream));
+  if (max_splits > 0) {
+    const dim3 grid((unsigned)tab.size(), (unsigned)max_qb, (unsigned)max_splits);
+    switch (W) {
+      case 1: launch_match_partial<1>(h, grid, a); break;
+      case 2: launch_match_partial<2>(h, grid, a); break;
+      case 3: launch_match_partial<3>(h, grid, a); break;
+      case 4: launch_match_partial<4>(h, grid, a); break;
+      case 5: launch_match_partial<5>(h, grid, a); break;
+      case 6: launch_match_partial<6>(h, grid, a); break;
+      case 7: launch_match_partial<7>(h, grid, a); break;
+      default: launch_match_partial<8>(h, grid, a); break;
+    }
+  }
+  int fin_qb = 0;
+  for (size_t p = 0; p < np; ++p) fin_qb = std::max(fin_qb, (tab[p].nq + MT_THREADS - 1) / MT_THREADS);
+  BA_LAUNCH(k_match_finish, dim3((unsigned)np, (unsigned)fin_qb), dim3(MT_THREADS), 0, h->stream, a);
+  int32_t* const outs[4] = {best, second, dist1, dist2};
+  for (int k = 0; k < 4; ++k)
+    if (outs[k]) HIPCHECK(hipMemcpyAsync(outs[k], h->mt_out.p + k * nr, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (good) HIPCHECK(hipMemcpyAsync(good, h->mt_good.p, nr, hipMemcpyDeviceToHost, h->stream));
+  if (n_good) HIPCHECK(hipMemcpyAsync(n_good, h->mt_ngood.p, np * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  BA_SYNC(h);
   return BA_OK;
 }
 

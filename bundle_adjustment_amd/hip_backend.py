@@ -115,6 +115,16 @@ class BARelposeOptions(C.Structure):
                 ("refine_iters", C.c_int32), ("min_inliers", C.c_int32), ("min_parallax_deg", C.c_double), ("max_depth", C.c_double)]
 
 
+class BAMatchOptions(C.Structure):
+    _fields_ = [("ratio", C.c_double), ("max_distance", C.c_int32), ("mutual", C.c_int32)]
+
+
+# ba_match_descriptors (csrc/ba_match.hpp): queries per workgroup, train descriptors per LDS tile, the shortest train split,
+# the most splits of a pair, the most descriptors of a set, the descriptor widths
+MATCH_BLOCK, MATCH_TILE, MATCH_MIN_SPLIT, MATCH_MAX_SPLITS, MATCH_MAX_SET = 256, 64, 128, 64, 1 << 20
+MATCH_DESC_BYTES = (8, 16, 24, 32, 40, 48, 56, 64)
+
+
 class BASimilarity(C.Structure):
     _fields_ = [("s", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3)]
 
@@ -195,6 +205,9 @@ SYMBOLS = {
     "ba_default_relpose_options": (C.c_int, [C.POINTER(BARelposeOptions)]),
     "ba_relative_pose": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.POINTER(C.c_int64), _DP, _DP, C.POINTER(BARelposeOptions), _DP, _DP,
                                    C.POINTER(C.c_uint8), _IP, _DP, _DP, _IP, C.POINTER(C.c_uint8)]),
+    "ba_default_match_options": (C.c_int, [C.POINTER(BAMatchOptions)]),
+    "ba_match_descriptors": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.c_int32, _IP, _IP,
+                                       C.POINTER(BAMatchOptions), C.POINTER(C.c_int64), _IP, _IP, _IP, _IP, C.POINTER(C.c_uint8), _IP]),
     "ba_get_centres": (C.c_int, [C.c_void_p, _DP]),
     "ba_transform": (C.c_int, [C.c_void_p, C.POINTER(BASimilarity)]),
     "ba_default_align_options": (C.c_int, [C.POINTER(BAAlignOptions)]),
@@ -734,6 +747,50 @@ class Solver:
                                           _dp(out["rms_px"]), _dp(out["parallax_deg"]), out["best_hyp"].ctypes.data_as(_IP),
                                           inl.ctypes.data_as(u8)))
         out["match_inlier"] = inl.astype(bool)
+        return out
+
+    def match_options(self, **kw) -> BAMatchOptions:
+        """ba_default_match_options overlaid with kw (any ba_match_options field; an unknown one raises TypeError)."""
+        return _options(BAMatchOptions, self._lib.ba_default_match_options, kw, names={})
+
+    def match_descriptors(self, sets, pairs=None, **opts):
+        """ba_match_descriptors: Hamming 2-nearest-neighbours of binary descriptors with the ratio test.  sets: a list of
+        (n_s, desc_bytes) uint8 arrays of one width (a multiple of 8 in 8 .. 64); pairs (P, 2) of (query set, train set), None
+        with two sets: [(0, 1)].  opts: ratio, max_distance, mutual.  Returns dict(row_off (P + 1,) int64, best, second, dist1,
+        dist2 (rows,) int32, good (rows,) bool, n_good (P,) int32); row row_off[p] + i is query i of pair p; -1 where there is
+        no such neighbour.  ValueError for mixed widths or dtypes.  Needs no problem and leaves a resident one as it is."""
+        arrs = [np.asarray(a) for a in sets]
+        for a in arrs:
+            if a.dtype != np.uint8 or a.ndim != 2:
+                raise ValueError(f"every descriptor set must be a 2-D uint8 array, not {a.dtype} with shape {a.shape}")
+        widths = {a.shape[1] for a in arrs}
+        if len(widths) > 1:
+            raise ValueError(f"descriptor sets of different widths: {sorted(widths)} bytes")
+        if pairs is None:
+            if len(arrs) not in (0, 2):
+                raise ValueError("pairs=None needs exactly two sets (query, train)")
+            pairs = [(0, 1)] if arrs else []
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        width = widths.pop() if widths else 32
+        set_off = np.zeros(len(arrs) + 1, dtype=np.int64)
+        set_off[1:] = np.cumsum([a.shape[0] for a in arrs])
+        desc = np.ascontiguousarray(np.concatenate(arrs, axis=0)) if arrs else np.zeros((0, width), dtype=np.uint8)
+        o = self.match_options(**opts)
+        P = pr.shape[0]
+        ok = P == 0 or (pr.min() >= 0 and pr.max() < len(arrs))
+        rows = int(sum(arrs[q].shape[0] for q in pr[:, 0])) if ok else 0      # (a bad index is the library's to refuse: it names the field)
+        out = dict(row_off=np.zeros(P + 1, dtype=np.int64), best=np.empty(rows, dtype=np.int32), second=np.empty(rows, dtype=np.int32),
+                   dist1=np.empty(rows, dtype=np.int32), dist2=np.empty(rows, dtype=np.int32))
+        good, n_good = np.zeros(rows, dtype=np.uint8), np.zeros(P, dtype=np.int32)
+        q, t = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        u8 = C.POINTER(C.c_uint8)
+        _check(self._lib.ba_match_descriptors(self._h, width, len(arrs), set_off.ctypes.data_as(C.POINTER(C.c_int64)), desc.ctypes.data_as(u8),
+                                              P, q.ctypes.data_as(_IP), t.ctypes.data_as(_IP), C.byref(o),
+                                              out["row_off"].ctypes.data_as(C.POINTER(C.c_int64)), out["best"].ctypes.data_as(_IP),
+                                              out["second"].ctypes.data_as(_IP), out["dist1"].ctypes.data_as(_IP),
+                                              out["dist2"].ctypes.data_as(_IP), good.ctypes.data_as(u8), n_good.ctypes.data_as(_IP)))
+        out["good"] = good.astype(bool)
+        out["n_good"] = n_good
         return out
 
     def centres(self):

@@ -406,6 +406,43 @@ int ba_default_relpose_options(ba_relpose_options* opts);   /* 256, 2, 0, 3.0, 2
 int ba_relative_pose(ba_handle* h, const double K[9], int32_t n_pairs, const int64_t* pair_off, const double* pts1, const double* pts2,
                      const ba_relpose_options* opts, double* R, double* t, uint8_t* status, int32_t* n_inliers, double* rms_px,
                      double* parallax_deg, int32_t* best_hyp, uint8_t* match_inlier);
+/* Descriptor matching: brute-force Hamming 2-nearest-neighbours of binary descriptors with Lowe's ratio test, the step that
+ * produces the matches ba_relative_pose starts from (the reference's BruteForceMatcher.match: cv2.BFMatcher(NORM_HAMMING,
+ * crossCheck=False).knnMatch(des1, des2, k=2), then m.distance < 0.75 n.distance).  Needs no ba_set_problem and leaves a resident
+ * problem untouched; the staging buffers live on the handle and are reused.  Local to the rank.
+ * Inputs: desc is uint8[set_off[n_sets]][desc_bytes], set s owns the rows set_off[s] .. set_off[s + 1] - 1; every set is uploaded
+ * once per call, however many pairs use it.  Pair p matches every descriptor of set pair_query[p] (the queries) against set
+ * pair_train[p]; a set may be matched against itself.  desc_bytes is a multiple of 8 in 8 .. 64 (ORB 32, BRISK 64); a caller
+ * with another length pads both sides with equal bytes, which adds nothing to any distance.
+ * Outputs, any of them NULL, by row: row row_off[p] + i belongs to query i of pair p; row_off int64[n_pairs + 1] is the exclusive
+ * prefix sum of the pairs' query-set sizes, computed and written by the library.  best, second, dist1, dist2 int32[rows], good
+ * uint8[rows], n_good int32[n_pairs].
+ * Per pair with nq queries and nt train descriptors: d(i, j) = popcount of the XOR of the two rows.  The train descriptors of
+ * query i are ordered by the key (d(i, j), j): ties go to the lower index.  best / dist1 are the first entry of that order,
+ * second / dist2 the second; nt = 0: best = second = dist1 = dist2 = -1; nt = 1: second = dist2 = -1.  This is the order cv2's
+ * knnMatch leaves by inserting the neighbours in index order (crossCheck=False); cv2 is not part of this project's test
+ * environment, so equality with cv2 on ties rests on its source and is NOT verified.
+ * good[i] = 1 if and only if all of: best >= 0; ratio <= 0, or second >= 0 and (double)dist1 < ratio * (double)dist2 in fp64
+ * exactly as written (with nt < 2 and a ratio test nothing is good, as the reference returns an empty list then);
+ * max_distance < 0, or dist1 <= max_distance; mutual = 0, or i is the first query under the key (d(i', best), i') over all
+ * queries i' of the pair (i is the best query of its best train descriptor, ties to the lower query; NOT cv2's crossCheck, which
+ * drops the ratio test's second neighbour).  n_good[p] = the number of good queries of pair p.
+ * n_pairs = 0, empty sets and empty query sets are no-ops with well-formed outputs (row_off written, n_good zero).
+ * BA_ERR_INVALID, naming the field: desc_bytes not as above; n_sets or n_pairs outside 0 .. 65535; ratio not finite; set_off NULL,
+ * set_off[0] != 0, a decreasing set_off, a set of more than 2^20 descriptors; desc NULL with descriptors to read; pair_query /
+ * pair_train NULL with n_pairs > 0 or an index outside 0 .. n_sets - 1.  A refused call leaves the handle usable.
+ * Results are pure integer arithmetic and bit-reproducible; a pair's rows do not depend on the other pairs of the call, nor on
+ * how the library splits the train set over workgroups (csrc/ba_match.hpp).  Not offered: float (L2) descriptors, k > 2, masks. */
+typedef struct ba_match_options {
+  double  ratio;         /* keep a query when (double)d1 < ratio * (double)d2, in fp64 exactly as written; <= 0: no ratio test; default 0.75 */
+  int32_t max_distance;  /* keep only d1 <= max_distance; < 0: no test; default -1 */
+  int32_t mutual;        /* 1: keep (i, j) only if i is also the best query of train j under the same order; default 0 */
+} ba_match_options;      /* 16 bytes */
+int ba_default_match_options(ba_match_options* opts);    /* 0.75, -1, 0 */
+int ba_match_descriptors(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc,
+                         int32_t n_pairs, const int32_t* pair_query, const int32_t* pair_train, const ba_match_options* opts,
+                         int64_t* row_off, int32_t* best, int32_t* second, int32_t* dist1, int32_t* dist2,
+                         uint8_t* good, int32_t* n_good);
 /* Similarity transform of the reconstruction and robust alignment to reference positions: the step after an adjustment that
  * moves the result into the frame its user needs (georegistration onto GPS / surveyed camera positions or ground-control
  * points -- COLMAP's model_aligner; the comparison of two gauge-free solves; re-centring / re-scaling).  No reference
