@@ -43,6 +43,7 @@
 #include "ba_ransac.hpp"
 #include "ba_relpose.hpp"
 #include "ba_match.hpp"
+#include "ba_match_guided.hpp"
 
 using namespace ba;
 
@@ -300,6 +301,11 @@ struct ba_handle {
   DBuf<int> mt_out, mt_ngood;
   DBuf<unsigned char> mt_good;
   int debug_match_splits = 0;  // BA_DEBUG_MATCH_SPLITS: train splits asked for per pair instead of match_plan's own choice (tests)
+  // ba_match_guided (ba_match_guided.hpp), beside the buffers above: the keypoints of every descriptor row, the windows by row,
+  // F by pair, the queries' gate records, the splits' counts of admitted rows, n_cand by row
+  DBuf<float> mg_xy, mg_win;
+  DBuf<double> mg_F, mg_rec;
+  DBuf<int> mg_cnt, mg_ncand;
   // ba_transform / ba_align / ba_get_centres (ba_similarity.hpp): correspondences a | b | w | u | err (9 doubles each), the
   // per-workgroup partial rows, the device record (similarity, centroids, status)
   DBuf<double> sim_buf, sim_part;
@@ -3722,81 +3728,119 @@ template <int W>
 static void launch_match_partial(ba_handle* h, dim3 grid, const MatchArgs& a) {
   BA_LAUNCH(k_match_partial<W>, grid, dim3(MT_THREADS), 0, h->stream, a);
 }
+// What ba_match_descriptors and ba_match_guided refuse alike; `who` is the call the message names.
+static int match_check(const char* who, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc, int32_t n_pairs,
+                       const int32_t* pair_query, const int32_t* pair_train, double ratio) {
+  if (desc_bytes < 8 || desc_bytes > 8 * MT_MAX_WORDS || desc_bytes % 8 != 0)
+    return fail(BA_ERR_INVALID, "%s: desc_bytes %d is not a multiple of 8 in 8 .. %d", who, desc_bytes, 8 * MT_MAX_WORDS);
+  if (n_sets < 0 || n_sets > 65535) return fail(BA_ERR_INVALID, "%s: n_sets %d is outside 0 .. 65535", who, n_sets);
+  if (n_pairs < 0 || n_pairs > 65535) return fail(BA_ERR_INVALID, "%s: n_pairs %d is outside 0 .. 65535", who, n_pairs);
+  if (!std::isfinite(ratio)) return fail(BA_ERR_INVALID, "%s: ratio must be finite", who);
+  if (!set_off) return fail(BA_ERR_INVALID, "%s: null set_off", who);
+  if (set_off[0] != 0) return fail(BA_ERR_INVALID, "%s: set_off[0] must be 0", who);
+  for (int32_t s = 0; s < n_sets; ++s) {
+    if (set_off[s + 1] < set_off[s]) return fail(BA_ERR_INVALID, "%s: set_off decreases at set %d", who, s);
+    if (set_off[s + 1] - set_off[s] > (1LL << MT_IDX_BITS))
+      return fail(BA_ERR_INVALID, "%s: set_off: set %d holds %lld descriptors, more than %d", who, s,
+                  (long long)(set_off[s + 1] - set_off[s]), 1 << MT_IDX_BITS);
+  }
+  if (set_off[n_sets] > 0 && !desc) return fail(BA_ERR_INVALID, "%s: null desc", who);
+  if (n_pairs > 0 && !pair_query) return fail(BA_ERR_INVALID, "%s: null pair_query", who);
+  if (n_pairs > 0 && !pair_train) return fail(BA_ERR_INVALID, "%s: null pair_train", who);
+  for (int32_t p = 0; p < n_pairs; ++p) {
+    if (pair_query[p] < 0 || pair_query[p] >= n_sets)
+      return fail(BA_ERR_INVALID, "%s: pair_query[%d] = %d is outside 0 .. n_sets - 1", who, p, pair_query[p]);
+    if (pair_train[p] < 0 || pair_train[p] >= n_sets)
+      return fail(BA_ERR_INVALID, "%s: pair_train[%d] = %d is outside 0 .. n_sets - 1", who, p, pair_train[p]);
+  }
+  return BA_OK;
+}
+// The entries of a call and what its launches are sized by
+struct MatchTable {
+  std::vector<MatchPair> tab;        // the call's pairs, then (mutual) the same pairs with the roles swapped
+  long long rows = 0, wave_rows = 0, n_part = 0;
+  int max_qb = 0, max_splits = 0, fin_qb = 0;
+};
+// A swapped entry's row0 is 0 (ba_match_descriptors: unused) or, with pair_rows, its pair's row0 (ba_match_guided: the rows of
+// the gate records its tiles carry).  Writes row_off when it is asked for.
+static void match_entries(MatchTable& m, const int64_t* set_off, int32_t n_pairs, const int32_t* pair_query, const int32_t* pair_train,
+                          bool mutual, bool pair_rows, int64_t* row_off) {
+  const size_t np = (size_t)n_pairs;
+  m.tab.assign((mutual ? 2 : 1) * np, MatchPair{});
+  for (size_t p = 0; p < np; ++p) {
+    MatchPair& e = m.tab[p];
+    e.q0 = set_off[pair_query[p]]; e.nq = (int)(set_off[pair_query[p] + 1] - e.q0);
+    e.t0 = set_off[pair_train[p]]; e.nt = (int)(set_off[pair_train[p] + 1] - e.t0);
+    e.row0 = m.rows;
+    if (row_off) row_off[p] = m.rows;
+    m.rows += e.nq;
+    m.wave_rows += (e.nq + 63) / 64;
+    if (mutual) {
+      MatchPair& r = m.tab[np + p];
+      r.q0 = e.t0; r.nq = e.nt; r.t0 = e.q0; r.nt = e.nq; r.row0 = pair_rows ? e.row0 : 0;
+      m.wave_rows += (r.nq + 63) / 64;
+    }
+  }
+  if (row_off) row_off[np] = m.rows;
+}
+// The splits of every entry (rows > 0).  Two waves per SIMD over the whole call: want = ceil(8 n_cu / wave rows of the call)
+static void match_plan_all(const ba_handle* h, MatchTable& m, size_t n_pairs) {
+  const long long target = 8LL * h->n_cu;
+  const int want = h->debug_match_splits > 0 ? h->debug_match_splits
+                                             : (int)std::min<long long>(MT_MAX_SPLITS, (target + m.wave_rows - 1) / m.wave_rows);
+  for (MatchPair& e : m.tab) {
+    match_plan(e, want);
+    e.part0 = m.n_part;
+    m.n_part += (long long)e.nq * e.n_splits;
+    if (e.n_splits > 0) m.max_qb = std::max(m.max_qb, (e.nq + MT_THREADS - 1) / MT_THREADS);
+    m.max_splits = std::max(m.max_splits, e.n_splits);
+  }
+  for (size_t p = 0; p < n_pairs; ++p) m.fin_qb = std::max(m.fin_qb, (m.tab[p].nq + MT_THREADS - 1) / MT_THREADS);
+}
+// The staging both calls share: buffers, the kernels' common arguments, the uploads of descriptors and table, n_good zeroed
+static int match_stage(ba_handle* h, const MatchTable& m, int32_t desc_bytes, size_t n_desc, const uint8_t* desc, int32_t n_pairs,
+                       double ratio, int32_t max_distance, bool mutual, MatchArgs& a) {
+  const size_t nr = (size_t)m.rows, np = (size_t)n_pairs, W = (size_t)desc_bytes / 8;
+  HIPCHECK(h->mt_desc.alloc(n_desc * W)); HIPCHECK(h->mt_pairs.alloc(m.tab.size())); HIPCHECK(h->mt_part.alloc(std::max<size_t>((size_t)m.n_part, 1)));
+  HIPCHECK(h->mt_out.alloc(4 * nr)); HIPCHECK(h->mt_good.alloc(nr)); HIPCHECK(h->mt_ngood.alloc(np));
+  a = {};
+  a.desc = h->mt_desc.p; a.pairs = h->mt_pairs.p; a.part = h->mt_part.p;
+  a.n_pairs = n_pairs; a.mutual = mutual ? 1 : 0; a.max_distance = max_distance; a.ratio = ratio;
+  a.best = h->mt_out.p; a.second = h->mt_out.p + nr; a.dist1 = h->mt_out.p + 2 * nr; a.dist2 = h->mt_out.p + 3 * nr;
+  a.good = h->mt_good.p; a.n_good = h->mt_ngood.p;
+  HIPCHECK(hipMemcpyAsync(h->mt_desc.p, desc, n_desc * (size_t)desc_bytes, hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(h->mt_pairs.p, m.tab.data(), m.tab.size() * sizeof(MatchPair), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemsetAsync(h->mt_ngood.p, 0, np * sizeof(int), h->stream));
+  return BA_OK;
+}
+// best | second | dist1 | dist2, good and n_good to the caller, where asked for (queued; the caller drains the stream)
+static int match_fetch(ba_handle* h, size_t nr, size_t np, int32_t* best, int32_t* second, int32_t* dist1, int32_t* dist2, uint8_t* good,
+                       int32_t* n_good) {
+  int32_t* const outs[4] = {best, second, dist1, dist2};
+  for (int k = 0; k < 4; ++k)
+    if (outs[k]) HIPCHECK(hipMemcpyAsync(outs[k], h->mt_out.p + k * nr, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (good) HIPCHECK(hipMemcpyAsync(good, h->mt_good.p, nr, hipMemcpyDeviceToHost, h->stream));
+  if (n_good) HIPCHECK(hipMemcpyAsync(n_good, h->mt_ngood.p, np * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  return BA_OK;
+}
 extern "C" int ba_match_descriptors(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc,
                                     int32_t n_pairs, const int32_t* pair_query, const int32_t* pair_train, const ba_match_options* opts,
                                     int64_t* row_off, int32_t* best, int32_t* second, int32_t* dist1, int32_t* dist2,
                                     uint8_t* good, int32_t* n_good) {
   if (!h || !opts) return fail(BA_ERR_INVALID, "null argument");
-  if (desc_bytes < 8 || desc_bytes > 8 * MT_MAX_WORDS || desc_bytes % 8 != 0)
-    return fail(BA_ERR_INVALID, "ba_match_descriptors: desc_bytes %d is not a multiple of 8 in 8 .. %d", desc_bytes, 8 * MT_MAX_WORDS);
-  if (n_sets < 0 || n_sets > 65535) return fail(BA_ERR_INVALID, "ba_match_descriptors: n_sets %d is outside 0 .. 65535", n_sets);
-  if (n_pairs < 0 || n_pairs > 65535) return fail(BA_ERR_INVALID, "ba_match_descriptors: n_pairs %d is outside 0 .. 65535", n_pairs);
-  if (!std::isfinite(opts->ratio)) return fail(BA_ERR_INVALID, "ba_match_descriptors: ratio must be finite");
-  if (!set_off) return fail(BA_ERR_INVALID, "ba_match_descriptors: null set_off");
-  if (set_off[0] != 0) return fail(BA_ERR_INVALID, "ba_match_descriptors: set_off[0] must be 0");
-  for (int32_t s = 0; s < n_sets; ++s) {
-    if (set_off[s + 1] < set_off[s]) return fail(BA_ERR_INVALID, "ba_match_descriptors: set_off decreases at set %d", s);
-    if (set_off[s + 1] - set_off[s] > (1LL << MT_IDX_BITS))
-      return fail(BA_ERR_INVALID, "ba_match_descriptors: set_off: set %d holds %lld descriptors, more than %d", s,
-                  (long long)(set_off[s + 1] - set_off[s]), 1 << MT_IDX_BITS);
-  }
+  if (int rc = match_check("ba_match_descriptors", desc_bytes, n_sets, set_off, desc, n_pairs, pair_query, pair_train, opts->ratio)) return rc;
   const size_t n_desc = (size_t)set_off[n_sets], np = (size_t)n_pairs, W = (size_t)desc_bytes / 8;
-  if (n_desc > 0 && !desc) return fail(BA_ERR_INVALID, "ba_match_descriptors: null desc");
-  if (n_pairs > 0 && !pair_query) return fail(BA_ERR_INVALID, "ba_match_descriptors: null pair_query");
-  if (n_pairs > 0 && !pair_train) return fail(BA_ERR_INVALID, "ba_match_descriptors: null pair_train");
-  for (int32_t p = 0; p < n_pairs; ++p) {
-    if (pair_query[p] < 0 || pair_query[p] >= n_sets)
-      return fail(BA_ERR_INVALID, "ba_match_descriptors: pair_query[%d] = %d is outside 0 .. n_sets - 1", p, pair_query[p]);
-    if (pair_train[p] < 0 || pair_train[p] >= n_sets)
-      return fail(BA_ERR_INVALID, "ba_match_descriptors: pair_train[%d] = %d is outside 0 .. n_sets - 1", p, pair_train[p]);
-  }
-  // the pair table: the call's pairs, then (mutual) the same pairs with the roles swapped
   const bool mutual = opts->mutual != 0;
-  std::vector<MatchPair> tab((mutual ? 2 : 1) * np);
-  long long rows = 0, wave_rows = 0;
-  int max_qb = 0, max_splits = 0;
-  for (size_t p = 0; p < np; ++p) {
-    MatchPair& e = tab[p];
-    e.q0 = set_off[pair_query[p]]; e.nq = (int)(set_off[pair_query[p] + 1] - e.q0);
-    e.t0 = set_off[pair_train[p]]; e.nt = (int)(set_off[pair_train[p] + 1] - e.t0);
-    e.row0 = rows;
-    if (row_off) row_off[p] = rows;
-    rows += e.nq;
-    wave_rows += (e.nq + 63) / 64;
-    if (mutual) {
-      MatchPair& r = tab[np + p];
-      r.q0 = e.t0; r.nq = e.nt; r.t0 = e.q0; r.nt = e.nq; r.row0 = 0;
-      wave_rows += (r.nq + 63) / 64;
-    }
-  }
-  if (row_off) row_off[np] = rows;
+  MatchTable m;
+  match_entries(m, set_off, n_pairs, pair_query, pair_train, mutual, false, row_off);
   if (n_good) memset(n_good, 0, np * sizeof(int32_t));
-  if (rows == 0) return BA_OK;     // no query anywhere: nothing to compute, and every output is already well-formed
+  if (m.rows == 0) return BA_OK;     // no query anywhere: nothing to compute, and every output is already well-formed
   if (set_device(h)) return BA_ERR_HIP;
-  // two waves per SIMD over the whole call: want = ceil(8 n_cu / wave rows of the call)
-  const long long target = 8LL * h->n_cu;
-  const int want = h->debug_match_splits > 0 ? h->debug_match_splits : (int)std::min<long long>(MT_MAX_SPLITS, (target + wave_rows - 1) / wave_rows);
-  long long n_part = 0;
-  for (MatchPair& e : tab) {
-    match_plan(e, want);
-    e.part0 = n_part;
-    n_part += (long long)e.nq * e.n_splits;
-    if (e.n_splits > 0) max_qb = std::max(max_qb, (e.nq + MT_THREADS - 1) / MT_THREADS);
-    max_splits = std::max(max_splits, e.n_splits);
-  }
-  const size_t nr = (size_t)rows;
-  HIPCHECK(h->mt_desc.alloc(n_desc * W)); HIPCHECK(h->mt_pairs.alloc(tab.size())); HIPCHECK(h->mt_part.alloc(std::max<size_t>((size_t)n_part, 1)));
-  HIPCHECK(h->mt_out.alloc(4 * nr)); HIPCHECK(h->mt_good.alloc(nr)); HIPCHECK(h->mt_ngood.alloc(np));
-  MatchArgs a = {};
-  a.desc = h->mt_desc.p; a.pairs = h->mt_pairs.p; a.part = h->mt_part.p;
-  a.n_pairs = n_pairs; a.mutual = mutual ? 1 : 0; a.max_distance = opts->max_distance; a.ratio = opts->ratio;
-  a.best = h->mt_out.p; a.second = h->mt_out.p + nr; a.dist1 = h->mt_out.p + 2 * nr; a.dist2 = h->mt_out.p + 3 * nr;
-  a.good = h->mt_good.p; a.n_good = h->mt_ngood.p;
-  HIPCHECK(hipMemcpyAsync(h->mt_desc.p, desc, n_desc * (size_t)desc_bytes, hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipMemcpyAsync(h->mt_pairs.p, tab.data(), tab.size() * sizeof(MatchPair), hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipMemsetAsync(h->mt_ngood.p, 0, np * sizeof(int), h->stream));
-  if (max_splits > 0) {
-    const dim3 grid((unsigned)tab.size(), (unsigned)max_qb, (unsigned)max_splits);
+  match_plan_all(h, m, np);
+  MatchArgs a;
+  if (int rc = match_stage(h, m, desc_bytes, n_desc, desc, n_pairs, opts->ratio, opts->max_distance, mutual, a)) return rc;
+  if (m.max_splits > 0) {
+    const dim3 grid((unsigned)m.tab.size(), (unsigned)m.max_qb, (unsigned)m.max_splits);
     switch (W) {
       case 1: launch_match_partial<1>(h, grid, a); break;
       case 2: launch_match_partial<2>(h, grid, a); break;
@@ -3808,14 +3852,90 @@ extern "C" int ba_match_descriptors(ba_handle* h, int32_t desc_bytes, int32_t n_
       default: launch_match_partial<8>(h, grid, a); break;
     }
   }
-  int fin_qb = 0;
-  for (size_t p = 0; p < np; ++p) fin_qb = std::max(fin_qb, (tab[p].nq + MT_THREADS - 1) / MT_THREADS);
-  BA_LAUNCH(k_match_finish, dim3((unsigned)np, (unsigned)fin_qb), dim3(MT_THREADS), 0, h->stream, a);
-  int32_t* const outs[4] = {best, second, dist1, dist2};
-  for (int k = 0; k < 4; ++k)
-    if (outs[k]) HIPCHECK(hipMemcpyAsync(outs[k], h->mt_out.p + k * nr, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  if (good) HIPCHECK(hipMemcpyAsync(good, h->mt_good.p, nr, hipMemcpyDeviceToHost, h->stream));
-  if (n_good) HIPCHECK(hipMemcpyAsync(n_good, h->mt_ngood.p, np * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  BA_LAUNCH(k_match_finish, dim3((unsigned)np, (unsigned)m.fin_qb), dim3(MT_THREADS), 0, h->stream, a);
+  if (int rc = match_fetch(h, (size_t)m.rows, np, best, second, dist1, dist2, good, n_good)) return rc;
+  BA_SYNC(h);
+  return BA_OK;
+}
+
+// ba_match_guided (csrc/ba_match_guided.hpp): the same 2-NN over the train rows a gate admits.  Needs no problem.
+static_assert(sizeof(ba_guided_options) == 32, "ba_guided_options (include/ba_hip.h)");
+static_assert(MG_WINDOW == BA_GATE_WINDOW && MG_EPIPOLAR == BA_GATE_EPIPOLAR, "device gate codes (ba_match_guided.hpp)");
+extern "C" int ba_default_guided_options(ba_guided_options* o) {
+  if (!o) return fail(BA_ERR_INVALID, "null argument");
+  memset(o, 0, sizeof *o);
+  o->ratio = 0.75;
+  o->max_distance = -1;
+  o->single = 1;
+  o->max_epi_px = 3.0;
+  return BA_OK;
+}
+template <int W>
+static void launch_guided_partial(ba_handle* h, dim3 grid, const GuidedArgs& a) {
+  if (a.gate == MG_WINDOW) BA_LAUNCH((k_guided_partial<W, MG_WINDOW>), grid, dim3(MT_THREADS), 0, h->stream, a);
+  else BA_LAUNCH((k_guided_partial<W, MG_EPIPOLAR>), grid, dim3(MT_THREADS), 0, h->stream, a);
+}
+extern "C" int ba_match_guided(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc, const float* xy,
+                               int32_t n_pairs, const int32_t* pair_query, const int32_t* pair_train, const ba_guided_options* opts,
+                               const float* window, const double* F, int64_t* row_off, int32_t* best, int32_t* second, int32_t* dist1,
+                               int32_t* dist2, uint8_t* good, int32_t* n_good, int32_t* n_cand) {
+  if (!h || !opts) return fail(BA_ERR_INVALID, "null argument");
+  if (int rc = match_check("ba_match_guided", desc_bytes, n_sets, set_off, desc, n_pairs, pair_query, pair_train, opts->ratio)) return rc;
+  const size_t n_desc = (size_t)set_off[n_sets], np = (size_t)n_pairs, W = (size_t)desc_bytes / 8;
+  if (n_desc > 0 && !xy) return fail(BA_ERR_INVALID, "ba_match_guided: null xy");
+  if (opts->gate != BA_GATE_WINDOW && opts->gate != BA_GATE_EPIPOLAR)
+    return fail(BA_ERR_INVALID, "ba_match_guided: gate %d is neither BA_GATE_WINDOW (1) nor BA_GATE_EPIPOLAR (2)", opts->gate);
+  if (opts->single != 0 && opts->single != 1) return fail(BA_ERR_INVALID, "ba_match_guided: single %d is not 0 or 1", opts->single);
+  const bool epi = opts->gate == BA_GATE_EPIPOLAR, mutual = opts->mutual != 0;
+  if (epi) {
+    if (!std::isfinite(opts->max_epi_px) || opts->max_epi_px < 0.0) return fail(BA_ERR_INVALID, "ba_match_guided: max_epi_px must be finite and not negative");
+    if (n_pairs > 0 && !F) return fail(BA_ERR_INVALID, "ba_match_guided: null F with the epipolar gate");
+    for (size_t k = 0; k < 9 * np; ++k)
+      if (!std::isfinite(F[k])) return fail(BA_ERR_INVALID, "ba_match_guided: F of pair %d has a non-finite entry", (int)(k / 9));
+  }
+  MatchTable m;
+  match_entries(m, set_off, n_pairs, pair_query, pair_train, mutual, true, nullptr);
+  if (!epi && m.rows > 0 && !window) return fail(BA_ERR_INVALID, "ba_match_guided: null window with the window gate");
+  if (row_off)
+    for (size_t p = 0; p <= np; ++p) row_off[p] = p < np ? m.tab[p].row0 : m.rows;
+  if (n_good) memset(n_good, 0, np * sizeof(int32_t));
+  if (m.rows == 0) return BA_OK;     // no query anywhere: nothing to compute, and every output is already well-formed
+  if (set_device(h)) return BA_ERR_HIP;
+  match_plan_all(h, m, np);
+  const size_t nr = (size_t)m.rows;
+  GuidedArgs a = {};
+  if (int rc = match_stage(h, m, desc_bytes, n_desc, desc, n_pairs, opts->ratio, opts->max_distance, mutual, a.m)) return rc;
+  HIPCHECK(h->mg_xy.alloc(2 * n_desc)); HIPCHECK(h->mg_rec.alloc(4 * nr)); HIPCHECK(h->mg_cnt.alloc(std::max<size_t>((size_t)m.n_part, 1)));
+  HIPCHECK(h->mg_ncand.alloc(nr));
+  a.xy = h->mg_xy.p; a.rec = h->mg_rec.p; a.cnt = h->mg_cnt.p; a.n_cand = h->mg_ncand.p;
+  a.gate = opts->gate; a.single = opts->single; a.max_epi2 = opts->max_epi_px * opts->max_epi_px;
+  HIPCHECK(hipMemcpyAsync(h->mg_xy.p, xy, 2 * n_desc * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (epi) {
+    HIPCHECK(h->mg_F.alloc(9 * np));
+    HIPCHECK(hipMemcpyAsync(h->mg_F.p, F, 9 * np * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    a.F = h->mg_F.p;
+  } else {
+    HIPCHECK(h->mg_win.alloc(3 * nr));
+    HIPCHECK(hipMemcpyAsync(h->mg_win.p, window, 3 * nr * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    a.window = h->mg_win.p;
+  }
+  BA_LAUNCH(k_guided_prepare, dim3((unsigned)np, (unsigned)m.fin_qb), dim3(MT_THREADS), 0, h->stream, a);
+  if (m.max_splits > 0) {
+    const dim3 grid((unsigned)m.tab.size(), (unsigned)m.max_qb, (unsigned)m.max_splits);
+    switch (W) {
+      case 1: launch_guided_partial<1>(h, grid, a); break;
+      case 2: launch_guided_partial<2>(h, grid, a); break;
+      case 3: launch_guided_partial<3>(h, grid, a); break;
+      case 4: launch_guided_partial<4>(h, grid, a); break;
+      case 5: launch_guided_partial<5>(h, grid, a); break;
+      case 6: launch_guided_partial<6>(h, grid, a); break;
+      case 7: launch_guided_partial<7>(h, grid, a); break;
+      default: launch_guided_partial<8>(h, grid, a); break;
+    }
+  }
+  BA_LAUNCH(k_guided_finish, dim3((unsigned)np, (unsigned)m.fin_qb), dim3(MT_THREADS), 0, h->stream, a);
+  if (int rc = match_fetch(h, nr, np, best, second, dist1, dist2, good, n_good)) return rc;
+  if (n_cand) HIPCHECK(hipMemcpyAsync(n_cand, h->mg_ncand.p, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   BA_SYNC(h);
   return BA_OK;
 }

@@ -4,6 +4,8 @@ Mirrors ``BruteForceMatcher.match`` of ``src/features.py`` (``cv2.BFMatcher(NORM
 k=2)`` then Lowe's ``m.distance < 0.75 * n.distance``) on the GPU (``ba_match_descriptors``: brute-force Hamming 2-nearest
 neighbours, ties to the lower train index, the ratio test in fp64).  The match objects are duck-typed for
 ``pose_estimator.estimate_pose``, which reads ``queryIdx`` / ``trainIdx``.  No cv2 is needed; ORB extraction is not offered.
+Once geometry is known, ``match_epipolar`` and ``match_by_projection`` match a second time under it (``ba_match_guided``: the
+same 2-NN over the keypoints an epipolar line or a search window admits; no counterpart in the reference).
 No CPU fallback: without the library / a GPU the call raises.
 """
 from __future__ import annotations
@@ -80,6 +82,82 @@ def match_to_keyframes(des_new, keyframe_descriptors, solver=None, **opts):
     for n, k in enumerate(have):
         lists[k] = _match_list(*_good_of_pair(out, n))
     return lists
+
+
+def fundamental(K, R, t):
+    """F = K^-T [t]x R K^-1 of x2 ~ K (R x1 + t), the convention of ``ba_relative_pose``: x2^T F x1 = 0 in pixels."""
+    K, R, t = np.asarray(K, dtype=np.float64).reshape(3, 3), np.asarray(R, dtype=np.float64).reshape(3, 3), np.asarray(t, dtype=np.float64).reshape(3)
+    tx = np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]])
+    Ki = np.linalg.inv(K)
+    return Ki.T @ tx @ R @ Ki
+
+
+def _positions(kp):
+    """(n, 2) float64 pixel positions of an (n, 2) array or of a sequence of objects with ``.pt``; None -> None."""
+    if kp is None:
+        return None
+    if isinstance(kp, np.ndarray):
+        return np.asarray(kp, dtype=np.float64).reshape(-1, 2)
+    kp = list(kp)
+    if kp and hasattr(kp[0], "pt"):
+        return np.array([k.pt for k in kp], dtype=np.float64).reshape(-1, 2)
+    return np.asarray(kp, dtype=np.float64).reshape(-1, 2)
+
+
+def _empty_matches():
+    z = np.zeros(0, dtype=np.int64)
+    return z, z.copy(), z.copy()
+
+
+def _guided(solver, sets, kps, **kw):
+    own = solver is None
+    s = hip_backend.Solver(0) if own else solver
+    try:
+        return s.match_guided(sets, kps, **kw)
+    finally:
+        if own:
+            s.close()
+
+
+def match_epipolar(des1, kp1, des2, kp2, K, R, t, max_epi_px=3.0, solver=None, **opts):
+    """The matches of des1 (queries, keypoints kp1) against des2 (kp2) that the pose explains: a train keypoint is a candidate
+    of a query only within ``max_epi_px`` of the query's epipolar line under x2 ~ K (R x1 + t) (``ba_match_guided``, epipolar
+    gate).  -> (query_idx, train_idx, distance) int64 arrays in query order.  ``kp*``: (n, 2) arrays or sequences of objects
+    with ``.pt``.  opts: ratio, max_distance, mutual, single.  ``None`` or empty descriptors on either side return no match."""
+    if des1 is None or des2 is None or len(des1) == 0 or len(des2) == 0:
+        return _empty_matches()
+    out = _guided(solver, [_descriptors(des1), _descriptors(des2)], [_positions(kp1), _positions(kp2)],
+                  fundamental=fundamental(K, R, t)[None], max_epi_px=max_epi_px, **opts)
+    return _good_of_pair(out, 0)
+
+
+def match_by_projection(K, R, t, points, point_desc, kp, des, radius_px, image_size=None, solver=None, **opts):
+    """Map points matched into an image by projection under a predicted pose (ORB-SLAM's ``SearchByProjection``): point n with
+    descriptor ``point_desc[n]`` is projected on the host, x ~ K (R X + t), and only the keypoints within ``radius_px`` (a scalar or
+    one per point) of the projection are its candidates (``ba_match_guided``, window gate).  A point with z <= 0, with a
+    projection that is not finite or, given ``image_size = (width, height)``, outside 0 <= x < width, 0 <= y < height gets radius
+    -1: no candidate.  -> (point_idx, kp_idx, distance) int64 arrays in point order: the 3D-2D observations ``ba_resect_ransac``
+    takes.  opts: ratio, max_distance, mutual, single.  ``None`` or empty inputs on either side return no match."""
+    if points is None or point_desc is None or des is None or len(point_desc) == 0 or len(des) == 0:
+        return _empty_matches()
+    X = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    pd = _descriptors(point_desc)
+    if len(X) != len(pd):
+        raise ValueError(f"{len(X)} points for {len(pd)} point descriptors")
+    Xc = X @ np.asarray(R, dtype=np.float64).reshape(3, 3).T + np.asarray(t, dtype=np.float64).reshape(3)
+    x = Xc @ np.asarray(K, dtype=np.float64).reshape(3, 3).T
+    front = Xc[:, 2] > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        uv = x[:, :2] / x[:, 2:3]
+    ok = front & np.isfinite(uv).all(axis=1)
+    if image_size is not None:
+        ok &= (uv[:, 0] >= 0) & (uv[:, 0] < image_size[0]) & (uv[:, 1] >= 0) & (uv[:, 1] < image_size[1])
+    window = np.zeros((len(X), 3), dtype=np.float32)
+    window[:, :2] = np.where(ok[:, None], uv, 0.0)
+    window[:, 2] = np.where(ok, np.broadcast_to(np.asarray(radius_px, dtype=np.float64), (len(X),)), -1.0)
+    kps = _positions(kp)
+    out = _guided(solver, [pd, _descriptors(des)], [np.zeros((len(X), 2), dtype=np.float32), kps], window=window, **opts)
+    return _good_of_pair(out, 0)
 
 
 class BruteForceMatcher:

@@ -119,6 +119,13 @@ class BAMatchOptions(C.Structure):
     _fields_ = [("ratio", C.c_double), ("max_distance", C.c_int32), ("mutual", C.c_int32)]
 
 
+class BAGuidedOptions(C.Structure):
+    _fields_ = [("ratio", C.c_double), ("max_distance", C.c_int32), ("mutual", C.c_int32), ("gate", C.c_int32), ("single", C.c_int32),
+                ("max_epi_px", C.c_double)]
+
+
+GATE = {"window": 1, "epipolar": 2}   # enum BA_GATE_*
+
 # ba_match_descriptors (csrc/ba_match.hpp): queries per workgroup, train descriptors per LDS tile, the shortest train split,
 # the most splits of a pair, the most descriptors of a set, the descriptor widths
 MATCH_BLOCK, MATCH_TILE, MATCH_MIN_SPLIT, MATCH_MAX_SPLITS, MATCH_MAX_SET = 256, 64, 128, 64, 1 << 20
@@ -208,6 +215,10 @@ SYMBOLS = {
     "ba_default_match_options": (C.c_int, [C.POINTER(BAMatchOptions)]),
     "ba_match_descriptors": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.c_int32, _IP, _IP,
                                        C.POINTER(BAMatchOptions), C.POINTER(C.c_int64), _IP, _IP, _IP, _IP, C.POINTER(C.c_uint8), _IP]),
+    "ba_default_guided_options": (C.c_int, [C.POINTER(BAGuidedOptions)]),
+    "ba_match_guided": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.c_int32,
+                                  _IP, _IP, C.POINTER(BAGuidedOptions), C.POINTER(C.c_float), _DP, C.POINTER(C.c_int64), _IP, _IP, _IP, _IP,
+                                  C.POINTER(C.c_uint8), _IP, _IP]),
     "ba_get_centres": (C.c_int, [C.c_void_p, _DP]),
     "ba_transform": (C.c_int, [C.c_void_p, C.POINTER(BASimilarity)]),
     "ba_default_align_options": (C.c_int, [C.POINTER(BAAlignOptions)]),
@@ -329,6 +340,40 @@ def _check(rc):
 
 def _dp(a):
     return a.ctypes.data_as(_DP) if a is not None else None
+
+
+def _match_inputs(sets, pairs):
+    """What ba_match_descriptors and ba_match_guided take of (sets, pairs): the sets as arrays, their width, set_off, the
+    concatenated descriptors, pair_query, pair_train and the number of output rows."""
+    arrs = [np.asarray(a) for a in sets]
+    for a in arrs:
+        if a.dtype != np.uint8 or a.ndim != 2:
+            raise ValueError(f"every descriptor set must be a 2-D uint8 array, not {a.dtype} with shape {a.shape}")
+    widths = {a.shape[1] for a in arrs}
+    if len(widths) > 1:
+        raise ValueError(f"descriptor sets of different widths: {sorted(widths)} bytes")
+    if pairs is None:
+        if len(arrs) not in (0, 2):
+            raise ValueError("pairs=None needs exactly two sets (query, train)")
+        pairs = [(0, 1)] if arrs else []
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    width = widths.pop() if widths else 32
+    set_off = np.zeros(len(arrs) + 1, dtype=np.int64)
+    set_off[1:] = np.cumsum([a.shape[0] for a in arrs])
+    desc = np.ascontiguousarray(np.concatenate(arrs, axis=0)) if arrs else np.zeros((0, width), dtype=np.uint8)
+    ok = pr.shape[0] == 0 or (pr.min() >= 0 and pr.max() < len(arrs))
+    rows = int(sum(arrs[q].shape[0] for q in pr[:, 0])) if ok else 0      # (a bad index is the library's to refuse: it names the field)
+    return arrs, width, set_off, desc, np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1]), rows
+
+
+def _match_outputs(P, rows):
+    """The result dict of a matching call, the good / n_good arrays the library writes, and the calls' common tail of output
+    pointers (row_off, best, second, dist1, dist2, good, n_good)."""
+    out = dict(row_off=np.zeros(P + 1, dtype=np.int64), best=np.empty(rows, dtype=np.int32), second=np.empty(rows, dtype=np.int32),
+               dist1=np.empty(rows, dtype=np.int32), dist2=np.empty(rows, dtype=np.int32))
+    good, n_good = np.zeros(rows, dtype=np.uint8), np.zeros(P, dtype=np.int32)
+    tail = [out["row_off"].ctypes.data_as(C.POINTER(C.c_int64))] + [out[k].ctypes.data_as(_IP) for k in ("best", "second", "dist1", "dist2")]
+    return out, good, n_good, tail + [good.ctypes.data_as(C.POINTER(C.c_uint8)), n_good.ctypes.data_as(_IP)]
 
 
 def device_count():
@@ -759,36 +804,59 @@ class Solver:
         with two sets: [(0, 1)].  opts: ratio, max_distance, mutual.  Returns dict(row_off (P + 1,) int64, best, second, dist1,
         dist2 (rows,) int32, good (rows,) bool, n_good (P,) int32); row row_off[p] + i is query i of pair p; -1 where there is
         no such neighbour.  ValueError for mixed widths or dtypes.  Needs no problem and leaves a resident one as it is."""
-        arrs = [np.asarray(a) for a in sets]
-        for a in arrs:
-            if a.dtype != np.uint8 or a.ndim != 2:
-                raise ValueError(f"every descriptor set must be a 2-D uint8 array, not {a.dtype} with shape {a.shape}")
-        widths = {a.shape[1] for a in arrs}
-        if len(widths) > 1:
-            raise ValueError(f"descriptor sets of different widths: {sorted(widths)} bytes")
-        if pairs is None:
-            if len(arrs) not in (0, 2):
-                raise ValueError("pairs=None needs exactly two sets (query, train)")
-            pairs = [(0, 1)] if arrs else []
-        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-        width = widths.pop() if widths else 32
-        set_off = np.zeros(len(arrs) + 1, dtype=np.int64)
-        set_off[1:] = np.cumsum([a.shape[0] for a in arrs])
-        desc = np.ascontiguousarray(np.concatenate(arrs, axis=0)) if arrs else np.zeros((0, width), dtype=np.uint8)
+        arrs, width, set_off, desc, q, t, rows = _match_inputs(sets, pairs)
         o = self.match_options(**opts)
-        P = pr.shape[0]
-        ok = P == 0 or (pr.min() >= 0 and pr.max() < len(arrs))
-        rows = int(sum(arrs[q].shape[0] for q in pr[:, 0])) if ok else 0      # (a bad index is the library's to refuse: it names the field)
-        out = dict(row_off=np.zeros(P + 1, dtype=np.int64), best=np.empty(rows, dtype=np.int32), second=np.empty(rows, dtype=np.int32),
-                   dist1=np.empty(rows, dtype=np.int32), dist2=np.empty(rows, dtype=np.int32))
-        good, n_good = np.zeros(rows, dtype=np.uint8), np.zeros(P, dtype=np.int32)
-        q, t = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
-        u8 = C.POINTER(C.c_uint8)
-        _check(self._lib.ba_match_descriptors(self._h, width, len(arrs), set_off.ctypes.data_as(C.POINTER(C.c_int64)), desc.ctypes.data_as(u8),
-                                              P, q.ctypes.data_as(_IP), t.ctypes.data_as(_IP), C.byref(o),
-                                              out["row_off"].ctypes.data_as(C.POINTER(C.c_int64)), out["best"].ctypes.data_as(_IP),
-                                              out["second"].ctypes.data_as(_IP), out["dist1"].ctypes.data_as(_IP),
-                                              out["dist2"].ctypes.data_as(_IP), good.ctypes.data_as(u8), n_good.ctypes.data_as(_IP)))
+        out, good, n_good, tail = _match_outputs(len(q), rows)
+        _check(self._lib.ba_match_descriptors(self._h, width, len(arrs), set_off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                              desc.ctypes.data_as(C.POINTER(C.c_uint8)), len(q), q.ctypes.data_as(_IP), t.ctypes.data_as(_IP),
+                                              C.byref(o), *tail))
+        out["good"] = good.astype(bool)
+        out["n_good"] = n_good
+        return out
+
+    def guided_options(self, **kw) -> BAGuidedOptions:
+        """ba_default_guided_options overlaid with kw (any ba_guided_options field; gate by name or value; an unknown one
+        raises TypeError)."""
+        return _options(BAGuidedOptions, self._lib.ba_default_guided_options, kw, names={"gate": lambda g: GATE[g] if isinstance(g, str) else g})
+
+    def match_guided(self, sets, keypoints, pairs=None, *, window=None, fundamental=None, **opts):
+        """ba_match_guided: match_descriptors over the train rows a geometric gate admits.  sets / pairs as there; keypoints: a
+        list of (n_s, 2) pixel positions parallel to sets (stored as float32).  Exactly one of window ((rows, 3): predicted x,
+        y in the train image and radius per query row, in row_off order; radius < 0 disables the row) and fundamental ((P, 3, 3),
+        x_train^T F x_query = 0; one (3, 3) for one pair) is given and picks the gate.  opts: ratio, max_distance, mutual, single,
+        max_epi_px.  Returns match_descriptors' dict plus n_cand (rows,) int32, the number of train rows the gate admits.
+        ValueError for keypoints that do not fit the sets, or for both / neither of window and fundamental."""
+        arrs, width, set_off, desc, q, t, rows = _match_inputs(sets, pairs)
+        kps = list(keypoints)
+        if len(kps) != len(arrs):
+            raise ValueError(f"{len(kps)} keypoint arrays for {len(arrs)} descriptor sets")
+        xy = []
+        for s, (a, k) in enumerate(zip(arrs, kps)):
+            k = np.asarray(k, dtype=np.float32).reshape(-1, 2) if np.size(k) else np.zeros((0, 2), dtype=np.float32)
+            if k.shape[0] != a.shape[0]:
+                raise ValueError(f"set {s}: {k.shape[0]} keypoints for {a.shape[0]} descriptors")
+            xy.append(k)
+        xy = np.ascontiguousarray(np.concatenate(xy, axis=0)) if xy else np.zeros((0, 2), dtype=np.float32)
+        if (window is None) == (fundamental is None):
+            raise ValueError("exactly one of window and fundamental picks the gate")
+        P = len(q)
+        win = F = None
+        if window is not None:
+            win = np.ascontiguousarray(window, dtype=np.float32).reshape(-1, 3)
+            if win.shape[0] != rows:
+                raise ValueError(f"window has {win.shape[0]} rows for {rows} query rows")
+        else:
+            F = np.ascontiguousarray(fundamental, dtype=np.float64).reshape(-1, 3, 3)
+            if F.shape[0] != P:
+                raise ValueError(f"{F.shape[0]} fundamental matrices for {P} pairs")
+        o = self.guided_options(gate="window" if win is not None else "epipolar", **opts)
+        out, good, n_good, tail = _match_outputs(P, rows)
+        out["n_cand"] = np.zeros(rows, dtype=np.int32)
+        fp = C.POINTER(C.c_float)
+        _check(self._lib.ba_match_guided(self._h, width, len(arrs), set_off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                         desc.ctypes.data_as(C.POINTER(C.c_uint8)), xy.ctypes.data_as(fp), P, q.ctypes.data_as(_IP),
+                                         t.ctypes.data_as(_IP), C.byref(o), None if win is None else win.ctypes.data_as(fp), _dp(F), *tail,
+                                         out["n_cand"].ctypes.data_as(_IP)))
         out["good"] = good.astype(bool)
         out["n_good"] = n_good
         return out

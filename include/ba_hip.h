@@ -432,7 +432,8 @@ int ba_relative_pose(ba_handle* h, const double K[9], int32_t n_pairs, const int
  * set_off[0] != 0, a decreasing set_off, a set of more than 2^20 descriptors; desc NULL with descriptors to read; pair_query /
  * pair_train NULL with n_pairs > 0 or an index outside 0 .. n_sets - 1.  A refused call leaves the handle usable.
  * Results are pure integer arithmetic and bit-reproducible; a pair's rows do not depend on the other pairs of the call, nor on
- * how the library splits the train set over workgroups (csrc/ba_match.hpp).  Not offered: float (L2) descriptors, k > 2, masks. */
+ * how the library splits the train set over workgroups (csrc/ba_match.hpp).  Not offered: float (L2) descriptors, k > 2;
+ * candidate masks are ba_match_guided's (below). */
 typedef struct ba_match_options {
   double  ratio;         /* keep a query when (double)d1 < ratio * (double)d2, in fp64 exactly as written; <= 0: no ratio test; default 0.75 */
   int32_t max_distance;  /* keep only d1 <= max_distance; < 0: no test; default -1 */
@@ -443,6 +444,44 @@ int ba_match_descriptors(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const
                          int32_t n_pairs, const int32_t* pair_query, const int32_t* pair_train, const ba_match_options* opts,
                          int64_t* row_off, int32_t* best, int32_t* second, int32_t* dist1, int32_t* dist2,
                          uint8_t* good, int32_t* n_good);
+/* Guided descriptor matching: ba_match_descriptors over the train rows a geometric GATE admits -- the second matching pass of a
+ * pipeline once geometry is known (ORB-SLAM's SearchByProjection / SearchForTriangulation, COLMAP's guided matching).  Sets,
+ * pairs, rows, row_off, the key (distance, index), ties, -1 and every refusal are ba_match_descriptors' (messages name
+ * ba_match_guided); what is added: xy float32[set_off[n_sets]][2], the keypoint position of every descriptor row (as cv2's
+ * KeyPoint.pt), and per call ONE gate kind, options.gate:
+ *   BA_GATE_WINDOW    window float32[rows][3] = (px, py, r) per query row in row_off order: the predicted position of the query
+ *                     in the train image and a radius.  With (x, y) the train row's xy, all widened to double:
+ *                     dx = x - px, dy = y - py; gate(i, j) iff r >= 0 && dx*dx + dy*dy <= r*r.  A negative radius disables
+ *                     the query (a point behind the camera or outside the image).
+ *   BA_GATE_EPIPOLAR  F double[n_pairs][9] row-major with x_train^T F x_query = 0.  With (x1, y1) the query row's own xy and
+ *                     (x, y) the train row's: l0 = (F00*x1 + F01*y1) + F02, l1 and l2 alike from rows 1 and 2;
+ *                     n = l0*l0 + l1*l1; e = (l0*x + l1*y) + l2; gate(i, j) iff n > 0 && e*e <= (max_epi_px*max_epi_px) * n.
+ *                     One-sided: the train keypoint against the query's line.
+ * The gate is evaluated in fp64, every operation rounded on its own as written (no fused multiply-add), so an IEEE double
+ * evaluation of the same expressions decides every case identically, border cases included.  A NaN anywhere (xy, window) fails
+ * the comparison and so the gate; non-finite xy / window values are not refused.
+ * Results: the 2-NN of query i is taken over { j : gate(i, j) } under the same key; n_cand int32[rows] is that set's size.  good
+ * as in ba_match_descriptors with one change: with single = 1 a query with best >= 0 and second < 0 passes the ratio test (a
+ * search window often holds one keypoint; max_distance is the guard then).  mutual: (i, j) is kept only if i is the lowest
+ * (distance, index) among the queries i' with gate(i', j) -- the same predicate.  Results are bit-reproducible and do not
+ * depend on the other pairs of the call nor on the split of the train set.  Any output may be NULL.
+ * BA_ERR_INVALID in addition, naming the field: xy NULL with rows present; gate not 1 or 2; single not 0 / 1; WINDOW: window NULL
+ * with query rows present; EPIPOLAR: F NULL with n_pairs > 0, a non-finite entry of F, max_epi_px not finite or negative.
+ * Not offered: both gates in one call, a symmetric epipolar distance, scale / octave gates, candidate lists. */
+enum { BA_GATE_WINDOW = 1, BA_GATE_EPIPOLAR = 2 };
+typedef struct ba_guided_options {
+  double  ratio;         /* as ba_match_options; default 0.75 */
+  int32_t max_distance;  /* as ba_match_options; default -1 */
+  int32_t mutual;        /* as ba_match_options, under the gate; default 0 */
+  int32_t gate;          /* BA_GATE_WINDOW or BA_GATE_EPIPOLAR; no default: 0 is refused */
+  int32_t single;        /* 1: a query whose gate admits exactly one train row passes the ratio test; default 1 */
+  double  max_epi_px;    /* EPIPOLAR: largest distance of the train keypoint from the query's epipolar line; default 3.0 */
+} ba_guided_options;     /* 32 bytes */
+int ba_default_guided_options(ba_guided_options* opts);    /* 0.75, -1, 0, 0, 1, 3.0 */
+int ba_match_guided(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc, const float* xy,
+                    int32_t n_pairs, const int32_t* pair_query, const int32_t* pair_train, const ba_guided_options* opts,
+                    const float* window, const double* F, int64_t* row_off, int32_t* best, int32_t* second, int32_t* dist1,
+                    int32_t* dist2, uint8_t* good, int32_t* n_good, int32_t* n_cand);
 /* Similarity transform of the reconstruction and robust alignment to reference positions: the step after an adjustment that
  * moves the result into the frame its user needs (georegistration onto GPS / surveyed camera positions or ground-control
  * points -- COLMAP's model_aligner; the comparison of two gauge-free solves; re-centring / re-scaling).  No reference
