@@ -4,4 +4,4 @@ from .map_structures import Keyframe, KeyPoint, Map, MapPoint  # noqa: F401
 from .problem import BAProblem  # noqa: F401
 from .bundle_adjuster import BundleAdjuster  # noqa: F401
 from .pose_estimator import estimate_pose, relative_pose  # noqa: F401
-from .features import BruteForceMatcher, fundamental, match, match_by_projection, match_epipolar  # noqa: F401
+from .features import BruteForceMatcher, ORBExtractor, fundamental, match, match_by_projection, match_epipolar  # noqa: F401

@@ -44,6 +44,7 @@
 #include "ba_relpose.hpp"
 #include "ba_match.hpp"
 #include "ba_match_guided.hpp"
+#include "ba_orb.hpp"
 
 using namespace ba;
 
@@ -306,6 +307,21 @@ struct ba_handle {
   DBuf<float> mg_xy, mg_win;
   DBuf<double> mg_F, mg_rec;
   DBuf<int> mg_cnt, mg_ncand;
+  // ba_orb_extract (ba_orb.hpp): the pyramid, score and blurred images of the batch (level-major), the score histograms, the
+  // cuts, the per-row counts (above | on the cut), the stage-1 lists and their Hs, the pattern, and the outputs by row:
+  // xy | size | angle | response, octave | level_xy | n_kp, cs, desc
+  DBuf<unsigned char> orb_pyr, orb_score, orb_blur, orb_desc;
+  DBuf<unsigned> orb_hist;
+  DBuf<OrbCut> orb_cut;
+  DBuf<int> orb_rows, orb_list, orb_i;
+  DBuf<long long> orb_hs;
+  DBuf<signed char> orb_pat;
+  DBuf<float> orb_f;
+  DBuf<double> orb_cs;
+  PinnedStage orb_stage;                       // what the call reads back: cs | xy size angle response | octave level_xy | n_kp | desc
+  bool orb_timing = false;                     // ba_orb_stage_times: events around the stages of ba_orb_extract
+  hipEvent_t orb_ev[BA_ORB_STAGES + 1] = {};
+  double orb_ms[BA_ORB_STAGES] = {};
   // ba_transform / ba_align / ba_get_centres (ba_similarity.hpp): correspondences a | b | w | u | err (9 doubles each), the
   // per-workgroup partial rows, the device record (similarity, centroids, status)
   DBuf<double> sim_buf, sim_part;
@@ -497,6 +513,7 @@ extern "C" int ba_destroy(ba_handle* h) {
   ipc_destroy(h);
   shm_destroy(h);
   for (auto e : h->ev) (void)hipEventDestroy(e);
+  for (auto e : h->orb_ev) if (e) (void)hipEventDestroy(e);
   if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;                    // every buffer the handle owns goes with it
@@ -3937,6 +3954,196 @@ extern "C" int ba_match_guided(ba_handle* h, int32_t desc_bytes, int32_t n_sets,
   if (int rc = match_fetch(h, nr, np, best, second, dist1, dist2, good, n_good)) return rc;
   if (n_cand) HIPCHECK(hipMemcpyAsync(n_cand, h->mg_ncand.p, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   BA_SYNC(h);
+  return BA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- ORB extraction
+// ba_orb_extract (csrc/ba_orb.hpp): pyramid, FAST-9, Harris ranking, orientation, steered BRIEF.  Needs no problem.
+static_assert(sizeof(ba_orb_options) == 24, "ba_orb_options (include/ba_hip.h)");
+constexpr int ORB_MAX_FEATURES = 65536, ORB_MAX_IMAGES = 1024;
+constexpr long long ORB_MAX_PIXELS = 1LL << 26, ORB_MAX_BATCH_PIXELS = 1LL << 28;
+extern "C" int ba_default_orb_options(ba_orb_options* o) {
+  if (!o) return fail(BA_ERR_INVALID, "null argument");
+  memset(o, 0, sizeof *o);
+  o->scale_factor = 1.2;
+  o->n_features = 3000;
+  o->n_levels = 8;
+  o->edge_threshold = 31;
+  o->fast_threshold = 20;
+  return BA_OK;
+}
+extern "C" int ba_orb_default_pattern(int8_t* pattern) {
+  if (!pattern) return fail(BA_ERR_INVALID, "null argument");
+  memcpy(pattern, kOrbDefaultPattern, sizeof kOrbDefaultPattern);
+  return BA_OK;
+}
+static int orb_check_options(const char* who, const ba_orb_options* o, int32_t height, int32_t width) {
+  if (!(o->scale_factor > 1.0) || !(o->scale_factor <= 2.0)) return fail(BA_ERR_INVALID, "%s: scale_factor must be above 1 and at most 2", who);
+  if (o->n_features < 1 || o->n_features > ORB_MAX_FEATURES)
+    return fail(BA_ERR_INVALID, "%s: n_features %d is outside 1 .. %d", who, o->n_features, ORB_MAX_FEATURES);
+  if (o->n_levels < 1 || o->n_levels > ORB_MAX_LEVELS) return fail(BA_ERR_INVALID, "%s: n_levels %d is outside 1 .. %d", who, o->n_levels, ORB_MAX_LEVELS);
+  if (o->edge_threshold < 25) return fail(BA_ERR_INVALID, "%s: edge_threshold %d is below 25", who, o->edge_threshold);
+  if (o->fast_threshold < 1 || o->fast_threshold > 254) return fail(BA_ERR_INVALID, "%s: fast_threshold %d is outside 1 .. 254", who, o->fast_threshold);
+  if (height <= 0) return fail(BA_ERR_INVALID, "%s: height %d is not positive", who, height);
+  if (width <= 0) return fail(BA_ERR_INVALID, "%s: width %d is not positive", who, width);
+  return BA_OK;
+}
+// The definition's levels (include/ba_hip.h): every operation on its own, in the order written there
+static void orb_levels(const ba_orb_options* o, int32_t height, int32_t width, int32_t* lw, int32_t* lh, double* ls, int32_t* lq) {
+  const int L = o->n_levels;
+  double s = 1.0;
+  for (int l = 0; l < L; ++l) {
+    if (l > 0) s = s * o->scale_factor;
+    ls[l] = s;
+    lw[l] = (int32_t)std::nearbyint((double)width / s);
+    lh[l] = (int32_t)std::nearbyint((double)height / s);
+  }
+  const double f = 1.0 / o->scale_factor;
+  double p = 1.0;
+  for (int l = 0; l < L; ++l) p = p * f;
+  if (L == 1) { lq[0] = o->n_features; return; }
+  double d = (double)o->n_features * (1.0 - f) / (1.0 - p);
+  int sum = 0;
+  for (int l = 0; l < L - 1; ++l) {
+    lq[l] = std::min((int32_t)std::nearbyint(d), o->n_features - sum);      // (the roundings of a small n_features can add up to more)
+    sum += lq[l];
+    d = d * f;
+  }
+  lq[L - 1] = o->n_features - sum;
+}
+extern "C" int ba_orb_levels(const ba_orb_options* opts, int32_t height, int32_t width, int32_t* level_w, int32_t* level_h,
+                             double* level_scale, int32_t* level_quota) {
+  if (!opts) return fail(BA_ERR_INVALID, "null argument");
+  if (int rc = orb_check_options("ba_orb_levels", opts, height, width)) return rc;
+  int32_t lw[ORB_MAX_LEVELS], lh[ORB_MAX_LEVELS], lq[ORB_MAX_LEVELS];
+  double ls[ORB_MAX_LEVELS];
+  orb_levels(opts, height, width, lw, lh, ls, lq);
+  const size_t L = (size_t)opts->n_levels;
+  if (level_w) memcpy(level_w, lw, L * sizeof(int32_t));
+  if (level_h) memcpy(level_h, lh, L * sizeof(int32_t));
+  if (level_scale) memcpy(level_scale, ls, L * sizeof(double));
+  if (level_quota) memcpy(level_quota, lq, L * sizeof(int32_t));
+  return BA_OK;
+}
+extern "C" int ba_orb_stage_times(ba_handle* h, int32_t enable, double* ms) {
+  if (!h) return fail(BA_ERR_INVALID, "null handle");
+  if (enable < -1 || enable > 1) return fail(BA_ERR_INVALID, "ba_orb_stage_times: enable %d is not -1, 0 or 1", enable);
+  if (set_device(h)) return BA_ERR_HIP;
+  if (enable == 1)
+    for (auto& e : h->orb_ev)
+      if (!e) HIPCHECK(hipEventCreate(&e));
+  if (enable >= 0) h->orb_timing = enable != 0;
+  if (ms) memcpy(ms, h->orb_ms, sizeof h->orb_ms);
+  return BA_OK;
+}
+extern "C" int ba_orb_extract(ba_handle* h, int32_t n_images, int32_t height, int32_t width, const uint8_t* images, const int8_t* pattern,
+                              const ba_orb_options* opts, int32_t* n_kp, float* xy, float* size, float* angle, float* response,
+                              int32_t* octave, int32_t* level_xy, double* cs, uint8_t* desc) {
+  if (!h || !opts) return fail(BA_ERR_INVALID, "null argument");
+  if (int rc = orb_check_options("ba_orb_extract", opts, height, width)) return rc;
+  if (n_images < 0 || n_images > ORB_MAX_IMAGES) return fail(BA_ERR_INVALID, "ba_orb_extract: n_images %d is outside 0 .. %d", n_images, ORB_MAX_IMAGES);
+  if (n_images > 0 && !images) return fail(BA_ERR_INVALID, "ba_orb_extract: null images");
+  const long long px = (long long)height * width;
+  if (px > ORB_MAX_PIXELS) return fail(BA_ERR_INVALID, "ba_orb_extract: height * width = %lld is above the cap of %lld pixels", px, ORB_MAX_PIXELS);
+  if (px * n_images > ORB_MAX_BATCH_PIXELS)
+    return fail(BA_ERR_INVALID, "ba_orb_extract: the batch n_images * height * width = %lld is above the cap of %lld pixels", px * n_images, ORB_MAX_BATCH_PIXELS);
+  const int8_t* pat = pattern ? pattern : &kOrbDefaultPattern[0][0];
+  for (int i = 0; i < 1024; ++i)
+    if (pat[i] < -15 || pat[i] > 15)
+      return fail(BA_ERR_INVALID, "ba_orb_extract: pattern row %d holds the coordinate %d, outside -15 .. 15", i / 4, (int)pat[i]);
+  const size_t B = (size_t)n_images, N = (size_t)opts->n_features;
+  if (n_kp) memset(n_kp, 0, B * sizeof(int32_t));
+  int32_t lw[ORB_MAX_LEVELS], lh[ORB_MAX_LEVELS], lq[ORB_MAX_LEVELS];
+  double ls[ORB_MAX_LEVELS];
+  orb_levels(opts, height, width, lw, lh, ls, lq);
+  const int edge = opts->edge_threshold;
+  OrbArgs a = {};
+  while (a.n_levels < opts->n_levels && lw[a.n_levels] > 2 * edge && lh[a.n_levels] > 2 * edge) ++a.n_levels;   // (sizes do not grow)
+  if (B == 0 || a.n_levels == 0) return BA_OK;       // no image, or none with an interior: zero keypoints
+  if (set_device(h)) return BA_ERR_HIP;
+  const int L = a.n_levels;
+  a.n_features = opts->n_features; a.edge = edge; a.thr = opts->fast_threshold; a.n_images = n_images;
+  long long pix = 0;
+  int max_cap = 0;
+  for (int l = 0; l < L; ++l) {
+    a.w[l] = lw[l]; a.h[l] = lh[l]; a.quota[l] = lq[l]; a.scale[l] = ls[l];
+    a.row0[l] = a.rows; a.rows += lh[l];
+    a.list0[l] = a.list_cap; a.list_cap += 2 * lq[l];
+    a.off[l] = pix; pix += (long long)B * lw[l] * lh[l];
+    max_cap = std::max(max_cap, 2 * lq[l]);
+  }
+  const size_t npx = (size_t)pix, cap = (size_t)std::max(a.list_cap, 1);
+  HIPCHECK(h->orb_pyr.alloc(npx)); HIPCHECK(h->orb_score.alloc(npx)); HIPCHECK(h->orb_blur.alloc(npx));
+  HIPCHECK(h->orb_hist.alloc(B * L * 256)); HIPCHECK(h->orb_cut.alloc(B * L)); HIPCHECK(h->orb_rows.alloc(2 * B * a.rows));
+  HIPCHECK(h->orb_list.alloc(B * cap)); HIPCHECK(h->orb_hs.alloc(B * cap)); HIPCHECK(h->orb_pat.alloc(1024));
+  HIPCHECK(h->orb_f.alloc(5 * B * N)); HIPCHECK(h->orb_i.alloc(3 * B * N + B)); HIPCHECK(h->orb_cs.alloc(2 * B * N)); HIPCHECK(h->orb_desc.alloc(32 * B * N));
+  a.pyr = h->orb_pyr.p; a.score = h->orb_score.p; a.blur = h->orb_blur.p; a.hist = h->orb_hist.p; a.cut = h->orb_cut.p;
+  a.row_a = h->orb_rows.p; a.row_b = h->orb_rows.p + B * a.rows; a.list = h->orb_list.p; a.hs = h->orb_hs.p; a.pattern = h->orb_pat.p;
+  a.xy = h->orb_f.p; a.size = a.xy + 2 * B * N; a.angle = a.size + B * N; a.response = a.angle + B * N;
+  a.octave = h->orb_i.p; a.level_xy = a.octave + B * N; a.n_kp = a.level_xy + 2 * B * N;
+  a.cs = h->orb_cs.p; a.desc = h->orb_desc.p;
+  int stamp = 0;
+#define ORB_STAMP() do { if (h->orb_timing) HIPCHECK(hipEventRecord(h->orb_ev[stamp++], h->stream)); } while (0)
+  ORB_STAMP();
+  HIPCHECK(hipMemcpyAsync(h->orb_pyr.p, images, B * (size_t)px, hipMemcpyHostToDevice, h->stream));      // level 0 of every image
+  HIPCHECK(hipMemcpyAsync(h->orb_pat.p, pat, 1024, hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemsetAsync(h->orb_hist.p, 0, B * L * 256 * sizeof(unsigned), h->stream));
+  const unsigned nb = (unsigned)B;
+  auto tiles = [&](int l) { return dim3((unsigned)((a.w[l] + ORB_TILE_W - 1) / ORB_TILE_W), (unsigned)((a.h[l] + ORB_TILE_H - 1) / ORB_TILE_H), nb); };
+  ORB_STAMP();
+  for (int l = 1; l < L; ++l)
+    BA_LAUNCH(k_orb_resize, dim3((unsigned)((a.w[l] * a.h[l] + ORB_THREADS - 1) / ORB_THREADS), nb), dim3(ORB_THREADS), 0, h->stream, a, l);
+  ORB_STAMP();
+  for (int l = 0; l < L; ++l) BA_LAUNCH(k_orb_fast, tiles(l), dim3(ORB_THREADS), 0, h->stream, a, l);
+  ORB_STAMP();
+  BA_LAUNCH(k_orb_cut, dim3(nb), dim3(64), 0, h->stream, a);
+  BA_LAUNCH(k_orb_rowcount, dim3((unsigned)a.rows, nb), dim3(64), 0, h->stream, a);
+  BA_LAUNCH(k_orb_scan, dim3((unsigned)L, nb), dim3(ORB_THREADS), 0, h->stream, a);
+  BA_LAUNCH(k_orb_compact, dim3((unsigned)a.rows, nb), dim3(64), 0, h->stream, a);
+  ORB_STAMP();
+  if (max_cap > 0) {
+    const dim3 grid((unsigned)((max_cap + ORB_THREADS - 1) / ORB_THREADS), (unsigned)L, nb);
+    BA_LAUNCH(k_orb_harris, grid, dim3(ORB_THREADS), 0, h->stream, a);
+    BA_LAUNCH(k_orb_rank, grid, dim3(ORB_THREADS), 0, h->stream, a);
+  }
+  ORB_STAMP();
+  for (int l = 0; l < L; ++l) BA_LAUNCH(k_orb_blur, tiles(l), dim3(ORB_THREADS), 0, h->stream, a, l);
+  ORB_STAMP();
+  BA_LAUNCH(k_orb_describe, dim3((unsigned)((N + ORB_KP_PER_BLOCK - 1) / ORB_KP_PER_BLOCK), nb), dim3(ORB_THREADS), 0, h->stream, a);
+  ORB_STAMP();
+  // the outputs come back whole (stride n_features) into pinned staging; only the rows an image owns go to the caller's arrays
+  const size_t stage_bytes = 2 * B * N * sizeof(double) + 5 * B * N * sizeof(float) + (3 * B * N + B) * sizeof(int32_t) + 32 * B * N;
+  HIPCHECK(h->orb_stage.reserve(stage_bytes, stage_bytes + stage_bytes / 2, h->stream));      // pinned, kept with the handle
+  double* const hc = (double*)h->orb_stage.p;
+  float* const hf = (float*)(hc + 2 * B * N);
+  int32_t* const hi = (int32_t*)(hf + 5 * B * N);
+  int32_t* const hn = hi + 3 * B * N;
+  uint8_t* const hd = (uint8_t*)(hn + B);
+  HIPCHECK(hipMemcpyAsync(hn, a.n_kp, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (xy || size || angle || response) HIPCHECK(hipMemcpyAsync(hf, h->orb_f.p, 5 * B * N * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (octave || level_xy) HIPCHECK(hipMemcpyAsync(hi, h->orb_i.p, 3 * B * N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (cs) HIPCHECK(hipMemcpyAsync(hc, h->orb_cs.p, 2 * B * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (desc) HIPCHECK(hipMemcpyAsync(hd, h->orb_desc.p, 32 * B * N, hipMemcpyDeviceToHost, h->stream));
+  ORB_STAMP();
+#undef ORB_STAMP
+  BA_SYNC(h);
+  for (int k = 0; k + 1 < stamp; ++k) {
+    float ms = 0;
+    HIPCHECK(hipEventElapsedTime(&ms, h->orb_ev[k], h->orb_ev[k + 1]));
+    h->orb_ms[k] = ms;
+  }
+  for (size_t b = 0; b < B; ++b) {
+    const size_t n = std::min((size_t)std::max(hn[b], 0), N), r = b * N;      // (n_kp <= n_features: the quotas sum to it)
+    if (n_kp) n_kp[b] = (int32_t)n;
+    if (xy) memcpy(xy + 2 * r, hf + 2 * r, 2 * n * sizeof(float));
+    if (size) memcpy(size + r, hf + 2 * B * N + r, n * sizeof(float));
+    if (angle) memcpy(angle + r, hf + 3 * B * N + r, n * sizeof(float));
+    if (response) memcpy(response + r, hf + 4 * B * N + r, n * sizeof(float));
+    if (octave) memcpy(octave + r, hi + r, n * sizeof(int32_t));
+    if (level_xy) memcpy(level_xy + 2 * r, hi + B * N + 2 * r, 2 * n * sizeof(int32_t));
+    if (cs) memcpy(cs + 2 * r, hc + 2 * r, 2 * n * sizeof(double));
+    if (desc) memcpy(desc + 32 * r, hd + 32 * r, 32 * n);
+  }
   return BA_OK;
 }
 

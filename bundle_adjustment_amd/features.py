@@ -1,9 +1,16 @@
-"""Descriptor matching -- the step that produces the matches everything downstream starts from.
+"""Feature extraction and descriptor matching -- the steps that produce the keypoints and matches everything downstream starts
+from.
 
-Mirrors ``BruteForceMatcher.match`` of ``src/features.py`` (``cv2.BFMatcher(NORM_HAMMING, crossCheck=False).knnMatch(des1, des2,
+``ORBExtractor.extract`` stands where ``ORBExtractor.extract`` of ``src/features.py`` does (``cv2.ORB_create(nfeatures=3000)
+.detectAndCompute(gray, None)``) and runs on the GPU (``ba_orb_extract``): ORB by the published algorithm -- multi-scale FAST-9,
+Harris ranking, intensity-centroid orientation, steered BRIEF on a blurred pyramid.  It is NOT cv2's output: neither the
+keypoints nor the descriptors are claimed equal to cv2's, and the default test pattern is not OpenCV's learned one (pass that
+table as ``pattern`` if you have it); descriptors match only descriptors made with the same pattern.
+
+The matcher mirrors ``BruteForceMatcher.match`` of ``src/features.py`` (``cv2.BFMatcher(NORM_HAMMING, crossCheck=False).knnMatch(des1, des2,
 k=2)`` then Lowe's ``m.distance < 0.75 * n.distance``) on the GPU (``ba_match_descriptors``: brute-force Hamming 2-nearest
 neighbours, ties to the lower train index, the ratio test in fp64).  The match objects are duck-typed for
-``pose_estimator.estimate_pose``, which reads ``queryIdx`` / ``trainIdx``.  No cv2 is needed; ORB extraction is not offered.
+``pose_estimator.estimate_pose``, which reads ``queryIdx`` / ``trainIdx``.  No cv2 is needed.
 Once geometry is known, ``match_epipolar`` and ``match_by_projection`` match a second time under it (``ba_match_guided``: the
 same 2-NN over the keypoints an epipolar line or a search window admits; no counterpart in the reference).
 No CPU fallback: without the library / a GPU the call raises.
@@ -173,3 +180,62 @@ class BruteForceMatcher:
         if des1 is None or des2 is None:
             return []
         return _match_list(*match(des1, des2, solver=self.solver, ratio=self.ratio))
+
+
+class KeyPoint:
+    """What the pipeline reads of a ``cv2.KeyPoint``: ``pt`` (x, y) in pixels of the full image, ``size`` (patch diameter),
+    ``angle`` (degrees in [0, 360)), ``response`` (Harris), ``octave`` (pyramid level), ``class_id`` (-1)."""
+    __slots__ = ("pt", "size", "angle", "response", "octave", "class_id")
+
+    def __init__(self, x, y, size, angle=-1.0, response=0.0, octave=0, class_id=-1):
+        self.pt, self.size, self.angle = (float(x), float(y)), float(size), float(angle)
+        self.response, self.octave, self.class_id = float(response), int(octave), int(class_id)
+
+    def __repr__(self):
+        return f"KeyPoint(pt={self.pt}, size={self.size}, angle={self.angle}, response={self.response}, octave={self.octave})"
+
+
+def to_gray(bgr):
+    """(H, W, 3) uint8 BGR -> (H, W) uint8 grey, the 14-bit fixed-point weights of ``cv2.cvtColor(..., COLOR_BGR2GRAY)``:
+    (1868 B + 9617 G + 4899 R + 8192) >> 14.  Numpy on the host; a 2-D array is returned as it is."""
+    a = np.asarray(bgr)
+    if a.dtype != np.uint8:
+        raise ValueError(f"the image must be uint8, not {a.dtype}")
+    if a.ndim == 2:
+        return a
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"the image must be (H, W) or (H, W, 3), not {a.shape}")
+    c = a.astype(np.uint32)
+    return ((1868 * c[..., 0] + 9617 * c[..., 1] + 4899 * c[..., 2] + 8192) >> 14).astype(np.uint8)
+
+
+def extract(images, solver=None, pattern=None, **opts):
+    """``hip_backend.Solver.extract_orb`` of one grey image (H, W) or a batch (n, H, W) of one size -> its dict of arrays
+    (kp_off, n_kp, xy, size, angle, response, octave, level_xy, cs, desc).  opts: n_features, scale_factor, n_levels,
+    edge_threshold, fast_threshold.  ``solver``: a ``hip_backend.Solver`` to run on (its resident problem is not touched);
+    default: one on device 0 for the call."""
+    own = solver is None
+    s = hip_backend.Solver(0) if own else solver
+    try:
+        return s.extract_orb(images, pattern=pattern, **opts)
+    finally:
+        if own:
+            s.close()
+
+
+class ORBExtractor:
+    """Drop-in for the reference's ``ORBExtractor``: ``extract(image)`` -> (list of ``KeyPoint``, uint8 (n, 32) descriptors), or
+    ``([], None)`` when the image has no keypoint.  A colour image (H, W, 3) is taken as BGR (``to_gray``).  ORB by the published
+    algorithm on the GPU, not cv2's keypoints or pattern (the module docstring)."""
+
+    def __init__(self, n_features=3000, solver=None, pattern=None, **opts):
+        self.n_features, self.solver, self.pattern, self.opts = n_features, solver, pattern, opts
+
+    def extract(self, image):
+        out = extract(to_gray(image), solver=self.solver, pattern=self.pattern, n_features=self.n_features, **self.opts)
+        n = int(out["n_kp"][0])
+        if n == 0:
+            return [], None
+        kps = [KeyPoint(x, y, sz, an, rs, oc) for (x, y), sz, an, rs, oc in zip(out["xy"].tolist(), out["size"].tolist(), out["angle"].tolist(),
+                                                                                 out["response"].tolist(), out["octave"].tolist())]
+        return kps, out["desc"]

@@ -124,12 +124,20 @@ class BAGuidedOptions(C.Structure):
                 ("max_epi_px", C.c_double)]
 
 
+class BAOrbOptions(C.Structure):
+    _fields_ = [("scale_factor", C.c_double), ("n_features", C.c_int32), ("n_levels", C.c_int32), ("edge_threshold", C.c_int32),
+                ("fast_threshold", C.c_int32)]
+
+
 GATE = {"window": 1, "epipolar": 2}   # enum BA_GATE_*
 
 # ba_match_descriptors (csrc/ba_match.hpp): queries per workgroup, train descriptors per LDS tile, the shortest train split,
 # the most splits of a pair, the most descriptors of a set, the descriptor widths
 MATCH_BLOCK, MATCH_TILE, MATCH_MIN_SPLIT, MATCH_MAX_SPLITS, MATCH_MAX_SET = 256, 64, 128, 64, 1 << 20
 MATCH_DESC_BYTES = (8, 16, 24, 32, 40, 48, 56, 64)
+# ba_orb_extract (csrc/ba_orb.hpp): the tile of the FAST and blur kernels, the most levels, and the caps of a call
+ORB_TILE_W, ORB_TILE_H, ORB_MAX_LEVELS, ORB_MAX_FEATURES, ORB_MAX_IMAGES = 64, 16, 16, 65536, 1024
+ORB_STAGES = ("upload", "pyramid", "fast", "select", "harris_rank", "blur", "describe", "download")   # ba_orb_stage_times
 
 
 class BASimilarity(C.Structure):
@@ -219,6 +227,13 @@ SYMBOLS = {
     "ba_match_guided": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.c_int32,
                                   _IP, _IP, C.POINTER(BAGuidedOptions), C.POINTER(C.c_float), _DP, C.POINTER(C.c_int64), _IP, _IP, _IP, _IP,
                                   C.POINTER(C.c_uint8), _IP, _IP]),
+    "ba_default_orb_options": (C.c_int, [C.POINTER(BAOrbOptions)]),
+    "ba_orb_default_pattern": (C.c_int, [C.POINTER(C.c_int8)]),
+    "ba_orb_levels": (C.c_int, [C.POINTER(BAOrbOptions), C.c_int32, C.c_int32, _IP, _IP, _DP, _IP]),
+    "ba_orb_extract": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_int8),
+                                 C.POINTER(BAOrbOptions), _IP, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                 C.POINTER(C.c_float), _IP, _IP, _DP, C.POINTER(C.c_uint8)]),
+    "ba_orb_stage_times": (C.c_int, [C.c_void_p, C.c_int32, _DP]),
     "ba_get_centres": (C.c_int, [C.c_void_p, _DP]),
     "ba_transform": (C.c_int, [C.c_void_p, C.POINTER(BASimilarity)]),
     "ba_default_align_options": (C.c_int, [C.POINTER(BAAlignOptions)]),
@@ -374,6 +389,31 @@ def _match_outputs(P, rows):
     good, n_good = np.zeros(rows, dtype=np.uint8), np.zeros(P, dtype=np.int32)
     tail = [out["row_off"].ctypes.data_as(C.POINTER(C.c_int64))] + [out[k].ctypes.data_as(_IP) for k in ("best", "second", "dist1", "dist2")]
     return out, good, n_good, tail + [good.ctypes.data_as(C.POINTER(C.c_uint8)), n_good.ctypes.data_as(_IP)]
+
+
+def orb_options(**kw) -> BAOrbOptions:
+    """ba_default_orb_options overlaid with kw (any ba_orb_options field; an unknown one raises TypeError)."""
+    return _options(BAOrbOptions, load_library().ba_default_orb_options, kw, names={})
+
+
+def orb_default_pattern():
+    """ba_orb_default_pattern: the (256, 4) int8 test pairs (x1, y1, x2, y2) the extractor uses when none is given.  No GPU."""
+    pat = np.zeros((256, 4), dtype=np.int8)
+    _check(load_library().ba_orb_default_pattern(pat.ctypes.data_as(C.POINTER(C.c_int8))))
+    return pat
+
+
+def orb_levels(height, width, **opts):
+    """ba_orb_levels: (level_w, level_h int32, level_scale float64, level_quota int32), n_levels entries each.  No GPU."""
+    o = orb_options(**opts)
+    L = max(int(o.n_levels), 0)
+    w, h, q = np.zeros(L, dtype=np.int32), np.zeros(L, dtype=np.int32), np.zeros(L, dtype=np.int32)
+    sc = np.zeros(L, dtype=np.float64)
+    if not 1 <= L <= ORB_MAX_LEVELS:            # (the library refuses it by name; the arrays above must not be overrun)
+        w = h = q = sc = None
+    _check(load_library().ba_orb_levels(C.byref(o), int(height), int(width), None if w is None else w.ctypes.data_as(_IP),
+                                        None if h is None else h.ctypes.data_as(_IP), _dp(sc), None if q is None else q.ctypes.data_as(_IP)))
+    return w, h, sc, q
 
 
 def device_count():
@@ -860,6 +900,51 @@ class Solver:
         out["good"] = good.astype(bool)
         out["n_good"] = n_good
         return out
+
+    def extract_orb(self, images, pattern=None, **opts):
+        """ba_orb_extract: ORB keypoints and descriptors of a batch of grey images -- (H, W) or (n, H, W) uint8 of one size.
+        pattern: (256, 4) int8 test pairs within +-15 (None: orb_default_pattern()).  opts: scale_factor, n_features, n_levels,
+        edge_threshold, fast_threshold.  Returns dict(kp_off (n + 1,) int64, n_kp (n,) int32, xy (K, 2) float32, size, angle,
+        response (K,) float32, octave (K,) int32, level_xy (K, 2) int32, cs (K, 2) float64, desc (K, 32) uint8): image b owns rows
+        kp_off[b] .. kp_off[b + 1] - 1.  ORB by the published algorithm, not cv2's keypoints or pattern (include/ba_hip.h).
+        Needs no problem and leaves a resident one as it is."""
+        imgs = np.asarray(images)
+        if imgs.dtype != np.uint8 or imgs.ndim not in (2, 3):
+            raise ValueError(f"images must be a uint8 array (H, W) or (n, H, W), not {imgs.dtype} with shape {imgs.shape}")
+        imgs = np.ascontiguousarray(imgs if imgs.ndim == 3 else imgs[None])
+        n, H, W = imgs.shape
+        pat = None
+        if pattern is not None:
+            pat = np.asarray(pattern)
+            if pat.shape != (256, 4) or not np.issubdtype(pat.dtype, np.integer):
+                raise ValueError(f"pattern must be a (256, 4) integer array, not {pat.dtype} with shape {pat.shape}")
+            if pat.min() < -128 or pat.max() > 127:
+                raise ValueError("pattern coordinates must fit int8")
+            pat = np.ascontiguousarray(pat, dtype=np.int8)
+        o = orb_options(**opts)
+        N = min(max(int(o.n_features), 0), ORB_MAX_FEATURES)      # (a bad n_features is the library's to refuse: it names it)
+        full = dict(xy=np.empty((n * N, 2), np.float32), size=np.empty(n * N, np.float32), angle=np.empty(n * N, np.float32),
+                    response=np.empty(n * N, np.float32), octave=np.empty(n * N, np.int32), level_xy=np.empty((n * N, 2), np.int32),
+                    cs=np.empty((n * N, 2), np.float64), desc=np.empty((n * N, 32), np.uint8))
+        n_kp = np.zeros(n, dtype=np.int32)
+        fp = C.POINTER(C.c_float)
+        _check(self._lib.ba_orb_extract(self._h, n, H, W, imgs.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                        None if pat is None else pat.ctypes.data_as(C.POINTER(C.c_int8)), C.byref(o), n_kp.ctypes.data_as(_IP),
+                                        full["xy"].ctypes.data_as(fp), full["size"].ctypes.data_as(fp), full["angle"].ctypes.data_as(fp),
+                                        full["response"].ctypes.data_as(fp), full["octave"].ctypes.data_as(_IP),
+                                        full["level_xy"].ctypes.data_as(_IP), _dp(full["cs"]), full["desc"].ctypes.data_as(C.POINTER(C.c_uint8))))
+        keep = np.concatenate([b * N + np.arange(int(n_kp[b])) for b in range(n)]) if n else np.zeros(0, dtype=np.int64)
+        out = {k: np.ascontiguousarray(v[keep]) for k, v in full.items()}
+        out["n_kp"] = n_kp
+        out["kp_off"] = np.concatenate([[0], np.cumsum(n_kp, dtype=np.int64)]).astype(np.int64)
+        return out
+
+    def orb_stage_times(self, enable=None):
+        """ba_orb_stage_times: enable=True / False switches the stage events of extract_orb on / off (None: as it is); returns
+        the stage times of the last timed call in milliseconds, a dict keyed by ORB_STAGES."""
+        ms = np.zeros(len(ORB_STAGES))
+        _check(self._lib.ba_orb_stage_times(self._h, -1 if enable is None else int(bool(enable)), _dp(ms)))
+        return dict(zip(ORB_STAGES, ms.tolist()))
 
     def centres(self):
         """ba_get_centres: (Nc, 3) camera centres -R_c^T t_c of the current cameras."""

@@ -482,6 +482,76 @@ int ba_match_guided(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const int6
                     int32_t n_pairs, const int32_t* pair_query, const int32_t* pair_train, const ba_guided_options* opts,
                     const float* window, const double* F, int64_t* row_off, int32_t* best, int32_t* second, int32_t* dist1,
                     int32_t* dist2, uint8_t* good, int32_t* n_good, int32_t* n_cand);
+/* ORB feature extraction: the step that produces keypoints and descriptors from a grey image, what the reference's
+ * ORBExtractor.extract (cv2.ORB_create(nfeatures = 3000).detectAndCompute) does on the host.  This is ORB BY THE PUBLISHED
+ * ALGORITHM -- multi-scale FAST-9, Harris ranking, intensity-centroid orientation, steered BRIEF on a blurred pyramid -- and NOT
+ * bit-parity with cv2: neither keypoints nor descriptors are claimed to equal cv2's, and the default test pattern is not
+ * OpenCV's learned one (a caller who has that table passes it as `pattern`; descriptors match only descriptors made with the
+ * same pattern).  Every stage is integer arithmetic, or fp64 with every operation rounded on its own, so the definition below
+ * decides every case, border cases included.  Needs no problem; a resident problem is not touched.
+ * images uint8[n_images][height][width], row-major and contiguous, one common size.  Per-keypoint outputs have a stride of
+ * n_features rows per image: image b owns rows b n_features .. b n_features + n_kp[b] - 1, rows beyond are not written.  Any
+ * output may be NULL.  xy float32[..][2], size, angle, response float32[..], octave int32[..], level_xy int32[..][2], cs
+ * double[..][2], desc uint8[..][32].
+ * LEVELS (ba_orb_levels, L = n_levels): s_0 = 1, s_l = s_(l-1) * scale_factor (repeated multiplication); w_l = rint(W / s_l),
+ *   h_l = rint(H / s_l), fp64 division, rint half-to-even.  Quotas: f = 1.0 / scale_factor, p = f^L by repeated multiplication,
+ *   d = n_features * (1 - f) / (1 - p); for l < L - 1: n_l = min(rint(d), n_features - sum of the quotas below l), d = d * f;
+ *   n_(L-1) = n_features - sum; L = 1: n_0 = n_features.  The quotas sum to n_features for every input (the min binds only for a
+ *   small n_features, where the roundings alone would add up to more), so n_kp[b] <= n_features.  A level with w_l <= 2 edge or h_l <= 2 edge has no interior and gives no keypoint (and none above it is built).
+ * PYRAMID: level l from level l - 1 by fixed-point bilinear interpolation: ratio = (double)w_(l-1) / (double)w_l, sx = (x + 0.5) *
+ *   ratio - 0.5 (each operation rounded), x0 = floor(sx), fx = sx - x0, x1 = x0 + 1, both clamped to [0, w_(l-1) - 1], fx = 0 if x0
+ *   was clamped; a1 = rint(fx * 2048), a0 = 2048 - a1; rows likewise; pixel = (sum of the four a_y a_x I + (1 << 21)) >> 22.
+ * FAST-9: the radius-3 ring in the order (0,-3) (1,-3) (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0)
+ *   (-3,-1) (-2,-2) (-1,-3); score = max over the 16 arcs of 9 contiguous ring pixels of max(min(ring - v), min(v - ring)); a
+ *   corner iff score > fast_threshold; it survives iff its score is strictly greater than that of each of its 8 neighbours
+ *   (non-corners count 0).  Candidates: survivors with edge <= x < w_l - edge, edge <= y < h_l - edge (neighbours outside
+ *   still suppress).
+ * STAGE 1, per image and level: of more than 2 n_l candidates the first 2 n_l under (score descending, raster index y w_l + x
+ *   ascending).
+ * HARRIS at each kept corner, over the offsets -3 .. 3 in x and y: Ix = 2 (I(x+1,y) - I(x-1,y)) + (I(x+1,y-1) - I(x-1,y-1)) +
+ *   (I(x+1,y+1) - I(x-1,y+1)), Iy likewise; a = sum Ix^2, b = sum Iy^2, c = sum Ix Iy; Hs = 25 (a b - c^2) - (a + b)^2 in int64
+ *   (k = 0.04 without rounding).
+ * STAGE 2: the first n_l under (Hs descending, raster index ascending); output order: level ascending, then that order.
+ *   response = (float)(((double)Hs / 25.0) / 2598919616160000.0)   (7140^4).
+ * ORIENTATION on the unblurred level image over the circular patch of half-widths umax[|v|] = 15 15 15 15 14 14 14 13 13 12 11
+ *   10 9 8 6 3 (|v| = 0 .. 15): m10 = sum u I, m01 = sum v I (integers); angle = atan2(m01, m10) in degrees in [0, 360), float32
+ *   (the one output not defined to the bit: it goes through atan2); r = sqrt((double)(m10^2 + m01^2)), c = m10 / r, s = m01 / r,
+ *   (c, s) = (1, 0) when both moments are 0; cs returns (c, s).
+ * BLUR: separable, integer weights 18 34 49 54 49 34 18 (sum 256): the row pass keeps the exact 16-bit sum, the column pass
+ *   gives (sum g t + 32768) >> 16.  With edge_threshold >= 25 no value within 3 pixels of a border is read.
+ * DESCRIPTOR: pattern row i = (x1, y1, x2, y2); each point maps to u = rint(px c - py s), v = rint(px s + py c) (fp64, products and
+ *   sums rounded separately, rint half-to-even); bit i % 8 of byte i / 8 = B(x + u1, y + v1) < B(x + u2, y + v2), B the blurred
+ *   level image.
+ * OUTPUTS: xy = (float)((double)x_l * s_l) and likewise y; size = (float)(31.0 * s_l); octave = l; level_xy = (x_l, y_l).
+ * An image too small to have an interior is no error: it returns zero keypoints.  Two calls give bit-equal outputs.
+ * BA_ERR_INVALID, naming the field: scale_factor not in (1, 2], n_features < 1 or > 65536, n_levels outside 1 .. 16,
+ * edge_threshold < 25, fast_threshold outside 1 .. 254; images NULL with n_images > 0; height or width not positive; a pattern
+ * coordinate outside -15 .. 15; n_images < 0; a batch beyond the cap: n_images > 1024, height * width > 2^26, or n_images *
+ * height * width > 2^28.  A refused call leaves the handle usable.
+ * Not offered: cv2's learned pattern, WTA_K 3 / 4, the FAST score type, firstLevel, masks, images of different sizes in one
+ * call, a quadtree distribution of keypoints, colour conversion. */
+typedef struct ba_orb_options {
+  double  scale_factor;    /* > 1, <= 2; default 1.2 */
+  int32_t n_features;      /* 1 .. 65536; default 3000 */
+  int32_t n_levels;        /* 1 .. 16; default 8 */
+  int32_t edge_threshold;  /* >= 25; default 31 */
+  int32_t fast_threshold;  /* 1 .. 254; default 20 */
+} ba_orb_options;          /* 24 bytes */
+int ba_default_orb_options(ba_orb_options* opts);    /* 1.2, 3000, 8, 31, 20 */
+/* The default test pattern, int8[256][4] = (x1, y1, x2, y2): BRIEF's "G II" sampling within +-13 (csrc/ba_orb.hpp).  Host only. */
+int ba_orb_default_pattern(int8_t* pattern);
+/* The level sizes, scales and quotas of the definition above, n_levels entries each; any output may be NULL.  Host only. */
+int ba_orb_levels(const ba_orb_options* opts, int32_t height, int32_t width, int32_t* level_w, int32_t* level_h,
+                  double* level_scale, int32_t* level_quota);
+int ba_orb_extract(ba_handle* h, int32_t n_images, int32_t height, int32_t width, const uint8_t* images, const int8_t* pattern,
+                   const ba_orb_options* opts, int32_t* n_kp, float* xy, float* size, float* angle, float* response,
+                   int32_t* octave, int32_t* level_xy, double* cs, uint8_t* desc);
+/* Measurement hook: enable = 1 makes every later ba_orb_extract on the handle record events around its stages on the stream,
+ * enable = 0 stops that, enable = -1 leaves the switch as it is; ms (may be NULL) receives the BA_ORB_STAGES stage times of the last timed call that reached the
+ * device, in milliseconds: upload, pyramid, FAST, stage-1 selection, Harris and ranking, blur, orientation and descriptors,
+ * download.  Results do not depend on it. */
+enum { BA_ORB_STAGES = 8 };
+int ba_orb_stage_times(ba_handle* h, int32_t enable, double* ms);
 /* Similarity transform of the reconstruction and robust alignment to reference positions: the step after an adjustment that
  * moves the result into the frame its user needs (georegistration onto GPS / surveyed camera positions or ground-control
  * points -- COLMAP's model_aligner; the comparison of two gauge-free solves; re-centring / re-scaling).  No reference
