@@ -3,5 +3,5 @@ egirgin/bundle_adjustment's ``src/bundle_adjuster.py``."""
 from .map_structures import Keyframe, KeyPoint, Map, MapPoint  # noqa: F401
 from .problem import BAProblem  # noqa: F401
 from .bundle_adjuster import BundleAdjuster  # noqa: F401
-from .pose_estimator import estimate_pose, relative_pose  # noqa: F401
-from .features import BruteForceMatcher, ORBExtractor, fundamental, match, match_by_projection, match_epipolar  # noqa: F401
+from .pose_estimator import estimate_pose, estimate_two_view, homography, relative_pose  # noqa: F401
+from .features import BruteForceMatcher, ORBExtractor, fundamental, match, match_by_homography, match_by_projection, match_epipolar  # noqa: F401

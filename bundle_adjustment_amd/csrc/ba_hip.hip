@@ -42,6 +42,7 @@
 #include "ba_resect.hpp"
 #include "ba_ransac.hpp"
 #include "ba_relpose.hpp"
+#include "ba_homography.hpp"
 #include "ba_match.hpp"
 #include "ba_match_guided.hpp"
 #include "ba_orb.hpp"
@@ -294,6 +295,11 @@ struct ba_handle {
   DBuf<long long> rp_off;
   DBuf<unsigned> rp_mask;
   DBuf<unsigned char> rp_cons, rp_inl;
+  // ba_homography (ba_homography.hpp): staging of the call -- both views' pixels, the pair offsets, the score blocks' winners,
+  // the consensus and inlier bytes, the results
+  DBuf<double> hg_pts, hg_best, hg_out;
+  DBuf<long long> hg_off;
+  DBuf<unsigned char> hg_cons, hg_inl;
   // ba_match_descriptors (ba_match.hpp): staging of the call -- every set's descriptors, the pair table, the splits' (k1, k2),
   // best | second | dist1 | dist2 by row, the good bytes, the per-pair counts
   DBuf<unsigned long long> mt_desc;
@@ -3718,6 +3724,95 @@ extern "C" int ba_relative_pose(ba_handle* h, const double K[9], int32_t n_pairs
       if (rms_px) rms_px[p] = r[14];
       if (parallax_deg) parallax_deg[p] = r[15];
       if (best_hyp) best_hyp[p] = (int32_t)r[16];
+    }
+  return BA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- two-view homography
+// ba_homography (csrc/ba_homography.hpp): four-point hypotheses and scores, local optimisation, decomposition.  Needs no problem.
+static_assert(HG_OK == BA_HOMOGRAPHY_OK && HG_FEW_MATCHES == BA_HOMOGRAPHY_FEW_MATCHES && HG_DEGENERATE == BA_HOMOGRAPHY_DEGENERATE &&
+              HG_FEW_INLIERS == BA_HOMOGRAPHY_FEW_INLIERS && HG_ROTATION == BA_HOMOGRAPHY_ROTATION && HG_AMBIGUOUS == BA_HOMOGRAPHY_AMBIGUOUS &&
+              sizeof(ba_homography_options) == 56, "device status codes (ba_homography.hpp)");
+extern "C" int ba_default_homography_options(ba_homography_options* o) {
+  if (!o) return fail(BA_ERR_INVALID, "null argument");
+  memset(o, 0, sizeof *o);
+  o->n_hyp = 256;
+  o->lo_rounds = 2;
+  o->max_px = 3.0;
+  o->refine_iters = 20;
+  o->min_inliers = 8;
+  o->max_depth = 50.0;
+  o->ambiguity_ratio = 0.75;
+  o->min_translation = 0.024;
+  return BA_OK;
+}
+extern "C" int ba_homography(ba_handle* h, const double K[9], int32_t n_pairs, const int64_t* pair_off, const double* pts1, const double* pts2,
+                             const ba_homography_options* opts, double* H, uint8_t* status, int32_t* n_inliers, double* rms_px, int32_t* best_hyp,
+                             uint8_t* match_inlier, int32_t* n_pose, double* R, double* t, double* normal, double* t_over_d, int32_t* votes,
+                             double* pose_cost) {
+  if (!h || !K || !opts) return fail(BA_ERR_INVALID, "null argument");
+  if (n_pairs < 0 || n_pairs > 65535) return fail(BA_ERR_INVALID, "ba_homography: n_pairs %d is outside 0 .. 65535", n_pairs);
+  if (opts->n_hyp < 1 || opts->n_hyp > RN_MAX_HYP) return fail(BA_ERR_INVALID, "ba_homography: n_hyp %d is outside 1 .. %d", opts->n_hyp, RN_MAX_HYP);
+  if (opts->lo_rounds < 0) return fail(BA_ERR_INVALID, "ba_homography: lo_rounds must not be negative");
+  if (!(opts->max_px > 0)) return fail(BA_ERR_INVALID, "ba_homography: max_px must be positive");
+  if (opts->refine_iters < 0) return fail(BA_ERR_INVALID, "ba_homography: refine_iters must not be negative");
+  if (opts->min_inliers < 0) return fail(BA_ERR_INVALID, "ba_homography: min_inliers must not be negative");
+  if (!(opts->ambiguity_ratio >= 0 && opts->ambiguity_ratio <= 1)) return fail(BA_ERR_INVALID, "ba_homography: ambiguity_ratio must lie in [0, 1]");
+  if (!(opts->min_translation >= 0)) return fail(BA_ERR_INVALID, "ba_homography: min_translation must not be negative");
+  if (!(K[0] > 0 && K[4] > 0 && std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) && std::isfinite(K[5])) || K[1] != 0 || K[3] != 0 ||
+      K[6] != 0 || K[7] != 0 || K[8] != 1)
+    return fail(BA_ERR_INVALID, "ba_homography: K must be the pinhole matrix [fx 0 cx; 0 fy cy; 0 0 1] with fx, fy > 0");
+  if (n_pairs == 0) return BA_OK;
+  if (!pair_off) return fail(BA_ERR_INVALID, "ba_homography: null pair_off");
+  if (pair_off[0] != 0) return fail(BA_ERR_INVALID, "ba_homography: pair_off[0] must be 0");
+  for (int32_t p = 0; p < n_pairs; ++p) {
+    if (pair_off[p + 1] < pair_off[p]) return fail(BA_ERR_INVALID, "ba_homography: pair_off decreases at pair %d", p);
+    if (pair_off[p + 1] - pair_off[p] > 0x7fffffffLL) return fail(BA_ERR_INVALID, "ba_homography: pair_off: pair %d has too many matches", p);
+  }
+  const size_t nm = (size_t)pair_off[n_pairs], np = (size_t)n_pairs;
+  if (nm > 0 && (!pts1 || !pts2)) return fail(BA_ERR_INVALID, "ba_homography: null point arrays");
+  if (set_device(h)) return BA_ERR_HIP;
+  const int n_blk = (opts->n_hyp + HG_THREADS - 1) / HG_THREADS;
+  const size_t nm1 = std::max<size_t>(nm, 1);
+  HIPCHECK(h->hg_pts.alloc(4 * nm1)); HIPCHECK(h->hg_off.alloc(np + 1)); HIPCHECK(h->hg_best.alloc(HG_BEST * np * n_blk));
+  HIPCHECK(h->hg_out.alloc(HG_OUT * np)); HIPCHECK(h->hg_cons.alloc(nm1)); HIPCHECK(h->hg_inl.alloc(nm1));
+  HomogArgs a = {};
+  a.fx = K[0]; a.fy = K[4]; a.cx = K[2]; a.cy = K[5];
+  a.fbar = 0.5 * (K[0] + K[4]); a.thr = opts->max_px / a.fbar;
+  a.max_depth = opts->max_depth; a.ambiguity = opts->ambiguity_ratio; a.min_translation = opts->min_translation;
+  a.n_hyp = opts->n_hyp; a.lo_rounds = opts->lo_rounds; a.iters = opts->refine_iters; a.min_inliers = opts->min_inliers;
+  a.n_blk = n_blk; a.seed = opts->seed;
+  a.off = h->hg_off.p; a.p1 = (const double2*)h->hg_pts.p; a.p2 = (const double2*)(h->hg_pts.p + 2 * nm1);
+  a.best = h->hg_best.p; a.cons = h->hg_cons.p; a.inl = h->hg_inl.p; a.out = h->hg_out.p;
+  HIPCHECK(hipMemcpyAsync(h->hg_off.p, pair_off, (np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  if (nm > 0) {
+    HIPCHECK(hipMemcpyAsync(h->hg_pts.p, pts1, 2 * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(h->hg_pts.p + 2 * nm1, pts2, 2 * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemsetAsync(h->hg_inl.p, 0, nm, h->stream));
+  }
+  const dim3 b(HG_THREADS);
+  BA_LAUNCH(k_homog_score, dim3(n_pairs, n_blk), b, 0, h->stream, a);
+  BA_LAUNCH(k_homog_lo, dim3(n_pairs), b, 0, h->stream, a);
+  const bool want = H || status || n_inliers || rms_px || best_hyp || n_pose || R || t || normal || t_over_d || votes || pose_cost;
+  std::vector<double> res(want ? HG_OUT * np : 0);
+  if (want) HIPCHECK(hipMemcpyAsync(res.data(), h->hg_out.p, HG_OUT * np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (match_inlier && nm > 0) HIPCHECK(hipMemcpyAsync(match_inlier, h->hg_inl.p, nm, hipMemcpyDeviceToHost, h->stream));
+  BA_SYNC(h);
+  if (want)
+    for (size_t p = 0; p < np; ++p) {
+      const double* r = res.data() + HG_OUT * p;
+      if (H) memcpy(H + 9 * p, r, 9 * sizeof(double));
+      if (status) status[p] = (uint8_t)r[9];
+      if (n_inliers) n_inliers[p] = (int32_t)r[10];
+      if (rms_px) rms_px[p] = r[11];
+      if (best_hyp) best_hyp[p] = (int32_t)r[12];
+      if (n_pose) n_pose[p] = (int32_t)r[13];
+      if (R) memcpy(R + 18 * p, r + 14, 18 * sizeof(double));
+      if (t) memcpy(t + 6 * p, r + 32, 6 * sizeof(double));
+      if (normal) memcpy(normal + 6 * p, r + 38, 6 * sizeof(double));
+      if (t_over_d) memcpy(t_over_d + 2 * p, r + 44, 2 * sizeof(double));
+      if (votes) { votes[2 * p] = (int32_t)r[46]; votes[2 * p + 1] = (int32_t)r[47]; }
+      if (pose_cost) memcpy(pose_cost + 2 * p, r + 48, 2 * sizeof(double));
     }
   return BA_OK;
 }

@@ -167,6 +167,27 @@ def match_by_projection(K, R, t, points, point_desc, kp, des, radius_px, image_s
     return _good_of_pair(out, 0)
 
 
+def match_by_homography(des1, kp1, des2, kp2, H, radius_px, solver=None, **opts):
+    """Matches of a planar scene under a known homography (pixels, p2 ~ H p1: ``ba_homography``'s ``H``): keypoint i of the
+    first image is predicted at pi(H kp1[i]) on the host, and only the keypoints of the second image within ``radius_px`` (a
+    scalar or one per keypoint) of the prediction are its candidates (``ba_match_guided``, window gate).  A keypoint whose
+    prediction has a non-positive third component or is not finite gets radius -1: no candidate.  -> (idx1, idx2, distance) int64
+    arrays in the order of the first image.  opts: ratio, max_distance, mutual, single.  ``None`` or empty inputs on either side
+    return no match."""
+    if des1 is None or des2 is None or len(des1) == 0 or len(des2) == 0:
+        return _empty_matches()
+    k1 = _positions(kp1)
+    y = np.c_[np.asarray(k1, dtype=np.float64), np.ones(len(k1))] @ np.asarray(H, dtype=np.float64).reshape(3, 3).T
+    with np.errstate(divide="ignore", invalid="ignore"):
+        uv = y[:, :2] / y[:, 2:3]
+    ok = (y[:, 2] > 0) & np.isfinite(uv).all(axis=1)
+    window = np.zeros((len(k1), 3), dtype=np.float32)
+    window[:, :2] = np.where(ok[:, None], uv, 0.0)
+    window[:, 2] = np.where(ok, np.broadcast_to(np.asarray(radius_px, dtype=np.float64), (len(k1),)), -1.0)
+    out = _guided(solver, [_descriptors(des1), _descriptors(des2)], [k1, _positions(kp2)], window=window, **opts)
+    return _good_of_pair(out, 0)
+
+
 class BruteForceMatcher:
     """Drop-in for the reference's ``BruteForceMatcher`` (Hamming norm): ``match(des1, des2)`` -> the good matches, a list in
     query order of objects with ``queryIdx``, ``trainIdx``, ``imgIdx = 0`` and ``distance`` (float).  ``None`` for either

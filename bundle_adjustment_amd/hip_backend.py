@@ -115,6 +115,12 @@ class BARelposeOptions(C.Structure):
                 ("refine_iters", C.c_int32), ("min_inliers", C.c_int32), ("min_parallax_deg", C.c_double), ("max_depth", C.c_double)]
 
 
+class BAHomographyOptions(C.Structure):
+    _fields_ = [("n_hyp", C.c_int32), ("lo_rounds", C.c_int32), ("seed", C.c_uint64), ("max_px", C.c_double),
+                ("refine_iters", C.c_int32), ("min_inliers", C.c_int32), ("max_depth", C.c_double), ("ambiguity_ratio", C.c_double),
+                ("min_translation", C.c_double)]
+
+
 class BAMatchOptions(C.Structure):
     _fields_ = [("ratio", C.c_double), ("max_distance", C.c_int32), ("mutual", C.c_int32)]
 
@@ -157,6 +163,7 @@ TRACK_STATUS = {"ok": 0, "few_views": 1, "degenerate": 2, "behind": 3, "low_angl
 RESECT_STATUS = {"ok": 0, "few_points": 1, "degenerate": 2, "behind": 3, "few_inliers": 4, "high_error": 5}   # enum ba_resect_status
 RESECT_INIT = {"dlt": 0, "current": 1}   # enum ba_resect_init
 RELPOSE_STATUS = {"ok": 0, "few_matches": 1, "degenerate": 2, "behind": 3, "few_inliers": 4, "low_parallax": 5}   # enum ba_relpose_status
+HOMOGRAPHY_STATUS = {"ok": 0, "few_matches": 1, "degenerate": 2, "few_inliers": 3, "rotation": 4, "ambiguous": 5}   # enum ba_homography_status
 
 
 def resect_init_code(init):
@@ -220,6 +227,9 @@ SYMBOLS = {
     "ba_default_relpose_options": (C.c_int, [C.POINTER(BARelposeOptions)]),
     "ba_relative_pose": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.POINTER(C.c_int64), _DP, _DP, C.POINTER(BARelposeOptions), _DP, _DP,
                                    C.POINTER(C.c_uint8), _IP, _DP, _DP, _IP, C.POINTER(C.c_uint8)]),
+    "ba_default_homography_options": (C.c_int, [C.POINTER(BAHomographyOptions)]),
+    "ba_homography": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.POINTER(C.c_int64), _DP, _DP, C.POINTER(BAHomographyOptions), _DP,
+                                C.POINTER(C.c_uint8), _IP, _DP, _IP, C.POINTER(C.c_uint8), _IP, _DP, _DP, _DP, _DP, _IP, _DP]),
     "ba_default_match_options": (C.c_int, [C.POINTER(BAMatchOptions)]),
     "ba_match_descriptors": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.c_int32, _IP, _IP,
                                        C.POINTER(BAMatchOptions), C.POINTER(C.c_int64), _IP, _IP, _IP, _IP, C.POINTER(C.c_uint8), _IP]),
@@ -831,6 +841,41 @@ class Solver:
                                           _dp(out["R"]), _dp(out["t"]), out["status"].ctypes.data_as(u8), out["n_inliers"].ctypes.data_as(_IP),
                                           _dp(out["rms_px"]), _dp(out["parallax_deg"]), out["best_hyp"].ctypes.data_as(_IP),
                                           inl.ctypes.data_as(u8)))
+        out["match_inlier"] = inl.astype(bool)
+        return out
+
+    def homography_options(self, **kw) -> BAHomographyOptions:
+        """ba_default_homography_options overlaid with kw (any ba_homography_options field; an unknown one raises TypeError)."""
+        return _options(BAHomographyOptions, self._lib.ba_default_homography_options, kw, names={})
+
+    def homography(self, K, pts1, pts2, pair_off=None, **opts):
+        """ba_homography: the plane-induced H (pixels, p2 ~ H p1, unit norm, det > 0) of every pair from raw pixel matches --
+        n_hyp four-point samples per pair scored on all of its matches, lo_rounds of (consensus, refinement) -- and the two
+        poses it decomposes into, the better first (H~ / d2 = R + (t / d) n^T, |t| = |n| = 1).  pts1 / pts2 / pair_off as
+        ``relative_pose``.  opts: n_hyp, lo_rounds, seed, max_px, refine_iters, min_inliers, max_depth, ambiguity_ratio,
+        min_translation.  Returns dict(H (P, 3, 3), status (P,) uint8 (HOMOGRAPHY_STATUS), n_inliers, rms_px, best_hyp, n_pose
+        (P,), match_inlier (n,) bool, R (P, 2, 3, 3), t, normal (P, 2, 3), t_over_d, votes, pose_cost (P, 2)).  Needs no problem
+        and leaves a resident one as it is."""
+        Km = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
+        p1 = np.ascontiguousarray(pts1, dtype=np.float64).reshape(-1, 2)
+        p2 = np.ascontiguousarray(pts2, dtype=np.float64).reshape(-1, 2)
+        if p1.shape[0] != p2.shape[0]:
+            raise ValueError("pts1 and pts2 must list the same number of points")
+        off = np.array([0, p1.shape[0]], dtype=np.int64) if pair_off is None else np.ascontiguousarray(pair_off, dtype=np.int64).ravel()
+        if off.size < 1 or (off.size > 1 and off[-1] != p1.shape[0]):
+            raise ValueError("pair_off must have n_pairs + 1 entries and end at the number of matches")
+        o = self.homography_options(**opts)
+        P, n = off.size - 1, p1.shape[0]
+        out = dict(H=np.empty((P, 3, 3)), status=np.empty(P, dtype=np.uint8), n_inliers=np.empty(P, dtype=np.int32), rms_px=np.empty(P),
+                   best_hyp=np.empty(P, dtype=np.int32), n_pose=np.empty(P, dtype=np.int32), R=np.empty((P, 2, 3, 3)), t=np.empty((P, 2, 3)),
+                   normal=np.empty((P, 2, 3)), t_over_d=np.empty((P, 2)), votes=np.empty((P, 2), dtype=np.int32), pose_cost=np.empty((P, 2)))
+        inl = np.zeros(n, dtype=np.uint8)
+        u8 = C.POINTER(C.c_uint8)
+        _check(self._lib.ba_homography(self._h, _dp(Km), P, off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(p1), _dp(p2), C.byref(o),
+                                       _dp(out["H"]), out["status"].ctypes.data_as(u8), out["n_inliers"].ctypes.data_as(_IP),
+                                       _dp(out["rms_px"]), out["best_hyp"].ctypes.data_as(_IP), inl.ctypes.data_as(u8),
+                                       out["n_pose"].ctypes.data_as(_IP), _dp(out["R"]), _dp(out["t"]), _dp(out["normal"]),
+                                       _dp(out["t_over_d"]), out["votes"].ctypes.data_as(_IP), _dp(out["pose_cost"])))
         out["match_inlier"] = inl.astype(bool)
         return out
 

@@ -5,8 +5,10 @@ Mirrors ``estimate_pose`` of ``src/pose_estimator.py`` (``cv2.findEssentialMat(.
 ``cv2.recoverPose``: same arguments, same five-tuple, same log lines) on the GPU (``ba_relative_pose``: five-point hypotheses
 scored on all matches, decomposition with cheirality votes, local optimisation on the consensus set).  A fixed number of
 hypotheses instead of cv2's adaptive stopping, so the result is not bit-comparable with cv2's; what comes back goes straight
-into ``triangulation.triangulate_points``.  No cv2 is needed: matches and keypoints are duck-typed.  No CPU fallback: without
-the library / a GPU the call raises.
+into ``triangulation.triangulate_points``.  ``estimate_two_view`` runs the planar model (``ba_homography``) next to the essential
+one and picks between them by COLMAP's inlier-ratio rule: exactly coplanar matches admit two essential matrices of zero cost,
+so the first pair of a sequence over a desk or a wall is the homography's to decide.  No cv2 is needed: matches and keypoints
+are duck-typed.  No CPU fallback: without the library / a GPU the call raises.
 """
 from __future__ import annotations
 
@@ -51,3 +53,82 @@ def estimate_pose(matches, kp1, kp2, camera_matrix, solver=None, quiet=False, **
     mask = out["match_inlier"]
     return (np.array(out["R"], dtype=np.float64).reshape(3, 3), np.array(out["t"], dtype=np.float64).reshape(3, 1), pts1[mask], pts2[mask],
             np.where(mask)[0])
+
+
+def homography(K, pts1, pts2, solver=None, **opts):
+    """One pair on arrays: ``hip_backend.Solver.homography`` with the leading pair axis removed -- dict(H (3, 3) in pixels, status
+    (int, ``hip_backend.HOMOGRAPHY_STATUS``), n_inliers, rms_px, best_hyp, n_pose, match_inlier (n,) bool, and the two poses, the
+    better first: R (2, 3, 3), t, normal (2, 3), t_over_d, votes, pose_cost (2,)).  ``solver`` as ``relative_pose``."""
+    own = solver is None
+    s = hip_backend.Solver(0) if own else solver
+    try:
+        out = s.homography(K, pts1, pts2, **opts)
+    finally:
+        if own:
+            s.close()
+    return dict(H=out["H"][0], status=int(out["status"][0]), n_inliers=int(out["n_inliers"][0]), rms_px=float(out["rms_px"][0]),
+                best_hyp=int(out["best_hyp"][0]), n_pose=int(out["n_pose"][0]), match_inlier=out["match_inlier"], R=out["R"][0],
+                t=out["t"][0], normal=out["normal"][0], t_over_d=out["t_over_d"][0], votes=out["votes"][0], pose_cost=out["pose_cost"][0])
+
+
+_BOTH = ("n_hyp", "lo_rounds", "seed", "refine_iters", "min_inliers", "max_depth")
+_ESSENTIAL_ONLY = ("max_epi_px", "min_parallax_deg")
+_HOMOGRAPHY_ONLY = ("max_px", "ambiguity_ratio", "min_translation")
+
+
+def estimate_two_view(matches, kp1, kp2, camera_matrix, solver=None, planar_ratio=0.8, quiet=False, **opts):
+    """``estimate_pose`` with planar model selection: both ``relative_pose`` (essential matrix) and ``homography`` run on the same
+    matches, and the homography's first pose is taken when ``n_inliers_H >= planar_ratio * n_inliers_E`` (COLMAP's
+    ``max_H_inlier_ratio``), its status is ok and that pose carries the most votes; otherwise the essential pose.
+    -> ``estimate_pose``'s five values and a dict: ``model`` ("essential", "homography", "rotation", "ambiguous"), ``essential`` and
+    ``homography`` (the two calls' outputs), ``normal`` (the plane's, or None) and ``second_pose`` ((R, t 3 x 1, normal) of the
+    homography's other pose, or None).  "rotation" (no translation to triangulate with: R alone, t = 0) and "ambiguous" (two poses
+    explain the plane equally well; the first is returned, the other is ``second_pose``) come with the pose but with empty inlier
+    arrays: nothing to triangulate, the reference would discard such a frame.  With model "essential" the five values are
+    ``estimate_pose``'s, bit for bit.  opts: n_hyp, lo_rounds, seed, refine_iters, min_inliers, max_depth go to both calls;
+    max_epi_px, min_parallax_deg to the essential one; max_px, ambiguity_ratio, min_translation to the homography."""
+    for k in opts:
+        if k not in _BOTH + _ESSENTIAL_ONLY + _HOMOGRAPHY_ONLY:
+            raise TypeError(f"unknown option {k}")
+    pts1 = np.float32([kp1[m.queryIdx].pt for m in matches]).reshape(-1, 2)
+    pts2 = np.float32([kp2[m.trainIdx].pt for m in matches]).reshape(-1, 2)
+    own = solver is None
+    s = hip_backend.Solver(0) if own else solver
+    try:
+        e = relative_pose(camera_matrix, pts1, pts2, solver=s, **{k: v for k, v in opts.items() if k in _BOTH + _ESSENTIAL_ONLY})
+        h = homography(camera_matrix, pts1, pts2, solver=s, **{k: v for k, v in opts.items() if k in _BOTH + _HOMOGRAPHY_ONLY})
+    finally:
+        if own:
+            s.close()
+    hs = hip_backend.HOMOGRAPHY_STATUS
+    info = dict(model="essential", essential=e, homography=h, normal=None, second_pose=None)
+    planar = h["best_hyp"] >= 0 and h["n_inliers"] >= planar_ratio * e["n_inliers"]
+    if planar and h["status"] == hs["ok"] and h["n_pose"] >= 1 and h["votes"][0] > h["votes"][1]:
+        info["model"] = "homography"
+    elif planar and h["status"] == hs["rotation"]:
+        info["model"] = "rotation"
+    elif planar and h["status"] == hs["ambiguous"] and h["n_pose"] >= 1:
+        info["model"] = "ambiguous"
+    num_matches = len(matches)
+    if info["model"] == "essential":
+        st = hip_backend.RELPOSE_STATUS
+        if e["status"] == st["few_matches"] or (e["status"] == st["degenerate"] and e["best_hyp"] < 0):
+            return None, None, None, None, None, info
+        R, t, mask = e["R"], e["t"], e["match_inlier"]
+    else:
+        R, t = h["R"][0], h["t"][0]
+        mask = h["match_inlier"] if info["model"] == "homography" else np.zeros(num_matches, dtype=bool)
+        if info["model"] != "rotation":
+            info["normal"] = np.array(h["normal"][0], dtype=np.float64)
+            info["second_pose"] = (np.array(h["R"][1], dtype=np.float64), np.array(h["t"][1], dtype=np.float64).reshape(3, 1),
+                                   np.array(h["normal"][1], dtype=np.float64))
+    if not quiet:
+        num_inliers = int(mask.sum())
+        inlier_ratio = num_inliers / num_matches if num_matches > 0 else 0
+        if info["model"] != "essential":
+            print(f"    -> Two-view model: {info['model']} ({h['n_inliers']} homography inliers, {e['n_inliers']} essential)")
+        print(f"    -> Pose Estimation: {num_inliers} inliers out of {num_matches} matches (Ratio: {inlier_ratio:.2f})")
+        if inlier_ratio < 0.4 and info["model"] in ("essential", "homography"):
+            print("    -> WARNING: Low inlier ratio. Pose estimate may be unreliable.")
+    return (np.array(R, dtype=np.float64).reshape(3, 3), np.array(t, dtype=np.float64).reshape(3, 1), pts1[mask], pts2[mask],
+            np.where(mask)[0], info)

@@ -406,6 +406,74 @@ int ba_default_relpose_options(ba_relpose_options* opts);   /* 256, 2, 0, 3.0, 2
 int ba_relative_pose(ba_handle* h, const double K[9], int32_t n_pairs, const int64_t* pair_off, const double* pts1, const double* pts2,
                      const ba_relpose_options* opts, double* R, double* t, uint8_t* status, int32_t* n_inliers, double* rms_px,
                      double* parallax_deg, int32_t* best_hyp, uint8_t* match_inlier);
+/* Two-view homography: the plane-induced H of raw pixel matches, a share of which may be wrong, and the poses it decomposes
+ * into -- the planar model next to ba_relative_pose's essential one (cv2.findHomography(RANSAC) then cv2.decomposeHomographyMat;
+ * the H half of ORB-SLAM's initialiser and of COLMAP's two-view geometry).  Exactly coplanar matches admit two essential matrices
+ * of zero Sampson cost, so a planar scene is decided here and not there.  K, n_pairs, pair_off, pts1, pts2, the staging buffers
+ * on the handle and the rule that no problem is needed or touched are ba_relative_pose's.  Convention x2~ ~ H~ x1~ with H~ / d2 = R +
+ * (t / d) n^T: x2 ~ K (R x1 + t), the plane n . X = d in the first view's frame, |t| = |n| = 1, d2 the middle singular value.
+ * Outputs, any of them NULL: H double[n_pairs][9] row-major, in PIXELS (p2 ~ H p1), unit Frobenius norm, det > 0; status uint8
+ * (ba_homography_status), n_inliers, rms_px, best_hyp int32 (the winning hypothesis, -1 when there is none), match_inlier
+ * uint8[pair_off[n_pairs]], n_pose int32, and per pair TWO poses, the better first: R double[n_pairs][2][9], t and normal
+ * double[n_pairs][2][3], t_over_d double[n_pairs][2] (|t| / d before t was scaled to 1), votes int32[n_pairs][2], pose_cost
+ * double[n_pairs][2].  n_pairs = 0 is a no-op.
+ * Per pair with n matches:
+ * (0) x~ = ((u - cx) / fx, (v - cy) / fy, 1) in both views; fbar = (fx + fy) / 2, thr = max_px / fbar.
+ * (1) n < 5: FEW_MATCHES (four matches reproduce themselves); H = I, no pose.
+ * (2) Hypothesis h = 0 .. n_hyp - 1 draws four distinct indices with ba_relative_pose's generator, d = 0 .. 3, and the same raising
+ * rule.  A triple of the four with |d12 x d13| <= 1e-6 max |d_ij|^2 in either image (collinear or coincident) voids the hypothesis.
+ * (3) Closed form, fp64, one lane per hypothesis, no elimination: per image M = [a b c] (the first three points as homogeneous
+ * columns), lambda = adj(M) d (d the fourth), B = M diag(lambda); H~ = B2 adj(B1), scaled to unit Frobenius norm and det > 0.
+ * |det| <= 1e-12 at unit norm, a non-finite entry, or a sample point with (H~ x1~)_2 <= 0 (cv2's orientation check) voids it.
+ * (4) Every H~ is scored on all n matches: f = |pi(H~ x1~) - x2~|^2, b = |pi(adj(H~) x2~) - x1~|^2, the cost is the sum of min(f,
+ * thr^2) + min(b, thr^2), a non-positive third component costs thr^2.  The lowest (cost, h) wins.  Every hypothesis void:
+ * DEGENERATE, H = I, 0 inliers, NaN measures, best_hyp = -1, n_pose = 0.
+ * (5) lo_rounds times: the consensus set = the matches with f <= thr^2, b <= thr^2 and both third components positive at the
+ * round's starting H~; an empty set ends the rounds.  Then at most refine_iters Marquardt-damped Gauss-Newton steps on 0.5 sum
+ * (|r_f|^2 + |r_b|^2) over the set (a trial H~ at which a third component of a match of the set is not positive is rejected:
+ * its cost counts as infinite) in the eight local
+ * parameters of H~ <- H~ (I + D), D = [p0 p1 p2; p3 p4 p5; p6 p7 -(p0 + p4)] traceless; to first order the backward residual sees
+ * (I - D) H~^-1; both Jacobians analytic; after a step H~ (I + D) is formed exactly and renormalised as in (3).  Damping, acceptance
+ * and lambda limits as ba_resect's step (3); |dx| <= 1e-14 ends it; an 8 x 8 Cholesky pivot <= 0 (or a non-finite step):
+ * DEGENERATE with the last accepted H~ and its measures.
+ * (6) At the final H~: match_inlier = the consensus test of (5), n_inliers their count, rms_px = fbar sqrt(mean (f + b) / 2) over
+ * them (NaN without inliers); H = K H~ K^-1 at unit Frobenius norm, det > 0.
+ * (7) H~ = U diag(d1, d2, d3) V^T (one-sided Jacobi; u3 = u1 x u2, v3 = v1 x v2, so det U = det V = +1 and d1 >= d2 >= d3 > 0).
+ * (d1 - d3) / d2 <= min_translation (it equals |t| / d): ROTATION, one pose R = U V^T with t = 0, normal = 0, t_over_d = the ratio,
+ * n_pose = 1.  Otherwise Faugeras & Lustman's (1988) candidates of the case d' = +d2: a1 = sqrt((d1^2 - d2^2) / (d1^2 - d3^2)), a3 =
+ * sqrt((d2^2 - d3^2) / (d1^2 - d3^2)), cos = (d2^2 + d1 d3) / ((d1 + d3) d2), sin = e sqrt((d1^2 - d2^2) (d2^2 - d3^2)) / ((d1 + d3) d2),
+ * R = U [cos 0 -sin; 0 1 0; sin 0 cos] V^T, t = U (a1, 0, -e a3), n = V (a1, 0, e a3), e = +1 (pose number 0) or -1 (number 1),
+ * t_over_d = (d1 - d3) / d2; the other two candidates flip both t and n, and of each such couple the one with n . x1~ > 0 for more
+ * inliers than n . x1~ < 0 is kept (a tie keeps the one above).  An inlier votes for a pose when both depths of lambda2 x2~ =
+ * lambda1 R x1~ + t (ba_relative_pose's step 5) lie in (0, max_depth] and n . x1~ > 0.  pose_cost is the MSAC cost of the squared
+ * Sampson distance of [t]x R on all matches with threshold thr (ba_relative_pose's step 4).  The poses are ordered by votes
+ * descending, then pose_cost ascending, then number; n_pose counts those with at least one vote.  AMBIGUOUS when the second
+ * pose's votes are >= ambiguity_ratio times the first's (ORB-SLAM's rule); both poses are returned either way.
+ * (8) Status: the first failing test in enum order; FEW_INLIERS: n_inliers < min_inliers.  A status other than FEW_MATCHES or a
+ * DEGENERATE of step (4) comes with the final H, its measures and its decomposition.
+ * BA_ERR_INVALID, naming the field: K not as in ba_relative_pose, n_pairs outside 0 .. 65535, n_hyp outside 1 .. 4096, lo_rounds < 0,
+ * max_px not > 0, refine_iters < 0, min_inliers < 0, ambiguity_ratio outside [0, 1], min_translation negative or NaN, pair_off[0]
+ * != 0, a decreasing pair_off.  Results are bit-reproducible from call to call, and a pair's result depends on its index in the
+ * call (the samples) but not on the other pairs.  Local to the rank. */
+enum ba_homography_status { BA_HOMOGRAPHY_OK = 0, BA_HOMOGRAPHY_FEW_MATCHES = 1, BA_HOMOGRAPHY_DEGENERATE = 2,
+                            BA_HOMOGRAPHY_FEW_INLIERS = 3, BA_HOMOGRAPHY_ROTATION = 4, BA_HOMOGRAPHY_AMBIGUOUS = 5 };
+typedef struct ba_homography_options {
+  int32_t  n_hyp;            /* minimal samples per pair, 1 .. 4096; default 256: at an inlier share of 0.5 all of them miss with
+                                probability (1 - 0.5^4)^256 = 7e-8 */
+  int32_t  lo_rounds;        /* rounds of (consensus, refinement); default 2; 0 = the best raw hypothesis, decomposed */
+  uint64_t seed;             /* default 0 */
+  double   max_px;           /* threshold on each transfer error in pixels, > 0; default 3.0 */
+  int32_t  refine_iters;     /* per round; default 20 */
+  int32_t  min_inliers;      /* default 8 */
+  double   max_depth;        /* a match votes when both depths are in (0, max_depth], unit = |t| = 1; <= 0: no upper limit; default 50 */
+  double   ambiguity_ratio;  /* in [0, 1]; default 0.75 */
+  double   min_translation;  /* ROTATION when (d1 - d3) / d2 = |t| / d is not above it; default 0.024 */
+} ba_homography_options;
+int ba_default_homography_options(ba_homography_options* opts);   /* 256, 2, 0, 3.0, 20, 8, 50.0, 0.75, 0.024 */
+int ba_homography(ba_handle* h, const double K[9], int32_t n_pairs, const int64_t* pair_off, const double* pts1, const double* pts2,
+                  const ba_homography_options* opts, double* H, uint8_t* status, int32_t* n_inliers, double* rms_px, int32_t* best_hyp,
+                  uint8_t* match_inlier, int32_t* n_pose, double* R, double* t, double* normal, double* t_over_d, int32_t* votes,
+                  double* pose_cost);
 /* Descriptor matching: brute-force Hamming 2-nearest-neighbours of binary descriptors with Lowe's ratio test, the step that
  * produces the matches ba_relative_pose starts from (the reference's BruteForceMatcher.match: cv2.BFMatcher(NORM_HAMMING,
  * crossCheck=False).knnMatch(des1, des2, k=2), then m.distance < 0.75 n.distance).  Needs no ba_set_problem and leaves a resident
