@@ -46,6 +46,7 @@
 #include "ba_match.hpp"
 #include "ba_match_guided.hpp"
 #include "ba_orb.hpp"
+#include "ba_posegraph.hpp"
 
 using namespace ba;
 
@@ -332,6 +333,15 @@ struct ba_handle {
   // per-workgroup partial rows, the device record (similarity, centroids, status)
   DBuf<double> sim_buf, sim_part;
   DBuf<SimRec> sim_rec;
+  // ba_pose_graph / ba_pose_graph_system (ba_posegraph.hpp): one arena of doubles (poses x 2, measurements, information blocks,
+  // edge records, node blocks, PCG vectors, partial rows), one of ints (edges, incidence lists, masks, hubs), the PCG state
+  // records, the record the host reads, the trace of the last call
+  DBuf<double> pg_d;
+  DBuf<int> pg_i;
+  DBuf<PgPcg> pg_st;
+  DBuf<PgRec> pg_rec;
+  std::vector<ba_iter_record> pg_trace;
+  int debug_pg_splits = 0;     // BA_DEBUG_PG_SPLITS: teams that share a hub node's incidence list instead of all 32 (tests)
   PinnedStage up;              // pinned arena of a window-sized problem's uploads (ba_set_problem: one copy, k_unpack_problem)
   char* h_small = nullptr;     // k_small_lm's results, host-mapped: ba_summary | int cur | trace records
   char* d_small_host = nullptr;
@@ -484,6 +494,7 @@ static int create_impl(ba_handle* h, int device_id) {
 #undef BA_BIG_LDS
   if (const char* e = getenv("BA_DEBUG_LDS_EXTRA")) h->debug_lds_extra = atoi(e);
   if (const char* e = getenv("BA_DEBUG_MATCH_SPLITS")) h->debug_match_splits = atoi(e);
+  if (const char* e = getenv("BA_DEBUG_PG_SPLITS")) h->debug_pg_splits = atoi(e);
   return BA_OK;
 }
 extern "C" int ba_destroy(ba_handle* h);
@@ -4414,6 +4425,324 @@ extern "C" int ba_align(ba_handle* h, const ba_align_options* opts, const double
   memcpy(out->sim.t, rec.t, sizeof rec.t);
   out->rms = rec.rms;
   out->max = rec.max;
+  return BA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- pose graph
+// ba_pose_graph, ba_pose_graph_system (csrc/ba_posegraph.hpp).  Local to the rank: no collective.  Own buffers and own trace:
+// a resident problem, its parameters and the trace of its last solve stay as they are.
+extern "C" int ba_default_posegraph_options(ba_posegraph_options* o) {
+  if (!o) return fail(BA_ERR_INVALID, "null options");
+  memset(o, 0, sizeof *o);
+  o->loss = BA_LOSS_LINEAR;
+  o->max_iters = 50;
+  o->f_scale = 1.0;
+  o->ftol = 1e-5; o->xtol = 1e-5; o->gtol = 1e-8;      // ba_default_options' values
+  o->initial_lambda = 1e-4;
+  o->pcg_tol = 0.1;
+  o->pcg_max_iters = 200;
+  o->pcg_min_iters = 1;
+  o->with_scale = 1;
+  return BA_OK;
+}
+
+// the similarity rvec | t | s of row `idx` of `what` (poses or meas): finite, s > 0, |rvec| <= pi, s == 1 without scale
+static int pg_check_sim(const char* fn, const char* what, int idx, const double* v, bool with_scale) {
+  for (int q = 0; q < 7; ++q)
+    if (!std::isfinite(v[q])) return fail(BA_ERR_INVALID, "%s: %s[%d]: non-finite entry", fn, what, idx);
+  if (!(v[6] > 0)) return fail(BA_ERR_INVALID, "%s: %s[%d]: the scale s must be positive", fn, what, idx);
+  if (std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) > M_PI + 1e-9)
+    return fail(BA_ERR_INVALID, "%s: %s[%d]: |rvec| exceeds pi", fn, what, idx);
+  if (!with_scale && v[6] != 1.0) return fail(BA_ERR_INVALID, "%s: %s[%d]: with_scale = 0 needs every scale s to be exactly 1", fn, what, idx);
+  return BA_OK;
+}
+static int pg_validate(const char* fn, const ba_handle* h, int n, const double* poses, int m, const int32_t* ei, const int32_t* ej,
+                       const double* meas, const double* info, const ba_posegraph_options* o) {
+  if (!h || !o) return fail(BA_ERR_INVALID, "null argument");
+  if (n < 0) return fail(BA_ERR_INVALID, "%s: n must not be negative", fn);
+  if (m < 0) return fail(BA_ERR_INVALID, "%s: m must not be negative", fn);
+  if ((n > 0 && !poses) || (m > 0 && (!ei || !ej || !meas))) return fail(BA_ERR_INVALID, "%s: null array", fn);
+  if (!loss_valid(o->loss)) return fail(BA_ERR_INVALID, "%s: unknown loss %d", fn, o->loss);
+  if (!(o->f_scale > 0) || !std::isfinite(o->f_scale)) return fail(BA_ERR_INVALID, "%s: f_scale must be positive", fn);
+  if (o->max_iters < 0) return fail(BA_ERR_INVALID, "%s: max_iters must not be negative", fn);
+  if (o->pcg_max_iters < 0) return fail(BA_ERR_INVALID, "%s: pcg_max_iters must not be negative", fn);
+  if (o->pcg_min_iters < 0) return fail(BA_ERR_INVALID, "%s: pcg_min_iters must not be negative", fn);
+  if (!(o->ftol >= 0)) return fail(BA_ERR_INVALID, "%s: ftol must not be negative", fn);
+  if (!(o->xtol >= 0)) return fail(BA_ERR_INVALID, "%s: xtol must not be negative", fn);
+  if (!(o->gtol >= 0)) return fail(BA_ERR_INVALID, "%s: gtol must not be negative", fn);
+  if (!(o->pcg_tol >= 0)) return fail(BA_ERR_INVALID, "%s: pcg_tol must not be negative", fn);
+  if (!(o->initial_lambda > 0) || !std::isfinite(o->initial_lambda)) return fail(BA_ERR_INVALID, "%s: initial_lambda must be positive", fn);
+  if (o->reserved0 != 0) return fail(BA_ERR_INVALID, "%s: reserved0 must be 0", fn);
+  const bool ws = o->with_scale != 0;
+  for (int k = 0; k < n; ++k)
+    if (int rc = pg_check_sim(fn, "poses", k, poses + 7 * (size_t)k, ws)) return rc;
+  for (int e = 0; e < m; ++e) {
+    if (ei[e] < 0 || ei[e] >= n) return fail(BA_ERR_INVALID, "%s: edge_i[%d] = %d outside 0 .. %d", fn, e, ei[e], n - 1);
+    if (ej[e] < 0 || ej[e] >= n) return fail(BA_ERR_INVALID, "%s: edge_j[%d] = %d outside 0 .. %d", fn, e, ej[e], n - 1);
+    if (ei[e] == ej[e]) return fail(BA_ERR_INVALID, "%s: edge %d: edge_i == edge_j (%d)", fn, e, ei[e]);
+    if (int rc = pg_check_sim(fn, "meas", e, meas + 7 * (size_t)e, ws)) return rc;
+    if (!info) continue;
+    const double* I = info + 49 * (size_t)e;
+    double big = 0.0;
+    for (int q = 0; q < 49; ++q) {
+      if (!std::isfinite(I[q])) return fail(BA_ERR_INVALID, "%s: info[%d]: non-finite entry", fn, e);
+      big = std::max(big, std::fabs(I[q]));
+    }
+    double packed[28];
+    for (int a = 0; a < 7; ++a)
+      for (int b = a; b < 7; ++b) {
+        if (std::fabs(I[7 * a + b] - I[7 * b + a]) > 1e-12 * big) return fail(BA_ERR_INVALID, "%s: info[%d] is not symmetric", fn, e);
+        packed[UT(7, a, b)] = I[7 * a + b];
+      }
+    if (big == 0.0) continue;
+    double lo, hi;
+    sym_eig_range(packed, 7, &lo, &hi);
+    if (lo < -1e-12 * hi || !(hi > 0.0))
+      return fail(BA_ERR_INVALID, "%s: info[%d] is not positive semidefinite (eigenvalues %g .. %g)", fn, e, lo, hi);
+  }
+  return BA_OK;
+}
+
+struct PgPlan {
+  PgGraph G;
+  double* poses[2];
+  int nbe, nbn, nbt, nbs;          // workgroups: edge passes, nodes that are no hubs, those plus the hubs, the step
+};
+// incidence lists, masks, hubs; every array uploaded; the device's view filled in
+static int pg_prepare(ba_handle* h, int n, const double* poses, int m, const int32_t* ei, const int32_t* ej, const double* meas,
+                      const double* info, const uint8_t* held, const ba_posegraph_options* o, bool want_e, PgPlan* P) {
+  std::vector<int> iv((size_t)2 * m + (n + 1) + (size_t)2 * m + n);
+  int* hei = iv.data();
+  int* hej = hei + m;
+  int* off = hej + m;
+  int* inc = off + n + 1;
+  int* mask = inc + 2 * (size_t)m;
+  memcpy(hei, ei, (size_t)m * sizeof(int));
+  memcpy(hej, ej, (size_t)m * sizeof(int));
+  std::fill(off, off + n + 1, 0);
+  for (int e = 0; e < m; ++e) { off[ei[e] + 1]++; off[ej[e] + 1]++; }
+  for (int k = 0; k < n; ++k) off[k + 1] += off[k];
+  std::vector<int> fill(off, off + n);
+  for (int e = 0; e < m; ++e) { inc[fill[ei[e]]++] = 2 * e; inc[fill[ej[e]]++] = 2 * e + 1; }      // by edge number; low bit: the node is j
+  std::vector<int> hubs;
+  for (int k = 0; k < n; ++k) {
+    const int deg = off[k + 1] - off[k];
+    mask[k] = ((held && held[k]) || deg == 0) ? 0x7f : (o->with_scale ? 0 : 0x40);
+    if (deg > PG_HUB_MIN) { hubs.push_back(k); }
+  }
+  const int nh = (int)hubs.size();
+  std::vector<int> hub_len(nh);
+  for (int q = 0; q < nh; ++q) hub_len[q] = pg_chunk_len(off[hubs[q] + 1] - off[hubs[q]]);
+  P->nbe = std::min((m + PG_TEAMS - 1) / PG_TEAMS, PG_MAX_BLOCKS);
+  P->nbn = std::min((n + PG_TEAMS - 1) / PG_TEAMS, PG_MAX_BLOCKS);
+  P->nbt = P->nbn + nh;
+  P->nbs = std::min((n + PG_THREADS - 1) / PG_THREADS, PG_MAX_BLOCKS);
+  const size_t nn = (size_t)n, mm = (size_t)m;
+  const size_t n_d = 14 * nn + 7 * mm + (info ? 49 * mm : 0) + 4 * 49 * mm + 8 * mm + 7 * mm + 2 * mm + 49 * nn + 16 * nn + 49 * nn +
+                     40 * nn + 8 * mm + 2 * PG_MAX_BLOCKS + 3 * (size_t)P->nbt + 5 * PG_MAX_BLOCKS;
+  HIPCHECK(h->pg_d.alloc(n_d));
+  HIPCHECK(h->pg_i.alloc(iv.size() + 2 * (size_t)nh + 1));
+  HIPCHECK(h->pg_st.alloc(2));
+  HIPCHECK(h->pg_rec.alloc(1));
+  double* d = h->pg_d.p;
+  auto take = [&](size_t cnt) { double* r = d; d += cnt; return r; };
+  PgGraph& G = P->G;
+  memset(&G, 0, sizeof G);
+  G.n = n; G.m = m;
+  P->poses[0] = take(7 * nn); P->poses[1] = take(7 * nn);
+  double* dmeas = take(7 * mm);
+  double* dinfo = info ? take(49 * mm) : nullptr;
+  G.meas = dmeas; G.info = dinfo;
+  G.At = take(49 * mm); G.Bt = take(49 * mm); G.WA = take(49 * mm); G.WB = take(49 * mm);
+  double* const de = take(7 * mm);                              // (the residuals leave the device for the inspection entry only)
+  G.We = take(8 * mm); G.e = want_e ? de : nullptr; G.chi2 = take(mm); G.wgt = take(mm);
+  G.Hd = take(49 * nn); G.g = take(8 * nn); G.D = take(8 * nn); G.Minv = take(49 * nn);
+  G.x = take(8 * nn); G.r = take(8 * nn); G.z = take(8 * nn); G.p = take(8 * nn); G.q = take(8 * nn);
+  G.u = take(8 * mm);
+  G.part_cost = take(2 * PG_MAX_BLOCKS); G.part_g = take(P->nbt); G.part_rz = take(P->nbt); G.part_pq = take(P->nbt);
+  G.part_step = take(5 * PG_MAX_BLOCKS);
+  int* di = h->pg_i.p;
+  G.ei = di; G.ej = di + m; G.inc_off = di + 2 * mm; G.inc = di + 2 * mm + n + 1; G.mask = di + 4 * mm + n + 1;
+  int* dhub = di + iv.size();
+  G.hub_node = dhub; G.hub_len = dhub + nh; G.bad = dhub + 2 * nh;
+  G.n_hubs = nh; G.nb_nodes = P->nbn;
+  G.hub_teams = (h->debug_pg_splits > 0) ? std::min(h->debug_pg_splits, PG_TEAMS) : PG_TEAMS;
+  G.st = h->pg_st.p; G.rec = h->pg_rec.p;
+  // (pageable sources: the copies have left the host arrays when the calls return)
+  HIPCHECK(hipMemcpyAsync(P->poses[0], poses, 7 * nn * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(dmeas, meas, 7 * mm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (info) HIPCHECK(hipMemcpyAsync(dinfo, info, 49 * mm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(di, iv.data(), iv.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  hubs.insert(hubs.end(), hub_len.begin(), hub_len.end());
+  hubs.push_back(0);                                            // the `bad` word
+  HIPCHECK(hipMemcpyAsync(dhub, hubs.data(), hubs.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));                    // the host vectors above go out of scope
+  return BA_OK;
+}
+// linearisation at parameter set `which`: edge records, node blocks, gradient; cost and max |g| into the record
+static void pg_linearize(ba_handle* h, const PgPlan& P, int which, int loss, double inv_f2) {
+  BA_LAUNCH(k_pg_edge<true>, dim3(P.nbe), dim3(PG_THREADS), 0, h->stream, P.G, (const double*)P.poses[which], loss, inv_f2);
+  BA_LAUNCH(k_pg_node_lin, dim3(P.nbt), dim3(PG_THREADS), 0, h->stream, P.G);
+  BA_LAUNCH(k_pg_fold, dim3(1), dim3(64), 0, h->stream, P.G, P.nbe, P.nbt, 0, -1, 0, 0.0, 0);
+}
+static int pg_read_rec(ba_handle* h, PgRec* rec) {
+  HIPCHECK(hipMemcpyAsync(rec, h->pg_rec.p, sizeof *rec, hipMemcpyDeviceToHost, h->stream));
+  BA_SYNC(h);
+  return BA_OK;
+}
+
+extern "C" int ba_pose_graph(ba_handle* h, int32_t n, const double* poses, int32_t m, const int32_t* edge_i, const int32_t* edge_j,
+                             const double* meas, const double* info, const uint8_t* held, const ba_posegraph_options* opts,
+                             double* poses_out, ba_summary* sum, double* edge_chi2, double* edge_weight) {
+  if (int rc = pg_validate("ba_pose_graph", h, n, poses, m, edge_i, edge_j, meas, info, opts)) return rc;
+  ba_summary local;
+  if (!sum) sum = &local;
+  memset(sum, 0, sizeof *sum);
+  h->pg_trace.clear();
+  if (n == 0 || m == 0) {          // nothing to adjust
+    if (poses_out && n > 0) memcpy(poses_out, poses, 7 * (size_t)n * sizeof(double));
+    sum->status = 3;
+    sum->final_lambda = opts->initial_lambda;
+    return BA_OK;
+  }
+  if (set_device(h)) return BA_ERR_HIP;
+  const double t_begin = now_s();
+  PgPlan P;
+  if (int rc = pg_prepare(h, n, poses, m, edge_i, edge_j, meas, info, held, opts, false, &P)) return rc;
+  const int loss = opts->loss;
+  const double fs2 = opts->f_scale * opts->f_scale, inv_f2 = 1.0 / fs2, tol2 = opts->pcg_tol * opts->pcg_tol;
+  LmState st(opts->initial_lambda);
+  PgRec rec;
+  int cur = 0;
+  pg_linearize(h, P, cur, loss, inv_f2);
+  if (int rc = pg_read_rec(h, &rec)) return rc;
+  st.sse = rec.sse; st.cost = 0.5 * fs2 * rec.rho;
+  sum->initial_sse = st.sse; sum->initial_cost = st.cost;
+  if (!std::isfinite(st.cost)) return fail(BA_ERR_NUMERIC, "ba_pose_graph: non-finite cost at the initial poses");
+  st.need_linearize = false;
+  bool fresh = true;               // the gradient in `rec` has not met the gtol test yet (ba_solve: fresh linearisations only, gtol > 0 only)
+  while (st.it < opts->max_iters && !st.stop) {
+    const double t0 = now_s();
+    if (st.need_linearize) {
+      pg_linearize(h, P, cur, loss, inv_f2);
+      if (int rc = pg_read_rec(h, &rec)) return rc;
+      st.need_linearize = false;
+      fresh = true;
+    }
+    if (fresh) {
+      fresh = false;
+      if (!std::isfinite(rec.gmax) || rec.gmax >= 1e308) return fail(BA_ERR_NUMERIC, "ba_pose_graph: non-finite gradient at LM iteration %d", st.it);
+      if (opts->gtol > 0 && rec.gmax <= opts->gtol) { st.status = 3; break; }
+    }
+    const double t1 = now_s();
+    sum->seconds_linearize += t1 - t0;
+    // ---- the inner solve: three launches per iteration, the verdicts on the device; the host looks once per batch
+    BA_LAUNCH(k_pg_damp, dim3(P.nbn), dim3(PG_THREADS), 0, h->stream, P.G, st.lambda);
+    int k = 0, batch = 4;
+    PgRec pr;
+    while (true) {
+      for (int b = 0; b < batch && k < opts->pcg_max_iters; ++b, ++k) {
+        BA_LAUNCH(k_pg_pcg_edge, dim3(P.nbe), dim3(PG_THREADS), 0, h->stream, P.G, k, P.nbn, tol2, (int)opts->pcg_min_iters);
+        BA_LAUNCH(k_pg_pcg_node, dim3(P.nbt), dim3(PG_THREADS), 0, h->stream, P.G, k, st.lambda);
+        BA_LAUNCH(k_pg_pcg_step, dim3(P.nbn), dim3(PG_THREADS), 0, h->stream, P.G, k, P.nbt);
+      }
+      BA_LAUNCH(k_pg_fold, dim3(1), dim3(64), 0, h->stream, P.G, P.nbe, 0, 0, k, P.nbn, tol2, (int)opts->pcg_min_iters);
+      if (int rc = pg_read_rec(h, &pr)) return rc;
+      if (pr.bad) return fail(BA_ERR_NUMERIC, "ba_pose_graph: a damped diagonal block is not positive definite (LM iteration %d)", st.it);
+      if (pr.pcg.done || k >= opts->pcg_max_iters) break;
+      batch = std::min(2 * batch, 32);
+    }
+    const int pcg_iters = pr.pcg.done ? pr.pcg.iters : k;
+    sum->pcg_iterations += pcg_iters;
+    if (pcg_iters >= opts->pcg_max_iters) st.lam_floor = std::max(st.lam_floor, 3.0 * st.lambda);      // ba_solve's cap-aware damping
+    const double t2 = now_s();
+    sum->seconds_pcg += t2 - t1;
+    // ---- step, trial cost, the LM sums
+    BA_LAUNCH(k_pg_step, dim3(P.nbs), dim3(PG_THREADS), 0, h->stream, P.G, (const double*)P.poses[cur], P.poses[1 - cur]);
+    BA_LAUNCH(k_pg_edge<false>, dim3(P.nbe), dim3(PG_THREADS), 0, h->stream, P.G, (const double*)P.poses[1 - cur], loss, inv_f2);
+    BA_LAUNCH(k_pg_fold, dim3(1), dim3(64), 0, h->stream, P.G, P.nbe, 0, P.nbs, -1, 0, 0.0, 0);
+    PgRec tr;
+    if (int rc = pg_read_rec(h, &tr)) return rc;
+    // ---- verdict: ba_solve's rules (apply_verdict, lm_decide)
+    const double cost_new = 0.5 * fs2 * tr.rho, sse_new = tr.sse;
+    const double model = 0.5 * (st.lambda * tr.dDd - tr.gTd + tr.dr);
+    const double rho = model > 0 ? (st.cost - cost_new) / model : -1.0;
+    const bool accept = rho > 0 && std::isfinite(cost_new);
+    const int it = ++st.it;
+    ba_iter_record r = {};
+    r.iteration = it; r.accepted = accept ? 1 : 0; r.pcg_iterations = pcg_iters;
+    r.cost = st.cost; r.cost_trial = cost_new; r.sse_trial = sse_new; r.lambda = st.lambda; r.gain_ratio = rho;
+    r.step_norm = std::sqrt(tr.step2); r.seconds = now_s() - t0;
+    h->pg_trace.push_back(r);
+    if (accept) {
+      const double dcost = st.cost - cost_new;
+      cur = 1 - cur;
+      st.cost = cost_new; st.sse = sse_new;
+      sum->accepted++;
+      const double t = 2.0 * rho - 1.0;
+      st.lambda = std::max(std::max(st.lambda * std::max(1.0 / 3.0, 1.0 - t * t * t), 1e-12), st.lam_floor);
+      st.nu = 2.0;
+      st.need_linearize = true;
+      if (dcost <= opts->ftol * st.cost) { st.status = 1; st.stop = true; }
+    } else {
+      if (!std::isfinite(cost_new) && st.lambda >= 1e12)
+        return fail(BA_ERR_NUMERIC, "ba_pose_graph: non-finite cost at the trial point of LM iteration %d with the damping at its cap", it);
+      st.lambda = std::min(st.lambda * st.nu, 1e12);
+      st.nu *= 2.0;
+    }
+    if (!st.stop && std::sqrt(tr.step2) <= opts->xtol * (opts->xtol + std::sqrt(tr.x2))) { st.status = 2; st.stop = true; }
+    sum->seconds_update += now_s() - t2;
+  }
+  // chi2_e and w_e at the returned poses
+  BA_LAUNCH(k_pg_edge<false>, dim3(P.nbe), dim3(PG_THREADS), 0, h->stream, P.G, (const double*)P.poses[cur], loss, inv_f2);
+  if (poses_out) HIPCHECK(hipMemcpyAsync(poses_out, P.poses[cur], 7 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (edge_chi2) HIPCHECK(hipMemcpyAsync(edge_chi2, P.G.chi2, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (edge_weight) HIPCHECK(hipMemcpyAsync(edge_weight, P.G.wgt, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  BA_SYNC(h);
+  return finish_solve(sum, st, t_begin);
+}
+
+extern "C" int ba_pose_graph_trace(ba_handle* h, ba_iter_record* out, int32_t capacity, int32_t* n) {
+  if (!h || !n) return fail(BA_ERR_INVALID, "null argument");
+  *n = (int32_t)h->pg_trace.size();
+  if (out)
+    for (int i = 0; i < *n && i < capacity; ++i) out[i] = h->pg_trace[i];
+  return BA_OK;
+}
+
+extern "C" int ba_pose_graph_system(ba_handle* h, int32_t n, const double* poses, int32_t m, const int32_t* edge_i, const int32_t* edge_j,
+                                    const double* meas, const double* info, const uint8_t* held, const ba_posegraph_options* opts,
+                                    double lambda, double* e, double* A, double* B, double* H, double* g) {
+  if (int rc = pg_validate("ba_pose_graph_system", h, n, poses, m, edge_i, edge_j, meas, info, opts)) return rc;
+  if (7 * (long long)n > 4096) return fail(BA_ERR_INVALID, "ba_pose_graph_system: n = %d: the dense system is offered up to 7 n = 4096", n);
+  if (!(lambda >= 0)) return fail(BA_ERR_INVALID, "ba_pose_graph_system: lambda must not be negative");
+  if (n == 0 || m == 0) return fail(BA_ERR_INVALID, "ba_pose_graph_system: n and m must be positive");
+  if (set_device(h)) return BA_ERR_HIP;
+  PgPlan P;
+  if (int rc = pg_prepare(h, n, poses, m, edge_i, edge_j, meas, info, held, opts, true, &P)) return rc;
+  pg_linearize(h, P, 0, opts->loss, 1.0 / (opts->f_scale * opts->f_scale));
+  const size_t N = 7 * (size_t)n, mm = (size_t)m;
+  DBuf<double> dense;
+  if (H) {
+    HIPCHECK(dense.alloc(N * N));
+    BA_LAUNCH(k_pg_dense, dim3((unsigned)((N * N + PG_THREADS - 1) / PG_THREADS)), dim3(PG_THREADS), 0, h->stream, P.G, lambda, dense.p);
+    HIPCHECK(hipMemcpyAsync(H, dense.p, N * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  std::vector<double> at, bt, g8;
+  if (e) HIPCHECK(hipMemcpyAsync(e, P.G.e, 7 * mm * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (A) { at.resize(49 * mm); HIPCHECK(hipMemcpyAsync(at.data(), P.G.At, 49 * mm * sizeof(double), hipMemcpyDeviceToHost, h->stream)); }
+  if (B) { bt.resize(49 * mm); HIPCHECK(hipMemcpyAsync(bt.data(), P.G.Bt, 49 * mm * sizeof(double), hipMemcpyDeviceToHost, h->stream)); }
+  if (g) { g8.resize(8 * (size_t)n); HIPCHECK(hipMemcpyAsync(g8.data(), P.G.g, 8 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream)); }
+  BA_SYNC(h);
+  for (size_t q = 0; q < mm; ++q)          // the device keeps the transposes
+    for (int a = 0; a < 7; ++a)
+      for (int c = 0; c < 7; ++c) {
+        if (A) A[49 * q + 7 * a + c] = at[49 * q + 7 * c + a];
+        if (B) B[49 * q + 7 * a + c] = bt[49 * q + 7 * c + a];
+      }
+  if (g)
+    for (int k = 0; k < n; ++k)
+      for (int c = 0; c < 7; ++c) g[7 * (size_t)k + c] = g8[8 * (size_t)k + c];
   return BA_OK;
 }
 

@@ -154,6 +154,12 @@ class BAAlignOptions(C.Structure):
     _fields_ = [("loss", C.c_int32), ("iters", C.c_int32), ("f_scale", C.c_double), ("with_scale", C.c_int32), ("apply", C.c_int32)]
 
 
+class BAPosegraphOptions(C.Structure):
+    _fields_ = [("loss", C.c_int32), ("max_iters", C.c_int32), ("f_scale", C.c_double), ("ftol", C.c_double),
+                ("xtol", C.c_double), ("gtol", C.c_double), ("initial_lambda", C.c_double), ("pcg_tol", C.c_double),
+                ("pcg_max_iters", C.c_int32), ("pcg_min_iters", C.c_int32), ("with_scale", C.c_int32), ("reserved0", C.c_int32)]
+
+
 class BAAlignResult(C.Structure):
     _fields_ = [("sim", BASimilarity), ("rms", C.c_double), ("max", C.c_double), ("n_used", C.c_int32), ("status", C.c_int32)]
 
@@ -248,6 +254,12 @@ SYMBOLS = {
     "ba_transform": (C.c_int, [C.c_void_p, C.POINTER(BASimilarity)]),
     "ba_default_align_options": (C.c_int, [C.POINTER(BAAlignOptions)]),
     "ba_align": (C.c_int, [C.c_void_p, C.POINTER(BAAlignOptions), _DP, _DP, _DP, _DP, C.POINTER(BAAlignResult), _DP, _DP]),
+    "ba_default_posegraph_options": (C.c_int, [C.POINTER(BAPosegraphOptions)]),
+    "ba_pose_graph": (C.c_int, [C.c_void_p, C.c_int32, _DP, C.c_int32, _IP, _IP, _DP, _DP, C.POINTER(C.c_uint8),
+                                C.POINTER(BAPosegraphOptions), _DP, C.POINTER(BASummary), _DP, _DP]),
+    "ba_pose_graph_trace": (C.c_int, [C.c_void_p, C.POINTER(BAIterRecord), C.c_int32, C.POINTER(C.c_int32)]),
+    "ba_pose_graph_system": (C.c_int, [C.c_void_p, C.c_int32, _DP, C.c_int32, _IP, _IP, _DP, _DP, C.POINTER(C.c_uint8),
+                                       C.POINTER(BAPosegraphOptions), C.c_double, _DP, _DP, _DP, _DP, _DP]),
     "ba_get_trace": (C.c_int, [C.c_void_p, C.POINTER(BAIterRecord), C.c_int32, C.POINTER(C.c_int32)]),
     "ba_get_stat": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
     "ba_debug_occupy": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double]),
@@ -1028,14 +1040,76 @@ class Solver:
         return dict(s=res.sim.s, R=np.array(res.sim.R[:]).reshape(3, 3), t=np.array(res.sim.t[:]), rms=res.rms, max=res.max,
                     n_used=res.n_used, status=res.status, cam_err=cam_err, pt_err=pt_err)
 
+    def posegraph_options(self, **kw) -> BAPosegraphOptions:
+        """ba_posegraph_options: the library's defaults overlaid with kw (loss by scipy name or code; with_scale as a bool).
+        An unknown option or loss name raises ValueError."""
+        o = BAPosegraphOptions()
+        _check(self._lib.ba_default_posegraph_options(C.byref(o)))
+        for k, v in kw.items():
+            if k == "reserved0" or not hasattr(o, k):
+                raise ValueError(f"unknown pose-graph option {k!r}: expected one of "
+                                 f"{', '.join(n for n, _ in BAPosegraphOptions._fields_ if n != 'reserved0')}")
+            setattr(o, k, loss_code(v) if k == "loss" else (int(bool(v)) if k == "with_scale" else v))
+        return o
+
+    @staticmethod
+    def _posegraph_inputs(poses, edge_i, edge_j, meas, info, held):
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
+        ei = np.ascontiguousarray(edge_i, dtype=np.int32).reshape(-1)
+        ej = np.ascontiguousarray(edge_j, dtype=np.int32).reshape(-1)
+        m = ei.shape[0]
+        if ej.shape[0] != m:
+            raise ValueError(f"edge_i has {m} entries, edge_j {ej.shape[0]}")
+        meas = np.ascontiguousarray(meas, dtype=np.float64).reshape(m, 7)
+        info = None if info is None else np.ascontiguousarray(info, dtype=np.float64).reshape(m, 49)
+        held = None if held is None else np.ascontiguousarray(np.asarray(held) != 0, dtype=np.uint8).reshape(poses.shape[0])
+        return poses, ei, ej, meas, info, held
+
+    def pose_graph(self, poses, edge_i, edge_j, meas, info=None, held=None, **opts):
+        """ba_pose_graph: Sim(3) (with_scale=False: SE(3)) pose-graph optimisation.  poses (n, 7) = rvec | t | s world-to-node,
+        edges (i, j) with meas (m, 7) = S_j o S_i^-1 and info (m, 7, 7) (None: identity), held (n,) marks whole nodes kept
+        constant; opts: ba_posegraph_options.  Returns the summary's fields (BASummary.as_dict) plus poses (n, 7),
+        edge_chi2 (m,) and edge_weight (m,) at the returned poses.  Needs no problem and leaves a resident one as it is."""
+        o = self.posegraph_options(**opts)
+        poses, ei, ej, meas, info, held = self._posegraph_inputs(poses, edge_i, edge_j, meas, info, held)
+        n, m = poses.shape[0], ei.shape[0]
+        out, chi2, wgt = np.empty((n, 7)), np.empty(m), np.empty(m)
+        sm = BASummary()
+        _check(self._lib.ba_pose_graph(self._h, n, _dp(poses), m, ei.ctypes.data_as(_IP), ej.ctypes.data_as(_IP), _dp(meas), _dp(info),
+                                       None if held is None else held.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(o), _dp(out),
+                                       C.byref(sm), _dp(chi2), _dp(wgt)))
+        d = sm.as_dict()
+        d.update(poses=out, edge_chi2=chi2, edge_weight=wgt)
+        return d
+
+    def pose_graph_system(self, poses, edge_i, edge_j, meas, info=None, held=None, lam=0.0, **opts):
+        """ba_pose_graph_system: at the given poses dict(e (m, 7), A, B (m, 7, 7), H (7n, 7n) = H + lam D with the held rows as
+        identity rows, g (7n,)); opts gives loss, f_scale and with_scale.  7 n <= 4096."""
+        o = self.posegraph_options(**opts)
+        poses, ei, ej, meas, info, held = self._posegraph_inputs(poses, edge_i, edge_j, meas, info, held)
+        n, m = poses.shape[0], ei.shape[0]
+        dense = 7 * n if 7 * n <= 4096 else 0       # (the library refuses the call by name)
+        e, A, B, H, g = np.empty((m, 7)), np.empty((m, 7, 7)), np.empty((m, 7, 7)), np.empty((dense, dense)), np.empty(7 * n)
+        _check(self._lib.ba_pose_graph_system(self._h, n, _dp(poses), m, ei.ctypes.data_as(_IP), ej.ctypes.data_as(_IP), _dp(meas),
+                                              _dp(info), None if held is None else held.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                              C.byref(o), float(lam), _dp(e), _dp(A), _dp(B), _dp(H), _dp(g)))
+        return dict(e=e, A=A, B=B, H=H, g=g)
+
+    def pose_graph_trace(self):
+        """Per-iteration records of the last pose_graph on this handle (ba_pose_graph_trace): list of dicts as trace()."""
+        return self._trace(self._lib.ba_pose_graph_trace)
+
     def trace(self):
         """Per-iteration records of the last solve (ba_get_trace): list of dicts."""
+        return self._trace(self._lib.ba_get_trace)
+
+    def _trace(self, get):
         n = C.c_int32(0)
-        _check(self._lib.ba_get_trace(self._h, None, 0, C.byref(n)))
+        _check(get(self._h, None, 0, C.byref(n)))
         if n.value == 0:
             return []
         buf = (BAIterRecord * n.value)()
-        _check(self._lib.ba_get_trace(self._h, buf, n.value, C.byref(n)))
+        _check(get(self._h, buf, n.value, C.byref(n)))
         return [dict(iteration=r.iteration, accepted=bool(r.accepted), pcg_iterations=r.pcg_iterations, cost=r.cost,
                      cost_trial=r.cost_trial, sse_trial=r.sse_trial, damping=r.lambda_, gain_ratio=r.gain_ratio,
                      step_norm=r.step_norm, seconds=r.seconds) for r in buf[:n.value]]

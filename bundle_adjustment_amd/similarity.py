@@ -40,7 +40,7 @@ def inverse(sim):
     return 1.0 / s, R.T.copy(), -(R.T @ t) / s
 
 
-def _log_map(Rs):
+def log_map(Rs):
     """(n, 3, 3) rotation matrices -> (n, 3) rotation vectors, ``|rvec| <= pi``, through the unit quaternion picked by the
     largest of trace and diagonal entries (Shepperd), ``w >= 0``, ``theta = 2 atan2(|v|, w)``; exact to rounding at every
     angle from 0 to pi."""
@@ -66,6 +66,9 @@ def _log_map(Rs):
     return q[:, 1:] * k[:, None]
 
 
+_log_map = log_map
+
+
 def _transform_arrays(cams, pts, s=1.0, R=None, t=None):
     """The similarity applied to (Nc, >= 6) cameras ``rvec | t | ...`` (further columns are kept) and (Np, 3) points."""
     s, R, t = _srt(s, R, t)
@@ -76,7 +79,7 @@ def _transform_arrays(cams, pts, s=1.0, R=None, t=None):
     cams = np.array(cams, dtype=np.float64)
     Rn = rvecs_to_matrices(cams[:, :3]) @ R.T
     tn = s * cams[:, 3:6] - Rn @ t
-    cams[:, :3] = _log_map(Rn)
+    cams[:, :3] = log_map(Rn)
     cams[:, 3:6] = tn
     return cams, s * (np.asarray(pts, dtype=np.float64) @ R.T) + t
 

@@ -673,6 +673,65 @@ int ba_align(ba_handle* h, const ba_align_options* opts,
              const double* cam_ref, const double* cam_w,      /* [Nc][3], [Nc]; either pair may be NULL */
              const double* pt_ref,  const double* pt_w,       /* [Np][3], [Np] */
              ba_align_result* out, double* cam_err, double* pt_err);   /* errors may be NULL */
+
+/* ba_pose_graph: Sim(3) pose-graph optimisation -- the step between a loop closure and the global adjustment that spreads
+ * accumulated drift over the keyframes (ORB-SLAM's OptimizeEssentialGraph, g2o's EdgeSim3).  It needs no ba_set_problem and
+ * leaves a resident problem, its parameters and the trace of its last solve untouched; staging lives on the handle and is
+ * reused; local to the rank, no collective.
+ * Nodes  poses double[n][7] = rvec(3) | t(3) | s: the world-to-node similarity x_k = s_k R_k X + t_k, s_k > 0, R_k = exp(rvec_k).
+ *        A camera of the handle is the node rvec | t | 1.
+ * Edges  edge_i, edge_j int32[m], i != j, duplicates and either order allowed; meas double[m][7] = rvec_ij | t_ij | s_ij, the
+ *        measured S_j o S_i^-1, i.e. x_j = s_ij R_ij x_i + t_ij (ba_relative_pose's and ba_similarity's convention); info
+ *        double[m][49] row-major, symmetric, positive SEMIdefinite (a rotation-only edge is a block with zeros elsewhere), the
+ *        inverse covariance of the seven residuals below; NULL = identity.
+ * Residual  with s_r = s_j / s_i, R_r = R_j R_i^T, t_r = t_j - s_r R_r t_i:
+ *             e = [ log(R_ij^T R_r) ; t_r - t_ij ; ln(s_r / s_ij) ]                                     (7)
+ *        log = the Shepperd-quaternion log map, exact from 0 to pi.  The decoupled chart on purpose, not the Lie logarithm of
+ *        Sim(3).  chi2_e = e^T info e, z_e = chi2_e / f_scale^2, cost = 0.5 f_scale^2 sum_e rho(z_e): ONE rho per edge, any of
+ *        the five losses, solved by IRLS with w_e = rho'(z_e).  *_sse of the summary = sum chi2_e.
+ * Local parameters of node k, d = (d_omega, d_t, d_sigma): R_k <- exp(d_omega) R_k, t_k <- t_k + d_t, s_k <- s_k exp(d_sigma); rvec_k is
+ *        written back through the log map.  A_e = de/dd_i, B_e = de/dd_j analytic in fp64 (csrc/ba_posegraph.hpp).
+ *        H = sum w_e [A B]^T info [A B], g = sum w_e [A B]^T info e.
+ * Held   identity row / column, zero gradient, values returned bit-equal: every node marked in held uint8[n] (NULL: none), every
+ *        d_sigma when with_scale = 0, every free node without an incident edge.  with_scale = 0 demands every s_k and s_ij to be
+ *        exactly 1.0 and leaves them exactly 1.0.  No gauge is demanded: as in ba_solve the damping carries a free gauge.
+ * LM     ba_solve's rules: damping matrix D = max(diag H, 1e-12), gain ratio against the model decrease of the damped, inexactly
+ *        solved system, Nielsen's update with the floor of capped inner solves, acceptance, ftol / xtol / gtol over the free
+ *        parameters only (|x| over the stored rvec | t | s of the free entries), the status codes of ba_summary.
+ * Inner  PCG on the block-sparse H + lambda D, preconditioned by its 7 x 7 diagonal blocks (Cholesky per node); pcg_tol /
+ *        pcg_max_iters / pcg_min_iters as in ba_options; verdicts on the device, the host looks once per batch of iterations.
+ * Outputs (any may be NULL)  poses_out double[n][7]; summary; edge_chi2 / edge_weight double[m] = chi2_e and w_e at the returned
+ *        poses.  n = 0 or m = 0: poses copied, zero cost, status gtol.  Every sum has a fixed order and there are no
+ *        floating-point atomics: two calls give the same bits.
+ * BA_ERR_INVALID, naming the field: negative n or m, edge_i == edge_j, an index outside 0 .. n-1, a non-finite entry, s <= 0,
+ *        |rvec| > pi + 1e-9, info not symmetric to 1e-12 relative or not positive semidefinite, an unknown loss, f_scale <= 0,
+ *        negative counts or tolerances, the with_scale = 0 rule.  A refused call leaves the handle as found.
+ * BA_ERR_NUMERIC: a non-finite initial cost, or a damped diagonal block that is not positive definite. */
+typedef struct ba_posegraph_options {
+  int32_t loss;            /* ba_loss; default linear */
+  int32_t max_iters;       /* 50 */
+  double f_scale;          /* 1.0, in the unit of sqrt(chi2) */
+  double ftol, xtol, gtol; /* 1e-5, 1e-5, 1e-8 (ba_default_options) */
+  double initial_lambda;   /* 1e-4 */
+  double pcg_tol;          /* 0.1 */
+  int32_t pcg_max_iters;   /* 200 */
+  int32_t pcg_min_iters;   /* 1 */
+  int32_t with_scale;      /* 1: Sim(3); 0: SE(3), every s stays exactly 1 */
+  int32_t reserved0;       /* must be 0 */
+} ba_posegraph_options;
+int ba_default_posegraph_options(ba_posegraph_options* o);
+int ba_pose_graph(ba_handle* h, int32_t n, const double* poses, int32_t m, const int32_t* edge_i, const int32_t* edge_j,
+                  const double* meas, const double* info, const uint8_t* held, const ba_posegraph_options* opts,
+                  double* poses_out, ba_summary* summary, double* edge_chi2, double* edge_weight);
+/* The per-iteration records of the last ba_pose_graph on this handle (as ba_get_trace for ba_solve). */
+int ba_pose_graph_trace(ba_handle* h, ba_iter_record* out, int32_t capacity, int32_t* n);
+/* The inspection entry (as ba_linearize / ba_schur_system for the solve): at the given poses, the residuals e double[m][7],
+ * the Jacobians A, B double[m][49] row-major, the dense row-major (7n)^2 H + lambda D with the held rows in it (identity) and
+ * g double[7n]; opts gives loss, f_scale and with_scale.  Any output may be NULL.  Refuses 7 n > 4096 (BA_ERR_INVALID, naming n). */
+int ba_pose_graph_system(ba_handle* h, int32_t n, const double* poses, int32_t m, const int32_t* edge_i, const int32_t* edge_j,
+                         const double* meas, const double* info, const uint8_t* held, const ba_posegraph_options* opts,
+                         double lambda, double* e, double* A, double* B, double* H, double* g);
+
 /* Copies up to `capacity` records of the last ba_solve into out (may be NULL to ask for the count only);
  * *n = number of LM iterations recorded. */
 int ba_get_trace(ba_handle* h, ba_iter_record* out, int32_t capacity, int32_t* n);
