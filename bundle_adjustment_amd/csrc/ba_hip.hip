@@ -47,6 +47,7 @@
 #include "ba_match_guided.hpp"
 #include "ba_orb.hpp"
 #include "ba_posegraph.hpp"
+#include "ba_bow.hpp"
 
 using namespace ba;
 
@@ -197,6 +198,13 @@ struct PinnedStage {
   }
 };
 
+// The vocabulary tree of ba_vocab_train / ba_vocab_set as the host keeps it (ba_vocab_get reads it back from here)
+struct BowVocab {
+  int desc_bytes = 0, n_words = 0, branching = 0, levels = 0;
+  std::vector<int32_t> child0, n_child, word_of_node, idf_q;
+  std::vector<uint8_t> node_desc;
+};
+
 struct ba_handle {
   int device = 0;
   int n_cu = 256;              // compute units of the device (hipDeviceAttributeMultiprocessorCount)
@@ -342,7 +350,14 @@ struct ba_handle {
   DBuf<PgRec> pg_rec;
   std::vector<ba_iter_record> pg_trace;
   int debug_pg_splits = 0;     // BA_DEBUG_PG_SPLITS: teams that share a hub node's incidence list instead of all 32 (tests)
-  PinnedStage up;              // pinned arena of a window-sized problem's uploads (ba_set_problem: one copy, k_unpack_problem)
+  // place recognition (ba_bow.hpp): the resident vocabulary (host copy `vocab`, device arrays bw_child0 .. bw_ndesc), the
+  // descriptors of the call, one arena of ints and one of 64-bit words per call (training, transform and score carve them up)
+  BowVocab vocab;
+  DBuf<int> bw_child0, bw_nchild, bw_wordof, bw_idf, bw_i, bw_j, bw_dense;
+  DBuf<unsigned long long> bw_ndesc, bw_desc, bw_l;
+  DBuf<unsigned char> bw_b;
+  int debug_bow_chunk = 0;     // BA_DEBUG_BOW_CHUNK: database vectors per score workgroup instead of BW_CHUNK (tests)
+  PinnedStage up;             // pinned arena of a window-sized problem's uploads (ba_set_problem: one copy, k_unpack_problem)
   char* h_small = nullptr;     // k_small_lm's results, host-mapped: ba_summary | int cur | trace records
   char* d_small_host = nullptr;
   size_t h_small_bytes = 0;
@@ -495,6 +510,7 @@ static int create_impl(ba_handle* h, int device_id) {
   if (const char* e = getenv("BA_DEBUG_LDS_EXTRA")) h->debug_lds_extra = atoi(e);
   if (const char* e = getenv("BA_DEBUG_MATCH_SPLITS")) h->debug_match_splits = atoi(e);
   if (const char* e = getenv("BA_DEBUG_PG_SPLITS")) h->debug_pg_splits = atoi(e);
+  if (const char* e = getenv("BA_DEBUG_BOW_CHUNK")) h->debug_bow_chunk = atoi(e);
   return BA_OK;
 }
 extern "C" int ba_destroy(ba_handle* h);
@@ -4745,6 +4761,403 @@ extern "C" int ba_pose_graph_system(ba_handle* h, int32_t n, const double* poses
       for (int c = 0; c < 7; ++c) g[7 * (size_t)k + c] = g8[8 * (size_t)k + c];
   return BA_OK;
 }
+
+// ------------------------------------------------------------------------------------------------- place recognition
+// ba_vocab_train / ba_vocab_set / ba_vocab_get / ba_bow_transform / ba_bow_score (csrc/ba_bow.hpp).  Need no problem.
+static_assert(sizeof(ba_vocab_options) == 24, "ba_vocab_options (include/ba_hip.h)");
+static_assert(BW_MAX_SET >= 65536 && BW_CHUNK % 64 == 0, "a set holds at least ORB's most features");
+extern "C" int ba_default_vocab_options(ba_vocab_options* o) {
+  if (!o) return fail(BA_ERR_INVALID, "null argument");
+  memset(o, 0, sizeof *o);
+  o->branching = 10;
+  o->levels = 6;
+  o->iters = 10;
+  return BA_OK;
+}
+// What the calls that take descriptor sets refuse alike; `who` is the call the message names.
+static int bow_sets_check(const char* who, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc) {
+  if (desc_bytes < 8 || desc_bytes > 8 * MT_MAX_WORDS || desc_bytes % 8 != 0)
+    return fail(BA_ERR_INVALID, "%s: desc_bytes %d is not a multiple of 8 in 8 .. %d", who, desc_bytes, 8 * MT_MAX_WORDS);
+  if (n_sets < 0 || n_sets > 65535) return fail(BA_ERR_INVALID, "%s: n_sets %d is outside 0 .. 65535", who, n_sets);
+  if (!set_off) return fail(BA_ERR_INVALID, "%s: null set_off", who);
+  if (set_off[0] != 0) return fail(BA_ERR_INVALID, "%s: set_off[0] must be 0", who);
+  for (int32_t s = 0; s < n_sets; ++s)
+    if (set_off[s + 1] < set_off[s]) return fail(BA_ERR_INVALID, "%s: set_off decreases at set %d", who, s);
+  if (set_off[n_sets] > 0 && !desc) return fail(BA_ERR_INVALID, "%s: null desc", who);
+  return BA_OK;
+}
+// The tree becomes the handle's vocabulary: words numbered, depth measured, device arrays uploaded
+static int vocab_install(ba_handle* h, BowVocab& v, int branching, int levels) {
+  const size_t nn = v.child0.size(), W = (size_t)v.desc_bytes / 8;
+  v.word_of_node.assign(nn, -1);
+  v.n_words = 0;
+  for (size_t n = 0; n < nn; ++n)
+    if (v.child0[n] < 0) v.word_of_node[n] = v.n_words++;
+  v.branching = branching;
+  v.levels = levels;
+  HIPCHECK(h->bw_child0.alloc(nn)); HIPCHECK(h->bw_nchild.alloc(nn)); HIPCHECK(h->bw_wordof.alloc(nn));
+  HIPCHECK(h->bw_idf.alloc((size_t)v.n_words)); HIPCHECK(h->bw_ndesc.alloc(nn * W));
+  HIPCHECK(hipMemcpyAsync(h->bw_child0.p, v.child0.data(), nn * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(h->bw_nchild.p, v.n_child.data(), nn * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(h->bw_wordof.p, v.word_of_node.data(), nn * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(h->bw_idf.p, v.idf_q.data(), (size_t)v.n_words * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(h->bw_ndesc.p, v.node_desc.data(), nn * W * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));       // (v's arrays may move below)
+  h->vocab = std::move(v);
+  return BA_OK;
+}
+template <int W>
+static void launch_vocab_assign(ba_handle* h, unsigned grid, const VocabArgs& a) {
+  BA_LAUNCH(k_vocab_assign<W>, dim3(grid), dim3(BW_THREADS), 0, h->stream, a);
+}
+template <int W>
+static void launch_vocab_vote(ba_handle* h, unsigned grid, const VocabArgs& a) {
+  BA_LAUNCH(k_vocab_vote<W>, dim3(grid), dim3(BW_THREADS), 0, h->stream, a);
+}
+template <int W>
+static void launch_bow_descend(ba_handle* h, unsigned grid, const BowArgs& a) {
+  BA_LAUNCH(k_bow_descend<W>, dim3(grid), dim3(BW_THREADS), 0, h->stream, a);
+}
+#define BA_BY_WORDS(W_, fn, ...)                   \
+  switch (W_) {                                    \
+    case 1: fn<1>(__VA_ARGS__); break;             \
+    case 2: fn<2>(__VA_ARGS__); break;             \
+    case 3: fn<3>(__VA_ARGS__); break;             \
+    case 4: fn<4>(__VA_ARGS__); break;             \
+    case 5: fn<5>(__VA_ARGS__); break;             \
+    case 6: fn<6>(__VA_ARGS__); break;             \
+    case 7: fn<7>(__VA_ARGS__); break;             \
+    default: fn<8>(__VA_ARGS__); break;            \
+  }
+extern "C" int ba_vocab_train(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc,
+                              const ba_vocab_options* opts, int32_t* train_word, int32_t* n_nodes, int32_t* n_words) {
+  if (!h || !opts) return fail(BA_ERR_INVALID, "null argument");
+  if (int rc = bow_sets_check("ba_vocab_train", desc_bytes, n_sets, set_off, desc)) return rc;
+  if (set_off[n_sets] >= (1LL << BW_ROW_BITS))
+    return fail(BA_ERR_INVALID, "ba_vocab_train: rows %lld is not below 2^%d", (long long)set_off[n_sets], BW_ROW_BITS);
+  if (opts->branching < 2 || opts->branching > BW_MAX_K) return fail(BA_ERR_INVALID, "ba_vocab_train: branching %d is outside 2 .. %d", opts->branching, BW_MAX_K);
+  if (opts->levels < 1 || opts->levels > BW_MAX_LEVELS) return fail(BA_ERR_INVALID, "ba_vocab_train: levels %d is outside 1 .. %d", opts->levels, BW_MAX_LEVELS);
+  if (opts->iters < 1) return fail(BA_ERR_INVALID, "ba_vocab_train: iters %d is below 1", opts->iters);
+  if (opts->min_split != 0 && opts->min_split < 2) return fail(BA_ERR_INVALID, "ba_vocab_train: min_split %d is neither 0 nor at least 2", opts->min_split);
+  const int k = opts->branching, rows = (int)set_off[n_sets], W = desc_bytes / 8, BITS = 64 * W;
+  const int min_split = opts->min_split == 0 ? 2 * k : opts->min_split;
+  if (set_device(h)) return BA_ERR_HIP;
+  BowVocab v;
+  v.desc_bytes = desc_bytes;
+  v.child0.assign(1, -1);
+  v.n_child.assign(1, 0);
+  v.node_desc.assign((size_t)desc_bytes, 0);
+  std::vector<int> count(1, rows), node_of_row((size_t)rows, 0);
+  if (rows >= min_split) {
+    const size_t nr = (size_t)rows;
+    const unsigned row_grid = (unsigned)((nr + BW_THREADS - 1) / BW_THREADS);
+    HIPCHECK(h->bw_desc.alloc(nr * W)); HIPCHECK(h->bw_i.alloc(3 * nr));
+    VocabArgs a = {};
+    a.desc = h->bw_desc.p; a.perm = h->bw_i.p; a.node = h->bw_i.p + nr; a.slot = h->bw_i.p + 2 * nr;
+    a.rows = rows; a.k = k; a.words = W;
+    {
+      std::vector<int> iota(nr);
+      for (size_t r = 0; r < nr; ++r) iota[r] = (int)r;
+      HIPCHECK(hipMemcpyAsync(h->bw_desc.p, desc, nr * (size_t)desc_bytes, hipMemcpyHostToDevice, h->stream));
+      HIPCHECK(hipMemcpyAsync(a.perm, iota.data(), nr * sizeof(int), hipMemcpyHostToDevice, h->stream));
+      HIPCHECK(hipMemsetAsync(a.node, 0, nr * sizeof(int), h->stream));
+      HIPCHECK(hipMemsetAsync(a.slot, 0xff, nr * sizeof(int), h->stream));
+      HIPCHECK(hipStreamSynchronize(h->stream));
+    }
+    int lvl_begin = 0, lvl_n = 1;
+    std::vector<unsigned char> open;
+    std::vector<int> size, child, cursor;
+    std::vector<unsigned long long> centre;
+    for (int d = 0; d < opts->levels && lvl_n > 0; ++d) {
+      open.assign((size_t)lvl_n, 0);
+      bool any = false;
+      for (int n = 0; n < lvl_n; ++n) any |= (open[n] = count[lvl_begin + n] >= min_split) != 0;
+      if (!any) break;
+      const size_t ns = (size_t)lvl_n * k, n_cursor = v.child0.size() + ns;
+      // ints: size | child | changed | cursor | votes; 64-bit words: seed_key | centre; bytes: open | usable
+      HIPCHECK(h->bw_j.alloc(2 * ns + 1 + n_cursor + ns * BITS)); HIPCHECK(h->bw_l.alloc(ns + ns * W)); HIPCHECK(h->bw_b.alloc((size_t)lvl_n + ns));
+      a.lvl_begin = lvl_begin; a.lvl_n = lvl_n;
+      a.size = h->bw_j.p; int* d_child = h->bw_j.p + ns; a.child = d_child; a.changed = h->bw_j.p + 2 * ns; a.cursor = a.changed + 1; a.votes = a.cursor + n_cursor;
+      a.seed_key = h->bw_l.p; a.centre = h->bw_l.p + ns;
+      unsigned char* d_open = h->bw_b.p; a.open = d_open; a.usable = h->bw_b.p + lvl_n;
+      for (int j = 0; j < k; ++j) a.pre[j] = bw_mix(bw_mix(bw_mix(opts->seed + BW_GOLDEN) + (unsigned long long)d) + (unsigned long long)j);
+      HIPCHECK(hipMemcpyAsync(d_open, open.data(), (size_t)lvl_n, hipMemcpyHostToDevice, h->stream));
+      HIPCHECK(hipMemsetAsync(a.seed_key, 0xff, ns * 8, h->stream));
+      const unsigned slot_grid = (unsigned)((ns + BW_THREADS - 1) / BW_THREADS);
+      BA_LAUNCH(k_vocab_seed_key, dim3(row_grid), dim3(BW_THREADS), 0, h->stream, a);
+      BA_LAUNCH(k_vocab_seed_set, dim3(slot_grid), dim3(BW_THREADS), 0, h->stream, a);
+      // iters rounds of (assign, stop when nothing moved, vote, centres), then the closing assignment
+      for (int it = 0; it <= opts->iters; ++it) {
+        HIPCHECK(hipMemsetAsync(a.size, 0, ns * sizeof(int), h->stream));
+        HIPCHECK(hipMemsetAsync(a.changed, 0, sizeof(int), h->stream));
+        BA_BY_WORDS(W, launch_vocab_assign, h, row_grid, a);
+        if (it == opts->iters) break;
+        int changed = 0;
+        HIPCHECK(hipMemcpyAsync(&changed, a.changed, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        BA_SYNC(h);
+        if (changed == 0) break;      // (this assignment already is the closing one: same centres, same slots, same sizes)
+        HIPCHECK(hipMemsetAsync(a.votes, 0, ns * BITS * sizeof(int), h->stream));
+        BA_BY_WORDS(W, launch_vocab_vote, h, row_grid, a);
+        BA_LAUNCH(k_vocab_centre, dim3((unsigned)((ns * W + BW_THREADS - 1) / BW_THREADS)), dim3(BW_THREADS), 0, h->stream, a);
+      }
+      size.resize(ns); centre.resize(ns * W);
+      HIPCHECK(hipMemcpyAsync(size.data(), a.size, ns * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+      HIPCHECK(hipMemcpyAsync(centre.data(), a.centre, ns * W * 8, hipMemcpyDeviceToHost, h->stream));
+      BA_SYNC(h);
+      // the children, breadth-first by (parent, slot)
+      child.assign(ns, -1);
+      const int first_new = (int)v.child0.size();
+      for (int n = 0; n < lvl_n; ++n) {
+        if (!open[n]) continue;
+        int full = 0;
+        for (int j = 0; j < k; ++j) full += size[(size_t)n * k + j] > 0;
+        if (full < 2) continue;
+        v.child0[lvl_begin + n] = (int)v.child0.size();
+        v.n_child[lvl_begin + n] = full;
+        count[lvl_begin + n] = 0;
+        for (int j = 0; j < k; ++j) {
+          const size_t e = (size_t)n * k + j;
+          if (size[e] == 0) continue;
+          child[e] = (int)v.child0.size();
+          v.child0.push_back(-1);
+          v.n_child.push_back(0);
+          count.push_back(size[e]);
+          const uint8_t* c = (const uint8_t*)(centre.data() + e * W);
+          v.node_desc.insert(v.node_desc.end(), c, c + desc_bytes);
+        }
+      }
+      const int n_new = (int)v.child0.size() - first_new;
+      if (n_new == 0) break;
+      cursor.assign(v.child0.size(), 0);
+      for (size_t n = 0, at = 0; n < v.child0.size(); ++n) { cursor[n] = (int)at; at += (size_t)count[n]; }
+      HIPCHECK(hipMemcpyAsync(d_child, child.data(), ns * sizeof(int), hipMemcpyHostToDevice, h->stream));
+      HIPCHECK(hipMemcpyAsync(a.cursor, cursor.data(), cursor.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+      BA_LAUNCH(k_vocab_children, dim3(row_grid), dim3(BW_THREADS), 0, h->stream, a);
+      BA_LAUNCH(k_vocab_scatter, dim3(row_grid), dim3(BW_THREADS), 0, h->stream, a);
+      BA_SYNC(h);                     // (the host vectors above are reused by the next level)
+      lvl_begin = first_new;
+      lvl_n = n_new;
+    }
+    HIPCHECK(hipMemcpyAsync(node_of_row.data(), a.node, nr * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    BA_SYNC(h);
+  }
+  // words, the sets that reach each word, idf
+  int nw = 0;
+  std::vector<int> word_of((size_t)v.child0.size(), -1);
+  for (size_t n = 0; n < v.child0.size(); ++n)
+    if (v.child0[n] < 0) word_of[n] = nw++;
+  std::vector<int> n_with((size_t)nw, 0), last((size_t)nw, -1);
+  for (int32_t s = 0; s < n_sets; ++s)
+    for (int64_t r = set_off[s]; r < set_off[s + 1]; ++r) {
+      const int w = word_of[node_of_row[r]];
+      if (train_word) train_word[r] = w;
+      if (last[w] != s) { last[w] = s; ++n_with[w]; }
+    }
+  v.idf_q.assign((size_t)nw, 0);
+  for (int w = 0; w < nw; ++w)
+    if (n_with[w] > 0) v.idf_q[w] = (int32_t)std::floor(std::log((double)n_sets / (double)n_with[w]) * 4096.0 + 0.5);
+  if (n_nodes) *n_nodes = (int32_t)v.child0.size();
+  if (n_words) *n_words = nw;
+  return vocab_install(h, v, k, opts->levels);
+}
+
+extern "C" int ba_vocab_size(ba_handle* h, int32_t* desc_bytes, int32_t* n_nodes, int32_t* n_words, int32_t* branching, int32_t* levels) {
+  if (!h) return fail(BA_ERR_INVALID, "null handle");
+  const BowVocab& v = h->vocab;       // (no vocabulary: every number is 0)
+  if (desc_bytes) *desc_bytes = v.desc_bytes;
+  if (n_nodes) *n_nodes = (int32_t)v.child0.size();
+  if (n_words) *n_words = v.n_words;
+  if (branching) *branching = v.branching;
+  if (levels) *levels = v.levels;
+  return BA_OK;
+}
+extern "C" int ba_vocab_get(ba_handle* h, int32_t* child0, int32_t* n_child, uint8_t* node_desc, int32_t* word_of_node, int32_t* idf_q) {
+  if (!h) return fail(BA_ERR_INVALID, "null handle");
+  const BowVocab& v = h->vocab;
+  if (v.child0.empty()) return fail(BA_ERR_STATE, "ba_vocab_get: no vocabulary: call ba_vocab_train or ba_vocab_set first");
+  if (child0) memcpy(child0, v.child0.data(), v.child0.size() * sizeof(int32_t));
+  if (n_child) memcpy(n_child, v.n_child.data(), v.n_child.size() * sizeof(int32_t));
+  if (node_desc) memcpy(node_desc, v.node_desc.data(), v.node_desc.size());
+  if (word_of_node) memcpy(word_of_node, v.word_of_node.data(), v.word_of_node.size() * sizeof(int32_t));
+  if (idf_q) memcpy(idf_q, v.idf_q.data(), v.idf_q.size() * sizeof(int32_t));
+  return BA_OK;
+}
+extern "C" int ba_vocab_set(ba_handle* h, int32_t desc_bytes, int32_t n_nodes, const int32_t* child0, const int32_t* n_child,
+                            const uint8_t* node_desc, const int32_t* idf_q) {
+  if (!h) return fail(BA_ERR_INVALID, "null handle");
+  if (desc_bytes < 8 || desc_bytes > 8 * MT_MAX_WORDS || desc_bytes % 8 != 0)
+    return fail(BA_ERR_INVALID, "ba_vocab_set: desc_bytes %d is not a multiple of 8 in 8 .. %d", desc_bytes, 8 * MT_MAX_WORDS);
+  if (n_nodes < 1) return fail(BA_ERR_INVALID, "ba_vocab_set: n_nodes %d is below 1", n_nodes);
+  if (!child0 || !n_child || !node_desc || !idf_q) return fail(BA_ERR_INVALID, "ba_vocab_set: null argument");
+  // breadth-first and contiguous: walking the nodes in order, the children of the inner nodes tile 1 .. n_nodes - 1 exactly
+  // once, in order -- so every node but the root is the child of exactly one node, and children follow their parent
+  std::vector<int> depth((size_t)n_nodes, 0);
+  int next = 1, deepest = 0, widest = 0, nw = 0;
+  for (int n = 0; n < n_nodes; ++n) {
+    if (child0[n] < 0) {
+      if (n_child[n] != 0) return fail(BA_ERR_INVALID, "ba_vocab_set: n_child[%d] = %d at a leaf (child0 < 0) must be 0", n, n_child[n]);
+      ++nw;
+      continue;
+    }
+    if (n_child[n] < 2 || n_child[n] > BW_MAX_K)
+      return fail(BA_ERR_INVALID, "ba_vocab_set: n_child[%d] = %d is neither 0 nor in 2 .. %d", n, n_child[n], BW_MAX_K);
+    if (child0[n] != next)
+      return fail(BA_ERR_INVALID, "ba_vocab_set: child0[%d] = %d: children are not breadth-first contiguous (expected %d)", n, child0[n], next);
+    if (n_child[n] > n_nodes - next)
+      return fail(BA_ERR_INVALID, "ba_vocab_set: the children of node %d reach past n_nodes", n);
+    if (depth[n] + 1 > BW_MAX_LEVELS) return fail(BA_ERR_INVALID, "ba_vocab_set: depth of the children of node %d exceeds %d", n, BW_MAX_LEVELS);
+    for (int c = next; c < next + n_child[n]; ++c) depth[c] = depth[n] + 1;
+    deepest = std::max(deepest, depth[n] + 1);
+    widest = std::max(widest, n_child[n]);
+    next += n_child[n];
+  }
+  if (next != n_nodes) return fail(BA_ERR_INVALID, "ba_vocab_set: node %d is the child of no node (every node but the root must be the child of exactly one)", next);
+  for (int w = 0; w < nw; ++w) {
+    if (idf_q[w] < 0) return fail(BA_ERR_INVALID, "ba_vocab_set: idf_q[%d] = %d is negative", w, idf_q[w]);
+    if (idf_q[w] > BW_MAX_IDF) return fail(BA_ERR_INVALID, "ba_vocab_set: idf_q[%d] = %d is above %d", w, idf_q[w], BW_MAX_IDF);
+  }
+  if (set_device(h)) return BA_ERR_HIP;
+  BowVocab v;
+  v.desc_bytes = desc_bytes;
+  v.child0.assign(child0, child0 + n_nodes);
+  v.n_child.assign(n_child, n_child + n_nodes);
+  v.node_desc.assign(node_desc, node_desc + (size_t)n_nodes * desc_bytes);
+  v.idf_q.assign(idf_q, idf_q + nw);
+  return vocab_install(h, v, widest, deepest);
+}
+
+extern "C" int ba_bow_transform(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc,
+                                int32_t weighting, int32_t* desc_word, int64_t* vec_off, int32_t* vec_word, int32_t* vec_val) {
+  if (!h) return fail(BA_ERR_INVALID, "null handle");
+  if (int rc = bow_sets_check("ba_bow_transform", desc_bytes, n_sets, set_off, desc)) return rc;
+  if (weighting != BA_BOW_TF_IDF && weighting != BA_BOW_TF)
+    return fail(BA_ERR_INVALID, "ba_bow_transform: weighting %d is neither BA_BOW_TF_IDF (0) nor BA_BOW_TF (1)", weighting);
+  for (int32_t s = 0; s < n_sets; ++s)
+    if (set_off[s + 1] - set_off[s] > BW_MAX_SET)
+      return fail(BA_ERR_INVALID, "ba_bow_transform: set_off: set %d holds %lld descriptors, more than %d", s,
+                  (long long)(set_off[s + 1] - set_off[s]), BW_MAX_SET);
+  if (set_off[n_sets] > 0x7fffffffLL) return fail(BA_ERR_INVALID, "ba_bow_transform: rows %lld is above 2^31 - 1", (long long)set_off[n_sets]);
+  const BowVocab& v = h->vocab;
+  if (v.child0.empty()) return fail(BA_ERR_STATE, "ba_bow_transform: no vocabulary: call ba_vocab_train or ba_vocab_set first");
+  if (desc_bytes != v.desc_bytes)
+    return fail(BA_ERR_INVALID, "ba_bow_transform: desc_bytes %d is not the vocabulary's %d", desc_bytes, v.desc_bytes);
+  if (vec_off) memset(vec_off, 0, ((size_t)n_sets + 1) * sizeof(int64_t));
+  const size_t nr = (size_t)set_off[n_sets], W = (size_t)desc_bytes / 8, ns = (size_t)n_sets, nw = (size_t)v.n_words;
+  if (nr == 0) return BA_OK;
+  if (set_device(h)) return BA_ERR_HIP;
+  const size_t batch = std::max<size_t>(1, std::min(ns, ((size_t)1 << 26) / nw));
+  // ints: word | out_word | out_val | nnz; dense counts of a batch of sets in bw_j; set_off in bw_l
+  HIPCHECK(h->bw_desc.alloc(nr * W)); HIPCHECK(h->bw_i.alloc(3 * nr + ns)); HIPCHECK(h->bw_j.alloc(batch * nw)); HIPCHECK(h->bw_l.alloc(ns + 1));
+  BowArgs a = {};
+  a.desc = h->bw_desc.p; a.set_off = (const long long*)h->bw_l.p;
+  a.child0 = h->bw_child0.p; a.n_child = h->bw_nchild.p; a.node_desc = h->bw_ndesc.p; a.word_of_node = h->bw_wordof.p; a.idf_q = h->bw_idf.p;
+  a.rows = (int)nr; a.n_sets = n_sets; a.n_words = v.n_words; a.tf = weighting == BA_BOW_TF;
+  a.word = h->bw_i.p; a.out_word = h->bw_i.p + nr; a.out_val = h->bw_i.p + 2 * nr; a.nnz = h->bw_i.p + 3 * nr; a.cnt = h->bw_j.p;
+  HIPCHECK(hipMemcpyAsync(h->bw_desc.p, desc, nr * (size_t)desc_bytes, hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(h->bw_l.p, set_off, (ns + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  BA_BY_WORDS(W, launch_bow_descend, h, (unsigned)((nr + BW_THREADS - 1) / BW_THREADS), a);
+  for (size_t s0 = 0; s0 < ns; s0 += batch) {
+    a.s0 = (int)s0; a.s1 = (int)std::min(ns, s0 + batch);
+    const size_t n = (size_t)(set_off[a.s1] - set_off[a.s0]);
+    HIPCHECK(hipMemsetAsync(a.cnt, 0, (size_t)(a.s1 - a.s0) * nw * sizeof(int), h->stream));
+    if (n > 0) BA_LAUNCH(k_bow_count, dim3((unsigned)((n + BW_THREADS - 1) / BW_THREADS)), dim3(BW_THREADS), 0, h->stream, a);
+    BA_LAUNCH(k_bow_vector, dim3((unsigned)(a.s1 - a.s0)), dim3(BW_THREADS), 0, h->stream, a);
+  }
+  std::vector<int32_t> nnz(ns), ow, ov;
+  if (desc_word) HIPCHECK(hipMemcpyAsync(desc_word, a.word, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(hipMemcpyAsync(nnz.data(), a.nnz, ns * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (vec_word) { ow.resize(nr); HIPCHECK(hipMemcpyAsync(ow.data(), a.out_word, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream)); }
+  if (vec_val) { ov.resize(nr); HIPCHECK(hipMemcpyAsync(ov.data(), a.out_val, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream)); }
+  BA_SYNC(h);
+  // the sets wrote from their own first row: close the gaps
+  int64_t at = 0;
+  for (size_t s = 0; s < ns; ++s) {
+    if (vec_word) memcpy(vec_word + at, ow.data() + set_off[s], (size_t)nnz[s] * sizeof(int32_t));
+    if (vec_val) memcpy(vec_val + at, ov.data() + set_off[s], (size_t)nnz[s] * sizeof(int32_t));
+    at += nnz[s];
+    if (vec_off) vec_off[s + 1] = at;
+  }
+  return BA_OK;
+}
+
+// A CSR of bag-of-words vectors as ba_bow_score takes it; `who` names the side in the message
+static int bow_csr_check(const char* who, int32_t n, const int64_t* off, const int32_t* word, const int32_t* val, int32_t* max_word) {
+  if (n < 0) return fail(BA_ERR_INVALID, "ba_bow_score: the number of %s vectors %d is negative", who, n);
+  if (!off) return fail(BA_ERR_INVALID, "ba_bow_score: null %s offsets", who);
+  if (off[0] != 0) return fail(BA_ERR_INVALID, "ba_bow_score: %s offsets must start at 0", who);
+  for (int32_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return fail(BA_ERR_INVALID, "ba_bow_score: %s offsets decrease at vector %d", who, i);
+  if (off[n] > 0x7fffffffLL) return fail(BA_ERR_INVALID, "ba_bow_score: %s entries %lld is above 2^31 - 1", who, (long long)off[n]);
+  if (off[n] > 0 && (!word || !val)) return fail(BA_ERR_INVALID, "ba_bow_score: null %s words or values", who);
+  for (int32_t i = 0; i < n; ++i) {
+    int64_t sum = 0;
+    for (int64_t e = off[i]; e < off[i + 1]; ++e) {
+      if (word[e] < 0 || (e > off[i] && word[e] <= word[e - 1]))
+        return fail(BA_ERR_INVALID, "ba_bow_score: the words of %s vector %d are not ascending from 0", who, i);
+      if (val[e] < 0) return fail(BA_ERR_INVALID, "ba_bow_score: %s vector %d has a negative value", who, i);
+      sum += val[e];
+      *max_word = std::max(*max_word, word[e]);
+    }
+    if (sum > (1LL << 30)) return fail(BA_ERR_INVALID, "ba_bow_score: the values of %s vector %d sum to more than 2^30", who, i);
+  }
+  return BA_OK;
+}
+extern "C" int ba_bow_score(ba_handle* h, int32_t nq, const int64_t* q_off, const int32_t* q_word, const int32_t* q_val, int32_t nd,
+                            const int64_t* d_off, const int32_t* d_word, const int32_t* d_val, const int32_t* db_end, int32_t top_k,
+                            int32_t* top_idx, int32_t* top_score, int32_t* score) {
+  if (!h) return fail(BA_ERR_INVALID, "null handle");
+  if (top_k < 1 || top_k > BW_MAX_TOPK) return fail(BA_ERR_INVALID, "ba_bow_score: top_k %d is outside 1 .. %d", top_k, BW_MAX_TOPK);
+  int32_t q_max = -1, d_max = -1;
+  if (int rc = bow_csr_check("query", nq, q_off, q_word, q_val, &q_max)) return rc;
+  if (int rc = bow_csr_check("database", nd, d_off, d_word, d_val, &d_max)) return rc;
+  const size_t nqs = (size_t)nq, nds = (size_t)nd, kq = nqs * (size_t)top_k, qn = (size_t)q_off[nq], dn = (size_t)d_off[nd];
+  for (size_t i = 0; i < kq; ++i) {
+    if (top_idx) top_idx[i] = -1;
+    if (top_score) top_score[i] = 0;
+  }
+  if (score) memset(score, 0, nqs * nds * sizeof(int32_t));
+  if (qn == 0 || dn == 0) return BA_OK;        // no common word anywhere: every output is already well-formed
+  const int chunk = h->debug_bow_chunk > 0 ? std::min(h->debug_bow_chunk, BW_CHUNK) : BW_CHUNK;
+  const size_t n_chunks = (nds + chunk - 1) / chunk, nw = (size_t)d_max + 1, n_keys = n_chunks * nw;
+  if (n_chunks > 65535 || n_keys > 0x7fffffffULL)
+    return fail(BA_ERR_INVALID, "ba_bow_score: %zu database chunks of %d vectors times %zu words is more than one call indexes", n_chunks, chunk, nw);
+  if (set_device(h)) return BA_ERR_HIP;
+  // 64-bit words: q_off | d_off | part; ints: q_word | q_val | d_word | d_val | inv_j | inv_v | db_end | top_idx | top_score;
+  // bw_j: hist | cursor
+  const size_t n_part = nqs * n_chunks * (size_t)top_k;
+  HIPCHECK(h->bw_l.alloc(nqs + 1 + nds + 1 + n_part)); HIPCHECK(h->bw_i.alloc(2 * qn + 4 * dn + nqs + 2 * kq)); HIPCHECK(h->bw_j.alloc(2 * n_keys + 1));
+  if (score) HIPCHECK(h->bw_dense.alloc(nqs * nds));
+  ScoreArgs a = {};
+  long long* d_qoff = (long long*)h->bw_l.p; long long* d_doff = d_qoff + nqs + 1;
+  a.q_off = d_qoff; a.d_off = d_doff; a.part = h->bw_l.p + nqs + 1 + nds + 1;
+  int* p = h->bw_i.p;
+  int* d_qw = p; int* d_qv = p + qn; int* d_dw = p + 2 * qn; int* d_dv = d_dw + dn;
+  a.q_word = d_qw; a.q_val = d_qv; a.d_word = d_dw; a.d_val = d_dv; a.inv_j = d_dv + dn; a.inv_v = a.inv_j + dn;
+  int* d_end = a.inv_v + dn; a.db_end = db_end ? d_end : nullptr; a.top_idx = d_end + nqs; a.top_score = a.top_idx + kq;
+  a.hist = h->bw_j.p; a.cursor = h->bw_j.p + n_keys + 1; a.dense = score ? h->bw_dense.p : nullptr;
+  a.nq = nq; a.nd = nd; a.n_words = (int)nw; a.chunk = chunk; a.n_chunks = (int)n_chunks; a.top_k = top_k; a.d_nnz = (long long)dn; a.n_keys = (long long)n_keys;
+  HIPCHECK(hipMemcpyAsync(d_qoff, q_off, (nqs + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(d_doff, d_off, (nds + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(d_qw, q_word, qn * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(d_qv, q_val, qn * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(d_dw, d_word, dn * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(d_dv, d_val, dn * 4, hipMemcpyHostToDevice, h->stream));
+  if (db_end) HIPCHECK(hipMemcpyAsync(d_end, db_end, nqs * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemsetAsync(a.hist, 0, (n_keys + 1) * sizeof(int), h->stream));
+  const unsigned entry_grid = (unsigned)((dn + BW_THREADS - 1) / BW_THREADS);
+  BA_LAUNCH(k_bow_inv_hist, dim3(entry_grid), dim3(BW_THREADS), 0, h->stream, a);
+  BA_LAUNCH(k_bow_scan, dim3(1), dim3(BW_SCAN_THREADS), 0, h->stream, a);
+  HIPCHECK(hipMemcpyAsync(a.cursor, a.hist, n_keys * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+  BA_LAUNCH(k_bow_inv_scatter, dim3(entry_grid), dim3(BW_THREADS), 0, h->stream, a);
+  BA_LAUNCH(k_bow_score_chunk, dim3((unsigned)nq, (unsigned)n_chunks), dim3(BW_THREADS), 0, h->stream, a);
+  BA_LAUNCH(k_bow_score_merge, dim3((unsigned)((nqs + BW_THREADS - 1) / BW_THREADS)), dim3(BW_THREADS), 0, h->stream, a);
+  if (top_idx) HIPCHECK(hipMemcpyAsync(top_idx, a.top_idx, kq * 4, hipMemcpyDeviceToHost, h->stream));
+  if (top_score) HIPCHECK(hipMemcpyAsync(top_score, a.top_score, kq * 4, hipMemcpyDeviceToHost, h->stream));
+  if (score) HIPCHECK(hipMemcpyAsync(score, a.dense, nqs * nds * 4, hipMemcpyDeviceToHost, h->stream));
+  BA_SYNC(h);
+  return BA_OK;
+}
+#undef BA_BY_WORDS
 
 // ------------------------------------------------------------------------ bench hook
 extern "C" int ba_time_kernel(ba_handle* h, int slot, int reps, double* mean_us) {

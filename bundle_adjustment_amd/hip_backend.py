@@ -135,7 +135,15 @@ class BAOrbOptions(C.Structure):
                 ("fast_threshold", C.c_int32)]
 
 
+class BAVocabOptions(C.Structure):
+    _fields_ = [("branching", C.c_int32), ("levels", C.c_int32), ("iters", C.c_int32), ("min_split", C.c_int32), ("seed", C.c_uint64)]
+
+
 GATE = {"window": 1, "epipolar": 2}   # enum BA_GATE_*
+BOW_WEIGHTING = {"tf_idf": 0, "tf": 1}   # enum BA_BOW_*
+# place recognition (csrc/ba_bow.hpp): the unit of a vector entry, the unit of idf_q, the most rows of a set in bow_transform,
+# the most training rows (exclusive), the database vectors per score workgroup, the largest top_k, branching and depth
+BOW_ONE, BOW_IDF_ONE, BOW_MAX_SET, BOW_MAX_TRAIN_ROWS, BOW_CHUNK, BOW_MAX_TOPK, BOW_MAX_BRANCHING, BOW_MAX_LEVELS = 1 << 30, 4096, 1 << 16, 1 << 24, 4096, 64, 32, 8
 
 # ba_match_descriptors (csrc/ba_match.hpp): queries per workgroup, train descriptors per LDS tile, the shortest train split,
 # the most splits of a pair, the most descriptors of a set, the descriptor widths
@@ -260,6 +268,16 @@ SYMBOLS = {
     "ba_pose_graph_trace": (C.c_int, [C.c_void_p, C.POINTER(BAIterRecord), C.c_int32, C.POINTER(C.c_int32)]),
     "ba_pose_graph_system": (C.c_int, [C.c_void_p, C.c_int32, _DP, C.c_int32, _IP, _IP, _DP, _DP, C.POINTER(C.c_uint8),
                                        C.POINTER(BAPosegraphOptions), C.c_double, _DP, _DP, _DP, _DP, _DP]),
+    "ba_default_vocab_options": (C.c_int, [C.POINTER(BAVocabOptions)]),
+    "ba_vocab_train": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(BAVocabOptions),
+                                 _IP, _IP, _IP]),
+    "ba_vocab_size": (C.c_int, [C.c_void_p, _IP, _IP, _IP, _IP, _IP]),
+    "ba_vocab_get": (C.c_int, [C.c_void_p, _IP, _IP, C.POINTER(C.c_uint8), _IP, _IP]),
+    "ba_vocab_set": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _IP, _IP, C.POINTER(C.c_uint8), _IP]),
+    "ba_bow_transform": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.c_int32, _IP,
+                                   C.POINTER(C.c_int64), _IP, _IP]),
+    "ba_bow_score": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _IP, _IP, C.c_int32, C.POINTER(C.c_int64), _IP, _IP, _IP,
+                               C.c_int32, _IP, _IP, _IP]),
     "ba_get_trace": (C.c_int, [C.c_void_p, C.POINTER(BAIterRecord), C.c_int32, C.POINTER(C.c_int32)]),
     "ba_get_stat": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
     "ba_debug_occupy": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double]),
@@ -411,6 +429,44 @@ def _match_outputs(P, rows):
     good, n_good = np.zeros(rows, dtype=np.uint8), np.zeros(P, dtype=np.int32)
     tail = [out["row_off"].ctypes.data_as(C.POINTER(C.c_int64))] + [out[k].ctypes.data_as(_IP) for k in ("best", "second", "dist1", "dist2")]
     return out, good, n_good, tail + [good.ctypes.data_as(C.POINTER(C.c_uint8)), n_good.ctypes.data_as(_IP)]
+
+
+def vocab_options(**kw) -> BAVocabOptions:
+    """ba_default_vocab_options overlaid with kw (any ba_vocab_options field; an unknown one raises TypeError).  No GPU."""
+    return _options(BAVocabOptions, load_library().ba_default_vocab_options, kw, names={})
+
+
+def _bow_sets(sets, width=None):
+    """What the place recognition calls take of a list of descriptor sets: the sets as arrays, their width, set_off and the
+    concatenated descriptors.  width: the width an empty list stands for, and, when given, the one every set must have."""
+    arrs = [np.asarray(a) for a in sets]
+    for a in arrs:
+        if a.dtype != np.uint8 or a.ndim != 2:
+            raise ValueError(f"every descriptor set must be a 2-D uint8 array, not {a.dtype} with shape {a.shape}")
+    widths = {a.shape[1] for a in arrs}
+    if len(widths) > 1:
+        raise ValueError(f"descriptor sets of different widths: {sorted(widths)} bytes")
+    if widths and width is not None and widths != {width}:
+        raise ValueError(f"descriptor sets of {widths.pop()} bytes, the vocabulary has {width}")
+    width = widths.pop() if widths else (32 if width is None else width)
+    set_off = np.zeros(len(arrs) + 1, dtype=np.int64)
+    set_off[1:] = np.cumsum([a.shape[0] for a in arrs])
+    desc = np.ascontiguousarray(np.concatenate(arrs, axis=0)) if arrs else np.zeros((0, width), dtype=np.uint8)
+    return arrs, width, set_off, desc
+
+
+def _bow_csr(v, what):
+    """(vec_off int64, vec_word int32, vec_val int32) of a dict of bag-of-words vectors as bow_transform returns it."""
+    try:
+        off, word, val = (np.asarray(v[k]) for k in ("vec_off", "vec_word", "vec_val"))
+    except (KeyError, TypeError, IndexError):
+        raise ValueError(f"{what} must be a dict with vec_off, vec_word and vec_val") from None
+    for name, a in (("vec_off", off), ("vec_word", word), ("vec_val", val)):
+        if a.ndim != 1 or a.dtype.kind not in "iu":
+            raise ValueError(f"{what}: {name} must be a 1-D integer array, not {a.dtype} with shape {a.shape}")
+    if len(off) < 1 or len(word) != len(val) or int(off[-1]) != len(word):
+        raise ValueError(f"{what}: vec_off must end at the number of entries of vec_word and vec_val")
+    return (np.ascontiguousarray(off, dtype=np.int64), np.ascontiguousarray(word, dtype=np.int32), np.ascontiguousarray(val, dtype=np.int32))
 
 
 def orb_options(**kw) -> BAOrbOptions:
@@ -1002,6 +1058,99 @@ class Solver:
         ms = np.zeros(len(ORB_STAGES))
         _check(self._lib.ba_orb_stage_times(self._h, -1 if enable is None else int(bool(enable)), _dp(ms)))
         return dict(zip(ORB_STAGES, ms.tolist()))
+
+    def train_vocabulary(self, sets, **opts):
+        """ba_vocab_train: a vocabulary tree of the descriptor sets (one set per training image) by hierarchical k-majority;
+        it becomes the handle's vocabulary.  opts: branching, levels, iters, min_split, seed.  Returns vocabulary()'s dict plus
+        train_word (rows,) int32, the word of every training row."""
+        arrs, width, set_off, desc = _bow_sets(sets)
+        o = vocab_options(**opts)
+        train_word = np.zeros(desc.shape[0], dtype=np.int32)
+        nn, nw = C.c_int32(0), C.c_int32(0)
+        _check(self._lib.ba_vocab_train(self._h, width, len(arrs), set_off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                        desc.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(o), train_word.ctypes.data_as(_IP),
+                                        C.byref(nn), C.byref(nw)))
+        out = self.vocabulary()
+        out["train_word"] = train_word
+        return out
+
+    def vocabulary_size(self):
+        """ba_vocab_size: dict(desc_bytes, n_nodes, n_words, branching, levels) of the resident vocabulary; zeros without one."""
+        v = [C.c_int32(0) for _ in range(5)]
+        _check(self._lib.ba_vocab_size(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("desc_bytes", "n_nodes", "n_words", "branching", "levels"), (x.value for x in v)))
+
+    def vocabulary(self):
+        """ba_vocab_get: the resident vocabulary as a dict: desc_bytes, n_nodes, n_words, branching, levels, child0, n_child,
+        word_of_node (n_nodes,) int32, node_desc (n_nodes, desc_bytes) uint8, idf_q (n_words,) int32."""
+        out = self.vocabulary_size()
+        nn, nw, B = out["n_nodes"], out["n_words"], out["desc_bytes"]
+        out.update(child0=np.zeros(nn, dtype=np.int32), n_child=np.zeros(nn, dtype=np.int32), word_of_node=np.zeros(nn, dtype=np.int32),
+                   node_desc=np.zeros((nn, B), dtype=np.uint8), idf_q=np.zeros(nw, dtype=np.int32))
+        _check(self._lib.ba_vocab_get(self._h, out["child0"].ctypes.data_as(_IP), out["n_child"].ctypes.data_as(_IP),
+                                      out["node_desc"].ctypes.data_as(C.POINTER(C.c_uint8)), out["word_of_node"].ctypes.data_as(_IP),
+                                      out["idf_q"].ctypes.data_as(_IP)))
+        return out
+
+    def set_vocabulary(self, vocab):
+        """ba_vocab_set: upload a saved or hand-made tree (child0, n_child, node_desc, idf_q of a dict or a place.Vocabulary);
+        the library validates it and names the violation."""
+        get = vocab.get if isinstance(vocab, dict) else lambda k: getattr(vocab, k)
+        child0 = np.ascontiguousarray(get("child0"), dtype=np.int32)
+        n_child = np.ascontiguousarray(get("n_child"), dtype=np.int32)
+        node_desc = np.asarray(get("node_desc"))
+        idf_q = np.ascontiguousarray(get("idf_q"), dtype=np.int32)
+        if node_desc.dtype != np.uint8 or node_desc.ndim != 2:
+            raise ValueError(f"node_desc must be a 2-D uint8 array, not {node_desc.dtype} with shape {node_desc.shape}")
+        node_desc = np.ascontiguousarray(node_desc)
+        if child0.ndim != 1 or child0.shape != n_child.shape or node_desc.shape[0] != child0.shape[0]:
+            raise ValueError("child0, n_child and node_desc must have one entry per node")
+        if idf_q.ndim != 1 or idf_q.shape[0] != int((child0 < 0).sum()):
+            raise ValueError("idf_q must have one entry per leaf (child0 < 0)")
+        _check(self._lib.ba_vocab_set(self._h, node_desc.shape[1], child0.shape[0], child0.ctypes.data_as(_IP), n_child.ctypes.data_as(_IP),
+                                      node_desc.ctypes.data_as(C.POINTER(C.c_uint8)), idf_q.ctypes.data_as(_IP)))
+
+    def bow_transform(self, sets, weighting="tf_idf"):
+        """ba_bow_transform: the bag-of-words vector of every descriptor set under the resident vocabulary.  weighting "tf_idf"
+        or "tf".  Returns dict(desc_word (rows,) int32, vec_off (n_sets + 1,) int64, vec_word, vec_val (nnz,) int32): a CSR with
+        the words ascending within a set and the values summing to at most BOW_ONE."""
+        if weighting not in BOW_WEIGHTING:
+            raise ValueError(f"unknown weighting {weighting!r}: expected one of {', '.join(map(repr, BOW_WEIGHTING))}")
+        sets = list(sets)          # (an empty list stands for no rows of the vocabulary's width; a wrong width is the library's to refuse)
+        arrs, width, set_off, desc = _bow_sets(sets, None if sets else self.vocabulary_size()["desc_bytes"] or None)
+        rows = desc.shape[0]
+        word, vw, vv = (np.zeros(rows, dtype=np.int32) for _ in range(3))
+        vec_off = np.zeros(len(arrs) + 1, dtype=np.int64)
+        _check(self._lib.ba_bow_transform(self._h, width, len(arrs), set_off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                          desc.ctypes.data_as(C.POINTER(C.c_uint8)), BOW_WEIGHTING[weighting], word.ctypes.data_as(_IP),
+                                          vec_off.ctypes.data_as(C.POINTER(C.c_int64)), vw.ctypes.data_as(_IP), vv.ctypes.data_as(_IP)))
+        nnz = int(vec_off[-1])
+        return dict(desc_word=word, vec_off=vec_off, vec_word=vw[:nnz].copy(), vec_val=vv[:nnz].copy())
+
+    def bow_score(self, query, db, db_end=None, top_k=10, dense=False):
+        """ba_bow_score: the L1 score sum of min(vq_i, vd_i) of every query vector against the database vectors, both dicts as
+        bow_transform returns them.  db_end (nq,): query q sees the database entries j < db_end[q] only.  Returns dict(top_idx,
+        top_score (nq, top_k) int32, padded with -1 / 0) and, with dense, score (nq, nd) int32."""
+        q_off, q_word, q_val = _bow_csr(query, "query")
+        d_off, d_word, d_val = _bow_csr(db, "db")
+        nq, nd = len(q_off) - 1, len(d_off) - 1
+        end = None
+        if db_end is not None:
+            end = np.ascontiguousarray(db_end, dtype=np.int32)
+            if end.shape != (nq,):
+                raise ValueError(f"db_end must have one entry per query ({nq}), not shape {end.shape}")
+        top_k = int(top_k)
+        if not 1 <= top_k <= BOW_MAX_TOPK:
+            raise ValueError(f"top_k {top_k} is outside 1 .. {BOW_MAX_TOPK}")
+        out = dict(top_idx=np.zeros((nq, top_k), dtype=np.int32), top_score=np.zeros((nq, top_k), dtype=np.int32))
+        if dense:
+            out["score"] = np.zeros((nq, nd), dtype=np.int32)
+        p64 = C.POINTER(C.c_int64)
+        _check(self._lib.ba_bow_score(self._h, nq, q_off.ctypes.data_as(p64), q_word.ctypes.data_as(_IP), q_val.ctypes.data_as(_IP), nd,
+                                      d_off.ctypes.data_as(p64), d_word.ctypes.data_as(_IP), d_val.ctypes.data_as(_IP),
+                                      None if end is None else end.ctypes.data_as(_IP), top_k, out["top_idx"].ctypes.data_as(_IP),
+                                      out["top_score"].ctypes.data_as(_IP), out["score"].ctypes.data_as(_IP) if dense else None))
+        return out
 
     def centres(self):
         """ba_get_centres: (Nc, 3) camera centres -R_c^T t_c of the current cameras."""

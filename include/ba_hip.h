@@ -731,6 +731,81 @@ int ba_pose_graph_trace(ba_handle* h, ba_iter_record* out, int32_t capacity, int
 int ba_pose_graph_system(ba_handle* h, int32_t n, const double* poses, int32_t m, const int32_t* edge_i, const int32_t* edge_j,
                          const double* meas, const double* info, const uint8_t* held, const ba_posegraph_options* opts,
                          double lambda, double* e, double* A, double* B, double* H, double* g);
+/* Place recognition: which earlier image does a new one revisit (the loop_i, loop_j ba_pose_graph takes as given), and which
+ * image pairs of a collection are worth matching at all.  A binary bag of words as in DBoW2 (ORB-SLAM's loop detection) and
+ * COLMAP's vocabulary-tree matcher: a vocabulary tree over the descriptors, one sparse vector per image, an L1 score between
+ * vectors.  Three calls, none of which needs ba_set_problem or touches a resident problem; the vocabulary IS resident on the
+ * handle: set by ba_vocab_train or ba_vocab_set, read by ba_bow_transform.  Local to the rank.  Everything is integer arithmetic
+ * (one log on the host for the idf weights), so results are bit-reproducible and independent of how the library tiles the work.
+ * Descriptor sets are given as in ba_match_descriptors: desc uint8[set_off[n_sets]][desc_bytes], desc_bytes a multiple of 8 in
+ * 8 .. 64, n_sets in 0 .. 65535; one set is one image.
+ *
+ * ba_vocab_train: hierarchical k-majority over all rows (rows < 2^24).  The root (node 0, depth 0, descriptor all zero) holds
+ * every row.  A node at depth d < levels with m >= min_split member rows is split:
+ *   seeds      slot j in 0 .. branching - 1 starts from the descriptor of the member row x with the smallest key
+ *              (draw(seed, d, j, x) & ~0xFFFFFF) | x, draw = ba_resect_ransac's counter-based generator (splitmix64 chained four
+ *              times) with (camera, hypothesis, draw number) = (d, j, x) and x the row's index in desc.  A slot whose row an earlier
+ *              slot of the node drew is void: it takes part in no assignment and stays empty.
+ *   iteration  at most iters times: (1) every member goes to the slot with the smallest (Hamming distance to the slot's centre,
+ *              slot) among the slots that are not void; (2) stop if no member's slot changed; (3) the centre of every non-empty
+ *              slot becomes the bitwise majority of its members, bit = 1 iff 2 * count >= size (a tie is 1, DBoW2's rule); an
+ *              empty slot keeps its centre.
+ *   closing    members are assigned once more to the final centres; the non-empty slots become the node's children in slot order,
+ *              their descriptors the centres.  With fewer than two non-empty slots the node stays a leaf.
+ * Nodes with m < min_split and nodes at depth `levels` are leaves.  Nodes are numbered breadth-first by (parent, slot), so a
+ * node's children are contiguous; the leaves are the WORDS, numbered in node order.  idf_q[i] = floor(ln(N / N_i) * 4096 + 0.5),
+ * N = n_sets, N_i the number of sets with a row in word i (computed on the host in double; 0 where N_i = 0).
+ * Outputs (any may be NULL): train_word int32[rows], the word of every row (equal to ba_bow_transform's desc_word of the same rows);
+ * n_nodes, n_words.  BA_ERR_INVALID, naming the field: the set arguments as in ba_match_descriptors, rows >= 2^24, an option out
+ * of range.  Cost and layout: csrc/ba_bow.hpp, DESIGN.md 4r.
+ *
+ * ba_vocab_size: the resident vocabulary's numbers (all 0 when there is none); branching and levels are the training options,
+ * or, after ba_vocab_set, the largest n_child and the tree's depth.  ba_vocab_get: child0, n_child, word_of_node int32[n_nodes]
+ * (child0 = -1, n_child = 0 at a leaf; word_of_node = -1 at an inner node), node_desc uint8[n_nodes][desc_bytes], idf_q
+ * int32[n_words]; any may be NULL; BA_ERR_STATE without a vocabulary.  ba_vocab_set uploads a saved or hand-made tree; BA_ERR_INVALID
+ * naming the violation unless: walking the nodes in order, the children of the inner nodes are breadth-first contiguous (child0
+ * of the first inner node is 1, each next inner node's follows the previous one's children); every node but the root is the
+ * child of exactly one node (the children end at n_nodes); n_child is 0 at a leaf and 2 .. 32 at an inner node; depth <= 8;
+ * 0 <= idf_q <= 131071 (so that no vector entry overflows 63 bits).
+ *
+ * ba_bow_transform: a row descends from the root, at each inner node to the child with the smallest (Hamming distance, slot), down
+ * to a leaf: its word.  Per set, with c_i the number of its rows in word i: a_i = c_i * idf_q[i] (weighting BA_BOW_TF_IDF) or
+ * c_i * 4096 (BA_BOW_TF, for a vocabulary trained on one set), A = sum a_i, v_i = (a_i << 30) / A in 64-bit integer division;
+ * entries with v_i = 0 are dropped and A = 0 gives an empty vector.  Outputs (any may be NULL): desc_word int32[rows]; the CSR
+ * vec_off int64[n_sets + 1], vec_word (ascending within a set) and vec_val int32[], for which the caller provides `rows` entries.
+ * A set's vector does not depend on the other sets of the call.  BA_ERR_STATE without a vocabulary; BA_ERR_INVALID: desc_bytes not
+ * the vocabulary's, a set of more than 65536 rows, weighting not 0 / 1, the set arguments as above.
+ *
+ * ba_bow_score: score(q, j) = sum over the common words of min(vq_i, vd_i), an integer in 0 .. 2^30; for L1-normalised
+ * non-negative vectors this equals 1 - |v_q - v_d|_1 / 2 (DBoW2's L1 score) in units of 2^-30.  Queries and database are CSRs
+ * as ba_bow_transform writes them (words ascending within a vector, values >= 0 that sum to at most 2^30; otherwise BA_ERR_INVALID).
+ * db_end int32[nq] or NULL: query q is scored against the database entries j < db_end[q] only (clamped to 0 .. nd; NULL: all) -- a
+ * SLAM front end passes its own index minus a gap, an image list scored against itself passes q.  Outputs (any may be NULL):
+ * top_idx, top_score int32[nq][top_k], top_k in 1 .. 64: the admitted entries with score > 0 ordered by (score descending, index
+ * ascending), padded with -1 / 0; score int32[nq][nd], the dense matrix, 0 where not admitted.
+ * Not offered: other weightings and norms (L2, chi-square, KL, dot product), DBoW2's direct index (desc_word lets a caller build
+ * one), k-means++ seeding, float descriptors, DBoW2's text / binary vocabulary files, temporal consistency checks, vocabularies
+ * spread over ranks. */
+typedef struct ba_vocab_options {
+  int32_t  branching;    /* k, 2 .. 32; default 10 */
+  int32_t  levels;       /* L, 1 .. 8; default 6 */
+  int32_t  iters;        /* k-majority iterations per level, >= 1; default 10 */
+  int32_t  min_split;    /* fewest members a node must have to be split, >= 2; 0 (default) means 2 * branching */
+  uint64_t seed;         /* seed of the row draws; default 0 */
+} ba_vocab_options;      /* 24 bytes */
+enum { BA_BOW_TF_IDF = 0, BA_BOW_TF = 1 };
+int ba_default_vocab_options(ba_vocab_options* opts);    /* 10, 6, 10, 0, 0 */
+int ba_vocab_train(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc,
+                   const ba_vocab_options* opts, int32_t* train_word, int32_t* n_nodes, int32_t* n_words);
+int ba_vocab_size(ba_handle* h, int32_t* desc_bytes, int32_t* n_nodes, int32_t* n_words, int32_t* branching, int32_t* levels);
+int ba_vocab_get(ba_handle* h, int32_t* child0, int32_t* n_child, uint8_t* node_desc, int32_t* word_of_node, int32_t* idf_q);
+int ba_vocab_set(ba_handle* h, int32_t desc_bytes, int32_t n_nodes, const int32_t* child0, const int32_t* n_child,
+                 const uint8_t* node_desc, const int32_t* idf_q);
+int ba_bow_transform(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc,
+                     int32_t weighting, int32_t* desc_word, int64_t* vec_off, int32_t* vec_word, int32_t* vec_val);
+int ba_bow_score(ba_handle* h, int32_t nq, const int64_t* q_off, const int32_t* q_word, const int32_t* q_val, int32_t nd,
+                 const int64_t* d_off, const int32_t* d_word, const int32_t* d_val, const int32_t* db_end, int32_t top_k,
+                 int32_t* top_idx, int32_t* top_score, int32_t* score);
 
 /* Copies up to `capacity` records of the last ba_solve into out (may be NULL to ask for the count only);
  * *n = number of LM iterations recorded. */
