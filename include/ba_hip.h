@@ -300,7 +300,8 @@ int ba_resect(ba_handle* h, const double* intr, const ba_resect_options* opts, c
  *               that are not selected, of points that are not known, those whose bearing failed, and those of a camera whose
  *               status is FEW_POINTS or DEGENERATE without a pose.  What a pipeline deletes before the next solve.
  * Per selected camera, over its n usable observations (point known, bearing exists), indexed 0 .. n - 1 in the handle's
- * camera-ordered list (within a camera: the caller's order):
+ * camera-ordered list (within a camera: ascending in the handle's internal point number -- the caller's point index while the
+ * camera table fits the point passes' LDS, DESIGN.md section 3 -- which is the caller's order only when that ascends in the point):
  * (1) n < 4: FEW_POINTS (three points reproduce themselves; a fourth chooses among P3P's solutions).
  * (2) Hypothesis h = 0 .. n_hyp - 1 draws three distinct indices.  mix(z) is the splitmix64 finaliser: z ^= z >> 30;
  * z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31.  With G = 0x9E3779B97F4A7C15 and everything

@@ -262,6 +262,28 @@ def decompose(Hn, x1, x2, inl, thr, max_depth, min_translation, ambiguity_ratio)
 
 
 # ------------------------------------------------------------------------------------------------------------ the call
+def hypothesis_costs(K, p1, p2, pair=0, n_hyp=256, seed=0, max_px=3.0):
+    """Steps 2 - 4 of the header, hypothesis by hypothesis -> (cost (n_hyp,): the MSAC cost of the hypothesis's H~, inf when it
+    is void; slot (n_hyp,): 0, -1 when void (a sample has one solution); H: that H~, None when void).  The winner of step 4
+    among the first N hypotheses is relpose_reference.winner(cost, N)."""
+    K = np.asarray(K, dtype=np.float64).reshape(3, 3)
+    x1, x2 = RP.normalise(K, p1), RP.normalise(K, p2)
+    thr = max_px / (0.5 * (K[0, 0] + K[1, 1]))
+    cost, slot, Hs = np.full(n_hyp, np.inf), np.full(n_hyp, -1, dtype=np.int64), [None] * n_hyp
+    for h in range(n_hyp):
+        idx = list(sample4(seed, pair, h, len(p1)))
+        Hh = four_point(x1[idx], x2[idx])
+        if Hh is None:
+            continue
+        c = msac(Hh, x1, x2, thr)
+        if c < np.inf:
+            cost[h], slot[h], Hs[h] = c, 0, Hh
+    return cost, slot, Hs
+
+
+winner = RP.winner
+
+
 def homography(K, p1, p2, pair=0, n_hyp=256, lo_rounds=2, seed=0, max_px=3.0, refine_iters=20, min_inliers=8, max_depth=50.0,
                ambiguity_ratio=0.75, min_translation=MIN_TRANSLATION):
     """One pair (its index in the call: `pair`), steps 0 - 8 of the header.  Hn is H~ (normalised coordinates), H the pixel one."""
@@ -277,15 +299,9 @@ def homography(K, p1, p2, pair=0, n_hyp=256, lo_rounds=2, seed=0, max_px=3.0, re
     x1, x2 = RP.normalise(K, p1), RP.normalise(K, p2)
     fbar = 0.5 * (K[0, 0] + K[1, 1])
     thr = max_px / fbar
-    best = (np.inf, -1, None)
-    for h in range(n_hyp):
-        idx = list(sample4(seed, pair, h, n))
-        Hh = four_point(x1[idx], x2[idx])
-        if Hh is None:
-            continue
-        c = msac(Hh, x1, x2, thr)
-        if c < best[0]:
-            best = (c, h, Hh)
+    cost, _, Hs = hypothesis_costs(K, p1, p2, pair, n_hyp, seed, max_px)
+    h = winner(cost)
+    best = (cost[h], h, Hs[h]) if h >= 0 else (np.inf, -1, None)
     if best[2] is None:
         out["status"] = DEGENERATE
         return out

@@ -11,7 +11,9 @@ first, ties to the lower h, then the lower solution; (5) lo_rounds times: consen
 (resect_reference.refine); (6) ba_resect's measures and status at the final pose.
 
 The samples index the usable observations in the order they are handed in; the device indexes them in its own
-camera-ordered list, so the two draw different triples from the same generator.  No test depends on which are drawn.
+camera-ordered list (ascending in the point within a camera), so the two draw different triples from the same generator
+unless the observations are handed in in that order.  The tests that compare hypothesis by hypothesis
+(tests/test_gpu_hypothesis_stage.py) do that and assert it on the handle's layout; no other test depends on which are drawn.
 """
 import numpy as np
 
@@ -144,32 +146,58 @@ def consensus(o, pose, thr, min_depth):
     return (depth > min_depth) & (np.sqrt((r * r).sum(axis=1)) <= thr)
 
 
+def hypothesis_costs(o, cam=0, n_hyp=256, seed=0, max_reproj_px=4.0, min_depth=0.0):
+    """Steps 2 - 4 of the header over the usable observations of o (n >= 4 of them), hypothesis by hypothesis -> (cost (n_hyp,):
+    the lowest MSAC cost over the hypothesis's poses, inf when it has none; slot (n_hyp,): which of p3p's poses that is, the
+    first of equal ones, -1 when void; poses: that (R, t), None when void).  The winner of step 4 among the first N
+    hypotheses is the first lowest of cost[:N]: `winner`."""
+    xy, ok = o.bearings()
+    return _costs_of_usable(o.keep(ok), xy[ok], cam, n_hyp, seed, max_reproj_px, min_depth)
+
+
+def _costs_of_usable(o, xy, cam, n_hyp, seed, max_reproj_px, min_depth):
+    """hypothesis_costs on observations that all have a bearing (xy)."""
+    n = len(o.uv)
+    y = unit_rays(xy, o.intr is not None)
+    cost, slot, poses = np.full(n_hyp, np.inf), np.full(n_hyp, -1, dtype=np.int64), [None] * n_hyp
+    for h in range(n_hyp):
+        idx = list(sample3(seed, cam, h, n))
+        for s, (R, t) in enumerate(p3p(y[idx], o.X[idx])):
+            P = o.X[idx] @ R.T + t
+            depth = P[:, 2] if o.intr is None else -P[:, 2]
+            if not (depth > min_depth).all():
+                continue
+            c = msac(o, R, t, max_reproj_px, min_depth)
+            if c < cost[h]:
+                cost[h], slot[h], poses[h] = c, s, (R, t)
+    return cost, slot, poses
+
+
+def winner(cost, n_hyp=None):
+    """The hypothesis step 4 takes among the first n_hyp: the lowest cost, ties to the lower h; -1 when every one is void."""
+    c = np.asarray(cost)[:n_hyp]
+    h = int(np.argmin(c))
+    return h if c[h] < np.inf else -1
+
+
 def ransac(o, current, cam=0, n_hyp=256, lo_rounds=2, seed=0, max_reproj_px=4.0, loss="linear", refine_iters=20, f_scale=1.0,
            min_inliers=6, max_rms_px=0.0, min_depth=0.0):
-    """One camera: dict(pose, status, n_inliers, rms_px, max_px, inlier (bool over o's observations))."""
+    """One camera: dict(pose, status, n_inliers, rms_px, max_px, inlier (bool over o's observations), best_hyp (the winning
+    hypothesis, -1 when there is none))."""
     current = np.asarray(current, dtype=np.float64)
     n_all = len(o.uv)
-    bad = dict(pose=current, n_inliers=0, rms_px=np.nan, max_px=np.nan, inlier=np.zeros(n_all, dtype=bool))
+    bad = dict(pose=current, n_inliers=0, rms_px=np.nan, max_px=np.nan, inlier=np.zeros(n_all, dtype=bool), best_hyp=-1)
     xy, ok = o.bearings()
     o, xy = o.keep(ok), xy[ok]
     n = len(o.uv)
     if n < 4:
         return dict(bad, status=FEW_POINTS)
-    y = unit_rays(xy, o.intr is not None)
     thr = max_reproj_px
-    best, best_cost = None, np.inf
-    for h in range(n_hyp):
-        idx = list(sample3(seed, cam, h, n))
-        for R, t in p3p(y[idx], o.X[idx]):
-            P = o.X[idx] @ R.T + t
-            depth = P[:, 2] if o.intr is None else -P[:, 2]
-            if not (depth > min_depth).all():
-                continue
-            cost = msac(o, R, t, thr, min_depth)
-            if cost < best_cost:
-                best, best_cost = (R, t), cost
-    if best is None:
+    cost, _, poses = _costs_of_usable(o, xy, cam, n_hyp, seed, thr, min_depth)
+    best_hyp = winner(cost)
+    if best_hyp < 0:
         return dict(bad, status=DEGENERATE)
+    best = poses[best_hyp]
     pose = np.concatenate([rr.log_map(best[0]), best[1]])
     degenerate = False
     for _ in range(lo_rounds):
@@ -184,7 +212,7 @@ def ransac(o, current, cam=0, n_hyp=256, lo_rounds=2, seed=0, max_reproj_px=4.0,
     inl = np.zeros(n_all, dtype=bool)
     inl[np.nonzero(ok)[0]] = consensus(o, pose, thr, min_depth)
     status = DEGENERATE if degenerate else m["status"]
-    return dict(pose=pose, status=status, n_inliers=m["n_inliers"], rms_px=m["rms_px"], max_px=m["max_px"], inlier=inl)
+    return dict(pose=pose, status=status, n_inliers=m["n_inliers"], rms_px=m["rms_px"], max_px=m["max_px"], inlier=inl, best_hyp=best_hyp)
 
 
 def resect_ransac(prob, cams=None, known=None, **opts):

@@ -8,7 +8,7 @@ import functools
 
 import numpy as np
 
-from tests.ransac_reference import GOLDEN, mix64
+from tests.ransac_reference import GOLDEN, mix64, winner
 
 OK, FEW_MATCHES, DEGENERATE, BEHIND, FEW_INLIERS, LOW_PARALLAX = range(6)
 W = np.array([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
@@ -268,6 +268,24 @@ def inlier_set(R, t, x1, x2, thr, max_depth):
 
 
 # ------------------------------------------------------------------------------------------------------------ the call
+def hypothesis_costs(K, p1, p2, pair=0, n_hyp=256, seed=0, max_epi_px=3.0):
+    """Steps 2 - 4 of the header, hypothesis by hypothesis -> (cost (n_hyp,): the lowest MSAC cost over the hypothesis's
+    solutions, inf when it has none; slot (n_hyp,): which of five_point's solutions that is, the first of equal ones, -1 when
+    void; E: that solution, None when void).  The winner of step 4 among the first N hypotheses is the first lowest of
+    cost[:N]: `winner`."""
+    K = np.asarray(K, dtype=np.float64).reshape(3, 3)
+    x1, x2 = normalise(K, p1), normalise(K, p2)
+    thr = max_epi_px / (0.5 * (K[0, 0] + K[1, 1]))
+    cost, slot, Es = np.full(n_hyp, np.inf), np.full(n_hyp, -1, dtype=np.int64), [None] * n_hyp
+    for h in range(n_hyp):
+        idx = list(sample5(seed, pair, h, len(p1)))
+        for s, E in enumerate(five_point(x1[idx], x2[idx])):
+            c = msac(E, x1, x2, thr)
+            if c < cost[h]:
+                cost[h], slot[h], Es[h] = c, s, E
+    return cost, slot, Es
+
+
 def relative_pose(K, p1, p2, pair=0, n_hyp=256, lo_rounds=2, seed=0, max_epi_px=3.0, refine_iters=20, min_inliers=8,
                   min_parallax_deg=0.0, max_depth=50.0):
     """One pair (its index in the call: `pair`), steps 0 - 7 of the header."""
@@ -282,13 +300,9 @@ def relative_pose(K, p1, p2, pair=0, n_hyp=256, lo_rounds=2, seed=0, max_epi_px=
     x1, x2 = normalise(K, p1), normalise(K, p2)
     fbar = 0.5 * (K[0, 0] + K[1, 1])
     thr = max_epi_px / fbar
-    best = (np.inf, -1, None)
-    for h in range(n_hyp):
-        idx = list(sample5(seed, pair, h, n))
-        for E in five_point(x1[idx], x2[idx]):
-            c = msac(E, x1, x2, thr)
-            if c < best[0]:
-                best = (c, h, E)
+    cost, _, Es = hypothesis_costs(K, p1, p2, pair, n_hyp, seed, max_epi_px)
+    h = winner(cost)
+    best = (cost[h], h, Es[h]) if h >= 0 else (np.inf, -1, None)
     if best[2] is None:
         out["status"] = DEGENERATE
         return out
