@@ -40,6 +40,7 @@
 #include "ba_tracks.hpp"
 #include "ba_similarity.hpp"
 #include "ba_resect.hpp"
+#include "ba_hypothesis.hpp"
 #include "ba_ransac.hpp"
 #include "ba_relpose.hpp"
 #include "ba_homography.hpp"
@@ -298,17 +299,17 @@ struct ba_handle {
   DBuf<int> rn_cnt;
   DBuf<unsigned char> rn_cons, rn_inl;
   RansacArgs rn_args = {};
-  // ba_relative_pose (ba_relpose.hpp): staging of the call -- both views' pixels, the pair offsets, the hypotheses' slots and
-  // masks, the score blocks' best candidates, consensus and inlier bytes per match, the per-pair results
-  DBuf<double> rp_pts, rp_E, rp_best, rp_out;
-  DBuf<long long> rp_off;
+  // ba_relative_pose and ba_homography (PairArgs of ba_hypothesis.hpp): staging of a call -- both views' pixels, the pair
+  // offsets, the score blocks' best models, the per-pair results, consensus and inlier bytes per match; the five-point call's
+  // own: the hypotheses' slots and masks
+  struct PairStage {
+    DBuf<double> pts, best, out;
+    DBuf<long long> off;
+    DBuf<unsigned char> cons, inl;
+  };
+  PairStage rp, hg;
+  DBuf<double> rp_E;
   DBuf<unsigned> rp_mask;
-  DBuf<unsigned char> rp_cons, rp_inl;
-  // ba_homography (ba_homography.hpp): staging of the call -- both views' pixels, the pair offsets, the score blocks' winners,
-  // the consensus and inlier bytes, the results
-  DBuf<double> hg_pts, hg_best, hg_out;
-  DBuf<long long> hg_off;
-  DBuf<unsigned char> hg_cons, hg_inl;
   // ba_match_descriptors (ba_match.hpp): staging of the call -- every set's descriptors, the pair table, the splits' (k1, k2),
   // best | second | dist1 | dist2 by row, the good bytes, the per-pair counts
   DBuf<unsigned long long> mt_desc;
@@ -3647,7 +3648,7 @@ extern "C" int ba_resect_ransac(ba_handle* h, const double* intr, const ba_ransa
                                 double* poses, uint8_t* status, int32_t* n_inliers, double* rms_px, double* max_px, uint8_t* obs_inlier) {
   if (!h || !opts) return fail(BA_ERR_INVALID, "null argument");
   if (!h->have_problem || !h->have_params) return fail(BA_ERR_STATE, "ba_resect_ransac: ba_set_problem / ba_set_params first");
-  if (opts->n_hyp < 1 || opts->n_hyp > RN_MAX_HYP) return fail(BA_ERR_INVALID, "ba_resect_ransac: n_hyp %d is outside 1 .. %d", opts->n_hyp, RN_MAX_HYP);
+  if (opts->n_hyp < 1 || opts->n_hyp > HY_MAX_HYP) return fail(BA_ERR_INVALID, "ba_resect_ransac: n_hyp %d is outside 1 .. %d", opts->n_hyp, HY_MAX_HYP);
   if (opts->lo_rounds < 0) return fail(BA_ERR_INVALID, "ba_resect_ransac: lo_rounds must not be negative");
   if (!(opts->max_reproj_px > 0)) return fail(BA_ERR_INVALID, "ba_resect_ransac: max_reproj_px must be positive");
   ba_resect_options common = {};
@@ -3673,6 +3674,64 @@ extern "C" int ba_resect_ransac(ba_handle* h, const double* intr, const ba_ransa
   return resect_end(h, h->rn, opts->write_cams, poses, status, n_inliers, rms_px, max_px);
 }
 
+// ------------------------------------------------------------------------------------------------- the two-view calls' plumbing
+// What ba_relative_pose and ba_homography refuse alike; `who` is the call the message names.
+static int pairs_check(const char* who, const double* K, int32_t n_pairs, const int64_t* pair_off, const double* pts1, const double* pts2,
+                       int32_t n_hyp, int32_t lo_rounds, int32_t refine_iters, int32_t min_inliers) {
+  if (n_pairs < 0 || n_pairs > 65535) return fail(BA_ERR_INVALID, "%s: n_pairs %d is outside 0 .. 65535", who, n_pairs);
+  if (n_hyp < 1 || n_hyp > HY_MAX_HYP) return fail(BA_ERR_INVALID, "%s: n_hyp %d is outside 1 .. %d", who, n_hyp, HY_MAX_HYP);
+  if (lo_rounds < 0) return fail(BA_ERR_INVALID, "%s: lo_rounds must not be negative", who);
+  if (refine_iters < 0) return fail(BA_ERR_INVALID, "%s: refine_iters must not be negative", who);
+  if (min_inliers < 0) return fail(BA_ERR_INVALID, "%s: min_inliers must not be negative", who);
+  if (!(K[0] > 0 && K[4] > 0 && std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) && std::isfinite(K[5])) || K[1] != 0 || K[3] != 0 ||
+      K[6] != 0 || K[7] != 0 || K[8] != 1)
+    return fail(BA_ERR_INVALID, "%s: K must be the pinhole matrix [fx 0 cx; 0 fy cy; 0 0 1] with fx, fy > 0", who);
+  if (n_pairs == 0) return BA_OK;
+  if (!pair_off) return fail(BA_ERR_INVALID, "%s: null pair_off", who);
+  if (pair_off[0] != 0) return fail(BA_ERR_INVALID, "%s: pair_off[0] must be 0", who);
+  for (int32_t p = 0; p < n_pairs; ++p) {
+    if (pair_off[p + 1] < pair_off[p]) return fail(BA_ERR_INVALID, "%s: pair_off decreases at pair %d", who, p);
+    if (pair_off[p + 1] - pair_off[p] > 0x7fffffffLL) return fail(BA_ERR_INVALID, "%s: pair_off: pair %d has too many matches", who, p);
+  }
+  if (pair_off[n_pairs] > 0 && (!pts1 || !pts2)) return fail(BA_ERR_INVALID, "%s: null point arrays", who);
+  return BA_OK;
+}
+// The staging of a call (n_pairs > 0) sized and filled, and the shared head of its arguments; max_px: the call's threshold in
+// pixels, best_per / out_per: its doubles per score block / per pair.  o: the call's options, which name these fields alike.
+template <class Opts>
+static int pairs_upload(ba_handle* h, ba_handle::PairStage& st, const double* K, int32_t n_pairs, const int64_t* pair_off, const double* pts1,
+                        const double* pts2, const Opts& o, double max_px, int n_blk, int best_per, int out_per, PairArgs& a) {
+  if (set_device(h)) return BA_ERR_HIP;
+  const size_t nm = (size_t)pair_off[n_pairs], np = (size_t)n_pairs, nm1 = std::max<size_t>(nm, 1);
+  HIPCHECK(st.pts.alloc(4 * nm1)); HIPCHECK(st.off.alloc(np + 1)); HIPCHECK(st.best.alloc((size_t)best_per * np * n_blk));
+  HIPCHECK(st.out.alloc((size_t)out_per * np)); HIPCHECK(st.cons.alloc(nm1)); HIPCHECK(st.inl.alloc(nm1));
+  a.fx = K[0]; a.fy = K[4]; a.cx = K[2]; a.cy = K[5];
+  a.fbar = 0.5 * (K[0] + K[4]); a.thr = max_px / a.fbar;
+  a.max_depth = o.max_depth;
+  a.n_hyp = o.n_hyp; a.lo_rounds = o.lo_rounds; a.iters = o.refine_iters; a.min_inliers = o.min_inliers;
+  a.n_blk = n_blk; a.seed = o.seed;
+  a.off = st.off.p; a.p1 = (const double2*)st.pts.p; a.p2 = (const double2*)(st.pts.p + 2 * nm1);
+  a.best = st.best.p; a.cons = st.cons.p; a.inl = st.inl.p; a.out = st.out.p;
+  static_assert(sizeof(long long) == sizeof(int64_t), "pair_off is uploaded as it is");
+  HIPCHECK(hipMemcpyAsync(st.off.p, pair_off, (np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  if (nm > 0) {
+    HIPCHECK(hipMemcpyAsync(st.pts.p, pts1, 2 * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(st.pts.p + 2 * nm1, pts2, 2 * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemsetAsync(st.inl.p, 0, nm, h->stream));
+  }
+  return BA_OK;
+}
+// The pairs' rows of out_per doubles into res (want: the call returns any of them) and match_inlier, and the stream drained
+static int pairs_download(ba_handle* h, ba_handle::PairStage& st, bool want, int out_per, int32_t n_pairs, const int64_t* pair_off,
+                          uint8_t* match_inlier, std::vector<double>& res) {
+  const size_t nm = (size_t)pair_off[n_pairs];
+  res.resize(want ? (size_t)out_per * n_pairs : 0);
+  if (want) HIPCHECK(hipMemcpyAsync(res.data(), st.out.p, res.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (match_inlier && nm > 0) HIPCHECK(hipMemcpyAsync(match_inlier, st.inl.p, nm, hipMemcpyDeviceToHost, h->stream));
+  BA_SYNC(h);
+  return BA_OK;
+}
+
 // ------------------------------------------------------------------------------------------------- two-view relative pose
 // ba_relative_pose (csrc/ba_relpose.hpp): five-point hypotheses, scores, decomposition and local optimisation.  Needs no problem.
 static_assert(RP_OK == BA_RELPOSE_OK && RP_FEW_MATCHES == BA_RELPOSE_FEW_MATCHES && RP_DEGENERATE == BA_RELPOSE_DEGENERATE &&
@@ -3693,54 +3752,23 @@ extern "C" int ba_relative_pose(ba_handle* h, const double K[9], int32_t n_pairs
                                 const ba_relpose_options* opts, double* R, double* t, uint8_t* status, int32_t* n_inliers, double* rms_px,
                                 double* parallax_deg, int32_t* best_hyp, uint8_t* match_inlier) {
   if (!h || !K || !opts) return fail(BA_ERR_INVALID, "null argument");
-  if (n_pairs < 0 || n_pairs > 65535) return fail(BA_ERR_INVALID, "ba_relative_pose: n_pairs %d is outside 0 .. 65535", n_pairs);
-  if (opts->n_hyp < 1 || opts->n_hyp > RN_MAX_HYP) return fail(BA_ERR_INVALID, "ba_relative_pose: n_hyp %d is outside 1 .. %d", opts->n_hyp, RN_MAX_HYP);
-  if (opts->lo_rounds < 0) return fail(BA_ERR_INVALID, "ba_relative_pose: lo_rounds must not be negative");
+  if (int rc = pairs_check("ba_relative_pose", K, n_pairs, pair_off, pts1, pts2, opts->n_hyp, opts->lo_rounds, opts->refine_iters, opts->min_inliers))
+    return rc;
   if (!(opts->max_epi_px > 0)) return fail(BA_ERR_INVALID, "ba_relative_pose: max_epi_px must be positive");
-  if (opts->refine_iters < 0) return fail(BA_ERR_INVALID, "ba_relative_pose: refine_iters must not be negative");
-  if (opts->min_inliers < 0) return fail(BA_ERR_INVALID, "ba_relative_pose: min_inliers must not be negative");
-  if (!(K[0] > 0 && K[4] > 0 && std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) && std::isfinite(K[5])) || K[1] != 0 || K[3] != 0 ||
-      K[6] != 0 || K[7] != 0 || K[8] != 1)
-    return fail(BA_ERR_INVALID, "ba_relative_pose: K must be the pinhole matrix [fx 0 cx; 0 fy cy; 0 0 1] with fx, fy > 0");
   if (n_pairs == 0) return BA_OK;
-  if (!pair_off) return fail(BA_ERR_INVALID, "ba_relative_pose: null pair_off");
-  if (pair_off[0] != 0) return fail(BA_ERR_INVALID, "ba_relative_pose: pair_off[0] must be 0");
-  for (int32_t p = 0; p < n_pairs; ++p) {
-    if (pair_off[p + 1] < pair_off[p]) return fail(BA_ERR_INVALID, "ba_relative_pose: pair_off decreases at pair %d", p);
-    if (pair_off[p + 1] - pair_off[p] > 0x7fffffffLL) return fail(BA_ERR_INVALID, "ba_relative_pose: pair_off: pair %d has too many matches", p);
-  }
-  const size_t nm = (size_t)pair_off[n_pairs], np = (size_t)n_pairs;
-  if (nm > 0 && (!pts1 || !pts2)) return fail(BA_ERR_INVALID, "ba_relative_pose: null point arrays");
-  if (set_device(h)) return BA_ERR_HIP;
+  const size_t np = (size_t)n_pairs;
   const int n_blk = (RP_SLOTS * opts->n_hyp + RP_THREADS - 1) / RP_THREADS;
-  const size_t nm1 = std::max<size_t>(nm, 1);
-  HIPCHECK(h->rp_pts.alloc(4 * nm1)); HIPCHECK(h->rp_off.alloc(np + 1)); HIPCHECK(h->rp_E.alloc(9 * (size_t)RP_SLOTS * np * opts->n_hyp));
-  HIPCHECK(h->rp_mask.alloc(np * opts->n_hyp)); HIPCHECK(h->rp_best.alloc(RP_BEST * np * n_blk)); HIPCHECK(h->rp_out.alloc(RP_OUT * np));
-  HIPCHECK(h->rp_cons.alloc(nm1)); HIPCHECK(h->rp_inl.alloc(nm1));
   RelposeArgs a = {};
-  a.fx = K[0]; a.fy = K[4]; a.cx = K[2]; a.cy = K[5];
-  a.fbar = 0.5 * (K[0] + K[4]); a.thr = opts->max_epi_px / a.fbar;
-  a.max_depth = opts->max_depth; a.min_parallax = opts->min_parallax_deg;
-  a.n_hyp = opts->n_hyp; a.lo_rounds = opts->lo_rounds; a.iters = opts->refine_iters; a.min_inliers = opts->min_inliers;
-  a.n_blk = n_blk; a.seed = opts->seed;
-  a.off = h->rp_off.p; a.p1 = (const double2*)h->rp_pts.p; a.p2 = (const double2*)(h->rp_pts.p + 2 * nm1);
-  a.E = h->rp_E.p; a.mask = h->rp_mask.p; a.best = h->rp_best.p; a.cons = h->rp_cons.p; a.inl = h->rp_inl.p; a.out = h->rp_out.p;
-  static_assert(sizeof(long long) == sizeof(int64_t), "pair_off is uploaded as it is");
-  HIPCHECK(hipMemcpyAsync(h->rp_off.p, pair_off, (np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-  if (nm > 0) {
-    HIPCHECK(hipMemcpyAsync(h->rp_pts.p, pts1, 2 * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemcpyAsync(h->rp_pts.p + 2 * nm1, pts2, 2 * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemsetAsync(h->rp_inl.p, 0, nm, h->stream));
-  }
+  if (int rc = pairs_upload(h, h->rp, K, n_pairs, pair_off, pts1, pts2, *opts, opts->max_epi_px, n_blk, RP_BEST, RP_OUT, a)) return rc;
+  HIPCHECK(h->rp_E.alloc(9 * (size_t)RP_SLOTS * np * opts->n_hyp)); HIPCHECK(h->rp_mask.alloc(np * opts->n_hyp));
+  a.min_parallax = opts->min_parallax_deg; a.E = h->rp_E.p; a.mask = h->rp_mask.p;
   const dim3 b(RP_THREADS);
   BA_LAUNCH(k_relpose_solve, dim3(n_pairs, (opts->n_hyp + RP_TEAMS - 1) / RP_TEAMS), b, 0, h->stream, a);
   BA_LAUNCH(k_relpose_score, dim3(n_pairs, n_blk), b, 0, h->stream, a);
   BA_LAUNCH(k_relpose_lo, dim3(n_pairs), b, 0, h->stream, a);
   const bool want = R || t || status || n_inliers || rms_px || parallax_deg || best_hyp;
-  std::vector<double> res(want ? RP_OUT * np : 0);
-  if (want) HIPCHECK(hipMemcpyAsync(res.data(), h->rp_out.p, RP_OUT * np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (match_inlier && nm > 0) HIPCHECK(hipMemcpyAsync(match_inlier, h->rp_inl.p, nm, hipMemcpyDeviceToHost, h->stream));
-  BA_SYNC(h);
+  std::vector<double> res;
+  if (int rc = pairs_download(h, h->rp, want, RP_OUT, n_pairs, pair_off, match_inlier, res)) return rc;
   if (want)
     for (size_t p = 0; p < np; ++p) {
       const double* r = res.data() + RP_OUT * p;
@@ -3778,53 +3806,23 @@ extern "C" int ba_homography(ba_handle* h, const double K[9], int32_t n_pairs, c
                              uint8_t* match_inlier, int32_t* n_pose, double* R, double* t, double* normal, double* t_over_d, int32_t* votes,
                              double* pose_cost) {
   if (!h || !K || !opts) return fail(BA_ERR_INVALID, "null argument");
-  if (n_pairs < 0 || n_pairs > 65535) return fail(BA_ERR_INVALID, "ba_homography: n_pairs %d is outside 0 .. 65535", n_pairs);
-  if (opts->n_hyp < 1 || opts->n_hyp > RN_MAX_HYP) return fail(BA_ERR_INVALID, "ba_homography: n_hyp %d is outside 1 .. %d", opts->n_hyp, RN_MAX_HYP);
-  if (opts->lo_rounds < 0) return fail(BA_ERR_INVALID, "ba_homography: lo_rounds must not be negative");
+  if (int rc = pairs_check("ba_homography", K, n_pairs, pair_off, pts1, pts2, opts->n_hyp, opts->lo_rounds, opts->refine_iters, opts->min_inliers))
+    return rc;
   if (!(opts->max_px > 0)) return fail(BA_ERR_INVALID, "ba_homography: max_px must be positive");
-  if (opts->refine_iters < 0) return fail(BA_ERR_INVALID, "ba_homography: refine_iters must not be negative");
-  if (opts->min_inliers < 0) return fail(BA_ERR_INVALID, "ba_homography: min_inliers must not be negative");
   if (!(opts->ambiguity_ratio >= 0 && opts->ambiguity_ratio <= 1)) return fail(BA_ERR_INVALID, "ba_homography: ambiguity_ratio must lie in [0, 1]");
   if (!(opts->min_translation >= 0)) return fail(BA_ERR_INVALID, "ba_homography: min_translation must not be negative");
-  if (!(K[0] > 0 && K[4] > 0 && std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) && std::isfinite(K[5])) || K[1] != 0 || K[3] != 0 ||
-      K[6] != 0 || K[7] != 0 || K[8] != 1)
-    return fail(BA_ERR_INVALID, "ba_homography: K must be the pinhole matrix [fx 0 cx; 0 fy cy; 0 0 1] with fx, fy > 0");
   if (n_pairs == 0) return BA_OK;
-  if (!pair_off) return fail(BA_ERR_INVALID, "ba_homography: null pair_off");
-  if (pair_off[0] != 0) return fail(BA_ERR_INVALID, "ba_homography: pair_off[0] must be 0");
-  for (int32_t p = 0; p < n_pairs; ++p) {
-    if (pair_off[p + 1] < pair_off[p]) return fail(BA_ERR_INVALID, "ba_homography: pair_off decreases at pair %d", p);
-    if (pair_off[p + 1] - pair_off[p] > 0x7fffffffLL) return fail(BA_ERR_INVALID, "ba_homography: pair_off: pair %d has too many matches", p);
-  }
-  const size_t nm = (size_t)pair_off[n_pairs], np = (size_t)n_pairs;
-  if (nm > 0 && (!pts1 || !pts2)) return fail(BA_ERR_INVALID, "ba_homography: null point arrays");
-  if (set_device(h)) return BA_ERR_HIP;
+  const size_t np = (size_t)n_pairs;
   const int n_blk = (opts->n_hyp + HG_THREADS - 1) / HG_THREADS;
-  const size_t nm1 = std::max<size_t>(nm, 1);
-  HIPCHECK(h->hg_pts.alloc(4 * nm1)); HIPCHECK(h->hg_off.alloc(np + 1)); HIPCHECK(h->hg_best.alloc(HG_BEST * np * n_blk));
-  HIPCHECK(h->hg_out.alloc(HG_OUT * np)); HIPCHECK(h->hg_cons.alloc(nm1)); HIPCHECK(h->hg_inl.alloc(nm1));
   HomogArgs a = {};
-  a.fx = K[0]; a.fy = K[4]; a.cx = K[2]; a.cy = K[5];
-  a.fbar = 0.5 * (K[0] + K[4]); a.thr = opts->max_px / a.fbar;
-  a.max_depth = opts->max_depth; a.ambiguity = opts->ambiguity_ratio; a.min_translation = opts->min_translation;
-  a.n_hyp = opts->n_hyp; a.lo_rounds = opts->lo_rounds; a.iters = opts->refine_iters; a.min_inliers = opts->min_inliers;
-  a.n_blk = n_blk; a.seed = opts->seed;
-  a.off = h->hg_off.p; a.p1 = (const double2*)h->hg_pts.p; a.p2 = (const double2*)(h->hg_pts.p + 2 * nm1);
-  a.best = h->hg_best.p; a.cons = h->hg_cons.p; a.inl = h->hg_inl.p; a.out = h->hg_out.p;
-  HIPCHECK(hipMemcpyAsync(h->hg_off.p, pair_off, (np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-  if (nm > 0) {
-    HIPCHECK(hipMemcpyAsync(h->hg_pts.p, pts1, 2 * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemcpyAsync(h->hg_pts.p + 2 * nm1, pts2, 2 * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemsetAsync(h->hg_inl.p, 0, nm, h->stream));
-  }
+  if (int rc = pairs_upload(h, h->hg, K, n_pairs, pair_off, pts1, pts2, *opts, opts->max_px, n_blk, HG_BEST, HG_OUT, a)) return rc;
+  a.ambiguity = opts->ambiguity_ratio; a.min_translation = opts->min_translation;
   const dim3 b(HG_THREADS);
   BA_LAUNCH(k_homog_score, dim3(n_pairs, n_blk), b, 0, h->stream, a);
   BA_LAUNCH(k_homog_lo, dim3(n_pairs), b, 0, h->stream, a);
   const bool want = H || status || n_inliers || rms_px || best_hyp || n_pose || R || t || normal || t_over_d || votes || pose_cost;
-  std::vector<double> res(want ? HG_OUT * np : 0);
-  if (want) HIPCHECK(hipMemcpyAsync(res.data(), h->hg_out.p, HG_OUT * np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (match_inlier && nm > 0) HIPCHECK(hipMemcpyAsync(match_inlier, h->hg_inl.p, nm, hipMemcpyDeviceToHost, h->stream));
-  BA_SYNC(h);
+  std::vector<double> res;
+  if (int rc = pairs_download(h, h->hg, want, HG_OUT, n_pairs, pair_off, match_inlier, res)) return rc;
   if (want)
     for (size_t p = 0; p < np; ++p) {
       const double* r = res.data() + HG_OUT * p;

@@ -5,12 +5,11 @@
 //
 // Two launches per call, for all pairs at once:
 //   k_homog_score  grid (pairs, ceil(n_hyp / 256)): lane = hypothesis.  Sample -> closed form (3 x 3 cofactors indexed by
-//                  constants: H~ and adj H~ in 18 registers) -> the pair's normalised matches stream through LDS in tiles of
-//                  HG_TILE (x1 | x2), every lane reads the same address; MSAC cost of the symmetric transfer error; the block's
-//                  lowest (cost, h) by two DPP min-reductions per wave and LDS, as in k_relpose_score.
+//                  constants: H~ and adj H~ in 18 registers) -> the pair's normalised matches stream through LDS
+//                  in tiles of HY_TILE (x1 | x2); MSAC cost of the symmetric transfer error; the block's lowest (cost, h) by hy_block_best.
 //   k_homog_lo     one workgroup per pair: the lowest (cost, h) over the score blocks, lo_rounds of {consensus bytes;
 //                  Marquardt-damped Gauss-Newton in the eight entries of the traceless D of H (I + D)}, the measures, the pixel
-//                  H, H~ = U diag V^T (jacobi_svd), the two poses with their votes and Sampson costs, the status.  The last
+//                  H, H~ = U diag V^T (hy_canon_svd), the two poses with their votes and Sampson costs, the status.  The last
 //                  accepted H~ and its 45 sums live in LDS.  Sums by rs_block_sums: fixed order, no atomics.
 #pragma once
 #include "ba_relpose.hpp"
@@ -18,50 +17,16 @@
 namespace ba {
 
 enum : int { HG_OK = 0, HG_FEW_MATCHES = 1, HG_DEGENERATE = 2, HG_FEW_INLIERS = 3, HG_ROTATION = 4, HG_AMBIGUOUS = 5 };
-constexpr int HG_THREADS = 256;
-constexpr int HG_TILE = 256;                   // matches per LDS tile of the scoring loop
+constexpr int HG_THREADS = HY_THREADS;
 constexpr int HG_BEST = 12;                    // doubles per (pair, score block): cost | h | H~[9] | one of padding (a block's record stays 16-byte aligned, as RP_BEST)
 constexpr int HG_OUT = 50;                     // doubles per pair: H[9] | status n_inliers rms best_hyp n_pose | R[18] | t[6] | n[6] | t/d[2] | votes[2] | cost[2]
 constexpr int HG_NSUM = 45;                    // a refinement pass: H (36) g (8) cost
 constexpr double HG_DET_TOL = 1e-12;
 static_assert(HG_THREADS == RS_THREADS, "rs_block_sums folds RS_WAVES waves");
 
-struct HomogArgs {
-  double fx, fy, cx, cy;   // K
-  double thr, fbar;        // max_px / fbar, fbar = (fx + fy) / 2
-  double max_depth, ambiguity, min_translation;
-  int n_hyp, lo_rounds, iters, min_inliers;
-  int n_blk;               // score blocks per pair
-  unsigned long long seed;
-  const long long* off;    // [pairs + 1]
-  const double2* p1;       // pixels, first / second view
-  const double2* p2;
-  double* best;            // HG_BEST doubles per (pair, score block)
-  unsigned char* cons;     // per match: in the consensus set of the round
-  unsigned char* inl;      // match_inlier (zeroed before the launch)
-  double* out;             // HG_OUT doubles per pair
+struct HomogArgs : PairArgs {   // thr = max_px / fbar; best: HG_BEST doubles per (pair, score block); out: HG_OUT per pair
+  double ambiguity, min_translation;
 };
-
-__device__ __forceinline__ double2 hg_norm(const HomogArgs& a, const double2 p) {
-  return make_double2((p.x - a.cx) / a.fx, (p.y - a.cy) / a.fy);
-}
-
-// step 2: four distinct indices below n (n >= 4), rp_sample's draws d = 0 .. 3
-__device__ __forceinline__ void hg_sample(const unsigned long long seed, const int pair, const int h, const int n, int (&idx)[4]) {
-  constexpr unsigned long long G = 0x9E3779B97F4A7C15ull;
-  const unsigned long long k = rn_mix(rn_mix(rn_mix(seed + G) + (unsigned long long)pair) + (unsigned long long)h);
-  int s[4];                                       // the earlier indices, ascending
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    int i = (int)__umul64hi(rn_mix(k + (unsigned long long)(d + 1) * G), (unsigned long long)(n - d));
-#pragma unroll
-    for (int j = 0; j < d; ++j) if (i >= s[j]) ++i;
-    idx[d] = i;
-    s[d] = i;
-#pragma unroll
-    for (int j = d; j > 0; --j) if (s[j - 1] > s[j]) { const int t = s[j - 1]; s[j - 1] = s[j]; s[j] = t; }
-  }
-}
 
 // ---------------------------------------------------------------------------------------------- 3 x 3, row-major, in registers
 __device__ __forceinline__ void hg_adj(const double (&A)[9], double (&C)[9]) {
@@ -95,11 +60,11 @@ __device__ __forceinline__ void hg_identity(double (&H)[9]) {
 #pragma unroll
   for (int q = 0; q < 9; ++q) H[q] = (q % 4 == 0) ? 1.0 : 0.0;
 }
-// a triple with |d12 x d13| <= RN_AREA_TOL max |d_ij|^2 (collinear or coincident)
+// a triple with |d12 x d13| <= HY_AREA_TOL max |d_ij|^2 (collinear or coincident)
 __device__ __forceinline__ bool hg_flat(const double2 p, const double2 q, const double2 r) {
   const double ax = q.x - p.x, ay = q.y - p.y, bx = r.x - p.x, by = r.y - p.y, cx = r.x - q.x, cy = r.y - q.y;
   const double ext = fmax(fmax(ax * ax + ay * ay, bx * bx + by * by), cx * cx + cy * cy);
-  return !(fabs(ax * by - ay * bx) > RN_AREA_TOL * ext) || !sim_finite(ext);
+  return !(fabs(ax * by - ay * bx) > HY_AREA_TOL * ext) || !sim_finite(ext);
 }
 __device__ __forceinline__ bool hg_flat4(const double2 (&s)[4]) {
   return hg_flat(s[0], s[1], s[2]) || hg_flat(s[0], s[1], s[3]) || hg_flat(s[0], s[2], s[3]) || hg_flat(s[1], s[2], s[3]);
@@ -148,14 +113,14 @@ __device__ __forceinline__ bool hg_inlier(const double (&H)[9], const double (&A
 
 // ------------------------------------------------------------------------------------------------ hypotheses and scores
 __global__ void __launch_bounds__(HG_THREADS) k_homog_score(const HomogArgs a) {
-  __shared__ double tile[HG_TILE * 4];
-  __shared__ double red[2 * RS_WAVES];
-  const int pair = blockIdx.x, blk = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  __shared__ double tile[HY_TILE * 4];
+  __shared__ double red[2 * HY_WAVES];
+  const int pair = blockIdx.x, blk = blockIdx.y, tid = threadIdx.x;
   const long long beg = a.off[pair];
   const int n = (int)(a.off[pair + 1] - beg);
   double* out = a.best + HG_BEST * ((size_t)pair * a.n_blk + blk);
   if (n < 5) {                                    // (workgroup-uniform) FEW_MATCHES
-    if (tid == 0) { out[0] = RN_INF; out[1] = 0.0; }
+    hy_void_block(out);
     return;
   }
   const int h = blk * HG_THREADS + tid;
@@ -163,22 +128,22 @@ __global__ void __launch_bounds__(HG_THREADS) k_homog_score(const HomogArgs a) {
   double H[9], A[9];
   {
     int idx[4];
-    hg_sample(a.seed, pair, valid ? h : 0, n, idx);   // (indices below n for every lane)
+    hy_sample(a.seed, pair, valid ? h : 0, n, idx);   // (indices below n for every lane)
     double2 s1[4], s2[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { s1[k] = hg_norm(a, a.p1[beg + idx[k]]); s2[k] = hg_norm(a, a.p2[beg + idx[k]]); }
+    for (int k = 0; k < 4; ++k) { s1[k] = pv_norm(a, a.p1[beg + idx[k]]); s2[k] = pv_norm(a, a.p2[beg + idx[k]]); }
     valid = hg_solve(s1, s2, H) && valid;
   }
   if (!valid) hg_identity(H);                     // a void hypothesis runs along on finite numbers
   hg_adj(H, A);
   const double thr2 = a.thr * a.thr;
   double cost = 0.0;
-  for (int i0 = 0; i0 < n; i0 += HG_TILE) {
-    const int m = min(HG_TILE, n - i0);
+  for (int i0 = 0; i0 < n; i0 += HY_TILE) {
+    const int m = min(HY_TILE, n - i0);
     __syncthreads();                              // (the readers of the previous tile are done)
     if (tid < m) {
       double2* d = (double2*)(tile + 4 * tid);
-      d[0] = hg_norm(a, a.p1[beg + i0 + tid]); d[1] = hg_norm(a, a.p2[beg + i0 + tid]);
+      d[0] = pv_norm(a, a.p1[beg + i0 + tid]); d[1] = pv_norm(a, a.p2[beg + i0 + tid]);
     }
     __syncthreads();
     for (int i = 0; i < m; ++i) {                 // every lane reads the same address: an LDS broadcast
@@ -189,22 +154,13 @@ __global__ void __launch_bounds__(HG_THREADS) k_homog_score(const HomogArgs a) {
       cost += (pf ? fmin(f, thr2) : thr2) + (pb ? fmin(b, thr2) : thr2);
     }
   }
-  const double bc = valid ? cost : RN_INF, bk = valid ? (double)h : RN_INF;
-  const double wc = wave_min_dpp(bc);
-  const double wk = wave_min_dpp(bc == wc ? bk : RN_INF);
-  if (lane == 0) { red[2 * wv] = wc; red[2 * wv + 1] = wk; }
-  __syncthreads();
-  double gc = red[0], gk = red[1];
-#pragma unroll
-  for (int w = 1; w < RS_WAVES; ++w) {
-    const double xc = red[2 * w], xk = red[2 * w + 1];
-    if (xc < gc || (xc == gc && xk < gk)) { gc = xc; gk = xk; }
-  }
-  if (!(gc < RN_INF)) {
-    if (tid == 0) { out[0] = RN_INF; out[1] = 0.0; }
+  double gc, gk;
+  const bool mine = hy_block_best(valid ? cost : HY_INF, valid ? (double)h : HY_INF, red, gc, gk);
+  if (!(gc < HY_INF)) {
+    hy_void_block(out);
     return;
   }
-  if (valid && bc == gc && bk == gk) {            // one lane: keys are distinct
+  if (mine) {
     out[0] = gc; out[1] = gk;
 #pragma unroll
     for (int q = 0; q < 9; ++q) out[2 + q] = H[q];
@@ -264,9 +220,9 @@ __device__ __forceinline__ void hg_pass(const HomogArgs& a, const double (&H)[9]
   for (int q = 0; q < HG_NSUM; ++q) acc[q] = 0.0;
   for (int j = (int)threadIdx.x; j < n; j += HG_THREADS) {
     if (!a.cons[beg + j]) continue;
-    const double2 x1 = hg_norm(a, a.p1[beg + j]), x2 = hg_norm(a, a.p2[beg + j]);
+    const double2 x1 = pv_norm(a, a.p1[beg + j]), x2 = pv_norm(a, a.p2[beg + j]);
     const double yw = H[6] * x1.x + H[7] * x1.y + H[8], zw = A[6] * x2.x + A[7] * x2.y + A[8];
-    if (!(yw > 0.0 && zw > 0.0)) { acc[44] = RN_INF; continue; }   // (RN_INF + anything finite stays above every accepted cost)
+    if (!(yw > 0.0 && zw > 0.0)) { acc[44] = HY_INF; continue; }   // (HY_INF + anything finite stays above every accepted cost)
     const double iy = 1.0 / yw, iz = 1.0 / zw;
     const double px = (H[0] * x1.x + H[1] * x1.y + H[2]) * iy, py = (H[3] * x1.x + H[4] * x1.y + H[5]) * iy;
     const double qx = (A[0] * x2.x + A[1] * x2.y + A[2]) * iz, qy = (A[3] * x2.x + A[4] * x2.y + A[5]) * iz;
@@ -324,13 +280,9 @@ __global__ void __launch_bounds__(HG_THREADS) k_homog_lo(const HomogArgs a) {
   if (n < 5) { hg_void(o, HG_FEW_MATCHES); return; }   // (workgroup-uniform, like every branch below)
   // the lowest (cost, h) over the score blocks, in block order: the same in every lane
   const double* b = a.best + HG_BEST * (size_t)pair * a.n_blk;
-  int win = 0;
-  double gc = b[0], gk = b[1];
-  for (int k = 1; k < a.n_blk; ++k) {
-    const double xc = b[HG_BEST * k], xk = b[HG_BEST * k + 1];
-    if (xc < gc || (xc == gc && xk < gk)) { gc = xc; gk = xk; win = k; }
-  }
-  if (!(gc < RN_INF)) { hg_void(o, HG_DEGENERATE); return; }   // every hypothesis void
+  double gc, gk;
+  const int win = hy_winner<HG_BEST>(b, a.n_blk, gc, gk);
+  if (!(gc < HY_INF)) { hg_void(o, HG_DEGENERATE); return; }   // every hypothesis void
   const int best = (int)gk;
   double H[9], A[9];
 #pragma unroll
@@ -343,7 +295,7 @@ __global__ void __launch_bounds__(HG_THREADS) k_homog_lo(const HomogArgs a) {
     double cn[1] = {0.0};
     for (int j = tid; j < n; j += HG_THREADS) {   // every lane writes the bytes it reads back in the passes (same stride)
       double f, bb;
-      const unsigned char in = hg_inlier(H, A, hg_norm(a, a.p1[beg + j]), hg_norm(a, a.p2[beg + j]), thr2, f, bb) ? 1 : 0;
+      const unsigned char in = hg_inlier(H, A, pv_norm(a, a.p1[beg + j]), pv_norm(a, a.p2[beg + j]), thr2, f, bb) ? 1 : 0;
       a.cons[beg + j] = in;
       cn[0] += (double)in;
     }
@@ -396,7 +348,7 @@ __global__ void __launch_bounds__(HG_THREADS) k_homog_lo(const HomogArgs a) {
   double m2[2] = {0.0, 0.0};                      // inliers | sum (f + b)
   for (int j = tid; j < n; j += HG_THREADS) {
     double f, bb;
-    if (!hg_inlier(H, A, hg_norm(a, a.p1[beg + j]), hg_norm(a, a.p2[beg + j]), thr2, f, bb)) continue;
+    if (!hg_inlier(H, A, pv_norm(a, a.p1[beg + j]), pv_norm(a, a.p2[beg + j]), thr2, f, bb)) continue;
     m2[0] += 1.0; m2[1] += f + bb;
     a.inl[beg + j] = 1;                           // (read back below by the lane that wrote it: same stride)
   }
@@ -404,24 +356,9 @@ __global__ void __launch_bounds__(HG_THREADS) k_homog_lo(const HomogArgs a) {
   const double rms = m2[0] > 0.0 ? a.fbar * sqrt(0.5 * m2[1] / m2[0]) : nan;
   if (status == HG_OK && m2[0] < (double)a.min_inliers) status = HG_FEW_INLIERS;
   // ---- H~ = U diag(d) V^T; the third columns are the cross products of the first two, so det U = det V = +1 and d3 > 0 (det H~ > 0)
-  double U[3][3], V[3][3], d1, d2, d3;
-  {
-    double n2[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) U[i][j] = H[3 * i + j];
-    jacobi_svd<3, 24>(U, V);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) n2[k] = U[0][k] * U[0][k] + U[1][k] * U[1][k] + U[2][k] * U[2][k];
-    sim_order<0, 1>(U, V, n2); sim_order<1, 2>(U, V, n2); sim_order<0, 1>(U, V, n2);
-    d1 = sqrt(n2[0]); d2 = sqrt(n2[1]); d3 = sqrt(n2[2]);
-    const double i0 = 1.0 / d1, i1 = 1.0 / d2;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { U[k][0] *= i0; U[k][1] *= i1; }
-    U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1]; U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1]; U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-    V[0][2] = V[1][0] * V[2][1] - V[2][0] * V[1][1]; V[1][2] = V[2][0] * V[0][1] - V[0][0] * V[2][1]; V[2][2] = V[0][0] * V[1][1] - V[1][0] * V[0][1];
-  }
+  double U[3][3], V[3][3], d[3];
+  hy_canon_svd(H, U, V, d);
+  const double d1 = d[0], d2 = d[1], d3 = d[2];
   const double ratio = (d1 - d3) / d2;
   RpPose P[2];
   double nv[2][3], vote[2] = {0.0, 0.0}, pcost[2] = {nan, nan}, tod[2] = {0.0, 0.0};
@@ -463,7 +400,7 @@ __global__ void __launch_bounds__(HG_THREADS) k_homog_lo(const HomogArgs a) {
     double side[4] = {0.0, 0.0, 0.0, 0.0};         // pose 0: n . x1~ > 0 | < 0, pose 1 alike
     for (int j = tid; j < n; j += HG_THREADS) {
       if (!a.inl[beg + j]) continue;
-      const double2 x1 = hg_norm(a, a.p1[beg + j]);
+      const double2 x1 = pv_norm(a, a.p1[beg + j]);
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         const double s = nv[k][0] * x1.x + nv[k][1] * x1.y + nv[k][2];
@@ -484,7 +421,7 @@ __global__ void __launch_bounds__(HG_THREADS) k_homog_lo(const HomogArgs a) {
     rp_essential(P[1], E1);
     double vc[4] = {0.0, 0.0, 0.0, 0.0};           // votes 0 | votes 1 | cost 0 | cost 1
     for (int j = tid; j < n; j += HG_THREADS) {
-      const double2 x1 = hg_norm(a, a.p1[beg + j]), x2 = hg_norm(a, a.p2[beg + j]);
+      const double2 x1 = pv_norm(a, a.p1[beg + j]), x2 = pv_norm(a, a.p2[beg + j]);
       double r2, ra[3];
       vc[2] += rp_sampson2(E0, x1.x, x1.y, x2.x, x2.y, r2) ? fmin(r2, thr2) : thr2;
       vc[3] += rp_sampson2(E1, x1.x, x1.y, x2.x, x2.y, r2) ? fmin(r2, thr2) : thr2;

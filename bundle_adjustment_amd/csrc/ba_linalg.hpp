@@ -8,6 +8,12 @@ namespace ba {
 
 __host__ __device__ __forceinline__ bool sim_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN
 
+// cofactors of a packed symmetric 3 x 3: 00 01 02 11 12 22
+__device__ __forceinline__ void sym3_cof(const double (&A)[6], double (&C)[6]) {
+  C[0] = A[3] * A[5] - A[4] * A[4]; C[1] = A[2] * A[4] - A[1] * A[5]; C[2] = A[1] * A[4] - A[2] * A[3];
+  C[3] = A[0] * A[5] - A[2] * A[2]; C[4] = A[1] * A[2] - A[0] * A[4]; C[5] = A[0] * A[3] - A[1] * A[1];
+}
+
 // Cyclic Jacobi on a symmetric N x N (full storage), at most SWEEPS sweeps: A <- V^T A V diagonal, columns of V the
 // eigenvectors.  A rotation is skipped once |a_pq| <= 1e-17 sqrt(|a_pp a_qq|) (the relative criterion: the small eigenvalue
 // keeps its digits).

@@ -10,15 +10,13 @@
 //                       R | t held in registers (slot = 2 * sign + root, fixed, so no register is indexed dynamically); then
 //                       the camera's records stream through LDS in tiles of RN_TILE and every lane reads the same address (a
 //                       broadcast) and adds to its own four MSAC costs.  No cross-lane traffic until the arg-min of
-//                       (cost, 4 h + slot): two DPP min-reductions per wave, the four waves through LDS in wave order.
+//                       (cost, 4 h + slot) (ba_hypothesis.hpp).
 //   k_ransac_lo<CM>     one workgroup per camera: the lowest (cost, 4 h + slot) of the score blocks, then lo_rounds times
 //                       {consensus bytes at the frozen pose; ba_resect's refinement (rs_refine<CM, true>) on them}, then
 //                       ba_resect's measures and status (rs_finish), and obs_inlier through c_orig in the caller's order.
 //
-// Generator (step 2): mix(z) = the splitmix64 finaliser (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27,
-// z *= 0x94D049BB133111EB, z ^= z >> 31); draw(d) = mix(mix(mix(mix(seed + G) + camera) + h) + (d + 1) G), G = 0x9E3779B97F4A7C15,
-// all modulo 2^64; index_d = high 64 bits of draw(d) * (n - d); i1 is raised by one when >= i0, i2 by one when >= min(i0, i1)
-// and again when >= max(i0, i1): three distinct indices into the camera's usable observations in camera order, no retries.
+// Sample (step 2): hy_sample<3> of (seed, camera, h, n) -- three distinct indices into the camera's usable observations in
+// camera order.
 //
 // P3P (step 3), Lambda Twist (Persson & Nordberg, ECCV 2018): with unit rays y_i and depths L_i the three cosine-law equations
 // L_i^2 + L_j^2 + b_ij L_i L_j = a_ij are L^T M_ij L = a_ij; D1 = a23 M12 - a12 M23 and D2 = a23 M13 - a13 M23 are homogeneous,
@@ -27,18 +25,16 @@
 // Newton steps on the three equations; R = [Y1 - Y2, Y1 - Y3, x] [X1 - X2, X1 - X3, x]^-1, t = Y1 - R X1, Y_i = L_i y_i.  No
 // quartic: the cubic always has a real root and the eigenvalue problem is symmetric.
 #pragma once
+#include "ba_hypothesis.hpp"
 #include "ba_resect.hpp"
 
 namespace ba {
 
-constexpr int RN_THREADS = 256;
+constexpr int RN_THREADS = HY_THREADS;
 constexpr int RN_TILE = 256;          // records per LDS tile of the scoring loop
 constexpr int RN_REC = 8;             // doubles per usable observation: X0 X1 | X2 u | v j | bx by (j: its place in the camera-ordered list)
 constexpr int RN_LDS = 6;             // doubles per record in LDS: X0 X1 | X2 u | v -
 constexpr int RN_BEST = 16;           // doubles per (camera, score block): cost | 4 h + slot | R[9] | t[3] | - -
-constexpr int RN_MAX_HYP = 4096;
-constexpr double RN_AREA_TOL = 1e-6;  // |d12 x d13| <= RN_AREA_TOL max |d_ij|^2: a void triple
-constexpr double RN_INF = 1.7976931348623157e308;
 
 struct RansacArgs {
   ResectArgs r;            // as ba_resect: t.max_px is the threshold (> 0), t.loss / t.iters / t.fscale the refinement's, r.out the results
@@ -52,28 +48,7 @@ struct RansacArgs {
   unsigned char* inl;      // obs_inlier, the caller's order (zeroed before the launch)
 };
 
-__device__ __forceinline__ unsigned long long rn_mix(unsigned long long z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ void rn_sample(const unsigned long long seed, const int cam, const int h, const int n, int& i0, int& i1, int& i2) {
-  constexpr unsigned long long G = 0x9E3779B97F4A7C15ull;
-  const unsigned long long k = rn_mix(rn_mix(rn_mix(seed + G) + (unsigned long long)cam) + (unsigned long long)h);
-  i0 = (int)__umul64hi(rn_mix(k + G), (unsigned long long)n);
-  i1 = (int)__umul64hi(rn_mix(k + 2ull * G), (unsigned long long)(n - 1));
-  i2 = (int)__umul64hi(rn_mix(k + 3ull * G), (unsigned long long)(n - 2));
-  if (i1 >= i0) ++i1;
-  const int lo = min(i0, i1), hi = max(i0, i1);
-  if (i2 >= lo) ++i2;
-  if (i2 >= hi) ++i2;
-}
-
 // packed symmetric 3 x 3: 00 01 02 11 12 22
-__device__ __forceinline__ void rn_cof(const double (&A)[6], double (&C)[6]) {
-  C[0] = A[3] * A[5] - A[4] * A[4]; C[1] = A[2] * A[4] - A[1] * A[5]; C[2] = A[1] * A[4] - A[2] * A[3];
-  C[3] = A[0] * A[5] - A[2] * A[2]; C[4] = A[1] * A[2] - A[0] * A[4]; C[5] = A[0] * A[3] - A[1] * A[1];
-}
 __device__ __forceinline__ double rn_dot6(const double (&A)[6], const double (&B)[6]) {
   return A[0] * B[0] + A[3] * B[3] + A[5] * B[5] + 2.0 * (A[1] * B[1] + A[2] * B[2] + A[4] * B[4]);
 }
@@ -201,7 +176,7 @@ __device__ inline int rn_p3p(const double* __restrict__ r0, const double* __rest
   const double nx[3] = {d12[1] * d13[2] - d12[2] * d13[1], d12[2] * d13[0] - d12[0] * d13[2], d12[0] * d13[1] - d12[1] * d13[0]};
   const double n2 = nx[0] * nx[0] + nx[1] * nx[1] + nx[2] * nx[2];
   const double ext = fmax(T.a12, fmax(T.a13, T.a23));
-  if (!(sqrt(n2) > RN_AREA_TOL * ext) || !sim_finite(ext)) return 0;
+  if (!(sqrt(n2) > HY_AREA_TOL * ext) || !sim_finite(ext)) return 0;
   // [d12 d13 n]^-1: rows (d13 x n, n x d12, n) / |n|^2
   {
     const double in2 = 1.0 / n2;
@@ -215,7 +190,7 @@ __device__ inline int rn_p3p(const double* __restrict__ r0, const double* __rest
   const double D1[6] = {T.a23, 0.5 * T.a23 * T.b12, 0.0, T.a23 - T.a12, -0.5 * T.a12 * T.b23, -T.a12};
   const double D2[6] = {T.a23, 0.0, 0.5 * T.a23 * T.b13, -T.a13, -0.5 * T.a13 * T.b23, T.a23 - T.a13};
   double C1[6], C2[6];
-  rn_cof(D1, C1); rn_cof(D2, C2);
+  sym3_cof(D1, C1); sym3_cof(D2, C2);
   const double c0 = D1[0] * C1[0] + D1[1] * C1[1] + D1[2] * C1[2], c3 = D2[0] * C2[0] + D2[1] * C2[1] + D2[2] * C2[2];
   const double c1 = rn_dot6(C1, D2), c2 = rn_dot6(D1, C2);
   if (!(fabs(c3) > 0.0)) return 0;
@@ -317,12 +292,12 @@ __global__ void __launch_bounds__(RN_THREADS) k_ransac_prep(const RansacArgs a) 
 template <class CM>
 __global__ void __launch_bounds__(RN_THREADS) k_ransac_score(const RansacArgs a) {
   __shared__ double tile[RN_TILE * RN_LDS];
-  __shared__ double red[2 * RS_WAVES];
-  const int c = blockIdx.x, blk = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  __shared__ double red[2 * HY_WAVES];
+  const int c = blockIdx.x, blk = blockIdx.y, tid = threadIdx.x;
   const int n = a.cnt[c];
   double* out = a.best + RN_BEST * ((size_t)c * a.n_blk + blk);
   if (n < 4) {                                    // (workgroup-uniform) FEW_POINTS, or not selected: k_ransac_lo reads no record
-    if (tid == 0) { out[0] = RN_INF; out[1] = 0.0; }
+    hy_void_block(out);
     return;
   }
   const int beg = a.r.offk[c * (NPART + 1)];
@@ -340,9 +315,9 @@ __global__ void __launch_bounds__(RN_THREADS) k_ransac_score(const RansacArgs a)
   }
   int mask = 0;
   if (h < a.n_hyp) {
-    int i0, i1, i2;
-    rn_sample(a.seed, c, h, n, i0, i1, i2);
-    mask = rn_p3p<CM>(rec + RN_REC * (size_t)i0, rec + RN_REC * (size_t)i1, rec + RN_REC * (size_t)i2, a.r.t.min_depth, R, t);
+    int idx[3];
+    hy_sample(a.seed, c, h, n, idx);
+    mask = rn_p3p<CM>(rec + RN_REC * (size_t)idx[0], rec + RN_REC * (size_t)idx[1], rec + RN_REC * (size_t)idx[2], a.r.t.min_depth, R, t);
 #pragma unroll
     for (int s = 0; s < 4; ++s)
       if (!(mask >> s & 1)) {
@@ -377,25 +352,16 @@ __global__ void __launch_bounds__(RN_THREADS) k_ransac_score(const RansacArgs a)
     }
   }
   // the lane's best slot, then the block's best (cost, 4 h + slot)
-  double bc = RN_INF, bk = RN_INF;
+  double bc = HY_INF, bk = HY_INF, gc, gk;
 #pragma unroll
   for (int k = 0; k < 4; ++k)
     if ((mask >> k & 1) && cost[k] < bc) { bc = cost[k]; bk = (double)(4 * h + k); }
-  const double wc = wave_min_dpp(bc);
-  const double wk = wave_min_dpp(bc == wc ? bk : RN_INF);
-  if (lane == 0) { red[2 * wv] = wc; red[2 * wv + 1] = wk; }
-  __syncthreads();
-  double gc = red[0], gk = red[1];
-#pragma unroll
-  for (int w = 1; w < RS_WAVES; ++w) {
-    const double xc = red[2 * w], xk = red[2 * w + 1];
-    if (xc < gc || (xc == gc && xk < gk)) { gc = xc; gk = xk; }
-  }
-  if (!(gc < RN_INF)) {
-    if (tid == 0) { out[0] = RN_INF; out[1] = 0.0; }
+  const bool mine = hy_block_best(bc, bk, red, gc, gk);
+  if (!(gc < HY_INF)) {
+    hy_void_block(out);
     return;
   }
-  if (bc == gc && bk == gk) {                     // one lane: keys are distinct
+  if (mine) {
     const int k = (int)gk & 3;
     double Rw[9], tw[3];
 #pragma unroll
@@ -428,13 +394,9 @@ __global__ void __launch_bounds__(RS_THREADS) k_ransac_lo(const RansacArgs a) {
   else {
     // the lowest (cost, 4 h + slot) over the score blocks, in block order: the same in every lane
     const double* b = a.best + RN_BEST * (size_t)c * a.n_blk;
-    int win = 0;
-    double gc = b[0], gk = b[1];
-    for (int k = 1; k < a.n_blk; ++k) {
-      const double xc = b[RN_BEST * k], xk = b[RN_BEST * k + 1];
-      if (xc < gc || (xc == gc && xk < gk)) { gc = xc; gk = xk; win = k; }
-    }
-    if (!(gc < RN_INF)) status = RS_DEGENERATE;   // every hypothesis void
+    double gc, gk;
+    const int win = hy_winner<RN_BEST>(b, a.n_blk, gc, gk);
+    if (!(gc < HY_INF)) status = RS_DEGENERATE;   // every hypothesis void
     else {
       double R[9];
 #pragma unroll

@@ -12,9 +12,9 @@
 //                    real roots (lane = interval between two roots of the next derivative, bisection) -> lane = root: back
 //                    substitution, two Gauss-Newton steps, E.  Ten slots of 9 doubles and a validity mask per hypothesis.
 //   k_relpose_score  grid (pairs, ceil(10 n_hyp / 256)): lane = candidate 10 h + slot, E in nine registers; the pair's normalised
-//                    matches stream through LDS in tiles of RP_TILE (x1 | x2), every lane reads the same address; MSAC cost of
-//                    the squared Sampson distance; the block's lowest (cost, key) by two DPP min-reductions per wave and LDS.
-//   k_relpose_lo     one workgroup per pair: the lowest (cost, key) over the score blocks, E = U diag V^T (jacobi_svd), the
+//                    matches stream through LDS in tiles of HY_TILE (x1 | x2); MSAC cost of the squared Sampson distance; the block's
+//                    lowest (cost, key) by hy_block_best.
+//   k_relpose_lo     one workgroup per pair: the lowest (cost, key) over the score blocks, E = U diag V^T (hy_canon_svd), the
 //                    four (R, t) and their votes, lo_rounds of {consensus bytes; Marquardt-damped Gauss-Newton in five local
 //                    parameters}, the measures, the status, match_inlier.  Sums by rs_block_sums: fixed order, no atomics.
 //
@@ -27,16 +27,16 @@
 // Polish (step 3.7) runs on the ten ELIMINATED rows (monomial_i + sum_j C_ij trailing_j = 0, i = 0 .. 9): the same variety as the
 // ten raw constraints, 100 coefficients per hypothesis in LDS instead of 200.
 #pragma once
-#include "ba_ransac.hpp"
+#include "ba_hypothesis.hpp"
+#include "ba_resect.hpp"
 
 namespace ba {
 
 enum : int { RP_OK = 0, RP_FEW_MATCHES = 1, RP_DEGENERATE = 2, RP_BEHIND = 3, RP_FEW_INLIERS = 4, RP_LOW_PARALLAX = 5 };
-constexpr int RP_THREADS = 256;
+constexpr int RP_THREADS = HY_THREADS;
 constexpr int RP_TEAM = 16;                    // lanes per hypothesis in k_relpose_solve
 constexpr int RP_TEAMS = RP_THREADS / RP_TEAM; // hypotheses per workgroup
 constexpr int RP_SLOTS = 10;                   // solutions per hypothesis, numbered by ascending z
-constexpr int RP_TILE = 256;                   // matches per LDS tile of the scoring loop
 constexpr int RP_BEST = 12;                    // doubles per (pair, score block): cost | key | E[9] | -
 constexpr int RP_OUT = 18;                     // doubles per pair: R[9] | t[3] | status | n_inliers | rms | parallax | best_hyp | -
 constexpr int RP_NSUM = 21;                    // a refinement pass: H (15) g (5) cost
@@ -44,44 +44,11 @@ constexpr int RP_BISECT = 64;
 constexpr double RP_PIVOT_TOL = 1e-12;
 constexpr double RP_RAY_TOL = 1e-24;
 
-struct RelposeArgs {
-  double fx, fy, cx, cy;   // K
-  double thr, fbar;        // max_epi_px / fbar, fbar = (fx + fy) / 2
-  double max_depth, min_parallax;
-  int n_hyp, lo_rounds, iters, min_inliers;
-  int n_blk;               // score blocks per pair
-  unsigned long long seed;
-  const long long* off;    // [pairs + 1]
-  const double2* p1;       // pixels, first / second view
-  const double2* p2;
+struct RelposeArgs : PairArgs {   // thr = max_epi_px / fbar; best: RP_BEST doubles per (pair, score block); out: RP_OUT per pair
+  double min_parallax;
   double* E;               // [pairs][n_hyp][RP_SLOTS][9]
   unsigned* mask;          // [pairs][n_hyp]: bit s = slot s holds an E
-  double* best;            // RP_BEST doubles per (pair, score block)
-  unsigned char* cons;     // per match: in the consensus set of the round
-  unsigned char* inl;      // match_inlier (zeroed before the launch)
-  double* out;             // RP_OUT doubles per pair
 };
-
-__device__ __forceinline__ double2 rp_norm(const RelposeArgs& a, const double2 p) {
-  return make_double2((p.x - a.cx) / a.fx, (p.y - a.cy) / a.fy);
-}
-
-// step 2: five distinct indices below n (n >= 5), a pure function of (seed, pair, h, n)
-__device__ __forceinline__ void rp_sample(const unsigned long long seed, const int pair, const int h, const int n, int (&idx)[5]) {
-  constexpr unsigned long long G = 0x9E3779B97F4A7C15ull;
-  const unsigned long long k = rn_mix(rn_mix(rn_mix(seed + G) + (unsigned long long)pair) + (unsigned long long)h);
-  int s[5];                                       // the earlier indices, ascending
-#pragma unroll
-  for (int d = 0; d < 5; ++d) {
-    int i = (int)__umul64hi(rn_mix(k + (unsigned long long)(d + 1) * G), (unsigned long long)(n - d));
-#pragma unroll
-    for (int j = 0; j < d; ++j) if (i >= s[j]) ++i;
-    idx[d] = i;
-    s[d] = i;
-#pragma unroll
-    for (int j = d; j > 0; --j) if (s[j - 1] > s[j]) { const int t = s[j - 1]; s[j - 1] = s[j]; s[j] = t; }
-  }
-}
 
 // ---------------------------------------------------------------------------------- polynomials in (x, y, z), fixed orders
 // linear: x y z 1;  quadratic: x2 y2 z2 xy xz yz x y z 1;  cubic: the column order of the 10 x 20 constraint matrix,
@@ -208,13 +175,13 @@ __global__ void __launch_bounds__(RP_THREADS) k_relpose_solve(const RelposeArgs 
 
   // ---- sample, and the 5 x 9 system by columns: lane c < 9 holds column c = 3 i + j of the rows x2_i x1_j
   int idx[5];
-  rp_sample(a.seed, pair, h, n, idx);
+  hy_sample(a.seed, pair, h, n, idx);
   double col[5];
   {
     const int ci = tl / 3, cj = tl % 3;
 #pragma unroll
     for (int r = 0; r < 5; ++r) {
-      const double2 x1 = rp_norm(a, a.p1[beg + idx[r]]), x2 = rp_norm(a, a.p2[beg + idx[r]]);
+      const double2 x1 = pv_norm(a, a.p1[beg + idx[r]]), x2 = pv_norm(a, a.p2[beg + idx[r]]);
       const double f2 = ci == 0 ? x2.x : ci == 1 ? x2.y : 1.0, f1 = cj == 0 ? x1.x : cj == 1 ? x1.y : 1.0;
       col[r] = tl < 9 ? f2 * f1 : 0.0;
     }
@@ -439,7 +406,7 @@ __global__ void __launch_bounds__(RP_THREADS) k_relpose_solve(const RelposeArgs 
         g[0] += jx * f; g[1] += jy * f; g[2] += jz * f;
       }
       double C[6];
-      rn_cof(H, C);
+      sym3_cof(H, C);
       const double det = H[0] * C[0] + H[1] * C[1] + H[2] * C[2];
       if (!(det > 0.0) || !sim_finite(det)) break;
       const double id = 1.0 / det;
@@ -472,14 +439,14 @@ __global__ void __launch_bounds__(RP_THREADS) k_relpose_solve(const RelposeArgs 
 
 // ------------------------------------------------------------------------------------------------ scores
 __global__ void __launch_bounds__(RP_THREADS) k_relpose_score(const RelposeArgs a) {
-  __shared__ double tile[RP_TILE * 4];
-  __shared__ double red[2 * RS_WAVES];
-  const int pair = blockIdx.x, blk = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  __shared__ double tile[HY_TILE * 4];
+  __shared__ double red[2 * HY_WAVES];
+  const int pair = blockIdx.x, blk = blockIdx.y, tid = threadIdx.x;
   const long long beg = a.off[pair];
   const int n = (int)(a.off[pair + 1] - beg);
   double* out = a.best + RP_BEST * ((size_t)pair * a.n_blk + blk);
   if (n < 6) {                                    // (workgroup-uniform) FEW_MATCHES
-    if (tid == 0) { out[0] = RN_INF; out[1] = 0.0; }
+    hy_void_block(out);
     return;
   }
   const int cand = blk * RP_THREADS + tid, h = cand / RP_SLOTS, slot = cand % RP_SLOTS;
@@ -498,11 +465,11 @@ __global__ void __launch_bounds__(RP_THREADS) k_relpose_score(const RelposeArgs 
   }
   const double thr2 = a.thr * a.thr;
   double cost = 0.0;
-  for (int i0 = 0; i0 < n; i0 += RP_TILE) {
-    const int m = min(RP_TILE, n - i0);
+  for (int i0 = 0; i0 < n; i0 += HY_TILE) {
+    const int m = min(HY_TILE, n - i0);
     __syncthreads();                              // (the readers of the previous tile are done)
     if (tid < m) {
-      const double2 x1 = rp_norm(a, a.p1[beg + i0 + tid]), x2 = rp_norm(a, a.p2[beg + i0 + tid]);
+      const double2 x1 = pv_norm(a, a.p1[beg + i0 + tid]), x2 = pv_norm(a, a.p2[beg + i0 + tid]);
       double2* d = (double2*)(tile + 4 * tid);
       d[0] = x1; d[1] = x2;
     }
@@ -515,22 +482,13 @@ __global__ void __launch_bounds__(RP_THREADS) k_relpose_score(const RelposeArgs 
       cost += has ? fmin(r2, thr2) : thr2;
     }
   }
-  const double bc = valid ? cost : RN_INF, bk = valid ? (double)cand : RN_INF;
-  const double wc = wave_min_dpp(bc);
-  const double wk = wave_min_dpp(bc == wc ? bk : RN_INF);
-  if (lane == 0) { red[2 * wv] = wc; red[2 * wv + 1] = wk; }
-  __syncthreads();
-  double gc = red[0], gk = red[1];
-#pragma unroll
-  for (int w = 1; w < RS_WAVES; ++w) {
-    const double xc = red[2 * w], xk = red[2 * w + 1];
-    if (xc < gc || (xc == gc && xk < gk)) { gc = xc; gk = xk; }
-  }
-  if (!(gc < RN_INF)) {
-    if (tid == 0) { out[0] = RN_INF; out[1] = 0.0; }
+  double gc, gk;
+  const bool mine = hy_block_best(valid ? cost : HY_INF, valid ? (double)cand : HY_INF, red, gc, gk);
+  if (!(gc < HY_INF)) {
+    hy_void_block(out);
     return;
   }
-  if (valid && bc == gc && bk == gk) {            // one lane: keys are distinct
+  if (mine) {
     out[0] = gc; out[1] = gk;
 #pragma unroll
     for (int q = 0; q < 9; ++q) out[2 + q] = E[q];
@@ -632,7 +590,7 @@ __device__ __forceinline__ void rp_pass(const RelposeArgs& a, const RpPose& p, c
   for (int q = 0; q < RP_NSUM; ++q) acc[q] = 0.0;
   for (int j = (int)threadIdx.x; j < n; j += RP_THREADS) {
     if (!a.cons[beg + j]) continue;
-    const double2 x1 = rp_norm(a, a.p1[beg + j]), x2 = rp_norm(a, a.p2[beg + j]);
+    const double2 x1 = pv_norm(a, a.p1[beg + j]), x2 = pv_norm(a, a.p2[beg + j]);
     const double b[3] = {x2.x, x2.y, 1.0};
     double ra[3], c[3], l[3], ac[3], ab[3];
 #pragma unroll
@@ -719,13 +677,9 @@ __global__ void __launch_bounds__(RP_THREADS) k_relpose_lo(const RelposeArgs a) 
   if (n < 6) { rp_write(o, x, RP_FEW_MATCHES, 0.0, nan, nan, -1); return; }   // (workgroup-uniform, like every branch below)
   // the lowest (cost, 10 h + slot) over the score blocks, in block order: the same in every lane
   const double* b = a.best + RP_BEST * (size_t)pair * a.n_blk;
-  int win = 0;
-  double gc = b[0], gk = b[1];
-  for (int k = 1; k < a.n_blk; ++k) {
-    const double xc = b[RP_BEST * k], xk = b[RP_BEST * k + 1];
-    if (xc < gc || (xc == gc && xk < gk)) { gc = xc; gk = xk; win = k; }
-  }
-  if (!(gc < RN_INF)) { rp_write(o, x, RP_DEGENERATE, 0.0, nan, nan, -1); return; }   // every slot void
+  double gc, gk;
+  const int win = hy_winner<RP_BEST>(b, a.n_blk, gc, gk);
+  if (!(gc < HY_INF)) { rp_write(o, x, RP_DEGENERATE, 0.0, nan, nan, -1); return; }   // every slot void
   const int best = (int)gk / RP_SLOTS;
   double E[9];
 #pragma unroll
@@ -735,20 +689,8 @@ __global__ void __launch_bounds__(RP_THREADS) k_relpose_lo(const RelposeArgs a) 
   // ---- E = U diag V^T; the third columns are the cross products of the first two, so det U = det V = +1
   RpPose cand[2];                                 // R_a, R_b; t = +-u3 in .t of both
   {
-    double U[3][3], V[3][3], n2[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) U[i][j] = E[3 * i + j];
-    jacobi_svd<3, 24>(U, V);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) n2[k] = U[0][k] * U[0][k] + U[1][k] * U[1][k] + U[2][k] * U[2][k];
-    sim_order<0, 1>(U, V, n2); sim_order<1, 2>(U, V, n2); sim_order<0, 1>(U, V, n2);
-    const double i0 = 1.0 / sqrt(n2[0]), i1 = 1.0 / sqrt(n2[1]);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { U[k][0] *= i0; U[k][1] *= i1; }
-    U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1]; U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1]; U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-    V[0][2] = V[1][0] * V[2][1] - V[2][0] * V[1][1]; V[1][2] = V[2][0] * V[0][1] - V[0][0] * V[2][1]; V[2][2] = V[0][0] * V[1][1] - V[1][0] * V[0][1];
+    double U[3][3], V[3][3], d[3];
+    hy_canon_svd(E, U, V, d);
     // U W = [u2, -u1, u3], U W^T = [-u2, u1, u3]
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -767,7 +709,7 @@ __global__ void __launch_bounds__(RP_THREADS) k_relpose_lo(const RelposeArgs a) 
   {
     double vote[4] = {0.0, 0.0, 0.0, 0.0};
     for (int j = tid; j < n; j += RP_THREADS) {
-      const double2 x1 = rp_norm(a, a.p1[beg + j]), x2 = rp_norm(a, a.p2[beg + j]);
+      const double2 x1 = pv_norm(a, a.p1[beg + j]), x2 = pv_norm(a, a.p2[beg + j]);
       double r2, ra[3];
       if (!rp_sampson2(E, x1.x, x1.y, x2.x, x2.y, r2) || !(r2 <= thr2)) continue;
 #pragma unroll
@@ -793,7 +735,7 @@ __global__ void __launch_bounds__(RP_THREADS) k_relpose_lo(const RelposeArgs a) 
     rp_essential(x, Ex);
     double cn[1] = {0.0};
     for (int j = tid; j < n; j += RP_THREADS) {   // every lane writes the bytes it reads back in the passes (same stride)
-      const double2 x1 = rp_norm(a, a.p1[beg + j]), x2 = rp_norm(a, a.p2[beg + j]);
+      const double2 x1 = pv_norm(a, a.p1[beg + j]), x2 = pv_norm(a, a.p2[beg + j]);
       double r2, ra[3];
       const unsigned char in = rp_sampson2(Ex, x1.x, x1.y, x2.x, x2.y, r2) && r2 <= thr2 && rp_front(x, 1.0, a.max_depth, x1.x, x1.y, x2.x, x2.y, ra) ? 1 : 0;
       a.cons[beg + j] = in;
@@ -853,7 +795,7 @@ __global__ void __launch_bounds__(RP_THREADS) k_relpose_lo(const RelposeArgs a) 
     double Ex[9];
     rp_essential(x, Ex);
     for (int j = tid; j < n; j += RP_THREADS) {
-      const double2 x1 = rp_norm(a, a.p1[beg + j]), x2 = rp_norm(a, a.p2[beg + j]);
+      const double2 x1 = pv_norm(a, a.p1[beg + j]), x2 = pv_norm(a, a.p2[beg + j]);
       double r2, ra[3];
       if (!(rp_sampson2(Ex, x1.x, x1.y, x2.x, x2.y, r2) && r2 <= thr2 && rp_front(x, 1.0, a.max_depth, x1.x, x1.y, x2.x, x2.y, ra))) continue;
       const double c0 = ra[1] - ra[2] * x2.y, c1 = ra[2] * x2.x - ra[0], c2 = ra[0] * x2.y - ra[1] * x2.x;

@@ -397,6 +397,20 @@ def _dp(a):
     return a.ctypes.data_as(_DP) if a is not None else None
 
 
+def _pair_inputs(K, pts1, pts2, pair_off):
+    """What ba_relative_pose and ba_homography take of (K, pts1, pts2, pair_off): K (3, 3), the pixels (n, 2) and the offsets
+    (n_pairs + 1,) int64, all contiguous (pair_off None: one pair of all matches)."""
+    Km = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
+    p1 = np.ascontiguousarray(pts1, dtype=np.float64).reshape(-1, 2)
+    p2 = np.ascontiguousarray(pts2, dtype=np.float64).reshape(-1, 2)
+    if p1.shape[0] != p2.shape[0]:
+        raise ValueError("pts1 and pts2 must list the same number of points")
+    off = np.array([0, p1.shape[0]], dtype=np.int64) if pair_off is None else np.ascontiguousarray(pair_off, dtype=np.int64).ravel()
+    if off.size < 1 or (off.size > 1 and off[-1] != p1.shape[0]):
+        raise ValueError("pair_off must have n_pairs + 1 entries and end at the number of matches")
+    return Km, p1, p2, off
+
+
 def _match_inputs(sets, pairs):
     """What ba_match_descriptors and ba_match_guided take of (sets, pairs): the sets as arrays, their width, set_off, the
     concatenated descriptors, pair_query, pair_train and the number of output rows."""
@@ -891,14 +905,7 @@ class Solver:
         refine_iters, min_inliers, min_parallax_deg, max_depth.  Returns dict(R (P, 3, 3), t (P, 3), status (P,) uint8
         (RELPOSE_STATUS), n_inliers, rms_px, parallax_deg, best_hyp (P,), match_inlier (n,) bool).  Needs no problem and
         leaves a resident one as it is."""
-        Km = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
-        p1 = np.ascontiguousarray(pts1, dtype=np.float64).reshape(-1, 2)
-        p2 = np.ascontiguousarray(pts2, dtype=np.float64).reshape(-1, 2)
-        if p1.shape[0] != p2.shape[0]:
-            raise ValueError("pts1 and pts2 must list the same number of points")
-        off = np.array([0, p1.shape[0]], dtype=np.int64) if pair_off is None else np.ascontiguousarray(pair_off, dtype=np.int64).ravel()
-        if off.size < 1 or (off.size > 1 and off[-1] != p1.shape[0]):
-            raise ValueError("pair_off must have n_pairs + 1 entries and end at the number of matches")
+        Km, p1, p2, off = _pair_inputs(K, pts1, pts2, pair_off)
         o = self.relpose_options(**opts)
         P, n = off.size - 1, p1.shape[0]
         out = dict(R=np.empty((P, 3, 3)), t=np.empty((P, 3)), status=np.empty(P, dtype=np.uint8), n_inliers=np.empty(P, dtype=np.int32),
@@ -924,14 +931,7 @@ class Solver:
         min_translation.  Returns dict(H (P, 3, 3), status (P,) uint8 (HOMOGRAPHY_STATUS), n_inliers, rms_px, best_hyp, n_pose
         (P,), match_inlier (n,) bool, R (P, 2, 3, 3), t, normal (P, 2, 3), t_over_d, votes, pose_cost (P, 2)).  Needs no problem
         and leaves a resident one as it is."""
-        Km = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
-        p1 = np.ascontiguousarray(pts1, dtype=np.float64).reshape(-1, 2)
-        p2 = np.ascontiguousarray(pts2, dtype=np.float64).reshape(-1, 2)
-        if p1.shape[0] != p2.shape[0]:
-            raise ValueError("pts1 and pts2 must list the same number of points")
-        off = np.array([0, p1.shape[0]], dtype=np.int64) if pair_off is None else np.ascontiguousarray(pair_off, dtype=np.int64).ravel()
-        if off.size < 1 or (off.size > 1 and off[-1] != p1.shape[0]):
-            raise ValueError("pair_off must have n_pairs + 1 entries and end at the number of matches")
+        Km, p1, p2, off = _pair_inputs(K, pts1, pts2, pair_off)
         o = self.homography_options(**opts)
         P, n = off.size - 1, p1.shape[0]
         out = dict(H=np.empty((P, 3, 3)), status=np.empty(P, dtype=np.uint8), n_inliers=np.empty(P, dtype=np.int32), rms_px=np.empty(P),
