@@ -3535,6 +3535,12 @@ static int resect_begin(ba_handle* h, const char* who, const double* intr, const
   if (!(o.f_scale > 0)) return fail(BA_ERR_INVALID, "%s: f_scale must be positive", who);
   if (o.refine_iters < 0) return fail(BA_ERR_INVALID, "%s: refine_iters must not be negative", who);
   if (o.min_inliers < 0) return fail(BA_ERR_INVALID, "%s: min_inliers must not be negative", who);
+  // the cameras of a multi-rank job are replicated and ba_solve relies on every rank holding the same bits: a pose
+  // resected from this rank's shard alone would split them (a forced communicator of one rank has nobody to differ from)
+  if (o.write_cams && h->world > 1)
+    return fail(BA_ERR_INVALID, "%s: write_cams = 1 on a multi-rank handle (world %d): every rank would store poses from its own "
+                                "shard's observations and the replicated cameras would differ; resect with write_cams = 0 and "
+                                "hand every rank the same poses (ba_set_params)", who, h->world);
   if (o.write_cams && any_prior(h))
     return fail(BA_ERR_STATE, "%s with write_cams = 1: priors are set (ba_set_priors) and their means were set for the old poses: "
                               "resect first, set the priors afterwards", who);
@@ -4356,6 +4362,12 @@ extern "C" int ba_align(ba_handle* h, const ba_align_options* opts, const double
   if (!(opts->f_scale > 0)) return fail(BA_ERR_INVALID, "ba_align: f_scale must be positive");
   if (opts->iters < 0) return fail(BA_ERR_INVALID, "ba_align: iters must not be negative");
   if (!cam_ref && !pt_ref) return fail(BA_ERR_INVALID, "ba_align: no reference positions (cam_ref and pt_ref are both NULL)");
+  // points are rank-local: a similarity estimated with pt_ref differs from rank to rank, and applying it would split the
+  // replicated cameras (cam_ref alone sees the same cameras on every rank and gives every rank the same similarity)
+  if (opts->apply && pt_ref && h->world > 1)
+    return fail(BA_ERR_INVALID, "ba_align: apply = 1 with pt_ref on a multi-rank handle (world %d): every rank would estimate its "
+                                "own similarity from its shard's points and the replicated cameras would differ; align with "
+                                "apply = 0 and pass every rank the same similarity (ba_transform), or give cam_ref alone", h->world);
   if (opts->apply && any_prior(h)) return fail(BA_ERR_STATE, kSimPriors, "ba_align with apply = 1");
   const int Nc = h->Nc, Np = h->Np;
   const int n_cam = cam_ref ? Nc : 0, n_pt = pt_ref ? Np : 0;

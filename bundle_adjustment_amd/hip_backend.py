@@ -870,7 +870,9 @@ class Solver:
         (Nc,) mask or a list of camera indices, None = every camera; known_points: bool (Np,) mask or a list of point
         indices, None = every point.  opts: loss, refine_iters, f_scale, init ("dlt" / "current"), min_inliers,
         max_reproj_px, max_rms_px, min_depth, write_cams.  Returns dict(poses (Nc, 6) rvec | t, status (Nc,) uint8
-        (RESECT_STATUS), n_inliers (Nc,) int32, rms_px, max_px (Nc,))."""
+        (RESECT_STATUS), n_inliers (Nc,) int32, rms_px, max_px (Nc,)).  Multi-rank handles: the poses come from the rank's
+        shard alone, and write_cams=1 raises BAHipError (BA_ERR_INVALID) when world > 1 -- it would split the replicated
+        cameras; ``resect_ransac`` alike."""
         (ip, selp, knownp), out, outp = self._resect_head(intr, cams, known_points)
         o = self.resect_options(**opts)
         _check(self._lib.ba_resect(self._h, ip, C.byref(o), selp, knownp, *outp))
@@ -1172,7 +1174,9 @@ class Solver:
         """ba_align: the similarity that brings the current camera centres (cam_ref (Nc, 3)) and / or points (pt_ref (Np, 3))
         onto reference positions, weighted (cam_w, pt_w; 0 = no reference, the row may be NaN) and robust (loss / f_scale in
         the references' unit, `iters` IRLS rounds); apply=True also transforms the handle's parameters.  Returns dict(s, R
-        (3, 3), t (3,), rms, max, n_used, status (ALIGN_STATUS), cam_err (Nc,) or None, pt_err (Np,) or None)."""
+        (3, 3), t (3,), rms, max, n_used, status (ALIGN_STATUS), cam_err (Nc,) or None, pt_err (Np,) or None).  Multi-rank
+        handles: apply=True with pt_ref raises BAHipError (BA_ERR_INVALID) when world > 1 (the points are the rank's own);
+        cam_ref alone gives every rank the same similarity."""
         o = BAAlignOptions()
         _check(self._lib.ba_default_align_options(C.byref(o)))
         o.loss, o.iters, o.f_scale, o.with_scale, o.apply = loss_code(loss), int(iters), float(f_scale), int(bool(with_scale)), int(bool(apply))

@@ -218,7 +218,8 @@ int ba_triangulate(ba_handle* h, const double K[9], const double R_rel[9], const
  * priors, groups stay); write_points = 0 leaves the handle exactly as found.
  * BA_ERR_STATE before ba_set_problem / ba_set_params; BA_ERR_INVALID for an unknown loss, f_scale <= 0, refine_iters < 0,
  * reserved0 != 0.  Multi-rank jobs: the call is local to the calling rank's shard (its points, all cameras), no collective;
- * untested on more than one rank. */
+ * points are rank-local, so write_points = 1 is a rank-local write that every rank may make.  Pinned on two ranks
+ * (tests/test_gpu_multirank_local.py): a handle with a communicator returns the bits of a plain handle on the same shard. */
 enum ba_track_status { BA_TRACK_OK = 0, BA_TRACK_FEW_VIEWS = 1, BA_TRACK_DEGENERATE = 2,
                        BA_TRACK_BEHIND = 3, BA_TRACK_LOW_ANGLE = 4, BA_TRACK_HIGH_ERROR = 5 };
 typedef struct ba_track_options {
@@ -273,7 +274,11 @@ int ba_triangulate_tracks(ba_handle* h, const double* intr, const ba_track_optio
  * set: their means were set for the old poses.  BA_ERR_INVALID for an unknown loss or init, f_scale <= 0, refine_iters < 0,
  * min_inliers < 0, reserved0 != 0.  One workgroup per camera, sums in a fixed order and without atomics: results are
  * bit-reproducible from call to call.  Multi-rank jobs: the call is local to the calling rank's shard (all cameras, its
- * observations and points), no collective; untested on more than one rank. */
+ * observations and points), no collective: a camera is resected from the shard's observations alone.  The cameras are
+ * replicated and ba_solve needs them bitwise identical on every rank, so write_cams = 1 is refused when world > 1
+ * (BA_ERR_INVALID, naming write_cams and "multi-rank", the handle left as found; a communicator of one rank is not refused):
+ * resect with write_cams = 0 and hand every rank the same poses (ba_set_params).  Pinned on two ranks
+ * (tests/test_gpu_multirank_local.py). */
 enum ba_resect_status { BA_RESECT_OK = 0, BA_RESECT_FEW_POINTS = 1, BA_RESECT_DEGENERATE = 2,
                         BA_RESECT_BEHIND = 3, BA_RESECT_FEW_INLIERS = 4, BA_RESECT_HIGH_ERROR = 5 };
 enum ba_resect_init   { BA_RESECT_INIT_DLT = 0, BA_RESECT_INIT_CURRENT = 1 };
@@ -325,7 +330,9 @@ int ba_resect(ba_handle* h, const double* intr, const ba_resect_options* opts, c
  * are set).  BA_ERR_STATE before ba_set_problem / ba_set_params.  BA_ERR_INVALID, naming the field: n_hyp outside 1 .. 4096,
  * lo_rounds < 0, max_reproj_px not > 0, an unknown loss, f_scale not > 0, refine_iters < 0, min_inliers < 0.  Results are
  * bit-reproducible from call to call (fixed-order sums, no atomics, one lexicographic arg-min).  Multi-rank jobs: local to the
- * calling rank's shard, no collective; untested on more than one rank. */
+ * calling rank's shard, no collective; obs_inlier covers the shard's observations in the shard's order; write_cams = 1 is
+ * refused when world > 1 as in ba_resect (BA_ERR_INVALID naming write_cams and "multi-rank").  Pinned on two ranks
+ * (tests/test_gpu_multirank_local.py). */
 typedef struct ba_ransac_options {
   int32_t  n_hyp;          /* minimal samples per camera, 1 .. 4096; default 256 */
   int32_t  lo_rounds;      /* rounds of (consensus at the current pose, refinement on it); default 2; 0 = the best raw hypothesis */
@@ -636,8 +643,9 @@ int ba_orb_stage_times(ba_handle* h, int32_t enable, double* ms);
  * leaves the handle exactly as ba_set_params(transformed cameras, transformed points) would.  BA_ERR_STATE before
  * ba_set_problem / parameters, and (naming "priors") while ba_set_priors blocks are set: their means live in the old frame,
  * so align first and set priors afterwards.  BA_ERR_INVALID for s not finite or <= 0, max |R R^T - I| > 1e-9, det R < 0, a
- * non-finite t.  A refused call leaves the handle as found.  Multi-rank jobs: local to the rank, every rank must pass the
- * same similarity; untested on more than one rank. */
+ * non-finite t.  A refused call leaves the handle as found.  Multi-rank jobs: local to the rank, no collective; every rank
+ * must pass the same similarity -- the replicated cameras then stay bitwise identical, the points are rank-local.  Pinned on
+ * two ranks (tests/test_gpu_multirank_local.py). */
 typedef struct ba_similarity { double s; double R[9]; double t[3]; } ba_similarity;
 
 int ba_get_centres(ba_handle* h, double* centres);            /* double[Nc][3]: -R_c^T t_c of the current cameras */
@@ -657,7 +665,10 @@ int ba_transform(ba_handle* h, const ba_similarity* sim);
  * BA_ERR_INVALID for an unknown loss, f_scale <= 0, iters < 0, both reference arrays NULL; BA_ERR_STATE as ba_transform
  * (the priors refusal only with apply = 1).  All rounds run on the device without a host synchronisation in between; the sums
  * use no atomics and a fixed order: results are bit-reproducible from call to call.  Local to the rank, no collective:
- * callers of multi-rank jobs align on camera references, which are replicated. */
+ * callers of multi-rank jobs align on camera references, which are replicated -- cam_ref alone gives every rank the same
+ * similarity, and apply = 1 then moves every rank's cameras alike.  pt_ref sees the rank's own points: with apply = 1 and
+ * world > 1 it is refused (BA_ERR_INVALID naming apply, pt_ref and "multi-rank", the handle left as found); estimate with
+ * apply = 0 and pass every rank one similarity (ba_transform).  Pinned on two ranks (tests/test_gpu_multirank_local.py). */
 enum ba_align_status { BA_ALIGN_OK = 0, BA_ALIGN_TOO_FEW = 1, BA_ALIGN_DEGENERATE = 2 };
 typedef struct ba_align_options {
   int32_t loss;        /* ba_loss, ONE rho per correspondence, on its 3-D distance */

@@ -134,7 +134,12 @@ def test_header_declares_both_symbols_and_the_structs_match():
     assert {k.lower(): int(v) for k, v in init.items()} == hb.RESECT_INIT
     assert (rr.OK, rr.FEW_POINTS, rr.DEGENERATE, rr.BEHIND, rr.FEW_INLIERS, rr.HIGH_ERROR) == tuple(range(6))
     assert re.search(r"BA_K_RESECT = (\d+)", hdr).group(1) == str(hb.K_RESECT)
-    assert hdr.count("untested on more than one rank") >= 3
+    flat = " ".join(hdr.replace("\n *", " ").split())
+    # what is pinned on two ranks: ba_triangulate_tracks, ba_resect, ba_resect_ransac, ba_transform, ba_align -- and the
+    # camera writes that are refused there: both resections' write_cams, ba_align's apply with pt_ref
+    assert flat.count("Pinned on two ranks (tests/test_gpu_multirank_local.py)") >= 5
+    assert flat.count("refused when world > 1") >= 2 and "with apply = 1 and world > 1 it is refused" in flat
+    assert "every rank must pass the same similarity" in flat and "untested on" not in hdr
 
 
 def test_library_exports_ba_resect_and_its_defaults_need_no_gpu():

@@ -159,7 +159,8 @@ def test_header_declares_both_symbols_and_the_structs_match():
     enum = dict(re.findall(r"BA_TRACK_(\w+) = (\d)", hdr))
     assert {k.lower(): int(v) for k, v in enum.items()} == hb.TRACK_STATUS
     assert (tr.OK, tr.FEW_VIEWS, tr.DEGENERATE, tr.BEHIND, tr.LOW_ANGLE, tr.HIGH_ERROR) == tuple(range(6))
-    assert "untested on more than one rank" in hdr
+    doc = " ".join(re.search(r"/\* N-view triangulation and filtering of whole tracks.*?\*/", hdr, flags=re.S).group(0).replace("\n *", " ").split())
+    assert "no collective" in doc and "write_points = 1 is a rank-local write" in doc and "Pinned on two ranks" in doc
 
 
 def test_default_track_options_need_no_gpu():
