@@ -5,5 +5,5 @@ from .problem import BAProblem  # noqa: F401
 from .bundle_adjuster import BundleAdjuster  # noqa: F401
 from .pose_estimator import estimate_pose, estimate_two_view, homography, relative_pose  # noqa: F401
 from .features import BruteForceMatcher, ORBExtractor, fundamental, match, match_by_homography, match_by_projection, match_epipolar  # noqa: F401
-from .posegraph import close_loop  # noqa: F401
+from .posegraph import close_loop, loop_measurement  # noqa: F401
 from .place import KeyframeDatabase, Vocabulary, bow_vector, pair_list  # noqa: F401

@@ -48,6 +48,7 @@
 #include "ba_match_guided.hpp"
 #include "ba_orb.hpp"
 #include "ba_posegraph.hpp"
+#include "ba_sim3.hpp"
 #include "ba_bow.hpp"
 
 using namespace ba;
@@ -308,6 +309,7 @@ struct ba_handle {
     DBuf<unsigned char> cons, inl;
   };
   PairStage rp, hg;
+  PairStage s3;                // ba_sim3 (ba_sim3.hpp): pts holds X1 | X2, three doubles per correspondence
   DBuf<double> rp_E;
   DBuf<unsigned> rp_mask;
   // ba_match_descriptors (ba_match.hpp): staging of the call -- every set's descriptors, the pair table, the splits' (k1, k2),
@@ -3844,6 +3846,70 @@ extern "C" int ba_homography(ba_handle* h, const double K[9], int32_t n_pairs, c
       if (t_over_d) memcpy(t_over_d + 2 * p, r + 44, 2 * sizeof(double));
       if (votes) { votes[2 * p] = (int32_t)r[46]; votes[2 * p + 1] = (int32_t)r[47]; }
       if (pose_cost) memcpy(pose_cost + 2 * p, r + 48, 2 * sizeof(double));
+    }
+  return BA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- Sim(3) from 3D-3D matches
+// ba_sim3 (csrc/ba_sim3.hpp): three-point hypotheses and scores, local optimisation, the Hessian of the result.  Needs no problem.
+static_assert(S3_OK == BA_SIM3_OK && S3_FEW_MATCHES == BA_SIM3_FEW_MATCHES && S3_DEGENERATE == BA_SIM3_DEGENERATE &&
+              S3_FEW_INLIERS == BA_SIM3_FEW_INLIERS && sizeof(ba_sim3_options) == 40, "device status codes (ba_sim3.hpp)");
+extern "C" int ba_default_sim3_options(ba_sim3_options* o) {
+  if (!o) return fail(BA_ERR_INVALID, "null argument");
+  memset(o, 0, sizeof *o);
+  o->n_hyp = 256;
+  o->lo_rounds = 2;
+  o->max_px = 4.0;
+  o->refine_iters = 20;
+  o->min_inliers = 8;
+  o->with_scale = 1;
+  return BA_OK;
+}
+extern "C" int ba_sim3(ba_handle* h, const double K[9], int32_t n_pairs, const int64_t* pair_off, const double* X1, const double* X2,
+                       const ba_sim3_options* opts, double* sim, double* R, uint8_t* status, int32_t* n_inliers, double* rms_px,
+                       int32_t* best_hyp, uint8_t* match_inlier, double* hessian) {
+  if (!h || !K || !opts) return fail(BA_ERR_INVALID, "null argument");
+  if (int rc = pairs_check("ba_sim3", K, n_pairs, pair_off, X1, X2, opts->n_hyp, opts->lo_rounds, opts->refine_iters, opts->min_inliers))
+    return rc;
+  if (!(opts->max_px > 0)) return fail(BA_ERR_INVALID, "ba_sim3: max_px must be positive");
+  if (opts->with_scale != 0 && opts->with_scale != 1) return fail(BA_ERR_INVALID, "ba_sim3: with_scale must be 0 or 1");
+  if (n_pairs == 0) return BA_OK;
+  if (set_device(h)) return BA_ERR_HIP;
+  ba_handle::PairStage& st = h->s3;
+  const size_t np = (size_t)n_pairs, nm = (size_t)pair_off[n_pairs], nm1 = std::max<size_t>(nm, 1);
+  const int n_blk = (opts->n_hyp + S3_THREADS - 1) / S3_THREADS;
+  HIPCHECK(st.pts.alloc(6 * nm1)); HIPCHECK(st.off.alloc(np + 1)); HIPCHECK(st.best.alloc((size_t)S3_BEST * np * n_blk));
+  HIPCHECK(st.out.alloc((size_t)S3_OUT * np)); HIPCHECK(st.cons.alloc(nm1)); HIPCHECK(st.inl.alloc(nm1));
+  Sim3Args a = {};
+  a.fbar = 0.5 * (K[0] + K[4]); a.thr = opts->max_px / a.fbar;
+  a.n_hyp = opts->n_hyp; a.lo_rounds = opts->lo_rounds; a.iters = opts->refine_iters; a.min_inliers = opts->min_inliers;
+  a.with_scale = opts->with_scale; a.n_blk = n_blk; a.seed = opts->seed;
+  a.off = st.off.p; a.X1 = st.pts.p; a.X2 = st.pts.p + 3 * nm1;
+  a.best = st.best.p; a.cons = st.cons.p; a.inl = st.inl.p; a.out = st.out.p;
+  HIPCHECK(hipMemcpyAsync(st.off.p, pair_off, (np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  if (nm > 0) {
+    HIPCHECK(hipMemcpyAsync(st.pts.p, X1, 3 * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(st.pts.p + 3 * nm1, X2, 3 * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemsetAsync(st.inl.p, 0, nm, h->stream));
+  }
+  const dim3 b(S3_THREADS);
+  BA_LAUNCH(k_sim3_score, dim3(n_pairs, n_blk), b, 0, h->stream, a);
+  BA_LAUNCH(k_sim3_lo, dim3(n_pairs), b, 0, h->stream, a);
+  const bool want = sim || R || status || n_inliers || rms_px || best_hyp || hessian;
+  std::vector<double> res;
+  if (int rc = pairs_download(h, st, want, S3_OUT, n_pairs, pair_off, match_inlier, res)) return rc;
+  if (want)
+    for (size_t p = 0; p < np; ++p) {
+      const double* r = res.data() + S3_OUT * p;
+      if (sim) memcpy(sim + 7 * p, r, 7 * sizeof(double));
+      if (R) memcpy(R + 9 * p, r + 7, 9 * sizeof(double));
+      if (status) status[p] = (uint8_t)r[16];
+      if (n_inliers) n_inliers[p] = (int32_t)r[17];
+      if (rms_px) rms_px[p] = r[18];
+      if (best_hyp) best_hyp[p] = (int32_t)r[19];
+      if (hessian)
+        for (int i = 0; i < 7; ++i)
+          for (int j = i; j < 7; ++j) hessian[49 * p + 7 * i + j] = hessian[49 * p + 7 * j + i] = r[20 + s3_u7(i, j)];
     }
   return BA_OK;
 }

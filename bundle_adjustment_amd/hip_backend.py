@@ -121,6 +121,11 @@ class BAHomographyOptions(C.Structure):
                 ("min_translation", C.c_double)]
 
 
+class BASim3Options(C.Structure):
+    _fields_ = [("n_hyp", C.c_int32), ("lo_rounds", C.c_int32), ("seed", C.c_uint64), ("max_px", C.c_double),
+                ("refine_iters", C.c_int32), ("min_inliers", C.c_int32), ("with_scale", C.c_int32), ("reserved0", C.c_int32)]
+
+
 class BAMatchOptions(C.Structure):
     _fields_ = [("ratio", C.c_double), ("max_distance", C.c_int32), ("mutual", C.c_int32)]
 
@@ -178,6 +183,7 @@ RESECT_STATUS = {"ok": 0, "few_points": 1, "degenerate": 2, "behind": 3, "few_in
 RESECT_INIT = {"dlt": 0, "current": 1}   # enum ba_resect_init
 RELPOSE_STATUS = {"ok": 0, "few_matches": 1, "degenerate": 2, "behind": 3, "few_inliers": 4, "low_parallax": 5}   # enum ba_relpose_status
 HOMOGRAPHY_STATUS = {"ok": 0, "few_matches": 1, "degenerate": 2, "few_inliers": 3, "rotation": 4, "ambiguous": 5}   # enum ba_homography_status
+SIM3_STATUS = {"ok": 0, "few_matches": 1, "degenerate": 2, "few_inliers": 3}   # enum ba_sim3_status
 
 
 def resect_init_code(init):
@@ -244,6 +250,9 @@ SYMBOLS = {
     "ba_default_homography_options": (C.c_int, [C.POINTER(BAHomographyOptions)]),
     "ba_homography": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.POINTER(C.c_int64), _DP, _DP, C.POINTER(BAHomographyOptions), _DP,
                                 C.POINTER(C.c_uint8), _IP, _DP, _IP, C.POINTER(C.c_uint8), _IP, _DP, _DP, _DP, _DP, _IP, _DP]),
+    "ba_default_sim3_options": (C.c_int, [C.POINTER(BASim3Options)]),
+    "ba_sim3": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.POINTER(C.c_int64), _DP, _DP, C.POINTER(BASim3Options), _DP, _DP,
+                          C.POINTER(C.c_uint8), _IP, _DP, _IP, C.POINTER(C.c_uint8), _DP]),
     "ba_default_match_options": (C.c_int, [C.POINTER(BAMatchOptions)]),
     "ba_match_descriptors": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.c_int32, _IP, _IP,
                                        C.POINTER(BAMatchOptions), C.POINTER(C.c_int64), _IP, _IP, _IP, _IP, C.POINTER(C.c_uint8), _IP]),
@@ -397,12 +406,12 @@ def _dp(a):
     return a.ctypes.data_as(_DP) if a is not None else None
 
 
-def _pair_inputs(K, pts1, pts2, pair_off):
+def _pair_inputs(K, pts1, pts2, pair_off, width=2):
     """What ba_relative_pose and ba_homography take of (K, pts1, pts2, pair_off): K (3, 3), the pixels (n, 2) and the offsets
-    (n_pairs + 1,) int64, all contiguous (pair_off None: one pair of all matches)."""
+    (n_pairs + 1,) int64, all contiguous (pair_off None: one pair of all matches).  width = 3: ba_sim3's (n, 3) points."""
     Km = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
-    p1 = np.ascontiguousarray(pts1, dtype=np.float64).reshape(-1, 2)
-    p2 = np.ascontiguousarray(pts2, dtype=np.float64).reshape(-1, 2)
+    p1 = np.ascontiguousarray(pts1, dtype=np.float64).reshape(-1, width)
+    p2 = np.ascontiguousarray(pts2, dtype=np.float64).reshape(-1, width)
     if p1.shape[0] != p2.shape[0]:
         raise ValueError("pts1 and pts2 must list the same number of points")
     off = np.array([0, p1.shape[0]], dtype=np.int64) if pair_off is None else np.ascontiguousarray(pair_off, dtype=np.int64).ravel()
@@ -946,6 +955,32 @@ class Solver:
                                        _dp(out["rms_px"]), out["best_hyp"].ctypes.data_as(_IP), inl.ctypes.data_as(u8),
                                        out["n_pose"].ctypes.data_as(_IP), _dp(out["R"]), _dp(out["t"]), _dp(out["normal"]),
                                        _dp(out["t_over_d"]), out["votes"].ctypes.data_as(_IP), _dp(out["pose_cost"])))
+        out["match_inlier"] = inl.astype(bool)
+        return out
+
+    def sim3_options(self, **kw) -> BASim3Options:
+        """ba_default_sim3_options overlaid with kw (any ba_sim3_options field; an unknown one raises TypeError)."""
+        return _options(BASim3Options, self._lib.ba_default_sim3_options, kw, names={})
+
+    def sim3(self, K, X1, X2, pair_off=None, **opts):
+        """ba_sim3: the similarity X2 ~ s R X1 + t of every pair from matched 3D points in the two camera frames (z forward) --
+        n_hyp three-point samples per pair scored by reprojection in both images, then lo_rounds of (consensus, closed form,
+        refinement).  X1 / X2 (n, 3); pair_off as ``relative_pose``.  opts: n_hyp, lo_rounds, seed, max_px, refine_iters,
+        min_inliers, with_scale.  Returns dict(sim (P, 7) rvec | t | s -- the meas of a pose-graph edge (1 -> 2) --, R (P, 3, 3), t
+        (P, 3), s (P,), status (P,) uint8 (SIM3_STATUS), n_inliers, rms_px, best_hyp (P,), match_inlier (n,) bool, hessian
+        (P, 7, 7): pixels^-2, in (d omega, d t, d sigma), see posegraph.edge_information).  Needs no problem and leaves a resident
+        one as it is."""
+        Km, p1, p2, off = _pair_inputs(K, X1, X2, pair_off, width=3)
+        o = self.sim3_options(**opts)
+        P, n = off.size - 1, p1.shape[0]
+        out = dict(sim=np.empty((P, 7)), R=np.empty((P, 3, 3)), status=np.empty(P, dtype=np.uint8), n_inliers=np.empty(P, dtype=np.int32),
+                   rms_px=np.empty(P), best_hyp=np.empty(P, dtype=np.int32), hessian=np.empty((P, 7, 7)))
+        inl = np.zeros(n, dtype=np.uint8)
+        u8 = C.POINTER(C.c_uint8)
+        _check(self._lib.ba_sim3(self._h, _dp(Km), P, off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(p1), _dp(p2), C.byref(o),
+                                 _dp(out["sim"]), _dp(out["R"]), out["status"].ctypes.data_as(u8), out["n_inliers"].ctypes.data_as(_IP),
+                                 _dp(out["rms_px"]), out["best_hyp"].ctypes.data_as(_IP), inl.ctypes.data_as(u8), _dp(out["hessian"])))
+        out["t"], out["s"] = out["sim"][:, 3:6].copy(), out["sim"][:, 6].copy()
         out["match_inlier"] = inl.astype(bool)
         return out
 

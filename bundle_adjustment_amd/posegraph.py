@@ -5,7 +5,8 @@ A node is a world-to-node similarity ``x = s R X + t`` stored as ``rvec | t | s`
 ``S_j o S_i^-1``.  The node ``(s, R, t)`` is the camera ``R | t / s``: both camera models divide by depth, so a camera frame
 scaled by ``s`` sees the same pixels (``ba_transform``'s argument, per keyframe).
 
-Everything here is numpy; ``close_loop`` alone calls the GPU (``hip_backend.Solver.pose_graph``).
+Everything here is numpy but two calls of the GPU: ``loop_measurement`` (``hip_backend.Solver.sim3``, the loop edge's
+``meas`` and ``info`` from matched map points) and ``close_loop`` (``hip_backend.Solver.pose_graph``).
 """
 from __future__ import annotations
 
@@ -103,6 +104,77 @@ def first_observers(cam_idx, pt_idx, n_pts):
     ref = np.full(n_pts, -1, dtype=np.int64)
     ref[pt_idx[::-1]] = cam_idx[::-1]          # the earliest observation is written last
     return ref
+
+
+def edge_information(sim, hessian, sigma_px=1.0):
+    """The ``info`` of a pose-graph edge from ``Solver.sim3``'s ``sim`` ((7,) or (m, 7)) and ``hessian`` ((7, 7) or (m, 7, 7)):
+    ``T H T^T / sigma_px^2`` with ``T = diag(R_ij^T, I, 1)``.  The call's chart moves the model by ``R <- exp(d omega) R, t <- t +
+    d t, s <- s exp(d sigma)``; the edge residual ``e = [log(R_ij^T R_r); t_r - t_ij; ln(s_r / s_ij)]`` of a relative pose that far
+    from the measurement is ``[R_ij^T d omega; d t; d sigma]`` to first order, so ``d = T^T e`` and ``0.5 d^T H d = 0.5 e^T (T H T^T)
+    e``.  ``sigma_px``: the standard deviation of a reprojection residual in pixels (``hessian`` is in pixels^-2)."""
+    sim, H = np.asarray(sim, dtype=np.float64), np.asarray(hessian, dtype=np.float64)
+    S, Hm = sim.reshape(-1, 7), H.reshape(-1, 7, 7)
+    T = np.zeros((S.shape[0], 7, 7))
+    T[:, :3, :3] = np.transpose(rvecs_to_matrices(S[:, :3]), (0, 2, 1))
+    T[:, 3, 3] = T[:, 4, 4] = T[:, 5, 5] = T[:, 6, 6] = 1.0
+    info = T @ Hm @ np.transpose(T, (0, 2, 1)) / float(sigma_px) ** 2
+    info = 0.5 * (info + np.transpose(info, (0, 2, 1)))
+    return info[0] if sim.ndim == 1 else info
+
+
+_FLIP = np.array([1.0, -1.0, -1.0])            # F = diag(1, -1, -1): BAL's camera frame (looks down -z) <-> the pinhole one
+
+
+def _camera_frame(prob, cam, pt):
+    """``pt`` -- (n,) indices into ``prob.pts`` or (n, 3) world coordinates -- in the frame of camera ``cam``."""
+    pt = np.asarray(pt)
+    X = prob.pts[pt.astype(np.int64)] if pt.ndim == 1 and np.issubdtype(pt.dtype, np.integer) else np.asarray(pt, dtype=np.float64).reshape(-1, 3)
+    c = np.asarray(prob.cams[cam], dtype=np.float64)
+    return X @ rvecs_to_matrices(c[:3])[0].T + c[3:6]
+
+
+def loop_measurement(prob, i, j, pt_i, pt_j, K=None, solver=None, sigma_px=1.0, **opts):
+    """The measurement of the loop edge ``(i, j)`` of a ``BAProblem`` or ``bal.BALProblem`` from matched map points: ``pt_i[k]``
+    (seen by camera ``i``) and ``pt_j[k]`` (seen by camera ``j``) are the same physical point, given as (n,) indices into
+    ``prob.pts`` or (n, 3) world coordinates; a share of the matches may be wrong.  The points are moved into the two camera
+    frames and ``Solver.sim3`` finds ``S_j o S_i^-1``.  Returns ``(meas (7,), info (7, 7), inlier (n,) bool, out)``, ready for
+    ``close_loop(prob, [i], [j], [meas], loop_info=[info])``; ``out`` is ``Solver.sim3``'s dict in the pinhole frames the call
+    saw.  A status other than OK raises ValueError naming it.  ``K``: (3, 3), default the problem's (``diag(f_j, f_j, 1)`` for
+    a BAL problem, whose frames are conjugated with ``F = diag(1, -1, -1)``: ``R = F R' F, t = F t'``, the Hessian's rotation and
+    translation blocks likewise).  ``solver``: a ``hip_backend.Solver`` to run on (its resident problem stays); default: one on
+    device 0 for the call.  ``sigma_px``: ``edge_information``'s.  opts: ``ba_sim3_options``."""
+    from . import hip_backend
+    bal = np.asarray(prob.cams).shape[1] == 9
+    Xi, Xj = _camera_frame(prob, i, pt_i), _camera_frame(prob, j, pt_j)
+    if Xi.shape[0] != Xj.shape[0]:
+        raise ValueError("pt_i and pt_j list different numbers of points")
+    if bal:
+        Xi, Xj = Xi * _FLIP, Xj * _FLIP
+    if K is None:
+        if bal:
+            f = float(prob.cams[j, 6])
+            K = np.diag([f, f, 1.0])
+        else:
+            fx, fy, cx, cy = (float(v) for v in prob.K4)
+            K = np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
+    own = solver is None
+    if own:
+        solver = hip_backend.Solver(0)
+    try:
+        out = solver.sim3(K, Xi, Xj, **opts)
+    finally:
+        if own:
+            solver.close()
+    status = int(out["status"][0])
+    if status != hip_backend.SIM3_STATUS["ok"]:
+        name = {v: k for k, v in hip_backend.SIM3_STATUS.items()}.get(status, str(status))
+        raise ValueError(f"loop_measurement: ba_sim3 status {name} ({int(out['n_inliers'][0])} inliers of {Xi.shape[0]} matches)")
+    R, t, s, H = out["R"][0], out["sim"][0, 3:6], out["sim"][0, 6], out["hessian"][0]
+    if bal:
+        T = np.r_[_FLIP, _FLIP, 1.0]
+        R, t, H = R * np.outer(_FLIP, _FLIP), t * _FLIP, H * np.outer(T, T)
+    meas = np.r_[log_map(R[None])[0], t, s]
+    return meas, edge_information(meas, H, sigma_px), out["match_inlier"], out
 
 
 def close_loop(prob, loop_i, loop_j, loop_meas, loop_info=None, held=(0,), solver=None, min_shared=15, **opts):

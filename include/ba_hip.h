@@ -482,6 +482,64 @@ int ba_homography(ba_handle* h, const double K[9], int32_t n_pairs, const int64_
                   const ba_homography_options* opts, double* H, uint8_t* status, int32_t* n_inliers, double* rms_px, int32_t* best_hyp,
                   uint8_t* match_inlier, int32_t* n_pose, double* R, double* t, double* normal, double* t_over_d, int32_t* votes,
                   double* pose_cost);
+/* Sim(3) from 3D-3D matches: the similarity between two camera frames from matched map points, a share of which may be
+ * wrong -- the measurement of a loop edge of ba_pose_graph (ORB-SLAM's Sim3Solver + OptimizeSim3 in ComputeSim3; COLMAP's
+ * similarity LO-RANSAC).  X1[k] and X2[k], double[pair_off[n_pairs]][3], are the same physical point in the CAMERA frame of view
+ * 1 and of view 2 (z forward, the pinhole convention); the model is X2 ~ s R X1 + t, and stored as rvec | t | s it is the meas of
+ * a pose-graph edge (1 -> 2), S_2 o S_1^-1.  K, n_pairs, pair_off, the staging buffers on the handle and the rule that no problem
+ * is needed or touched are ba_relative_pose's; K's principal point is not used (no pixels are passed).
+ * Outputs, any of them NULL: sim double[n_pairs][7] rvec | t | s, R double[n_pairs][9] row-major, status uint8 (ba_sim3_status),
+ * n_inliers, rms_px, best_hyp int32 (the winning hypothesis, -1 when there is none), match_inlier uint8[pair_off[n_pairs]],
+ * hessian double[n_pairs][49].  n_pairs = 0 is a no-op.
+ * Per pair with n correspondences:
+ * (0) x(X) = (X_x / X_z, X_y / X_z); fbar = (fx + fy) / 2, thr = max_px / fbar.  The images are the projections of the points
+ * themselves, x1_k = x(X1_k), x2_k = x(X2_k), as in ORB-SLAM's solver.  A correspondence with a non-finite coordinate or z <= 0 in
+ * its own frame is invalid: never an inlier, it costs 2 thr^2 under every model, and a sample that draws it is void.
+ * (1) n < 4: FEW_MATCHES (three correspondences reproduce themselves); the identity (rvec = t = 0, s = 1, R = I), no inliers, NaN
+ * rms_px, a zero hessian, best_hyp = -1.
+ * (2) Hypothesis h = 0 .. n_hyp - 1 draws three distinct indices with ba_relative_pose's generator, d = 0 .. 2, item = the pair.
+ * A triple with |d12 x d13| <= 1e-6 max |d_ij|^2 in either frame (3D vectors: collinear or coincident) is void.
+ * (3) The closed form of ba_align on the three points with unit weights, fp64, one lane per hypothesis: the centroids mu_a,
+ * mu_b, the centred Sigma = mean (b - mu_b)(a - mu_a)^T = U D V^T (one-sided Jacobi), R = U diag(1, 1, det U det V) V^T with the
+ * third left vector formed as u1 x u2, s = tr(D diag(1, 1, det U det V)) / mean |a - mu_a|^2 (1 when with_scale = 0), t = mu_b - s R
+ * mu_a.  Void when s is not finite or not positive, or the second singular value is <= 1e-12 times the first.
+ * (4) Every model is scored on all n: f = |x(s R X1 + t) - x2|^2, b = |x(R^T (X2 - t) / s) - x1|^2, the cost is the sum of min(f,
+ * thr^2) + min(b, thr^2), a non-positive transformed depth costs thr^2 on its side.  The lowest (cost, h) wins.  Every hypothesis
+ * void: DEGENERATE with the outputs of (1).
+ * (5) lo_rounds times: the consensus set = the valid correspondences with f <= thr^2, b <= thr^2 and both transformed depths
+ * positive at the round's starting model; fewer than three end the rounds.  Then (a) the closed form of (3) on the whole set,
+ * centred before Sigma is formed; it replaces the starting model only if its cost (b) over the set is lower (a void one never
+ * does).  (b) At most refine_iters Marquardt-damped Gauss-Newton steps on 0.5 sum (|r_f|^2 + |r_b|^2) over the set in the seven
+ * local parameters of ba_pose_graph, R <- exp(d omega) R, t <- t + d t, s <- s exp(d sigma) (six without scale: d sigma = 0), both
+ * Jacobians analytic (x does not see the 1 / s of the backward map: r_b does not move with d sigma).  A trial model at which a
+ * transformed depth of a member of the set is not positive is rejected: its cost counts as infinite.  Damping, acceptance and
+ * lambda limits as ba_resect's step (3); |dx| <= 1e-14 ends it; a 7 x 7 Cholesky pivot <= 0 (or a non-finite step): DEGENERATE with
+ * the last accepted model and its measures.
+ * (6) At the final model: match_inlier = the consensus test of (5), n_inliers their count, rms_px = fbar sqrt(mean (f + b) / 2)
+ * over them (NaN without inliers); hessian = fbar^2 J^T J of (5b)'s residuals over the final inliers in (d omega, d t, d sigma),
+ * row-major and bit-symmetric (row and column 6 are zero without scale): the information of the model in pixels^-2, see
+ * posegraph.edge_information; sim's rvec is the log map of R (|rvec| <= pi).
+ * (7) Status: the first failing test in enum order; FEW_INLIERS: n_inliers < min_inliers.
+ * BA_ERR_INVALID, naming the field: K not as in ba_relative_pose, n_pairs outside 0 .. 65535, n_hyp outside 1 .. 4096, lo_rounds < 0,
+ * refine_iters < 0, min_inliers < 0, max_px not > 0, with_scale not 0 or 1, pair_off[0] != 0, a decreasing pair_off.  Results are
+ * bit-reproducible from call to call, and a pair's result depends on its index in the call (the samples) but not on the other
+ * pairs.  Local to the rank. */
+enum ba_sim3_status { BA_SIM3_OK = 0, BA_SIM3_FEW_MATCHES = 1, BA_SIM3_DEGENERATE = 2, BA_SIM3_FEW_INLIERS = 3 };
+typedef struct ba_sim3_options {
+  int32_t  n_hyp;            /* minimal samples per pair, 1 .. 4096; default 256: at an inlier share of 0.5 all of them miss with
+                                probability (1 - 0.5^3)^256 = 1e-15 */
+  int32_t  lo_rounds;        /* rounds of (consensus, closed form, refinement); default 2; 0 = the best raw hypothesis */
+  uint64_t seed;             /* default 0 */
+  double   max_px;           /* threshold on each reprojection error in pixels, > 0; default 4.0 */
+  int32_t  refine_iters;     /* per round; default 20 */
+  int32_t  min_inliers;      /* default 8 */
+  int32_t  with_scale;       /* 1: Sim(3); 0: SE(3), every s exactly 1 (stereo / RGB-D maps); default 1 */
+  int32_t  reserved0;
+} ba_sim3_options;
+int ba_default_sim3_options(ba_sim3_options* opts);   /* 256, 2, 0, 4.0, 20, 8, 1 */
+int ba_sim3(ba_handle* h, const double K[9], int32_t n_pairs, const int64_t* pair_off, const double* X1, const double* X2,
+            const ba_sim3_options* opts, double* sim, double* R, uint8_t* status, int32_t* n_inliers, double* rms_px, int32_t* best_hyp,
+            uint8_t* match_inlier, double* hessian);
 /* Descriptor matching: brute-force Hamming 2-nearest-neighbours of binary descriptors with Lowe's ratio test, the step that
  * produces the matches ba_relative_pose starts from (the reference's BruteForceMatcher.match: cv2.BFMatcher(NORM_HAMMING,
  * crossCheck=False).knnMatch(des1, des2, k=2), then m.distance < 0.75 n.distance).  Needs no ba_set_problem and leaves a resident
