@@ -49,6 +49,7 @@
 #include "ba_orb.hpp"
 #include "ba_posegraph.hpp"
 #include "ba_sim3.hpp"
+#include "ba_fundamental.hpp"
 #include "ba_bow.hpp"
 
 using namespace ba;
@@ -312,6 +313,10 @@ struct ba_handle {
   PairStage s3;                // ba_sim3 (ba_sim3.hpp): pts holds X1 | X2, three doubles per correspondence
   DBuf<double> rp_E;
   DBuf<unsigned> rp_mask;
+  // ba_fundamental (ba_fundamental.hpp): its staging, the pairs' normalisation table, the seven-point slots and masks
+  PairStage fd;
+  DBuf<double> fd_nrm, fd_F;
+  DBuf<unsigned> fd_mask;
   // ba_match_descriptors (ba_match.hpp): staging of the call -- every set's descriptors, the pair table, the splits' (k1, k2),
   // best | second | dist1 | dist2 by row, the good bytes, the per-pair counts
   DBuf<unsigned long long> mt_desc;
@@ -3910,6 +3915,60 @@ extern "C" int ba_sim3(ba_handle* h, const double K[9], int32_t n_pairs, const i
       if (hessian)
         for (int i = 0; i < 7; ++i)
           for (int j = i; j < 7; ++j) hessian[49 * p + 7 * i + j] = hessian[49 * p + 7 * j + i] = r[20 + s3_u7(i, j)];
+    }
+  return BA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- two-view fundamental matrix
+// ba_fundamental (csrc/ba_fundamental.hpp): Hartley normalisation, seven-point hypotheses, scores, local optimisation.  Needs no
+// problem and no K: the shared plumbing runs with K = I, so its thr is max_epi_px and the pixels pass as they are.
+static_assert(FD_OK == BA_FUNDAMENTAL_OK && FD_FEW_MATCHES == BA_FUNDAMENTAL_FEW_MATCHES && FD_DEGENERATE == BA_FUNDAMENTAL_DEGENERATE &&
+              FD_FEW_INLIERS == BA_FUNDAMENTAL_FEW_INLIERS && sizeof(ba_fundamental_options) == 32, "device status codes (ba_fundamental.hpp)");
+extern "C" int ba_default_fundamental_options(ba_fundamental_options* o) {
+  if (!o) return fail(BA_ERR_INVALID, "null argument");
+  memset(o, 0, sizeof *o);
+  o->n_hyp = 1024;
+  o->lo_rounds = 2;
+  o->max_epi_px = 3.0;
+  o->refine_iters = 20;
+  o->min_inliers = 16;
+  return BA_OK;
+}
+extern "C" int ba_fundamental(ba_handle* h, int32_t n_pairs, const int64_t* pair_off, const double* pts1, const double* pts2,
+                              const ba_fundamental_options* opts, double* F, uint8_t* status, int32_t* n_inliers, double* rms_px,
+                              int32_t* best_hyp, uint8_t* match_inlier, double* epipole1, double* epipole2) {
+  if (!h || !opts) return fail(BA_ERR_INVALID, "null argument");
+  static const double KI[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  if (int rc = pairs_check("ba_fundamental", KI, n_pairs, pair_off, pts1, pts2, opts->n_hyp, opts->lo_rounds, opts->refine_iters, opts->min_inliers))
+    return rc;
+  if (!(opts->max_epi_px > 0)) return fail(BA_ERR_INVALID, "ba_fundamental: max_epi_px must be positive");
+  if (n_pairs == 0) return BA_OK;
+  const size_t np = (size_t)n_pairs;
+  const int n_blk = (FD_SLOTS * opts->n_hyp + FD_THREADS - 1) / FD_THREADS;
+  struct { int32_t n_hyp, lo_rounds, refine_iters, min_inliers; uint64_t seed; double max_depth; } o = {
+      opts->n_hyp, opts->lo_rounds, opts->refine_iters, opts->min_inliers, opts->seed, 0.0};   // what pairs_upload reads of a call's options
+  FundArgs a = {};
+  if (int rc = pairs_upload(h, h->fd, KI, n_pairs, pair_off, pts1, pts2, o, opts->max_epi_px, n_blk, FD_BEST, FD_OUT, a)) return rc;
+  HIPCHECK(h->fd_nrm.alloc(FD_NORM * np)); HIPCHECK(h->fd_F.alloc(9 * (size_t)FD_SLOTS * np * opts->n_hyp)); HIPCHECK(h->fd_mask.alloc(np * opts->n_hyp));
+  a.nrm = h->fd_nrm.p; a.F = h->fd_F.p; a.mask = h->fd_mask.p;
+  const dim3 b(FD_THREADS);
+  BA_LAUNCH(k_fund_norm, dim3(n_pairs), b, 0, h->stream, a);
+  BA_LAUNCH(k_fund_solve, dim3(n_pairs, (opts->n_hyp + FD_SOLVE_THREADS - 1) / FD_SOLVE_THREADS), dim3(FD_SOLVE_THREADS), 0, h->stream, a);
+  BA_LAUNCH(k_fund_score, dim3(n_pairs, n_blk), b, 0, h->stream, a);
+  BA_LAUNCH(k_fund_lo, dim3(n_pairs), b, 0, h->stream, a);
+  const bool want = F || status || n_inliers || rms_px || best_hyp || epipole1 || epipole2;
+  std::vector<double> res;
+  if (int rc = pairs_download(h, h->fd, want, FD_OUT, n_pairs, pair_off, match_inlier, res)) return rc;
+  if (want)
+    for (size_t p = 0; p < np; ++p) {
+      const double* r = res.data() + FD_OUT * p;
+      if (F) memcpy(F + 9 * p, r, 9 * sizeof(double));
+      if (status) status[p] = (uint8_t)r[9];
+      if (n_inliers) n_inliers[p] = (int32_t)r[10];
+      if (rms_px) rms_px[p] = r[11];
+      if (best_hyp) best_hyp[p] = (int32_t)r[12];
+      if (epipole1) memcpy(epipole1 + 3 * p, r + 13, 3 * sizeof(double));
+      if (epipole2) memcpy(epipole2 + 3 * p, r + 16, 3 * sizeof(double));
     }
   return BA_OK;
 }

@@ -138,6 +138,17 @@ def match_epipolar(des1, kp1, des2, kp2, K, R, t, max_epi_px=3.0, solver=None, *
     return _good_of_pair(out, 0)
 
 
+def match_by_fundamental(des1, kp1, des2, kp2, F, max_epi_px=3.0, solver=None, **opts):
+    """``match_epipolar`` with a given fundamental matrix (pixels, p2^T F p1 = 0: ``ba_fundamental``'s ``F``) in place of K, R, t:
+    the guided second pass of an uncalibrated pair.  -> (query_idx, train_idx, distance) int64 arrays in query order.  opts:
+    ratio, max_distance, mutual, single.  ``None`` or empty descriptors on either side return no match."""
+    if des1 is None or des2 is None or len(des1) == 0 or len(des2) == 0:
+        return _empty_matches()
+    out = _guided(solver, [_descriptors(des1), _descriptors(des2)], [_positions(kp1), _positions(kp2)],
+                  fundamental=np.asarray(F, dtype=np.float64).reshape(1, 3, 3), max_epi_px=max_epi_px, **opts)
+    return _good_of_pair(out, 0)
+
+
 def match_by_projection(K, R, t, points, point_desc, kp, des, radius_px, image_size=None, solver=None, **opts):
     """Map points matched into an image by projection under a predicted pose (ORB-SLAM's ``SearchByProjection``): point n with
     descriptor ``point_desc[n]`` is projected on the host, x ~ K (R X + t), and only the keypoints within ``radius_px`` (a scalar or

@@ -126,6 +126,11 @@ class BASim3Options(C.Structure):
                 ("refine_iters", C.c_int32), ("min_inliers", C.c_int32), ("with_scale", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class BAFundamentalOptions(C.Structure):
+    _fields_ = [("n_hyp", C.c_int32), ("lo_rounds", C.c_int32), ("seed", C.c_uint64), ("max_epi_px", C.c_double),
+                ("refine_iters", C.c_int32), ("min_inliers", C.c_int32)]
+
+
 class BAMatchOptions(C.Structure):
     _fields_ = [("ratio", C.c_double), ("max_distance", C.c_int32), ("mutual", C.c_int32)]
 
@@ -184,6 +189,7 @@ RESECT_INIT = {"dlt": 0, "current": 1}   # enum ba_resect_init
 RELPOSE_STATUS = {"ok": 0, "few_matches": 1, "degenerate": 2, "behind": 3, "few_inliers": 4, "low_parallax": 5}   # enum ba_relpose_status
 HOMOGRAPHY_STATUS = {"ok": 0, "few_matches": 1, "degenerate": 2, "few_inliers": 3, "rotation": 4, "ambiguous": 5}   # enum ba_homography_status
 SIM3_STATUS = {"ok": 0, "few_matches": 1, "degenerate": 2, "few_inliers": 3}   # enum ba_sim3_status
+FUNDAMENTAL_STATUS = {"ok": 0, "few_matches": 1, "degenerate": 2, "few_inliers": 3}   # enum ba_fundamental_status
 
 
 def resect_init_code(init):
@@ -253,6 +259,9 @@ SYMBOLS = {
     "ba_default_sim3_options": (C.c_int, [C.POINTER(BASim3Options)]),
     "ba_sim3": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.POINTER(C.c_int64), _DP, _DP, C.POINTER(BASim3Options), _DP, _DP,
                           C.POINTER(C.c_uint8), _IP, _DP, _IP, C.POINTER(C.c_uint8), _DP]),
+    "ba_default_fundamental_options": (C.c_int, [C.POINTER(BAFundamentalOptions)]),
+    "ba_fundamental": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _DP, _DP, C.POINTER(BAFundamentalOptions), _DP,
+                                 C.POINTER(C.c_uint8), _IP, _DP, _IP, C.POINTER(C.c_uint8), _DP, _DP]),
     "ba_default_match_options": (C.c_int, [C.POINTER(BAMatchOptions)]),
     "ba_match_descriptors": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.c_int32, _IP, _IP,
                                        C.POINTER(BAMatchOptions), C.POINTER(C.c_int64), _IP, _IP, _IP, _IP, C.POINTER(C.c_uint8), _IP]),
@@ -981,6 +990,31 @@ class Solver:
                                  _dp(out["sim"]), _dp(out["R"]), out["status"].ctypes.data_as(u8), out["n_inliers"].ctypes.data_as(_IP),
                                  _dp(out["rms_px"]), out["best_hyp"].ctypes.data_as(_IP), inl.ctypes.data_as(u8), _dp(out["hessian"])))
         out["t"], out["s"] = out["sim"][:, 3:6].copy(), out["sim"][:, 6].copy()
+        out["match_inlier"] = inl.astype(bool)
+        return out
+
+    def fundamental_options(self, **kw) -> BAFundamentalOptions:
+        """ba_default_fundamental_options overlaid with kw (any ba_fundamental_options field; an unknown one raises TypeError)."""
+        return _options(BAFundamentalOptions, self._lib.ba_default_fundamental_options, kw, names={})
+
+    def fundamental(self, pts1, pts2, pair_off=None, **opts):
+        """ba_fundamental: the fundamental matrix (pixels, p2^T F p1 = 0, unit norm, largest entry positive) of every pair from
+        raw pixel matches of an uncalibrated pair -- n_hyp seven-point samples per pair scored on all of its matches, then
+        lo_rounds of (consensus, refinement).  No K.  pts1 / pts2 / pair_off as ``relative_pose``.  opts: n_hyp, lo_rounds, seed,
+        max_epi_px, refine_iters, min_inliers.  Returns dict(F (P, 3, 3), status (P,) uint8 (FUNDAMENTAL_STATUS), n_inliers,
+        rms_px, best_hyp (P,), match_inlier (n,) bool, epipole1, epipole2 (P, 3): F e1 = 0, F^T e2 = 0, unit homogeneous pixels).
+        A pair without a model has F = 0.  Needs no problem and leaves a resident one as it is."""
+        _, p1, p2, off = _pair_inputs(np.eye(3), pts1, pts2, pair_off)
+        o = self.fundamental_options(**opts)
+        P, n = off.size - 1, p1.shape[0]
+        out = dict(F=np.empty((P, 3, 3)), status=np.empty(P, dtype=np.uint8), n_inliers=np.empty(P, dtype=np.int32), rms_px=np.empty(P),
+                   best_hyp=np.empty(P, dtype=np.int32), epipole1=np.empty((P, 3)), epipole2=np.empty((P, 3)))
+        inl = np.zeros(n, dtype=np.uint8)
+        u8 = C.POINTER(C.c_uint8)
+        _check(self._lib.ba_fundamental(self._h, P, off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(p1), _dp(p2), C.byref(o), _dp(out["F"]),
+                                        out["status"].ctypes.data_as(u8), out["n_inliers"].ctypes.data_as(_IP), _dp(out["rms_px"]),
+                                        out["best_hyp"].ctypes.data_as(_IP), inl.ctypes.data_as(u8), _dp(out["epipole1"]),
+                                        _dp(out["epipole2"])))
         out["match_inlier"] = inl.astype(bool)
         return out
 

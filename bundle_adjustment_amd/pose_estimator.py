@@ -71,6 +71,97 @@ def homography(K, pts1, pts2, solver=None, **opts):
                 t=out["t"][0], normal=out["normal"][0], t_over_d=out["t_over_d"][0], votes=out["votes"][0], pose_cost=out["pose_cost"][0])
 
 
+def fundamental(pts1, pts2, solver=None, **opts):
+    """One pair on arrays: ``hip_backend.Solver.fundamental`` with the leading pair axis removed -- dict(F (3, 3) in pixels
+    (p2^T F p1 = 0), status (int, ``hip_backend.FUNDAMENTAL_STATUS``), n_inliers, rms_px, best_hyp, match_inlier (n,) bool,
+    epipole1, epipole2 (3,)).  No camera matrix is needed.  ``solver`` as ``relative_pose``."""
+    own = solver is None
+    s = hip_backend.Solver(0) if own else solver
+    try:
+        out = s.fundamental(pts1, pts2, **opts)
+    finally:
+        if own:
+            s.close()
+    return dict(F=out["F"][0], status=int(out["status"][0]), n_inliers=int(out["n_inliers"][0]), rms_px=float(out["rms_px"][0]),
+                best_hyp=int(out["best_hyp"][0]), match_inlier=out["match_inlier"], epipole1=out["epipole1"][0], epipole2=out["epipole2"][0])
+
+
+def _skew(v):
+    return np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+
+
+def focal_from_fundamental(F, pp1, pp2):
+    """(f1, f2): the focal lengths of the two views from a fundamental matrix (pixels, p2^T F p1 = 0), for square pixels, no skew
+    and known principal points ``pp1`` / ``pp2`` -- Bougnoux's closed form (1998), numpy on the host: a first focal length for a
+    BAL solve of an uncalibrated pair.  With I~ = diag(1, 1, 0), p_k = (pp_k, 1) and e2 the null vector of F^T,
+    f1^2 = -(p2^T [e2]x I~ F p1)(p1^T F^T p2) / (p2^T [e2]x I~ F I~ F^T p2), and f2^2 is the same expression for F^T with e1 and
+    the roles of p1 and p2 swapped.  NaN where the squared focal length is not positive (noise, or a wrong principal point) or
+    not finite.  Degenerate motions, for which the denominator vanishes and no F determines the focal lengths: optical axes that
+    intersect (a camera turning about a point it looks at, which includes parallel axes under a sideways translation), and a pure
+    translation along the optical axes."""
+    F = np.asarray(F, dtype=np.float64).reshape(3, 3)
+    p1 = np.r_[np.asarray(pp1, dtype=np.float64).reshape(2), 1.0]
+    p2 = np.r_[np.asarray(pp2, dtype=np.float64).reshape(2), 1.0]
+    It = np.diag([1.0, 1.0, 0.0])
+
+    def one(Fm, pa, pb):
+        e = np.linalg.svd(Fm.T)[2][2]                # Fm^T e = 0
+        ex = _skew(e)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            f2 = -(pb @ ex @ It @ Fm @ pa) * (pa @ Fm.T @ pb) / (pb @ ex @ It @ Fm @ It @ Fm.T @ pb)
+        return float(np.sqrt(f2)) if np.isfinite(f2) and f2 > 0.0 else float("nan")
+
+    return one(F, p1, p2), one(F.T, p2, p1)
+
+
+_FUNDAMENTAL_OPTS = ("n_hyp", "lo_rounds", "seed", "refine_iters", "min_inliers", "max_epi_px")
+_PLANE_OPTS = ("n_hyp", "lo_rounds", "seed", "refine_iters", "min_inliers", "max_px")
+
+
+def estimate_uncalibrated(matches, kp1, kp2, solver=None, planar_ratio=0.8, quiet=False, **opts):
+    """Two-view geometry of an UNCALIBRATED pair: ``fundamental`` (``ba_fundamental``) on the matches, and ``homography`` beside it
+    for the degeneracy no fundamental matrix can see -- a plane (or a pure rotation) admits a family of them.
+    -> (F 3 x 3 in pixels, inlier pts1, inlier pts2, inlier indices, info); four ``None`` in front of ``info`` when there is no
+    F (status few_matches, or degenerate with no hypothesis).  ``info``: ``model`` -- "planar" when ``n_inliers_H >= planar_ratio *
+    n_inliers_F`` (COLMAP's planar-or-panoramic rule: F is still returned, it explains the matches, but it is NOT unique and its
+    epipoles mean nothing), else "fundamental" --, ``unique`` (model == "fundamental"), ``fundamental`` and ``homography`` (the two
+    calls' outputs).  The homography runs with K = [f0 0 cx; 0 f0 cy; 0 0 1], f0 = 1000 and (cx, cy) the centroid of both images'
+    matches: its H, n_inliers and match_inlier do not depend on that K beyond rounding; its poses do, and are not returned.
+    ``matches`` / ``kp*`` as ``estimate_pose`` (points are float32 as there).  opts: n_hyp, lo_rounds, seed, refine_iters,
+    min_inliers go to both calls; max_epi_px to the fundamental matrix, max_px to the homography."""
+    for k in opts:
+        if k not in _FUNDAMENTAL_OPTS + _PLANE_OPTS:
+            raise TypeError(f"unknown option {k}")
+    pts1 = np.float32([kp1[m.queryIdx].pt for m in matches]).reshape(-1, 2)
+    pts2 = np.float32([kp2[m.trainIdx].pt for m in matches]).reshape(-1, 2)
+    own = solver is None
+    s = hip_backend.Solver(0) if own else solver
+    try:
+        f = fundamental(pts1, pts2, solver=s, **{k: v for k, v in opts.items() if k in _FUNDAMENTAL_OPTS})
+        centre = np.concatenate([pts1, pts2]).astype(np.float64).mean(axis=0) if len(pts1) else np.zeros(2)
+        K0 = np.array([[1000.0, 0.0, centre[0]], [0.0, 1000.0, centre[1]], [0.0, 0.0, 1.0]])
+        h = homography(K0, pts1, pts2, solver=s, **{k: v for k, v in opts.items() if k in _PLANE_OPTS})
+    finally:
+        if own:
+            s.close()
+    info = dict(model="fundamental", unique=True, fundamental=f, homography=h)
+    st = hip_backend.FUNDAMENTAL_STATUS
+    if f["status"] == st["few_matches"] or (f["status"] == st["degenerate"] and f["best_hyp"] < 0):
+        return None, None, None, None, info
+    if h["best_hyp"] >= 0 and h["n_inliers"] >= planar_ratio * f["n_inliers"]:
+        info.update(model="planar", unique=False)
+    mask = f["match_inlier"]
+    if not quiet:
+        num_matches = len(matches)
+        num_inliers = int(mask.sum())
+        inlier_ratio = num_inliers / num_matches if num_matches > 0 else 0
+        print(f"    -> Two-view model: {info['model']} ({h['n_inliers']} homography inliers, {f['n_inliers']} fundamental)")
+        print(f"    -> Fundamental matrix: {num_inliers} inliers out of {num_matches} matches (Ratio: {inlier_ratio:.2f})")
+        if info["model"] == "planar":
+            print("    -> WARNING: Planar or panoramic pair. The fundamental matrix is not unique.")
+    return np.array(f["F"], dtype=np.float64).reshape(3, 3), pts1[mask], pts2[mask], np.where(mask)[0], info
+
+
 _BOTH = ("n_hyp", "lo_rounds", "seed", "refine_iters", "min_inliers", "max_depth")
 _ESSENTIAL_ONLY = ("max_epi_px", "min_parallax_deg")
 _HOMOGRAPHY_ONLY = ("max_px", "ambiguity_ratio", "min_translation")

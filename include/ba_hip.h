@@ -540,6 +540,73 @@ int ba_default_sim3_options(ba_sim3_options* opts);   /* 256, 2, 0, 4.0, 20, 8, 
 int ba_sim3(ba_handle* h, const double K[9], int32_t n_pairs, const int64_t* pair_off, const double* X1, const double* X2,
             const ba_sim3_options* opts, double* sim, double* R, uint8_t* status, int32_t* n_inliers, double* rms_px, int32_t* best_hyp,
             uint8_t* match_inlier, double* hessian);
+/* Two-view fundamental matrix: the F of raw pixel matches of an UNCALIBRATED pair, a share of which may be wrong -- the one
+ * two-view model that needs no K (cv2.findFundamentalMat(FM_RANSAC); the F half of COLMAP's uncalibrated two-view geometry).
+ * Convention p2^T F p1 = 0 in pixels, what ba_match_guided's epipolar gate takes.  n_pairs, pair_off, pts1, pts2, the staging
+ * buffers on the handle and the rule that no problem is needed or touched are ba_relative_pose's; there is no K.
+ * Outputs, any of them NULL: F double[n_pairs][9] row-major, in PIXELS, unit Frobenius norm, its largest-magnitude entry positive
+ * (the first in row-major order of equal ones); status uint8 (ba_fundamental_status), n_inliers, rms_px, best_hyp int32 (the
+ * winning hypothesis, -1 when there is none), match_inlier uint8[pair_off[n_pairs]], epipole1 and epipole2 double[n_pairs][3]: F
+ * e1 = 0 and F^T e2 = 0, homogeneous pixels at unit length, the largest-magnitude component positive (the first of equal ones;
+ * an epipole at infinity has a third component near 0).  n_pairs = 0 is a no-op.
+ * Per pair with n matches:
+ * (0) n < 8: FEW_MATCHES (seven matches reproduce themselves under up to three F; an eighth chooses).  The row of a pair without
+ * a model, here and in every DEGENERATE below that says so: F = 0 (all nine entries: not a fundamental matrix, where
+ * ba_homography's H = I would be a rank-3 one), n_inliers = 0, rms_px = NaN, best_hyp = -1, epipole1 = epipole2 = 0, no match an
+ * inlier.
+ * (1) Hartley normalisation, per image over ALL n matches: c = the centroid, s = sqrt(2) / mean |p - c|; q = p - c are centred
+ * pixels, x~ = (s q, 1) normalised ones, S = diag(s, s, 1).  A mean distance that is zero or not finite in either image:
+ * DEGENERATE, the row of (0).  Sums in a fixed order, no atomics.
+ * (2) Hypothesis h = 0 .. n_hyp - 1 draws seven distinct indices with ba_relative_pose's generator, d = 0 .. 6, and the same raising
+ * rule.  Seven-point solver, fp64, one lane per hypothesis: the rows kron(x2~, x1~) form A (7 x 9); Gauss-Jordan by rows, the
+ * pivot of row r its largest entry among the columns not used yet (the first of equal ones); a pivot <= 1e-12 times the FIRST
+ * pivot, or not finite, voids the hypothesis (rank below 7).  The pivot column of row r changes places with the column at place
+ * r, which leaves the two free columns at places 7 and 8; they give the null vectors: N_k = 1 at its free column, 0 at the other,
+ * minus the reduced rows' entries at the pivot columns; F1 = N of place 7, F2 = N of place 8.  det(a F1 + (1 - a) F2) = c3 a^3 + c2 a^2 + c1 a + c0 with D = F1 - F2, c0 = det F2, c1 = tr(adj(F2) D), c2 = tr(adj(D)
+ * F2), c3 = det D.  |c3| <= 1e-12 max(|c0|, |c1|, |c2|) (F1 - F2 itself is singular: a root at infinity, the others ill-scaled in
+ * a) or a non-finite coefficient voids the hypothesis.  Its real roots inside the Cauchy bound B = 1 + max |c_i / c3|: the real
+ * critical points (discriminant c2^2 - 3 c3 c1 > 0) split [-B, B] into intervals of which every one with a sign change is bisected
+ * 64 times, then two Newton steps kept inside the bracket.  At most three roots, numbered by ascending a: the slot.  F~ = a F1 +
+ * (1 - a) F2 at unit Frobenius norm; a non-finite entry voids the slot.
+ * (3) Every F~ is scored on all n matches in centred pixels with F_c = S2 F~ S1: the sum of min(d^2, max_epi_px^2), d^2 = (q2^T F_c
+ * q1)^2 / ((F_c q1)_x^2 + (F_c q1)_y^2 + (F_c^T q2)_x^2 + (F_c^T q2)_y^2) (Sampson; it does not change under translation, so it is the
+ * pixel distance), a zero denominator costs max_epi_px^2.  The lowest (cost, 3 h + slot) wins, ties go to the lower key.  Every
+ * slot void: DEGENERATE, the row of (0).
+ * (4) lo_rounds times: the consensus set = the matches with d^2 <= max_epi_px^2 at the round's starting F~ (a zero denominator is
+ * never in, here and in (5)); fewer than 8 end the rounds.  F~ = U diag(d1, d2, d3) V^T (one-sided Jacobi; u3 = u1 x u2, v3 = v1 x v2, so det U = det V = +1), sigma = d2 / d1, and
+ * the model is U diag(1, sigma, 0) V^T (a non-finite entry: DEGENERATE with the round's starting F~ and its measures).  Then at
+ * most refine_iters Marquardt-damped Gauss-Newton steps on 0.5 sum d^2 (signed Sampson distances in centred pixels) over the set
+ * in the seven local parameters of that orthonormal representation, U <- U exp([a]x), V <- V exp([b]x), sigma <- sigma + ds
+ * (ba_relative_pose's chart with the singular-value ratio freed); analytic Jacobian; damping, acceptance and lambda limits as
+ * ba_resect's step (3); |dx| <= 1e-14 ends it; a 7 x 7 Cholesky pivot <= 0 (or a non-finite step): DEGENERATE with the last
+ * accepted model and its measures.  The round ends with F~ = U diag(1, sigma, 0) V^T at unit Frobenius norm.  With lo_rounds = 0
+ * the best raw hypothesis is measured as it is.
+ * (5) At the final F~: match_inlier = d^2 <= max_epi_px^2, n_inliers their count, rms_px = sqrt(mean d^2) over them (NaN without
+ * inliers); F = T2^T F_c T1, T = [1 0 -cx; 0 1 -cy; 0 0 1], normalised and signed as above; the epipoles from F~ = U diag V^T
+ * again: e1 = T1^-1 S1^-1 v3, e2 = T2^-1 S2^-1 u3.
+ * (6) Status: the first failing test in enum order; FEW_INLIERS: n_inliers < min_inliers.
+ * BA_ERR_INVALID, naming the field: n_pairs outside 0 .. 65535, n_hyp outside 1 .. 4096, lo_rounds < 0, max_epi_px not > 0,
+ * refine_iters < 0, min_inliers < 0, pair_off[0] != 0, a decreasing pair_off.  Pixels that are not finite are not refused (the
+ * sibling calls do not either): they make their pair DEGENERATE in step (1).  Results are bit-reproducible from call to call,
+ * and a pair's result depends on its index in the call (the samples) but not on the other pairs.  Local to the rank.
+ * Not offered: adaptive stopping, PROSAC, an eight-point refit, a degeneracy test for planes (run ba_homography beside it:
+ * pose_estimator.estimate_uncalibrated), radial distortion, pose recovery from F. */
+enum ba_fundamental_status { BA_FUNDAMENTAL_OK = 0, BA_FUNDAMENTAL_FEW_MATCHES = 1, BA_FUNDAMENTAL_DEGENERATE = 2,
+                             BA_FUNDAMENTAL_FEW_INLIERS = 3 };
+typedef struct ba_fundamental_options {
+  int32_t  n_hyp;            /* minimal samples per pair, 1 .. 4096; default 1024, not the siblings' 256: a seven-point sample at an
+                                inlier share of 0.5 is clean with probability 0.5^7 = 1 / 128, so all of 256 miss with probability
+                                (1 - 0.5^7)^256 = 0.13, all of 1024 with 3e-4, all of 2048 with 1e-7 */
+  int32_t  lo_rounds;        /* rounds of (consensus, refinement); default 2; 0 = the best raw hypothesis */
+  uint64_t seed;             /* default 0 */
+  double   max_epi_px;       /* Sampson threshold in pixels, > 0; default 3.0 */
+  int32_t  refine_iters;     /* per round; default 20 */
+  int32_t  min_inliers;      /* default 16 */
+} ba_fundamental_options;
+int ba_default_fundamental_options(ba_fundamental_options* opts);   /* 1024, 2, 0, 3.0, 20, 16 */
+int ba_fundamental(ba_handle* h, int32_t n_pairs, const int64_t* pair_off, const double* pts1, const double* pts2,
+                   const ba_fundamental_options* opts, double* F, uint8_t* status, int32_t* n_inliers, double* rms_px, int32_t* best_hyp,
+                   uint8_t* match_inlier, double* epipole1, double* epipole2);
 /* Descriptor matching: brute-force Hamming 2-nearest-neighbours of binary descriptors with Lowe's ratio test, the step that
  * produces the matches ba_relative_pose starts from (the reference's BruteForceMatcher.match: cv2.BFMatcher(NORM_HAMMING,
  * crossCheck=False).knnMatch(des1, des2, k=2), then m.distance < 0.75 n.distance).  Needs no ba_set_problem and leaves a resident
