@@ -33,7 +33,7 @@ constexpr int FD_SOLVE_THREADS = 64;           // hypotheses per workgroup of k_
 constexpr int FD_SLOTS = 3;                    // solutions per hypothesis, numbered by ascending a
 constexpr int FD_BEST = 12;                    // doubles per (pair, score block): cost | key | F~[9] | -
 constexpr int FD_OUT = 20;                     // doubles per pair: F[9] | status n_inliers rms best_hyp | epipole1[3] | epipole2[3] | -
-constexpr int FD_NSUM = S3_NSUM;               // a refinement pass: J^T J (28, packed upper: s3_u7) | g (7) | cost -- solved by s3_step
+constexpr int FD_NSUM = S3_NSUM;               // a refinement pass: J^T J (28, packed upper) | g (7) | cost, as ba_sim3's
 constexpr int FD_NORM = 6;                     // doubles per pair: c1x c1y s1 c2x c2y s2
 constexpr int FD_MODEL = 19;                   // U[9] | V[9] | sigma
 constexpr int FD_MIN_SET = 8;                  // a smaller consensus set ends the rounds: seven matches fit any of three F exactly
@@ -372,7 +372,7 @@ __device__ __forceinline__ void fd_pass(const FundArgs& a, const FdNorm& t, cons
 #pragma unroll
     for (int q = 0; q < 7; ++q) {
 #pragma unroll
-      for (int s2 = q; s2 < 7; ++s2) acc[s3_u7(q, s2)] += J[q] * J[s2];
+      for (int s2 = q; s2 < 7; ++s2) acc[UT(7, q, s2)] += J[q] * J[s2];
       acc[28 + q] += J[q] * r;
     }
     acc[35] += 0.5 * r * r;
@@ -412,7 +412,7 @@ __device__ __forceinline__ void fd_unit_signed(double (&v)[N]) {
 __device__ __forceinline__ void fd_void(double* __restrict__ o, const int status) {
   if (threadIdx.x != 0) return;
   for (int q = 0; q < FD_OUT; ++q) o[q] = 0.0;
-  o[9] = (double)status; o[11] = __longlong_as_double(0x7ff8000000000000ll); o[12] = -1.0;
+  o[9] = (double)status; o[11] = HY_NAN; o[12] = -1.0;
 }
 
 __global__ void __launch_bounds__(FD_THREADS) k_fund_lo(const FundArgs a) {
@@ -422,7 +422,6 @@ __global__ void __launch_bounds__(FD_THREADS) k_fund_lo(const FundArgs a) {
   const long long beg = a.off[pair];
   const int n = (int)(a.off[pair + 1] - beg);
   double* o = a.out + FD_OUT * (size_t)pair;
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
   if (n < 8) { fd_void(o, FD_FEW_MATCHES); return; }   // (workgroup-uniform, like every branch below)
   const FdNorm t = fd_load_norm(a, pair);
   if (!fd_norm_ok(t)) { fd_void(o, FD_DEGENERATE); return; }   // step 1
@@ -473,14 +472,7 @@ __global__ void __launch_bounds__(FD_THREADS) k_fund_lo(const FundArgs a) {
     for (;;) {
       fd_pass(a, t, xt, beg, n, acc, lds);
       if (first || acc[35] <= s_cur[35] * (1.0 + TRK_COST_SLACK)) {   // (workgroup-uniform)
-        __syncthreads();                          // (the readers of s_cur are done)
-        if (tid == 0) {
-#pragma unroll
-          for (int q = 0; q < FD_NSUM; ++q) s_cur[q] = acc[q];
-#pragma unroll
-          for (int q = 0; q < FD_MODEL; ++q) s_x[q] = xt[q];
-        }
-        __syncthreads();
+        hy_keep(s_cur, s_x, acc, xt);
         if (!first) lam = fmax(0.1 * lam, 1e-12);
       } else {
         lam *= 10.0;
@@ -491,7 +483,7 @@ __global__ void __launch_bounds__(FD_THREADS) k_fund_lo(const FundArgs a) {
       double dx[7];
 #pragma unroll
       for (int q = 0; q < FD_NSUM; ++q) acc[q] = s_cur[q];
-      if (!s3_step(acc, lam, 1, dx)) { status = FD_DEGENERATE; break; }
+      if (!lm_step(acc, lam, false, dx)) { status = FD_DEGENERATE; break; }
       double d2 = 0.0;
       bool fin = true;
 #pragma unroll
@@ -517,7 +509,7 @@ __global__ void __launch_bounds__(FD_THREADS) k_fund_lo(const FundArgs a) {
     a.inl[beg + j] = 1;
   }
   rs_block_sums<2>(m2, lds);
-  const double rms = m2[0] > 0.0 ? sqrt(m2[1] / m2[0]) : nan;
+  const double rms = m2[0] > 0.0 ? sqrt(m2[1] / m2[0]) : HY_NAN;
   if (status == FD_OK && m2[0] < (double)a.min_inliers) status = FD_FEW_INLIERS;
   if (tid != 0) return;
   // ---- the pixel F = T2^T F_c T1, T = [1 0 -cx; 0 1 -cy; 0 0 1], at unit norm, its largest entry positive

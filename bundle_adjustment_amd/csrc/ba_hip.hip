@@ -301,22 +301,17 @@ struct ba_handle {
   DBuf<int> rn_cnt;
   DBuf<unsigned char> rn_cons, rn_inl;
   RansacArgs rn_args = {};
-  // ba_relative_pose and ba_homography (PairArgs of ba_hypothesis.hpp): staging of a call -- both views' pixels, the pair
-  // offsets, the score blocks' best models, the per-pair results, consensus and inlier bytes per match; the five-point call's
-  // own: the hypotheses' slots and masks
+  // The pair-shaped calls (HypArgs of ba_hypothesis.hpp): staging of a call -- both views' points (two doubles each, three for
+  // ba_sim3), the pair offsets, the score blocks' best models, the per-pair results, consensus and inlier bytes per match; for
+  // the calls whose hypotheses are solved in a launch of their own (five-point, seven-point): their slots and masks
   struct PairStage {
-    DBuf<double> pts, best, out;
+    DBuf<double> pts, best, out, slots;
     DBuf<long long> off;
     DBuf<unsigned char> cons, inl;
+    DBuf<unsigned> mask;
   };
-  PairStage rp, hg;
-  PairStage s3;                // ba_sim3 (ba_sim3.hpp): pts holds X1 | X2, three doubles per correspondence
-  DBuf<double> rp_E;
-  DBuf<unsigned> rp_mask;
-  // ba_fundamental (ba_fundamental.hpp): its staging, the pairs' normalisation table, the seven-point slots and masks
-  PairStage fd;
-  DBuf<double> fd_nrm, fd_F;
-  DBuf<unsigned> fd_mask;
+  PairStage rp, hg, s3, fd;
+  DBuf<double> fd_nrm;         // ba_fundamental: the pairs' normalisation table
   // ba_match_descriptors (ba_match.hpp): staging of the call -- every set's descriptors, the pair table, the splits' (k1, k2),
   // best | second | dist1 | dist2 by row, the good bytes, the per-pair counts
   DBuf<unsigned long long> mt_desc;
@@ -3687,8 +3682,9 @@ extern "C" int ba_resect_ransac(ba_handle* h, const double* intr, const ba_ransa
   return resect_end(h, h->rn, opts->write_cams, poses, status, n_inliers, rms_px, max_px);
 }
 
-// ------------------------------------------------------------------------------------------------- the two-view calls' plumbing
-// What ba_relative_pose and ba_homography refuse alike; `who` is the call the message names.
+// ------------------------------------------------------------------------------------------------- the pair-shaped calls' plumbing
+// What ba_relative_pose, ba_homography, ba_sim3 and ba_fundamental refuse alike; `who` is the call the message names.  K null: the
+// call has none.
 static int pairs_check(const char* who, const double* K, int32_t n_pairs, const int64_t* pair_off, const double* pts1, const double* pts2,
                        int32_t n_hyp, int32_t lo_rounds, int32_t refine_iters, int32_t min_inliers) {
   if (n_pairs < 0 || n_pairs > 65535) return fail(BA_ERR_INVALID, "%s: n_pairs %d is outside 0 .. 65535", who, n_pairs);
@@ -3696,8 +3692,8 @@ static int pairs_check(const char* who, const double* K, int32_t n_pairs, const 
   if (lo_rounds < 0) return fail(BA_ERR_INVALID, "%s: lo_rounds must not be negative", who);
   if (refine_iters < 0) return fail(BA_ERR_INVALID, "%s: refine_iters must not be negative", who);
   if (min_inliers < 0) return fail(BA_ERR_INVALID, "%s: min_inliers must not be negative", who);
-  if (!(K[0] > 0 && K[4] > 0 && std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) && std::isfinite(K[5])) || K[1] != 0 || K[3] != 0 ||
-      K[6] != 0 || K[7] != 0 || K[8] != 1)
+  if (K && (!(K[0] > 0 && K[4] > 0 && std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) && std::isfinite(K[5])) || K[1] != 0 ||
+            K[3] != 0 || K[6] != 0 || K[7] != 0 || K[8] != 1))
     return fail(BA_ERR_INVALID, "%s: K must be the pinhole matrix [fx 0 cx; 0 fy cy; 0 0 1] with fx, fy > 0", who);
   if (n_pairs == 0) return BA_OK;
   if (!pair_off) return fail(BA_ERR_INVALID, "%s: null pair_off", who);
@@ -3709,29 +3705,39 @@ static int pairs_check(const char* who, const double* K, int32_t n_pairs, const 
   if (pair_off[n_pairs] > 0 && (!pts1 || !pts2)) return fail(BA_ERR_INVALID, "%s: null point arrays", who);
   return BA_OK;
 }
-// The staging of a call (n_pairs > 0) sized and filled, and the shared head of its arguments; max_px: the call's threshold in
-// pixels, best_per / out_per: its doubles per score block / per pair.  o: the call's options, which name these fields alike.
-template <class Opts>
-static int pairs_upload(ba_handle* h, ba_handle::PairStage& st, const double* K, int32_t n_pairs, const int64_t* pair_off, const double* pts1,
-                        const double* pts2, const Opts& o, double max_px, int n_blk, int best_per, int out_per, PairArgs& a) {
+// What the calls' options hold alike, each under its own names; max_px: the call's threshold in pixels
+struct PairOpts { int32_t n_hyp, lo_rounds, refine_iters, min_inliers; uint64_t seed; double max_px; };
+// The staging of a call (n_pairs > 0) sized and filled, and the shared head of its arguments.  K null: fbar = 1.  width: doubles
+// per point (2, or ba_sim3's 3); best_per / out_per: the call's doubles per score block / per pair.  d1 | d2: the two point
+// arrays on the device.
+static int pairs_upload(ba_handle* h, ba_handle::PairStage& st, const double* K, int32_t n_pairs, const int64_t* pair_off, int width,
+                        const double* pts1, const double* pts2, const PairOpts& o, int n_blk, int best_per, int out_per, HypArgs& a,
+                        const double*& d1, const double*& d2) {
   if (set_device(h)) return BA_ERR_HIP;
   const size_t nm = (size_t)pair_off[n_pairs], np = (size_t)n_pairs, nm1 = std::max<size_t>(nm, 1);
-  HIPCHECK(st.pts.alloc(4 * nm1)); HIPCHECK(st.off.alloc(np + 1)); HIPCHECK(st.best.alloc((size_t)best_per * np * n_blk));
+  HIPCHECK(st.pts.alloc(2 * width * nm1)); HIPCHECK(st.off.alloc(np + 1)); HIPCHECK(st.best.alloc((size_t)best_per * np * n_blk));
   HIPCHECK(st.out.alloc((size_t)out_per * np)); HIPCHECK(st.cons.alloc(nm1)); HIPCHECK(st.inl.alloc(nm1));
-  a.fx = K[0]; a.fy = K[4]; a.cx = K[2]; a.cy = K[5];
-  a.fbar = 0.5 * (K[0] + K[4]); a.thr = max_px / a.fbar;
-  a.max_depth = o.max_depth;
+  a.fbar = K ? 0.5 * (K[0] + K[4]) : 1.0; a.thr = o.max_px / a.fbar;
   a.n_hyp = o.n_hyp; a.lo_rounds = o.lo_rounds; a.iters = o.refine_iters; a.min_inliers = o.min_inliers;
   a.n_blk = n_blk; a.seed = o.seed;
-  a.off = st.off.p; a.p1 = (const double2*)st.pts.p; a.p2 = (const double2*)(st.pts.p + 2 * nm1);
-  a.best = st.best.p; a.cons = st.cons.p; a.inl = st.inl.p; a.out = st.out.p;
+  a.off = st.off.p; a.best = st.best.p; a.cons = st.cons.p; a.inl = st.inl.p; a.out = st.out.p;
+  d1 = st.pts.p; d2 = st.pts.p + width * nm1;
   static_assert(sizeof(long long) == sizeof(int64_t), "pair_off is uploaded as it is");
   HIPCHECK(hipMemcpyAsync(st.off.p, pair_off, (np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
   if (nm > 0) {
-    HIPCHECK(hipMemcpyAsync(st.pts.p, pts1, 2 * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemcpyAsync(st.pts.p + 2 * nm1, pts2, 2 * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(st.pts.p, pts1, width * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(st.pts.p + width * nm1, pts2, width * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemsetAsync(st.inl.p, 0, nm, h->stream));
   }
+  return BA_OK;
+}
+// The same for the calls on pixels, with their K (null: fx = fy = 1, cx = cy = 0) and the two views; max_depth is the caller's
+static int pairs_upload(ba_handle* h, ba_handle::PairStage& st, const double* K, int32_t n_pairs, const int64_t* pair_off, const double* pts1,
+                        const double* pts2, const PairOpts& o, int n_blk, int best_per, int out_per, PairArgs& a) {
+  const double *d1, *d2;
+  if (int rc = pairs_upload(h, st, K, n_pairs, pair_off, 2, pts1, pts2, o, n_blk, best_per, out_per, a, d1, d2)) return rc;
+  a.fx = K ? K[0] : 1.0; a.fy = K ? K[4] : 1.0; a.cx = K ? K[2] : 0.0; a.cy = K ? K[5] : 0.0;
+  a.p1 = (const double2*)d1; a.p2 = (const double2*)d2;
   return BA_OK;
 }
 // The pairs' rows of out_per doubles into res (want: the call returns any of them) and match_inlier, and the stream drained
@@ -3772,9 +3778,10 @@ extern "C" int ba_relative_pose(ba_handle* h, const double K[9], int32_t n_pairs
   const size_t np = (size_t)n_pairs;
   const int n_blk = (RP_SLOTS * opts->n_hyp + RP_THREADS - 1) / RP_THREADS;
   RelposeArgs a = {};
-  if (int rc = pairs_upload(h, h->rp, K, n_pairs, pair_off, pts1, pts2, *opts, opts->max_epi_px, n_blk, RP_BEST, RP_OUT, a)) return rc;
-  HIPCHECK(h->rp_E.alloc(9 * (size_t)RP_SLOTS * np * opts->n_hyp)); HIPCHECK(h->rp_mask.alloc(np * opts->n_hyp));
-  a.min_parallax = opts->min_parallax_deg; a.E = h->rp_E.p; a.mask = h->rp_mask.p;
+  const PairOpts o = {opts->n_hyp, opts->lo_rounds, opts->refine_iters, opts->min_inliers, opts->seed, opts->max_epi_px};
+  if (int rc = pairs_upload(h, h->rp, K, n_pairs, pair_off, pts1, pts2, o, n_blk, RP_BEST, RP_OUT, a)) return rc;
+  HIPCHECK(h->rp.slots.alloc(9 * (size_t)RP_SLOTS * np * opts->n_hyp)); HIPCHECK(h->rp.mask.alloc(np * opts->n_hyp));
+  a.max_depth = opts->max_depth; a.min_parallax = opts->min_parallax_deg; a.E = h->rp.slots.p; a.mask = h->rp.mask.p;
   const dim3 b(RP_THREADS);
   BA_LAUNCH(k_relpose_solve, dim3(n_pairs, (opts->n_hyp + RP_TEAMS - 1) / RP_TEAMS), b, 0, h->stream, a);
   BA_LAUNCH(k_relpose_score, dim3(n_pairs, n_blk), b, 0, h->stream, a);
@@ -3828,8 +3835,9 @@ extern "C" int ba_homography(ba_handle* h, const double K[9], int32_t n_pairs, c
   const size_t np = (size_t)n_pairs;
   const int n_blk = (opts->n_hyp + HG_THREADS - 1) / HG_THREADS;
   HomogArgs a = {};
-  if (int rc = pairs_upload(h, h->hg, K, n_pairs, pair_off, pts1, pts2, *opts, opts->max_px, n_blk, HG_BEST, HG_OUT, a)) return rc;
-  a.ambiguity = opts->ambiguity_ratio; a.min_translation = opts->min_translation;
+  const PairOpts o = {opts->n_hyp, opts->lo_rounds, opts->refine_iters, opts->min_inliers, opts->seed, opts->max_px};
+  if (int rc = pairs_upload(h, h->hg, K, n_pairs, pair_off, pts1, pts2, o, n_blk, HG_BEST, HG_OUT, a)) return rc;
+  a.max_depth = opts->max_depth; a.ambiguity = opts->ambiguity_ratio; a.min_translation = opts->min_translation;
   const dim3 b(HG_THREADS);
   BA_LAUNCH(k_homog_score, dim3(n_pairs, n_blk), b, 0, h->stream, a);
   BA_LAUNCH(k_homog_lo, dim3(n_pairs), b, 0, h->stream, a);
@@ -3879,30 +3887,18 @@ extern "C" int ba_sim3(ba_handle* h, const double K[9], int32_t n_pairs, const i
   if (!(opts->max_px > 0)) return fail(BA_ERR_INVALID, "ba_sim3: max_px must be positive");
   if (opts->with_scale != 0 && opts->with_scale != 1) return fail(BA_ERR_INVALID, "ba_sim3: with_scale must be 0 or 1");
   if (n_pairs == 0) return BA_OK;
-  if (set_device(h)) return BA_ERR_HIP;
-  ba_handle::PairStage& st = h->s3;
-  const size_t np = (size_t)n_pairs, nm = (size_t)pair_off[n_pairs], nm1 = std::max<size_t>(nm, 1);
+  const size_t np = (size_t)n_pairs;
   const int n_blk = (opts->n_hyp + S3_THREADS - 1) / S3_THREADS;
-  HIPCHECK(st.pts.alloc(6 * nm1)); HIPCHECK(st.off.alloc(np + 1)); HIPCHECK(st.best.alloc((size_t)S3_BEST * np * n_blk));
-  HIPCHECK(st.out.alloc((size_t)S3_OUT * np)); HIPCHECK(st.cons.alloc(nm1)); HIPCHECK(st.inl.alloc(nm1));
   Sim3Args a = {};
-  a.fbar = 0.5 * (K[0] + K[4]); a.thr = opts->max_px / a.fbar;
-  a.n_hyp = opts->n_hyp; a.lo_rounds = opts->lo_rounds; a.iters = opts->refine_iters; a.min_inliers = opts->min_inliers;
-  a.with_scale = opts->with_scale; a.n_blk = n_blk; a.seed = opts->seed;
-  a.off = st.off.p; a.X1 = st.pts.p; a.X2 = st.pts.p + 3 * nm1;
-  a.best = st.best.p; a.cons = st.cons.p; a.inl = st.inl.p; a.out = st.out.p;
-  HIPCHECK(hipMemcpyAsync(st.off.p, pair_off, (np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-  if (nm > 0) {
-    HIPCHECK(hipMemcpyAsync(st.pts.p, X1, 3 * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemcpyAsync(st.pts.p + 3 * nm1, X2, 3 * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemsetAsync(st.inl.p, 0, nm, h->stream));
-  }
+  const PairOpts o = {opts->n_hyp, opts->lo_rounds, opts->refine_iters, opts->min_inliers, opts->seed, opts->max_px};
+  if (int rc = pairs_upload(h, h->s3, K, n_pairs, pair_off, 3, X1, X2, o, n_blk, S3_BEST, S3_OUT, a, a.X1, a.X2)) return rc;
+  a.with_scale = opts->with_scale;
   const dim3 b(S3_THREADS);
   BA_LAUNCH(k_sim3_score, dim3(n_pairs, n_blk), b, 0, h->stream, a);
   BA_LAUNCH(k_sim3_lo, dim3(n_pairs), b, 0, h->stream, a);
   const bool want = sim || R || status || n_inliers || rms_px || best_hyp || hessian;
   std::vector<double> res;
-  if (int rc = pairs_download(h, st, want, S3_OUT, n_pairs, pair_off, match_inlier, res)) return rc;
+  if (int rc = pairs_download(h, h->s3, want, S3_OUT, n_pairs, pair_off, match_inlier, res)) return rc;
   if (want)
     for (size_t p = 0; p < np; ++p) {
       const double* r = res.data() + S3_OUT * p;
@@ -3914,14 +3910,14 @@ extern "C" int ba_sim3(ba_handle* h, const double K[9], int32_t n_pairs, const i
       if (best_hyp) best_hyp[p] = (int32_t)r[19];
       if (hessian)
         for (int i = 0; i < 7; ++i)
-          for (int j = i; j < 7; ++j) hessian[49 * p + 7 * i + j] = hessian[49 * p + 7 * j + i] = r[20 + s3_u7(i, j)];
+          for (int j = i; j < 7; ++j) hessian[49 * p + 7 * i + j] = hessian[49 * p + 7 * j + i] = r[20 + UT(7, i, j)];
     }
   return BA_OK;
 }
 
 // ------------------------------------------------------------------------------------------------- two-view fundamental matrix
 // ba_fundamental (csrc/ba_fundamental.hpp): Hartley normalisation, seven-point hypotheses, scores, local optimisation.  Needs no
-// problem and no K: the shared plumbing runs with K = I, so its thr is max_epi_px and the pixels pass as they are.
+// problem and no K: thr is max_epi_px and the pixels pass as they are.
 static_assert(FD_OK == BA_FUNDAMENTAL_OK && FD_FEW_MATCHES == BA_FUNDAMENTAL_FEW_MATCHES && FD_DEGENERATE == BA_FUNDAMENTAL_DEGENERATE &&
               FD_FEW_INLIERS == BA_FUNDAMENTAL_FEW_INLIERS && sizeof(ba_fundamental_options) == 32, "device status codes (ba_fundamental.hpp)");
 extern "C" int ba_default_fundamental_options(ba_fundamental_options* o) {
@@ -3938,19 +3934,17 @@ extern "C" int ba_fundamental(ba_handle* h, int32_t n_pairs, const int64_t* pair
                               const ba_fundamental_options* opts, double* F, uint8_t* status, int32_t* n_inliers, double* rms_px,
                               int32_t* best_hyp, uint8_t* match_inlier, double* epipole1, double* epipole2) {
   if (!h || !opts) return fail(BA_ERR_INVALID, "null argument");
-  static const double KI[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-  if (int rc = pairs_check("ba_fundamental", KI, n_pairs, pair_off, pts1, pts2, opts->n_hyp, opts->lo_rounds, opts->refine_iters, opts->min_inliers))
+  if (int rc = pairs_check("ba_fundamental", nullptr, n_pairs, pair_off, pts1, pts2, opts->n_hyp, opts->lo_rounds, opts->refine_iters, opts->min_inliers))
     return rc;
   if (!(opts->max_epi_px > 0)) return fail(BA_ERR_INVALID, "ba_fundamental: max_epi_px must be positive");
   if (n_pairs == 0) return BA_OK;
   const size_t np = (size_t)n_pairs;
   const int n_blk = (FD_SLOTS * opts->n_hyp + FD_THREADS - 1) / FD_THREADS;
-  struct { int32_t n_hyp, lo_rounds, refine_iters, min_inliers; uint64_t seed; double max_depth; } o = {
-      opts->n_hyp, opts->lo_rounds, opts->refine_iters, opts->min_inliers, opts->seed, 0.0};   // what pairs_upload reads of a call's options
   FundArgs a = {};
-  if (int rc = pairs_upload(h, h->fd, KI, n_pairs, pair_off, pts1, pts2, o, opts->max_epi_px, n_blk, FD_BEST, FD_OUT, a)) return rc;
-  HIPCHECK(h->fd_nrm.alloc(FD_NORM * np)); HIPCHECK(h->fd_F.alloc(9 * (size_t)FD_SLOTS * np * opts->n_hyp)); HIPCHECK(h->fd_mask.alloc(np * opts->n_hyp));
-  a.nrm = h->fd_nrm.p; a.F = h->fd_F.p; a.mask = h->fd_mask.p;
+  const PairOpts o = {opts->n_hyp, opts->lo_rounds, opts->refine_iters, opts->min_inliers, opts->seed, opts->max_epi_px};
+  if (int rc = pairs_upload(h, h->fd, nullptr, n_pairs, pair_off, pts1, pts2, o, n_blk, FD_BEST, FD_OUT, a)) return rc;
+  HIPCHECK(h->fd_nrm.alloc(FD_NORM * np)); HIPCHECK(h->fd.slots.alloc(9 * (size_t)FD_SLOTS * np * opts->n_hyp)); HIPCHECK(h->fd.mask.alloc(np * opts->n_hyp));
+  a.nrm = h->fd_nrm.p; a.F = h->fd.slots.p; a.mask = h->fd.mask.p;
   const dim3 b(FD_THREADS);
   BA_LAUNCH(k_fund_norm, dim3(n_pairs), b, 0, h->stream, a);
   BA_LAUNCH(k_fund_solve, dim3(n_pairs, (opts->n_hyp + FD_SOLVE_THREADS - 1) / FD_SOLVE_THREADS), dim3(FD_SOLVE_THREADS), 0, h->stream, a);

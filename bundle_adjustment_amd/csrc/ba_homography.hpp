@@ -168,44 +168,6 @@ __global__ void __launch_bounds__(HG_THREADS) k_homog_score(const HomogArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ LO, measures, decomposition
-// (A + lam diag A) dx = -g, A packed upper 8 x 8 row by row, g at 36; false: a pivot <= 0
-__host__ __device__ constexpr int hg_u8(const int i, const int j) { return i * 8 - i * (i - 1) / 2 + (j - i); }
-__device__ inline bool hg_step(const double (&c)[HG_NSUM], const double lam, double (&dx)[8]) {
-  double L[8][8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    double s = c[hg_u8(j, j)] * (1.0 + lam);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) if (k < j) s -= L[j][k] * L[j][k];
-    if (!(s > 0.0)) return false;
-    const double l = sqrt(s);
-    L[j][j] = l;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) if (i > j) {
-      double t = c[hg_u8(j, i)];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) if (k < j) t -= L[i][k] * L[j][k];
-      L[i][j] = t / l;
-    }
-  }
-  double y[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    double t = -c[36 + i];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) if (k < i) t -= L[i][k] * y[k];
-    y[i] = t / L[i][i];
-  }
-#pragma unroll
-  for (int i = 7; i >= 0; --i) {
-    double t = y[i];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) if (k > i) t -= L[k][i] * dx[k];
-    dx[i] = t / L[i][i];
-  }
-  return true;
-}
-
 // The sums of a refinement pass over the consensus set at H~: the 8 x 8 normal matrix, the gradient and 0.5 sum (|r_f|^2 + |r_b|^2)
 // in the entries p0 .. p7 of D = [p0 p1 p2; p3 p4 p5; p6 p7 -(p0 + p4)].  Forward: d pi(H (I + D) x1~) = J_pi(y) H (D x1~), y = H x1~;
 // backward, to first order: d pi((I - D) z) = -J_pi(z) (D z), z = adj(H) x2~ (any positive multiple of H^-1 x2~ projects alike).
@@ -241,7 +203,7 @@ __device__ __forceinline__ void hg_pass(const HomogArgs& a, const double (&H)[9]
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
 #pragma unroll
-      for (int s2 = q; s2 < 8; ++s2) acc[hg_u8(q, s2)] += (J[0][q] * J[0][s2] + J[1][q] * J[1][s2]) + (J[2][q] * J[2][s2] + J[3][q] * J[3][s2]);
+      for (int s2 = q; s2 < 8; ++s2) acc[UT(8, q, s2)] += (J[0][q] * J[0][s2] + J[1][q] * J[1][s2]) + (J[2][q] * J[2][s2] + J[3][q] * J[3][s2]);
       acc[36 + q] += (J[0][q] * r[0] + J[1][q] * r[1]) + (J[2][q] * r[2] + J[3][q] * r[3]);
     }
     acc[44] += 0.5 * ((r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3]));
@@ -263,10 +225,9 @@ __device__ __forceinline__ void hg_move(const double (&H)[9], const double (&p)[
 // a pair without a homography: H = I, no pose
 __device__ __forceinline__ void hg_void(double* __restrict__ o, const int status) {
   if (threadIdx.x != 0) return;
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
   for (int q = 0; q < HG_OUT; ++q) o[q] = 0.0;
   for (int q = 0; q < 9; ++q) o[q] = o[14 + q] = o[23 + q] = (q % 4 == 0) ? 1.0 : 0.0;
-  o[9] = (double)status; o[11] = nan; o[12] = -1.0; o[48] = nan; o[49] = nan;
+  o[9] = (double)status; o[11] = HY_NAN; o[12] = -1.0; o[48] = HY_NAN; o[49] = HY_NAN;
 }
 
 __global__ void __launch_bounds__(HG_THREADS) k_homog_lo(const HomogArgs a) {
@@ -276,7 +237,6 @@ __global__ void __launch_bounds__(HG_THREADS) k_homog_lo(const HomogArgs a) {
   const long long beg = a.off[pair];
   const int n = (int)(a.off[pair + 1] - beg);
   double* o = a.out + HG_OUT * (size_t)pair;
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
   if (n < 5) { hg_void(o, HG_FEW_MATCHES); return; }   // (workgroup-uniform, like every branch below)
   // the lowest (cost, h) over the score blocks, in block order: the same in every lane
   const double* b = a.best + HG_BEST * (size_t)pair * a.n_blk;
@@ -311,14 +271,7 @@ __global__ void __launch_bounds__(HG_THREADS) k_homog_lo(const HomogArgs a) {
     for (;;) {
       hg_pass(a, Ht, beg, n, acc, lds);
       if (first || acc[44] <= s_cur[44] * (1.0 + TRK_COST_SLACK)) {   // (workgroup-uniform)
-        __syncthreads();                          // (the readers of s_cur are done)
-        if (tid == 0) {
-#pragma unroll
-          for (int q = 0; q < HG_NSUM; ++q) s_cur[q] = acc[q];
-#pragma unroll
-          for (int q = 0; q < 9; ++q) s_x[q] = Ht[q];
-        }
-        __syncthreads();
+        hy_keep(s_cur, s_x, acc, Ht);
         if (!first) lam = fmax(0.1 * lam, 1e-12);
       } else {
         lam *= 10.0;
@@ -329,7 +282,7 @@ __global__ void __launch_bounds__(HG_THREADS) k_homog_lo(const HomogArgs a) {
       double dx[8];
 #pragma unroll
       for (int q = 0; q < HG_NSUM; ++q) acc[q] = s_cur[q];
-      if (!hg_step(acc, lam, dx)) { status = HG_DEGENERATE; break; }
+      if (!lm_step(acc, lam, false, dx)) { status = HG_DEGENERATE; break; }
       double d2 = 0.0;
       bool fin = true;
 #pragma unroll
@@ -353,7 +306,7 @@ __global__ void __launch_bounds__(HG_THREADS) k_homog_lo(const HomogArgs a) {
     a.inl[beg + j] = 1;                           // (read back below by the lane that wrote it: same stride)
   }
   rs_block_sums<2>(m2, lds);
-  const double rms = m2[0] > 0.0 ? a.fbar * sqrt(0.5 * m2[1] / m2[0]) : nan;
+  const double rms = m2[0] > 0.0 ? a.fbar * sqrt(0.5 * m2[1] / m2[0]) : HY_NAN;
   if (status == HG_OK && m2[0] < (double)a.min_inliers) status = HG_FEW_INLIERS;
   // ---- H~ = U diag(d) V^T; the third columns are the cross products of the first two, so det U = det V = +1 and d3 > 0 (det H~ > 0)
   double U[3][3], V[3][3], d[3];
@@ -361,7 +314,7 @@ __global__ void __launch_bounds__(HG_THREADS) k_homog_lo(const HomogArgs a) {
   const double d1 = d[0], d2 = d[1], d3 = d[2];
   const double ratio = (d1 - d3) / d2;
   RpPose P[2];
-  double nv[2][3], vote[2] = {0.0, 0.0}, pcost[2] = {nan, nan}, tod[2] = {0.0, 0.0};
+  double nv[2][3], vote[2] = {0.0, 0.0}, pcost[2] = {HY_NAN, HY_NAN}, tod[2] = {0.0, 0.0};
 #pragma unroll
   for (int k = 0; k < 2; ++k)
 #pragma unroll

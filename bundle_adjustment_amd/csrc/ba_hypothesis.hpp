@@ -1,6 +1,7 @@
-// The hypothesis stage ba_resect_ransac, ba_relative_pose and ba_homography share: which sample a hypothesis
-// draws, which (cost, key) a score block and a call keep, and the two-view calls' common arguments and canonical
-// SVD.  Device code on ba_dpp.hpp and ba_linalg.hpp; the minimal solvers and the score of a model stay in the calls' own headers.
+// The hypothesis stage ba_resect_ransac, ba_relative_pose, ba_homography, ba_sim3 and ba_fundamental share:
+// which sample a hypothesis draws, which (cost, key) a score block and a call keep, how a refinement keeps its accepted trial,
+// and the pair-shaped calls' common arguments and canonical SVD.  Device code on ba_dpp.hpp and ba_linalg.hpp (the damped step
+// lm_step is there); the minimal solvers and the score of a model stay in the calls' own headers.
 //
 // Generator: mix(z) = the splitmix64 finaliser (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB,
 // z ^= z >> 31); draw(d) = mix(mix(mix(mix(seed + G) + item) + h) + (d + 1) G), G the golden-ratio increment of hy_sample, all
@@ -75,21 +76,36 @@ __device__ __forceinline__ int hy_winner(const double* __restrict__ b, const int
   return win;
 }
 
-// ---------------------------------------------------------------------------------------------- the two-view calls
-struct PairArgs {          // what ba_relative_pose and ba_homography pass alike; RelposeArgs and HomogArgs begin with it
-  double fx, fy, cx, cy;   // K
+// The refinement's accepted trial into LDS, where every lane reads it back: the sums of its pass and its model
+template <int NSUM, int NX>
+__device__ __forceinline__ void hy_keep(double (&s_cur)[NSUM], double (&s_x)[NX], const double (&acc)[NSUM], const double (&x)[NX]) {
+  __syncthreads();                                // (the readers of s_cur are done)
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int q = 0; q < NSUM; ++q) s_cur[q] = acc[q];
+#pragma unroll
+    for (int q = 0; q < NX; ++q) s_x[q] = x[q];
+  }
+  __syncthreads();
+}
+
+// ---------------------------------------------------------------------------------------------- the pair-shaped calls
+struct HypArgs {           // what ba_relative_pose, ba_homography, ba_sim3 and ba_fundamental pass alike: the head of their arguments
   double thr, fbar;        // the call's pixel threshold / fbar, fbar = (fx + fy) / 2
-  double max_depth;
   int n_hyp, lo_rounds, iters, min_inliers;
   int n_blk;               // score blocks per pair
   unsigned long long seed;
   const long long* off;    // [pairs + 1]
-  const double2* p1;       // pixels, first / second view
-  const double2* p2;
   double* best;            // the call's record per (pair, score block): cost | key | model
   unsigned char* cons;     // per match: in the consensus set of the round
   unsigned char* inl;      // match_inlier (zeroed before the launch)
   double* out;             // the call's row per pair
+};
+struct PairArgs : HypArgs {   // the two-view calls on pixels: RelposeArgs, HomogArgs and FundArgs begin with it
+  double fx, fy, cx, cy;   // K
+  double max_depth;
+  const double2* p1;       // pixels, first / second view
+  const double2* p2;
 };
 
 __device__ __forceinline__ double2 pv_norm(const PairArgs& a, const double2 p) {

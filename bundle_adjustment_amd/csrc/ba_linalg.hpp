@@ -1,12 +1,56 @@
 // Dense small-matrix helpers of the stand-alone features (triangulation, tracks, similarity, resection): the two Jacobi
-// iterations on register-resident N x N matrices, the rotation log map, the finiteness test.  Every loop bound is a
-// compile-time constant: the matrices stay in registers, no entry is indexed dynamically.
+// iterations on register-resident N x N matrices, the damped Cholesky step of the refinements, the rotation log map, the
+// finiteness test and the quiet NaN.  Every loop bound is a compile-time constant: the matrices stay in registers, no entry is
+// indexed dynamically.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "ba_device.hpp"
 
 namespace ba {
 
 __host__ __device__ __forceinline__ bool sim_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN
+constexpr double HY_NAN = __builtin_nan("");   // the quiet NaN 0x7ff8000000000000: an output without a value
+
+// (A + lam diag A) dx = -g by Cholesky: c holds A packed upper N x N row by row (UT) and g behind it.  hold_last: the last
+// parameter is held, its pivot 1 and its step 0 (its row and column of c are zero).  false: a pivot <= 0
+template <int N, int M>
+__device__ inline bool lm_step(const double (&c)[M], const double lam, const bool hold_last, double (&dx)[N]) {
+  constexpr int G = N * (N + 1) / 2;
+  static_assert(M >= G + N, "c holds the packed matrix and the gradient");
+  double L[N][N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    double s = (j == N - 1 && hold_last) ? 1.0 : c[UT(N, j, j)] * (1.0 + lam);
+#pragma unroll
+    for (int k = 0; k < N; ++k) if (k < j) s -= L[j][k] * L[j][k];
+    if (!(s > 0.0)) return false;
+    const double l = sqrt(s);
+    L[j][j] = l;
+#pragma unroll
+    for (int i = 0; i < N; ++i) if (i > j) {
+      double t = c[UT(N, j, i)];
+#pragma unroll
+      for (int k = 0; k < N; ++k) if (k < j) t -= L[i][k] * L[j][k];
+      L[i][j] = t / l;
+    }
+  }
+  double y[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    double t = -c[G + i];
+#pragma unroll
+    for (int k = 0; k < N; ++k) if (k < i) t -= L[i][k] * y[k];
+    y[i] = t / L[i][i];
+  }
+#pragma unroll
+  for (int i = N - 1; i >= 0; --i) {
+    double t = y[i];
+#pragma unroll
+    for (int k = 0; k < N; ++k) if (k > i) t -= L[k][i] * dx[k];
+    dx[i] = t / L[i][i];
+  }
+  return true;
+}
 
 // cofactors of a packed symmetric 3 x 3: 00 01 02 11 12 22
 __device__ __forceinline__ void sym3_cof(const double (&A)[6], double (&C)[6]) {

@@ -25,6 +25,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ba_linalg.hpp"
 #include "ba_match.hpp"
 
 namespace ba {
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(MT_THREADS) void k_guided_prepare(GuidedArgs a) {
   const int i = blockIdx.y * MT_THREADS + threadIdx.x;
   if (i >= pr.nq) return;
   const long long row = pr.row0 + i;
-  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const double nan = HY_NAN;
   double r0, r1, r2, r3;
   if (a.gate == MG_WINDOW) {
     const double r = (double)a.window[3 * row + 2];
@@ -91,7 +92,7 @@ __device__ __forceinline__ void mg_scan(const GuidedArgs& a, const MatchPair& pr
   const int s = blockIdx.z;
   const int i = blockIdx.y * MT_THREADS + threadIdx.x;
   const bool live = i < pr.nq;
-  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const double nan = HY_NAN;
   unsigned long long q[W];
 #pragma unroll
   for (int w = 0; w < W; ++w) q[w] = live ? a.m.desc[(pr.q0 + i) * W + w] : 0ull;

@@ -538,43 +538,6 @@ __device__ __forceinline__ void rp_tangent(const double (&t)[3], double (&b1)[3]
   b1[0] *= in; b1[1] *= in; b1[2] *= in;
   b2[0] = t[1] * b1[2] - t[2] * b1[1]; b2[1] = t[2] * b1[0] - t[0] * b1[2]; b2[2] = t[0] * b1[1] - t[1] * b1[0];
 }
-// (H + lam diag H) dx = -g, H packed upper 5 x 5 (rows 0 .. 4: 0, 5, 9, 12, 14), g at 15; false: a pivot <= 0
-__host__ __device__ constexpr int rp_u5(const int i, const int j) { return i * 5 - i * (i - 1) / 2 + (j - i); }
-__device__ inline bool rp_step(const double (&c)[RP_NSUM], const double lam, double (&dx)[5]) {
-  double L[5][5];
-#pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    double s = c[rp_u5(j, j)] * (1.0 + lam);
-#pragma unroll
-    for (int k = 0; k < 5; ++k) if (k < j) s -= L[j][k] * L[j][k];
-    if (!(s > 0.0)) return false;
-    const double l = sqrt(s);
-    L[j][j] = l;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) if (i > j) {
-      double t = c[rp_u5(j, i)];
-#pragma unroll
-      for (int k = 0; k < 5; ++k) if (k < j) t -= L[i][k] * L[j][k];
-      L[i][j] = t / l;
-    }
-  }
-  double y[5];
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    double t = -c[15 + i];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) if (k < i) t -= L[i][k] * y[k];
-    y[i] = t / L[i][i];
-  }
-#pragma unroll
-  for (int i = 4; i >= 0; --i) {
-    double t = y[i];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) if (k > i) t -= L[k][i] * dx[k];
-    dx[i] = t / L[i][i];
-  }
-  return true;
-}
 
 // the sums of a refinement pass over the consensus set at the pose p: H, g in the five local parameters (w | tau), and 0.5 sum r^2.
 // With a = R x1~ and c = x2~ x t: num = a.c, E x1~ = t x a, E^T x2~ = R^T c, so the derivatives are cross products per match
@@ -627,7 +590,7 @@ __device__ __forceinline__ void rp_pass(const RelposeArgs& a, const RpPose& p, c
 #pragma unroll
     for (int q = 0; q < 5; ++q) {
 #pragma unroll
-      for (int s2 = q; s2 < 5; ++s2) acc[rp_u5(q, s2)] += J[q] * J[s2];
+      for (int s2 = q; s2 < 5; ++s2) acc[UT(5, q, s2)] += J[q] * J[s2];
       acc[15 + q] += J[q] * r;
     }
     acc[20] += 0.5 * r * r;
@@ -668,18 +631,17 @@ __global__ void __launch_bounds__(RP_THREADS) k_relpose_lo(const RelposeArgs a) 
   const long long beg = a.off[pair];
   const int n = (int)(a.off[pair + 1] - beg);
   double* o = a.out + RP_OUT * (size_t)pair;
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
   RpPose x;
 #pragma unroll
   for (int q = 0; q < 9; ++q) x.R[q] = (q % 4 == 0) ? 1.0 : 0.0;
 #pragma unroll
   for (int q = 0; q < 3; ++q) x.t[q] = 0.0;
-  if (n < 6) { rp_write(o, x, RP_FEW_MATCHES, 0.0, nan, nan, -1); return; }   // (workgroup-uniform, like every branch below)
+  if (n < 6) { rp_write(o, x, RP_FEW_MATCHES, 0.0, HY_NAN, HY_NAN, -1); return; }   // (workgroup-uniform, like every branch below)
   // the lowest (cost, 10 h + slot) over the score blocks, in block order: the same in every lane
   const double* b = a.best + RP_BEST * (size_t)pair * a.n_blk;
   double gc, gk;
   const int win = hy_winner<RP_BEST>(b, a.n_blk, gc, gk);
-  if (!(gc < HY_INF)) { rp_write(o, x, RP_DEGENERATE, 0.0, nan, nan, -1); return; }   // every slot void
+  if (!(gc < HY_INF)) { rp_write(o, x, RP_DEGENERATE, 0.0, HY_NAN, HY_NAN, -1); return; }   // every slot void
   const int best = (int)gk / RP_SLOTS;
   double E[9];
 #pragma unroll
@@ -704,7 +666,7 @@ __global__ void __launch_bounds__(RP_THREADS) k_relpose_lo(const RelposeArgs a) 
       cand[0].t[i] = U[i][2]; cand[1].t[i] = U[i][2];
     }
   }
-  if (status != RP_OK) { rp_write(o, x, RP_DEGENERATE, 0.0, nan, nan, best); return; }
+  if (status != RP_OK) { rp_write(o, x, RP_DEGENERATE, 0.0, HY_NAN, HY_NAN, best); return; }
   // ---- votes of the matches within thr of the winning E
   {
     double vote[4] = {0.0, 0.0, 0.0, 0.0};
@@ -753,7 +715,7 @@ __global__ void __launch_bounds__(RP_THREADS) k_relpose_lo(const RelposeArgs a) 
     for (;;) {
       rp_pass(a, xt, beg, n, acc, lds);
       if (first || acc[20] <= s_cur[20] * (1.0 + TRK_COST_SLACK)) {   // (workgroup-uniform)
-        __syncthreads();                          // (the readers of s_cur are done)
+        __syncthreads();                          // (hy_keep, spelled out: a flat view of RpPose moves this kernel's code)
         if (tid == 0) {
 #pragma unroll
           for (int q = 0; q < RP_NSUM; ++q) s_cur[q] = acc[q];
@@ -773,7 +735,7 @@ __global__ void __launch_bounds__(RP_THREADS) k_relpose_lo(const RelposeArgs a) 
       double dx[5];
 #pragma unroll
       for (int q = 0; q < RP_NSUM; ++q) acc[q] = s_cur[q];
-      if (!rp_step(acc, lam, dx)) { status = RP_DEGENERATE; break; }
+      if (!lm_step(acc, lam, false, dx)) { status = RP_DEGENERATE; break; }
       double d2 = 0.0;
 #pragma unroll
       for (int q = 0; q < 5; ++q) d2 += dx[q] * dx[q];
@@ -806,8 +768,8 @@ __global__ void __launch_bounds__(RP_THREADS) k_relpose_lo(const RelposeArgs a) 
     rs_block_sums<3>(m3, lds);
   }
   const bool any = m3[0] > 0.0;
-  const double rms = any ? a.fbar * sqrt(m3[1] / m3[0]) : nan;
-  const double par = any ? (m3[2] / m3[0]) * 57.29577951308232 : nan;
+  const double rms = any ? a.fbar * sqrt(m3[1] / m3[0]) : HY_NAN;
+  const double par = any ? (m3[2] / m3[0]) * 57.29577951308232 : HY_NAN;
   if (status == RP_OK) {
     if (m3[0] < (double)a.min_inliers) status = RP_FEW_INLIERS;
     else if (a.min_parallax > 0.0 && !(par >= a.min_parallax)) status = RP_LOW_PARALLAX;

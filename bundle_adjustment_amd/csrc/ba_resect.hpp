@@ -223,43 +223,6 @@ __device__ inline bool rs_dlt_pose(const double (&sa)[20], const double (&sb)[20
   return ok;
 }
 
-// (H + lam diag H) dx = -g, H packed upper 6 x 6; false: a pivot <= 0
-__device__ inline bool rs_step(const double (&c)[RS_NSUM], const double lam, double (&dx)[6]) {
-  double L[6][6];
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double s = c[U6(j, j)] * (1.0 + lam);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) if (k < j) s -= L[j][k] * L[j][k];
-    if (!(s > 0.0)) return false;
-    const double l = sqrt(s);
-    L[j][j] = l;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) if (i > j) {
-      double t = c[U6(j, i)];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) if (k < j) t -= L[i][k] * L[j][k];
-      L[i][j] = t / l;
-    }
-  }
-  double y[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double t = -c[21 + i];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) if (k < i) t -= L[i][k] * y[k];
-    y[i] = t / L[i][i];
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double t = y[i];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) if (k > i) t -= L[k][i] * dx[k];
-    dx[i] = t / L[i][i];
-  }
-  return true;
-}
-
 // camera state of the pose x into cam (R | t; the intrinsics of a BAL camera stay) and M
 template <class CM>
 __device__ __forceinline__ void rs_pose(const double (&x)[6], double (&cam)[CM::CAM], double (&M)[9]) {
@@ -324,9 +287,8 @@ __device__ __forceinline__ void rs_pass(const ResectArgs& a, const double (&cam)
 // a camera without a refinement (not selected, or failed before it): the pose x, no measures
 __device__ __forceinline__ void rs_write_unrefined(double* __restrict__ o, const double (&x)[6], const int status) {
   if (threadIdx.x != 0) return;
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
   for (int q = 0; q < 6; ++q) o[q] = x[q];
-  o[6] = (double)status; o[7] = 0.0; o[8] = nan; o[9] = nan;
+  o[6] = (double)status; o[7] = 0.0; o[8] = HY_NAN; o[9] = HY_NAN;
 }
 
 // step 3 from the pose x, which ends as the last accepted one; status becomes DEGENERATE on a failed pivot.  CONS: as rs_pass
@@ -358,7 +320,7 @@ __device__ __forceinline__ void rs_refine(const ResectArgs& a, double (&cam)[CM:
     if (small || it >= a.t.iters) break;
     ++it;
     double dx[6];
-    if (!rs_step(cur, lam, dx)) { status = RS_DEGENERATE; break; }
+    if (!lm_step(cur, lam, false, dx)) { status = RS_DEGENERATE; break; }
     double d2 = 0.0, x2 = 0.0;
 #pragma unroll
     for (int q = 0; q < 6; ++q) { xt[q] = x[q] + dx[q]; d2 += dx[q] * dx[q]; x2 += x[q] * x[q]; }
@@ -394,11 +356,10 @@ __device__ __forceinline__ void rs_finish(const ResectArgs& a, double (&cam)[CM:
   mx_in = rs_block_max(mx_in, lds);
   mx_fr = rs_block_max(mx_fr, lds);
   if (threadIdx.x == 0) {
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
     const bool any_in = m5[2] > 0.0;
     const double cnt = any_in ? m5[2] : m5[0];
-    const double rms = cnt > 0.0 ? sqrt((any_in ? m5[3] : m5[4]) / cnt) : nan;
-    const double emax = cnt > 0.0 ? sqrt(any_in ? mx_in : mx_fr) : nan;
+    const double rms = cnt > 0.0 ? sqrt((any_in ? m5[3] : m5[4]) / cnt) : HY_NAN;
+    const double emax = cnt > 0.0 ? sqrt(any_in ? mx_in : mx_fr) : HY_NAN;
     if (status == RS_OK) {
       if (2.0 * m5[1] > n) status = RS_BEHIND;
       else if (m5[2] < (double)a.min_inliers) status = RS_FEW_INLIERS;

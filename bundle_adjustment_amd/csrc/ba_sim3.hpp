@@ -35,21 +35,11 @@ constexpr int S3_OUT = 48;                     // doubles per pair: rvec t s | R
 constexpr int S3_CORR = 10;                    // doubles of a correspondence in the LDS tile: X1 | X2 | x1 | x2
 static_assert(S3_THREADS == RS_THREADS, "rs_block_sums folds RS_WAVES waves");
 
-struct Sim3Args {
-  double thr, fbar;        // max_px / fbar, fbar = (fx + fy) / 2
-  int n_hyp, lo_rounds, iters, min_inliers, with_scale;
-  int n_blk;               // score blocks per pair
-  unsigned long long seed;
-  const long long* off;    // [pairs + 1]
+struct Sim3Args : HypArgs {   // thr = max_px / fbar; best: S3_BEST doubles per (pair, score block); out: S3_OUT per pair
+  int with_scale;
   const double* X1;        // 3 per correspondence: the point in the first / second camera frame
   const double* X2;
-  double* best;            // S3_BEST per (pair, score block)
-  unsigned char* cons;     // per correspondence: in the consensus set of the round
-  unsigned char* inl;      // match_inlier (zeroed before the launch)
-  double* out;             // S3_OUT per pair
 };
-
-__host__ __device__ constexpr int s3_u7(const int i, const int j) { return i * 7 - i * (i - 1) / 2 + (j - i); }
 
 // correspondence j: both points and their images; false (and NaN images) for a non-finite coordinate or z <= 0 in its own frame
 __device__ __forceinline__ bool s3_load(const Sim3Args& a, const long long j, double (&A)[3], double (&B)[3], double2& x1, double2& x2) {
@@ -57,9 +47,8 @@ __device__ __forceinline__ bool s3_load(const Sim3Args& a, const long long j, do
   for (int k = 0; k < 3; ++k) { A[k] = a.X1[3 * j + k]; B[k] = a.X2[3 * j + k]; }
   const bool ok = sim_finite(A[0]) && sim_finite(A[1]) && sim_finite(A[2]) && sim_finite(B[0]) && sim_finite(B[1]) && sim_finite(B[2]) &&
                   A[2] > 0.0 && B[2] > 0.0;
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  x1 = ok ? make_double2(A[0] / A[2], A[1] / A[2]) : make_double2(nan, nan);
-  x2 = ok ? make_double2(B[0] / B[2], B[1] / B[2]) : make_double2(nan, nan);
+  x1 = ok ? make_double2(A[0] / A[2], A[1] / A[2]) : make_double2(HY_NAN, HY_NAN);
+  x2 = ok ? make_double2(B[0] / B[2], B[1] / B[2]) : make_double2(HY_NAN, HY_NAN);
   return ok;
 }
 __device__ __forceinline__ void s3_identity(double (&M)[S3_MODEL]) {
@@ -209,44 +198,6 @@ __global__ void __launch_bounds__(S3_THREADS) k_sim3_score(const Sim3Args a) {
 }
 
 // ------------------------------------------------------------------------------------------------ LO, measures, Hessian
-// (A + lam diag A) dx = -g, A packed upper 7 x 7 row by row, g at 28; without scale sigma is held: its pivot is 1 and its step 0.
-// false: a pivot <= 0
-__device__ inline bool s3_step(const double (&c)[S3_NSUM], const double lam, const int with_scale, double (&dx)[7]) {
-  double L[7][7];
-#pragma unroll
-  for (int j = 0; j < 7; ++j) {
-    double s = (j == 6 && !with_scale) ? 1.0 : c[s3_u7(j, j)] * (1.0 + lam);
-#pragma unroll
-    for (int k = 0; k < 7; ++k) if (k < j) s -= L[j][k] * L[j][k];
-    if (!(s > 0.0)) return false;
-    const double l = sqrt(s);
-    L[j][j] = l;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) if (i > j) {
-      double t = c[s3_u7(j, i)];
-#pragma unroll
-      for (int k = 0; k < 7; ++k) if (k < j) t -= L[i][k] * L[j][k];
-      L[i][j] = t / l;
-    }
-  }
-  double y[7];
-#pragma unroll
-  for (int i = 0; i < 7; ++i) {
-    double t = -c[28 + i];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) if (k < i) t -= L[i][k] * y[k];
-    y[i] = t / L[i][i];
-  }
-#pragma unroll
-  for (int i = 6; i >= 0; --i) {
-    double t = y[i];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) if (k > i) t -= L[k][i] * dx[k];
-    dx[i] = t / L[i][i];
-  }
-  return true;
-}
-
 // The sums of a refinement pass over the correspondences flagged in `set` at the model M: the 7 x 7 normal matrix, the gradient
 // and 0.5 sum (|r_f|^2 + |r_b|^2) in (omega, tau, sigma); the sigma column is zero without scale.  A member whose transformed
 // depth is not positive at this model makes the cost infinite: leaving it out would lower the cost, and the acceptance test
@@ -290,7 +241,7 @@ __device__ __forceinline__ void s3_pass(const Sim3Args& a, const double (&M)[S3_
 #pragma unroll
     for (int q = 0; q < 7; ++q) {
 #pragma unroll
-      for (int s2 = q; s2 < 7; ++s2) acc[s3_u7(q, s2)] += (J[0][q] * J[0][s2] + J[1][q] * J[1][s2]) + (J[2][q] * J[2][s2] + J[3][q] * J[3][s2]);
+      for (int s2 = q; s2 < 7; ++s2) acc[UT(7, q, s2)] += (J[0][q] * J[0][s2] + J[1][q] * J[1][s2]) + (J[2][q] * J[2][s2] + J[3][q] * J[3][s2]);
       acc[28 + q] += (J[0][q] * r[0] + J[1][q] * r[1]) + (J[2][q] * r[2] + J[3][q] * r[3]);
     }
     acc[35] += 0.5 * ((r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3]));
@@ -349,7 +300,7 @@ __device__ __forceinline__ void s3_void(double* __restrict__ o, const int status
   if (threadIdx.x != 0) return;
   for (int q = 0; q < S3_OUT; ++q) o[q] = 0.0;
   o[6] = 1.0; o[7] = 1.0; o[11] = 1.0; o[15] = 1.0;
-  o[16] = (double)status; o[18] = __longlong_as_double(0x7ff8000000000000ll); o[19] = -1.0;
+  o[16] = (double)status; o[18] = HY_NAN; o[19] = -1.0;
 }
 
 __global__ void __launch_bounds__(S3_THREADS) k_sim3_lo(const Sim3Args a) {
@@ -388,26 +339,10 @@ __global__ void __launch_bounds__(S3_THREADS) k_sim3_lo(const Sim3Args a) {
     double acc[S3_NSUM], Mt[S3_MODEL];
     // the set's sums at the starting model, then (a): the closed form, kept if it lowers the set's cost
     s3_pass(a, M, a.cons, beg, n, acc, lds);
-    __syncthreads();                              // (the readers of s_cur are done)
-    if (tid == 0) {
-#pragma unroll
-      for (int q = 0; q < S3_NSUM; ++q) s_cur[q] = acc[q];
-#pragma unroll
-      for (int q = 0; q < S3_MODEL; ++q) s_x[q] = M[q];
-    }
-    __syncthreads();
+    hy_keep(s_cur, s_x, acc, M);
     if (s3_fit_set(a, beg, n, cn[0], Mt, lds)) {  // (workgroup-uniform: the sums are the same in every lane)
       s3_pass(a, Mt, a.cons, beg, n, acc, lds);
-      if (acc[35] < s_cur[35]) {
-        __syncthreads();
-        if (tid == 0) {
-#pragma unroll
-          for (int q = 0; q < S3_NSUM; ++q) s_cur[q] = acc[q];
-#pragma unroll
-          for (int q = 0; q < S3_MODEL; ++q) s_x[q] = Mt[q];
-        }
-        __syncthreads();
-      }
+      if (acc[35] < s_cur[35]) hy_keep(s_cur, s_x, acc, Mt);
     }
     // (b): ba_resect's step 3 in the seven local parameters; a pass keeps only the trial model and its own sums in registers
     double lam = 1e-4;
@@ -416,7 +351,7 @@ __global__ void __launch_bounds__(S3_THREADS) k_sim3_lo(const Sim3Args a) {
       double dx[7];
 #pragma unroll
       for (int q = 0; q < S3_NSUM; ++q) acc[q] = s_cur[q];
-      if (!s3_step(acc, lam, a.with_scale, dx)) { status = S3_DEGENERATE; break; }
+      if (!lm_step(acc, lam, !a.with_scale, dx)) { status = S3_DEGENERATE; break; }
       double d2 = 0.0;
       bool fin = true;
 #pragma unroll
@@ -428,14 +363,7 @@ __global__ void __launch_bounds__(S3_THREADS) k_sim3_lo(const Sim3Args a) {
       small = sqrt(d2) <= 1e-14;
       s3_pass(a, Mt, a.cons, beg, n, acc, lds);
       if (acc[35] <= s_cur[35] * (1.0 + TRK_COST_SLACK)) {   // (workgroup-uniform)
-        __syncthreads();                          // (the readers of s_cur are done)
-        if (tid == 0) {
-#pragma unroll
-          for (int q = 0; q < S3_NSUM; ++q) s_cur[q] = acc[q];
-#pragma unroll
-          for (int q = 0; q < S3_MODEL; ++q) s_x[q] = Mt[q];
-        }
-        __syncthreads();
+        hy_keep(s_cur, s_x, acc, Mt);
         lam = fmax(0.1 * lam, 1e-12);
       } else {
         lam *= 10.0;
@@ -456,7 +384,7 @@ __global__ void __launch_bounds__(S3_THREADS) k_sim3_lo(const Sim3Args a) {
     a.inl[beg + j] = 1;                           // (read back below by the lane that wrote it: same stride)
   }
   rs_block_sums<2>(m2, lds);
-  const double rms = m2[0] > 0.0 ? a.fbar * sqrt(0.5 * m2[1] / m2[0]) : __longlong_as_double(0x7ff8000000000000ll);
+  const double rms = m2[0] > 0.0 ? a.fbar * sqrt(0.5 * m2[1] / m2[0]) : HY_NAN;
   if (status == S3_OK && m2[0] < (double)a.min_inliers) status = S3_FEW_INLIERS;
   // ---- fbar^2 J^T J of the final inlier set
   double acc[S3_NSUM];

@@ -286,7 +286,7 @@ k_sim_errors(const SimRec* __restrict__ rec, int n, const double* __restrict__ a
              const double* __restrict__ w, double* __restrict__ err, double* __restrict__ part) {
   __shared__ double lds[SIM_WAVES * 2];
   const bool ok = rec->status == SIM_OK;
-  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const double nan = HY_NAN;
   double v[1] = {0.0};
   double m = 0.0;
   for (int i = blockIdx.x * SIM_THREADS + threadIdx.x; i < n; i += gridDim.x * SIM_THREADS) {
@@ -315,7 +315,7 @@ k_sim_errors(const SimRec* __restrict__ rec, int n, const double* __restrict__ a
 // fold of the error pass; a record that is not OK ends as the identity with NaN measures
 __global__ void __launch_bounds__(64) k_sim_finish(const double* __restrict__ part, int n_blocks, int n_used, SimRec* __restrict__ rec) {
   if (threadIdx.x != 0) return;
-  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const double nan = HY_NAN;
   if (rec->status != SIM_OK) {
     rec->s = 1.0;
     for (int j = 0; j < 9; ++j) rec->R[j] = (j % 4 == 0) ? 1.0 : 0.0;

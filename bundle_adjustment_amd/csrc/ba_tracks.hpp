@@ -129,7 +129,7 @@ __device__ __forceinline__ void trk_unit(const double* __restrict__ ctr, int c, 
 template <class CM, int G>
 __device__ __forceinline__ void track_solve(const TrackArgs& a, const int s, const int l, double* __restrict__ stage) {
   const int beg = a.pt_off[s], end = a.pt_off[s + 1], n = end - beg;
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double nan = HY_NAN;
   double* o = a.out + TRK_OUT * (size_t)s;
   double cam[CM::CAM];
   // distinct cameras, mean camera centre

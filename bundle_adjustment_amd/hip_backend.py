@@ -415,10 +415,11 @@ def _dp(a):
     return a.ctypes.data_as(_DP) if a is not None else None
 
 
-def _pair_inputs(K, pts1, pts2, pair_off, width=2):
-    """What ba_relative_pose and ba_homography take of (K, pts1, pts2, pair_off): K (3, 3), the pixels (n, 2) and the offsets
-    (n_pairs + 1,) int64, all contiguous (pair_off None: one pair of all matches).  width = 3: ba_sim3's (n, 3) points."""
-    Km = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
+def _pair_inputs(pts1, pts2, pair_off, K=None, width=2):
+    """What the pair-shaped calls take of (pts1, pts2, pair_off, K): K (3, 3) (None: ba_fundamental has none), the pixels (n, 2)
+    and the offsets (n_pairs + 1,) int64, all contiguous (pair_off None: one pair of all matches).  width = 3: ba_sim3's (n, 3)
+    points."""
+    Km = None if K is None else np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
     p1 = np.ascontiguousarray(pts1, dtype=np.float64).reshape(-1, width)
     p2 = np.ascontiguousarray(pts2, dtype=np.float64).reshape(-1, width)
     if p1.shape[0] != p2.shape[0]:
@@ -427,6 +428,27 @@ def _pair_inputs(K, pts1, pts2, pair_off, width=2):
     if off.size < 1 or (off.size > 1 and off[-1] != p1.shape[0]):
         raise ValueError("pair_off must have n_pairs + 1 entries and end at the number of matches")
     return Km, p1, p2, off
+
+
+_F8, _I4, _U1 = np.float64, np.int32, np.uint8
+_PAIR_PTR = {_F8: _DP, _I4: _IP, _U1: C.POINTER(C.c_uint8)}
+_INLIER = ("match_inlier", (), _U1)
+_PAIR_TAIL = [("status", (), _U1), ("n_inliers", (), _I4), ("rms_px", (), _F8)]   # three outputs every pair-shaped call has in a row
+
+
+def _pair_call(fn, handle, inputs, o, spec):
+    """The C call `fn` of a pair-shaped call on _pair_inputs' tuple and the options o.  spec lists the call's output arguments
+    in its order as (name, shape per pair, dtype), "match_inlier" where the (n,) inlier bytes go.  Returns the outputs by name in
+    that order, match_inlier last and as bool."""
+    Km, p1, p2, off = inputs
+    P = off.size - 1
+    out = {name: np.empty((P,) + shape, dtype=dt) for name, shape, dt in spec if name != "match_inlier"}
+    inl = np.zeros(p1.shape[0], dtype=np.uint8)
+    ptrs = [(inl if name == "match_inlier" else out[name]).ctypes.data_as(_PAIR_PTR[dt]) for name, _, dt in spec]
+    head = (handle,) if Km is None else (handle, _dp(Km))
+    _check(fn(*head, P, off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(p1), _dp(p2), C.byref(o), *ptrs))
+    out["match_inlier"] = inl.astype(bool)
+    return out
 
 
 def _match_inputs(sets, pairs):
@@ -925,19 +947,8 @@ class Solver:
         refine_iters, min_inliers, min_parallax_deg, max_depth.  Returns dict(R (P, 3, 3), t (P, 3), status (P,) uint8
         (RELPOSE_STATUS), n_inliers, rms_px, parallax_deg, best_hyp (P,), match_inlier (n,) bool).  Needs no problem and
         leaves a resident one as it is."""
-        Km, p1, p2, off = _pair_inputs(K, pts1, pts2, pair_off)
-        o = self.relpose_options(**opts)
-        P, n = off.size - 1, p1.shape[0]
-        out = dict(R=np.empty((P, 3, 3)), t=np.empty((P, 3)), status=np.empty(P, dtype=np.uint8), n_inliers=np.empty(P, dtype=np.int32),
-                   rms_px=np.empty(P), parallax_deg=np.empty(P), best_hyp=np.empty(P, dtype=np.int32))
-        inl = np.zeros(n, dtype=np.uint8)
-        u8 = C.POINTER(C.c_uint8)
-        _check(self._lib.ba_relative_pose(self._h, _dp(Km), P, off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(p1), _dp(p2), C.byref(o),
-                                          _dp(out["R"]), _dp(out["t"]), out["status"].ctypes.data_as(u8), out["n_inliers"].ctypes.data_as(_IP),
-                                          _dp(out["rms_px"]), _dp(out["parallax_deg"]), out["best_hyp"].ctypes.data_as(_IP),
-                                          inl.ctypes.data_as(u8)))
-        out["match_inlier"] = inl.astype(bool)
-        return out
+        return _pair_call(self._lib.ba_relative_pose, self._h, _pair_inputs(pts1, pts2, pair_off, K), self.relpose_options(**opts),
+                          [("R", (3, 3), _F8), ("t", (3,), _F8)] + _PAIR_TAIL + [("parallax_deg", (), _F8), ("best_hyp", (), _I4), _INLIER])
 
     def homography_options(self, **kw) -> BAHomographyOptions:
         """ba_default_homography_options overlaid with kw (any ba_homography_options field; an unknown one raises TypeError)."""
@@ -951,21 +962,9 @@ class Solver:
         min_translation.  Returns dict(H (P, 3, 3), status (P,) uint8 (HOMOGRAPHY_STATUS), n_inliers, rms_px, best_hyp, n_pose
         (P,), match_inlier (n,) bool, R (P, 2, 3, 3), t, normal (P, 2, 3), t_over_d, votes, pose_cost (P, 2)).  Needs no problem
         and leaves a resident one as it is."""
-        Km, p1, p2, off = _pair_inputs(K, pts1, pts2, pair_off)
-        o = self.homography_options(**opts)
-        P, n = off.size - 1, p1.shape[0]
-        out = dict(H=np.empty((P, 3, 3)), status=np.empty(P, dtype=np.uint8), n_inliers=np.empty(P, dtype=np.int32), rms_px=np.empty(P),
-                   best_hyp=np.empty(P, dtype=np.int32), n_pose=np.empty(P, dtype=np.int32), R=np.empty((P, 2, 3, 3)), t=np.empty((P, 2, 3)),
-                   normal=np.empty((P, 2, 3)), t_over_d=np.empty((P, 2)), votes=np.empty((P, 2), dtype=np.int32), pose_cost=np.empty((P, 2)))
-        inl = np.zeros(n, dtype=np.uint8)
-        u8 = C.POINTER(C.c_uint8)
-        _check(self._lib.ba_homography(self._h, _dp(Km), P, off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(p1), _dp(p2), C.byref(o),
-                                       _dp(out["H"]), out["status"].ctypes.data_as(u8), out["n_inliers"].ctypes.data_as(_IP),
-                                       _dp(out["rms_px"]), out["best_hyp"].ctypes.data_as(_IP), inl.ctypes.data_as(u8),
-                                       out["n_pose"].ctypes.data_as(_IP), _dp(out["R"]), _dp(out["t"]), _dp(out["normal"]),
-                                       _dp(out["t_over_d"]), out["votes"].ctypes.data_as(_IP), _dp(out["pose_cost"])))
-        out["match_inlier"] = inl.astype(bool)
-        return out
+        return _pair_call(self._lib.ba_homography, self._h, _pair_inputs(pts1, pts2, pair_off, K), self.homography_options(**opts),
+                          [("H", (3, 3), _F8)] + _PAIR_TAIL + [("best_hyp", (), _I4), _INLIER, ("n_pose", (), _I4), ("R", (2, 3, 3), _F8),
+                           ("t", (2, 3), _F8), ("normal", (2, 3), _F8), ("t_over_d", (2,), _F8), ("votes", (2,), _I4), ("pose_cost", (2,), _F8)])
 
     def sim3_options(self, **kw) -> BASim3Options:
         """ba_default_sim3_options overlaid with kw (any ba_sim3_options field; an unknown one raises TypeError)."""
@@ -979,18 +978,10 @@ class Solver:
         (P, 3), s (P,), status (P,) uint8 (SIM3_STATUS), n_inliers, rms_px, best_hyp (P,), match_inlier (n,) bool, hessian
         (P, 7, 7): pixels^-2, in (d omega, d t, d sigma), see posegraph.edge_information).  Needs no problem and leaves a resident
         one as it is."""
-        Km, p1, p2, off = _pair_inputs(K, X1, X2, pair_off, width=3)
-        o = self.sim3_options(**opts)
-        P, n = off.size - 1, p1.shape[0]
-        out = dict(sim=np.empty((P, 7)), R=np.empty((P, 3, 3)), status=np.empty(P, dtype=np.uint8), n_inliers=np.empty(P, dtype=np.int32),
-                   rms_px=np.empty(P), best_hyp=np.empty(P, dtype=np.int32), hessian=np.empty((P, 7, 7)))
-        inl = np.zeros(n, dtype=np.uint8)
-        u8 = C.POINTER(C.c_uint8)
-        _check(self._lib.ba_sim3(self._h, _dp(Km), P, off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(p1), _dp(p2), C.byref(o),
-                                 _dp(out["sim"]), _dp(out["R"]), out["status"].ctypes.data_as(u8), out["n_inliers"].ctypes.data_as(_IP),
-                                 _dp(out["rms_px"]), out["best_hyp"].ctypes.data_as(_IP), inl.ctypes.data_as(u8), _dp(out["hessian"])))
-        out["t"], out["s"] = out["sim"][:, 3:6].copy(), out["sim"][:, 6].copy()
-        out["match_inlier"] = inl.astype(bool)
+        out = _pair_call(self._lib.ba_sim3, self._h, _pair_inputs(X1, X2, pair_off, K, width=3), self.sim3_options(**opts),
+                         [("sim", (7,), _F8), ("R", (3, 3), _F8)] + _PAIR_TAIL + [("best_hyp", (), _I4), _INLIER, ("hessian", (7, 7), _F8)])
+        inl = out.pop("match_inlier")
+        out["t"], out["s"], out["match_inlier"] = out["sim"][:, 3:6].copy(), out["sim"][:, 6].copy(), inl
         return out
 
     def fundamental_options(self, **kw) -> BAFundamentalOptions:
@@ -1004,19 +995,8 @@ class Solver:
         max_epi_px, refine_iters, min_inliers.  Returns dict(F (P, 3, 3), status (P,) uint8 (FUNDAMENTAL_STATUS), n_inliers,
         rms_px, best_hyp (P,), match_inlier (n,) bool, epipole1, epipole2 (P, 3): F e1 = 0, F^T e2 = 0, unit homogeneous pixels).
         A pair without a model has F = 0.  Needs no problem and leaves a resident one as it is."""
-        _, p1, p2, off = _pair_inputs(np.eye(3), pts1, pts2, pair_off)
-        o = self.fundamental_options(**opts)
-        P, n = off.size - 1, p1.shape[0]
-        out = dict(F=np.empty((P, 3, 3)), status=np.empty(P, dtype=np.uint8), n_inliers=np.empty(P, dtype=np.int32), rms_px=np.empty(P),
-                   best_hyp=np.empty(P, dtype=np.int32), epipole1=np.empty((P, 3)), epipole2=np.empty((P, 3)))
-        inl = np.zeros(n, dtype=np.uint8)
-        u8 = C.POINTER(C.c_uint8)
-        _check(self._lib.ba_fundamental(self._h, P, off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(p1), _dp(p2), C.byref(o), _dp(out["F"]),
-                                        out["status"].ctypes.data_as(u8), out["n_inliers"].ctypes.data_as(_IP), _dp(out["rms_px"]),
-                                        out["best_hyp"].ctypes.data_as(_IP), inl.ctypes.data_as(u8), _dp(out["epipole1"]),
-                                        _dp(out["epipole2"])))
-        out["match_inlier"] = inl.astype(bool)
-        return out
+        return _pair_call(self._lib.ba_fundamental, self._h, _pair_inputs(pts1, pts2, pair_off), self.fundamental_options(**opts),
+                          [("F", (3, 3), _F8)] + _PAIR_TAIL + [("best_hyp", (), _I4), _INLIER, ("epipole1", (3,), _F8), ("epipole2", (3,), _F8)])
 
     def match_options(self, **kw) -> BAMatchOptions:
         """ba_default_match_options overlaid with kw (any ba_match_options field; an unknown one raises TypeError)."""

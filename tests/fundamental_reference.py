@@ -11,7 +11,7 @@ import numpy as np
 
 from tests import homography_reference as HG
 from tests import relpose_reference as RP
-from tests.ransac_reference import GOLDEN, mix64, winner  # noqa: F401
+from tests.ransac_reference import sample, winner  # noqa: F401
 
 OK, FEW_MATCHES, DEGENERATE, FEW_INLIERS = range(4)
 K_TEST = RP.K_TEST
@@ -21,17 +21,7 @@ MIN_SET = 8
 
 # ------------------------------------------------------------------------------------------------------------ generator
 def sample7(seed, pair, h, n):
-    """Seven distinct indices in [0, n), n >= 7: ba_relative_pose's generator with d = 0 .. 6."""
-    k = mix64(mix64(mix64(int(seed) + GOLDEN) + int(pair)) + int(h))
-    taken, out = [], []
-    for d in range(7):
-        i = (mix64(k + (d + 1) * GOLDEN) * (n - d)) >> 64
-        for s in sorted(taken):
-            if i >= s:
-                i += 1
-        taken.append(i)
-        out.append(i)
-    return tuple(out)
+    return sample(seed, pair, h, n, 7)
 
 
 # ------------------------------------------------------------------------------------------------------------ geometry

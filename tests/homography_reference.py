@@ -10,7 +10,7 @@ import itertools
 import numpy as np
 
 from tests import relpose_reference as RP
-from tests.ransac_reference import GOLDEN, mix64
+from tests.ransac_reference import sample
 
 OK, FEW_MATCHES, DEGENERATE, FEW_INLIERS, ROTATION, AMBIGUOUS = range(6)
 K_TEST = RP.K_TEST
@@ -23,17 +23,7 @@ MIN_TRANSLATION = 0.024
 
 # ------------------------------------------------------------------------------------------------------------ generator
 def sample4(seed, pair, h, n):
-    """Four distinct indices in [0, n), n >= 4: ba_relative_pose's generator with d = 0 .. 3."""
-    k = mix64(mix64(mix64(int(seed) + GOLDEN) + int(pair)) + int(h))
-    taken, out = [], []
-    for d in range(4):
-        i = (mix64(k + (d + 1) * GOLDEN) * (n - d)) >> 64
-        for s in sorted(taken):
-            if i >= s:
-                i += 1
-        taken.append(i)
-        out.append(i)
-    return tuple(out)
+    return sample(seed, pair, h, n, 4)
 
 
 # ------------------------------------------------------------------------------------------------------------ geometry

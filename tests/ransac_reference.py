@@ -38,20 +38,22 @@ def draw(seed, cam, h, d):
     return mix64(mix64(mix64(mix64(int(seed) + GOLDEN) + int(cam)) + int(h)) + (int(d) + 1) * GOLDEN)
 
 
+def sample(seed, item, h, n, k):
+    """k distinct indices in [0, n), n >= k, of hypothesis h of an item (the camera or the pair): ranges n .. n - k + 1 (index =
+    high word of draw * range), each raised past the indices already taken, in ascending order of those.  A longer sample
+    begins with the shorter one."""
+    out = []
+    for d in range(k):
+        i = (draw(seed, item, h, d) * (n - d)) >> 64
+        for s in sorted(out):
+            if i >= s:
+                i += 1
+        out.append(i)
+    return tuple(out)
+
+
 def sample3(seed, cam, h, n):
-    """Three distinct indices in [0, n), n >= 3: ranges n, n - 1, n - 2 (index = high word of draw * range), each shifted
-    past the indices already taken, in ascending order of those."""
-    i0 = (draw(seed, cam, h, 0) * n) >> 64
-    i1 = (draw(seed, cam, h, 1) * (n - 1)) >> 64
-    i2 = (draw(seed, cam, h, 2) * (n - 2)) >> 64
-    if i1 >= i0:
-        i1 += 1
-    lo, hi = min(i0, i1), max(i0, i1)
-    if i2 >= lo:
-        i2 += 1
-    if i2 >= hi:
-        i2 += 1
-    return i0, i1, i2
+    return sample(seed, cam, h, n, 3)
 
 
 def unit_rays(xy, bal):

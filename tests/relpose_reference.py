@@ -8,7 +8,7 @@ import functools
 
 import numpy as np
 
-from tests.ransac_reference import GOLDEN, mix64, winner
+from tests.ransac_reference import sample, winner
 
 OK, FEW_MATCHES, DEGENERATE, BEHIND, FEW_INLIERS, LOW_PARALLAX = range(6)
 W = np.array([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
@@ -16,17 +16,7 @@ W = np.array([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
 
 # ------------------------------------------------------------------------------------------------------------ generator
 def sample5(seed, pair, h, n):
-    """Five distinct indices in [0, n), n >= 5: ranges n .. n - 4, each raised past the earlier indices in ascending order."""
-    k = mix64(mix64(mix64(int(seed) + GOLDEN) + int(pair)) + int(h))
-    taken, out = [], []
-    for d in range(5):
-        i = (mix64(k + (d + 1) * GOLDEN) * (n - d)) >> 64
-        for s in sorted(taken):
-            if i >= s:
-                i += 1
-        taken.append(i)
-        out.append(i)
-    return tuple(out)
+    return sample(seed, pair, h, n, 5)
 
 
 # ------------------------------------------------------------------------------------------------------------ geometry
