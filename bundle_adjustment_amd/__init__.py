@@ -9,3 +9,4 @@ from .pose_estimator import fundamental as fundamental_matrix  # noqa: F401
 from .features import BruteForceMatcher, ORBExtractor, fundamental, match, match_by_fundamental, match_by_homography, match_by_projection, match_epipolar  # noqa: F401
 from .posegraph import close_loop, loop_measurement  # noqa: F401
 from .place import KeyframeDatabase, Vocabulary, bow_vector, pair_list  # noqa: F401
+from .tracks import build_tracks, chain_edges, observations, to_problem  # noqa: F401

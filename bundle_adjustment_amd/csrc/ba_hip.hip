@@ -51,6 +51,7 @@
 #include "ba_sim3.hpp"
 #include "ba_fundamental.hpp"
 #include "ba_bow.hpp"
+#include "ba_trackbuild.hpp"
 
 using namespace ba;
 
@@ -360,6 +361,12 @@ struct ba_handle {
   DBuf<unsigned long long> bw_ndesc, bw_desc, bw_l;
   DBuf<unsigned char> bw_b;
   int debug_bow_chunk = 0;     // BA_DEBUG_BOW_CHUNK: database vectors per score workgroup instead of BW_CHUNK (tests)
+  // ba_build_tracks (ba_trackbuild.hpp): one arena of ints (edges, parents, images, segments, scans, lists), one of bytes (edge
+  // flags, node status, conflict flags), one of 64-bit words (kp_off, the smallest bad edge, the counters)
+  DBuf<int> tb_i;
+  DBuf<unsigned char> tb_b;
+  DBuf<unsigned long long> tb_l;
+  int debug_track_seg = 0;     // BA_DEBUG_TRACK_SEG: lowers the two segment-class thresholds of ba_build_tracks (tests)
   PinnedStage up;             // pinned arena of a window-sized problem's uploads (ba_set_problem: one copy, k_unpack_problem)
   char* h_small = nullptr;     // k_small_lm's results, host-mapped: ba_summary | int cur | trace records
   char* d_small_host = nullptr;
@@ -514,6 +521,7 @@ static int create_impl(ba_handle* h, int device_id) {
   if (const char* e = getenv("BA_DEBUG_MATCH_SPLITS")) h->debug_match_splits = atoi(e);
   if (const char* e = getenv("BA_DEBUG_PG_SPLITS")) h->debug_pg_splits = atoi(e);
   if (const char* e = getenv("BA_DEBUG_BOW_CHUNK")) h->debug_bow_chunk = atoi(e);
+  if (const char* e = getenv("BA_DEBUG_TRACK_SEG")) h->debug_track_seg = atoi(e);
   return BA_OK;
 }
 extern "C" int ba_destroy(ba_handle* h);
@@ -5287,6 +5295,179 @@ extern "C" int ba_bow_score(ba_handle* h, int32_t nq, const int64_t* q_off, cons
   return BA_OK;
 }
 #undef BA_BY_WORDS
+
+// ------------------------------------------------------------------------ feature tracks
+// ba_build_tracks (csrc/ba_trackbuild.hpp).  Needs no problem.
+extern "C" int ba_default_trackbuild_options(ba_trackbuild_options* o) {
+  if (!o) return fail(BA_ERR_INVALID, "null options");
+  o->min_length = 2; o->conflict = BA_TRACKS_DROP; o->max_rounds = 0; o->reserved = 0;
+  return BA_OK;
+}
+static_assert(TB_DROP == BA_TRACKS_DROP && TB_FIRST == BA_TRACKS_FIRST && TB_IN_TRACK == BA_TRACKBUILD_IN_TRACK &&
+              TB_ISOLATED == BA_TRACKBUILD_ISOLATED && TB_CONFLICT == BA_TRACKBUILD_CONFLICT && TB_SHORT == BA_TRACKBUILD_SHORT,
+              "device codes of ba_build_tracks (ba_trackbuild.hpp)");
+// out[i] = sum of in[0 .. i), out[n] = total, for any n < 2^31: k_scan_* passes of at most 1024 * SETUP_SCAN_BLOCK items, the
+// running total carried into the next pass through its block sums.  in and out are different arrays.
+static int tb_scan(ba_handle* h, const int* in, size_t n, int* bsum, int* out) {
+  const size_t pass = (size_t)1024 * SETUP_SCAN_BLOCK;
+  if (n == 0) { HIPCHECK(hipMemsetAsync(out, 0, sizeof(int), h->stream)); return BA_OK; }
+  for (size_t c0 = 0; c0 < n; c0 += pass) {
+    const int nc = (int)std::min(pass, n - c0), nb = (nc + SETUP_SCAN_BLOCK - 1) / SETUP_SCAN_BLOCK;
+    BA_LAUNCH(k_scan_block_sums, dim3(nb), dim3(1024), 0, h->stream, in + c0, nc, bsum);
+    BA_LAUNCH(k_scan_top, dim3(1), dim3(1024), 0, h->stream, bsum, nb);
+    if (c0 > 0) BA_LAUNCH(k_tb_scan_base, dim3(1), dim3(1024), 0, h->stream, bsum, nb, (const int*)(out + c0));   // = the previous pass's total
+    BA_LAUNCH(k_scan_final, dim3(nb), dim3(1024), 0, h->stream, in + c0, nc, (const int*)bsum, out + c0);
+  }
+  return BA_OK;
+}
+extern "C" int ba_build_tracks(ba_handle* h, int32_t n_images, const int64_t* kp_off, int64_t n_edges, const int32_t* edge_a,
+                               const int32_t* edge_b, const uint8_t* edge_keep, const ba_trackbuild_options* opts, int32_t* node_label,
+                               int32_t* node_track, uint8_t* node_status, int64_t* track_off, int32_t* track_node, int64_t* counts) {
+  if (!h) return fail(BA_ERR_INVALID, "null handle");
+  if (!kp_off) return fail(BA_ERR_INVALID, "ba_build_tracks: kp_off is NULL");
+  if (!opts) return fail(BA_ERR_INVALID, "ba_build_tracks: opts is NULL");
+  if (!node_label) return fail(BA_ERR_INVALID, "ba_build_tracks: node_label is NULL");
+  if (!node_track) return fail(BA_ERR_INVALID, "ba_build_tracks: node_track is NULL");
+  if (!node_status) return fail(BA_ERR_INVALID, "ba_build_tracks: node_status is NULL");
+  if (!track_off) return fail(BA_ERR_INVALID, "ba_build_tracks: track_off is NULL");
+  if (!track_node) return fail(BA_ERR_INVALID, "ba_build_tracks: track_node is NULL");
+  if (!counts) return fail(BA_ERR_INVALID, "ba_build_tracks: counts is NULL");
+  if (n_images < 0) return fail(BA_ERR_INVALID, "ba_build_tracks: n_images %d is negative", n_images);
+  if (n_edges < 0 || n_edges > (1LL << 36)) return fail(BA_ERR_INVALID, "ba_build_tracks: n_edges %lld is outside 0 .. 2^36", (long long)n_edges);
+  if (n_edges > 0 && !edge_a) return fail(BA_ERR_INVALID, "ba_build_tracks: edge_a is NULL");
+  if (n_edges > 0 && !edge_b) return fail(BA_ERR_INVALID, "ba_build_tracks: edge_b is NULL");
+  if (kp_off[0] != 0) return fail(BA_ERR_INVALID, "ba_build_tracks: kp_off must start at 0, not %lld", (long long)kp_off[0]);
+  for (int32_t i = 0; i < n_images; ++i)
+    if (kp_off[i + 1] < kp_off[i]) return fail(BA_ERR_INVALID, "ba_build_tracks: kp_off decreases at image %d", i);
+  if (kp_off[n_images] > 0x7fffffffLL) return fail(BA_ERR_INVALID, "ba_build_tracks: kp_off: N = %lld nodes is above 2^31 - 1", (long long)kp_off[n_images]);
+  if (opts->min_length < 2) return fail(BA_ERR_INVALID, "ba_build_tracks: min_length %d is below 2", opts->min_length);
+  if (opts->conflict != BA_TRACKS_DROP && opts->conflict != BA_TRACKS_FIRST)
+    return fail(BA_ERR_INVALID, "ba_build_tracks: conflict %d is neither BA_TRACKS_DROP (0) nor BA_TRACKS_FIRST (1)", opts->conflict);
+  if (opts->max_rounds < 0) return fail(BA_ERR_INVALID, "ba_build_tracks: max_rounds %d is negative", opts->max_rounds);
+  const size_t N = (size_t)kp_off[n_images], E = (size_t)n_edges, H = N / 2 + 2, ni = (size_t)n_images;
+  const int n = (int)N;
+  memset(counts, 0, 8 * sizeof(int64_t));
+  track_off[0] = 0;
+  if (N == 0 && E == 0) return BA_OK;
+  if (set_device(h)) return BA_ERR_HIP;
+  // two rounds do it (ba_trackbuild.hpp: a lane leaves the first hook round only with its edge's ends in one tree); the cap is a
+  // net far above that, ceil(log2 max(N, 2)) + 2
+  int cap = 2;
+  while (cap - 2 < 31 && ((size_t)1 << (cap - 2)) < std::max<size_t>(N, 2)) ++cap;
+  if (opts->max_rounds > 0) cap = opts->max_rounds;
+  // ints: ea | eb | parent | img | cnt | fill | seg_len (later: out) | seg_off (later: pos) [N + 1] | is_comp | comp_id [N + 1] | seg |
+  //       sorted | node_track | track_node (twelve of N, two with one more) | seven arrays of H: comp_root, comp_off, n_conf, is_track, trk_id, big, giant | track_off [H] |
+  //       bsum [1026] | flag | lists [2]
+  HIPCHECK(h->tb_i.alloc(2 * E + 12 * N + 2 + 8 * H + 1026 + 3));
+  HIPCHECK(h->tb_b.alloc(2 * E + 2 * N + 1));
+  HIPCHECK(h->tb_l.alloc(ni + 1 + 8));
+  int* p = h->tb_i.p;
+  int* d_ea = p; p += E; int* d_eb = p; p += E;
+  int* d_parent = p; p += N; int* d_img = p; p += N; int* d_cnt = p; p += N; int* d_fill = p; p += N;
+  int* d_seglen = p; p += N; int* d_segoff = p; p += N + 1; int* d_iscomp = p; p += N; int* d_compid = p; p += N + 1;
+  int* d_seg = p; p += N; int* d_sorted = p; p += N; int* d_ntrack = p; p += N; int* d_tnode = p; p += N;
+  int* d_croot = p; p += H; int* d_coff = p; p += H; int* d_nconf = p; p += H; int* d_istrack = p; p += H; int* d_trkid = p; p += H;
+  int* d_big = p; p += H; int* d_giant = p; p += H; int* d_toff = p; p += H;
+  int* d_bsum = p; p += 1026; int* d_flag = p; p += 1; int* d_lists = p; p += 2;
+  int* d_out = d_seglen; int* d_pos = d_segoff;
+  unsigned char* d_keep = h->tb_b.p; unsigned char* d_use = d_keep + E; unsigned char* d_status = d_use + E; unsigned char* d_conf = d_status + N;
+  long long* d_kpoff = (long long*)h->tb_l.p;
+  unsigned long long* d_stat = h->tb_l.p + ni + 1;       // [0] smallest bad edge, [3 .. 5] k_tb_comp_verdict, [6] same-image edges
+  auto grid = [](size_t items) { return dim3((unsigned)((items + TB_THREADS - 1) / TB_THREADS)); };
+  HIPCHECK(hipMemcpyAsync(d_kpoff, kp_off, (ni + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemsetAsync(d_stat, 0, 8 * sizeof(unsigned long long), h->stream));
+  HIPCHECK(hipMemsetAsync(d_stat, 0xff, sizeof(unsigned long long), h->stream));
+  if (N > 0) BA_LAUNCH(k_tb_init, grid(N), dim3(TB_THREADS), 0, h->stream, n, (const long long*)d_kpoff, n_images, d_parent, d_img, d_ntrack, d_status);
+  int rounds = 0;
+  if (E > 0) {
+    HIPCHECK(hipMemcpyAsync(d_ea, edge_a, E * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(d_eb, edge_b, E * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if (edge_keep) HIPCHECK(hipMemcpyAsync(d_keep, edge_keep, E, hipMemcpyHostToDevice, h->stream));
+    BA_LAUNCH(k_tb_edges, grid(E), dim3(TB_THREADS), 0, h->stream, (const int*)d_ea, (const int*)d_eb, (const unsigned char*)(edge_keep ? d_keep : nullptr),
+              (long long)E, n, (const int*)d_img, d_use, d_stat, d_stat + 6);
+    unsigned long long bad = 0;
+    HIPCHECK(hipMemcpyAsync(&bad, d_stat, sizeof bad, hipMemcpyDeviceToHost, h->stream));
+    BA_SYNC(h);
+    if (bad != ~0ULL)
+      return fail(BA_ERR_INVALID, "ba_build_tracks: edge %llu: edge_a = %d, edge_b = %d is outside 0 .. N - 1 = %d", bad, edge_a[bad], edge_b[bad], n - 1);
+    for (;;) {
+      if (rounds == cap)
+        return fail(BA_ERR_INTERNAL, "ba_build_tracks: BA_ERR_INTERNAL: max_rounds: the components of %d nodes were not finished after %d hook rounds", n, cap);
+      int differed = 0;
+      HIPCHECK(hipMemsetAsync(d_flag, 0, sizeof(int), h->stream));
+      BA_LAUNCH(k_tb_hook, grid(E), dim3(TB_THREADS), 0, h->stream, (const int*)d_ea, (const int*)d_eb, (const unsigned char*)d_use, (long long)E, d_parent, d_flag);
+      ++rounds;
+      HIPCHECK(hipMemcpyAsync(&differed, d_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+      BA_SYNC(h);
+      if (!differed) break;                    // no link was made in this round: the trees are the stars the last compress left
+      BA_LAUNCH(k_tb_compress, grid(N), dim3(TB_THREADS), 0, h->stream, n, d_parent);
+    }
+  }
+  int M = 0, C = 0, T = 0, members = 0;
+  if (N > 0) {
+    const int* label = d_parent;
+    HIPCHECK(hipMemsetAsync(d_cnt, 0, 2 * N * sizeof(int), h->stream));        // cnt | fill
+    BA_LAUNCH(k_tb_sizes, grid(N), dim3(TB_THREADS), 0, h->stream, n, label, d_cnt);
+    BA_LAUNCH(k_tb_roots, grid(N), dim3(TB_THREADS), 0, h->stream, n, label, (const int*)d_cnt, d_seglen, d_iscomp);
+    if (int rc = tb_scan(h, d_seglen, N, d_bsum, d_segoff)) return rc;
+    if (int rc = tb_scan(h, d_iscomp, N, d_bsum, d_compid)) return rc;
+    HIPCHECK(hipMemcpyAsync(&M, d_segoff + N, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipMemcpyAsync(&C, d_compid + N, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    BA_SYNC(h);
+  }
+  if (C > 0) {
+    const int* label = d_parent;
+    const size_t Ms = (size_t)M, Cs = (size_t)C;
+    const int wave_max = h->debug_track_seg > 0 ? std::max(1, std::min(TB_WAVE_MAX, h->debug_track_seg / 2)) : TB_WAVE_MAX;
+    const int lds_max = h->debug_track_seg > 0 ? std::max(wave_max, std::min(TB_LDS_MAX, h->debug_track_seg)) : TB_LDS_MAX;
+    BA_LAUNCH(k_tb_comp_list, grid(N), dim3(TB_THREADS), 0, h->stream, n, (const int*)d_iscomp, (const int*)d_compid, (const int*)d_segoff, d_croot, d_coff);
+    BA_LAUNCH(k_tb_scatter, grid(N), dim3(TB_THREADS), 0, h->stream, n, label, (const int*)d_cnt, (const int*)d_segoff, lds_max, d_fill, d_seg);
+    HIPCHECK(hipMemsetAsync(d_lists, 0, 2 * sizeof(int), h->stream));
+    HIPCHECK(hipMemsetAsync(d_nconf, 0, Cs * sizeof(int), h->stream));
+    const unsigned sort_grid = (unsigned)std::min<size_t>(Cs, TB_SORT_GRID);
+    BA_LAUNCH(k_tb_sort_wave, dim3((unsigned)((Cs + TB_THREADS / 64 - 1) / (TB_THREADS / 64))), dim3(TB_THREADS), 0, h->stream, C, (const int*)d_coff,
+              (const int*)d_seg, d_sorted, wave_max, lds_max, d_big, d_giant, d_lists);
+    BA_LAUNCH(k_tb_sort_lds, dim3(sort_grid), dim3(TB_THREADS), 0, h->stream, (const int*)d_big, (const int*)d_lists, (const int*)d_coff, (const int*)d_seg, d_sorted);
+    int n_giant = 0;
+    HIPCHECK(hipMemcpyAsync(&n_giant, d_lists + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    BA_SYNC(h);
+    for (int g = 0; g < n_giant; ++g) {        // (d_out and d_pos are free here: seg_len and seg_off have been used up)
+      BA_LAUNCH(k_tb_giant_flags, grid(N), dim3(TB_THREADS), 0, h->stream, n, label, (const int*)(d_giant + g), (const int*)d_croot, d_out);
+      if (int rc = tb_scan(h, d_out, N, d_bsum, d_pos)) return rc;
+      BA_LAUNCH(k_tb_giant_place, grid(N), dim3(TB_THREADS), 0, h->stream, n, (const int*)d_out, (const int*)d_pos, (const int*)(d_giant + g), (const int*)d_coff,
+                d_sorted);
+    }
+    BA_LAUNCH(k_tb_conflict, grid(Ms), dim3(TB_THREADS), 0, h->stream, M, (const int*)d_sorted, label, (const int*)d_compid, (const int*)d_coff, (const int*)d_img,
+              d_conf, d_nconf);
+    BA_LAUNCH(k_tb_comp_verdict, grid(Cs), dim3(TB_THREADS), 0, h->stream, C, (const int*)d_coff, (const int*)d_nconf, (int)opts->conflict, (int)opts->min_length,
+              d_istrack, d_stat);
+    if (int rc = tb_scan(h, d_istrack, Cs, d_bsum, d_trkid)) return rc;
+    BA_LAUNCH(k_tb_out_flags, grid(Ms), dim3(TB_THREADS), 0, h->stream, M, (const int*)d_sorted, label, (const int*)d_compid, (const int*)d_istrack,
+              (const unsigned char*)d_conf, d_out);
+    if (int rc = tb_scan(h, d_out, Ms, d_bsum, d_pos)) return rc;
+    BA_LAUNCH(k_tb_emit, grid(Ms), dim3(TB_THREADS), 0, h->stream, M, (const int*)d_sorted, label, (const int*)d_compid, (const int*)d_coff, (const int*)d_istrack,
+              (const int*)d_trkid, (const int*)d_nconf, (const unsigned char*)d_conf, (const int*)d_pos, (int)opts->conflict, d_tnode, d_toff, d_ntrack, d_status);
+    HIPCHECK(hipMemcpyAsync(&T, d_trkid + C, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipMemcpyAsync(&members, d_pos + M, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    BA_SYNC(h);
+  }
+  unsigned long long stat[8] = {};
+  std::vector<int32_t> toff((size_t)T);
+  HIPCHECK(hipMemcpyAsync(stat, d_stat, sizeof stat, hipMemcpyDeviceToHost, h->stream));
+  if (N > 0) {
+    HIPCHECK(hipMemcpyAsync(node_label, d_parent, N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipMemcpyAsync(node_track, d_ntrack, N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipMemcpyAsync(node_status, d_status, N, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (T > 0) HIPCHECK(hipMemcpyAsync(toff.data(), d_toff, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (members > 0) HIPCHECK(hipMemcpyAsync(track_node, d_tnode, (size_t)members * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  BA_SYNC(h);
+  for (int t = 0; t < T; ++t) track_off[t] = toff[t];
+  track_off[T] = members;
+  counts[0] = T; counts[1] = members; counts[2] = C; counts[3] = (int64_t)stat[3]; counts[4] = (int64_t)stat[4]; counts[5] = (int64_t)stat[5];
+  counts[6] = (int64_t)stat[6]; counts[7] = rounds;
+  return BA_OK;
+}
 
 // ------------------------------------------------------------------------ bench hook
 extern "C" int ba_time_kernel(ba_handle* h, int slot, int reps, double* mean_us) {

@@ -149,7 +149,16 @@ class BAVocabOptions(C.Structure):
     _fields_ = [("branching", C.c_int32), ("levels", C.c_int32), ("iters", C.c_int32), ("min_split", C.c_int32), ("seed", C.c_uint64)]
 
 
+class BATrackBuildOptions(C.Structure):
+    _fields_ = [("min_length", C.c_int32), ("conflict", C.c_int32), ("max_rounds", C.c_int32), ("reserved", C.c_int32)]
+
+
 GATE = {"window": 1, "epipolar": 2}   # enum BA_GATE_*
+TRACKBUILD_CONFLICT = {"drop": 0, "first": 1}   # enum BA_TRACKS_*
+TRACKBUILD_STATUS = {"in_track": 0, "isolated": 1, "conflict": 2, "short": 3}   # enum ba_trackbuild_status
+# ba_build_tracks' counts, in order
+TRACKBUILD_COUNTS = ("tracks", "members", "components", "conflict_components", "conflict_nodes", "short_components", "same_image_edges",
+                     "rounds")
 BOW_WEIGHTING = {"tf_idf": 0, "tf": 1}   # enum BA_BOW_*
 # place recognition (csrc/ba_bow.hpp): the unit of a vector entry, the unit of idf_q, the most rows of a set in bow_transform,
 # the most training rows (exclusive), the database vectors per score workgroup, the largest top_k, branching and depth
@@ -296,6 +305,10 @@ SYMBOLS = {
                                    C.POINTER(C.c_int64), _IP, _IP]),
     "ba_bow_score": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _IP, _IP, C.c_int32, C.POINTER(C.c_int64), _IP, _IP, _IP,
                                C.c_int32, _IP, _IP, _IP]),
+    "ba_default_trackbuild_options": (C.c_int, [C.POINTER(BATrackBuildOptions)]),
+    "ba_build_tracks": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int64, _IP, _IP, C.POINTER(C.c_uint8),
+                                  C.POINTER(BATrackBuildOptions), _IP, _IP, C.POINTER(C.c_uint8), C.POINTER(C.c_int64), _IP,
+                                  C.POINTER(C.c_int64)]),
     "ba_get_trace": (C.c_int, [C.c_void_p, C.POINTER(BAIterRecord), C.c_int32, C.POINTER(C.c_int32)]),
     "ba_get_stat": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
     "ba_debug_occupy": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double]),
@@ -488,6 +501,21 @@ def _match_outputs(P, rows):
 def vocab_options(**kw) -> BAVocabOptions:
     """ba_default_vocab_options overlaid with kw (any ba_vocab_options field; an unknown one raises TypeError).  No GPU."""
     return _options(BAVocabOptions, load_library().ba_default_vocab_options, kw, names={})
+
+
+def _node_array(x, name):
+    """Node numbers as a contiguous int32 (n,) array.  A value that does not fit int32 raises ValueError naming the edge: narrowing
+    would wrap it into a valid node (2^32 + 5 -> 5) that the library's range check could not tell from a real one."""
+    x = np.asarray(x).reshape(-1)
+    if x.dtype == np.int32:
+        return np.ascontiguousarray(x)
+    if x.size and not np.issubdtype(x.dtype, np.integer):
+        raise ValueError(f"{name} must hold integers, not {x.dtype}")
+    wide = x.astype(np.int64) if x.dtype != np.uint64 else x
+    bad = np.nonzero((wide < -(1 << 31)) | (wide > (1 << 31) - 1))[0] if x.size else ()
+    if len(bad):
+        raise ValueError(f"{name}[{int(bad[0])}] = {int(wide[bad[0]])} is not a node number: it does not fit int32")
+    return np.ascontiguousarray(wide, dtype=np.int32)
 
 
 def _bow_sets(sets, width=None):
@@ -1202,6 +1230,46 @@ class Solver:
                                       None if end is None else end.ctypes.data_as(_IP), top_k, out["top_idx"].ctypes.data_as(_IP),
                                       out["top_score"].ctypes.data_as(_IP), out["score"].ctypes.data_as(_IP) if dense else None))
         return out
+
+    def build_tracks(self, kp_counts, edge_a, edge_b, edge_keep=None, min_length=2, conflict="drop", max_rounds=0):
+        """ba_build_tracks: feature tracks from pairwise matches.  kp_counts (n_images,): keypoints per image; node = (keypoints
+        of the earlier images) + keypoint.  edge_a, edge_b (n_edges,) node pairs, one per match; edge_keep (n_edges,) or None: 0
+        removes an edge (a match_inlier array as it is).  conflict "drop" (a component with two nodes in one image is no track) or
+        "first" (the smallest node of every image stays).  Returns dict(kp_off (n_images + 1,) int64, node_label, node_track (N,)
+        int32, node_status (N,) uint8 (TRACKBUILD_STATUS), track_off (tracks + 1,) int64, track_node (members,) int32, counts:
+        dict by TRACKBUILD_COUNTS).  Everything but counts["rounds"] is a function of the set of kept edges.  Needs no problem."""
+        if isinstance(conflict, str):
+            if conflict not in TRACKBUILD_CONFLICT:
+                raise ValueError(f"unknown conflict policy {conflict!r}: expected one of {', '.join(map(repr, TRACKBUILD_CONFLICT))}")
+            conflict = TRACKBUILD_CONFLICT[conflict]
+        kp_counts = np.asarray(kp_counts, dtype=np.int64).reshape(-1)
+        kp_off = np.zeros(kp_counts.shape[0] + 1, dtype=np.int64)
+        np.cumsum(kp_counts, out=kp_off[1:])
+        a, b = _node_array(edge_a, "edge_a"), _node_array(edge_b, "edge_b")
+        if a.shape != b.shape:
+            raise ValueError(f"edge_a and edge_b must have the same length, not {a.shape[0]} and {b.shape[0]}")
+        keep = None
+        if edge_keep is not None:
+            keep = np.ascontiguousarray(np.asarray(edge_keep).reshape(-1) != 0, dtype=np.uint8)
+            if keep.shape != a.shape:
+                raise ValueError(f"edge_keep must have one entry per edge ({a.shape[0]}), not {keep.shape[0]}")
+        return self._build_tracks(kp_off, a, b, keep, BATrackBuildOptions(int(min_length), int(conflict), int(max_rounds), 0))
+
+    def _build_tracks(self, kp_off, a, b, keep, opts):
+        """The call itself on prepared arrays (kp_off int64, a / b int32, keep uint8 or None); build_tracks' dict."""
+        n = max(int(kp_off[-1]), 0) if kp_off[-1] < (1 << 31) else 0      # (a refused kp_off writes nothing)
+        label, track, node = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        status = np.zeros(n, dtype=np.uint8)
+        track_off = np.zeros(n // 2 + 2, dtype=np.int64)
+        counts = np.zeros(8, dtype=np.int64)
+        p64, p8 = C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+        _check(self._lib.ba_build_tracks(self._h, kp_off.shape[0] - 1, kp_off.ctypes.data_as(p64), a.shape[0], a.ctypes.data_as(_IP),
+                                         b.ctypes.data_as(_IP), None if keep is None else keep.ctypes.data_as(p8), C.byref(opts),
+                                         label.ctypes.data_as(_IP), track.ctypes.data_as(_IP), status.ctypes.data_as(p8),
+                                         track_off.ctypes.data_as(p64), node.ctypes.data_as(_IP), counts.ctypes.data_as(p64)))
+        n_tracks, members = int(counts[0]), int(counts[1])
+        return dict(kp_off=kp_off, node_label=label, node_track=track, node_status=status, track_off=track_off[:n_tracks + 1].copy(),
+                    track_node=node[:members].copy(), counts={k: int(v) for k, v in zip(TRACKBUILD_COUNTS, counts)})
 
     def centres(self):
         """ba_get_centres: (Nc, 3) camera centres -R_c^T t_c of the current cameras."""

@@ -37,7 +37,8 @@ enum ba_status {
   BA_ERR_HIP = -2,       /* a HIP runtime call failed */
   BA_ERR_STATE = -3,     /* call order (e.g. solve before set_problem) */
   BA_ERR_NUMERIC = -4,   /* non-finite residuals or cost */
-  BA_ERR_COMM = -5       /* RCCL load / init / collective failure */
+  BA_ERR_COMM = -5,      /* RCCL load / init / collective failure */
+  BA_ERR_INTERNAL = -6   /* a safety net of the library's own was hit (ba_build_tracks: the round cap) */
 };
 
 /* scipy least_squares' losses, rho(z) of z = (f / f_scale)^2 per scalar residual f; cost = 0.5 sum f_scale^2 rho(z):
@@ -943,6 +944,59 @@ int ba_bow_transform(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const int
 int ba_bow_score(ba_handle* h, int32_t nq, const int64_t* q_off, const int32_t* q_word, const int32_t* q_val, int32_t nd,
                  const int64_t* d_off, const int32_t* d_word, const int32_t* d_val, const int32_t* db_end, int32_t top_k,
                  int32_t* top_idx, int32_t* top_score, int32_t* score);
+
+/* Feature tracks from pairwise matches: which keypoints of which images are one 3D point.  The step between the verified
+ * matches of the image pairs (ba_match_descriptors / ba_match_guided; match_inlier of ba_fundamental, ba_relative_pose,
+ * ba_homography) and the (cam_idx, pt_idx, uv) lists ba_triangulate_tracks and ba_set_problem start from.  Replaces the
+ * per-keyframe dict bookkeeping of the reference (src/pipeline.py, _add_new_keyframe and _add_new_keyframe_exhaustive: the
+ * last_kf_obs_lookup / kf_obs_lookup parts), OpenMVG's TracksBuilder, COLMAP's correspondence graph.  Needs the handle only:
+ * it neither reads nor touches a resident problem.  Local to the rank, no collective.  Integer arithmetic throughout.
+ *
+ * A node is a keypoint: node = kp_off[image] + keypoint, kp_off int64[n_images + 1] ascending from 0, N = kp_off[n_images]
+ * < 2^31.  An edge e is one match between nodes edge_a[e] and edge_b[e]; edge_keep[e] == 0 (edge_keep may be NULL: keep all)
+ * removes it, and a removed edge's ends are not examined.  A kept edge whose ends lie in one image (a == b included) is ignored
+ * and counted.  Duplicates and either orientation are allowed.
+ *
+ * Every output but counts[6] and counts[7] is a function of the SET of kept edges: not of their order, their orientation,
+ * their multiplicity, the launch grid or the order in which atomics are served (counts[6] counts edges, duplicates included).
+ *   node_label[v]   the smallest node of v's connected component over the kept edges (v itself when isolated).
+ *   A component of at least two nodes is a candidate track; it has a conflict when two of its nodes lie in one image.
+ *     BA_TRACKS_DROP   the whole component is no track (OpenMVG's track filter).
+ *     BA_TRACKS_FIRST  the smallest node of every image stays, the image's other nodes get no track.  The kept nodes are then
+ *                      the track EVEN THOUGH THEY NEED NOT BE CONNECTED BY KEPT EDGES ANY MORE: the dropped node may have been
+ *                      the only link between them.
+ *   A candidate with fewer than min_length kept nodes is no track.
+ *   Tracks are numbered by ascending label (the label is always a member: a track's first member); members are listed by
+ *   ascending node, i.e. by ascending image.  track_off int64[tracks + 1] / track_node int32[members] are the CSR (the caller
+ *   provides N / 2 + 2 and N entries).  node_track[v] = the track of v or -1.  node_status[v]: enum ba_trackbuild_status --
+ *   IN_TRACK; ISOLATED (no kept edge to another image); CONFLICT (DROP: every node of a conflicting component; FIRST: the nodes
+ *   that were not the smallest of their image); SHORT (a node kept by the conflict policy whose component has fewer than
+ *   min_length kept nodes).
+ *   counts int64[8]: tracks, track members, components of at least two nodes, components with a conflict, nodes dropped for
+ *   a conflict, components dropped as short, same-image edges ignored, hook rounds run.  The hook-round count is a diagnostic:
+ *   it is the ONE value that may differ between two calls on the same input.
+ * max_rounds: the components come from rounds of (link roots, flatten).  A lane of the linking kernel leaves only when the two
+ * ends of its edge have one root or its own link went in, so after the first round every edge is inside one tree and the second
+ * finds nothing to link: two rounds, in whatever order atomics are served.  0 means the library's cap, ceil(log2 max(N, 2)) + 2,
+ * a net well above that.  Hitting the cap returns BA_ERR_INTERNAL naming max_rounds, outputs unspecified.
+ * BA_ERR_INVALID, naming the argument: a NULL pointer other than edge_keep; n_images < 0; kp_off not starting at 0 or
+ * decreasing; N >= 2^31; n_edges < 0 or above 2^36; min_length < 2; conflict not 0 / 1; max_rounds < 0; a kept edge with an end
+ * outside [0, N) -- found on the device, the message names the smallest such edge.  n_edges == 0 and N == 0 are valid: no tracks.
+ * Not offered: splitting a conflicting component by cutting weak edges, a cap on track length, per-edge weights, tracks
+ * across ranks, a persistent incrementally updated forest (the call is stateless: an existing map passes its tracks as chain
+ * edges next to the new matches).  Kernels, cost and layout: csrc/ba_trackbuild.hpp, DESIGN.md 4v. */
+typedef struct ba_trackbuild_options {
+  int32_t min_length;   /* 2: fewest members (= distinct images) of a track */
+  int32_t conflict;     /* 0 = BA_TRACKS_DROP, 1 = BA_TRACKS_FIRST */
+  int32_t max_rounds;   /* 0 = the library's cap */
+  int32_t reserved;
+} ba_trackbuild_options;   /* 16 bytes */
+enum { BA_TRACKS_DROP = 0, BA_TRACKS_FIRST = 1 };
+enum ba_trackbuild_status { BA_TRACKBUILD_IN_TRACK = 0, BA_TRACKBUILD_ISOLATED = 1, BA_TRACKBUILD_CONFLICT = 2, BA_TRACKBUILD_SHORT = 3 };
+int ba_default_trackbuild_options(ba_trackbuild_options* opts);    /* 2, BA_TRACKS_DROP, 0, 0 */
+int ba_build_tracks(ba_handle* h, int32_t n_images, const int64_t* kp_off, int64_t n_edges, const int32_t* edge_a,
+                    const int32_t* edge_b, const uint8_t* edge_keep, const ba_trackbuild_options* opts, int32_t* node_label,
+                    int32_t* node_track, uint8_t* node_status, int64_t* track_off, int32_t* track_node, int64_t* counts);
 
 /* Copies up to `capacity` records of the last ba_solve into out (may be NULL to ask for the count only);
  * *n = number of LM iterations recorded. */
