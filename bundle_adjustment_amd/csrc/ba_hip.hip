@@ -202,6 +202,78 @@ struct PinnedStage {
   }
 };
 
+// The device memory of the calls that keep nothing on the device between calls: a bump arena over a list of blocks.
+// Nothing is zero-filled: the bytes served another array in the call before, so a call uploads, clears or writes every word
+// before a kernel reads it.
+struct Scratch {
+  struct Block { char* p; size_t cap; };
+  struct Mark { size_t blk, off; };
+  std::vector<Block> blocks;
+  Mark at = {0, 0};                // where the next take starts
+  size_t bytes = 0;                // the blocks' capacities together
+  long long allocs = 0;            // hipMalloc calls since ba_create
+  bool fresh = true, untidy = false;   // the call began on an empty arena; a call added blocks to the ones it found
+  Scratch() = default;
+  Scratch(const Scratch&) = delete;
+  Scratch& operator=(const Scratch&) = delete;
+  ~Scratch() { release(); }
+  void release() {
+    for (Block& b : blocks) (void)hipFree(b.p);
+    blocks.clear();
+    bytes = 0;
+  }
+  hipError_t open(size_t cap) {
+    Block b = {nullptr, cap};
+    const hipError_t e = hipMalloc((void**)&b.p, cap);
+    if (e == hipSuccess) { blocks.push_back(b); bytes += cap; ++allocs; }
+    return e;
+  }
+  // Starts a call.  After a call that added blocks to the ones it found, some lie unused: the stream is drained (that call may
+  // have failed half way) and one block of their total size replaces them.  A first call's blocks are its takes exactly, and stay.
+  hipError_t begin(hipStream_t stream) {
+    at = {0, 0};
+    fresh = blocks.empty();
+    if (!untidy) return hipSuccess;
+    untidy = false;
+    const hipError_t e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return e;
+    const size_t total = bytes;
+    release();
+    return open(total);
+  }
+  // n elements at a 256-byte boundary, valid until the call returns (n = 0: an address that is never read).  A take that fits
+  // nowhere opens a block of its own size, so nothing handed out before moves.
+  template <typename T>
+  hipError_t take(size_t n, T** out) {
+    const size_t need = (std::max<size_t>(n * sizeof(T), 1) + 255) & ~(size_t)255;
+    while (at.blk < blocks.size() && blocks[at.blk].cap - at.off < need) at = {at.blk + 1, 0};
+    if (at.blk == blocks.size()) {
+      untidy = !fresh;
+      const hipError_t e = open(need);
+      if (e != hipSuccess) return e;
+    }
+    *out = (T*)(blocks[at.blk].p + at.off);
+    at.off += need;
+    return hipSuccess;
+  }
+  template <typename T, typename... Ts>
+  hipError_t take(size_t n, T** out, Ts**... more) {      // several arrays of n elements each
+    const hipError_t e = take(n, out);
+    return e != hipSuccess ? e : take(n, more...);
+  }
+  // take, and the n elements queued for upload from src
+  template <typename T>
+  hipError_t put(hipStream_t stream, size_t n, const void* src, const T** out) {
+    T* p = nullptr;
+    hipError_t e = take(n, &p);
+    if (e == hipSuccess && n > 0) e = hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyHostToDevice, stream);
+    *out = p;
+    return e;
+  }
+  Mark mark() const { return at; }   // rewind(mark()) gives back what was taken since
+  void rewind(Mark m) { at = m; }
+};
+
 // The vocabulary tree of ba_vocab_train / ba_vocab_set as the host keeps it (ba_vocab_get reads it back from here)
 struct BowVocab {
   int desc_bytes = 0, n_words = 0, branching = 0, levels = 0;
@@ -302,41 +374,10 @@ struct ba_handle {
   DBuf<int> rn_cnt;
   DBuf<unsigned char> rn_cons, rn_inl;
   RansacArgs rn_args = {};
-  // The pair-shaped calls (HypArgs of ba_hypothesis.hpp): staging of a call -- both views' points (two doubles each, three for
-  // ba_sim3), the pair offsets, the score blocks' best models, the per-pair results, consensus and inlier bytes per match; for
-  // the calls whose hypotheses are solved in a launch of their own (five-point, seven-point): their slots and masks
-  struct PairStage {
-    DBuf<double> pts, best, out, slots;
-    DBuf<long long> off;
-    DBuf<unsigned char> cons, inl;
-    DBuf<unsigned> mask;
-  };
-  PairStage rp, hg, s3, fd;
-  DBuf<double> fd_nrm;         // ba_fundamental: the pairs' normalisation table
-  // ba_match_descriptors (ba_match.hpp): staging of the call -- every set's descriptors, the pair table, the splits' (k1, k2),
-  // best | second | dist1 | dist2 by row, the good bytes, the per-pair counts
-  DBuf<unsigned long long> mt_desc;
-  DBuf<MatchPair> mt_pairs;
-  DBuf<uint2> mt_part;
-  DBuf<int> mt_out, mt_ngood;
-  DBuf<unsigned char> mt_good;
+  // Device memory of the calls that need no problem and keep nothing on the device between calls: the pair-shaped RANSAC
+  // calls, matching, ORB, the pose graph, place recognition (but for the resident vocabulary) and track building
+  Scratch scratch;
   int debug_match_splits = 0;  // BA_DEBUG_MATCH_SPLITS: train splits asked for per pair instead of match_plan's own choice (tests)
-  // ba_match_guided (ba_match_guided.hpp), beside the buffers above: the keypoints of every descriptor row, the windows by row,
-  // F by pair, the queries' gate records, the splits' counts of admitted rows, n_cand by row
-  DBuf<float> mg_xy, mg_win;
-  DBuf<double> mg_F, mg_rec;
-  DBuf<int> mg_cnt, mg_ncand;
-  // ba_orb_extract (ba_orb.hpp): the pyramid, score and blurred images of the batch (level-major), the score histograms, the
-  // cuts, the per-row counts (above | on the cut), the stage-1 lists and their Hs, the pattern, and the outputs by row:
-  // xy | size | angle | response, octave | level_xy | n_kp, cs, desc
-  DBuf<unsigned char> orb_pyr, orb_score, orb_blur, orb_desc;
-  DBuf<unsigned> orb_hist;
-  DBuf<OrbCut> orb_cut;
-  DBuf<int> orb_rows, orb_list, orb_i;
-  DBuf<long long> orb_hs;
-  DBuf<signed char> orb_pat;
-  DBuf<float> orb_f;
-  DBuf<double> orb_cs;
   PinnedStage orb_stage;                       // what the call reads back: cs | xy size angle response | octave level_xy | n_kp | desc
   bool orb_timing = false;                     // ba_orb_stage_times: events around the stages of ba_orb_extract
   hipEvent_t orb_ev[BA_ORB_STAGES + 1] = {};
@@ -345,27 +386,13 @@ struct ba_handle {
   // per-workgroup partial rows, the device record (similarity, centroids, status)
   DBuf<double> sim_buf, sim_part;
   DBuf<SimRec> sim_rec;
-  // ba_pose_graph / ba_pose_graph_system (ba_posegraph.hpp): one arena of doubles (poses x 2, measurements, information blocks,
-  // edge records, node blocks, PCG vectors, partial rows), one of ints (edges, incidence lists, masks, hubs), the PCG state
-  // records, the record the host reads, the trace of the last call
-  DBuf<double> pg_d;
-  DBuf<int> pg_i;
-  DBuf<PgPcg> pg_st;
-  DBuf<PgRec> pg_rec;
-  std::vector<ba_iter_record> pg_trace;
+  std::vector<ba_iter_record> pg_trace;   // ba_pose_graph: the trace of the last call
   int debug_pg_splits = 0;     // BA_DEBUG_PG_SPLITS: teams that share a hub node's incidence list instead of all 32 (tests)
-  // place recognition (ba_bow.hpp): the resident vocabulary (host copy `vocab`, device arrays bw_child0 .. bw_ndesc), the
-  // descriptors of the call, one arena of ints and one of 64-bit words per call (training, transform and score carve them up)
+  // place recognition (ba_bow.hpp): the resident vocabulary (host copy `vocab`, device arrays bw_child0 .. bw_ndesc)
   BowVocab vocab;
-  DBuf<int> bw_child0, bw_nchild, bw_wordof, bw_idf, bw_i, bw_j, bw_dense;
-  DBuf<unsigned long long> bw_ndesc, bw_desc, bw_l;
-  DBuf<unsigned char> bw_b;
+  DBuf<int> bw_child0, bw_nchild, bw_wordof, bw_idf;
+  DBuf<unsigned long long> bw_ndesc;
   int debug_bow_chunk = 0;     // BA_DEBUG_BOW_CHUNK: database vectors per score workgroup instead of BW_CHUNK (tests)
-  // ba_build_tracks (ba_trackbuild.hpp): one arena of ints (edges, parents, images, segments, scans, lists), one of bytes (edge
-  // flags, node status, conflict flags), one of 64-bit words (kp_off, the smallest bad edge, the counters)
-  DBuf<int> tb_i;
-  DBuf<unsigned char> tb_b;
-  DBuf<unsigned long long> tb_l;
   int debug_track_seg = 0;     // BA_DEBUG_TRACK_SEG: lowers the two segment-class thresholds of ba_build_tracks (tests)
   PinnedStage up;             // pinned arena of a window-sized problem's uploads (ba_set_problem: one copy, k_unpack_problem)
   char* h_small = nullptr;     // k_small_lm's results, host-mapped: ba_summary | int cur | trace records
@@ -1010,11 +1037,19 @@ static bool uv_f32_wanted() {
   return !(e && strcmp(e, "f64") == 0);
 }
 static inline UvArr uv_arr(const ba_handle* h, const DBuf<double2>& b) { return UvArr{b.p, h->uv_f32 ? 1 : 0}; }
-static int dev_scan(ba_handle* h, const int* in, int n, int* bsum, int* out) {
-  const int nb = (n + SETUP_SCAN_BLOCK - 1) / SETUP_SCAN_BLOCK;
-  BA_LAUNCH(k_scan_block_sums, dim3(nb), dim3(1024), 0, h->stream, in, n, bsum);
-  BA_LAUNCH(k_scan_top, dim3(1), dim3(1024), 0, h->stream, bsum, nb);
-  BA_LAUNCH(k_scan_final, dim3(nb), dim3(1024), 0, h->stream, in, n, (const int*)bsum, out);
+// out[i] = sum of in[0 .. i), out[n] = total, for any n < 2^31: k_scan_* passes of at most 1024 * SETUP_SCAN_BLOCK items, the
+// running total carried into the next pass through its block sums (so an n within one pass is three launches).  in and out are
+// different arrays; bsum holds 1026 ints.
+static int dev_scan(ba_handle* h, const int* in, size_t n, int* bsum, int* out) {
+  const size_t pass = (size_t)1024 * SETUP_SCAN_BLOCK;
+  if (n == 0) { HIPCHECK(hipMemsetAsync(out, 0, sizeof(int), h->stream)); return BA_OK; }
+  for (size_t c0 = 0; c0 < n; c0 += pass) {
+    const int nc = (int)std::min(pass, n - c0), nb = (nc + SETUP_SCAN_BLOCK - 1) / SETUP_SCAN_BLOCK;
+    BA_LAUNCH(k_scan_block_sums, dim3(nb), dim3(1024), 0, h->stream, in + c0, nc, bsum);
+    BA_LAUNCH(k_scan_top, dim3(1), dim3(1024), 0, h->stream, bsum, nb);
+    if (c0 > 0) BA_LAUNCH(k_tb_scan_base, dim3(1), dim3(1024), 0, h->stream, bsum, nb, (const int*)(out + c0));   // = the previous pass's total
+    BA_LAUNCH(k_scan_final, dim3(nb), dim3(1024), 0, h->stream, in + c0, nc, (const int*)bsum, out + c0);
+  }
   return BA_OK;
 }
 // BA_TIME_SETUP=1: one stderr line per stage of ba_set_problem, with the time since the previous line.  A device-build
@@ -1088,7 +1123,7 @@ static int set_problem_device(ba_handle* h, int Nc, int Np, int No, const int32_
   // (words: 0 first bad observation, 1 tracks, 2 big points, 3 "some pixel is not a float32 value")
   BA_LAUNCH(k_setup_hist, go, b256, 0, h->stream, (const int*)d_cam, (const int*)d_pt, No, Nc, Np, S + o_cnt, S + o_words,
             (uv_f32_wanted() && Nc > SMALL_MAX_CAMS) ? (const double2*)h->rbuf.p : (const double2*)nullptr, S + o_words + 3);
-  dev_scan(h, S + o_cnt, Np, S + o_bsum, h->pt_off.p);
+  if (int rc = dev_scan(h, S + o_cnt, Np, S + o_bsum, h->pt_off.p)) return rc;
   BA_LAUNCH(k_setup_scatter_pt, go, b256, 0, h->stream, (const int*)d_pt, No, (const int*)h->pt_off.p, S + o_fill, seg);
   BA_LAUNCH(k_setup_sort_pt, gp, b256, 0, h->stream, (const int*)h->pt_off.p, Np, (const int*)seg, (const int*)d_cam, p_src, h->p_cam.p, p_pt,
             S + o_hist, SETUP_HIST_BINS, u64, S + o_words + 1, S + o_big, S + o_words + 2);
@@ -1121,7 +1156,7 @@ static int set_problem_device(ba_handle* h, int Nc, int Np, int No, const int32_
   HIPCHECK(h->long_pts.alloc(std::max(h->n_long, 1)));
   if (h->n_long > 0) {
     BA_LAUNCH(k_setup_long_flags, gp, b256, 0, h->stream, (const int*)h->pt_off.p, Np, h->long_thr, S + o_flag);
-    dev_scan(h, S + o_flag, Np, S + o_bsum, S + o_pos);
+    if (int rc = dev_scan(h, S + o_flag, Np, S + o_bsum, S + o_pos)) return rc;
     BA_LAUNCH(k_setup_long_list, gp, b256, 0, h->stream, (const int*)h->pt_off.p, Np, h->long_thr, (const int*)(S + o_pos), h->long_pts.p);
   }
   if (h->lanes == LPP) {
@@ -1133,7 +1168,7 @@ static int set_problem_device(ba_handle* h, int Nc, int Np, int No, const int32_
   // camera order (keys: positions of the point-ordered list)
   const dim3 gt((No + SETUP_CAM_TILE - 1) / SETUP_CAM_TILE);
   BA_LAUNCH(k_setup_hist_cam, gt, b256, (size_t)Nc * sizeof(int), h->stream, (const int*)h->p_cam.p, No, Nc, S + o_ccnt);
-  dev_scan(h, S + o_ccnt, Nc, S + o_bsum, S + o_coff);
+  if (int rc = dev_scan(h, S + o_ccnt, Nc, S + o_bsum, S + o_coff)) return rc;
   BA_LAUNCH(k_setup_scatter_cam, gt, b256, 2 * (size_t)Nc * sizeof(int), h->stream, (const int*)h->p_cam.p, No, Nc, (const int*)(S + o_coff),
             S + o_cfill, seg);
   BA_LAUNCH(k_setup_sort_cam, dim3(Nc), b256, 0, h->stream, (const int*)(S + o_coff), (const int*)seg, (const int*)p_pt, (const int*)p_src,
@@ -3330,11 +3365,22 @@ extern "C" int ba_get_stat(ba_handle* h, int32_t which, int64_t* value) {
   if (!h || !value || which < 0 || which >= BA_STAT_END) return fail(BA_ERR_INVALID, "bad argument");
   if (which == BA_STAT_PRIOR_BLOCKS) { *value = h->have_problem ? h->prior_blocks : 0; return BA_OK; }
   if (which == BA_STAT_SHARED_GROUPS) { *value = h->have_problem ? h->n_shared : 0; return BA_OK; }
+  if (which == BA_STAT_SCRATCH_BYTES) { *value = (int64_t)h->scratch.bytes; return BA_OK; }
+  if (which == BA_STAT_SCRATCH_ALLOCS) { *value = h->scratch.allocs; return BA_OK; }
   if (which == BA_STAT_HELD_PARAMS) {
     *value = h->have_problem ? held_params(h, (h->cam_held_or & ~0x3fu) ? BalCam::NB : Pinhole::NB) : 0;
     return BA_OK;
   }
   *value = which == BA_STAT_PIXELS_F32 ? (int64_t)(h->have_problem && h->uv_f32) : (int64_t)h->stats[which];
+  return BA_OK;
+}
+// Test hook: every byte of the scratch arena set to `byte`, so a test sees whether a call reads what it did not write itself
+extern "C" int ba_debug_scratch_fill(ba_handle* h, int32_t byte) {
+  if (!h) return fail(BA_ERR_INVALID, "null handle");
+  if (set_device(h)) return BA_ERR_HIP;
+  BA_SYNC(h);
+  for (const Scratch::Block& b : h->scratch.blocks) HIPCHECK(hipMemset(b.p, byte & 0xff, b.cap));
+  HIPCHECK(hipStreamSynchronize(nullptr));       // (the fill is queued on the null stream, which the handle's stream does not wait for)
   return BA_OK;
 }
 // Test hook: the layout ba_set_problem built, copied to the host (tests compare the device build with the host build).
@@ -3715,46 +3761,41 @@ static int pairs_check(const char* who, const double* K, int32_t n_pairs, const 
 }
 // What the calls' options hold alike, each under its own names; max_px: the call's threshold in pixels
 struct PairOpts { int32_t n_hyp, lo_rounds, refine_iters, min_inliers; uint64_t seed; double max_px; };
-// The staging of a call (n_pairs > 0) sized and filled, and the shared head of its arguments.  K null: fbar = 1.  width: doubles
-// per point (2, or ba_sim3's 3); best_per / out_per: the call's doubles per score block / per pair.  d1 | d2: the two point
-// arrays on the device.
-static int pairs_upload(ba_handle* h, ba_handle::PairStage& st, const double* K, int32_t n_pairs, const int64_t* pair_off, int width,
-                        const double* pts1, const double* pts2, const PairOpts& o, int n_blk, int best_per, int out_per, HypArgs& a,
-                        const double*& d1, const double*& d2) {
+// A call (n_pairs > 0) begun: its arrays taken from the scratch arena and uploaded, and the shared head of its arguments.  K null:
+// fbar = 1.  width: doubles per point (2, or ba_sim3's 3); best_per / out_per: the call's doubles per score block / per pair.
+// d1 | d2: the two point arrays on the device.
+static int pairs_upload(ba_handle* h, const double* K, int32_t n_pairs, const int64_t* pair_off, int width, const double* pts1,
+                        const double* pts2, const PairOpts& o, int n_blk, int best_per, int out_per, HypArgs& a, const double*& d1,
+                        const double*& d2) {
   if (set_device(h)) return BA_ERR_HIP;
-  const size_t nm = (size_t)pair_off[n_pairs], np = (size_t)n_pairs, nm1 = std::max<size_t>(nm, 1);
-  HIPCHECK(st.pts.alloc(2 * width * nm1)); HIPCHECK(st.off.alloc(np + 1)); HIPCHECK(st.best.alloc((size_t)best_per * np * n_blk));
-  HIPCHECK(st.out.alloc((size_t)out_per * np)); HIPCHECK(st.cons.alloc(nm1)); HIPCHECK(st.inl.alloc(nm1));
+  Scratch& sc = h->scratch;
+  HIPCHECK(sc.begin(h->stream));
+  const size_t nm = (size_t)pair_off[n_pairs], np = (size_t)n_pairs;
+  static_assert(sizeof(long long) == sizeof(int64_t), "pair_off is uploaded as it is");
+  HIPCHECK(sc.put(h->stream, width * nm, pts1, &d1)); HIPCHECK(sc.put(h->stream, width * nm, pts2, &d2)); HIPCHECK(sc.put(h->stream, np + 1, pair_off, &a.off));
+  HIPCHECK(sc.take((size_t)best_per * np * n_blk, &a.best)); HIPCHECK(sc.take((size_t)out_per * np, &a.out)); HIPCHECK(sc.take(nm, &a.cons, &a.inl));
   a.fbar = K ? 0.5 * (K[0] + K[4]) : 1.0; a.thr = o.max_px / a.fbar;
   a.n_hyp = o.n_hyp; a.lo_rounds = o.lo_rounds; a.iters = o.refine_iters; a.min_inliers = o.min_inliers;
   a.n_blk = n_blk; a.seed = o.seed;
-  a.off = st.off.p; a.best = st.best.p; a.cons = st.cons.p; a.inl = st.inl.p; a.out = st.out.p;
-  d1 = st.pts.p; d2 = st.pts.p + width * nm1;
-  static_assert(sizeof(long long) == sizeof(int64_t), "pair_off is uploaded as it is");
-  HIPCHECK(hipMemcpyAsync(st.off.p, pair_off, (np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-  if (nm > 0) {
-    HIPCHECK(hipMemcpyAsync(st.pts.p, pts1, width * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemcpyAsync(st.pts.p + width * nm1, pts2, width * nm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemsetAsync(st.inl.p, 0, nm, h->stream));
-  }
+  if (nm > 0) HIPCHECK(hipMemsetAsync(a.inl, 0, nm, h->stream));
   return BA_OK;
 }
 // The same for the calls on pixels, with their K (null: fx = fy = 1, cx = cy = 0) and the two views; max_depth is the caller's
-static int pairs_upload(ba_handle* h, ba_handle::PairStage& st, const double* K, int32_t n_pairs, const int64_t* pair_off, const double* pts1,
-                        const double* pts2, const PairOpts& o, int n_blk, int best_per, int out_per, PairArgs& a) {
+static int pairs_upload(ba_handle* h, const double* K, int32_t n_pairs, const int64_t* pair_off, const double* pts1, const double* pts2,
+                        const PairOpts& o, int n_blk, int best_per, int out_per, PairArgs& a) {
   const double *d1, *d2;
-  if (int rc = pairs_upload(h, st, K, n_pairs, pair_off, 2, pts1, pts2, o, n_blk, best_per, out_per, a, d1, d2)) return rc;
+  if (int rc = pairs_upload(h, K, n_pairs, pair_off, 2, pts1, pts2, o, n_blk, best_per, out_per, a, d1, d2)) return rc;
   a.fx = K ? K[0] : 1.0; a.fy = K ? K[4] : 1.0; a.cx = K ? K[2] : 0.0; a.cy = K ? K[5] : 0.0;
   a.p1 = (const double2*)d1; a.p2 = (const double2*)d2;
   return BA_OK;
 }
 // The pairs' rows of out_per doubles into res (want: the call returns any of them) and match_inlier, and the stream drained
-static int pairs_download(ba_handle* h, ba_handle::PairStage& st, bool want, int out_per, int32_t n_pairs, const int64_t* pair_off,
+static int pairs_download(ba_handle* h, const HypArgs& a, bool want, int out_per, int32_t n_pairs, const int64_t* pair_off,
                           uint8_t* match_inlier, std::vector<double>& res) {
   const size_t nm = (size_t)pair_off[n_pairs];
   res.resize(want ? (size_t)out_per * n_pairs : 0);
-  if (want) HIPCHECK(hipMemcpyAsync(res.data(), st.out.p, res.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (match_inlier && nm > 0) HIPCHECK(hipMemcpyAsync(match_inlier, st.inl.p, nm, hipMemcpyDeviceToHost, h->stream));
+  if (want) HIPCHECK(hipMemcpyAsync(res.data(), a.out, res.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (match_inlier && nm > 0) HIPCHECK(hipMemcpyAsync(match_inlier, a.inl, nm, hipMemcpyDeviceToHost, h->stream));
   BA_SYNC(h);
   return BA_OK;
 }
@@ -3787,16 +3828,16 @@ extern "C" int ba_relative_pose(ba_handle* h, const double K[9], int32_t n_pairs
   const int n_blk = (RP_SLOTS * opts->n_hyp + RP_THREADS - 1) / RP_THREADS;
   RelposeArgs a = {};
   const PairOpts o = {opts->n_hyp, opts->lo_rounds, opts->refine_iters, opts->min_inliers, opts->seed, opts->max_epi_px};
-  if (int rc = pairs_upload(h, h->rp, K, n_pairs, pair_off, pts1, pts2, o, n_blk, RP_BEST, RP_OUT, a)) return rc;
-  HIPCHECK(h->rp.slots.alloc(9 * (size_t)RP_SLOTS * np * opts->n_hyp)); HIPCHECK(h->rp.mask.alloc(np * opts->n_hyp));
-  a.max_depth = opts->max_depth; a.min_parallax = opts->min_parallax_deg; a.E = h->rp.slots.p; a.mask = h->rp.mask.p;
+  if (int rc = pairs_upload(h, K, n_pairs, pair_off, pts1, pts2, o, n_blk, RP_BEST, RP_OUT, a)) return rc;
+  HIPCHECK(h->scratch.take(9 * (size_t)RP_SLOTS * np * opts->n_hyp, &a.E)); HIPCHECK(h->scratch.take(np * opts->n_hyp, &a.mask));
+  a.max_depth = opts->max_depth; a.min_parallax = opts->min_parallax_deg;
   const dim3 b(RP_THREADS);
   BA_LAUNCH(k_relpose_solve, dim3(n_pairs, (opts->n_hyp + RP_TEAMS - 1) / RP_TEAMS), b, 0, h->stream, a);
   BA_LAUNCH(k_relpose_score, dim3(n_pairs, n_blk), b, 0, h->stream, a);
   BA_LAUNCH(k_relpose_lo, dim3(n_pairs), b, 0, h->stream, a);
   const bool want = R || t || status || n_inliers || rms_px || parallax_deg || best_hyp;
   std::vector<double> res;
-  if (int rc = pairs_download(h, h->rp, want, RP_OUT, n_pairs, pair_off, match_inlier, res)) return rc;
+  if (int rc = pairs_download(h, a, want, RP_OUT, n_pairs, pair_off, match_inlier, res)) return rc;
   if (want)
     for (size_t p = 0; p < np; ++p) {
       const double* r = res.data() + RP_OUT * p;
@@ -3844,14 +3885,14 @@ extern "C" int ba_homography(ba_handle* h, const double K[9], int32_t n_pairs, c
   const int n_blk = (opts->n_hyp + HG_THREADS - 1) / HG_THREADS;
   HomogArgs a = {};
   const PairOpts o = {opts->n_hyp, opts->lo_rounds, opts->refine_iters, opts->min_inliers, opts->seed, opts->max_px};
-  if (int rc = pairs_upload(h, h->hg, K, n_pairs, pair_off, pts1, pts2, o, n_blk, HG_BEST, HG_OUT, a)) return rc;
+  if (int rc = pairs_upload(h, K, n_pairs, pair_off, pts1, pts2, o, n_blk, HG_BEST, HG_OUT, a)) return rc;
   a.max_depth = opts->max_depth; a.ambiguity = opts->ambiguity_ratio; a.min_translation = opts->min_translation;
   const dim3 b(HG_THREADS);
   BA_LAUNCH(k_homog_score, dim3(n_pairs, n_blk), b, 0, h->stream, a);
   BA_LAUNCH(k_homog_lo, dim3(n_pairs), b, 0, h->stream, a);
   const bool want = H || status || n_inliers || rms_px || best_hyp || n_pose || R || t || normal || t_over_d || votes || pose_cost;
   std::vector<double> res;
-  if (int rc = pairs_download(h, h->hg, want, HG_OUT, n_pairs, pair_off, match_inlier, res)) return rc;
+  if (int rc = pairs_download(h, a, want, HG_OUT, n_pairs, pair_off, match_inlier, res)) return rc;
   if (want)
     for (size_t p = 0; p < np; ++p) {
       const double* r = res.data() + HG_OUT * p;
@@ -3899,14 +3940,14 @@ extern "C" int ba_sim3(ba_handle* h, const double K[9], int32_t n_pairs, const i
   const int n_blk = (opts->n_hyp + S3_THREADS - 1) / S3_THREADS;
   Sim3Args a = {};
   const PairOpts o = {opts->n_hyp, opts->lo_rounds, opts->refine_iters, opts->min_inliers, opts->seed, opts->max_px};
-  if (int rc = pairs_upload(h, h->s3, K, n_pairs, pair_off, 3, X1, X2, o, n_blk, S3_BEST, S3_OUT, a, a.X1, a.X2)) return rc;
+  if (int rc = pairs_upload(h, K, n_pairs, pair_off, 3, X1, X2, o, n_blk, S3_BEST, S3_OUT, a, a.X1, a.X2)) return rc;
   a.with_scale = opts->with_scale;
   const dim3 b(S3_THREADS);
   BA_LAUNCH(k_sim3_score, dim3(n_pairs, n_blk), b, 0, h->stream, a);
   BA_LAUNCH(k_sim3_lo, dim3(n_pairs), b, 0, h->stream, a);
   const bool want = sim || R || status || n_inliers || rms_px || best_hyp || hessian;
   std::vector<double> res;
-  if (int rc = pairs_download(h, h->s3, want, S3_OUT, n_pairs, pair_off, match_inlier, res)) return rc;
+  if (int rc = pairs_download(h, a, want, S3_OUT, n_pairs, pair_off, match_inlier, res)) return rc;
   if (want)
     for (size_t p = 0; p < np; ++p) {
       const double* r = res.data() + S3_OUT * p;
@@ -3950,9 +3991,9 @@ extern "C" int ba_fundamental(ba_handle* h, int32_t n_pairs, const int64_t* pair
   const int n_blk = (FD_SLOTS * opts->n_hyp + FD_THREADS - 1) / FD_THREADS;
   FundArgs a = {};
   const PairOpts o = {opts->n_hyp, opts->lo_rounds, opts->refine_iters, opts->min_inliers, opts->seed, opts->max_epi_px};
-  if (int rc = pairs_upload(h, h->fd, nullptr, n_pairs, pair_off, pts1, pts2, o, n_blk, FD_BEST, FD_OUT, a)) return rc;
-  HIPCHECK(h->fd_nrm.alloc(FD_NORM * np)); HIPCHECK(h->fd.slots.alloc(9 * (size_t)FD_SLOTS * np * opts->n_hyp)); HIPCHECK(h->fd.mask.alloc(np * opts->n_hyp));
-  a.nrm = h->fd_nrm.p; a.F = h->fd.slots.p; a.mask = h->fd.mask.p;
+  if (int rc = pairs_upload(h, nullptr, n_pairs, pair_off, pts1, pts2, o, n_blk, FD_BEST, FD_OUT, a)) return rc;
+  HIPCHECK(h->scratch.take(FD_NORM * np, &a.nrm)); HIPCHECK(h->scratch.take(9 * (size_t)FD_SLOTS * np * opts->n_hyp, &a.F));
+  HIPCHECK(h->scratch.take(np * opts->n_hyp, &a.mask));
   const dim3 b(FD_THREADS);
   BA_LAUNCH(k_fund_norm, dim3(n_pairs), b, 0, h->stream, a);
   BA_LAUNCH(k_fund_solve, dim3(n_pairs, (opts->n_hyp + FD_SOLVE_THREADS - 1) / FD_SOLVE_THREADS), dim3(FD_SOLVE_THREADS), 0, h->stream, a);
@@ -3960,7 +4001,7 @@ extern "C" int ba_fundamental(ba_handle* h, int32_t n_pairs, const int64_t* pair
   BA_LAUNCH(k_fund_lo, dim3(n_pairs), b, 0, h->stream, a);
   const bool want = F || status || n_inliers || rms_px || best_hyp || epipole1 || epipole2;
   std::vector<double> res;
-  if (int rc = pairs_download(h, h->fd, want, FD_OUT, n_pairs, pair_off, match_inlier, res)) return rc;
+  if (int rc = pairs_download(h, a, want, FD_OUT, n_pairs, pair_off, match_inlier, res)) return rc;
   if (want)
     for (size_t p = 0; p < np; ++p) {
       const double* r = res.data() + FD_OUT * p;
@@ -3994,27 +4035,48 @@ static void match_plan(MatchPair& e, int want) {
   e.split_len = (tiles + n - 1) / n * MT_TILE;
   e.n_splits = (e.nt + e.split_len - 1) / e.split_len;
 }
+// The statement fn<W>(...) with W = W_, the 64-bit words of a descriptor (1 .. MT_MAX_WORDS = 8)
+#define BA_BY_WORDS(W_, fn, ...)                   \
+  switch (W_) {                                    \
+    case 1: fn<1>(__VA_ARGS__); break;             \
+    case 2: fn<2>(__VA_ARGS__); break;             \
+    case 3: fn<3>(__VA_ARGS__); break;             \
+    case 4: fn<4>(__VA_ARGS__); break;             \
+    case 5: fn<5>(__VA_ARGS__); break;             \
+    case 6: fn<6>(__VA_ARGS__); break;             \
+    case 7: fn<7>(__VA_ARGS__); break;             \
+    default: fn<8>(__VA_ARGS__); break;            \
+  }
 template <int W>
 static void launch_match_partial(ba_handle* h, dim3 grid, const MatchArgs& a) {
   BA_LAUNCH(k_match_partial<W>, grid, dim3(MT_THREADS), 0, h->stream, a);
 }
-// What ba_match_descriptors and ba_match_guided refuse alike; `who` is the call the message names.
-static int match_check(const char* who, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc, int32_t n_pairs,
-                       const int32_t* pair_query, const int32_t* pair_train, double ratio) {
+static int desc_bytes_check(const char* who, int32_t desc_bytes) {
   if (desc_bytes < 8 || desc_bytes > 8 * MT_MAX_WORDS || desc_bytes % 8 != 0)
     return fail(BA_ERR_INVALID, "%s: desc_bytes %d is not a multiple of 8 in 8 .. %d", who, desc_bytes, 8 * MT_MAX_WORDS);
+  return BA_OK;
+}
+// What the calls that take descriptor sets (matching, place recognition) refuse alike; `who` is the call the message names.
+static int desc_sets_check(const char* who, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc) {
+  if (int rc = desc_bytes_check(who, desc_bytes)) return rc;
   if (n_sets < 0 || n_sets > 65535) return fail(BA_ERR_INVALID, "%s: n_sets %d is outside 0 .. 65535", who, n_sets);
-  if (n_pairs < 0 || n_pairs > 65535) return fail(BA_ERR_INVALID, "%s: n_pairs %d is outside 0 .. 65535", who, n_pairs);
-  if (!std::isfinite(ratio)) return fail(BA_ERR_INVALID, "%s: ratio must be finite", who);
   if (!set_off) return fail(BA_ERR_INVALID, "%s: null set_off", who);
   if (set_off[0] != 0) return fail(BA_ERR_INVALID, "%s: set_off[0] must be 0", who);
-  for (int32_t s = 0; s < n_sets; ++s) {
+  for (int32_t s = 0; s < n_sets; ++s)
     if (set_off[s + 1] < set_off[s]) return fail(BA_ERR_INVALID, "%s: set_off decreases at set %d", who, s);
+  if (set_off[n_sets] > 0 && !desc) return fail(BA_ERR_INVALID, "%s: null desc", who);
+  return BA_OK;
+}
+// What ba_match_descriptors and ba_match_guided refuse beyond that
+static int match_check(const char* who, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc, int32_t n_pairs,
+                       const int32_t* pair_query, const int32_t* pair_train, double ratio) {
+  if (int rc = desc_sets_check(who, desc_bytes, n_sets, set_off, desc)) return rc;
+  if (n_pairs < 0 || n_pairs > 65535) return fail(BA_ERR_INVALID, "%s: n_pairs %d is outside 0 .. 65535", who, n_pairs);
+  if (!std::isfinite(ratio)) return fail(BA_ERR_INVALID, "%s: ratio must be finite", who);
+  for (int32_t s = 0; s < n_sets; ++s)
     if (set_off[s + 1] - set_off[s] > (1LL << MT_IDX_BITS))
       return fail(BA_ERR_INVALID, "%s: set_off: set %d holds %lld descriptors, more than %d", who, s,
                   (long long)(set_off[s + 1] - set_off[s]), 1 << MT_IDX_BITS);
-  }
-  if (set_off[n_sets] > 0 && !desc) return fail(BA_ERR_INVALID, "%s: null desc", who);
   if (n_pairs > 0 && !pair_query) return fail(BA_ERR_INVALID, "%s: null pair_query", who);
   if (n_pairs > 0 && !pair_train) return fail(BA_ERR_INVALID, "%s: null pair_train", who);
   for (int32_t p = 0; p < n_pairs; ++p) {
@@ -4067,30 +4129,30 @@ static void match_plan_all(const ba_handle* h, MatchTable& m, size_t n_pairs) {
   }
   for (size_t p = 0; p < n_pairs; ++p) m.fin_qb = std::max(m.fin_qb, (m.tab[p].nq + MT_THREADS - 1) / MT_THREADS);
 }
-// The staging both calls share: buffers, the kernels' common arguments, the uploads of descriptors and table, n_good zeroed
+// The call begun and what both calls share of it: the arrays, the kernels' common arguments, the uploads of descriptors and table,
+// n_good zeroed
 static int match_stage(ba_handle* h, const MatchTable& m, int32_t desc_bytes, size_t n_desc, const uint8_t* desc, int32_t n_pairs,
                        double ratio, int32_t max_distance, bool mutual, MatchArgs& a) {
   const size_t nr = (size_t)m.rows, np = (size_t)n_pairs, W = (size_t)desc_bytes / 8;
-  HIPCHECK(h->mt_desc.alloc(n_desc * W)); HIPCHECK(h->mt_pairs.alloc(m.tab.size())); HIPCHECK(h->mt_part.alloc(std::max<size_t>((size_t)m.n_part, 1)));
-  HIPCHECK(h->mt_out.alloc(4 * nr)); HIPCHECK(h->mt_good.alloc(nr)); HIPCHECK(h->mt_ngood.alloc(np));
+  Scratch& sc = h->scratch;
+  HIPCHECK(sc.begin(h->stream));
   a = {};
-  a.desc = h->mt_desc.p; a.pairs = h->mt_pairs.p; a.part = h->mt_part.p;
+  HIPCHECK(sc.put(h->stream, n_desc * W, desc, &a.desc)); HIPCHECK(sc.put(h->stream, m.tab.size(), m.tab.data(), &a.pairs));
+  HIPCHECK(sc.take((size_t)m.n_part, &a.part)); HIPCHECK(sc.take(nr, &a.best, &a.second, &a.dist1, &a.dist2));
+  HIPCHECK(sc.take(nr, &a.good)); HIPCHECK(sc.take(np, &a.n_good));
   a.n_pairs = n_pairs; a.mutual = mutual ? 1 : 0; a.max_distance = max_distance; a.ratio = ratio;
-  a.best = h->mt_out.p; a.second = h->mt_out.p + nr; a.dist1 = h->mt_out.p + 2 * nr; a.dist2 = h->mt_out.p + 3 * nr;
-  a.good = h->mt_good.p; a.n_good = h->mt_ngood.p;
-  HIPCHECK(hipMemcpyAsync(h->mt_desc.p, desc, n_desc * (size_t)desc_bytes, hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipMemcpyAsync(h->mt_pairs.p, m.tab.data(), m.tab.size() * sizeof(MatchPair), hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipMemsetAsync(h->mt_ngood.p, 0, np * sizeof(int), h->stream));
+  HIPCHECK(hipMemsetAsync(a.n_good, 0, np * sizeof(int), h->stream));
   return BA_OK;
 }
 // best | second | dist1 | dist2, good and n_good to the caller, where asked for (queued; the caller drains the stream)
-static int match_fetch(ba_handle* h, size_t nr, size_t np, int32_t* best, int32_t* second, int32_t* dist1, int32_t* dist2, uint8_t* good,
-                       int32_t* n_good) {
+static int match_fetch(ba_handle* h, const MatchArgs& a, size_t nr, size_t np, int32_t* best, int32_t* second, int32_t* dist1, int32_t* dist2,
+                       uint8_t* good, int32_t* n_good) {
   int32_t* const outs[4] = {best, second, dist1, dist2};
+  const int* const from[4] = {a.best, a.second, a.dist1, a.dist2};
   for (int k = 0; k < 4; ++k)
-    if (outs[k]) HIPCHECK(hipMemcpyAsync(outs[k], h->mt_out.p + k * nr, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  if (good) HIPCHECK(hipMemcpyAsync(good, h->mt_good.p, nr, hipMemcpyDeviceToHost, h->stream));
-  if (n_good) HIPCHECK(hipMemcpyAsync(n_good, h->mt_ngood.p, np * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (outs[k]) HIPCHECK(hipMemcpyAsync(outs[k], from[k], nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (good) HIPCHECK(hipMemcpyAsync(good, a.good, nr, hipMemcpyDeviceToHost, h->stream));
+  if (n_good) HIPCHECK(hipMemcpyAsync(n_good, a.n_good, np * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   return BA_OK;
 }
 extern "C" int ba_match_descriptors(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc,
@@ -4111,19 +4173,10 @@ extern "C" int ba_match_descriptors(ba_handle* h, int32_t desc_bytes, int32_t n_
   if (int rc = match_stage(h, m, desc_bytes, n_desc, desc, n_pairs, opts->ratio, opts->max_distance, mutual, a)) return rc;
   if (m.max_splits > 0) {
     const dim3 grid((unsigned)m.tab.size(), (unsigned)m.max_qb, (unsigned)m.max_splits);
-    switch (W) {
-      case 1: launch_match_partial<1>(h, grid, a); break;
-      case 2: launch_match_partial<2>(h, grid, a); break;
-      case 3: launch_match_partial<3>(h, grid, a); break;
-      case 4: launch_match_partial<4>(h, grid, a); break;
-      case 5: launch_match_partial<5>(h, grid, a); break;
-      case 6: launch_match_partial<6>(h, grid, a); break;
-      case 7: launch_match_partial<7>(h, grid, a); break;
-      default: launch_match_partial<8>(h, grid, a); break;
-    }
+    BA_BY_WORDS(W, launch_match_partial, h, grid, a);
   }
   BA_LAUNCH(k_match_finish, dim3((unsigned)np, (unsigned)m.fin_qb), dim3(MT_THREADS), 0, h->stream, a);
-  if (int rc = match_fetch(h, (size_t)m.rows, np, best, second, dist1, dist2, good, n_good)) return rc;
+  if (int rc = match_fetch(h, a, (size_t)m.rows, np, best, second, dist1, dist2, good, n_good)) return rc;
   BA_SYNC(h);
   return BA_OK;
 }
@@ -4175,37 +4228,19 @@ extern "C" int ba_match_guided(ba_handle* h, int32_t desc_bytes, int32_t n_sets,
   const size_t nr = (size_t)m.rows;
   GuidedArgs a = {};
   if (int rc = match_stage(h, m, desc_bytes, n_desc, desc, n_pairs, opts->ratio, opts->max_distance, mutual, a.m)) return rc;
-  HIPCHECK(h->mg_xy.alloc(2 * n_desc)); HIPCHECK(h->mg_rec.alloc(4 * nr)); HIPCHECK(h->mg_cnt.alloc(std::max<size_t>((size_t)m.n_part, 1)));
-  HIPCHECK(h->mg_ncand.alloc(nr));
-  a.xy = h->mg_xy.p; a.rec = h->mg_rec.p; a.cnt = h->mg_cnt.p; a.n_cand = h->mg_ncand.p;
+  Scratch& sc = h->scratch;
+  HIPCHECK(sc.put(h->stream, 2 * n_desc, xy, &a.xy)); HIPCHECK(sc.take(4 * nr, &a.rec)); HIPCHECK(sc.take((size_t)m.n_part, &a.cnt)); HIPCHECK(sc.take(nr, &a.n_cand));
   a.gate = opts->gate; a.single = opts->single; a.max_epi2 = opts->max_epi_px * opts->max_epi_px;
-  HIPCHECK(hipMemcpyAsync(h->mg_xy.p, xy, 2 * n_desc * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  if (epi) {
-    HIPCHECK(h->mg_F.alloc(9 * np));
-    HIPCHECK(hipMemcpyAsync(h->mg_F.p, F, 9 * np * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    a.F = h->mg_F.p;
-  } else {
-    HIPCHECK(h->mg_win.alloc(3 * nr));
-    HIPCHECK(hipMemcpyAsync(h->mg_win.p, window, 3 * nr * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    a.window = h->mg_win.p;
-  }
+  if (epi) HIPCHECK(sc.put(h->stream, 9 * np, F, &a.F));
+  else HIPCHECK(sc.put(h->stream, 3 * nr, window, &a.window));
   BA_LAUNCH(k_guided_prepare, dim3((unsigned)np, (unsigned)m.fin_qb), dim3(MT_THREADS), 0, h->stream, a);
   if (m.max_splits > 0) {
     const dim3 grid((unsigned)m.tab.size(), (unsigned)m.max_qb, (unsigned)m.max_splits);
-    switch (W) {
-      case 1: launch_guided_partial<1>(h, grid, a); break;
-      case 2: launch_guided_partial<2>(h, grid, a); break;
-      case 3: launch_guided_partial<3>(h, grid, a); break;
-      case 4: launch_guided_partial<4>(h, grid, a); break;
-      case 5: launch_guided_partial<5>(h, grid, a); break;
-      case 6: launch_guided_partial<6>(h, grid, a); break;
-      case 7: launch_guided_partial<7>(h, grid, a); break;
-      default: launch_guided_partial<8>(h, grid, a); break;
-    }
+    BA_BY_WORDS(W, launch_guided_partial, h, grid, a);
   }
   BA_LAUNCH(k_guided_finish, dim3((unsigned)np, (unsigned)m.fin_qb), dim3(MT_THREADS), 0, h->stream, a);
-  if (int rc = match_fetch(h, nr, np, best, second, dist1, dist2, good, n_good)) return rc;
-  if (n_cand) HIPCHECK(hipMemcpyAsync(n_cand, h->mg_ncand.p, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (int rc = match_fetch(h, a.m, nr, np, best, second, dist1, dist2, good, n_good)) return rc;
+  if (n_cand) HIPCHECK(hipMemcpyAsync(n_cand, a.n_cand, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   BA_SYNC(h);
   return BA_OK;
 }
@@ -4325,22 +4360,22 @@ extern "C" int ba_orb_extract(ba_handle* h, int32_t n_images, int32_t height, in
     a.off[l] = pix; pix += (long long)B * lw[l] * lh[l];
     max_cap = std::max(max_cap, 2 * lq[l]);
   }
-  const size_t npx = (size_t)pix, cap = (size_t)std::max(a.list_cap, 1);
-  HIPCHECK(h->orb_pyr.alloc(npx)); HIPCHECK(h->orb_score.alloc(npx)); HIPCHECK(h->orb_blur.alloc(npx));
-  HIPCHECK(h->orb_hist.alloc(B * L * 256)); HIPCHECK(h->orb_cut.alloc(B * L)); HIPCHECK(h->orb_rows.alloc(2 * B * a.rows));
-  HIPCHECK(h->orb_list.alloc(B * cap)); HIPCHECK(h->orb_hs.alloc(B * cap)); HIPCHECK(h->orb_pat.alloc(1024));
-  HIPCHECK(h->orb_f.alloc(5 * B * N)); HIPCHECK(h->orb_i.alloc(3 * B * N + B)); HIPCHECK(h->orb_cs.alloc(2 * B * N)); HIPCHECK(h->orb_desc.alloc(32 * B * N));
-  a.pyr = h->orb_pyr.p; a.score = h->orb_score.p; a.blur = h->orb_blur.p; a.hist = h->orb_hist.p; a.cut = h->orb_cut.p;
-  a.row_a = h->orb_rows.p; a.row_b = h->orb_rows.p + B * a.rows; a.list = h->orb_list.p; a.hs = h->orb_hs.p; a.pattern = h->orb_pat.p;
-  a.xy = h->orb_f.p; a.size = a.xy + 2 * B * N; a.angle = a.size + B * N; a.response = a.angle + B * N;
-  a.octave = h->orb_i.p; a.level_xy = a.octave + B * N; a.n_kp = a.level_xy + 2 * B * N;
-  a.cs = h->orb_cs.p; a.desc = h->orb_desc.p;
+  // the outputs by row: xy | size | angle | response, octave | level_xy | n_kp (each group is read back in one copy)
+  const size_t npx = (size_t)pix, cap = (size_t)a.list_cap;
+  Scratch& sc = h->scratch;
+  HIPCHECK(sc.begin(h->stream));
+  HIPCHECK(sc.take(npx, &a.pyr, &a.score, &a.blur));
+  HIPCHECK(sc.take(B * L * 256, &a.hist)); HIPCHECK(sc.take(B * L, &a.cut)); HIPCHECK(sc.take(B * a.rows, &a.row_a, &a.row_b));
+  HIPCHECK(sc.take(B * cap, &a.list)); HIPCHECK(sc.take(B * cap, &a.hs));
+  HIPCHECK(sc.take(5 * B * N, &a.xy)); HIPCHECK(sc.take(3 * B * N + B, &a.octave)); HIPCHECK(sc.take(2 * B * N, &a.cs)); HIPCHECK(sc.take(32 * B * N, &a.desc));
+  a.size = a.xy + 2 * B * N; a.angle = a.size + B * N; a.response = a.angle + B * N;
+  a.level_xy = a.octave + B * N; a.n_kp = a.level_xy + 2 * B * N;
   int stamp = 0;
 #define ORB_STAMP() do { if (h->orb_timing) HIPCHECK(hipEventRecord(h->orb_ev[stamp++], h->stream)); } while (0)
   ORB_STAMP();
-  HIPCHECK(hipMemcpyAsync(h->orb_pyr.p, images, B * (size_t)px, hipMemcpyHostToDevice, h->stream));      // level 0 of every image
-  HIPCHECK(hipMemcpyAsync(h->orb_pat.p, pat, 1024, hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipMemsetAsync(h->orb_hist.p, 0, B * L * 256 * sizeof(unsigned), h->stream));
+  HIPCHECK(hipMemcpyAsync(a.pyr, images, B * (size_t)px, hipMemcpyHostToDevice, h->stream));      // level 0 of every image
+  HIPCHECK(sc.put(h->stream, 1024, pat, &a.pattern));
+  HIPCHECK(hipMemsetAsync(a.hist, 0, B * L * 256 * sizeof(unsigned), h->stream));
   const unsigned nb = (unsigned)B;
   auto tiles = [&](int l) { return dim3((unsigned)((a.w[l] + ORB_TILE_W - 1) / ORB_TILE_W), (unsigned)((a.h[l] + ORB_TILE_H - 1) / ORB_TILE_H), nb); };
   ORB_STAMP();
@@ -4373,10 +4408,10 @@ extern "C" int ba_orb_extract(ba_handle* h, int32_t n_images, int32_t height, in
   int32_t* const hn = hi + 3 * B * N;
   uint8_t* const hd = (uint8_t*)(hn + B);
   HIPCHECK(hipMemcpyAsync(hn, a.n_kp, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  if (xy || size || angle || response) HIPCHECK(hipMemcpyAsync(hf, h->orb_f.p, 5 * B * N * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  if (octave || level_xy) HIPCHECK(hipMemcpyAsync(hi, h->orb_i.p, 3 * B * N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  if (cs) HIPCHECK(hipMemcpyAsync(hc, h->orb_cs.p, 2 * B * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (desc) HIPCHECK(hipMemcpyAsync(hd, h->orb_desc.p, 32 * B * N, hipMemcpyDeviceToHost, h->stream));
+  if (xy || size || angle || response) HIPCHECK(hipMemcpyAsync(hf, a.xy, 5 * B * N * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (octave || level_xy) HIPCHECK(hipMemcpyAsync(hi, a.octave, 3 * B * N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (cs) HIPCHECK(hipMemcpyAsync(hc, a.cs, 2 * B * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (desc) HIPCHECK(hipMemcpyAsync(hd, a.desc, 32 * B * N, hipMemcpyDeviceToHost, h->stream));
   ORB_STAMP();
 #undef ORB_STAMP
   BA_SYNC(h);
@@ -4690,42 +4725,28 @@ static int pg_prepare(ba_handle* h, int n, const double* poses, int m, const int
   P->nbn = std::min((n + PG_TEAMS - 1) / PG_TEAMS, PG_MAX_BLOCKS);
   P->nbt = P->nbn + nh;
   P->nbs = std::min((n + PG_THREADS - 1) / PG_THREADS, PG_MAX_BLOCKS);
-  const size_t nn = (size_t)n, mm = (size_t)m;
-  const size_t n_d = 14 * nn + 7 * mm + (info ? 49 * mm : 0) + 4 * 49 * mm + 8 * mm + 7 * mm + 2 * mm + 49 * nn + 16 * nn + 49 * nn +
-                     40 * nn + 8 * mm + 2 * PG_MAX_BLOCKS + 3 * (size_t)P->nbt + 5 * PG_MAX_BLOCKS;
-  HIPCHECK(h->pg_d.alloc(n_d));
-  HIPCHECK(h->pg_i.alloc(iv.size() + 2 * (size_t)nh + 1));
-  HIPCHECK(h->pg_st.alloc(2));
-  HIPCHECK(h->pg_rec.alloc(1));
-  double* d = h->pg_d.p;
-  auto take = [&](size_t cnt) { double* r = d; d += cnt; return r; };
+  const size_t nn = (size_t)n, mm = (size_t)m, nbt = (size_t)P->nbt;
+  Scratch& sc = h->scratch;
+  HIPCHECK(sc.begin(h->stream));
   PgGraph& G = P->G;
   memset(&G, 0, sizeof G);
   G.n = n; G.m = m;
-  P->poses[0] = take(7 * nn); P->poses[1] = take(7 * nn);
-  double* dmeas = take(7 * mm);
-  double* dinfo = info ? take(49 * mm) : nullptr;
-  G.meas = dmeas; G.info = dinfo;
-  G.At = take(49 * mm); G.Bt = take(49 * mm); G.WA = take(49 * mm); G.WB = take(49 * mm);
-  double* const de = take(7 * mm);                              // (the residuals leave the device for the inspection entry only)
-  G.We = take(8 * mm); G.e = want_e ? de : nullptr; G.chi2 = take(mm); G.wgt = take(mm);
-  G.Hd = take(49 * nn); G.g = take(8 * nn); G.D = take(8 * nn); G.Minv = take(49 * nn);
-  G.x = take(8 * nn); G.r = take(8 * nn); G.z = take(8 * nn); G.p = take(8 * nn); G.q = take(8 * nn);
-  G.u = take(8 * mm);
-  G.part_cost = take(2 * PG_MAX_BLOCKS); G.part_g = take(P->nbt); G.part_rz = take(P->nbt); G.part_pq = take(P->nbt);
-  G.part_step = take(5 * PG_MAX_BLOCKS);
-  int* di = h->pg_i.p;
-  G.ei = di; G.ej = di + m; G.inc_off = di + 2 * mm; G.inc = di + 2 * mm + n + 1; G.mask = di + 4 * mm + n + 1;
-  int* dhub = di + iv.size();
+  // (pageable sources: the copies have left the host arrays when the calls return)
+  HIPCHECK(sc.take(7 * nn, &P->poses[0], &P->poses[1])); HIPCHECK(sc.put(h->stream, 7 * mm, meas, &G.meas));
+  if (info) HIPCHECK(sc.put(h->stream, 49 * mm, info, &G.info));
+  HIPCHECK(hipMemcpyAsync(P->poses[0], poses, 7 * nn * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(sc.take(49 * mm, &G.At, &G.Bt, &G.WA, &G.WB)); HIPCHECK(sc.take(8 * mm, &G.We, &G.u)); HIPCHECK(sc.take(mm, &G.chi2, &G.wgt));
+  if (want_e) HIPCHECK(sc.take(7 * mm, &G.e));                 // (the residuals leave the device for the inspection entry only)
+  HIPCHECK(sc.take(49 * nn, &G.Hd, &G.Minv)); HIPCHECK(sc.take(8 * nn, &G.g, &G.D, &G.x, &G.r, &G.z, &G.p, &G.q));
+  HIPCHECK(sc.take(2 * PG_MAX_BLOCKS, &G.part_cost)); HIPCHECK(sc.take(nbt, &G.part_g, &G.part_rz, &G.part_pq)); HIPCHECK(sc.take(5 * PG_MAX_BLOCKS, &G.part_step));
+  HIPCHECK(sc.put(h->stream, iv.size(), iv.data(), &G.ei));     // ei | ej | inc_off | inc | mask, as iv holds them
+  G.ej = G.ei + m; G.inc_off = G.ei + 2 * mm; G.inc = G.inc_off + n + 1; G.mask = G.inc + 2 * mm;
+  int* dhub;
+  HIPCHECK(sc.take(2 * (size_t)nh + 1, &dhub));                 // hub_node | hub_len | bad
   G.hub_node = dhub; G.hub_len = dhub + nh; G.bad = dhub + 2 * nh;
+  HIPCHECK(sc.take(2, &G.st)); HIPCHECK(sc.take(1, &G.rec));
   G.n_hubs = nh; G.nb_nodes = P->nbn;
   G.hub_teams = (h->debug_pg_splits > 0) ? std::min(h->debug_pg_splits, PG_TEAMS) : PG_TEAMS;
-  G.st = h->pg_st.p; G.rec = h->pg_rec.p;
-  // (pageable sources: the copies have left the host arrays when the calls return)
-  HIPCHECK(hipMemcpyAsync(P->poses[0], poses, 7 * nn * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipMemcpyAsync(dmeas, meas, 7 * mm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (info) HIPCHECK(hipMemcpyAsync(dinfo, info, 49 * mm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipMemcpyAsync(di, iv.data(), iv.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
   hubs.insert(hubs.end(), hub_len.begin(), hub_len.end());
   hubs.push_back(0);                                            // the `bad` word
   HIPCHECK(hipMemcpyAsync(dhub, hubs.data(), hubs.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -4738,8 +4759,8 @@ static void pg_linearize(ba_handle* h, const PgPlan& P, int which, int loss, dou
   BA_LAUNCH(k_pg_node_lin, dim3(P.nbt), dim3(PG_THREADS), 0, h->stream, P.G);
   BA_LAUNCH(k_pg_fold, dim3(1), dim3(64), 0, h->stream, P.G, P.nbe, P.nbt, 0, -1, 0, 0.0, 0);
 }
-static int pg_read_rec(ba_handle* h, PgRec* rec) {
-  HIPCHECK(hipMemcpyAsync(rec, h->pg_rec.p, sizeof *rec, hipMemcpyDeviceToHost, h->stream));
+static int pg_read_rec(ba_handle* h, const PgPlan& P, PgRec* rec) {
+  HIPCHECK(hipMemcpyAsync(rec, P.G.rec, sizeof *rec, hipMemcpyDeviceToHost, h->stream));
   BA_SYNC(h);
   return BA_OK;
 }
@@ -4768,7 +4789,7 @@ extern "C" int ba_pose_graph(ba_handle* h, int32_t n, const double* poses, int32
   PgRec rec;
   int cur = 0;
   pg_linearize(h, P, cur, loss, inv_f2);
-  if (int rc = pg_read_rec(h, &rec)) return rc;
+  if (int rc = pg_read_rec(h, P, &rec)) return rc;
   st.sse = rec.sse; st.cost = 0.5 * fs2 * rec.rho;
   sum->initial_sse = st.sse; sum->initial_cost = st.cost;
   if (!std::isfinite(st.cost)) return fail(BA_ERR_NUMERIC, "ba_pose_graph: non-finite cost at the initial poses");
@@ -4778,7 +4799,7 @@ extern "C" int ba_pose_graph(ba_handle* h, int32_t n, const double* poses, int32
     const double t0 = now_s();
     if (st.need_linearize) {
       pg_linearize(h, P, cur, loss, inv_f2);
-      if (int rc = pg_read_rec(h, &rec)) return rc;
+      if (int rc = pg_read_rec(h, P, &rec)) return rc;
       st.need_linearize = false;
       fresh = true;
     }
@@ -4800,7 +4821,7 @@ extern "C" int ba_pose_graph(ba_handle* h, int32_t n, const double* poses, int32
         BA_LAUNCH(k_pg_pcg_step, dim3(P.nbn), dim3(PG_THREADS), 0, h->stream, P.G, k, P.nbt);
       }
       BA_LAUNCH(k_pg_fold, dim3(1), dim3(64), 0, h->stream, P.G, P.nbe, 0, 0, k, P.nbn, tol2, (int)opts->pcg_min_iters);
-      if (int rc = pg_read_rec(h, &pr)) return rc;
+      if (int rc = pg_read_rec(h, P, &pr)) return rc;
       if (pr.bad) return fail(BA_ERR_NUMERIC, "ba_pose_graph: a damped diagonal block is not positive definite (LM iteration %d)", st.it);
       if (pr.pcg.done || k >= opts->pcg_max_iters) break;
       batch = std::min(2 * batch, 32);
@@ -4815,7 +4836,7 @@ extern "C" int ba_pose_graph(ba_handle* h, int32_t n, const double* poses, int32
     BA_LAUNCH(k_pg_edge<false>, dim3(P.nbe), dim3(PG_THREADS), 0, h->stream, P.G, (const double*)P.poses[1 - cur], loss, inv_f2);
     BA_LAUNCH(k_pg_fold, dim3(1), dim3(64), 0, h->stream, P.G, P.nbe, 0, P.nbs, -1, 0, 0.0, 0);
     PgRec tr;
-    if (int rc = pg_read_rec(h, &tr)) return rc;
+    if (int rc = pg_read_rec(h, P, &tr)) return rc;
     // ---- verdict: ba_solve's rules (apply_verdict, lm_decide)
     const double cost_new = 0.5 * fs2 * tr.rho, sse_new = tr.sse;
     const double model = 0.5 * (st.lambda * tr.dDd - tr.gTd + tr.dr);
@@ -4875,11 +4896,11 @@ extern "C" int ba_pose_graph_system(ba_handle* h, int32_t n, const double* poses
   if (int rc = pg_prepare(h, n, poses, m, edge_i, edge_j, meas, info, held, opts, true, &P)) return rc;
   pg_linearize(h, P, 0, opts->loss, 1.0 / (opts->f_scale * opts->f_scale));
   const size_t N = 7 * (size_t)n, mm = (size_t)m;
-  DBuf<double> dense;
   if (H) {
-    HIPCHECK(dense.alloc(N * N));
-    BA_LAUNCH(k_pg_dense, dim3((unsigned)((N * N + PG_THREADS - 1) / PG_THREADS)), dim3(PG_THREADS), 0, h->stream, P.G, lambda, dense.p);
-    HIPCHECK(hipMemcpyAsync(H, dense.p, N * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    double* dense;
+    HIPCHECK(h->scratch.take(N * N, &dense));
+    BA_LAUNCH(k_pg_dense, dim3((unsigned)((N * N + PG_THREADS - 1) / PG_THREADS)), dim3(PG_THREADS), 0, h->stream, P.G, lambda, dense);
+    HIPCHECK(hipMemcpyAsync(H, dense, N * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   }
   std::vector<double> at, bt, g8;
   if (e) HIPCHECK(hipMemcpyAsync(e, P.G.e, 7 * mm * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -4909,18 +4930,6 @@ extern "C" int ba_default_vocab_options(ba_vocab_options* o) {
   o->branching = 10;
   o->levels = 6;
   o->iters = 10;
-  return BA_OK;
-}
-// What the calls that take descriptor sets refuse alike; `who` is the call the message names.
-static int bow_sets_check(const char* who, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc) {
-  if (desc_bytes < 8 || desc_bytes > 8 * MT_MAX_WORDS || desc_bytes % 8 != 0)
-    return fail(BA_ERR_INVALID, "%s: desc_bytes %d is not a multiple of 8 in 8 .. %d", who, desc_bytes, 8 * MT_MAX_WORDS);
-  if (n_sets < 0 || n_sets > 65535) return fail(BA_ERR_INVALID, "%s: n_sets %d is outside 0 .. 65535", who, n_sets);
-  if (!set_off) return fail(BA_ERR_INVALID, "%s: null set_off", who);
-  if (set_off[0] != 0) return fail(BA_ERR_INVALID, "%s: set_off[0] must be 0", who);
-  for (int32_t s = 0; s < n_sets; ++s)
-    if (set_off[s + 1] < set_off[s]) return fail(BA_ERR_INVALID, "%s: set_off decreases at set %d", who, s);
-  if (set_off[n_sets] > 0 && !desc) return fail(BA_ERR_INVALID, "%s: null desc", who);
   return BA_OK;
 }
 // The tree becomes the handle's vocabulary: words numbered, depth measured, device arrays uploaded
@@ -4955,21 +4964,10 @@ template <int W>
 static void launch_bow_descend(ba_handle* h, unsigned grid, const BowArgs& a) {
   BA_LAUNCH(k_bow_descend<W>, dim3(grid), dim3(BW_THREADS), 0, h->stream, a);
 }
-#define BA_BY_WORDS(W_, fn, ...)                   \
-  switch (W_) {                                    \
-    case 1: fn<1>(__VA_ARGS__); break;             \
-    case 2: fn<2>(__VA_ARGS__); break;             \
-    case 3: fn<3>(__VA_ARGS__); break;             \
-    case 4: fn<4>(__VA_ARGS__); break;             \
-    case 5: fn<5>(__VA_ARGS__); break;             \
-    case 6: fn<6>(__VA_ARGS__); break;             \
-    case 7: fn<7>(__VA_ARGS__); break;             \
-    default: fn<8>(__VA_ARGS__); break;            \
-  }
 extern "C" int ba_vocab_train(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc,
                               const ba_vocab_options* opts, int32_t* train_word, int32_t* n_nodes, int32_t* n_words) {
   if (!h || !opts) return fail(BA_ERR_INVALID, "null argument");
-  if (int rc = bow_sets_check("ba_vocab_train", desc_bytes, n_sets, set_off, desc)) return rc;
+  if (int rc = desc_sets_check("ba_vocab_train", desc_bytes, n_sets, set_off, desc)) return rc;
   if (set_off[n_sets] >= (1LL << BW_ROW_BITS))
     return fail(BA_ERR_INVALID, "ba_vocab_train: rows %lld is not below 2^%d", (long long)set_off[n_sets], BW_ROW_BITS);
   if (opts->branching < 2 || opts->branching > BW_MAX_K) return fail(BA_ERR_INVALID, "ba_vocab_train: branching %d is outside 2 .. %d", opts->branching, BW_MAX_K);
@@ -4988,14 +4986,15 @@ extern "C" int ba_vocab_train(ba_handle* h, int32_t desc_bytes, int32_t n_sets, 
   if (rows >= min_split) {
     const size_t nr = (size_t)rows;
     const unsigned row_grid = (unsigned)((nr + BW_THREADS - 1) / BW_THREADS);
-    HIPCHECK(h->bw_desc.alloc(nr * W)); HIPCHECK(h->bw_i.alloc(3 * nr));
+    Scratch& sc = h->scratch;
+    HIPCHECK(sc.begin(h->stream));
     VocabArgs a = {};
-    a.desc = h->bw_desc.p; a.perm = h->bw_i.p; a.node = h->bw_i.p + nr; a.slot = h->bw_i.p + 2 * nr;
+    HIPCHECK(sc.put(h->stream, nr * W, desc, &a.desc)); HIPCHECK(sc.take(nr, &a.perm, &a.node, &a.slot));
+    const Scratch::Mark levels_from = sc.mark();      // what a level takes holds nothing across levels
     a.rows = rows; a.k = k; a.words = W;
     {
       std::vector<int> iota(nr);
       for (size_t r = 0; r < nr; ++r) iota[r] = (int)r;
-      HIPCHECK(hipMemcpyAsync(h->bw_desc.p, desc, nr * (size_t)desc_bytes, hipMemcpyHostToDevice, h->stream));
       HIPCHECK(hipMemcpyAsync(a.perm, iota.data(), nr * sizeof(int), hipMemcpyHostToDevice, h->stream));
       HIPCHECK(hipMemsetAsync(a.node, 0, nr * sizeof(int), h->stream));
       HIPCHECK(hipMemsetAsync(a.slot, 0xff, nr * sizeof(int), h->stream));
@@ -5011,14 +5010,12 @@ extern "C" int ba_vocab_train(ba_handle* h, int32_t desc_bytes, int32_t n_sets, 
       for (int n = 0; n < lvl_n; ++n) any |= (open[n] = count[lvl_begin + n] >= min_split) != 0;
       if (!any) break;
       const size_t ns = (size_t)lvl_n * k, n_cursor = v.child0.size() + ns;
-      // ints: size | child | changed | cursor | votes; 64-bit words: seed_key | centre; bytes: open | usable
-      HIPCHECK(h->bw_j.alloc(2 * ns + 1 + n_cursor + ns * BITS)); HIPCHECK(h->bw_l.alloc(ns + ns * W)); HIPCHECK(h->bw_b.alloc((size_t)lvl_n + ns));
-      a.lvl_begin = lvl_begin; a.lvl_n = lvl_n;
-      a.size = h->bw_j.p; int* d_child = h->bw_j.p + ns; a.child = d_child; a.changed = h->bw_j.p + 2 * ns; a.cursor = a.changed + 1; a.votes = a.cursor + n_cursor;
-      a.seed_key = h->bw_l.p; a.centre = h->bw_l.p + ns;
-      unsigned char* d_open = h->bw_b.p; a.open = d_open; a.usable = h->bw_b.p + lvl_n;
+      sc.rewind(levels_from);
+      int* d_child;
+      HIPCHECK(sc.take(ns, &a.size, &d_child)); HIPCHECK(sc.take(1, &a.changed)); HIPCHECK(sc.take(n_cursor, &a.cursor)); HIPCHECK(sc.take(ns * BITS, &a.votes));
+      HIPCHECK(sc.take(ns, &a.seed_key)); HIPCHECK(sc.take(ns * W, &a.centre)); HIPCHECK(sc.put(h->stream, (size_t)lvl_n, open.data(), &a.open)); HIPCHECK(sc.take(ns, &a.usable));
+      a.lvl_begin = lvl_begin; a.lvl_n = lvl_n; a.child = d_child;
       for (int j = 0; j < k; ++j) a.pre[j] = bw_mix(bw_mix(bw_mix(opts->seed + BW_GOLDEN) + (unsigned long long)d) + (unsigned long long)j);
-      HIPCHECK(hipMemcpyAsync(d_open, open.data(), (size_t)lvl_n, hipMemcpyHostToDevice, h->stream));
       HIPCHECK(hipMemsetAsync(a.seed_key, 0xff, ns * 8, h->stream));
       const unsigned slot_grid = (unsigned)((ns + BW_THREADS - 1) / BW_THREADS);
       BA_LAUNCH(k_vocab_seed_key, dim3(row_grid), dim3(BW_THREADS), 0, h->stream, a);
@@ -5122,8 +5119,7 @@ extern "C" int ba_vocab_get(ba_handle* h, int32_t* child0, int32_t* n_child, uin
 extern "C" int ba_vocab_set(ba_handle* h, int32_t desc_bytes, int32_t n_nodes, const int32_t* child0, const int32_t* n_child,
                             const uint8_t* node_desc, const int32_t* idf_q) {
   if (!h) return fail(BA_ERR_INVALID, "null handle");
-  if (desc_bytes < 8 || desc_bytes > 8 * MT_MAX_WORDS || desc_bytes % 8 != 0)
-    return fail(BA_ERR_INVALID, "ba_vocab_set: desc_bytes %d is not a multiple of 8 in 8 .. %d", desc_bytes, 8 * MT_MAX_WORDS);
+  if (int rc = desc_bytes_check("ba_vocab_set", desc_bytes)) return rc;
   if (n_nodes < 1) return fail(BA_ERR_INVALID, "ba_vocab_set: n_nodes %d is below 1", n_nodes);
   if (!child0 || !n_child || !node_desc || !idf_q) return fail(BA_ERR_INVALID, "ba_vocab_set: null argument");
   // breadth-first and contiguous: walking the nodes in order, the children of the inner nodes tile 1 .. n_nodes - 1 exactly
@@ -5166,7 +5162,7 @@ extern "C" int ba_vocab_set(ba_handle* h, int32_t desc_bytes, int32_t n_nodes, c
 extern "C" int ba_bow_transform(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc,
                                 int32_t weighting, int32_t* desc_word, int64_t* vec_off, int32_t* vec_word, int32_t* vec_val) {
   if (!h) return fail(BA_ERR_INVALID, "null handle");
-  if (int rc = bow_sets_check("ba_bow_transform", desc_bytes, n_sets, set_off, desc)) return rc;
+  if (int rc = desc_sets_check("ba_bow_transform", desc_bytes, n_sets, set_off, desc)) return rc;
   if (weighting != BA_BOW_TF_IDF && weighting != BA_BOW_TF)
     return fail(BA_ERR_INVALID, "ba_bow_transform: weighting %d is neither BA_BOW_TF_IDF (0) nor BA_BOW_TF (1)", weighting);
   for (int32_t s = 0; s < n_sets; ++s)
@@ -5183,15 +5179,13 @@ extern "C" int ba_bow_transform(ba_handle* h, int32_t desc_bytes, int32_t n_sets
   if (nr == 0) return BA_OK;
   if (set_device(h)) return BA_ERR_HIP;
   const size_t batch = std::max<size_t>(1, std::min(ns, ((size_t)1 << 26) / nw));
-  // ints: word | out_word | out_val | nnz; dense counts of a batch of sets in bw_j; set_off in bw_l
-  HIPCHECK(h->bw_desc.alloc(nr * W)); HIPCHECK(h->bw_i.alloc(3 * nr + ns)); HIPCHECK(h->bw_j.alloc(batch * nw)); HIPCHECK(h->bw_l.alloc(ns + 1));
+  Scratch& sc = h->scratch;
+  HIPCHECK(sc.begin(h->stream));
   BowArgs a = {};
-  a.desc = h->bw_desc.p; a.set_off = (const long long*)h->bw_l.p;
+  HIPCHECK(sc.put(h->stream, nr * W, desc, &a.desc)); HIPCHECK(sc.put(h->stream, ns + 1, set_off, &a.set_off));
+  HIPCHECK(sc.take(nr, &a.word, &a.out_word, &a.out_val)); HIPCHECK(sc.take(ns, &a.nnz)); HIPCHECK(sc.take(batch * nw, &a.cnt));      // cnt: dense counts of a batch of sets
   a.child0 = h->bw_child0.p; a.n_child = h->bw_nchild.p; a.node_desc = h->bw_ndesc.p; a.word_of_node = h->bw_wordof.p; a.idf_q = h->bw_idf.p;
   a.rows = (int)nr; a.n_sets = n_sets; a.n_words = v.n_words; a.tf = weighting == BA_BOW_TF;
-  a.word = h->bw_i.p; a.out_word = h->bw_i.p + nr; a.out_val = h->bw_i.p + 2 * nr; a.nnz = h->bw_i.p + 3 * nr; a.cnt = h->bw_j.p;
-  HIPCHECK(hipMemcpyAsync(h->bw_desc.p, desc, nr * (size_t)desc_bytes, hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipMemcpyAsync(h->bw_l.p, set_off, (ns + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
   BA_BY_WORDS(W, launch_bow_descend, h, (unsigned)((nr + BW_THREADS - 1) / BW_THREADS), a);
   for (size_t s0 = 0; s0 < ns; s0 += batch) {
     a.s0 = (int)s0; a.s1 = (int)std::min(ns, s0 + batch);
@@ -5259,27 +5253,18 @@ extern "C" int ba_bow_score(ba_handle* h, int32_t nq, const int64_t* q_off, cons
   if (n_chunks > 65535 || n_keys > 0x7fffffffULL)
     return fail(BA_ERR_INVALID, "ba_bow_score: %zu database chunks of %d vectors times %zu words is more than one call indexes", n_chunks, chunk, nw);
   if (set_device(h)) return BA_ERR_HIP;
-  // 64-bit words: q_off | d_off | part; ints: q_word | q_val | d_word | d_val | inv_j | inv_v | db_end | top_idx | top_score;
-  // bw_j: hist | cursor
   const size_t n_part = nqs * n_chunks * (size_t)top_k;
-  HIPCHECK(h->bw_l.alloc(nqs + 1 + nds + 1 + n_part)); HIPCHECK(h->bw_i.alloc(2 * qn + 4 * dn + nqs + 2 * kq)); HIPCHECK(h->bw_j.alloc(2 * n_keys + 1));
-  if (score) HIPCHECK(h->bw_dense.alloc(nqs * nds));
+  Scratch& sc = h->scratch;
+  HIPCHECK(sc.begin(h->stream));
   ScoreArgs a = {};
-  long long* d_qoff = (long long*)h->bw_l.p; long long* d_doff = d_qoff + nqs + 1;
-  a.q_off = d_qoff; a.d_off = d_doff; a.part = h->bw_l.p + nqs + 1 + nds + 1;
-  int* p = h->bw_i.p;
-  int* d_qw = p; int* d_qv = p + qn; int* d_dw = p + 2 * qn; int* d_dv = d_dw + dn;
-  a.q_word = d_qw; a.q_val = d_qv; a.d_word = d_dw; a.d_val = d_dv; a.inv_j = d_dv + dn; a.inv_v = a.inv_j + dn;
-  int* d_end = a.inv_v + dn; a.db_end = db_end ? d_end : nullptr; a.top_idx = d_end + nqs; a.top_score = a.top_idx + kq;
-  a.hist = h->bw_j.p; a.cursor = h->bw_j.p + n_keys + 1; a.dense = score ? h->bw_dense.p : nullptr;
+  HIPCHECK(sc.put(h->stream, nqs + 1, q_off, &a.q_off)); HIPCHECK(sc.put(h->stream, nds + 1, d_off, &a.d_off));
+  HIPCHECK(sc.put(h->stream, qn, q_word, &a.q_word)); HIPCHECK(sc.put(h->stream, qn, q_val, &a.q_val));
+  HIPCHECK(sc.put(h->stream, dn, d_word, &a.d_word)); HIPCHECK(sc.put(h->stream, dn, d_val, &a.d_val));
+  if (db_end) HIPCHECK(sc.put(h->stream, nqs, db_end, &a.db_end));
+  HIPCHECK(sc.take(n_part, &a.part)); HIPCHECK(sc.take(dn, &a.inv_j, &a.inv_v)); HIPCHECK(sc.take(kq, &a.top_idx, &a.top_score));
+  HIPCHECK(sc.take(n_keys + 1, &a.hist)); HIPCHECK(sc.take(n_keys, &a.cursor));
+  if (score) HIPCHECK(sc.take(nqs * nds, &a.dense));
   a.nq = nq; a.nd = nd; a.n_words = (int)nw; a.chunk = chunk; a.n_chunks = (int)n_chunks; a.top_k = top_k; a.d_nnz = (long long)dn; a.n_keys = (long long)n_keys;
-  HIPCHECK(hipMemcpyAsync(d_qoff, q_off, (nqs + 1) * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipMemcpyAsync(d_doff, d_off, (nds + 1) * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipMemcpyAsync(d_qw, q_word, qn * 4, hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipMemcpyAsync(d_qv, q_val, qn * 4, hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipMemcpyAsync(d_dw, d_word, dn * 4, hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipMemcpyAsync(d_dv, d_val, dn * 4, hipMemcpyHostToDevice, h->stream));
-  if (db_end) HIPCHECK(hipMemcpyAsync(d_end, db_end, nqs * 4, hipMemcpyHostToDevice, h->stream));
   HIPCHECK(hipMemsetAsync(a.hist, 0, (n_keys + 1) * sizeof(int), h->stream));
   const unsigned entry_grid = (unsigned)((dn + BW_THREADS - 1) / BW_THREADS);
   BA_LAUNCH(k_bow_inv_hist, dim3(entry_grid), dim3(BW_THREADS), 0, h->stream, a);
@@ -5294,7 +5279,6 @@ extern "C" int ba_bow_score(ba_handle* h, int32_t nq, const int64_t* q_off, cons
   BA_SYNC(h);
   return BA_OK;
 }
-#undef BA_BY_WORDS
 
 // ------------------------------------------------------------------------ feature tracks
 // ba_build_tracks (csrc/ba_trackbuild.hpp).  Needs no problem.
@@ -5306,20 +5290,6 @@ extern "C" int ba_default_trackbuild_options(ba_trackbuild_options* o) {
 static_assert(TB_DROP == BA_TRACKS_DROP && TB_FIRST == BA_TRACKS_FIRST && TB_IN_TRACK == BA_TRACKBUILD_IN_TRACK &&
               TB_ISOLATED == BA_TRACKBUILD_ISOLATED && TB_CONFLICT == BA_TRACKBUILD_CONFLICT && TB_SHORT == BA_TRACKBUILD_SHORT,
               "device codes of ba_build_tracks (ba_trackbuild.hpp)");
-// out[i] = sum of in[0 .. i), out[n] = total, for any n < 2^31: k_scan_* passes of at most 1024 * SETUP_SCAN_BLOCK items, the
-// running total carried into the next pass through its block sums.  in and out are different arrays.
-static int tb_scan(ba_handle* h, const int* in, size_t n, int* bsum, int* out) {
-  const size_t pass = (size_t)1024 * SETUP_SCAN_BLOCK;
-  if (n == 0) { HIPCHECK(hipMemsetAsync(out, 0, sizeof(int), h->stream)); return BA_OK; }
-  for (size_t c0 = 0; c0 < n; c0 += pass) {
-    const int nc = (int)std::min(pass, n - c0), nb = (nc + SETUP_SCAN_BLOCK - 1) / SETUP_SCAN_BLOCK;
-    BA_LAUNCH(k_scan_block_sums, dim3(nb), dim3(1024), 0, h->stream, in + c0, nc, bsum);
-    BA_LAUNCH(k_scan_top, dim3(1), dim3(1024), 0, h->stream, bsum, nb);
-    if (c0 > 0) BA_LAUNCH(k_tb_scan_base, dim3(1), dim3(1024), 0, h->stream, bsum, nb, (const int*)(out + c0));   // = the previous pass's total
-    BA_LAUNCH(k_scan_final, dim3(nb), dim3(1024), 0, h->stream, in + c0, nc, (const int*)bsum, out + c0);
-  }
-  return BA_OK;
-}
 extern "C" int ba_build_tracks(ba_handle* h, int32_t n_images, const int64_t* kp_off, int64_t n_edges, const int32_t* edge_a,
                                const int32_t* edge_b, const uint8_t* edge_keep, const ba_trackbuild_options* opts, int32_t* node_label,
                                int32_t* node_track, uint8_t* node_status, int64_t* track_off, int32_t* track_node, int64_t* counts) {
@@ -5355,34 +5325,30 @@ extern "C" int ba_build_tracks(ba_handle* h, int32_t n_images, const int64_t* kp
   int cap = 2;
   while (cap - 2 < 31 && ((size_t)1 << (cap - 2)) < std::max<size_t>(N, 2)) ++cap;
   if (opts->max_rounds > 0) cap = opts->max_rounds;
-  // ints: ea | eb | parent | img | cnt | fill | seg_len (later: out) | seg_off (later: pos) [N + 1] | is_comp | comp_id [N + 1] | seg |
-  //       sorted | node_track | track_node (twelve of N, two with one more) | seven arrays of H: comp_root, comp_off, n_conf, is_track, trk_id, big, giant | track_off [H] |
-  //       bsum [1026] | flag | lists [2]
-  HIPCHECK(h->tb_i.alloc(2 * E + 12 * N + 2 + 8 * H + 1026 + 3));
-  HIPCHECK(h->tb_b.alloc(2 * E + 2 * N + 1));
-  HIPCHECK(h->tb_l.alloc(ni + 1 + 8));
-  int* p = h->tb_i.p;
-  int* d_ea = p; p += E; int* d_eb = p; p += E;
-  int* d_parent = p; p += N; int* d_img = p; p += N; int* d_cnt = p; p += N; int* d_fill = p; p += N;
-  int* d_seglen = p; p += N; int* d_segoff = p; p += N + 1; int* d_iscomp = p; p += N; int* d_compid = p; p += N + 1;
-  int* d_seg = p; p += N; int* d_sorted = p; p += N; int* d_ntrack = p; p += N; int* d_tnode = p; p += N;
-  int* d_croot = p; p += H; int* d_coff = p; p += H; int* d_nconf = p; p += H; int* d_istrack = p; p += H; int* d_trkid = p; p += H;
-  int* d_big = p; p += H; int* d_giant = p; p += H; int* d_toff = p; p += H;
-  int* d_bsum = p; p += 1026; int* d_flag = p; p += 1; int* d_lists = p; p += 2;
-  int* d_out = d_seglen; int* d_pos = d_segoff;
-  unsigned char* d_keep = h->tb_b.p; unsigned char* d_use = d_keep + E; unsigned char* d_status = d_use + E; unsigned char* d_conf = d_status + N;
-  long long* d_kpoff = (long long*)h->tb_l.p;
-  unsigned long long* d_stat = h->tb_l.p + ni + 1;       // [0] smallest bad edge, [3 .. 5] k_tb_comp_verdict, [6] same-image edges
+  Scratch& sc = h->scratch;
+  HIPCHECK(sc.begin(h->stream));
+  const int *d_ea, *d_eb;
+  const unsigned char* d_keep = nullptr;
+  const long long* d_kpoff;
+  int *d_parent, *d_img, *d_cnt, *d_seglen, *d_segoff, *d_iscomp, *d_compid, *d_seg, *d_sorted, *d_ntrack, *d_tnode;
+  int *d_croot, *d_coff, *d_nconf, *d_istrack, *d_trkid, *d_big, *d_giant, *d_toff, *d_bsum, *d_flag, *d_lists;
+  unsigned char *d_use, *d_status, *d_conf;
+  unsigned long long* d_stat;                            // [0] smallest bad edge, [3 .. 5] k_tb_comp_verdict, [6] same-image edges
+  HIPCHECK(sc.put(h->stream, ni + 1, kp_off, &d_kpoff)); HIPCHECK(sc.put(h->stream, E, edge_a, &d_ea)); HIPCHECK(sc.put(h->stream, E, edge_b, &d_eb));
+  if (edge_keep) HIPCHECK(sc.put(h->stream, E, edge_keep, &d_keep));
+  HIPCHECK(sc.take(N, &d_parent, &d_img, &d_seglen, &d_iscomp, &d_seg, &d_sorted, &d_ntrack, &d_tnode));
+  HIPCHECK(sc.take(2 * N, &d_cnt)); HIPCHECK(sc.take(N + 1, &d_segoff, &d_compid));      // cnt | fill: cleared together
+  HIPCHECK(sc.take(H, &d_croot, &d_coff, &d_nconf, &d_istrack, &d_trkid, &d_big, &d_giant, &d_toff));
+  HIPCHECK(sc.take(1026, &d_bsum)); HIPCHECK(sc.take(1, &d_flag)); HIPCHECK(sc.take(2, &d_lists));
+  HIPCHECK(sc.take(E, &d_use)); HIPCHECK(sc.take(N, &d_status)); HIPCHECK(sc.take(N + 1, &d_conf)); HIPCHECK(sc.take(8, &d_stat));
+  int* const d_fill = d_cnt + N;
+  int* const d_out = d_seglen; int* const d_pos = d_segoff;      // (seg_len and seg_off are used up when out and pos are written)
   auto grid = [](size_t items) { return dim3((unsigned)((items + TB_THREADS - 1) / TB_THREADS)); };
-  HIPCHECK(hipMemcpyAsync(d_kpoff, kp_off, (ni + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
   HIPCHECK(hipMemsetAsync(d_stat, 0, 8 * sizeof(unsigned long long), h->stream));
   HIPCHECK(hipMemsetAsync(d_stat, 0xff, sizeof(unsigned long long), h->stream));
   if (N > 0) BA_LAUNCH(k_tb_init, grid(N), dim3(TB_THREADS), 0, h->stream, n, (const long long*)d_kpoff, n_images, d_parent, d_img, d_ntrack, d_status);
   int rounds = 0;
   if (E > 0) {
-    HIPCHECK(hipMemcpyAsync(d_ea, edge_a, E * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemcpyAsync(d_eb, edge_b, E * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    if (edge_keep) HIPCHECK(hipMemcpyAsync(d_keep, edge_keep, E, hipMemcpyHostToDevice, h->stream));
     BA_LAUNCH(k_tb_edges, grid(E), dim3(TB_THREADS), 0, h->stream, (const int*)d_ea, (const int*)d_eb, (const unsigned char*)(edge_keep ? d_keep : nullptr),
               (long long)E, n, (const int*)d_img, d_use, d_stat, d_stat + 6);
     unsigned long long bad = 0;
@@ -5409,8 +5375,8 @@ extern "C" int ba_build_tracks(ba_handle* h, int32_t n_images, const int64_t* kp
     HIPCHECK(hipMemsetAsync(d_cnt, 0, 2 * N * sizeof(int), h->stream));        // cnt | fill
     BA_LAUNCH(k_tb_sizes, grid(N), dim3(TB_THREADS), 0, h->stream, n, label, d_cnt);
     BA_LAUNCH(k_tb_roots, grid(N), dim3(TB_THREADS), 0, h->stream, n, label, (const int*)d_cnt, d_seglen, d_iscomp);
-    if (int rc = tb_scan(h, d_seglen, N, d_bsum, d_segoff)) return rc;
-    if (int rc = tb_scan(h, d_iscomp, N, d_bsum, d_compid)) return rc;
+    if (int rc = dev_scan(h, d_seglen, N, d_bsum, d_segoff)) return rc;
+    if (int rc = dev_scan(h, d_iscomp, N, d_bsum, d_compid)) return rc;
     HIPCHECK(hipMemcpyAsync(&M, d_segoff + N, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipMemcpyAsync(&C, d_compid + N, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     BA_SYNC(h);
@@ -5433,7 +5399,7 @@ extern "C" int ba_build_tracks(ba_handle* h, int32_t n_images, const int64_t* kp
     BA_SYNC(h);
     for (int g = 0; g < n_giant; ++g) {        // (d_out and d_pos are free here: seg_len and seg_off have been used up)
       BA_LAUNCH(k_tb_giant_flags, grid(N), dim3(TB_THREADS), 0, h->stream, n, label, (const int*)(d_giant + g), (const int*)d_croot, d_out);
-      if (int rc = tb_scan(h, d_out, N, d_bsum, d_pos)) return rc;
+      if (int rc = dev_scan(h, d_out, N, d_bsum, d_pos)) return rc;
       BA_LAUNCH(k_tb_giant_place, grid(N), dim3(TB_THREADS), 0, h->stream, n, (const int*)d_out, (const int*)d_pos, (const int*)(d_giant + g), (const int*)d_coff,
                 d_sorted);
     }
@@ -5441,10 +5407,10 @@ extern "C" int ba_build_tracks(ba_handle* h, int32_t n_images, const int64_t* kp
               d_conf, d_nconf);
     BA_LAUNCH(k_tb_comp_verdict, grid(Cs), dim3(TB_THREADS), 0, h->stream, C, (const int*)d_coff, (const int*)d_nconf, (int)opts->conflict, (int)opts->min_length,
               d_istrack, d_stat);
-    if (int rc = tb_scan(h, d_istrack, Cs, d_bsum, d_trkid)) return rc;
+    if (int rc = dev_scan(h, d_istrack, Cs, d_bsum, d_trkid)) return rc;
     BA_LAUNCH(k_tb_out_flags, grid(Ms), dim3(TB_THREADS), 0, h->stream, M, (const int*)d_sorted, label, (const int*)d_compid, (const int*)d_istrack,
               (const unsigned char*)d_conf, d_out);
-    if (int rc = tb_scan(h, d_out, Ms, d_bsum, d_pos)) return rc;
+    if (int rc = dev_scan(h, d_out, Ms, d_bsum, d_pos)) return rc;
     BA_LAUNCH(k_tb_emit, grid(Ms), dim3(TB_THREADS), 0, h->stream, M, (const int*)d_sorted, label, (const int*)d_compid, (const int*)d_coff, (const int*)d_istrack,
               (const int*)d_trkid, (const int*)d_nconf, (const unsigned char*)d_conf, (const int*)d_pos, (int)opts->conflict, d_tnode, d_toff, d_ntrack, d_status);
     HIPCHECK(hipMemcpyAsync(&T, d_trkid + C, sizeof(int), hipMemcpyDeviceToHost, h->stream));

@@ -313,11 +313,12 @@ SYMBOLS = {
     "ba_get_stat": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
     "ba_debug_occupy": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double]),
     "ba_debug_layout": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "ba_debug_scratch_fill": (C.c_int, [C.c_void_p, C.c_int32]),
 }
 # enum ba_stat (include/ba_hip.h)
 STATS = {"window_mw_launches": 0, "window_lm_launches": 1, "window_fallbacks": 2, "precond_builds": 3, "precond_reuses": 4, "banded": 5,
          "cap_floor_raises": 6, "ipc_exchanges": 7, "pixels_f32": 8, "held_params": 9,
-         "prior_blocks": 10, "shared_groups": 11}
+         "prior_blocks": 10, "shared_groups": 11, "scratch_bytes": 12, "scratch_allocs": 13}
 
 
 def held_camera_mask(cams, n_cams, nb=6):
@@ -464,9 +465,9 @@ def _pair_call(fn, handle, inputs, o, spec):
     return out
 
 
-def _match_inputs(sets, pairs):
-    """What ba_match_descriptors and ba_match_guided take of (sets, pairs): the sets as arrays, their width, set_off, the
-    concatenated descriptors, pair_query, pair_train and the number of output rows."""
+def _desc_sets(sets, width=None):
+    """What the matching and place recognition calls take of a list of descriptor sets: the sets as arrays, their width, set_off and the
+    concatenated descriptors.  width: the width an empty list stands for, and, when given, the one every set must have."""
     arrs = [np.asarray(a) for a in sets]
     for a in arrs:
         if a.dtype != np.uint8 or a.ndim != 2:
@@ -474,15 +475,24 @@ def _match_inputs(sets, pairs):
     widths = {a.shape[1] for a in arrs}
     if len(widths) > 1:
         raise ValueError(f"descriptor sets of different widths: {sorted(widths)} bytes")
+    if widths and width is not None and widths != {width}:
+        raise ValueError(f"descriptor sets of {widths.pop()} bytes, the vocabulary has {width}")
+    width = widths.pop() if widths else (32 if width is None else width)
+    set_off = np.zeros(len(arrs) + 1, dtype=np.int64)
+    set_off[1:] = np.cumsum([a.shape[0] for a in arrs])
+    desc = np.ascontiguousarray(np.concatenate(arrs, axis=0)) if arrs else np.zeros((0, width), dtype=np.uint8)
+    return arrs, width, set_off, desc
+
+
+def _match_inputs(sets, pairs):
+    """What ba_match_descriptors and ba_match_guided take of (sets, pairs): the sets as arrays, their width, set_off, the
+    concatenated descriptors, pair_query, pair_train and the number of output rows."""
+    arrs, width, set_off, desc = _desc_sets(sets)
     if pairs is None:
         if len(arrs) not in (0, 2):
             raise ValueError("pairs=None needs exactly two sets (query, train)")
         pairs = [(0, 1)] if arrs else []
     pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-    width = widths.pop() if widths else 32
-    set_off = np.zeros(len(arrs) + 1, dtype=np.int64)
-    set_off[1:] = np.cumsum([a.shape[0] for a in arrs])
-    desc = np.ascontiguousarray(np.concatenate(arrs, axis=0)) if arrs else np.zeros((0, width), dtype=np.uint8)
     ok = pr.shape[0] == 0 or (pr.min() >= 0 and pr.max() < len(arrs))
     rows = int(sum(arrs[q].shape[0] for q in pr[:, 0])) if ok else 0      # (a bad index is the library's to refuse: it names the field)
     return arrs, width, set_off, desc, np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1]), rows
@@ -516,25 +526,6 @@ def _node_array(x, name):
     if len(bad):
         raise ValueError(f"{name}[{int(bad[0])}] = {int(wide[bad[0]])} is not a node number: it does not fit int32")
     return np.ascontiguousarray(wide, dtype=np.int32)
-
-
-def _bow_sets(sets, width=None):
-    """What the place recognition calls take of a list of descriptor sets: the sets as arrays, their width, set_off and the
-    concatenated descriptors.  width: the width an empty list stands for, and, when given, the one every set must have."""
-    arrs = [np.asarray(a) for a in sets]
-    for a in arrs:
-        if a.dtype != np.uint8 or a.ndim != 2:
-            raise ValueError(f"every descriptor set must be a 2-D uint8 array, not {a.dtype} with shape {a.shape}")
-    widths = {a.shape[1] for a in arrs}
-    if len(widths) > 1:
-        raise ValueError(f"descriptor sets of different widths: {sorted(widths)} bytes")
-    if widths and width is not None and widths != {width}:
-        raise ValueError(f"descriptor sets of {widths.pop()} bytes, the vocabulary has {width}")
-    width = widths.pop() if widths else (32 if width is None else width)
-    set_off = np.zeros(len(arrs) + 1, dtype=np.int64)
-    set_off[1:] = np.cumsum([a.shape[0] for a in arrs])
-    desc = np.ascontiguousarray(np.concatenate(arrs, axis=0)) if arrs else np.zeros((0, width), dtype=np.uint8)
-    return arrs, width, set_off, desc
 
 
 def _bow_csr(v, what):
@@ -1142,7 +1133,7 @@ class Solver:
         """ba_vocab_train: a vocabulary tree of the descriptor sets (one set per training image) by hierarchical k-majority;
         it becomes the handle's vocabulary.  opts: branching, levels, iters, min_split, seed.  Returns vocabulary()'s dict plus
         train_word (rows,) int32, the word of every training row."""
-        arrs, width, set_off, desc = _bow_sets(sets)
+        arrs, width, set_off, desc = _desc_sets(sets)
         o = vocab_options(**opts)
         train_word = np.zeros(desc.shape[0], dtype=np.int32)
         nn, nw = C.c_int32(0), C.c_int32(0)
@@ -1196,7 +1187,7 @@ class Solver:
         if weighting not in BOW_WEIGHTING:
             raise ValueError(f"unknown weighting {weighting!r}: expected one of {', '.join(map(repr, BOW_WEIGHTING))}")
         sets = list(sets)          # (an empty list stands for no rows of the vocabulary's width; a wrong width is the library's to refuse)
-        arrs, width, set_off, desc = _bow_sets(sets, None if sets else self.vocabulary_size()["desc_bytes"] or None)
+        arrs, width, set_off, desc = _desc_sets(sets, None if sets else self.vocabulary_size()["desc_bytes"] or None)
         rows = desc.shape[0]
         word, vw, vv = (np.zeros(rows, dtype=np.int32) for _ in range(3))
         vec_off = np.zeros(len(arrs) + 1, dtype=np.int64)
@@ -1429,6 +1420,10 @@ class Solver:
         _check(self._lib.ba_debug_layout(self._h, which, buf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
         out = buf[:n.value].copy()
         return dict(zip(self.LAYOUT_SCALARS, (int(v) for v in out))) if name == "scalars" else out
+
+    def debug_scratch_fill(self, byte):
+        """Test hook (ba_debug_scratch_fill): every byte of the scratch arena set to `byte`."""
+        _check(self._lib.ba_debug_scratch_fill(self._h, int(byte)))
 
     def debug_occupy(self, n_workgroups, lds_bytes, milliseconds):
         """Test hook (ba_debug_occupy): idle workgroups on a second stream hold compute units' LDS for a bounded time."""

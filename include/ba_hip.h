@@ -169,7 +169,10 @@ enum ba_stat {
   BA_STAT_COUNT = 10,               /* statistics 0 - 9: the set callers of earlier releases size their arrays by */
   BA_STAT_PRIOR_BLOCKS = 10,        /* cameras + points of the calling rank that carry a non-zero prior block (ba_set_priors) */
   BA_STAT_SHARED_GROUPS = 11,       /* groups of two or more cameras that share their intrinsics (ba_set_shared_intrinsics) */
-  BA_STAT_END = 12                  /* one past the last statistic ba_get_stat answers */
+  BA_STAT_SCRATCH_BYTES = 12,       /* device memory of the calls that need no problem (two-view RANSAC, matching, ORB, pose graph, place
+                                       recognition, track building), now: it follows the largest call so far, not their sum */
+  BA_STAT_SCRATCH_ALLOCS = 13,      /* device allocations the scratch arena has made since ba_create; constant once calls repeat */
+  BA_STAT_END = 14                  /* one past the last statistic ba_get_stat answers */
 };
 
 const char* ba_last_error(void);
@@ -180,6 +183,10 @@ int ba_get_stat(ba_handle* h, int32_t which, int64_t* value);
  * lds_bytes of LDS each idle for `milliseconds` (at most 2000) of the device's wall clock, then leave.  Returns at once.
  * Lets a test hold the units the window solver's workgroups would need (tests/test_gpu_small.py). */
 int ba_debug_occupy(ba_handle* h, int32_t n_workgroups, int32_t lds_bytes, double milliseconds);
+/* Test hook: drains the stream and sets every byte of the scratch arena to `byte` (its low 8 bits).  The calls that use the
+ * arena promise to read nothing they did not upload, clear or compute themselves; a test fills the arena with 0xff and with
+ * 0x00 and expects the same results. */
+int ba_debug_scratch_fill(ba_handle* h, int32_t byte);
 /* Test hook: one array of the layout ba_set_problem built (the two observation orderings, their offsets, windows, grid
  * scalars), copied to out; `which` as listed in csrc/ba_hip.hip.  Lets a test compare the device build of large problems
  * (csrc/ba_setup.hpp) with the host build (BA_SETUP=host) element by element. */

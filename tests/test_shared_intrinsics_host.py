@@ -26,7 +26,8 @@ def test_header_declares_the_function_and_the_stat():
     h = _header()
     assert re.search(r"int\s+ba_set_shared_intrinsics\(ba_handle\*\s*h,\s*const int32_t\*\s*cam_group\);", h)
     stats = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"BA_STAT_(\w+)\s*=\s*(\d+)", h)}
-    assert stats["shared_groups"] == 11 and stats["end"] == 12 and stats["count"] == 10
+    assert stats["shared_groups"] == 11 and stats["count"] == 10
+    assert stats["scratch_bytes"] == 12 and stats["scratch_allocs"] == 13 and stats["end"] == 14      # the scratch arena's two follow it
     assert hip_backend.STATS["shared_groups"] == 11
     assert max(hip_backend.STATS.values()) == stats["end"] - 1
     res, args = hip_backend.SYMBOLS["ba_set_shared_intrinsics"]
