@@ -46,6 +46,7 @@
 #include "ba_homography.hpp"
 #include "ba_match.hpp"
 #include "ba_match_guided.hpp"
+#include "ba_match_l2.hpp"
 #include "ba_orb.hpp"
 #include "ba_posegraph.hpp"
 #include "ba_sim3.hpp"
@@ -4026,13 +4027,18 @@ extern "C" int ba_default_match_options(ba_match_options* o) {
   o->max_distance = -1;
   return BA_OK;
 }
+// What the split rule takes of a partial kernel: queries per workgroup, train descriptors per LDS tile, the shortest split, and
+// the waves a workgroup spends on 64 queries
+struct MatchGeom { int block, tile, min_split, waves_per_row; };
+constexpr MatchGeom MT_GEOM = {MT_THREADS, MT_TILE, MT_MIN_SPLIT, 1};      // k_match_partial, k_guided_partial
+constexpr MatchGeom ML_GEOM = {ML_BLOCK, ML_TILE, ML_MIN_SPLIT, 2};        // k_l2_partial
 // Train splits of one entry.  `want` splits are asked for (the call-wide wish, or the test hook's number); a split is whole
-// tiles and at least MT_MIN_SPLIT descriptors unless it is the whole set; at most MT_MAX_SPLITS.
-static void match_plan(MatchPair& e, int want) {
-  if (e.nt == 0 || e.nq == 0) { e.split_len = MT_TILE; e.n_splits = 0; return; }   // nothing to launch for the entry
-  const int tiles = (e.nt + MT_TILE - 1) / MT_TILE;
-  const int n = std::max(1, std::min({want, MT_MAX_SPLITS, tiles / (MT_MIN_SPLIT / MT_TILE)}));
-  e.split_len = (tiles + n - 1) / n * MT_TILE;
+// tiles and at least min_split descriptors unless it is the whole set; at most MT_MAX_SPLITS.
+static void match_plan(MatchPair& e, int want, const MatchGeom& g) {
+  if (e.nt == 0 || e.nq == 0) { e.split_len = g.tile; e.n_splits = 0; return; }   // nothing to launch for the entry
+  const int tiles = (e.nt + g.tile - 1) / g.tile;
+  const int n = std::max(1, std::min({want, MT_MAX_SPLITS, tiles / (g.min_split / g.tile)}));
+  e.split_len = (tiles + n - 1) / n * g.tile;
   e.n_splits = (e.nt + e.split_len - 1) / e.split_len;
 }
 // The statement fn<W>(...) with W = W_, the 64-bit words of a descriptor (1 .. MT_MAX_WORDS = 8)
@@ -4051,14 +4057,19 @@ template <int W>
 static void launch_match_partial(ba_handle* h, dim3 grid, const MatchArgs& a) {
   BA_LAUNCH(k_match_partial<W>, grid, dim3(MT_THREADS), 0, h->stream, a);
 }
-static int desc_bytes_check(const char* who, int32_t desc_bytes) {
-  if (desc_bytes < 8 || desc_bytes > 8 * MT_MAX_WORDS || desc_bytes % 8 != 0)
-    return fail(BA_ERR_INVALID, "%s: desc_bytes %d is not a multiple of 8 in 8 .. %d", who, desc_bytes, 8 * MT_MAX_WORDS);
+// The widths a call takes: the multiples of `unit` bytes in unit .. most
+struct WidthRule { int unit, most; };
+constexpr WidthRule MT_WIDTHS = {8, 8 * MT_MAX_WORDS};      // binary descriptors: matching, guided matching, place recognition
+constexpr WidthRule ML_WIDTHS = {32, 32 * ML_MAX_W};        // ba_match_l2
+static int desc_bytes_check(const char* who, int32_t desc_bytes, const WidthRule& w = MT_WIDTHS) {
+  if (desc_bytes < w.unit || desc_bytes > w.most || desc_bytes % w.unit != 0)
+    return fail(BA_ERR_INVALID, "%s: desc_bytes %d is not a multiple of %d in %d .. %d", who, desc_bytes, w.unit, w.unit, w.most);
   return BA_OK;
 }
 // What the calls that take descriptor sets (matching, place recognition) refuse alike; `who` is the call the message names.
-static int desc_sets_check(const char* who, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc) {
-  if (int rc = desc_bytes_check(who, desc_bytes)) return rc;
+static int desc_sets_check(const char* who, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc,
+                           const WidthRule& w = MT_WIDTHS) {
+  if (int rc = desc_bytes_check(who, desc_bytes, w)) return rc;
   if (n_sets < 0 || n_sets > 65535) return fail(BA_ERR_INVALID, "%s: n_sets %d is outside 0 .. 65535", who, n_sets);
   if (!set_off) return fail(BA_ERR_INVALID, "%s: null set_off", who);
   if (set_off[0] != 0) return fail(BA_ERR_INVALID, "%s: set_off[0] must be 0", who);
@@ -4067,10 +4078,10 @@ static int desc_sets_check(const char* who, int32_t desc_bytes, int32_t n_sets, 
   if (set_off[n_sets] > 0 && !desc) return fail(BA_ERR_INVALID, "%s: null desc", who);
   return BA_OK;
 }
-// What ba_match_descriptors and ba_match_guided refuse beyond that
+// What ba_match_descriptors, ba_match_guided and ba_match_l2 (with ML_WIDTHS) refuse beyond that
 static int match_check(const char* who, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc, int32_t n_pairs,
-                       const int32_t* pair_query, const int32_t* pair_train, double ratio) {
-  if (int rc = desc_sets_check(who, desc_bytes, n_sets, set_off, desc)) return rc;
+                       const int32_t* pair_query, const int32_t* pair_train, double ratio, const WidthRule& w = MT_WIDTHS) {
+  if (int rc = desc_sets_check(who, desc_bytes, n_sets, set_off, desc, w)) return rc;
   if (n_pairs < 0 || n_pairs > 65535) return fail(BA_ERR_INVALID, "%s: n_pairs %d is outside 0 .. 65535", who, n_pairs);
   if (!std::isfinite(ratio)) return fail(BA_ERR_INVALID, "%s: ratio must be finite", who);
   for (int32_t s = 0; s < n_sets; ++s)
@@ -4115,30 +4126,30 @@ static void match_entries(MatchTable& m, const int64_t* set_off, int32_t n_pairs
   }
   if (row_off) row_off[np] = m.rows;
 }
-// The splits of every entry (rows > 0).  Two waves per SIMD over the whole call: want = ceil(8 n_cu / wave rows of the call)
-static void match_plan_all(const ba_handle* h, MatchTable& m, size_t n_pairs) {
-  const long long target = 8LL * h->n_cu;
+// The splits of every entry (rows > 0).  Two waves per SIMD over the whole call: want = ceil(8 n_cu / waves of the call's wave rows)
+static void match_plan_all(const ba_handle* h, MatchTable& m, size_t n_pairs, const MatchGeom& g = MT_GEOM) {
+  const long long target = 8LL * h->n_cu, waves = m.wave_rows * g.waves_per_row;
   const int want = h->debug_match_splits > 0 ? h->debug_match_splits
-                                             : (int)std::min<long long>(MT_MAX_SPLITS, (target + m.wave_rows - 1) / m.wave_rows);
+                                             : (int)std::min<long long>(MT_MAX_SPLITS, (target + waves - 1) / waves);
   for (MatchPair& e : m.tab) {
-    match_plan(e, want);
+    match_plan(e, want, g);
     e.part0 = m.n_part;
     m.n_part += (long long)e.nq * e.n_splits;
-    if (e.n_splits > 0) m.max_qb = std::max(m.max_qb, (e.nq + MT_THREADS - 1) / MT_THREADS);
+    if (e.n_splits > 0) m.max_qb = std::max(m.max_qb, (e.nq + g.block - 1) / g.block);
     m.max_splits = std::max(m.max_splits, e.n_splits);
   }
   for (size_t p = 0; p < n_pairs; ++p) m.fin_qb = std::max(m.fin_qb, (m.tab[p].nq + MT_THREADS - 1) / MT_THREADS);
 }
-// The call begun and what both calls share of it: the arrays, the kernels' common arguments, the uploads of descriptors and table,
-// n_good zeroed
+// The call begun and what the matching calls share of it: the arrays, the kernels' common arguments, the uploads of descriptors and
+// table, n_good zeroed.  part_words: the 8-byte words of one (query, split) of `part` (ba_match_l2: two 64-bit keys)
 static int match_stage(ba_handle* h, const MatchTable& m, int32_t desc_bytes, size_t n_desc, const uint8_t* desc, int32_t n_pairs,
-                       double ratio, int32_t max_distance, bool mutual, MatchArgs& a) {
+                       double ratio, int32_t max_distance, bool mutual, MatchArgs& a, size_t part_words = 1) {
   const size_t nr = (size_t)m.rows, np = (size_t)n_pairs, W = (size_t)desc_bytes / 8;
   Scratch& sc = h->scratch;
   HIPCHECK(sc.begin(h->stream));
   a = {};
   HIPCHECK(sc.put(h->stream, n_desc * W, desc, &a.desc)); HIPCHECK(sc.put(h->stream, m.tab.size(), m.tab.data(), &a.pairs));
-  HIPCHECK(sc.take((size_t)m.n_part, &a.part)); HIPCHECK(sc.take(nr, &a.best, &a.second, &a.dist1, &a.dist2));
+  HIPCHECK(sc.take((size_t)m.n_part * part_words, &a.part)); HIPCHECK(sc.take(nr, &a.best, &a.second, &a.dist1, &a.dist2));
   HIPCHECK(sc.take(nr, &a.good)); HIPCHECK(sc.take(np, &a.n_good));
   a.n_pairs = n_pairs; a.mutual = mutual ? 1 : 0; a.max_distance = max_distance; a.ratio = ratio;
   HIPCHECK(hipMemsetAsync(a.n_good, 0, np * sizeof(int), h->stream));
@@ -4177,6 +4188,42 @@ extern "C" int ba_match_descriptors(ba_handle* h, int32_t desc_bytes, int32_t n_
   }
   BA_LAUNCH(k_match_finish, dim3((unsigned)np, (unsigned)m.fin_qb), dim3(MT_THREADS), 0, h->stream, a);
   if (int rc = match_fetch(h, a, (size_t)m.rows, np, best, second, dist1, dist2, good, n_good)) return rc;
+  BA_SYNC(h);
+  return BA_OK;
+}
+
+// ba_match_l2 (csrc/ba_match_l2.hpp): the same call under the squared Euclidean distance of uint8 descriptors.  Needs no problem.
+template <int W>
+static void launch_l2_partial(ba_handle* h, dim3 grid, const L2Args& a) {
+  BA_LAUNCH(k_l2_partial<W>, grid, dim3(ML_THREADS), 0, h->stream, a);
+}
+extern "C" int ba_match_l2(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc,
+                           int32_t n_pairs, const int32_t* pair_query, const int32_t* pair_train, const ba_match_options* opts,
+                           int64_t* row_off, int32_t* best, int32_t* second, int32_t* dist1, int32_t* dist2,
+                           uint8_t* good, int32_t* n_good) {
+  if (!h || !opts) return fail(BA_ERR_INVALID, "null argument");
+  if (int rc = match_check("ba_match_l2", desc_bytes, n_sets, set_off, desc, n_pairs, pair_query, pair_train, opts->ratio, ML_WIDTHS)) return rc;
+  const size_t n_desc = (size_t)set_off[n_sets], np = (size_t)n_pairs, W = (size_t)desc_bytes / 32;
+  const bool mutual = opts->mutual != 0;
+  MatchTable m;
+  match_entries(m, set_off, n_pairs, pair_query, pair_train, mutual, false, row_off);
+  if (n_good) memset(n_good, 0, np * sizeof(int32_t));
+  if (m.rows == 0) return BA_OK;     // no query anywhere: nothing to compute, and every output is already well-formed
+  if (set_device(h)) return BA_ERR_HIP;
+  match_plan_all(h, m, np, ML_GEOM);
+  L2Args a = {};
+  if (int rc = match_stage(h, m, desc_bytes, n_desc, desc, n_pairs, opts->ratio, opts->max_distance, mutual, a.m, 2)) return rc;
+  int *norm = nullptr, *tbase = nullptr;
+  HIPCHECK(h->scratch.take(n_desc, &norm, &tbase));
+  a.norm = norm; a.tbase = tbase;
+  if (m.max_splits > 0) {
+    BA_LAUNCH(k_l2_norms, dim3((unsigned)((n_desc + 255) / 256)), dim3(256), 0, h->stream, (uint4*)a.m.desc, norm, tbase, (long long)n_desc,
+              (int)(2 * W));
+    const dim3 grid((unsigned)m.tab.size(), (unsigned)m.max_qb, (unsigned)m.max_splits);
+    BA_BY_WORDS(W, launch_l2_partial, h, grid, a);
+  }
+  BA_LAUNCH(k_l2_finish, dim3((unsigned)np, (unsigned)m.fin_qb), dim3(MT_THREADS), 0, h->stream, a);
+  if (int rc = match_fetch(h, a.m, (size_t)m.rows, np, best, second, dist1, dist2, good, n_good)) return rc;
   BA_SYNC(h);
   return BA_OK;
 }

@@ -11,6 +11,8 @@ The matcher mirrors ``BruteForceMatcher.match`` of ``src/features.py`` (``cv2.BF
 k=2)`` then Lowe's ``m.distance < 0.75 * n.distance``) on the GPU (``ba_match_descriptors``: brute-force Hamming 2-nearest
 neighbours, ties to the lower train index, the ratio test in fp64).  The match objects are duck-typed for
 ``pose_estimator.estimate_pose``, which reads ``queryIdx`` / ``trainIdx``.  No cv2 is needed.
+``match_l2`` and ``BruteForceMatcher(norm="l2")`` match uint8 descriptors under the Euclidean distance (``ba_match_l2``: SIFT /
+RootSIFT as COLMAP stores them, 128 uint8 per keypoint; ``quantize_descriptors`` takes float descriptors there).
 Once geometry is known, ``match_epipolar`` and ``match_by_projection`` match a second time under it (``ba_match_guided``: the
 same 2-NN over the keypoints an epipolar line or a search window admits; no counterpart in the reference).
 No CPU fallback: without the library / a GPU the call raises.
@@ -65,11 +67,45 @@ def match(des1, des2, solver=None, **opts):
     return _good_of_pair(out, 0)
 
 
-def match_to_keyframes(des_new, keyframe_descriptors, solver=None, **opts):
+def match_l2(des1, des2, solver=None, **opts):
+    """``match`` for uint8 descriptors under the Euclidean distance (``hip_backend.Solver.match_l2``; width a multiple of 32 in
+    32 .. 256) -> (query_idx, train_idx, sqdist) int64 arrays of the good matches in query order; sqdist is the SQUARED
+    distance, and so is the unit of ``max_distance``.  opts: ratio (default 0.75, Lowe's test on the distances), max_distance,
+    mutual."""
+    own = solver is None
+    s = hip_backend.Solver(0) if own else solver
+    try:
+        out = s.match_l2([_descriptors(des1), _descriptors(des2)], **opts)
+    finally:
+        if own:
+            s.close()
+    return _good_of_pair(out, 0)
+
+
+def quantize_descriptors(x, root=False):
+    """Float descriptors (n, D) -> uint8 the way COLMAP stores SIFT: with ``root`` (RootSIFT) every row is L1-normalised and
+    its square root taken; then every row is L2-normalised and stored as min(255, floor(512 x + 0.5)).  All-zero rows stay
+    zero.  Computed in float64 on the host.  This follows COLMAP's published steps; equality with COLMAP's bytes (float32
+    arithmetic there) is NOT verified."""
+    a = np.asarray(x, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError(f"descriptors must be a 2-D array, not shape {a.shape}")
+    if root:
+        l1 = np.abs(a).sum(axis=1, keepdims=True)
+        a = np.sqrt(np.abs(a) / np.where(l1 > 0, l1, 1.0))
+    l2 = np.sqrt((a * a).sum(axis=1, keepdims=True))
+    a = a / np.where(l2 > 0, l2, 1.0)
+    return np.minimum(255.0, np.floor(512.0 * a + 0.5)).clip(0.0, 255.0).astype(np.uint8)
+
+
+def match_to_keyframes(des_new, keyframe_descriptors, solver=None, norm="hamming", **opts):
     """The exhaustive loop of ``pipeline.py:133-134`` in ONE call: every keyframe's descriptors are a query set against the new
     frame's (the argument order ``match(kf.descriptors, des_new)`` there), the new frame's set is uploaded once.  Returns one
     list of ``Match`` per keyframe, in query order; a keyframe without descriptors (``None``) gets ``[]``, and so does
-    every keyframe when ``des_new`` is ``None``."""
+    every keyframe when ``des_new`` is ``None``.  ``norm``: "hamming" (binary descriptors, the default) or "l2" (uint8 descriptors
+    through ``ba_match_l2``; ``Match.distance`` is then the Euclidean distance, the square root of ``dist1``)."""
+    if norm not in ("hamming", "l2"):
+        raise ValueError(f"norm must be 'hamming' or 'l2', not {norm!r}")
     kfs = list(keyframe_descriptors)
     if des_new is None or not kfs:
         return [[] for _ in kfs]
@@ -81,13 +117,14 @@ def match_to_keyframes(des_new, keyframe_descriptors, solver=None, **opts):
     own = solver is None
     s = hip_backend.Solver(0) if own else solver
     try:
-        out = s.match_descriptors(sets, pairs, **opts)
+        out = (s.match_l2 if norm == "l2" else s.match_descriptors)(sets, pairs, **opts)
     finally:
         if own:
             s.close()
     lists = [[] for _ in kfs]
     for n, k in enumerate(have):
-        lists[k] = _match_list(*_good_of_pair(out, n))
+        q, t, d = _good_of_pair(out, n)
+        lists[k] = _match_list(q, t, np.sqrt(d.astype(np.float64)) if norm == "l2" else d)
     return lists
 
 
@@ -203,14 +240,20 @@ class BruteForceMatcher:
     """Drop-in for the reference's ``BruteForceMatcher`` (Hamming norm): ``match(des1, des2)`` -> the good matches, a list in
     query order of objects with ``queryIdx``, ``trainIdx``, ``imgIdx = 0`` and ``distance`` (float).  ``None`` for either
     argument returns ``[]`` as there, and so does a train set of fewer than two descriptors (there ``for m, n in matches``
-    raises and the ``except`` returns the empty list)."""
+    raises and the ``except`` returns the empty list).  ``norm="l2"``: uint8 descriptors under the Euclidean distance
+    (``match_l2``), ``distance`` the square root of the squared distance as a float, cv2's ``NORM_L2`` convention."""
 
-    def __init__(self, ratio=0.75, solver=None):
-        self.ratio, self.solver = ratio, solver
+    def __init__(self, ratio=0.75, solver=None, norm="hamming"):
+        if norm not in ("hamming", "l2"):
+            raise ValueError(f"norm must be 'hamming' or 'l2', not {norm!r}")
+        self.ratio, self.solver, self.norm = ratio, solver, norm
 
     def match(self, des1, des2):
         if des1 is None or des2 is None:
             return []
+        if self.norm == "l2":
+            q, t, d = match_l2(des1, des2, solver=self.solver, ratio=self.ratio)
+            return _match_list(q, t, np.sqrt(d.astype(np.float64)))
         return _match_list(*match(des1, des2, solver=self.solver, ratio=self.ratio))
 
 

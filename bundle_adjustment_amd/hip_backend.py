@@ -168,6 +168,11 @@ BOW_ONE, BOW_IDF_ONE, BOW_MAX_SET, BOW_MAX_TRAIN_ROWS, BOW_CHUNK, BOW_MAX_TOPK, 
 # the most splits of a pair, the most descriptors of a set, the descriptor widths
 MATCH_BLOCK, MATCH_TILE, MATCH_MIN_SPLIT, MATCH_MAX_SPLITS, MATCH_MAX_SET = 256, 64, 128, 64, 1 << 20
 MATCH_DESC_BYTES = (8, 16, 24, 32, 40, 48, 56, 64)
+# ba_match_l2 (csrc/ba_match_l2.hpp): queries per workgroup, train descriptors per LDS tile, the shortest train split, the
+# descriptor widths, and per width the chunk: the train rows of a split that share one 32-bit key range (2^ml_idx_bits)
+MATCH_L2_BLOCK, MATCH_L2_TILE, MATCH_L2_MIN_SPLIT = 128, 64, 256
+MATCH_L2_DESC_BYTES = (32, 64, 96, 128, 160, 192, 224, 256)
+MATCH_L2_CHUNK = {32: 1024, 64: 512, 96: 256, 128: 256, 160: 256, 192: 128, 224: 128, 256: 128}
 # ba_orb_extract (csrc/ba_orb.hpp): the tile of the FAST and blur kernels, the most levels, and the caps of a call
 ORB_TILE_W, ORB_TILE_H, ORB_MAX_LEVELS, ORB_MAX_FEATURES, ORB_MAX_IMAGES = 64, 16, 16, 65536, 1024
 ORB_STAGES = ("upload", "pyramid", "fast", "select", "harris_rank", "blur", "describe", "download")   # ba_orb_stage_times
@@ -274,6 +279,8 @@ SYMBOLS = {
     "ba_default_match_options": (C.c_int, [C.POINTER(BAMatchOptions)]),
     "ba_match_descriptors": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.c_int32, _IP, _IP,
                                        C.POINTER(BAMatchOptions), C.POINTER(C.c_int64), _IP, _IP, _IP, _IP, C.POINTER(C.c_uint8), _IP]),
+    "ba_match_l2": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.c_int32, _IP, _IP,
+                              C.POINTER(BAMatchOptions), C.POINTER(C.c_int64), _IP, _IP, _IP, _IP, C.POINTER(C.c_uint8), _IP]),
     "ba_default_guided_options": (C.c_int, [C.POINTER(BAGuidedOptions)]),
     "ba_match_guided": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.c_int32,
                                   _IP, _IP, C.POINTER(BAGuidedOptions), C.POINTER(C.c_float), _DP, C.POINTER(C.c_int64), _IP, _IP, _IP, _IP,
@@ -1033,6 +1040,21 @@ class Solver:
         _check(self._lib.ba_match_descriptors(self._h, width, len(arrs), set_off.ctypes.data_as(C.POINTER(C.c_int64)),
                                               desc.ctypes.data_as(C.POINTER(C.c_uint8)), len(q), q.ctypes.data_as(_IP), t.ctypes.data_as(_IP),
                                               C.byref(o), *tail))
+        out["good"] = good.astype(bool)
+        out["n_good"] = n_good
+        return out
+
+    def match_l2(self, sets, pairs=None, **opts):
+        """ba_match_l2: exact 2-nearest-neighbours of uint8 descriptors (SIFT as COLMAP stores it) under the squared Euclidean
+        distance, with the ratio test on the squares.  sets / pairs / opts and the returned dict as match_descriptors; the
+        width is a multiple of 32 in 32 .. 256, dist1 / dist2 and max_distance are SQUARED distances.  Needs no problem and
+        leaves a resident one as it is."""
+        arrs, width, set_off, desc, q, t, rows = _match_inputs(sets, pairs)
+        o = self.match_options(**opts)
+        out, good, n_good, tail = _match_outputs(len(q), rows)
+        _check(self._lib.ba_match_l2(self._h, width, len(arrs), set_off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                     desc.ctypes.data_as(C.POINTER(C.c_uint8)), len(q), q.ctypes.data_as(_IP), t.ctypes.data_as(_IP),
+                                     C.byref(o), *tail))
         out["good"] = good.astype(bool)
         out["n_good"] = n_good
         return out

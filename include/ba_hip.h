@@ -641,8 +641,8 @@ int ba_fundamental(ba_handle* h, int32_t n_pairs, const int64_t* pair_off, const
  * set_off[0] != 0, a decreasing set_off, a set of more than 2^20 descriptors; desc NULL with descriptors to read; pair_query /
  * pair_train NULL with n_pairs > 0 or an index outside 0 .. n_sets - 1.  A refused call leaves the handle usable.
  * Results are pure integer arithmetic and bit-reproducible; a pair's rows do not depend on the other pairs of the call, nor on
- * how the library splits the train set over workgroups (csrc/ba_match.hpp).  Not offered: float (L2) descriptors, k > 2;
- * candidate masks are ba_match_guided's (below). */
+ * how the library splits the train set over workgroups (csrc/ba_match.hpp).  Not offered: k > 2; uint8 descriptors under the L2
+ * distance (SIFT) are ba_match_l2's, candidate masks ba_match_guided's (both below). */
 typedef struct ba_match_options {
   double  ratio;         /* keep a query when (double)d1 < ratio * (double)d2, in fp64 exactly as written; <= 0: no ratio test; default 0.75 */
   int32_t max_distance;  /* keep only d1 <= max_distance; < 0: no test; default -1 */
@@ -653,6 +653,30 @@ int ba_match_descriptors(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const
                          int32_t n_pairs, const int32_t* pair_query, const int32_t* pair_train, const ba_match_options* opts,
                          int64_t* row_off, int32_t* best, int32_t* second, int32_t* dist1, int32_t* dist2,
                          uint8_t* good, int32_t* n_good);
+/* L2 descriptor matching: exact brute-force 2-nearest-neighbours of uint8 descriptors under the squared Euclidean distance with
+ * Lowe's ratio test -- SIFT and RootSIFT as COLMAP stores them (128 uint8 per keypoint), learned descriptors quantised the same
+ * way.  The surface is ba_match_descriptors' with another metric: sets, pairs, rows, row_off, the outputs (any of them NULL), the
+ * -1 conventions for nt = 0 and nt = 1, the empty cases and every refusal are as there, word for word, with messages that name
+ * ba_match_l2 (n_sets and n_pairs outside 0 .. 65535 and a set of more than 2^20 descriptors included); ba_match_options is reused
+ * unchanged.  Needs no ba_set_problem and leaves a resident problem untouched.  Local to the rank.
+ * desc_bytes is a multiple of 32 in 32 .. 256; other values are refused by name.  A caller with another length pads both sides
+ * with equal bytes, which adds nothing to any distance.
+ * d(i, j) = sum_k (q_ik - t_jk)^2 over the bytes taken as unsigned 0 .. 255, an int32 (at 256 bytes at most 256 * 255^2 =
+ * 16 646 400 < 2^24); dist1 / dist2 are this SQUARED distance.  The train rows of query i are ordered by the key (d(i, j), j):
+ * ties go to the lower index.  best / dist1 are the first entry of that order, second / dist2 the second.
+ * good[i] = 1 if and only if all of: best >= 0; ratio <= 0, or second >= 0 and (double)dist1 < (ratio * ratio) * (double)dist2 in
+ * fp64 exactly as written (Lowe's test on the distances, stated on the squares: a zero dist2 never passes, and with nt < 2 and a
+ * ratio test nothing is good); max_distance < 0, or dist1 <= max_distance (in squared units); mutual = 0, or i is the first query
+ * under the key (d(i', best), i') over all queries i' of the pair, as in ba_match_descriptors under this metric's order.
+ * n_good[p] = the number of good queries of pair p.
+ * Results are pure integer arithmetic (int8 matrix cores, csrc/ba_match_l2.hpp) and bit-reproducible; a pair's rows do not
+ * depend on the other pairs of the call, nor on how the library splits the work.  Equality with cv2.BFMatcher(NORM_L2) on ties
+ * is NOT verified (cv2 is not part of this project's test environment).  Not offered: float inputs on the device, k > 2,
+ * geometric gates with this metric, cosine or arccos ratio tests, more than one rank. */
+int ba_match_l2(ba_handle* h, int32_t desc_bytes, int32_t n_sets, const int64_t* set_off, const uint8_t* desc,
+                int32_t n_pairs, const int32_t* pair_query, const int32_t* pair_train, const ba_match_options* opts,
+                int64_t* row_off, int32_t* best, int32_t* second, int32_t* dist1, int32_t* dist2,
+                uint8_t* good, int32_t* n_good);
 /* Guided descriptor matching: ba_match_descriptors over the train rows a geometric GATE admits -- the second matching pass of a
  * pipeline once geometry is known (ORB-SLAM's SearchByProjection / SearchForTriangulation, COLMAP's guided matching).  Sets,
  * pairs, rows, row_off, the key (distance, index), ties, -1 and every refusal are ba_match_descriptors' (messages name
