@@ -173,6 +173,23 @@ MATCH_DESC_BYTES = (8, 16, 24, 32, 40, 48, 56, 64)
 MATCH_L2_BLOCK, MATCH_L2_TILE, MATCH_L2_MIN_SPLIT = 128, 64, 256
 MATCH_L2_DESC_BYTES = (32, 64, 96, 128, 160, 192, 224, 256)
 MATCH_L2_CHUNK = {32: 1024, 64: 512, 96: 256, 128: 256, 160: 256, 192: 128, 224: 128, 256: 128}
+# ba_triangulate_tracks (csrc/ba_tracks.hpp): the unit vectors a long track's wave stages in LDS at a time
+TRACK_STAGE = 512
+# ba_covariance (csrc/ba_cov.hpp): the tile edge of the blocked dense algorithms
+COV_TILE = 64
+# ba_pose_graph (csrc/ba_posegraph.hpp): 8-lane teams per workgroup, threads per workgroup, the most workgroups of an edge or
+# node pass, the degree above which a node is a hub, the most chunks of a hub's edge list, the shortest chunk
+PG_TEAMS, PG_THREADS, PG_MAX_BLOCKS, PG_HUB_MIN, PG_HUB_CHUNKS, PG_CHUNK_MIN = 32, 256, 256, 64, 64, 16
+# ba_align (csrc/ba_similarity.hpp): threads per workgroup of the reduction passes, the most workgroups (= partial rows)
+ALIGN_THREADS, ALIGN_MAX_BLOCKS = 256, 128
+
+
+def pg_chunk_len(deg):
+    """pg_chunk_len of csrc/ba_posegraph.hpp: the edges per chunk of a hub of degree deg."""
+    c = (deg + PG_HUB_CHUNKS - 1) // PG_HUB_CHUNKS
+    return c if c > PG_CHUNK_MIN else PG_CHUNK_MIN
+
+
 # ba_orb_extract (csrc/ba_orb.hpp): the tile of the FAST and blur kernels, the most levels, and the caps of a call
 ORB_TILE_W, ORB_TILE_H, ORB_MAX_LEVELS, ORB_MAX_FEATURES, ORB_MAX_IMAGES = 64, 16, 16, 65536, 1024
 ORB_STAGES = ("upload", "pyramid", "fast", "select", "harris_rank", "blur", "describe", "download")   # ba_orb_stage_times

@@ -393,3 +393,50 @@ def pose_distance(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     rot = np.abs(log_map(rodrigues(a[:, :3]) @ np.swapaxes(rodrigues(b[:, :3]), 1, 2))).max()
     return max(float(rot), float(np.abs(a[:, 3:] - b[:, 3:]).max()))
+
+
+# ---- large rings, vectorised ------------------------------------------------------------------------------------------------
+def big_ring(n, chord_every=97, held_every=64, seed=0):
+    """A ring of n nodes for the node and edge grids (n in the thousands; no Python loop over the nodes): odometry edges
+    (k, k + 1 mod n), n // chord_every chords (chord_every c, chord_every c + n // 3 mod n), info = RING_INFO, measurements
+    with N(0, 3e-3 rad | 2e-2 | 3e-3) noise.  The minimiser absorbs most of that noise -- 7 n unknowns against
+    7 (n + n // chord_every) residuals -- and leaves chi2 of 6e-4 per edge on average, so a robust loss needs an f_scale of
+    about 0.02 for its weights to differ at the end.  Every held_every-th node is held, from node held_every // 2 on: the
+    last node of a ring of a multiple of held_every nodes, plus one, is free.  The start is the truth moved by a similarity
+    that grows along the ring (0.02 rad, 0.05 in t, 2 % in scale at its end: the loop edge sees all of it) and by
+    N(0, 1e-3 rad | 1e-2 | 1e-3) per node; held nodes start at the truth.  Every node has degree 2 to 4.
+    -> dict(truth, start, ei, ej, meas, info, held)."""
+    rng = np.random.default_rng(seed)
+    k = np.arange(n)
+    a = 2.0 * math.pi * k / n
+    Rt = rodrigues(np.stack([np.zeros(n), a, np.zeros(n)], axis=1))
+    c = np.stack([5.0 * np.cos(a), np.zeros(n), 5.0 * np.sin(a)], axis=1)
+    truth = np.concatenate([log_map(Rt), -np.einsum("nij,nj->ni", Rt, c), np.ones((n, 1))], axis=1)
+    chords = np.arange(n // chord_every) * chord_every
+    ei = np.concatenate([k, chords]).astype(np.int32)
+    ej = np.concatenate([(k + 1) % n, (chords + n // 3) % n]).astype(np.int32)
+    f = (k / n)[:, None]
+    drift = np.concatenate([f * np.array([[0.0, 0.02, 0.004]]), f * 0.05 * np.ones((1, 3)), 1.0 + 0.02 * f], axis=1)
+    noise = np.concatenate([rng.normal(0.0, 1e-3, (n, 3)), rng.normal(0.0, 1e-2, (n, 3)), rng.normal(0.0, 1e-3, (n, 1))], axis=1)
+    start = retract(compose(drift, truth), noise)
+    held = (k % held_every == held_every // 2).astype(np.uint8)
+    start[held != 0] = truth[held != 0]
+    m = len(ei)
+    mnoise = np.concatenate([rng.normal(0.0, 3e-3, (m, 3)), rng.normal(0.0, 2e-2, (m, 3)), np.exp(rng.normal(0.0, 3e-3, (m, 1)))], axis=1)
+    return dict(truth=truth, start=start, ei=ei, ej=ej, meas=compose(mnoise, relative(truth[ei], truth[ej])),
+                info=np.broadcast_to(RING_INFO, (m, 7, 7)).copy(), held=held)
+
+
+def gradient(poses, ei, ej, meas, info, w, mask):
+    """g = sum_e w_e [A B]^T info e scattered to the nodes with np.add.at (held entries 0), and the same sum of absolute
+    values: (g (n, 7), sum |terms| (n, 7))."""
+    poses = np.asarray(poses, dtype=np.float64)
+    n, m = poses.shape[0], len(ei)
+    A, B = jacobians_analytic(poses, ei, ej, meas)
+    We = w[:, None] * np.einsum("eij,ej->ei", _info(info, m), residuals(poses, ei, ej, meas))
+    g, ga = np.zeros((n, 7)), np.zeros((n, 7))
+    for J, idx in ((A, ei), (B, ej)):
+        np.add.at(g, idx, np.einsum("eai,ea->ei", J, We))
+        np.add.at(ga, idx, np.einsum("eai,ea->ei", np.abs(J), np.abs(We)))
+    g[mask] = 0.0
+    return g, ga

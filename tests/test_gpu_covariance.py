@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from bundle_adjustment_amd import hip_backend
+from bundle_adjustment_amd.hip_backend import COV_TILE
 from bundle_adjustment_amd.problem import BAProblem
 from oracle import ba_oracle as o
 from tests import covariance_reference as cr
@@ -78,13 +79,31 @@ def _run(case, loss):
     return ref, out, red
 
 
-@pytest.mark.parametrize("model", ["pinhole", "bal"])
-@pytest.mark.parametrize("loss", ["linear", "huber"])
-@pytest.mark.parametrize("n_cams", [3, 17, 70])
+def _cams_with(nb, rem, k=1):
+    """The k-th camera count whose system N = nb Nc leaves N % COV_TILE == rem."""
+    hits = [c for c in range(1, 64 * COV_TILE) if nb * c % COV_TILE == rem]
+    return hits[k - 1]
+
+
+# the sizes at the tile's borders, by what N = nb Nc leaves of a tile: nothing (no padding at all, every tile full; pinhole
+# twice, BAL once), two rows into the next tile, one row short of a tile.  6 Nc: 32, 64, 11 cameras; 9 Nc: 64, 7 cameras.
+BORDER_SIZES = {("pinhole", _cams_with(6, 0)): 0, ("pinhole", _cams_with(6, 0, 2)): 0, ("pinhole", _cams_with(6, 2)): 2,
+                ("bal", _cams_with(9, COV_TILE - 1)): COV_TILE - 1, ("bal", _cams_with(9, 0)): 0}
+PARITY_SIZES = [(model, n) for model in ("pinhole", "bal") for n in (3, 17, 70)] + list(BORDER_SIZES)
+
+
+@pytest.mark.parametrize("model,loss,n_cams", [pytest.param(model, loss, n, id=f"{n}-{loss}-{model}")
+                                               for model, n in PARITY_SIZES for loss in ("linear", "huber")])
 def test_parity_with_the_reference(model, loss, n_cams):
-    """N = nb Nc crosses the 64-wide tiles at every size (18 / 27, 102 / 153, 420 / 630)."""
+    """N = nb Nc crosses the 64-wide tiles at every size (18 / 27, 102 / 153, 420 / 630), and at the sizes of BORDER_SIZES it
+    ends on a tile's border (192, 384 and 576: no identity padding, npad == N), two rows past one (66) and one row short of
+    one (63)."""
     mk = pinhole_case if model == "pinhole" else bal_case
     case = _gauge_fixed(mk(n_cams, 12 * n_cams, min(4, n_cams), seed=n_cams))
+    if (model, n_cams) in BORDER_SIZES:
+        assert case.nb * n_cams % COV_TILE == BORDER_SIZES[(model, n_cams)]
+    else:
+        assert case.nb * n_cams % COV_TILE not in (0, 1, COV_TILE - 1)
     ref, out, _ = _run(case, loss)
     check_covariance(ref, out, case.nb)
     assert np.all(np.diagonal(out["full"])[~_reduced(case).held_cam.ravel()] > 0)
@@ -123,6 +142,52 @@ def test_free_gauge_is_refused_by_camera(model):
     assert rc == -4, msg
     assert "camera" in msg and "gauge" in msg
     assert np.all(cam == 7.0) and np.all(pts == 7.0) and np.all(full == 7.0)
+
+
+def _without_camera(case, cam):
+    """The case with every observation of camera `cam` removed (4 observations per point: every point keeps three)."""
+    keep = case.ci != cam
+    case.ci, case.pi, case.uv = case.ci[keep], case.pi[keep], case.uv[keep]
+    assert np.bincount(case.pi, minlength=len(case.pts)).min() >= 3 and not (case.ci == cam).any()
+    return case
+
+
+PARAM_NAMES = ("rvec[0]", "rvec[1]", "rvec[2]", "t[0]", "t[1]", "t[2]", "f", "k1", "k2")     # the header's names of a camera's parameters
+# (model, cameras, the empty camera, bits held on it, the parameter named, its row, what the row is to the tiles)
+NAMED_PIVOTS = [("bal", 12, 7, 0, "rvec[0]", COV_TILE - 1, "last row of tile 0"),
+                ("pinhole", 12, 10, 0b1111, "t[1]", COV_TILE, "first row of tile 1"),
+                ("pinhole", _cams_with(6, 0), _cams_with(6, 0) - 1, 0, "rvec[0]", 6 * (_cams_with(6, 0) - 1), "no padding")]
+
+
+@pytest.mark.parametrize("model,n_cams,empty,bits,name,row,where", NAMED_PIVOTS, ids=[c[-1].replace(" ", "-") for c in NAMED_PIVOTS])
+def test_rank_test_names_the_first_failing_pivot(model, n_cams, empty, bits, name, row, where):
+    """A free camera without observations has an exactly zero block in S: with the gauge fixed, its first free parameter is
+    the first failing pivot, with no rounding involved.  The refusal names that camera and parameter when the pivot is the
+    last row of a tile, the first row of the next, and a row of a system without padding; nothing is written; with that
+    camera held the call succeeds."""
+    mk = pinhole_case if model == "pinhole" else bal_case
+    case = _gauge_fixed(_without_camera(mk(n_cams, 12 * n_cams, 4, seed=n_cams + 40), empty))
+    nb = case.nb
+    first_free = min(q for q in range(nb) if not bits >> q & 1)
+    assert nb * empty + first_free == row and PARAM_NAMES[first_free] == name
+    if where == "no padding":
+        assert nb * n_cams % COV_TILE == 0
+    else:
+        assert row == {"last row of tile 0": COV_TILE - 1, "first row of tile 1": COV_TILE}[where] and nb * n_cams > COV_TILE + 1
+    case.cam_mask[empty] |= np.uint16(bits)
+    with hip_backend.Solver(0) as s:
+        intr = case.upload(s)
+        rc, msg, cam, pts, full = _raw(s, intr, nb)
+        assert rc == -4, msg
+        assert f"singular at camera {empty}, parameter {name} (" in msg, msg
+        assert np.all(cam == 7.0) and np.all(pts == 7.0) and np.all(full == 7.0)
+        case.cam_mask[empty] = np.uint16((1 << nb) - 1)
+        s.set_held(cams=case.cam_mask, points=case.pt_held)
+        out = s.covariance(loss="linear", intr=intr, full=True)
+    ref = cr.schur_covariance(_reduced(case), case.cams, case.pts, "linear")
+    ref["ci"], ref["pi"] = case.ci, case.pi
+    check_covariance(ref, out, nb)
+    assert np.all(out["cams"][empty] == 0.0)
 
 
 def test_one_camera_point_is_nan_and_leaves_the_cameras_alone():

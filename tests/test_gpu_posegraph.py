@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from bundle_adjustment_amd import hip_backend, posegraph
+from bundle_adjustment_amd.hip_backend import PG_CHUNK_MIN, PG_HUB_CHUNKS, PG_HUB_MIN, PG_MAX_BLOCKS, PG_TEAMS, PG_THREADS, pg_chunk_len
 from bundle_adjustment_amd.problem import BAProblem
 from bundle_adjustment_amd.synthetic import make_problem
 from tests import posegraph_reference as R
@@ -175,6 +176,126 @@ def test_system(solver, with_scale):
     assert np.all(got["g"][rows] == 0.0)
 
 
+# ------------------------------------------------------------------------------------------------------------ 1b: hubs, edge grid
+N_ORDINARY = 40
+# degrees of the chosen nodes 0 .. 5: one short of a hub and the largest node that is none; a hub whose last chunk holds one
+# edge; 64 chunks of 16; chunk length 17; chunk length 65 in 64 chunks, the last one short
+CHOSEN_DEGREES = (PG_HUB_MIN - 1, PG_HUB_MIN, PG_HUB_MIN + 1, PG_HUB_CHUNKS * PG_CHUNK_MIN, PG_HUB_CHUNKS * PG_CHUNK_MIN + 1,
+                  PG_HUB_CHUNKS * PG_HUB_CHUNKS + 1)
+
+
+@functools.lru_cache(maxsize=None)
+def multigraph_scene(with_scale=True):
+    """48 nodes, m = 2 PG_MAX_BLOCKS PG_TEAMS + 5 edges (the edge pass makes a third, partly filled trip), parallel edges
+    throughout.  Nodes 0 .. 5 have the CHOSEN_DEGREES, nodes 6 and 7 are two further hubs that take the rest, nodes 8 .. 47 are
+    ordinary: a ring among themselves plus ten edges from every chosen node.  Each chosen node's other edges alternate between
+    the two further hubs, and the remaining edges join those two.  Edges in random order and random direction (i > j on about
+    half); poses, noise and information blocks as in system_scene: generic rotations, |t| <= 10, scales 0.5 .. 2, random
+    full-rank info and a rotation-only one, node 12 held."""
+    rng = np.random.default_rng(31)
+    n = 8 + N_ORDINARY
+    m = 2 * PG_MAX_BLOCKS * PG_TEAMS + 5
+    h1, h2, first = 6, 7, 8
+    pairs = [(first + k, first + (k + 1) % N_ORDINARY) for k in range(N_ORDINARY)]
+    for c, deg in enumerate(CHOSEN_DEGREES):
+        pairs += [(c, first + (10 * c + k) % N_ORDINARY) for k in range(10)]
+        pairs += [(c, h1 if k % 2 else h2) for k in range(deg - 10)]
+    assert len(pairs) < m
+    pairs += [(h1, h2)] * (m - len(pairs))
+    pairs = np.array(pairs)[rng.permutation(m)]
+    flip = rng.random(m) < 0.5
+    ei = np.where(flip, pairs[:, 1], pairs[:, 0]).astype(np.int32)
+    ej = np.where(flip, pairs[:, 0], pairs[:, 1]).astype(np.int32)
+    poses = np.zeros((n, 7))
+    poses[:, :3] = rng.normal(0.0, 0.8, (n, 3))
+    poses[:, 3:6] = rng.uniform(-10.0, 10.0, (n, 3))
+    poses[:, 6] = rng.uniform(0.5, 2.0, n) if with_scale else 1.0
+    noise = np.concatenate([rng.normal(0.0, 0.3, (m, 3)), rng.normal(0.0, 0.5, (m, 3)),
+                            np.exp(rng.normal(0.0, 0.2, (m, 1))) if with_scale else np.ones((m, 1))], axis=1)
+    meas = R.compose(noise, R.relative(poses[ei], poses[ej]))
+    M = rng.normal(0.0, 1.0, (m, 7, 7))
+    info = M @ np.swapaxes(M, 1, 2) + np.eye(7)
+    info[6] = 0.0
+    info[6, :3, :3] = M[6, :3, :3] @ M[6, :3, :3].T + np.eye(3)      # rotation only: rank 3
+    held = np.zeros(n, np.uint8)
+    held[12] = 1
+    return dict(poses=poses, ei=ei, ej=ej, meas=meas, info=info, held=held)
+
+
+def check_multigraph_borders(sc):
+    """The degree list, the hubs and their chunks, the trips of the edge pass: what the scene is for."""
+    n, m = sc["poses"].shape[0], len(sc["ei"])
+    deg = np.bincount(np.concatenate([sc["ei"], sc["ej"]]), minlength=n)
+    assert 7 * n <= 4096 and m == 2 * PG_MAX_BLOCKS * PG_TEAMS + 5
+    assert -(-m // (PG_MAX_BLOCKS * PG_TEAMS)) == 3 and m % (PG_MAX_BLOCKS * PG_TEAMS) == 5
+    assert tuple(deg[:6]) == CHOSEN_DEGREES
+    hubs = np.flatnonzero(deg > PG_HUB_MIN)
+    assert hubs.tolist() == [2, 3, 4, 5, 6, 7] and int((deg <= PG_HUB_MIN).sum()) == n - 6 == 42
+    assert deg[8:].max() < PG_HUB_MIN and deg[8:].min() >= 2
+    chunks = {int(k): (pg_chunk_len(int(deg[k])), -(-int(deg[k]) // pg_chunk_len(int(deg[k]))), int(deg[k]) % pg_chunk_len(int(deg[k]))) for k in hubs}
+    assert chunks[2] == (PG_CHUNK_MIN, 5, 1)                                   # 65 edges: four chunks of 16 and one edge
+    assert chunks[3] == (PG_CHUNK_MIN, PG_HUB_CHUNKS, 0) and chunks[4] == (PG_CHUNK_MIN + 1, 61, 5)
+    assert chunks[5] == (PG_HUB_CHUNKS + 1, PG_HUB_CHUNKS, 2)                  # 4097 edges: 63 chunks of 65 and one of 2
+    assert all(c[1] <= PG_HUB_CHUNKS for c in chunks.values()) and min(chunks[6][0], chunks[7][0]) > PG_HUB_CHUNKS + 1
+    assert (sc["ei"] > sc["ej"]).sum() > 1000 and (sc["ei"] < sc["ej"]).sum() > 1000
+    return deg
+
+
+@pytest.mark.parametrize("with_scale", [True, False])
+def test_system_multigraph(solver, with_scale):
+    """test_system on the multigraph scene: hubs of every chunk geometry and three trips of the edge pass.  e, A, B against the
+    closed form in numpy (absolute 1e-12, as there with d_fd = 0); H and g against the sums formed in numpy from the device's
+    own e, A, B, 1e-12 of the largest entry -- test_system's bound, which holds at degree 13 152 too (measured: H 7.0e-15,
+    g 3.7e-15), so no componentwise bound replaces it."""
+    sc = multigraph_scene(with_scale)
+    deg = check_multigraph_borders(sc)
+    n, m = sc["poses"].shape[0], len(sc["ei"])
+    ref = R.system(sc["poses"], sc["ei"], sc["ej"], sc["meas"], sc["info"], sc["held"], "huber", 1.5, with_scale, lam=0.3, analytic=True)
+    got = solver.pose_graph_system(sc["poses"], sc["ei"], sc["ej"], sc["meas"], info=sc["info"], held=sc["held"], lam=0.3,
+                                   loss="huber", f_scale=1.5, with_scale=with_scale)
+    e_err = float(np.abs(got["e"] - ref["e"]).max())
+    j_err = max(float(np.abs(got["A"] - ref["A"]).max()), float(np.abs(got["B"] - ref["B"]).max()))
+    print(f"multigraph system ({m} edges, degrees up to {deg.max()}): max |e - e_ref| {e_err:.2e}; max |J - J_ref| {j_err:.2e} "
+          f"(max |J| {max(np.abs(ref['A']).max(), np.abs(ref['B']).max()):.1f}); weights below 1: {(ref['w'] < 1).mean():.2f}")
+    assert (ref["w"] < 1).any()
+    assert e_err <= 1e-12
+    assert j_err <= 10.0 * ref["d_fd"] + 1e-12 and ref["d_fd"] == 0.0
+    H, g, _ = R.dense_system(n, sc["ei"], sc["ej"], got["e"], got["A"], got["B"], sc["info"], ref["w"], ref["mask"], lam=0.3)
+    h_err = float(np.abs(got["H"] - H).max() / np.abs(H).max())
+    g_err = float(np.abs(got["g"] - g).max() / np.abs(g).max())
+    print(f"  H relative {h_err:.2e}, g relative {g_err:.2e}")
+    assert h_err <= 1e-12 and g_err <= 1e-12
+    assert same_bits(got["H"], got["H"].T)
+    rows = np.flatnonzero(ref["mask"].reshape(-1))
+    assert rows.size == (7 if with_scale else 7 + (n - 1))
+    assert np.array_equal(got["H"][rows], np.eye(7 * n)[rows]) and np.array_equal(got["H"][:, rows], np.eye(7 * n)[:, rows])
+    assert np.all(got["g"][rows] == 0.0)
+
+
+def test_jacobians_to_fp64_accuracy(solver):
+    """e, A, B of the nine edges of tests/golden/pg_jacobians.npz -- residual rotations 0, 1e-9, 1e-5, both sides of the series
+    switch at 0.01, 1, 3, pi - 1e-3, pi - 1e-6 -- against central differences in 60-digit arithmetic, to 50 x the error the
+    fp64 closed form of the yardstick has against the same values (tests/golden/make_posegraph_jacobians.py says why)."""
+    import importlib.util
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    spec = importlib.util.spec_from_file_location("make_posegraph_jacobians", os.path.join(golden, "make_posegraph_jacobians.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)                              # (for its constants: only the fixture's values are used here)
+    fix = np.load(os.path.join(golden, "pg_jacobians.npz"))
+    tol = gen.TOL
+    assert tol == 50.0 * 5.2e-16
+    got = solver.pose_graph_system(fix["poses"], fix["ei"], fix["ej"], fix["meas"])
+    jmax = max(float(np.abs(fix["A"]).max()), float(np.abs(fix["B"]).max()))
+    a_err, b_err = float(np.abs(got["A"] - fix["A"]).max()), float(np.abs(got["B"] - fix["B"]).max())
+    e_err = float(np.abs(got["e"] - fix["e"]).max())
+    per_edge = np.maximum(np.abs(got["A"] - fix["A"]).max(axis=(1, 2)), np.abs(got["B"] - fix["B"]).max(axis=(1, 2)))
+    print(f"Jacobians against the 60-digit differences: A {a_err:.2e}, B {b_err:.2e} (bound {tol * jmax:.2e}, max |J| {jmax:.3f}); "
+          f"e {e_err:.2e} (bound {tol:.2e}); per edge " + " ".join(f"{v:.1e}" for v in per_edge))
+    assert fix["phi"][3] ** 2 < 1e-4 < fix["phi"][4] ** 2 and len(fix["phi"]) == 9
+    assert a_err <= tol * jmax and b_err <= tol * jmax
+    assert e_err <= tol
+
+
 # ------------------------------------------------------------------------------------------------------------ 2: clean ring
 @pytest.mark.parametrize("with_scale", [True, False])
 def test_clean_ring(solver, with_scale):
@@ -289,6 +410,89 @@ def test_star_bits_do_not_depend_on_the_split(solver):
             os.environ.pop("BA_DEBUG_PG_SPLITS", None)
         else:
             os.environ["BA_DEBUG_PG_SPLITS"] = old
+
+
+def test_multigraph_bits_do_not_depend_on_the_split(solver):
+    """The split test on the multigraph scene, whose hubs have chunks of 16, 17, 65 and some 200 edges and short last chunks:
+    the dense system and three LM iterations with 1 and 7 teams per hub give the bits of the default 32."""
+    sc = multigraph_scene(True)
+    check_multigraph_borders(sc)
+    args = (sc["poses"], sc["ei"], sc["ej"], sc["meas"])
+    kw = dict(info=sc["info"], held=sc["held"], loss="huber", f_scale=1.5)
+    ref_sys = solver.pose_graph_system(*args, lam=0.3, **kw)
+    ref = solver.pose_graph(*args, max_iters=3, **kw)
+    assert ref["pcg_iterations"] > 0 and ref["final_cost"] < ref["initial_cost"]
+    old = os.environ.get("BA_DEBUG_PG_SPLITS")
+    try:
+        for k in (1, 7):
+            os.environ["BA_DEBUG_PG_SPLITS"] = str(k)
+            with hip_backend.Solver(0) as s:
+                out_sys = s.pose_graph_system(*args, lam=0.3, **kw)
+                out = s.pose_graph(*args, max_iters=3, **kw)
+            for key in ("H", "g"):
+                assert same_bits(out_sys[key], ref_sys[key]), (k, key)
+            for key in ("poses", "edge_chi2", "edge_weight"):
+                assert same_bits(out[key], ref[key]), (k, key)
+            assert out["final_cost"] == ref["final_cost"] and out["pcg_iterations"] == ref["pcg_iterations"]
+    finally:
+        if old is None:
+            os.environ.pop("BA_DEBUG_PG_SPLITS", None)
+        else:
+            os.environ["BA_DEBUG_PG_SPLITS"] = old
+
+
+# ------------------------------------------------------------------------------------------------------------ 5b: node grids
+NODE_GRID_SIZES = (PG_MAX_BLOCKS * PG_TEAMS, PG_MAX_BLOCKS * PG_TEAMS + 1, PG_MAX_BLOCKS * PG_THREADS, PG_MAX_BLOCKS * PG_THREADS + 1)
+U = 2.0 ** -53
+
+
+@pytest.mark.parametrize("n", NODE_GRID_SIZES)
+def test_node_grids(solver, n):
+    """Rings of PG_MAX_BLOCKS PG_TEAMS and PG_MAX_BLOCKS PG_THREADS nodes and one more: the last node is the second trip of the
+    grid-stride loops of the node passes (a team per node) and of the step kernel (a thread per node); the edge pass makes
+    its second trip at every size.  Six LM iterations under Huber; the dense mirror cannot follow at this size, so what a
+    vectorised reference certifies at the returned poses: chi2 and weight of every edge, their sum, the initial cost, the held
+    nodes, a decrease of the cost and of the gradient, and the bits of a second call."""
+    sc = R.big_ring(n)
+    m = len(sc["ei"])
+    teams, threads = PG_MAX_BLOCKS * PG_TEAMS, PG_MAX_BLOCKS * PG_THREADS
+    assert (-(-n // teams), -(-n // threads)) == {teams: (1, 1), teams + 1: (2, 1), threads: (8, 1), threads + 1: (9, 2)}[n]
+    assert m > teams and np.bincount(np.concatenate([sc["ei"], sc["ej"]])).max() <= 4 < PG_HUB_MIN        # no hubs
+    loss, fs = "huber", 0.02
+    lmax = lam_max(sc["info"][0])
+    gtol = 1e-8
+    opts = dict(loss=loss, f_scale=fs, max_iters=6, gtol=gtol)
+    out = run(solver, sc, **opts)
+    again = run(solver, sc, **opts)
+    print(f"ring of {n} nodes / {m} edges: {out['iterations']} LM / {out['pcg_iterations']} PCG iterations, status {out['status_name']}, "
+          f"cost {out['initial_cost']:.6e} -> {out['final_cost']:.6e}")
+    cost0, _, w0 = R.cost(sc["start"], sc["ei"], sc["ej"], sc["meas"], sc["info"], loss, fs)
+    assert abs(out["initial_cost"] - cost0) <= cost_bound(cost0, m, lmax)
+    cost1, c2, w = R.cost(out["poses"], sc["ei"], sc["ej"], sc["meas"], sc["info"], loss, fs)
+    per_edge = COST_RTOL * c2 + np.sqrt(2.0 * lmax * c2 * 7) * E_ROUND                # cost_bound of one edge
+    d_c2 = np.abs(out["edge_chi2"] - c2)
+    assert np.all(d_c2 <= per_edge), float((d_c2 / per_edge).max())
+    # Huber's w = min(1, (chi2 / f_scale^2)^-1/2) has |dw / w| <= |d chi2 / chi2| / 2
+    assert np.all(np.abs(out["edge_weight"] - w) * c2 <= w * per_edge)
+    assert 0.02 < (w < 1).mean() < 0.98                 # (the weights compared above are not all 1)
+    assert abs(out["final_sse"] - c2.sum()) <= cost_bound(c2.sum(), m, lmax)
+    assert abs(out["final_cost"] - cost1) <= cost_bound(cost1, m, lmax)
+    held = sc["held"] != 0
+    assert held.sum() == n // 64 and not held[n - 1] and same_bits(out["poses"][held], sc["start"][held])
+    assert not same_bits(out["poses"][n - 1], sc["start"][n - 1])                       # the last node moved too
+    assert out["final_cost"] < out["initial_cost"] and out["accepted"] > 0
+    for key in ("poses", "edge_chi2", "edge_weight"):
+        assert same_bits(out[key], again[key]), key
+    assert out["final_cost"] == again["final_cost"] and out["pcg_iterations"] == again["pcg_iterations"]
+    # the gradient at the returned poses: a term is two inner products of length 7 of factors known to a few u each
+    mask = R.held_mask(n, sc["ei"], sc["ej"], sc["held"])
+    g0, _ = R.gradient(sc["start"], sc["ei"], sc["ej"], sc["meas"], sc["info"], w0, mask)
+    g1, g1_abs = R.gradient(out["poses"], sc["ei"], sc["ej"], sc["meas"], sc["info"], w, mask)
+    print(f"  max |g| over the free parameters {np.abs(g0).max():.3e} -> {np.abs(g1).max():.3e}")
+    if out["status_name"] == "gtol":
+        assert np.all(np.abs(g1) <= gtol + 64.0 * U * g1_abs)
+    else:
+        assert np.abs(g1).max() < np.abs(g0).max()
 
 
 # ------------------------------------------------------------------------------------------------------------ 6: reproducibility

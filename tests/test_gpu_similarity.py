@@ -18,6 +18,7 @@ from bundle_adjustment_amd import bal, hip_backend, similarity
 from bundle_adjustment_amd.bal import BALProblem, from_pinhole
 from bundle_adjustment_amd.problem import BAProblem
 from bundle_adjustment_amd.synthetic import _project, bal_project, make_bal_like, make_problem, make_shared_bal_problem
+from tests import similarity_cases as sc
 from tests import similarity_reference as sr
 
 pytestmark = pytest.mark.gpu
@@ -405,6 +406,34 @@ def test_align_sizes(n):
     d = compare_alignment(got, sr.align(a, b), max(1.0, float(np.linalg.norm(t0))))
     print(f"align size {n}: s {d[0]:.2e} R {d[1]:.2e} t {d[2]:.2e} errors {d[3]:.2e}")
     assert (d <= 1e-10).all()
+
+
+@pytest.mark.parametrize("nn", sc.BORDER_COUNTS)
+def test_align_grid_borders(nn):
+    """64 and 65 partial rows; ALIGN_MAX_BLOCKS workgroups with one correspondence per thread, and one correspondence more,
+    which starts the second trip of the grid-stride loops (tests/similarity_cases.py).  The last 40 correspondences weigh
+    1000: test_similarity_host.py shows that without them s or t moves by more than 100 x the tolerance."""
+    blocks, per_thread = sc.partial_rows(nn)
+    assert (blocks, per_thread) == {sc.BORDER_COUNTS[0]: (64, 1), sc.BORDER_COUNTS[1]: (65, 1),
+                                    sc.BORDER_COUNTS[2]: (hip_backend.ALIGN_MAX_BLOCKS, 1),
+                                    sc.BORDER_COUNTS[3]: (hip_backend.ALIGN_MAX_BLOCKS, 2)}[nn]
+    prob, a, b, w, (s0, R0, t0) = sc.border_scene(nn)
+    t_scale = max(1.0, float(np.linalg.norm(t0)))
+    with hip_backend.Solver(0) as s:
+        s.set_problem(prob)
+        for loss, iters in (("linear", 0), ("cauchy", 5)):
+            kw = dict(cam_ref=b[:3], cam_w=w[:3], pt_ref=b[3:], pt_w=w[3:], loss=loss, f_scale=0.15, iters=iters)
+            got, again = s.align(**kw), s.align(**kw)
+            want = sr.align(a, b, w, loss=loss, f_scale=0.15, iters=iters)
+            d = compare_alignment(got, want, t_scale)
+            last = abs(got["pt_err"][-1] - want["err"][-1]) / max(want["err"][-1], NOISE)
+            print(f"align {nn} correspondences ({blocks} partial rows, {per_thread} per thread), {loss}: s {d[0]:.2e} R {d[1]:.2e} "
+                  f"t {d[2]:.2e} errors {d[3]:.2e}, the last point's {last:.2e}")
+            assert got["n_used"] == nn
+            assert (d <= sc.TOL).all() and last <= sc.TOL
+            for key in ("R", "t", "cam_err", "pt_err"):
+                assert same_bits(got[key], again[key]), key
+            assert same_bits([got[k] for k in ("s", "rms", "max")], [again[k] for k in ("s", "rms", "max")])
 
 
 # ---------------------------------------------------------------------------------------------------- 8 exact data

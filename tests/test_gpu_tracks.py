@@ -14,6 +14,8 @@ from bundle_adjustment_amd.problem import BAProblem
 from bundle_adjustment_amd.rotations import rvecs_to_matrices
 from bundle_adjustment_amd.synthetic import _project, bal_project, make_problem, make_shared_bal_problem
 from bundle_adjustment_amd.triangulation import filter_tracks, triangulate_tracks
+from bundle_adjustment_amd.hip_backend import TRACK_STAGE
+from tests import track_cases as tc
 from tests import track_reference as tr
 
 pytestmark = pytest.mark.gpu
@@ -140,6 +142,51 @@ def test_status_and_measures_match_the_reference(model, lanes2, monkeypatch):
     assert np.isnan(out["xyz"][nanp]).all() and np.isnan(out["angle_deg"][nanp]).all() and np.isnan(out["max_px"][nanp]).all()
     assert np.isfinite(out["xyz"][~nanp]).all()
     check_measures(prob, out, np.nonzero(~nanp)[0])
+
+
+@functools.lru_cache(maxsize=None)
+def long_reference(model):
+    return tr.triangulate_tracks(tc.long_track_problem(model)[0], **OPTS)
+
+
+@pytest.mark.parametrize("lanes2", [True, False], ids=["long-tracks-split-off", "one-launch-form"])
+@pytest.mark.parametrize("model", ["pinhole", "bal"])
+def test_tracks_longer_than_a_stage(model, lanes2, monkeypatch):
+    """Tracks of TRACK_STAGE - 1, TRACK_STAGE, TRACK_STAGE + 1, 2 TRACK_STAGE, 2 TRACK_STAGE + 1 views and three of
+    2 TRACK_STAGE + 76 whose widest pair of cameras sits in stages (0, 0), (0, 1) -- last position of stage 0, first of stage 1
+    -- and (1, 2) of the track's list as the device holds it (tests/track_cases.py): the second and third trip of the long-track
+    kernel's staging loop, its `j <= c0` skip and its shortened last stage.  test_tracks_host.py shows that an angle over
+    same-stage pairs alone is off by 2e-3 on the last two, against the 1e-9 asserted here.  The same tracks under the
+    default lane count go through the 8-lane form, which stages nothing."""
+    prob, _, pairs = tc.long_track_problem(model)
+    ref = long_reference(model)
+    if lanes2:
+        monkeypatch.setenv("BA_PT_LANES", "2")
+    with hip_backend.Solver(0) as s:
+        intr = s._set_bal(prob) if isinstance(prob, BALProblem) else s.set_problem(prob)
+        out = s.triangulate_tracks(intr=intr, **OPTS)
+        lay = s.debug_layout("scalars")
+        pt_off, p_cam, slot = s.debug_layout("pt_off"), s.debug_layout("p_cam"), s.debug_layout("slot")
+    lengths = np.bincount(prob.pt_idx, minlength=prob.n_pts)
+    if lanes2:
+        assert lay["lanes"] == 2 and lay["long_thr"] == 8
+        assert lay["n_long"] == int((lengths > lay["long_thr"]).sum()) == len(tc.LONG_POINTS)
+    else:
+        assert lay["n_long"] == 0
+    # the borders, from the layout the kernel reads: the lengths of the tracks, and the stages the widest pairs fall in
+    seg = {p: p_cam[pt_off[slot[p]]:pt_off[slot[p] + 1]] for p in tc.LONG_POINTS}
+    assert tuple(len(seg[p]) for p in tc.LONG_POINTS) == tc.BORDER_LENGTHS + (tc.N_WIDE,) * 3
+    for p, stages, positions in zip(tc.WIDE_POINTS, tc.WIDE_STAGES, tc.WIDE_POSITIONS):
+        at = tuple(int(np.nonzero(seg[p] == c)[0][0]) for c in pairs[p])
+        assert tuple(q // TRACK_STAGE for q in at) == stages, (p, at)
+        if stages == (0, 1):
+            assert at == (TRACK_STAGE - 1, TRACK_STAGE)
+    far = decided_far_from_threshold(ref, OPTS)
+    assert far.all()                                   # the yardstick excludes nothing
+    assert (ref["status"] == tr.OK).all()
+    assert np.array_equal(out["status"], ref["status"]), np.nonzero(out["status"] != ref["status"])[0]
+    assert np.isfinite(out["xyz"]).all()
+    check_measures(prob, out, np.arange(prob.n_pts))
 
 
 def test_both_sides_of_the_angle_test_on_the_stock_generator():

@@ -223,3 +223,48 @@ def test_close_loop_on_a_double(kind):
     assert not np.array_equal(fixed.pts, prob.pts)
     with pytest.raises(ValueError):
         posegraph.close_loop(prob, [5, 4], [0], posegraph.relative(truth[5], truth[0])[None], solver=s)
+
+
+# ---- the Jacobian fixture ---------------------------------------------------------------------------------------------------
+def _fixture_generator():
+    import importlib.util
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_posegraph_jacobians.py")
+    spec = importlib.util.spec_from_file_location("make_posegraph_jacobians", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_jacobian_fixture_bounds_the_closed_form():
+    """tests/golden/pg_jacobians.npz: e, A, B of nine edges from 60-digit central differences of the header's residual and
+    retraction.  The inputs are the generator's (the values are regenerated by the next test).  The fp64 closed form of the yardstick, held to 10 d_fd = 6e-7 by the test above,
+    is measured against the fixture: the figure printed here, rounded up, is the generator's REF_REL, and 50 x REF_REL is
+    what test_gpu_posegraph.py asks of the device."""
+    gen = _fixture_generator()
+    fix = np.load(gen.OUT)
+    poses, ei, ej, meas = gen.inputs()
+    for key, want in (("poses", poses), ("ei", ei), ("ej", ej), ("meas", meas), ("phi", np.array(gen.PHI))):
+        assert np.array_equal(fix[key], want), key
+    assert np.abs(np.linalg.norm(fix["e"][:, :3], axis=1) - fix["phi"]).max() <= 1e-15
+    assert fix["phi"][3] ** 2 < 1e-4 < fix["phi"][4] ** 2                       # the two sides of the series switch
+    assert np.linalg.norm(meas[:, :3], axis=1).max() <= np.pi and (np.abs(np.log(poses[ei, 6] / poses[ej, 6])) > 0.01).all()
+    Aa, Ba = R.jacobians_analytic(poses, ei, ej, meas)
+    jmax = max(np.abs(fix["A"]).max(), np.abs(fix["B"]).max())
+    rel = max(np.abs(Aa - fix["A"]).max(), np.abs(Ba - fix["B"]).max()) / jmax
+    e_err = np.abs(R.residuals(poses, ei, ej, meas) - fix["e"]).max()
+    print(f"closed form against the 60-digit differences: {rel:.3e} of max |J| = {jmax:.3f}; residuals {e_err:.3e}; REF_REL {gen.REF_REL:.1e}")
+    # (measured 5.16e-16 with this machine's libm; twice REF_REL leaves room for one whose sin and cos round another way)
+    assert rel <= 2.0 * gen.REF_REL and gen.TOL == 50.0 * gen.REF_REL
+    assert e_err <= gen.TOL
+
+
+def test_jacobian_fixture_regenerates():
+    """Where mpmath imports, the generator's 60-digit values are the fixture's (1e-15 relative: the differences' own error is 1e-40)."""
+    pytest.importorskip("mpmath")
+    gen = _fixture_generator()
+    fix = np.load(gen.OUT)
+    poses, ei, ej, meas = gen.inputs()
+    e, A, B = gen.values(poses, ei, ej, meas)
+    for key, want in (("e", e), ("A", A), ("B", B)):
+        assert np.allclose(fix[key], want, rtol=1e-15, atol=1e-300), key

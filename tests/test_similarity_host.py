@@ -161,3 +161,24 @@ def test_option_validation_without_a_gpu():
     s._lib, s._h, s.n_cams, s.n_pts = lib, None, 3, 4
     with pytest.raises(ValueError, match="unknown loss"):
         s.align(cam_ref=np.zeros((3, 3)), loss="tukey")
+
+
+def test_grid_border_scenes_notice_their_last_rows():
+    """The scenes of tests/similarity_cases.py: their block counts are the ones named, and the yardstick with the last 40
+    (heavy) rows dropped differs from the full one by more than 100 x the device tests' tolerance in s or t -- a fold that
+    lost the last partial row, or a grid-stride loop that lost its second trip, would be seen."""
+    from bundle_adjustment_amd.hip_backend import ALIGN_MAX_BLOCKS
+    from tests import similarity_cases as sc
+    assert [sc.partial_rows(nn) for nn in sc.BORDER_COUNTS] == [(64, 1), (65, 1), (ALIGN_MAX_BLOCKS, 1), (ALIGN_MAX_BLOCKS, 2)]
+    for nn in sc.BORDER_COUNTS:
+        _, a, b, w, (s0, R0, t0) = sc.border_scene(nn)
+        assert a.shape == (nn, 3) and (w[-sc.HEAVY:] == sc.HEAVY_WEIGHT).all() and (w[:-sc.HEAVY] == 1.0).all()
+        for loss, iters in (("linear", 0), ("cauchy", 5)):
+            full = sr.align(a, b, w, loss=loss, f_scale=0.15, iters=iters)
+            cut = sr.align(a[:-sc.HEAVY], b[:-sc.HEAVY], w[:-sc.HEAVY], loss=loss, f_scale=0.15, iters=iters)
+            assert full["status"] == cut["status"] == 0 and full["n_used"] == nn
+            d_s = abs(full["s"] - cut["s"]) / full["s"]
+            d_t = np.abs(full["t"] - cut["t"]).max() / max(1.0, float(np.linalg.norm(t0)))
+            print(f"{nn} correspondences, {loss}: without the last {sc.HEAVY} rows s moves by {d_s:.2e}, t by {d_t:.2e}")
+            assert max(d_s, d_t) > 100.0 * sc.TOL
+            assert abs(full["s"] - s0) / s0 < 1e-2                     # (the fit is the planted similarity, to the noise of the heavy rows)

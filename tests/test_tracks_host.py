@@ -117,6 +117,39 @@ def test_robust_refinement_lands_on_a_stationary_point_of_its_cost():
     assert np.abs(hub - X).max() < np.abs(lin - X).max()
 
 
+@pytest.mark.parametrize("model", ["pinhole", "bal"])
+def test_long_track_cases_tell_a_same_stage_angle_from_the_true_one(model):
+    """The three tracks of tests/track_cases.py with a placed widest pair: an angle over the pairs of one stage only (the
+    mutant of track_reference) is the true one when both cameras sit in stage 0, and is off by more than 1e-6 relative --
+    the device tests assert 1e-9 -- when they sit in stages (0, 1) and (1, 2)."""
+    from bundle_adjustment_amd.hip_backend import TRACK_STAGE
+    from tests import track_cases as tc
+    prob, truth, pairs = tc.long_track_problem(model)
+    R = rvecs_to_matrices(prob.cams[:, :3])
+    by_pt = tr.observations_by_point(prob)
+    lengths = np.bincount(prob.pt_idx, minlength=prob.n_pts)
+    assert tuple(lengths[list(tc.LONG_POINTS)]) == tc.BORDER_LENGTHS + (tc.N_WIDE,) * 3
+    assert np.sort(lengths)[prob.n_pts // 2] == 4 and lengths[:tc.N_SHORT].max() <= 6      # the library's median: long_thr = 8
+    for p, stages, positions in zip(tc.WIDE_POINTS, tc.WIDE_STAGES, tc.WIDE_POSITIONS):
+        v = tr.views_of(prob, p, R, by_pt)
+        assert len(set(v.cam.tolist())) == tc.N_WIDE                      # distinct cameras
+        assert tuple(int(np.nonzero(v.cam == c)[0][0]) for c in pairs[p]) == positions
+        assert tuple(q // TRACK_STAGE for q in positions) == stages
+        stage = np.arange(tc.N_WIDE) // TRACK_STAGE
+        true, mutant = tr.max_angle_deg(v.centres, truth[p]), tr.max_angle_deg_same_stage(v.centres, truth[p], stage)
+        rel = abs(true - mutant) / true
+        print(f"{model} point {p}, widest pair in stages {stages}: true angle {true:.6f} deg, same-stage pairs only {mutant:.6f} ({rel:.2e})")
+        assert mutant <= true
+        if stages[0] == stages[1]:
+            assert rel <= 1e-12
+        else:
+            assert rel > 1e-6
+    # one stage for every view: the mutant is the yardstick
+    v = tr.views_of(prob, tc.WIDE_POINTS[1], R, by_pt)
+    assert tr.max_angle_deg_same_stage(v.centres, truth[tc.WIDE_POINTS[1]], np.zeros(tc.N_WIDE, int)) == \
+        pytest.approx(tr.max_angle_deg(v.centres, truth[tc.WIDE_POINTS[1]]), rel=1e-14)
+
+
 def test_filter_tracks_bookkeeping():
     prob = make_problem(5, 40, 3, seed=3)
     rng = np.random.default_rng(0)

@@ -191,6 +191,21 @@ def max_angle_deg(centres, X):
     return 2.0 * np.arctan2(np.sqrt(d2), np.sqrt(max(4.0 - d2, 0.0))) * (180.0 / np.pi)
 
 
+def max_angle_deg_same_stage(centres, X, stage):
+    """A MUTANT of max_angle_deg, not a yardstick: only views of the same stage (an integer per view) are paired -- what a
+    kernel that staged the views in pieces and dropped the pairs across two pieces would report.  The tests use it to show
+    that their tracks tell the two apart."""
+    u = centres - X
+    u = u / np.sqrt((u * u).sum(axis=1))[:, None]
+    stage = np.asarray(stage)
+    d2 = 0.0
+    for s in np.unique(stage):
+        us = u[stage == s]
+        d = us[:, None, :] - us[None, :, :]
+        d2 = max(d2, float((d * d).sum(axis=2).max()))
+    return 2.0 * np.arctan2(np.sqrt(d2), np.sqrt(max(4.0 - d2, 0.0))) * (180.0 / np.pi)
+
+
 def measures_at(v, X, min_depth=0.0):
     """(angle_deg, rms_px, max_px, views behind) at X."""
     s = sums_at(v, X, "linear", 1.0, min_depth)
