@@ -48,6 +48,7 @@
 #include "ba_match_guided.hpp"
 #include "ba_match_l2.hpp"
 #include "ba_orb.hpp"
+#include "ba_klt.hpp"
 #include "ba_posegraph.hpp"
 #include "ba_sim3.hpp"
 #include "ba_fundamental.hpp"
@@ -376,13 +377,16 @@ struct ba_handle {
   DBuf<unsigned char> rn_cons, rn_inl;
   RansacArgs rn_args = {};
   // Device memory of the calls that need no problem and keep nothing on the device between calls: the pair-shaped RANSAC
-  // calls, matching, ORB, the pose graph, place recognition (but for the resident vocabulary) and track building
+  // calls, matching, ORB, KLT tracking, the pose graph, place recognition (but for the resident vocabulary) and track building
   Scratch scratch;
   int debug_match_splits = 0;  // BA_DEBUG_MATCH_SPLITS: train splits asked for per pair instead of match_plan's own choice (tests)
   PinnedStage orb_stage;                       // what the call reads back: cs | xy size angle response | octave level_xy | n_kp | desc
   bool orb_timing = false;                     // ba_orb_stage_times: events around the stages of ba_orb_extract
   hipEvent_t orb_ev[BA_ORB_STAGES + 1] = {};
   double orb_ms[BA_ORB_STAGES] = {};
+  bool klt_timing = false;                     // ba_klt_stage_times: events around the stages of ba_track_klt
+  hipEvent_t klt_ev[BA_KLT_STAGES + 1] = {};
+  double klt_ms[BA_KLT_STAGES] = {};
   // ba_transform / ba_align / ba_get_centres (ba_similarity.hpp): correspondences a | b | w | u | err (9 doubles each), the
   // per-workgroup partial rows, the device record (similarity, centroids, status)
   DBuf<double> sim_buf, sim_part;
@@ -586,6 +590,7 @@ extern "C" int ba_destroy(ba_handle* h) {
   shm_destroy(h);
   for (auto e : h->ev) (void)hipEventDestroy(e);
   for (auto e : h->orb_ev) if (e) (void)hipEventDestroy(e);
+  for (auto e : h->klt_ev) if (e) (void)hipEventDestroy(e);
   if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;                    // every buffer the handle owns goes with it
@@ -4478,6 +4483,160 @@ extern "C" int ba_orb_extract(ba_handle* h, int32_t n_images, int32_t height, in
     if (level_xy) memcpy(level_xy + 2 * r, hi + B * N + 2 * r, 2 * n * sizeof(int32_t));
     if (cs) memcpy(cs + 2 * r, hc + 2 * r, 2 * n * sizeof(double));
     if (desc) memcpy(desc + 32 * r, hd + 32 * r, 32 * n);
+  }
+  return BA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- KLT tracking
+// ba_track_klt (csrc/ba_klt.hpp): pyramidal Lucas-Kanade.  Needs no problem; its device memory is the scratch arena's.
+static_assert(sizeof(ba_klt_options) == 40, "ba_klt_options (include/ba_hip.h)");
+static_assert(BA_KLT_OK == KLT_OK && BA_KLT_OUT == KLT_OUT && BA_KLT_FLAT == KLT_FLAT && BA_KLT_FB_FAIL == KLT_FB_FAIL, "device status codes (ba_klt.hpp)");
+constexpr int KLT_MAX_PAIRS = 65535;
+constexpr long long KLT_MAX_POINTS = 1LL << 24;
+extern "C" int ba_default_klt_options(ba_klt_options* o) {
+  if (!o) return fail(BA_ERR_INVALID, "null argument");
+  memset(o, 0, sizeof *o);
+  o->half_window = 10;
+  o->max_level = 3;
+  o->max_iters = 30;
+  o->eps = 0.01;
+  o->min_eig = 1e-4;
+  o->fb_max_px = 0.0;
+  return BA_OK;
+}
+static int klt_check_options(const char* who, const ba_klt_options* o, int32_t height, int32_t width) {
+  if (o->half_window < 1 || o->half_window > KLT_MAX_HALF) return fail(BA_ERR_INVALID, "%s: half_window %d is outside 1 .. %d", who, o->half_window, KLT_MAX_HALF);
+  if (o->max_level < 0 || o->max_level > KLT_MAX_LEVELS - 1) return fail(BA_ERR_INVALID, "%s: max_level %d is outside 0 .. %d", who, o->max_level, KLT_MAX_LEVELS - 1);
+  if (o->max_iters < 1 || o->max_iters > 100) return fail(BA_ERR_INVALID, "%s: max_iters %d is outside 1 .. 100", who, o->max_iters);
+  if (!(o->eps >= 0.0)) return fail(BA_ERR_INVALID, "%s: eps is negative or NaN", who);
+  if (!(o->min_eig >= 0.0)) return fail(BA_ERR_INVALID, "%s: min_eig is negative or NaN", who);
+  if (o->fb_max_px != o->fb_max_px) return fail(BA_ERR_INVALID, "%s: fb_max_px is NaN", who);
+  if (height <= 0) return fail(BA_ERR_INVALID, "%s: height %d is not positive", who, height);
+  if (width <= 0) return fail(BA_ERR_INVALID, "%s: width %d is not positive", who, width);
+  const int n = 2 * o->half_window + 1;
+  if (std::min(height, width) < n) return fail(BA_ERR_INVALID, "%s: the image, width %d x height %d, is smaller than the %d x %d window", who, width, height, n, n);
+  return BA_OK;
+}
+// The definition's levels (include/ba_hip.h) -> the number of levels, L + 1
+static int klt_levels(const ba_klt_options* o, int32_t height, int32_t width, int32_t* lw, int32_t* lh) {
+  const int n = 2 * o->half_window + 1;
+  int l = 0;
+  lw[0] = width; lh[0] = height;
+  while (l < o->max_level && std::min((lw[l] + 1) / 2, (lh[l] + 1) / 2) >= n) {
+    lw[l + 1] = (lw[l] + 1) / 2; lh[l + 1] = (lh[l] + 1) / 2;
+    ++l;
+  }
+  return l + 1;
+}
+extern "C" int ba_klt_levels(const ba_klt_options* opts, int32_t height, int32_t width, int32_t* n_levels, int32_t* level_w, int32_t* level_h) {
+  if (!opts) return fail(BA_ERR_INVALID, "null argument");
+  if (int rc = klt_check_options("ba_klt_levels", opts, height, width)) return rc;
+  int32_t lw[KLT_MAX_LEVELS], lh[KLT_MAX_LEVELS];
+  const int nl = klt_levels(opts, height, width, lw, lh);
+  if (n_levels) *n_levels = nl;
+  if (level_w) memcpy(level_w, lw, (size_t)nl * sizeof(int32_t));
+  if (level_h) memcpy(level_h, lh, (size_t)nl * sizeof(int32_t));
+  return BA_OK;
+}
+extern "C" int ba_klt_stage_times(ba_handle* h, int32_t enable, double* ms) {
+  if (!h) return fail(BA_ERR_INVALID, "null handle");
+  if (enable < -1 || enable > 1) return fail(BA_ERR_INVALID, "ba_klt_stage_times: enable %d is not -1, 0 or 1", enable);
+  if (set_device(h)) return BA_ERR_HIP;
+  if (enable == 1)
+    for (auto& e : h->klt_ev)
+      if (!e) HIPCHECK(hipEventCreate(&e));
+  if (enable >= 0) h->klt_timing = enable != 0;
+  if (ms) memcpy(ms, h->klt_ms, sizeof h->klt_ms);
+  return BA_OK;
+}
+extern "C" int ba_track_klt(ba_handle* h, int32_t n_images, int32_t height, int32_t width, const uint8_t* images, int32_t n_pairs,
+                            const int32_t* pairs, const int64_t* pt_off, const float* prev, const float* guess, const ba_klt_options* opts,
+                            float* next, uint8_t* status, float* err, float* fb_err) {
+  if (!h || !opts) return fail(BA_ERR_INVALID, "null argument");
+  if (int rc = klt_check_options("ba_track_klt", opts, height, width)) return rc;
+  if (n_images < 0 || n_images > ORB_MAX_IMAGES) return fail(BA_ERR_INVALID, "ba_track_klt: n_images %d is outside 0 .. %d", n_images, ORB_MAX_IMAGES);
+  const long long px = (long long)height * width;
+  if (px > ORB_MAX_PIXELS) return fail(BA_ERR_INVALID, "ba_track_klt: height * width = %lld is above the cap of %lld pixels", px, ORB_MAX_PIXELS);
+  if (px * n_images > ORB_MAX_BATCH_PIXELS)
+    return fail(BA_ERR_INVALID, "ba_track_klt: the batch n_images * height * width = %lld is above the cap of %lld pixels", px * n_images, ORB_MAX_BATCH_PIXELS);
+  if (n_pairs < 0 || n_pairs > KLT_MAX_PAIRS) return fail(BA_ERR_INVALID, "ba_track_klt: n_pairs %d is outside 0 .. %d", n_pairs, KLT_MAX_PAIRS);
+  if (n_pairs == 0) return BA_OK;
+  if (!pairs || !pt_off) return fail(BA_ERR_INVALID, "ba_track_klt: null pairs or pt_off");
+  if (pt_off[0] != 0) return fail(BA_ERR_INVALID, "ba_track_klt: pt_off[0] = %lld is not 0", (long long)pt_off[0]);
+  for (int p = 0; p < n_pairs; ++p) {
+    if (pt_off[p + 1] < pt_off[p]) return fail(BA_ERR_INVALID, "ba_track_klt: pt_off decreases at pair %d", p);
+    if (pt_off[p + 1] > KLT_MAX_POINTS) return fail(BA_ERR_INVALID, "ba_track_klt: more than %lld points (pt_off[%d] = %lld)", KLT_MAX_POINTS, p + 1, (long long)pt_off[p + 1]);
+    for (int k = 0; k < 2; ++k)
+      if (pairs[2 * p + k] < 0 || pairs[2 * p + k] >= n_images)
+        return fail(BA_ERR_INVALID, "ba_track_klt: pairs[%d][%d] = %d is no image index (n_images %d)", p, k, pairs[2 * p + k], n_images);
+  }
+  const size_t N = (size_t)pt_off[n_pairs];
+  if (N == 0) return BA_OK;
+  if (!images) return fail(BA_ERR_INVALID, "ba_track_klt: null images");
+  if (!prev) return fail(BA_ERR_INVALID, "ba_track_klt: null prev");
+  // a slot for every image that a pair with points names
+  std::vector<int> slot((size_t)n_images, -1), slots(2 * (size_t)n_pairs, 0);
+  for (int p = 0; p < n_pairs; ++p)
+    if (pt_off[p + 1] > pt_off[p]) slot[pairs[2 * p]] = slot[pairs[2 * p + 1]] = 0;
+  int S = 0;
+  for (int b = 0; b < n_images; ++b)
+    if (slot[b] == 0) slot[b] = S++;
+  for (int p = 0; p < n_pairs; ++p)
+    for (int k = 0; k < 2; ++k) slots[2 * p + k] = std::max(slot[pairs[2 * p + k]], 0);
+  KltArgs a = {};
+  int32_t lw[KLT_MAX_LEVELS], lh[KLT_MAX_LEVELS];
+  a.n_levels = klt_levels(opts, height, width, lw, lh);
+  a.hw = opts->half_window; a.n = 2 * a.hw + 1; a.max_iters = opts->max_iters; a.fb = opts->fb_max_px > 0.0; a.n_pairs = n_pairs;
+  a.eps2 = opts->eps * opts->eps; a.min_eig = opts->min_eig; a.fb_max = opts->fb_max_px;
+  long long pix = 0;
+  for (int l = 0; l < a.n_levels; ++l) {
+    a.w[l] = lw[l]; a.h[l] = lh[l];
+    a.off[l] = pix; pix += (long long)S * lw[l] * lh[l];
+  }
+  if (set_device(h)) return BA_ERR_HIP;
+  Scratch& sc = h->scratch;
+  HIPCHECK(sc.begin(h->stream));
+  HIPCHECK(sc.take((size_t)pix, &a.pyr));
+  int stamp = 0;
+#define KLT_STAMP() do { if (h->klt_timing) HIPCHECK(hipEventRecord(h->klt_ev[stamp++], h->stream)); } while (0)
+  KLT_STAMP();
+  HIPCHECK(sc.put(h->stream, 2 * (size_t)n_pairs, slots.data(), &a.pair_slot));
+  HIPCHECK(sc.put(h->stream, (size_t)n_pairs + 1, pt_off, &a.pt_off));
+  HIPCHECK(sc.put(h->stream, 2 * N, prev, &a.prev));
+  if (guess) HIPCHECK(sc.put(h->stream, 2 * N, guess, &a.guess));
+  HIPCHECK(sc.take(2 * N, &a.next)); HIPCHECK(sc.take(N, &a.err, &a.fb_err)); HIPCHECK(sc.take(N, &a.status));
+  for (int b = 0; b < n_images;) {      // level 0 of the slots: the used images, a copy per run of consecutive ones
+    if (slot[b] < 0) { ++b; continue; }
+    int e = b + 1;
+    while (e < n_images && slot[e] >= 0) ++e;
+    HIPCHECK(hipMemcpyAsync(a.pyr + (size_t)slot[b] * (size_t)px, images + (size_t)b * (size_t)px, (size_t)(e - b) * (size_t)px, hipMemcpyHostToDevice, h->stream));
+    b = e;
+  }
+  KLT_STAMP();
+  for (int l = 1; l < a.n_levels; ++l)
+    BA_LAUNCH(k_klt_down, dim3((unsigned)((a.w[l] + KLT_TILE_W - 1) / KLT_TILE_W), (unsigned)((a.h[l] + KLT_TILE_H - 1) / KLT_TILE_H), (unsigned)S),
+              dim3(KLT_THREADS), 0, h->stream, a, l);
+  KLT_STAMP();
+  // the window's elements per lane, ceil(n^2 / 64), rounded up to an instantiation
+  const int epl = (a.n * a.n + 63) / 64;
+  const dim3 grid((unsigned)N), block(64);
+  if (epl <= 2) BA_LAUNCH(k_klt_track<2>, grid, block, 0, h->stream, a);
+  else if (epl <= 4) BA_LAUNCH(k_klt_track<4>, grid, block, 0, h->stream, a);
+  else if (epl <= 7) BA_LAUNCH(k_klt_track<7>, grid, block, 0, h->stream, a);
+  else BA_LAUNCH(k_klt_track<16>, grid, block, 0, h->stream, a);
+  static_assert((2 * KLT_MAX_HALF + 1) * (2 * KLT_MAX_HALF + 1) <= 16 * 64, "k_klt_track<16> holds the largest window");
+  KLT_STAMP();
+  if (next) HIPCHECK(hipMemcpyAsync(next, a.next, 2 * N * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (status) HIPCHECK(hipMemcpyAsync(status, a.status, N, hipMemcpyDeviceToHost, h->stream));
+  if (err) HIPCHECK(hipMemcpyAsync(err, a.err, N * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (fb_err) HIPCHECK(hipMemcpyAsync(fb_err, a.fb_err, N * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  KLT_STAMP();
+#undef KLT_STAMP
+  BA_SYNC(h);
+  for (int k = 0; k + 1 < stamp; ++k) {
+    float ms = 0;
+    HIPCHECK(hipEventElapsedTime(&ms, h->klt_ev[k], h->klt_ev[k + 1]));
+    h->klt_ms[k] = ms;
   }
   return BA_OK;
 }

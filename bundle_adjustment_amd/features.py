@@ -15,6 +15,9 @@ neighbours, ties to the lower train index, the ratio test in fp64).  The match o
 RootSIFT as COLMAP stores them, 128 uint8 per keypoint; ``quantize_descriptors`` takes float descriptors there).
 Once geometry is known, ``match_epipolar`` and ``match_by_projection`` match a second time under it (``ba_match_guided``: the
 same 2-NN over the keypoints an epipolar line or a search window admits; no counterpart in the reference).
+``track``, ``calc_optical_flow_pyr_lk`` (the shapes of ``cv2.calcOpticalFlowPyrLK``) and ``refine_matches`` follow known points
+from one image into another by pyramidal Lucas-Kanade (``ba_track_klt``): the per-frame step between keyframes, and the
+sub-pixel refinement of an ORB match.  Lucas-Kanade by the library's definition, not cv2's numbers.
 No CPU fallback: without the library / a GPU the call raises.
 """
 from __future__ import annotations
@@ -296,6 +299,66 @@ def extract(images, solver=None, pattern=None, **opts):
     finally:
         if own:
             s.close()
+
+
+def _track_pair(img1, img2, pts, guess, solver, opts):
+    """``hip_backend.Solver.track_klt`` of one image pair (colour images through ``to_gray``) -> its dict."""
+    a, b = to_gray(img1), to_gray(img2)
+    if a.shape != b.shape:
+        raise ValueError(f"the two images must have one size, not {a.shape} and {b.shape}")
+    p = np.asarray(pts, dtype=np.float32).reshape(-1, 2)
+    g = None if guess is None else [np.asarray(guess, dtype=np.float32).reshape(-1, 2)]
+    own = solver is None
+    s = hip_backend.Solver(0) if own else solver
+    try:
+        return s.track_klt(np.stack([a, b]), [(0, 1)], [p], guess=g, **opts)
+    finally:
+        if own:
+            s.close()
+
+
+def track(img1, img2, pts, guess=None, solver=None, **opts):
+    """Follows the points ``pts`` (n, 2), pixels of ``img1``, into ``img2`` by pyramidal Lucas-Kanade (``ba_track_klt``) ->
+    (next (n, 2) float32, ok (n,) bool, err (n,) float32): ok where the status is OK, err the mean absolute intensity difference
+    of the window there (NaN elsewhere).  ``guess``: the starts in ``img2`` (default: ``pts``).  opts: half_window, max_level,
+    max_iters, eps, min_eig, fb_max_px (> 0: forward-backward check).  Lucas-Kanade by the library's definition, not cv2's
+    output.  ``solver``: a ``hip_backend.Solver`` to run on (its resident problem is not touched); default: one on device 0."""
+    out = _track_pair(img1, img2, pts, guess, solver, opts)
+    return out["next"], out["status"] == hip_backend.KLT_STATUS["ok"], out["err"]
+
+
+def calc_optical_flow_pyr_lk(prev_img, next_img, prev_pts, next_pts=None, win_size=(21, 21), max_level=3, criteria=(30, 0.01),
+                             min_eig_threshold=1e-4, solver=None):
+    """Drop-in with the shapes of ``cv2.calcOpticalFlowPyrLK``: ``prev_pts`` (n, 1, 2) (or (n, 2)) float32, ``next_pts`` the
+    initial guesses or None -> (next_pts (n, 1, 2) float32, status (n, 1) uint8 with 1 = found, err (n, 1) float32).
+    ``criteria`` = (max iterations, epsilon).  A square window of odd size only; any other raises ValueError.  Not cv2's numbers
+    (``track``)."""
+    if len(win_size) != 2 or win_size[0] != win_size[1] or int(win_size[0]) != win_size[0] or int(win_size[0]) % 2 != 1:
+        raise ValueError(f"win_size must be square and odd, not {tuple(win_size)}")
+    out = _track_pair(prev_img, next_img, prev_pts, next_pts, solver,
+                      dict(half_window=(int(win_size[0]) - 1) // 2, max_level=int(max_level), max_iters=int(criteria[0]), eps=float(criteria[1]),
+                           min_eig=float(min_eig_threshold)))
+    n = len(out["status"])
+    found = (out["status"] == hip_backend.KLT_STATUS["ok"]).astype(np.uint8)
+    return out["next"].reshape(n, 1, 2), found.reshape(n, 1), out["err"].reshape(n, 1)
+
+
+def refine_matches(img1, kp1, img2, kp2, q, t, max_shift_px=2.0, solver=None, **opts):
+    """Subpixel positions for the matches (q[k], t[k]) of keypoints ``kp1`` of ``img1`` and ``kp2`` of ``img2``: ``kp1[q]`` is tracked
+    into ``img2`` from ``kp2[t]`` (``ba_track_klt`` with ``guess``) -> (xy2 (m, 2) float32, keep (m,) bool).  A match is kept when the
+    status is OK and the refined point lies within ``max_shift_px`` of ``kp2[t]``; xy2 of a match that is not kept is ``kp2[t]``.
+    ``kp*``: (n, 2) arrays or sequences of objects with ``.pt``.  xy2[keep] is the ``uv`` of the second image for ``to_problem`` /
+    ``ba_set_problem``."""
+    k1, k2 = _positions(kp1), _positions(kp2)
+    q, t = np.asarray(q, dtype=np.int64).reshape(-1), np.asarray(t, dtype=np.int64).reshape(-1)
+    if len(q) != len(t):
+        raise ValueError("q and t must list the same number of matches")
+    start = k2[t].astype(np.float32)
+    out = _track_pair(img1, img2, k1[q], start, solver, opts)
+    moved = np.hypot(*(out["next"].astype(np.float64) - start.astype(np.float64)).T)
+    with np.errstate(invalid="ignore"):
+        keep = (out["status"] == hip_backend.KLT_STATUS["ok"]) & (moved <= max_shift_px)
+    return np.where(keep[:, None], out["next"], start), keep
 
 
 class ORBExtractor:

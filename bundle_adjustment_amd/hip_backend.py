@@ -145,6 +145,11 @@ class BAOrbOptions(C.Structure):
                 ("fast_threshold", C.c_int32)]
 
 
+class BAKltOptions(C.Structure):
+    _fields_ = [("half_window", C.c_int32), ("max_level", C.c_int32), ("max_iters", C.c_int32), ("reserved", C.c_int32),
+                ("eps", C.c_double), ("min_eig", C.c_double), ("fb_max_px", C.c_double)]
+
+
 class BAVocabOptions(C.Structure):
     _fields_ = [("branching", C.c_int32), ("levels", C.c_int32), ("iters", C.c_int32), ("min_split", C.c_int32), ("seed", C.c_uint64)]
 
@@ -193,6 +198,10 @@ def pg_chunk_len(deg):
 # ba_orb_extract (csrc/ba_orb.hpp): the tile of the FAST and blur kernels, the most levels, and the caps of a call
 ORB_TILE_W, ORB_TILE_H, ORB_MAX_LEVELS, ORB_MAX_FEATURES, ORB_MAX_IMAGES = 64, 16, 16, 65536, 1024
 ORB_STAGES = ("upload", "pyramid", "fast", "select", "harris_rank", "blur", "describe", "download")   # ba_orb_stage_times
+# ba_track_klt (csrc/ba_klt.hpp): the tile of the pyramid kernel, the most levels, the largest half_window, the caps of a call
+KLT_TILE_W, KLT_TILE_H, KLT_MAX_LEVELS, KLT_MAX_HALF, KLT_MAX_PAIRS, KLT_MAX_POINTS = 32, 8, 9, 15, 65535, 1 << 24
+KLT_STATUS = {"ok": 0, "out": 1, "flat": 2, "fb_fail": 3}   # enum ba_klt_status
+KLT_STAGES = ("upload", "pyramid", "track", "download")   # ba_klt_stage_times
 
 
 class BASimilarity(C.Structure):
@@ -309,6 +318,12 @@ SYMBOLS = {
                                  C.POINTER(BAOrbOptions), _IP, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                  C.POINTER(C.c_float), _IP, _IP, _DP, C.POINTER(C.c_uint8)]),
     "ba_orb_stage_times": (C.c_int, [C.c_void_p, C.c_int32, _DP]),
+    "ba_default_klt_options": (C.c_int, [C.POINTER(BAKltOptions)]),
+    "ba_klt_levels": (C.c_int, [C.POINTER(BAKltOptions), C.c_int32, C.c_int32, _IP, _IP, _IP]),
+    "ba_klt_stage_times": (C.c_int, [C.c_void_p, C.c_int32, _DP]),
+    "ba_track_klt": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_int32, _IP, C.POINTER(C.c_int64),
+                               C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(BAKltOptions), C.POINTER(C.c_float),
+                               C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ba_get_centres": (C.c_int, [C.c_void_p, _DP]),
     "ba_transform": (C.c_int, [C.c_void_p, C.POINTER(BASimilarity)]),
     "ba_default_align_options": (C.c_int, [C.POINTER(BAAlignOptions)]),
@@ -589,6 +604,19 @@ def orb_levels(height, width, **opts):
     _check(load_library().ba_orb_levels(C.byref(o), int(height), int(width), None if w is None else w.ctypes.data_as(_IP),
                                         None if h is None else h.ctypes.data_as(_IP), _dp(sc), None if q is None else q.ctypes.data_as(_IP)))
     return w, h, sc, q
+
+
+def klt_options(**kw) -> BAKltOptions:
+    """ba_default_klt_options overlaid with kw (any ba_klt_options field; an unknown one raises TypeError).  No GPU."""
+    return _options(BAKltOptions, load_library().ba_default_klt_options, kw, names={})
+
+
+def klt_levels(height, width, **opts):
+    """ba_klt_levels: (level_w, level_h) int32, one entry per pyramid level of ba_track_klt, the image first.  No GPU."""
+    o = klt_options(**opts)
+    w, h, n = np.zeros(KLT_MAX_LEVELS, dtype=np.int32), np.zeros(KLT_MAX_LEVELS, dtype=np.int32), C.c_int32(0)
+    _check(load_library().ba_klt_levels(C.byref(o), int(height), int(width), C.byref(n), w.ctypes.data_as(_IP), h.ctypes.data_as(_IP)))
+    return w[:n.value].copy(), h[:n.value].copy()
 
 
 def device_count():
@@ -1160,6 +1188,49 @@ class Solver:
         out["n_kp"] = n_kp
         out["kp_off"] = np.concatenate([[0], np.cumsum(n_kp, dtype=np.int64)]).astype(np.int64)
         return out
+
+    def track_klt(self, images, pairs, points, guess=None, **opts):
+        """ba_track_klt: pyramidal Lucas-Kanade tracking of points from image a into image b of every pair.  images: (n, H, W)
+        uint8 grey images of one size ((H, W): one image); pairs: (n_pairs, 2) image indices (a, b); points: one (n_p, 2) array
+        per pair, pixels (x, y) in image a; guess: None, or the starts in image b, shaped like points.  opts: half_window,
+        max_level, max_iters, eps, min_eig, fb_max_px.  Returns dict(pt_off (n_pairs + 1,) int64, next (N, 2) float32, status (N,)
+        uint8 (KLT_STATUS), err, fb_err (N,) float32, levels (level_w, level_h)): pair k owns rows pt_off[k] .. pt_off[k + 1] - 1.
+        Lucas-Kanade by the definition of include/ba_hip.h, not cv2's output.  Needs no problem and leaves a resident one as it is."""
+        imgs = np.asarray(images)
+        if imgs.dtype != np.uint8 or imgs.ndim not in (2, 3):
+            raise ValueError(f"images must be a uint8 array (H, W) or (n, H, W), not {imgs.dtype} with shape {imgs.shape}")
+        imgs = np.ascontiguousarray(imgs if imgs.ndim == 3 else imgs[None])
+        n, H, W = imgs.shape
+        pr = np.ascontiguousarray(_node_array(pairs, "pairs").reshape(-1, 2))
+        pts = [np.asarray(p, dtype=np.float32).reshape(-1, 2) for p in points]
+        if len(pts) != len(pr):
+            raise ValueError(f"{len(pts)} point arrays for {len(pr)} pairs")
+        pt_off = np.concatenate([[0], np.cumsum([len(p) for p in pts])]).astype(np.int64)
+        N = int(pt_off[-1])
+        prev = np.ascontiguousarray(np.concatenate(pts) if pts else np.zeros((0, 2)), dtype=np.float32)
+        g = None
+        if guess is not None:
+            gs = [np.asarray(q, dtype=np.float32).reshape(-1, 2) for q in guess]
+            if [len(q) for q in gs] != [len(p) for p in pts]:
+                raise ValueError("guess must hold one start per point")
+            g = np.ascontiguousarray(np.concatenate(gs) if gs else np.zeros((0, 2)), dtype=np.float32)
+        o = klt_options(**opts)
+        out = dict(pt_off=pt_off, next=np.zeros((N, 2), np.float32), status=np.zeros(N, np.uint8), err=np.full(N, np.nan, np.float32),
+                   fb_err=np.full(N, np.nan, np.float32))
+        fp, bp = C.POINTER(C.c_float), C.POINTER(C.c_uint8)
+        _check(self._lib.ba_track_klt(self._h, n, H, W, imgs.ctypes.data_as(bp), len(pr), pr.ctypes.data_as(_IP),
+                                      pt_off.ctypes.data_as(C.POINTER(C.c_int64)), prev.ctypes.data_as(fp),
+                                      None if g is None else g.ctypes.data_as(fp), C.byref(o), out["next"].ctypes.data_as(fp),
+                                      out["status"].ctypes.data_as(bp), out["err"].ctypes.data_as(fp), out["fb_err"].ctypes.data_as(fp)))
+        out["levels"] = klt_levels(H, W, **opts)
+        return out
+
+    def klt_stage_times(self, enable=None):
+        """ba_klt_stage_times: enable=True / False switches the stage events of track_klt on / off (None: as it is); returns the
+        stage times of the last timed call in milliseconds, a dict keyed by KLT_STAGES."""
+        ms = np.zeros(len(KLT_STAGES))
+        _check(self._lib.ba_klt_stage_times(self._h, -1 if enable is None else int(bool(enable)), _dp(ms)))
+        return dict(zip(KLT_STAGES, ms.tolist()))
 
     def orb_stage_times(self, enable=None):
         """ba_orb_stage_times: enable=True / False switches the stage events of extract_orb on / off (None: as it is); returns

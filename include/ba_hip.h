@@ -785,6 +785,79 @@ int ba_orb_extract(ba_handle* h, int32_t n_images, int32_t height, int32_t width
  * download.  Results do not depend on it. */
 enum { BA_ORB_STAGES = 8 };
 int ba_orb_stage_times(ba_handle* h, int32_t enable, double* ms);
+/* Pyramidal Lucas-Kanade (KLT) point tracking: known points of image a are followed into image b without detecting or matching
+ * anything -- what a visual-odometry front end does between keyframes (cv2.calcOpticalFlowPyrLK, VINS, SVO, OpenVINS; no
+ * reference counterpart: its pipeline extracts and matches every frame), and, started at a matched keypoint (`guess`), the
+ * refinement of an ORB match to a fraction of a pixel.  The results feed pts1 / pts2 of ba_relative_pose, ba_homography and
+ * ba_fundamental, edge_a / edge_b of ba_build_tracks and uv of ba_set_problem.  This is LUCAS-KANADE BY THE DEFINITION BELOW, NOT
+ * cv2's output; the defaults are cv2's (21 x 21 window, maxLevel 3, criteria (30, 0.01), minEigThreshold 1e-4) and one rule
+ * differs on purpose: a point must lie INSIDE the image, 0 <= x <= w - 1, at every level it is iterated on, where cv2 lets the
+ * window's corner leave the image by a window.  Sums are integers; everything else is fp64 with every operation rounded on its
+ * own, so the definition decides every case.  Needs no problem; a resident problem is not touched; device memory is the scratch
+ * arena's.
+ * images uint8[n_images][height][width], row-major and contiguous, one common size.  Pair k = (image a, image b) = pairs[k] owns
+ * the points pt_off[k] .. pt_off[k + 1] - 1; prev float32[.][2] are pixels (x, y) of image a, guess (or NULL: prev) the starts in
+ * image b.  Outputs (any may be NULL): next float32[.][2], status uint8[.] (ba_klt_status), err float32[.], fb_err float32[.].
+ * LEVELS (ba_klt_levels): n = 2 half_window + 1; w_0 = W, h_0 = H; level l + 1 exists while l < max_level and min((w_l + 1) / 2,
+ *   (h_l + 1) / 2) >= n (integer division) and has that size; L is the top level.
+ * PYRAMID, once for every image a pair with points names: P_(l+1)(x, y) = (sum over i, j = -2 .. 2 of g_i g_j P_l(r(2x + j),
+ *   r(2y + i)) + 128) >> 8, g = 1 4 6 4 1; r reflects without repeating the border: -1 -> 1, -2 -> 2, n -> n - 2, n + 1 -> n - 3.
+ * GRADIENTS of a level, integer Scharr, not normalised: Ix = 3 (P(x+1,y-1) - P(x-1,y-1)) + 10 (P(x+1,y) - P(x-1,y)) + 3 (P(x+1,y+1)
+ *   - P(x-1,y+1)), Iy its transpose; coordinates clamped to the image.
+ * WINDOW SAMPLE S(A, c, shift) of a level array A (P, Ix or Iy) at the top-left corner c (fp64): ix = floor(c.x), a = c.x - ix, rows
+ *   likewise iy, b; w00 = rint((1 - a) * (1 - b) * 16384), w01 = rint(a * (1 - b) * 16384), w10 = rint((1 - a) * b * 16384), w11 =
+ *   16384 - w00 - w01 - w10 (rint half to even, every product rounded); element (i, j), i, j = 0 .. n - 1, is (w00 A(ix+j, iy+i) +
+ *   w01 A(ix+j+1, iy+i) + w10 A(ix+j, iy+i+1) + w11 A(ix+j+1, iy+i+1) + (1 << (shift - 1))) >> shift, an arithmetic shift, every
+ *   coordinate clamped to the image.
+ * PER POINT: p = prev widened to fp64.  !(0 <= p.x && p.x <= W - 1 && 0 <= p.y && p.y <= H - 1) (so a NaN too) is OUT with
+ *   next = prev.  q = (guess or p) / 2^L.  For l = L .. 0:
+ *   1. c = p / 2^l - half_window; T = S(P_a, c, 9) (the intensity times 32), Gx = S(Ix_a, c, 14), Gy = S(Iy_a, c, 14); A11 = sum Gx^2,
+ *      A12 = sum Gx Gy, A22 = sum Gy^2 exact in int64, then fp64; D = A11 * A22 - A12 * A12; e = (A11 + A22 - sqrt((A11 - A22) *
+ *      (A11 - A22) + 4 * (A12 * A12))) / (2 * n * n) / 1048576.  If !(D > 0) or e < min_eig: at l = 0 the status is FLAT with next =
+ *      (float)q; at l > 0 the level is skipped, q <- 2 q.
+ *   2. For it = 0 .. max_iters - 1: if q is not inside [0, w_l - 1] x [0, h_l - 1] the level ends, at l = 0 with status OUT;
+ *      d = S(P_b, q - half_window, 9) - T; b1 = sum d Gx, b2 = sum d Gy exact in int64; delta = ((A12 * b2 - A22 * b1) / D,
+ *      (A12 * b1 - A11 * b2) / D); q <- q + delta; stop if delta.x^2 + delta.y^2 <= eps^2; if it > 0, |delta.x + prevdelta.x| < 0.01
+ *      and |delta.y + prevdelta.y| < 0.01 (an oscillation): q <- q - 0.5 delta and stop.
+ *   3. At l > 0: q <- 2 q.
+ *   At the end, status still OK: q outside the level-0 image is OUT; otherwise err = (float)(sum |S(P_b, q - half_window, 9) - T| /
+ *   (32.0 * n * n)), T of level 0.  next = (float)q for every status but an OUT start.  err is NaN unless the status is OK or
+ *   FB_FAIL.
+ * FORWARD-BACKWARD CHECK (fb_max_px > 0): every OK point is tracked back from image b to image a from (double)next with no guess
+ *   -- exactly what a second call with the roles swapped returns; fb_err = (float)sqrt(dx^2 + dy^2) of that result against prev;
+ *   the status becomes FB_FAIL when the backward status is not OK or the fp64 distance exceeds fb_max_px.  fb_err is NaN where
+ *   the backward pass did not run or did not end OK.
+ * n_pairs = 0 or no points is a no-op.  Two calls give bit-equal outputs.
+ * BA_ERR_INVALID, naming the field: half_window outside 1 .. 15, max_level outside 0 .. 8, max_iters outside 1 .. 100, eps or
+ * min_eig negative or NaN, fb_max_px NaN; height or width not positive or min(W, H) < n; n_images outside 0 .. 1024, height *
+ * width > 2^26 or n_images * height * width > 2^28 (ORB's caps); n_pairs outside 0 .. 65535; pt_off[0] != 0 or a decreasing
+ * pt_off; more than 2^24 points; an image index out of range; images or prev NULL when there are points.  A refused call leaves
+ * the handle usable.
+ * Not offered: affine or illumination-compensating LK, rectangular windows, OPTFLOW_LK_GET_MIN_EIGENVALS as the error measure,
+ * detection of new corners to track (ORB's keypoints are the corners), images of different sizes in one call, more than one
+ * rank, a helper that turns tracks over a sequence into ba_build_tracks edges. */
+typedef struct ba_klt_options {
+  int32_t half_window;     /* 1 .. 15: the window is n x n, n = 2 half_window + 1; default 10 */
+  int32_t max_level;       /* 0 .. 8: the most pyramid levels above the image; default 3 */
+  int32_t max_iters;       /* 1 .. 100 iterations per level; default 30 */
+  int32_t reserved;        /* 0 */
+  double  eps;             /* >= 0: an iteration that moves by at most eps ends the level; default 0.01 */
+  double  min_eig;         /* >= 0: the smallest normalised eigenvalue a level is tracked on; default 1e-4 */
+  double  fb_max_px;       /* > 0: forward-backward check with this bound in pixels; default 0 (off) */
+} ba_klt_options;          /* 40 bytes */
+enum ba_klt_status { BA_KLT_OK = 0, BA_KLT_OUT = 1, BA_KLT_FLAT = 2, BA_KLT_FB_FAIL = 3 };
+int ba_default_klt_options(ba_klt_options* opts);    /* 10, 3, 30, 0.01, 1e-4, 0 */
+/* The levels of the definition above: n_levels = L + 1 and that many sizes; any output may be NULL (level_w, level_h: room for
+ * 9).  Checks every option as ba_track_klt does.  Host only. */
+int ba_klt_levels(const ba_klt_options* opts, int32_t height, int32_t width, int32_t* n_levels, int32_t* level_w, int32_t* level_h);
+int ba_track_klt(ba_handle* h, int32_t n_images, int32_t height, int32_t width, const uint8_t* images, int32_t n_pairs,
+                 const int32_t* pairs, const int64_t* pt_off, const float* prev, const float* guess, const ba_klt_options* opts,
+                 float* next, uint8_t* status, float* err, float* fb_err);
+/* Measurement hook, as ba_orb_stage_times: enable = 1 makes every later ba_track_klt on the handle record events around its
+ * stages on the stream, 0 stops that, -1 leaves the switch as it is; ms (may be NULL) receives the BA_KLT_STAGES stage times of the
+ * last timed call that reached the device, in milliseconds: upload, pyramid, tracking, download.  Results do not depend on it. */
+enum { BA_KLT_STAGES = 4 };
+int ba_klt_stage_times(ba_handle* h, int32_t enable, double* ms);
 /* Similarity transform of the reconstruction and robust alignment to reference positions: the step after an adjustment that
  * moves the result into the frame its user needs (georegistration onto GPS / surveyed camera positions or ground-control
  * points -- COLMAP's model_aligner; the comparison of two gauge-free solves; re-centring / re-scaling).  No reference
